@@ -290,7 +290,7 @@ def build_device(ctx, cfg, dev):
     w = th.tensor([1.0, 0.5, -0.3][:cfg["P"]])
     w = w / w.sum().abs()
     H, W = cfg["hw"]
-    x0_star = th.tanh(th.randn(1, 3, H, W, device=dev))
+    x0_star = th.tanh(th.randn(1, 3, H, W, generator=g)).to(dev)  # seeded: the device's default generator starts from a random seed
     lp = None
     if cfg["lpips"]:
         lp = nets.LpipsVGG(ctx).load_state_dict(synthetic.lpips_state_dict(device=dev))
@@ -309,8 +309,12 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true", help="skip the untimed HIP-event pass (roofline / hbm objects)")
     ap.add_argument("--profile-steps", type=int, default=20)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step yielded (the sampling "
+                                                           "loop's `sample` and `pred_xstart`, rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline()), flush=True)
         return
@@ -414,6 +418,15 @@ def main():
     n1 = launch_counts()  # kernel launches of the library over the K timed steps (torch's own few elementwise / RNG launches not included)
     finite = bool(th.isfinite(out["sample"]).all().item())
     peak = float(out["sample"].abs().max().item())
+    if args.dump_outputs and rank == 0:
+        # every input is seeded (weights, targets and x0* in build_device, the loop's draws by th.manual_seed above), so the dumps of two
+        # runs, or of two builds, compare element for element
+        import numpy as np
+        arrays = {name: t.detach().float().cpu().numpy() for name, t in out.items()}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), a)
     # host cost of ONE step in isolation (untimed, after the timed region): the queue is empty and the 4-slot upload ring is free, so the
     # call returns as soon as the step is enqueued — wall time and main-thread CPU time of the enqueue, without any waiting on the GPU
     # (inside the timed loop the host is held back by that ring: it may run at most 4 steps ahead of the GPU)

@@ -121,11 +121,17 @@ def main():
         pass
     finally:
         argparse.ArgumentParser.parse_args = orig
-    meta["cli_flags"] = flags
+    # the reference expands `~` at import (script_util.CACHE_PATH): its home-relative defaults are stored as `~/...`, the tests expand them
+    home = os.path.join(os.path.expanduser("~"), "")
+
+    def unexpand(s):
+        return s.replace(home, "~/") if isinstance(s, str) else s
+
+    meta["cli_flags"] = [dict(f, default=unexpand(f["default"])) for f in flags]
     # signature of the generator
     import inspect
     sig = inspect.signature(ref_cgd.clip_guided_diffusion)
-    meta["generator_signature"] = [[k, repr(p.default)] for k, p in sig.parameters.items()]
+    meta["generator_signature"] = [[k, unexpand(repr(p.default))] for k, p in sig.parameters.items()]
     # per-checkpoint UNet flags (data/diffusion_model_flags.py): they fix every layer shape of the supported models
     lookup = importlib.import_module("data.diffusion_model_flags").DIFFUSION_LOOKUP
     meta["diffusion_lookup"] = {cond: {str(size): entry for size, entry in table.items()} for cond, table in lookup.items()}

@@ -2,8 +2,10 @@
 
 Hot path: `CLIP_NORMALIZE` (:45, fused into the cutout kernel on the native path) and `load_clip(...)` whose
 `.encode_image` / `.visual.input_resolution` (:59-66) are served by the MI355X image tower.  Prompt encoding
-(`encode_text_prompt`, :104-108) is one-off setup that stays in PyTorch through the optional `clip` package
-(out of scope for kernels); without it only synthetic-weight runs are possible.
+(`encode_text_prompt`, :104-108) is one-off setup: with the optional `clip` package installed it runs there, unchanged; without it a
+checkpoint's text weights go to the native text tower (`cgd_amd.nets.ClipTextTower`) and prompts are tokenised by `cgd_amd.tokenizer`
+(merges file: $CGD_CLIP_BPE or <cache>/clip/bpe_simple_vocab_16e6.txt.gz).  Synthetic-weight runs without text weights keep the
+hash-seeded prompt embeddings.
 """
 import hashlib
 import os
@@ -14,6 +16,7 @@ import torch as th
 from cgd_amd import nets as _nets
 from cgd_amd import shard as _shard
 from cgd_amd import synthetic as _synthetic
+from cgd_amd import tokenizer as _tokenizer
 from cgd_amd.guidance import CLIP_MEAN, CLIP_STD, MakeCutouts  # noqa: F401
 
 from . import script_util
@@ -68,8 +71,8 @@ _EncodeImageFunction = _nets.EncodeImageFunction  # autograd node over cgd_*_for
 
 
 class ClipModel:
-    """The slice of clip.model.CLIP the generator touches: `.visual.input_resolution`, `.encode_image`, and (when the
-    `clip` package + checkpoint are present) `.encode_text`."""
+    """The slice of clip.model.CLIP the generator touches: `.visual.input_resolution`, `.encode_image`, and (when a checkpoint with text
+    weights is loaded) `.encode_text` — the `clip` package's text model when it is installed, else the native text tower."""
 
     def __init__(self, tower, text_model=None, name="ViT-B/32"):
         self.visual = _Visual(tower)
@@ -86,8 +89,12 @@ class ClipModel:
 
     def encode_text(self, tokens):
         if self.text_model is None:
-            raise RuntimeError("text encoding needs the `clip` package and a CLIP checkpoint (setup-time, stays in PyTorch)")
+            raise RuntimeError("text encoding needs a CLIP checkpoint with text weights (the native text tower, or the `clip` package)")
         return self.text_model.encode_text(tokens)
+
+    @property
+    def native_text(self):
+        return isinstance(self.text_model, _nets.ClipTextTower)
 
     def eval(self):
         return self
@@ -100,6 +107,26 @@ def _vit_config_from_state_dict(sd):
     patch = sd["visual.conv1.weight"].shape[-1]
     grid = round((sd["visual.positional_embedding"].shape[0] - 1) ** 0.5)
     return (patch * grid, patch, width, layers, width // 64, sd["visual.proj"].shape[1])
+
+
+def _text_config_from_state_dict(sd):
+    """clip.model.build_model's shape inference for the text tower: (context_length, vocab_size, width, layers, heads, out_dim)."""
+    width = sd["ln_final.weight"].shape[0]
+    layers = len({k.split(".")[2] for k in sd if k.startswith("transformer.resblocks.")})
+    return (sd["positional_embedding"].shape[0], sd["token_embedding.weight"].shape[0], width, layers, width // 64,
+            sd["text_projection"].shape[1])
+
+
+def _is_text_key(k):
+    return k.startswith(("token_embedding.", "transformer.", "ln_final.")) or k in ("positional_embedding", "text_projection")
+
+
+def _clip_importable():
+    try:
+        import clip  # noqa: F401  (optional, setup-time only)
+    except ImportError:
+        return False
+    return True
 
 
 def _rn_config_from_state_dict(sd):
@@ -120,26 +147,31 @@ def load_clip(model_name="ViT-B/32", device="cpu"):
     model_path = download_clip_model(model_name) if model_name in CLIP_MODEL_URLS else model_name
     if os.path.isfile(model_path):
         held = {}
+        have_clip = _clip_importable()
 
-        def probe():  # rank 0 only (multi-GPU runs): un-pickle the archive once, infer the tower like clip.model.build_model
+        def probe():  # rank 0 only (multi-GPU runs): un-pickle the archive once, infer the tower(s) like clip.model.build_model
             try:
                 sd = th.jit.load(model_path, map_location="cpu").state_dict()
             except RuntimeError:
                 sd = th.load(model_path, map_location="cpu")
             held["sd"] = sd
-            return ("vit", _vit_config_from_state_dict(sd)) if "visual.proj" in sd else ("rn", _rn_config_from_state_dict(sd))
+            text_cfg = _text_config_from_state_dict(sd) if (not have_clip and "text_projection" in sd) else None
+            if "visual.proj" in sd:
+                return "vit", _vit_config_from_state_dict(sd), text_cfg
+            return "rn", _rn_config_from_state_dict(sd), text_cfg
 
-        kind, cfg = _shard.on_rank0(probe)  # the other ranks receive the configuration, never the file
+        kind, cfg, text_cfg = _shard.on_rank0(probe)  # the other ranks receive the configurations, never the file
         tower = _nets.ClipImageTower(ctx, config=cfg) if kind == "vit" else _nets.ClipResNetTower(ctx, config=cfg)
         _shard.load_broadcast(tower, lambda: {k: v.float() for k, v in held["sd"].items() if k.startswith("visual.")},
                               f"cuda:{ctx.device}", prefix="visual.")
-        held.clear()
         text_model = None
-        try:
-            import clip  # optional, setup-time only
+        if have_clip:
+            import clip
             text_model = clip.load(model_path, jit=False, device=device)[0].eval().requires_grad_(False)
-        except ImportError:
-            pass
+        elif text_cfg is not None:  # no `clip` package: the archive's text weights go to the native text tower
+            text_model = _nets.ClipTextTower(ctx, config=text_cfg)
+            _shard.load_broadcast(text_model, lambda: {k: v.float() for k, v in held["sd"].items() if _is_text_key(k)}, f"cuda:{ctx.device}")
+        held.clear()
         return ClipModel(tower, text_model, model_name), tower.input_resolution
     if script_util.synthetic_weights_enabled():
         if model_name in _nets.VIT_CONFIGS:
@@ -166,7 +198,10 @@ def encode_text_prompt(txt, weight, clip_model_name="ViT-B/32", device="cpu"):
     if clip_model.text_model is None:
         if script_util.synthetic_weights_enabled():
             return _synthetic_text_embedding(txt, clip_model.visual.output_dim, device), weight
-        raise RuntimeError("encode_text_prompt needs the `clip` package (tokenizer + text tower)")
+        raise RuntimeError("encode_text_prompt needs a CLIP checkpoint with text weights (native text tower) or the `clip` package")
+    if clip_model.native_text:
+        tokens = _tokenizer.tokenize(txt, clip_model.text_model.context_length, checkpoints_dir=script_util.CACHE_PATH)
+        return clip_model.encode_text(tokens.to(device)).float(), weight
     import clip
     tokens = clip.tokenize(txt).to(device)
     return clip_model.encode_text(tokens).float(), weight

@@ -12,11 +12,14 @@
 
 namespace {
 
-// one wavefront per row, three passes over an L1/L2-resident row
+// one wavefront per row, three passes over an L1/L2-resident row.  CAUSAL: the rows are [sequence x head][T] blocks of query rows and row i
+// keeps columns 0..i (clip.model.CLIP.build_attention_mask), a row-dependent column limit; the other columns are set to 0 like those >= T
+template <bool CAUSAL>
 __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ S, long rows, int T, int ld) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
+  if constexpr (CAUSAL) T = (int)(row % T) + 1;
   float* r = S + row * ld;
   float mx = -INFINITY;
   for (int c = lane; c < T; c += 64) mx = fmaxf(mx, r[c]);
@@ -234,7 +237,9 @@ __device__ __forceinline__ void am_sstore(float* dst, int pitch, const am_f32x4 
   }
 }
 
-template <bool X3>
+// CAUSAL: key j > query i is masked (clip.model.CLIP.build_attention_mask); key blocks that lie entirely above the diagonal of the 32-row query tile are
+// skipped, so every block the loops visit holds key 128 j <= q0 <= every query row of the tile: no row of a visited block is fully masked
+template <bool X3, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_mid_fwd_kernel(const float* __restrict__ qkv, int ldq, float* __restrict__ out, int ldo,
                                                            float* __restrict__ Ocopy, float* __restrict__ P, int T, int Tp, int H,
                                                            long qo, long ko, long vo, long step, float alpha) {
@@ -244,7 +249,8 @@ __global__ __launch_bounds__(256) void attn_mid_fwd_kernel(const float* __restri
   const int qb = blockIdx.x, h = blockIdx.y, n = blockIdx.z;
   const float* base = qkv + (long)n * T * ldq + h * step;
   am_stage64<32>(Qs, AM_P68, base + (long)qb * 32 * ldq + qo, ldq, tid, T - qb * 32);
-  const int nkb = (T + 127) >> 7;  // key blocks; keys >= T are masked (score -inf, probability 0), query rows >= T not stored
+  // key blocks; keys >= T are masked (score -inf, probability 0), query rows >= T not stored
+  const int nkb = CAUSAL ? ((T < qb * 32 + 32 ? T : qb * 32 + 32) + 127) >> 7 : (T + 127) >> 7;
   const int srow = tid >> 3, seg = tid & 7;
   float m_run = -INFINITY, l_run = 0.f;
   AmPre qpre;  // X3: this lane's Q fragments, split once (am_presplit64)
@@ -268,8 +274,10 @@ __global__ __launch_bounds__(256) void attn_mid_fwd_kernel(const float* __restri
       am_mma_nt64<X3>(sacc, &Qs[l31 * AM_P68], &Ks[(32 * w + l31) * AM_P68], hh);
     }
 #pragma unroll
-    for (int r = 0; r < 16; ++r)
-      Ss[((r & 3) + 8 * (r >> 2) + 4 * hh) * AM_PS + 32 * w + l31] = (j * 128 + 32 * w + l31 < T) ? sacc[r] * alpha : -INFINITY;
+    for (int r = 0; r < 16; ++r) {
+      const int row = (r & 3) + 8 * (r >> 2) + 4 * hh, key = j * 128 + 32 * w + l31;
+      Ss[row * AM_PS + 32 * w + l31] = (key < T && (!CAUSAL || key <= qb * 32 + row)) ? sacc[r] * alpha : -INFINITY;
+    }
     __syncthreads();
     float v[16], bm = -INFINITY;
 #pragma unroll
@@ -328,7 +336,7 @@ __global__ __launch_bounds__(256) void attn_mid_fwd_kernel(const float* __restri
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = (r & 3) + 8 * (r >> 2) + 4 * hh;
-      const float p = key < T ? __expf(sacc[r] * alpha - mr[r]) * il[r] : 0.f;
+      const float p = (key < T && (!CAUSAL || key <= qb * 32 + row)) ? __expf(sacc[r] * alpha - mr[r]) * il[r] : 0.f;
       Ss[row * AM_PS + 32 * w + l31] = p;
       if (qb * 32 + row < T && key < Tp) Pg[(long)row * Tp + j * 128] = p;
     }
@@ -518,7 +526,8 @@ __device__ __forceinline__ void am_stage_rows(float* dst, int pitch, const float
   }
 }
 
-template <bool X3>
+// CAUSAL: row i keeps keys 0..i
+template <bool X3, bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_s64_fwd_kernel(const float* __restrict__ qkv, int ldq, float* __restrict__ out, int ldo,
                                                            float* __restrict__ P, int T, int Tp, int H, long qo, long ko, long vo, long step,
                                                            float alpha) {
@@ -540,11 +549,12 @@ __global__ __launch_bounds__(256) void attn_s64_fwd_kernel(const float* __restri
   __syncthreads();
   {
     const int row = tid >> 2, seg = tid & 3;
+    const int lim = CAUSAL ? (row < T ? row + 1 : T) : T;
     float v[16], mx = -INFINITY;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int sidx = seg * 16 + i;
-      v[i] = sidx < T ? Ss[row * AM_P68 + sidx] : -INFINITY;
+      v[i] = sidx < lim ? Ss[row * AM_P68 + sidx] : -INFINITY;
       mx = fmaxf(mx, v[i]);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 1, 64));
@@ -681,14 +691,17 @@ AttnPath attn_select(const cgd_ctx* ctx, const AttnShape& sh, int ldq, int ldo, 
 
 // the forward's kernel family per statistics / probabilities buffer: the fused families leave in bufs.P what only their OWN backward can
 // read (row statistics vs probabilities), so the backward refuses to run another family than the forward that last wrote the buffer
-void attn_note_path(cgd_ctx* ctx, const float* P, AttnPath path) {
+// (+ ATTN_CAUSAL_NOTE when the forward was causal: there is no causal backward, the backward refuses those buffers)
+constexpr int ATTN_CAUSAL_NOTE = 16;
+void attn_note_path(cgd_ctx* ctx, const float* P, AttnPath path, bool causal) {
+  const int v = (int)path + (causal ? ATTN_CAUSAL_NOTE : 0);
   for (auto& e : ctx->attn_fwd_path)
     if (e.first == P) {
-      e.second = (int)path;
+      e.second = v;
       return;
     }
   if (ctx->attn_fwd_path.size() >= 4096) ctx->attn_fwd_path.clear();  // op-level callers with ever-new buffers: forget, never grow without bound
-  ctx->attn_fwd_path.emplace_back(P, (int)path);
+  ctx->attn_fwd_path.emplace_back(P, v);
 }
 int attn_noted_path(const cgd_ctx* ctx, const float* P) {
   for (const auto& e : ctx->attn_fwd_path)
@@ -714,7 +727,12 @@ size_t cgd_attn_buf_floats(const cgd_ctx* ctx, const AttnShape& sh, int ldq, int
 }
 
 int cgd_launch_softmax_rows(cgd_ctx* ctx, float* S, long rows, int T, int ld, hipStream_t s) {
-  CGD_LAUNCH(softmax_rows_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, S, rows, T, ld);
+  CGD_LAUNCH(softmax_rows_kernel<false>, dim3(cdiv(rows, 4)), dim3(256), 0, s, S, rows, T, ld);
+  CGD_HIP(ctx, hipGetLastError());
+  return 0;
+}
+static int launch_softmax_rows_causal(cgd_ctx* ctx, float* S, long rows, int T, int ld, hipStream_t s) {
+  CGD_LAUNCH(softmax_rows_kernel<true>, dim3(cdiv(rows, 4)), dim3(256), 0, s, S, rows, T, ld);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }
@@ -732,26 +750,38 @@ int cgd_attn_fwd(cgd_ctx* ctx, const AttnShape& sh, const float* qkv, int ldq, f
   if (d % 4) CGD_FAIL(ctx, "attention: head dim must be a multiple of 4");
   const HeadOff ho = head_off(sh);
   const AttnPath path = attn_select(ctx, sh, ldq, ldo, x3);
-  attn_note_path(ctx, bufs.P, path);
+  attn_note_path(ctx, bufs.P, path, sh.causal != 0);
   if (path == ATTN_FLASH) return cgd_attn_flash_fwd(ctx, sh, qkv, ldq, out, ldo, bufs, ho.q, ho.k, ho.v, ho.step, s);
   if (path == ATTN_S64) {
-    if (x3) {
-      CGD_LAUNCH((attn_s64_fwd_kernel<true>), dim3(H, sh.nb), dim3(256), 0, s, qkv, ldq, out, ldo, bufs.P, T, Tp, H, ho.q, ho.k, ho.v, ho.step,
-                       1.f / sqrtf((float)d));
+    const dim3 grid(H, sh.nb);
+    const float alpha = 1.f / sqrtf((float)d);
+    if (x3 && sh.causal) {
+      CGD_LAUNCH((attn_s64_fwd_kernel<true, true>), grid, dim3(256), 0, s, qkv, ldq, out, ldo, bufs.P, T, Tp, H, ho.q, ho.k, ho.v, ho.step, alpha);
+    } else if (x3) {
+      CGD_LAUNCH((attn_s64_fwd_kernel<true, false>), grid, dim3(256), 0, s, qkv, ldq, out, ldo, bufs.P, T, Tp, H, ho.q, ho.k, ho.v, ho.step, alpha);
+    } else if (sh.causal) {
+      CGD_LAUNCH((attn_s64_fwd_kernel<false, true>), grid, dim3(256), 0, s, qkv, ldq, out, ldo, bufs.P, T, Tp, H, ho.q, ho.k, ho.v, ho.step, alpha);
     } else {
-      CGD_LAUNCH((attn_s64_fwd_kernel<false>), dim3(H, sh.nb), dim3(256), 0, s, qkv, ldq, out, ldo, bufs.P, T, Tp, H, ho.q, ho.k, ho.v, ho.step,
-                       1.f / sqrtf((float)d));
+      CGD_LAUNCH((attn_s64_fwd_kernel<false, false>), grid, dim3(256), 0, s, qkv, ldq, out, ldo, bufs.P, T, Tp, H, ho.q, ho.k, ho.v, ho.step, alpha);
     }
     CGD_HIP(ctx, hipGetLastError());
     return 0;
   }
   if (path == ATTN_MID) {
-    if (x3) {
-      CGD_LAUNCH((attn_mid_fwd_kernel<true>), dim3(cdiv(T, 32), H, sh.nb), dim3(256), 0, s, qkv, ldq, out, ldo, bufs.qkvT, bufs.P, T, Tp, H, ho.q, ho.k,
-                       ho.v, ho.step, 1.f / sqrtf((float)d));
+    const dim3 grid(cdiv(T, 32), H, sh.nb);
+    const float alpha = 1.f / sqrtf((float)d);
+    if (x3 && sh.causal) {
+      CGD_LAUNCH((attn_mid_fwd_kernel<true, true>), grid, dim3(256), 0, s, qkv, ldq, out, ldo, bufs.qkvT, bufs.P, T, Tp, H, ho.q, ho.k, ho.v, ho.step,
+                 alpha);
+    } else if (x3) {
+      CGD_LAUNCH((attn_mid_fwd_kernel<true, false>), grid, dim3(256), 0, s, qkv, ldq, out, ldo, bufs.qkvT, bufs.P, T, Tp, H, ho.q, ho.k, ho.v, ho.step,
+                 alpha);
+    } else if (sh.causal) {
+      CGD_LAUNCH((attn_mid_fwd_kernel<false, true>), grid, dim3(256), 0, s, qkv, ldq, out, ldo, bufs.qkvT, bufs.P, T, Tp, H, ho.q, ho.k, ho.v, ho.step,
+                 alpha);
     } else {
-      CGD_LAUNCH((attn_mid_fwd_kernel<false>), dim3(cdiv(T, 32), H, sh.nb), dim3(256), 0, s, qkv, ldq, out, ldo, bufs.qkvT, bufs.P, T, Tp, H, ho.q, ho.k,
-                       ho.v, ho.step, 1.f / sqrtf((float)d));
+      CGD_LAUNCH((attn_mid_fwd_kernel<false, false>), grid, dim3(256), 0, s, qkv, ldq, out, ldo, bufs.qkvT, bufs.P, T, Tp, H, ho.q, ho.k, ho.v, ho.step,
+                 alpha);
     }
     CGD_HIP(ctx, hipGetLastError());
     return 0;
@@ -770,7 +800,10 @@ int cgd_attn_fwd(cgd_ctx* ctx, const AttnShape& sh, const float* qkv, int ldq, f
   g.sB1 = (long)T * ldq; g.sB2 = ho.step;
   g.sC1 = (long)H * T * Tp; g.sC2 = (long)T * Tp;
   CGD_TRY(cgd_launch_gemm(ctx, g, s));
-  CGD_TRY(cgd_launch_softmax_rows(ctx, bufs.P, (long)sh.nb * H * T, T, Tp, s));
+  if (sh.causal)
+    CGD_TRY(launch_softmax_rows_causal(ctx, bufs.P, (long)sh.nb * H * T, T, Tp, s));
+  else
+    CGD_TRY(cgd_launch_softmax_rows(ctx, bufs.P, (long)sh.nb * H * T, T, Tp, s));
   // O = P v : B operand = v^T rows inside qkvT
   GemmParams o;
   o.A = bufs.P;  o.lda = Tp;
@@ -796,7 +829,10 @@ int cgd_attn_bwd(cgd_ctx* ctx, const AttnShape& sh, const float* qkv, int ldq, c
   const AttnPath path = attn_select(ctx, sh, ldq, lddo, x3);  // the forward's choice when out and dout share a row stride and no knob changed
   // ... and when they do not (a dout stride that is not a multiple of 4 floats, a precision / knob change between the passes): fail loudly instead of
   // reading row statistics as probabilities
+  if (sh.causal) CGD_FAIL(ctx, "attention backward: causal attention (the CLIP text tower) has a forward pass only");
   const int noted = attn_noted_path(ctx, bufs.P);
+  if (noted >= ATTN_CAUSAL_NOTE)
+    CGD_FAIL(ctx, "attention backward: the forward that filled these buffers was causal, and causal attention has a forward pass only");
   if (noted >= 0 && noted != (int)path)
     CGD_FAIL(ctx, "attention backward: the forward that filled these buffers ran kernel family " + std::to_string(noted) + ", the backward would run " +
                       std::to_string((int)path) + " (row stride of dout, precision or CGD_ATTN_* changed between the passes)");

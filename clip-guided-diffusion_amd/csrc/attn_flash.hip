@@ -147,6 +147,11 @@ constexpr int FA_FWD_WAVE = 2 * FA_NPLANE + 2 * FA_TPLANE;  // K natural + V tra
 static_assert(FA_FWD_WAVE * 2 >= 32 * FA_OP * 4, "forward merge slab must fit the wavefront's staging region");
 
 // lse: [nb * H][Tq] with Tq = 32 * ceil(T / 32); rows >= T hold +inf (their recomputed probabilities are exactly 0)
+// CAUSAL (the CLIP text tower, forward only): key j > query i is masked.  Key blocks above the diagonal of the 32-row query tile (b > qb) are skipped,
+// so a wavefront can own no block at all: its m_run stays -inf, l_run and o 0, and the merge weighs it with exp(-inf - M) = 0 — M is finite because
+// wavefront 0 always owns block 0.  In every block a wavefront does visit, key 32 b <= q0 <= each query of the tile, so a row maximum is finite and
+// no -inf - -inf is formed.
+template <bool CAUSAL>
 __global__ __launch_bounds__(256) void attn_flash_fwd_kernel(const float* __restrict__ qkv, int ldq, float* __restrict__ out, int ldo,
                                                              float* __restrict__ Ocopy, float* __restrict__ lse, int T, int Tq, int H,
                                                              long qo, long ko, long vo, long step, float alpha) {
@@ -162,7 +167,7 @@ __global__ __launch_bounds__(256) void attn_flash_fwd_kernel(const float* __rest
   __bf16* const Kl = Kh + FA_NPLANE;
   __bf16* const Vh = Kl + FA_NPLANE;
   __bf16* const Vl = Vh + FA_TPLANE;
-  const int nkb = (T + 31) >> 5;
+  const int nkb = CAUSAL ? ((T + 31) >> 5 < qb + 1 ? (T + 31) >> 5 : qb + 1) : (T + 31) >> 5;
   fa_f32x16 o[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
@@ -188,11 +193,11 @@ __global__ __launch_bounds__(256) void attn_flash_fwd_kernel(const float* __rest
 #pragma unroll
     for (int s = 0; s < 4; ++s) fa_mma3(sacc, fa_frag_nat(Kh, l31, hh, s), fa_frag_nat(Kl, l31, hh, s), qh[s], ql[s]);
     float p[16], bm = -INFINITY;
-    if (b * 32 + 32 > T) {  // the ragged last block only (wave-uniform): keys beyond T leave the softmax
+    if (b * 32 + 32 > T || (CAUSAL && b == qb)) {  // the ragged last block (and the diagonal block) only (wave-uniform): keys beyond T leave the softmax
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int key = b * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-        p[r] = key < T ? sacc[r] : -INFINITY;
+        p[r] = (key < T && (!CAUSAL || key <= q0 + l31)) ? sacc[r] : -INFINITY;
       }
     } else {
 #pragma unroll
@@ -637,8 +642,12 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_small_kernel(const float* 
 int cgd_attn_flash_fwd(cgd_ctx* ctx, const AttnShape& sh, const float* qkv, int ldq, float* out, int ldo, const AttnBufs& bufs, long qo,
                        long ko, long vo, long step, hipStream_t s) {
   const int T = sh.T, H = sh.heads, Tq = cdiv(T, 32) * 32;
-  CGD_LAUNCH(attn_flash_fwd_kernel, dim3(Tq / 32, H, sh.nb), dim3(256), 0, s, qkv, ldq, out, ldo, bufs.qkvT, bufs.P, T, Tq, H, qo, ko, vo, step,
-             1.f / sqrtf((float)sh.d));
+  if (sh.causal)
+    CGD_LAUNCH(attn_flash_fwd_kernel<true>, dim3(Tq / 32, H, sh.nb), dim3(256), 0, s, qkv, ldq, out, ldo, bufs.qkvT, bufs.P, T, Tq, H, qo, ko, vo, step,
+               1.f / sqrtf((float)sh.d));
+  else
+    CGD_LAUNCH(attn_flash_fwd_kernel<false>, dim3(Tq / 32, H, sh.nb), dim3(256), 0, s, qkv, ldq, out, ldo, bufs.qkvT, bufs.P, T, Tq, H, qo, ko, vo, step,
+               1.f / sqrtf((float)sh.d));
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }

@@ -435,6 +435,12 @@ int cgd_op_attn_fwd(cgd_ctx* ctx, const float* qkv, float* out, int nb, int head
   AttnBufs bf{bufs[0], bufs[1], bufs[2], bufs[3], bufs[4]};
   return cgd_attn_fwd(ctx, sh, qkv, 3 * heads * d, out, heads * d, bf, S(stream));
 }
+int cgd_op_attn_fwd_causal(cgd_ctx* ctx, const float* qkv, float* out, int nb, int heads, int T, int d, float* bufs[5], void* stream) {
+  CGD_NEED_CTX(ctx);
+  AttnShape sh{nb, heads, T, d, heads * d, 0, 1};
+  AttnBufs bf{bufs[0], bufs[1], bufs[2], bufs[3], bufs[4]};
+  return cgd_attn_fwd(ctx, sh, qkv, 3 * heads * d, out, heads * d, bf, S(stream));
+}
 int cgd_op_attn_bwd(cgd_ctx* ctx, const float* qkv, const float* dout, float* dqkv, int nb, int heads, int T, int d, int legacy,
                     float* bufs[5], void* stream) {
   CGD_NEED_CTX(ctx);

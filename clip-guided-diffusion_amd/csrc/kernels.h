@@ -74,6 +74,7 @@ struct AttnShape {
   int d;       // head dim
   int C;       // = heads*d
   int legacy;  // 1: per-head [q|k|v] interleave (QKVAttentionLegacy); 0: [Q all heads | K | V]
+  int causal;  // 1: key j > query i is masked (the CLIP text tower); forward only, cgd_attn_bwd refuses it
 };
 struct AttnBufs {     // all owned by the caller, sized by cgd_attn_buf_floats
   float* qkvT;        // [nb][3C][Tp]
@@ -94,6 +95,7 @@ int cgd_attn_bwd(cgd_ctx* ctx, const AttnShape& sh, const float* qkv, int ldq, c
 
 // attn_flash.hip (round 5): d = 64, T > 32 in bf16x3 contexts (T > 64 only at CGD_ATTN_FLASH=1); P is never materialised, bufs.P holds the row statistics (LSE | D),
 // bufs.qkvT a copy of O for the backward's D = rowsum(dO * O).  qo / ko / vo / step: column offsets of head 0 and the per-head step
+// (sh.causal: the causal instantiation)
 int cgd_attn_flash_fwd(cgd_ctx* ctx, const AttnShape& sh, const float* qkv, int ldq, float* out, int ldo, const AttnBufs& bufs, long qo,
                        long ko, long vo, long step, hipStream_t s);
 int cgd_attn_flash_bwd(cgd_ctx* ctx, const AttnShape& sh, const float* qkv, int ldq, const float* dout, int lddo, float* dqkv, int lddq,

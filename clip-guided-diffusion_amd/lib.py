@@ -31,6 +31,10 @@ class ViTConfig(C.Structure):
     _fields_ = [("resolution", i32), ("patch", i32), ("width", i32), ("layers", i32), ("heads", i32), ("out_dim", i32)]
 
 
+class TextConfig(C.Structure):
+    _fields_ = [("context_length", i32), ("vocab_size", i32), ("width", i32), ("layers", i32), ("heads", i32), ("out_dim", i32)]
+
+
 class RNConfig(C.Structure):
     _fields_ = [("resolution", i32), ("width", i32), ("layers", i32 * 4), ("out_dim", i32), ("heads", i32)]
 
@@ -49,6 +53,7 @@ _SIGS = {
     "cgd_unet_manifest": (i32, [C.POINTER(UNetConfig), MANIFEST_CB, vp]),
     "cgd_vit_manifest": (i32, [C.POINTER(ViTConfig), MANIFEST_CB, vp]),
     "cgd_rn_manifest": (i32, [C.POINTER(RNConfig), MANIFEST_CB, vp]),
+    "cgd_text_manifest": (i32, [C.POINTER(TextConfig), MANIFEST_CB, vp]),
     "cgd_lpips_manifest": (i32, [MANIFEST_CB, vp]),
     "cgd_version": (C.c_char_p, []),
     "cgd_ctx_create": (i32, [C.POINTER(vp), i32]),
@@ -80,6 +85,13 @@ _SIGS = {
     "cgd_vit_finalize": (i32, [vp]),
     "cgd_vit_forward": (i32, [vp, vp, i32, i32, vp, vp]),
     "cgd_vit_dgrad": (i32, [vp, vp, vp, vp]),
+    "cgd_text_create": (i32, [vp, C.POINTER(TextConfig), C.POINTER(vp)]),
+    "cgd_text_destroy": (None, [vp]),
+    "cgd_text_num_params": (i32, [vp]),
+    "cgd_text_param_info": (i32, [vp, i32, C.c_char_p, i32, C.POINTER(i64)]),
+    "cgd_text_set_param": (i32, [vp, C.c_char_p, vp, i64]),
+    "cgd_text_finalize": (i32, [vp]),
+    "cgd_text_forward": (i32, [vp, vp, i32, vp, vp]),
     "cgd_rn_create": (i32, [vp, C.POINTER(RNConfig), C.POINTER(vp)]),
     "cgd_rn_destroy": (None, [vp]),
     "cgd_rn_num_params": (i32, [vp]),
@@ -136,6 +148,7 @@ _SIGS = {
     "cgd_op_attn_buf_floats": (i64, [i32, i32, i32, i32, i32]),
     "cgd_op_attn_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(vp), vp]),
     "cgd_op_attn_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(vp), vp]),
+    "cgd_op_attn_fwd_causal": (i32, [vp, vp, vp, i32, i32, i32, i32, C.POINTER(vp), vp]),
     "cgd_op_attn_plan": (i32, [i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
 }
 

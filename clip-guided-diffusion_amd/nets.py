@@ -4,7 +4,7 @@
 (/root/reference/cgd/cgd.py:251, built by /root/reference/cgd/script_util.py:281-324); `ClipImageTower`
 mirrors `clip_model.encode_image` + `.visual.input_resolution` (/root/reference/cgd/clip_util.py:59-66,
 /root/reference/cgd/cgd.py:194).  Both add `dgrad`, the hand-derived backward-to-input that replaces
-`th.autograd.grad(loss, x)` (cgd.py:228).
+`th.autograd.grad(loss, x)` (cgd.py:228).  `ClipTextTower` mirrors `clip_model.encode_text` (prompt encoding, forward only).
 """
 import ctypes as C
 
@@ -19,6 +19,18 @@ VIT_CONFIGS = {
     "ViT-B/32": (224, 32, 768, 12, 12, 512),
     "ViT-B/16": (224, 16, 768, 12, 12, 512),
     "ViT-L/14": (224, 14, 1024, 24, 16, 768),
+}
+
+TEXT_CONFIGS = {
+    # name: (context_length, vocab_size, width, layers, heads, out_dim) of the text tower of each published CLIP model
+    # (clip/model.py build_model: width = ln_final.weight.shape[0], heads = width // 64, out_dim = text_projection.shape[1])
+    "ViT-B/16": (77, 49408, 512, 12, 8, 512),
+    "ViT-B/32": (77, 49408, 512, 12, 8, 512),
+    "RN50": (77, 49408, 512, 12, 8, 1024),
+    "RN101": (77, 49408, 512, 12, 8, 512),
+    "RN50x4": (77, 49408, 640, 12, 10, 640),
+    "RN50x16": (77, 49408, 768, 12, 12, 768),
+    "ViT-L/14": (77, 49408, 768, 12, 12, 768),
 }
 
 
@@ -221,6 +233,42 @@ class EncodeImageFunction(th.autograd.Function):
     @staticmethod
     def backward(ctx, d_emb):
         return ctx.tower.dgrad(d_emb.float().contiguous()).view(ctx.in_shape), None
+
+
+class ClipTextTower(_Net):
+    """`clip_model.encode_text(tokens)` (clip.model.CLIP.encode_text) on the device: forward only, in the context's precision mode."""
+    _prefix = "text"
+
+    def __init__(self, ctx, name="ViT-B/32", config=None):
+        self.ctx = ctx
+        T, vocab, width, layers, heads, out = config or TEXT_CONFIGS[name]
+        self.cfg = L.TextConfig(T, vocab, width, layers, heads, out)
+        self.context_length, self.vocab_size, self.width, self.out_dim = T, vocab, width, out
+        h = C.c_void_p()
+        ctx.check(ctx.lib.cgd_text_create(ctx.h, C.byref(self.cfg), C.byref(h)))
+        self._adopt(h)
+
+    def load_clip_state_dict(self, sd):
+        """An OpenAI CLIP state dict: the text tower's keys are top-level (`visual.*` and `logit_scale` are not read)."""
+        return self.load_state_dict(sd)
+
+    def encode_text(self, tokens, out=None):
+        """tokens (N, context_length) integer ids in [0, vocab_size) -> (N, out_dim) fp32."""
+        if tokens.dim() != 2 or tokens.shape[1] != self.context_length:
+            raise ValueError(f"tokens must be (N, {self.context_length}), got {tuple(tokens.shape)}")
+        if tokens.is_floating_point() or tokens.is_complex() or tokens.dtype == th.bool:
+            raise ValueError(f"tokens must be integer ids, got {tokens.dtype}")
+        if tokens.shape[0] == 0:
+            raise ValueError("tokens: empty batch")
+        lo, hi = int(tokens.min()), int(tokens.max())
+        if lo < 0 or hi >= self.vocab_size:
+            raise ValueError(f"token ids must lie in [0, {self.vocab_size}), got [{lo}, {hi}]")
+        tok = tokens.to(device=f"cuda:{self.ctx.device}", dtype=th.int64).contiguous()
+        if out is None:
+            out = th.empty((tok.shape[0], self.out_dim), device=tok.device, dtype=th.float32)
+        self.ctx.check(self.ctx.lib.cgd_text_forward(self.h, tok.data_ptr(), tok.shape[0], out.data_ptr(), self.ctx.stream()))
+        self._keep = tok  # the launch reads it asynchronously
+        return out
 
 
 RN_CONFIGS = {

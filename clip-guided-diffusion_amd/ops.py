@@ -163,6 +163,16 @@ class Attention:
                                                     self.legacy, self._arr, _s()))
         return out
 
+    def forward_causal(self, qkv):
+        """The forward with key j > query i masked (the CLIP text tower; [Q | K | V] rows only, no backward)."""
+        if self.legacy:
+            raise ValueError("causal attention takes the [Q all heads | K | V] row layout (legacy=0)")
+        Cc = self.heads * self.d
+        out = th.empty((self.nb * self.T, Cc), device=qkv.device, dtype=th.float32)
+        self.ctx.check(self.ctx.lib.cgd_op_attn_fwd_causal(self.ctx.h, qkv.data_ptr(), out.data_ptr(), self.nb, self.heads, self.T, self.d,
+                                                           self._arr, _s()))
+        return out
+
     def backward(self, qkv, dout):
         dqkv = th.empty_like(qkv)
         self.ctx.check(self.ctx.lib.cgd_op_attn_bwd(self.ctx.h, qkv.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), self.nb, self.heads,

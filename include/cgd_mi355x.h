@@ -114,6 +114,26 @@ int cgd_vit_finalize(cgd_vit* v);
 int cgd_vit_forward(cgd_vit* v, const float* img, int layout, int N, float* emb /* (N,out_dim) */, void* stream);
 int cgd_vit_dgrad(cgd_vit* v, const float* d_emb, float* d_img /* same layout as the forward input */, void* stream);
 
+/* ---- CLIP text tower (clip.model.CLIP.encode_text): token embedding + positional embedding, `layers` pre-LN residual blocks with CAUSAL
+ *      self-attention, ln_final on the end-of-text row of each sequence (the first maximal token id, CLIP's EOT convention), @ text_projection.
+ *      Replaces the `clip` package's text transformer behind encode_text_prompt (cgd/clip_util.py).  Forward only; runs in the context's
+ *      precision mode.  Parameter names are the OpenAI top-level keys: token_embedding.weight, positional_embedding,
+ *      transformer.resblocks.{l}.* (the image tower's block names), ln_final.{weight,bias}, text_projection (W x out_dim, x @ text_projection). ---- */
+typedef struct cgd_text cgd_text;
+typedef struct cgd_text_config {
+  int context_length, vocab_size, width, layers, heads, out_dim;
+} cgd_text_config;
+int cgd_text_manifest(const cgd_text_config* cfg, cgd_manifest_cb cb, void* user);
+int cgd_text_create(cgd_ctx* ctx, const cgd_text_config* cfg, cgd_text** out);
+void cgd_text_destroy(cgd_text* t);
+int cgd_text_num_params(cgd_text* t);
+int cgd_text_param_info(cgd_text* t, int index, char* name_buf, int buf_len, int64_t* numel);
+int cgd_text_set_param(cgd_text* t, const char* name, const float* data, int64_t numel);
+int cgd_text_finalize(cgd_text* t);
+/* tokens: DEVICE int64 (N, context_length), ids in [0, vocab_size) (an id outside that range reads nothing and makes its row NaN);
+ * emb: (N, out_dim) */
+int cgd_text_forward(cgd_text* t, const int64_t* tokens, int N, float* emb, void* stream);
+
 /* ---- CLIP image tower, ModifiedResNet variant (RN50 / RN101; clip_util.py:17): same role as the ViT tower.  Parameters use
  *      the OpenAI `visual.*` names including the BatchNorm running statistics (folded into the convolutions by finalize).
  *      img: (N,3,res,res) NCHW, CLIP-normalised. ---- */
@@ -290,6 +310,9 @@ int cgd_op_attn_fwd(cgd_ctx* ctx, const float* qkv, float* out, int nb, int head
                     void* stream);
 int cgd_op_attn_bwd(cgd_ctx* ctx, const float* qkv, const float* dout, float* dqkv, int nb, int heads, int T, int d, int legacy,
                     float* bufs[5], void* stream);
+/* cgd_op_attn_fwd with a causal mask (key j > query i excluded; [Q all heads | K | V] rows): every kernel family honours it.  There is no causal
+ * backward: cgd_op_attn_bwd fails (-2) on the buffers of a causal forward. */
+int cgd_op_attn_fwd_causal(cgd_ctx* ctx, const float* qkv, float* out, int nb, int heads, int T, int d, float* bufs[5], void* stream);
 /* host-only (no GPU, no context): the kernel family cgd_op_attn_fwd / _bwd (and the UNet / ViT towers) pick for one attention shape.  ldq / ldo =
  * row strides of qkv and of out / dout in floats; precision as in cgd_ctx_create; attn_flash = the CGD_ATTN_FLASH knob (0..3), < 0 = its default.
  * out2 = {family: 0 batched GEMMs + row softmax (any head dim), 1 attn_s64_* (d = 64, T <= 64), 2 attn_mid_* (d = 64, T > 64, probabilities

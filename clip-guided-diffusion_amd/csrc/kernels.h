@@ -111,6 +111,17 @@ int cgd_launch_cutouts_fwd(cgd_ctx* ctx, const float* x_in /*B,3,H,W in [-1,1]*/
 // G[b,c,y,x] (+)= sum over cutouts of pooled-gradient scatter; dout has the forward's layout
 int cgd_launch_cutouts_bwd(cgd_ctx* ctx, const float* dout, const int* coords, float* G /*B,3,H,W*/, int B, int H, int W, int cutn,
                            int cs, int layout, int P, int accumulate, hipStream_t s);
+// cutaug.hip: cutouts with the `use_augs` augmentations between crop and pool (params: device float [cutn][16], the record of
+// include/cgd_mi355x.h; noise: device float or null, noise_off: device int64 [cutn] offsets of each cutout's four (B,3,h,w) planes)
+int cgd_launch_cutouts_aug_fwd(cgd_ctx* ctx, const float* x_in, const int* coords, const float* params, const float* noise,
+                               const int64_t* noise_off, float* out, int B, int H, int W, int cutn, int cs, int layout, int P,
+                               hipStream_t s);
+// G[b,c,y,x] (+)= adjoint of the above (noise does not enter); scratch: cgd_cutouts_aug_scratch(B, H, W, cutn) floats
+int cgd_launch_cutouts_aug_bwd(cgd_ctx* ctx, const float* dout, const int* coords, const float* params, float* G, float* scratch, int B,
+                               int H, int W, int cutn, int cs, int layout, int P, int accumulate, hipStream_t s);
+size_t cgd_cutouts_aug_scratch(int B, int H, int W, int cutn);
+// host: per output pixel of an h x w crop, the affine nearest source index (-1: fill) and the perspective's 4 taps / weights
+int cgd_aug_sample_map(const float* params, int h, int w, int32_t* affine_src, int32_t* persp_idx, float* persp_w);
 // spherical-distance loss and its gradient w.r.t. the cutout embeddings
 //   emb [cutn*B][D] (row = cut*B + b), targets [P][D], weights [B][P] (dense per-sample prompt weights, see
 //   host-side broadcast rules), loss_part: per-(cut,b) partial losses [cutn*B] (already * scale / cutn)

@@ -7,7 +7,9 @@ gradient in closed form through the C ABI:
     cutouts -> CLIP ViT forward -> spherical loss (+grad) -> ViT dgrad -> cutout scatter -> tv/range/sat grads
     -> chain through the blend and x0 = a*x - b*eps -> UNet dgrad -> negative gradient (-> magnitude clamp).
 Cutout coordinates are drawn exactly like the reference does (three CPU-generator draws per cutout,
-/root/reference/cgd/modules.py:44-46).
+/root/reference/cgd/modules.py:44-46).  With `use_augs=True` the cutouts are augmented (flip / nearest affine / bilinear
+perspective / grayscale / additive noise) inside the cutaug HIP kernels, whose adjoint is a deterministic gather; the parameters
+are drawn like reference_augs draws them (draw_aug_params), the noise on the device generator in its randn_like order.
 """
 import math
 
@@ -56,16 +58,23 @@ def aug_affine(x, angle_deg, tx, ty):
     return _sample_grid(x, xi, yi, "nearest")
 
 
-def aug_perspective(x, startpoints, endpoints):
-    """torchvision.transforms.functional.perspective(x, startpoints, endpoints), BILINEAR, fill 0: the homography that takes the
-    `endpoints` (output corners) to the `startpoints` (input corners), solved like torchvision's _get_perspective_coeffs."""
-    _, _, H, W = x.shape
+def perspective_coeffs(startpoints, endpoints):
+    """The 8 coefficients of the homography that takes the `endpoints` (output corners) to the `startpoints` (input corners), solved
+    like torchvision's _get_perspective_coeffs (float64 least squares), as the float32 values aug_perspective and the kernels use."""
     A = th.zeros(8, 8, dtype=th.float64)
     for i, ((x1, y1), (x2, y2)) in enumerate(zip(endpoints, startpoints)):
         A[2 * i] = th.tensor([x1, y1, 1, 0, 0, 0, -x2 * x1, -x2 * y1], dtype=th.float64)
         A[2 * i + 1] = th.tensor([0, 0, 0, x1, y1, 1, -y2 * x1, -y2 * y1], dtype=th.float64)
     b = th.tensor([c for p in startpoints for c in p], dtype=th.float64)
-    co = th.linalg.lstsq(A, b).solution.float().tolist()
+    return th.linalg.lstsq(A, b).solution.float().tolist()
+
+
+def aug_perspective(x, startpoints, endpoints, coeffs=None):
+    """torchvision.transforms.functional.perspective(x, startpoints, endpoints), BILINEAR, fill 0: the homography that takes the
+    `endpoints` (output corners) to the `startpoints` (input corners), solved like torchvision's _get_perspective_coeffs (or the
+    already solved `coeffs`: the least-squares solve is not bit-reproducible from call to call in its near-zero coefficients)."""
+    _, _, H, W = x.shape
+    co = perspective_coeffs(startpoints, endpoints) if coeffs is None else coeffs
     ys, xs = th.meshgrid(th.arange(H, device=x.device, dtype=th.float32) + 0.5, th.arange(W, device=x.device, dtype=th.float32) + 0.5,
                          indexing="ij")
     den = co[6] * xs + co[7] * ys + 1.0
@@ -83,6 +92,58 @@ def aug_grayscale(x):
 AUG_NOISE_STD = 0.01  # the reference's `x + randn_like(x) * 0.01` between the transforms (tests set it to 0 for CPU/GPU comparisons)
 
 
+class AugParams:
+    """One cutout's draw of the `use_augs` parameters (see draw_aug_params) and its record for the cutaug kernels."""
+    __slots__ = ("flip", "angle", "tx", "ty", "persp", "startpoints", "endpoints", "coeffs", "gray")
+
+    def __init__(self):
+        self.flip = self.persp = self.gray = False
+        self.angle, self.tx, self.ty = 0.0, 0, 0
+        self.startpoints = self.endpoints = self.coeffs = None
+
+    def record(self):
+        """The 16-float parameter record of include/cgd_mi355x.h (cgd_cutouts_aug_fwd): flip, cos, sin, tx, ty, perspective flag,
+        8 homography coefficients, grayscale flag, 0.  cos / sin / coefficients become float32 exactly as aug_affine / aug_perspective
+        apply them to a float32 tensor."""
+        a = math.radians(self.angle)
+        co = self.coeffs if self.persp else [0.0] * 8
+        return [float(self.flip), math.cos(a), math.sin(a), float(self.tx), float(self.ty), float(self.persp), *co, float(self.gray), 0.0]
+
+
+def _aug_draws(H, W):
+    """The parameter draws of reference_augs on an (N,3,H,W) cutout, in torchvision's order on the global CPU generator, one
+    transform at a time: yields the same AugParams after the flip, the affine, the perspective and the grayscale draws (the torch
+    path adds its noise in between; on CPU tensors that noise comes from the same generator)."""
+    p = AugParams()
+    p.flip = th.rand(1).item() < 0.5
+    yield p
+    p.angle = float(th.empty(1).uniform_(-15.0, 15.0).item())
+    p.tx = int(round(th.empty(1).uniform_(-0.1 * W, 0.1 * W).item()))
+    p.ty = int(round(th.empty(1).uniform_(-0.1 * H, 0.1 * H).item()))
+    yield p
+    if th.rand(1).item() < 0.7:
+        hw, hh = W // 2, H // 2
+        d = 0.4
+        tl = [int(th.randint(0, int(d * hw) + 1, (1,)).item()), int(th.randint(0, int(d * hh) + 1, (1,)).item())]
+        tr = [int(th.randint(W - int(d * hw) - 1, W, (1,)).item()), int(th.randint(0, int(d * hh) + 1, (1,)).item())]
+        br = [int(th.randint(W - int(d * hw) - 1, W, (1,)).item()), int(th.randint(H - int(d * hh) - 1, H, (1,)).item())]
+        bl = [int(th.randint(0, int(d * hw) + 1, (1,)).item()), int(th.randint(H - int(d * hh) - 1, H, (1,)).item())]
+        p.persp = True
+        p.startpoints, p.endpoints = [[0, 0], [W - 1, 0], [W - 1, H - 1], [0, H - 1]], [tl, tr, br, bl]
+        p.coeffs = perspective_coeffs(p.startpoints, p.endpoints)
+    yield p
+    p.gray = th.rand(1).item() < 0.15
+    yield p
+
+
+def draw_aug_params(h, w):
+    """All parameter draws of reference_augs on one h x w cutout, in its order on the global CPU generator (flip; angle, tx, ty;
+    perspective and its 8 corner offsets if taken; grayscale): what the native `use_augs` path draws per cutout."""
+    for p in _aug_draws(h, w):
+        pass
+    return p
+
+
 def reference_augs(x):
     """The reference's `use_augs` pipeline (/root/reference/cgd/modules.py:13-24) on one batched cutout (N,3,h,w):
     RandomHorizontalFlip(0.5), RandomAffine(degrees=15, translate=(0.1, 0.1)), RandomPerspective(0.4, p=0.7),
@@ -93,32 +154,101 @@ def reference_augs(x):
     _, _, H, W = x.shape
     # no draw at all when the noise is switched off: on CPU tensors randn_like advances the same generator the parameters come from
     noise = lambda t: t + th.randn_like(t) * AUG_NOISE_STD if AUG_NOISE_STD else t  # noqa: E731
-    if th.rand(1).item() < 0.5:
+    draws = _aug_draws(H, W)
+    p = next(draws)
+    if p.flip:
         x = x.flip(-1)
     x = noise(x)
-    angle = float(th.empty(1).uniform_(-15.0, 15.0).item())
-    tx = int(round(th.empty(1).uniform_(-0.1 * W, 0.1 * W).item()))
-    ty = int(round(th.empty(1).uniform_(-0.1 * H, 0.1 * H).item()))
-    x = noise(aug_affine(x, angle, tx, ty))
-    if th.rand(1).item() < 0.7:
-        hw, hh = W // 2, H // 2
-        d = 0.4
-        tl = [int(th.randint(0, int(d * hw) + 1, (1,)).item()), int(th.randint(0, int(d * hh) + 1, (1,)).item())]
-        tr = [int(th.randint(W - int(d * hw) - 1, W, (1,)).item()), int(th.randint(0, int(d * hh) + 1, (1,)).item())]
-        br = [int(th.randint(W - int(d * hw) - 1, W, (1,)).item()), int(th.randint(H - int(d * hh) - 1, H, (1,)).item())]
-        bl = [int(th.randint(0, int(d * hw) + 1, (1,)).item()), int(th.randint(H - int(d * hh) - 1, H, (1,)).item())]
-        x = aug_perspective(x, [[0, 0], [W - 1, 0], [W - 1, H - 1], [0, H - 1]], [tl, tr, br, bl])
+    next(draws)
+    x = noise(aug_affine(x, p.angle, p.tx, p.ty))
+    next(draws)
+    if p.persp:
+        x = aug_perspective(x, p.startpoints, p.endpoints, p.coeffs)
     x = noise(x)
-    if th.rand(1).item() < 0.15:
+    next(draws)
+    if p.gray:
         x = aug_grayscale(x)
     return noise(x)
+
+
+AUG_GROUP_FLOATS = 1 << 25  # cutouts per launch group of the native `use_augs` path: noise + adjoint scratch of a group <= 128 MiB
+
+
+def _upload(t, dev):
+    """Small host table -> device without stalling the enqueueing thread: staged in pinned memory and copied asynchronously (torch's
+    pinned allocator does not hand the staging block out again before the copy that reads it has completed)."""
+    if th.device(dev).type != "cuda":
+        return t.to(dev)
+    return t.pin_memory().to(dev, non_blocking=True)
+
+
+class _AugLaunch:
+    """One draw of the native `use_augs` inputs for a list of cutout boxes: the parameters of every cutout (global CPU generator,
+    draw_aug_params order), then, per launch group of cutouts, the additive noise (4 x randn((B,3,h,w)) per cutout on the device
+    generator, the torch path's randn_like order; none while AUG_NOISE_STD is 0) right before the group's forward launch.  The
+    two generators are independent, so the same seed gives the same augmentations and noise as reference_augs on the device."""
+
+    def __init__(self, lib, coords, B, H, W, dev):
+        self.lib, self.B, self.H, self.W = lib, B, H, W
+        self.geo_list = crop_geometry(coords, H, W)
+        recs = [draw_aug_params(h, w).record() for (_, _, h, w) in self.geo_list]
+        self.geo = _upload(th.tensor(self.geo_list, dtype=th.int32).view(-1, 4), dev)
+        self.params = _upload(th.tensor(recs, dtype=th.float32).view(-1, 16), dev)
+        self.std = float(AUG_NOISE_STD)
+        self.groups, k0, used = [], 0, 0
+        for k, (_, _, h, w) in enumerate(self.geo_list):
+            n = (12 * B * h * w if self.std else 0) + 6 * B * H * W
+            if k > k0 and used + n > AUG_GROUP_FLOATS:
+                self.groups.append((k0, k))
+                k0, used = k, 0
+            used += n
+        if self.geo_list:
+            self.groups.append((k0, len(self.geo_list)))
+
+    def forward(self, ctx, x_pm1, out, cs, layout, patch):
+        """out rows (cut*B + b) of the cutouts of x_pm1 (B,3,H,W in [-1,1]), layout 0 or 1, CLIP-normalised."""
+        B, H, W, dev = self.B, self.H, self.W, x_pm1.device
+        row = out.element_size() * 3 * cs * cs * B
+        for k0, k1 in self.groups:
+            noise = off = None
+            if self.std:
+                sizes = [3 * B * h * w for (_, _, h, w) in self.geo_list[k0:k1]]
+                noise = th.empty(4 * sum(sizes), device=dev)
+                o, offs = 0, []
+                for (_, _, h, w), n in zip(self.geo_list[k0:k1], sizes):
+                    offs.append(o)
+                    for _ in range(4):
+                        noise[o:o + n].view(B, 3, h, w).normal_()
+                        o += n
+                noise.mul_(self.std)
+                off = _upload(th.tensor(offs, dtype=th.int64), dev)
+            ctx.check(self.lib.cgd_cutouts_aug_fwd(ctx.h, x_pm1.data_ptr(), self.geo[k0].data_ptr(), self.params[k0].data_ptr(),
+                                                   None if noise is None else noise.data_ptr(), None if off is None else off.data_ptr(),
+                                                   out.data_ptr() + k0 * row, B, H, W, k1 - k0, cs, layout, patch, ctx.stream()))
+
+    def backward(self, ctx, d_out, g, cs, layout, patch, accumulate):
+        """g (+)= d/dx_pm1 of <forward(x_pm1), d_out> (deterministic: the groups accumulate in order)."""
+        B, H, W = self.B, self.H, self.W
+        if not self.groups:  # no cutout: a zero adjoint
+            if not accumulate:
+                g.zero_()
+            return
+        row = d_out.element_size() * 3 * cs * cs * B
+        most = max(k1 - k0 for k0, k1 in self.groups)
+        scratch = th.empty(max(1, self.lib.cgd_cutouts_aug_scratch_floats(B, H, W, most)), device=d_out.device)
+        for k0, k1 in self.groups:
+            ctx.check(self.lib.cgd_cutouts_aug_bwd(ctx.h, d_out.data_ptr() + k0 * row, self.geo[k0].data_ptr(), self.params[k0].data_ptr(),
+                                                   g.data_ptr(), scratch.data_ptr(), B, H, W, k1 - k0, cs, layout, patch,
+                                                   int(bool(accumulate) or k0 > 0), ctx.stream()))
 
 
 class MakeCutouts(th.nn.Module):
     """Drop-in for cgd.modules.MakeCutouts (modules.py:5-66): same constructor, forward(input, use_cache,
     num_cutouts_override) and cache_coordinates(side_x, side_y); the crop+pool runs in one HIP kernel.
     `use_augs=True` (Python API only: the reference CLI hard-codes False, cgd.py:402) applies the reference's augmentation
-    pipeline to every crop before pooling; that path is plain differentiable torch ops (`reference_augs`), not a HIP kernel."""
+    pipeline to every crop before pooling: on a GPU input in the cutaug HIP kernels (crop + augment + pool in one launch, a
+    deterministic gather-form adjoint as the autograd backward), on a CPU input as plain differentiable torch ops
+    (`augmented`, the `reference_augs` restatement)."""
 
     def __init__(self, cut_size, num_cutouts, cutout_size_power=1.0, use_augs=False, ctx=None):
         super().__init__()
@@ -143,10 +273,15 @@ class MakeCutouts(th.nn.Module):
         _, _, H, W = input.shape
         coords = self.draw(H, W, use_cache, num_cutouts_override)  # (side_x, side_y) = (H, W): reference naming
         self.last_coords = coords
-        if self.augs is not None:
+        if self.augs is not None and input.device.type != "cuda":
             return self.augmented(input, coords)
         if self.ctx is None:
             self.ctx = L.Context(input.device.index or 0)
+        if self.augs is not None:
+            aug = _AugLaunch(self.ctx.lib, coords, input.shape[0], H, W, input.device)
+            if input.requires_grad and th.is_grad_enabled():
+                return _AugCutoutsFunction.apply(input, self, aug)
+            return self._aug_pool(input, aug)
         geo = th.tensor(crop_geometry(coords, H, W), dtype=th.int32, device=input.device)
         if input.requires_grad and th.is_grad_enabled():
             return _CutoutsFunction.apply(input, self, geo, len(coords))
@@ -170,6 +305,36 @@ class MakeCutouts(th.nn.Module):
         mean = th.tensor(CLIP_MEAN, device=input.device).view(1, 3, 1, 1)
         std = th.tensor(CLIP_STD, device=input.device).view(1, 3, 1, 1)
         return out * std + mean
+
+
+    def _aug_pool(self, input, aug):
+        """The augmented cutouts of `input` (B,3,H,W in [0,1]) through cgd_cutouts_aug_fwd, not normalised (like _pool)."""
+        B = input.shape[0]
+        x_pm1 = (input.detach().float() * 2 - 1).contiguous()
+        out = th.empty((len(aug.geo_list) * B, 3, self.cut_size, self.cut_size), device=input.device, dtype=th.float32)
+        aug.forward(self.ctx, x_pm1, out, self.cut_size, 0, 0)
+        mean = th.tensor(CLIP_MEAN, device=input.device).view(1, 3, 1, 1)
+        std = th.tensor(CLIP_STD, device=input.device).view(1, 3, 1, 1)
+        return out * std + mean
+
+
+class _AugCutoutsFunction(th.autograd.Function):
+    """MakeCutouts(use_augs=True).forward on a GPU input as an autograd node; its backward is cgd_cutouts_aug_bwd."""
+
+    @staticmethod
+    def forward(ctx, input, mk, aug):
+        ctx.mk, ctx.aug, ctx.in_shape = mk, aug, tuple(input.shape)
+        return mk._aug_pool(input, aug)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        mk = ctx.mk
+        # as in _CutoutsFunction: the kernel's convention is out = (pool(aug((x+1)/2)) - mean) / std
+        std = th.tensor(CLIP_STD, device=d_out.device).view(1, 3, 1, 1)
+        d = (d_out.float() * std).contiguous()
+        g = th.empty(ctx.in_shape, device=d_out.device, dtype=th.float32)
+        ctx.aug.backward(mk.ctx, d, g, mk.cut_size, 0, 0, accumulate=False)
+        return g * 2, None, None
 
 
 class _CutoutsFunction(th.autograd.Function):
@@ -390,9 +555,42 @@ class ClipGuidance:
         return g
 
     def _clip_leg_with_augs(self, x_in, coords, wm, gclip, clip_part, accumulate):
-        """`use_augs=True`: the augmentations sit between the crop and the pool, so the closed-form cutout adjoint does not
-        apply; this leg follows the reference recipe (cgd.py:190-204) with torch autograd — crop / augment / pool / normalise in
-        torch, the CLIP tower as the autograd node over cgd_*_forward / _dgrad — and hands d(CLIP loss)/d x_in to the native chain."""
+        """`use_augs=True`: the augmentations sit between the crop and the pool.  Per tower, in tower order, with fresh parameter
+        draws per tower: augmented cutouts (cgd_cutouts_aug_fwd, patch rows for ViT towers, images for ResNet towers) -> tower
+        forward -> spherical loss (per-row partials into clip_part) -> tower dgrad -> the augmented cutouts' gather-form adjoint
+        (cgd_cutouts_aug_bwd) into gclip.  _clip_leg_with_augs_torch is the same leg in torch ops with autograd."""
+        ctx, lib = self.ctx, self.ctx.lib
+        B, _, H, W = x_in.shape
+        dev = x_in.device
+        s = ctx.stream()
+        cutn = len(coords)
+        N = cutn * B
+        acc = accumulate
+        for k, (tower, targets) in enumerate(zip(self.towers, self.targets_list)):
+            aug = _AugLaunch(lib, coords, B, H, W, dev)
+            cs, patch = tower.input_resolution, tower.patch
+            if patch:
+                gsz = cs // patch
+                clip_in = self._b(f"patches{k}", (N * gsz * gsz, 3 * patch * patch), dev)
+                layout = 1
+            else:
+                clip_in = self._b(f"cut_images{k}", (N, 3, cs, cs), dev)
+                layout = 0
+            aug.forward(ctx, x_in, clip_in, cs, layout, patch)
+            emb = tower.encode_image(clip_in, layout=layout, n=N, out=self._b(f"emb{k}", (N, tower.out_dim), dev))
+            demb = self._b(f"demb{k}", (N, tower.out_dim), dev)
+            ctx.check(lib.cgd_spherical_loss(ctx.h, emb.data_ptr(), targets.data_ptr(), wm.data_ptr(), demb.data_ptr(),
+                                             clip_part[k * N:].data_ptr(), cutn, B, targets.shape[0], tower.out_dim, self.cgs, s))
+            dclip_in = tower.dgrad(demb, self._b(f"dclip_in{k}", tuple(clip_in.shape), dev))
+            aug.backward(ctx, dclip_in, gclip, cs, layout, patch, acc)
+            acc = 1
+            if k == 0:
+                self.emb = emb
+
+    def _clip_leg_with_augs_torch(self, x_in, coords, wm, gclip, clip_part, accumulate):
+        """The torch restatement of _clip_leg_with_augs (the equivalence reference of the tests): it follows the reference recipe
+        (cgd.py:190-204) with torch autograd — crop / augment / pool / normalise in torch, the CLIP tower as the autograd node over
+        cgd_*_forward / _dgrad — and hands d(CLIP loss)/d x_in to the native chain.  Same draws, in the same order, as the native leg."""
         from .nets import EncodeImageFunction
         B = x_in.shape[0]
         mean = th.tensor(CLIP_MEAN, device=x_in.device).view(1, 3, 1, 1)

@@ -185,6 +185,28 @@ int cgd_cutouts_fwd(cgd_ctx* ctx, const float* x_in, const int32_t* coords, floa
 int cgd_cutouts_bwd(cgd_ctx* ctx, const float* d_out, const int32_t* coords, float* g_in, int B, int H, int W, int cutn,
                     int cut_size, int layout, int patch, int accumulate, void* stream);
 
+/* ---- augmented cutouts (`use_augs`, the reference's modules.py:13-24 between the crop and the pool): per cutout k and sample b, in [0,1]
+ *      space, z1 = flip((x_in crop + 1) / 2) + n1; z2 = nearest affine(z1) + n2; z3 = (bilinear perspective(z2) or z2) + n3;
+ *      z4 = (3-channel grayscale(z3) or z3) + n4; out = (adaptive_avg_pool(z4, cut_size) - mean) / std, layouts as cgd_cutouts_fwd.
+ *      Resampling fills 0 in [0,1] space; source coordinates follow grid_sample(align_corners=False) in float32 (nearest: half to even).
+ *      params: device float [cutn][16] per cutout:
+ *        [0] flip (1: flip along W)   [1] float32(cos a)   [2] float32(sin a)   [3] tx   [4] ty   (a = rotation angle, clockwise)
+ *        [5] perspective (1: on)      [6..13] float32 homography coefficients c0..c7 (output pixel centre -> input, as torchvision's
+ *                                             perspective coefficients)       [14] grayscale (1: on)   [15] unused (0)
+ *      noise: device float or NULL (no noise); noise_off: device int64 [cutn], float offset into `noise` of cutout k's four
+ *      consecutive (B,3,h,w) planes n1..n4 (h, w = the crop's extent).  The adjoint is deterministic (gather form, no atomics) and
+ *      needs `scratch` of cgd_cutouts_aug_scratch_floats(B, H, W, cutn) floats. ---- */
+int cgd_cutouts_aug_fwd(cgd_ctx* ctx, const float* x_in, const int32_t* coords, const float* params, const float* noise,
+                        const int64_t* noise_off, float* out, int B, int H, int W, int cutn, int cut_size, int layout, int patch,
+                        void* stream);
+int cgd_cutouts_aug_bwd(cgd_ctx* ctx, const float* d_out, const int32_t* coords, const float* params, float* g_in, float* scratch, int B,
+                        int H, int W, int cutn, int cut_size, int layout, int patch, int accumulate, void* stream);
+int64_t cgd_cutouts_aug_scratch_floats(int B, int H, int W, int cutn); /* host-only */
+/* host-only, test support: for every output pixel p = i*w + j of an h x w crop with the HOST record `params` (16 floats), the affine's
+ * nearest source index affine_src[p] (-1: fill) and the perspective's bilinear taps persp_idx[4p..4p+3] (nw, ne, sw, se; -1: fill) and
+ * weights persp_w[4p..4p+3] (0 for a fill tap), whatever the record's flags say */
+int cgd_op_aug_sample_map(const float* params, int h, int w, int32_t* affine_src, int32_t* persp_idx, float* persp_w);
+
 /* ---- losses.spherical_dist_loss (cgd/losses.py:10-14) weighted as at cgd.py:196-204, with its gradient.
  *      emb (cutn*B, D) row = cut*B+b; targets_n (P, D) L2-normalised; weights (B, P) dense per-sample prompt
  *      weights; d_emb (cutn*B, D); loss_part (cutn*B) partial losses (sum = 'CLIP Loss'). ---- */

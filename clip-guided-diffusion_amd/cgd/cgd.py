@@ -6,6 +6,7 @@ of `main` (:286-358) — while every per-timestep computation runs through the M
 (UNet / CLIP tower handles, `ClipGuidance` cond_fn, `GuidedSampler` loops).
 """
 import argparse
+import functools
 import glob
 from pathlib import Path
 
@@ -123,7 +124,11 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
     if nranks > 1:
         cond_fn.shard = diffusion.shard = (mine, batch_size)
 
-    loop = diffusion.ddim_sample_loop_progressive if timestep_respacing.startswith("ddim") else diffusion.p_sample_loop_progressive
+    # "plmsN" (PLMS of order 2, spaced like "ddimN") extends what the reference accepts, like the "A+B" CLIP names
+    if timestep_respacing.startswith("plms"):
+        loop = functools.partial(diffusion.plms_sample_loop_progressive, order=2)
+    else:
+        loop = diffusion.ddim_sample_loop_progressive if timestep_respacing.startswith("ddim") else diffusion.p_sample_loop_progressive
     try:
         samples = loop(gd_model, (local_batch, 3, image_size + height_offset, image_size + width_offset), clip_denoised=False,
                        model_kwargs=model_kwargs, cond_fn=cond_fn, progress=progress, skip_timesteps=skip_timesteps, init_image=init_tensor,
@@ -204,7 +209,7 @@ _CLI_SPEC = f"""
 --seed -seed int 0 | RNG seed
 --save_frequency -freq int 1 | write a frame every N steps
 --diffusion_steps -steps int 1000 | length of the training schedule
---timestep_respacing -respace str 1000 | number of sampling steps ('250') or 'ddimN'
+--timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', or 'plmsN' for PLMS (e.g. -respace plms50)
 --num_cutouts -cutn int 16 | random cutouts shown to CLIP per step
 --cutout_power -cutpow float 1.0 | exponent of the cutout size distribution
 --clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, or 'A+B' to sum two towers

@@ -260,6 +260,14 @@ int cgd_sample_update(cgd_ctx* ctx, const float* x, const float* x0, const float
   CGD_NEED_CTX(ctx);
   return cgd_launch_sample_update(ctx, x, x0, mean, logvar, g, noise, scalars, sample, x0_out, B, H, W, *k, mode, S(stream));
 }
+int cgd_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eval, const float* x0, const float* g, const float* scalars,
+                         const float* noise, const float* const eps_hist[3], float* eps_out, float* sample, float* x0_out, int B, int H,
+                         int W, const cgd_step_coef* k, const cgd_step_coef* k_step, const cgd_multistep* m, void* stream) {
+  CGD_NEED_CTX(ctx);
+  if (!k || !m) return -3;
+  return cgd_launch_multistep_update(ctx, x, x_eval, x0, g, scalars, noise, eps_hist, eps_out, sample, x0_out, B, H, W, *k, k_step, *m,
+                                     S(stream));
+}
 
 // ---- single ops -------------------------------------------------------------------------------------------------
 int cgd_op_gemm(cgd_ctx* ctx, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias, const float* R,

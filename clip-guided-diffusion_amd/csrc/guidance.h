@@ -17,3 +17,7 @@ int cgd_launch_scalars(cgd_ctx* ctx, const float* clip_part, int n_clip, const f
 int cgd_launch_sample_update(cgd_ctx* ctx, const float* x, const float* x0, const float* mean, const float* logvar, const float* g,
                              const float* noise, const float* scalars, float* sample, float* x0_out, int B, int H, int W,
                              const StepCoef& k, int mode, hipStream_t s);
+// plms.hip
+int cgd_launch_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eval, const float* x0, const float* g, const float* scalars,
+                                const float* noise, const float* const* eps_hist, float* eps_out, float* sample, float* x0_out, int B,
+                                int H, int W, const StepCoef& k, const StepCoef* k_step, const cgd_multistep& m, hipStream_t s);

@@ -25,9 +25,10 @@ def named_beta_schedule(name, steps):
 
 
 def space_timesteps(num_timesteps, spec):
-    """'ddimN' -> fixed integer stride with exactly N steps; 'a,b,c' -> per-section even spacing (rounded)."""
+    """'ddimN' (and 'plmsN', spaced the same way) -> fixed integer stride with exactly N steps; 'a,b,c' -> per-section even
+    spacing (rounded)."""
     if isinstance(spec, str):
-        if spec.startswith("ddim"):
+        if spec.startswith(("ddim", "plms")):
             want = int(spec[4:])
             for stride in range(1, num_timesteps):
                 if len(range(0, num_timesteps, stride)) == want:

@@ -46,6 +46,11 @@ class StepCoef(C.Structure):
     ]
 
 
+class Multistep(C.Structure):
+    """cgd_multistep: phase 0 Adams-Bashforth, 1 start predictor, 2 start corrector, 3 DDIM with eta"""
+    _fields_ = [("phase", i32), ("order", i32), ("sigma", f32), ("dir", f32)]
+
+
 MANIFEST_CB = C.CFUNCTYPE(None, C.c_char_p, i64, vp)
 
 # name -> (restype, argtypes).  Pointers to device memory are passed as integers (tensor.data_ptr()).
@@ -125,6 +130,8 @@ _SIGS = {
     "cgd_grad_finish": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "cgd_scalars": (i32, [vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp]),
     "cgd_sample_update": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), i32, vp]),
+    "cgd_multistep_update": (i32, [vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef),
+                                    C.POINTER(StepCoef), C.POINTER(Multistep), vp]),
     "cgd_op_gemm": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
     "cgd_op_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
     "cgd_op_pack_conv3x3_frag": (i32, [vp, vp, vp, i32, i32, i32, vp]),

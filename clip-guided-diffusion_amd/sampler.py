@@ -6,7 +6,11 @@
 Per step: UNet forward (C ABI) -> p_mean_variance tail + blend (HIP) -> noise draw -> cond_fn -> update (HIP).
 With a `ClipGuidance` cond_fn everything stays native; any other Python callable gets the reference semantics
 through autograd Functions whose forward/backward call the same C ABI (`UNetFunction`).
+PLMS (`plms_sample_loop_progressive`, from the fork's history) and DDIM with eta > 0 reuse the same guided evaluation and finish
+it with one cgd_multistep_update launch per evaluation; PLMS draws no per-step noise.
 """
+import ctypes as C
+import math
 import os
 
 import torch as th
@@ -107,7 +111,9 @@ class GuidedSampler:
         return th.randn((gb,) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype)[idx].contiguous()
 
     # ---- one step -------------------------------------------------------------------------------------
-    def _step(self, model, x, i, cond_fn, model_kwargs, noise, mode, bufs, ahead=None):
+    def _evaluate(self, model, x, i, cond_fn, model_kwargs, noise, bufs, ahead=None, draw_noise=True):
+        """One guided evaluation at (x, i): UNet forward -> p_mean_variance tail + blend -> (noise draw) -> cond_fn.  Returns the pieces
+        the update kernels read; nothing of the update itself."""
         ctx, lib = self.ctx, self.ctx.lib
         B, _, H, W = x.shape
         dev = x.device
@@ -130,7 +136,7 @@ class GuidedSampler:
             return t
 
         x0, mean, logvar, xin = (buf(n, (B, 3, H, W)) for n in ("x0", "mean", "logvar", "xin"))
-        sample, x0_out = th.empty_like(x), th.empty_like(x)
+        scal = None
         if cond_fn is None or native:
             if ahead is not None:
                 # the embedding head of this step ran ahead on the side stream (EmbedAhead): wait for it, run the rest of the model
@@ -139,12 +145,10 @@ class GuidedSampler:
                 out6 = model.forward(x, ts, y, out=buf("out6", (B, 6, H, W)))
             ctx.check(lib.cgd_pmv_blend(ctx.h, x.data_ptr(), out6.data_ptr(), x0.data_ptr(), mean.data_ptr(), logvar.data_ptr(),
                                         xin.data_ptr(), B, H, W, coef, s))
-            if noise is None:
+            if noise is None and draw_noise:
                 noise = self._draw_like(x)  # drawn before cond_fn, as in p_sample_with_grad
             g = cond_fn.native(x, x0, xin, coef) if native else None
             scal = cond_fn.scalars if (native and g is not None and cond_fn.use_magnitude) else None
-            ctx.check(lib.cgd_sample_update(ctx.h, x.data_ptr(), x0.data_ptr(), mean.data_ptr(), logvar.data_ptr(), L.ptr(g),
-                                            noise.data_ptr(), L.ptr(scal), sample.data_ptr(), x0_out.data_ptr(), B, H, W, coef, mode, s))
         else:
             # generic plugin path: reference semantics via autograd over the C-ABI UNet node
             with th.enable_grad():
@@ -155,25 +159,91 @@ class GuidedSampler:
                 lv = frac * coef.max_log + (1 - frac) * coef.min_log
                 p0 = coef.sqrt_recip * xr - coef.sqrt_recipm1 * eps
                 mu = coef.coef1 * p0 + coef.coef2 * xr
-                if noise is None:
+                if noise is None and draw_noise:
                     noise = self._draw_like(x)
                 t_idx = th.full((B,), i, device=dev, dtype=th.long)
                 p = {"mean": mu, "variance": th.exp(lv), "log_variance": lv, "pred_xstart": p0}
                 g = cond_fn(xr, t_idx, p, **(model_kwargs or {}))
             g = g.detach().float().contiguous()
             x0.copy_(p0.detach()); mean.copy_(mu.detach()); logvar.copy_(lv.detach())
-            ctx.check(lib.cgd_sample_update(ctx.h, x.data_ptr(), x0.data_ptr(), mean.data_ptr(), logvar.data_ptr(), g.data_ptr(),
-                                            noise.data_ptr(), None, sample.data_ptr(), x0_out.data_ptr(), B, H, W, coef, mode, s))
-        bufs["_keep"] = (noise, g, ts)
+        return {"x0": x0, "mean": mean, "logvar": logvar, "g": g, "scal": scal, "noise": noise, "coef": coef, "ts": ts,
+                "fac_index": fac_index}
+
+    def _step(self, model, x, i, cond_fn, model_kwargs, noise, mode, bufs, ahead=None, eta=0.0):
+        """One step of the p_sample (mode 0) or DDIM (mode 1) loop.  DDIM with eta > 0 runs its update through
+        cgd_multistep_update (phase 3); eta == 0 keeps cgd_sample_update mode 1."""
+        ctx, lib = self.ctx, self.ctx.lib
+        B, _, H, W = x.shape
+        ev = self._evaluate(model, x, i, cond_fn, model_kwargs, noise, bufs, ahead)
+        noise, g, coef = ev["noise"], ev["g"], ev["coef"]
+        sample, x0_out = th.empty_like(x), th.empty_like(x)
+        if eta:
+            ab, abp = float(self.tables.alphas_cumprod[i]), float(self.tables.alphas_cumprod_prev[i])
+            sigma = eta * math.sqrt((1 - abp) / (1 - ab)) * math.sqrt(1 - ab / abp)
+            m = L.Multistep(3, 0, sigma, math.sqrt(max(0.0, 1 - abp - sigma * sigma)))
+            ctx.check(lib.cgd_multistep_update(ctx.h, x.data_ptr(), None, ev["x0"].data_ptr(), L.ptr(g), L.ptr(ev["scal"]),
+                                               noise.data_ptr(), None, None, sample.data_ptr(), x0_out.data_ptr(), B, H, W, coef, None,
+                                               m, ctx.stream()))
+        else:
+            ctx.check(lib.cgd_sample_update(ctx.h, x.data_ptr(), ev["x0"].data_ptr(), ev["mean"].data_ptr(), ev["logvar"].data_ptr(),
+                                            L.ptr(g), noise.data_ptr(), L.ptr(ev["scal"]), sample.data_ptr(), x0_out.data_ptr(), B, H,
+                                            W, coef, mode, ctx.stream()))
+        bufs["_keep"] = (noise, g, ev["ts"])
+        return {"sample": sample, "pred_xstart": x0_out}
+
+    def _plms_step(self, model, x, i, cond_fn, model_kwargs, bufs, st):
+        """One PLMS step (plms_sample of the guided_diffusion fork).  `st`: {'order', 'old_eps': history buffers (oldest first),
+        'free': spare buffers}.  The history rotates by pointer: the buffer dropped from the front is the next step's eps_out."""
+        ctx, lib = self.ctx, self.ctx.lib
+        B, _, H, W = x.shape
+        s = ctx.stream()
+        order, old = st["order"], st["old_eps"]
+        eps_new = st["free"].pop() if st["free"] else th.empty_like(x)
+        sample, x0_out = th.empty_like(x), th.empty_like(x)
+        ev = self._evaluate(model, x, i, cond_fn, model_kwargs, None, bufs, draw_noise=False)
+        g = ev["g"]
+        if order > 1 and not old:
+            # start step, pseudo improved Euler: predictor at t, a second guided evaluation at (predictor, t-1), corrector
+            xp = bufs.get("_plms_xp")
+            if xp is None or xp.shape != x.shape or xp.device != x.device:
+                xp = bufs["_plms_xp"] = th.empty_like(x)
+            ctx.check(lib.cgd_multistep_update(ctx.h, x.data_ptr(), None, ev["x0"].data_ptr(), L.ptr(g), L.ptr(ev["scal"]), None, None,
+                                               eps_new.data_ptr(), xp.data_ptr(), x0_out.data_ptr(), B, H, W, ev["coef"], None,
+                                               L.Multistep(1, 0, 0.0, 0.0), s))
+            old.append(eps_new)
+            ev2 = self._evaluate(model, xp, i - 1, cond_fn, model_kwargs, None, bufs, draw_noise=False)
+            hist = (C.c_void_p * 3)(eps_new.data_ptr(), None, None)
+            k_t = self.tables.step_coef(i, ev["fac_index"])
+            ctx.check(lib.cgd_multistep_update(ctx.h, x.data_ptr(), xp.data_ptr(), ev2["x0"].data_ptr(), L.ptr(ev2["g"]),
+                                               L.ptr(ev2["scal"]), None, hist, None, sample.data_ptr(), None, B, H, W, ev2["coef"], k_t,
+                                               L.Multistep(2, 0, 0.0, 0.0), s))
+            keep = (g, ev2["g"], ev["ts"], ev2["ts"], xp)
+        else:
+            # Adams-Bashforth of min(order, history + 1) terms, the newest history entry first
+            k = min(order, len(old) + 1)
+            prev = [old[-1 - j].data_ptr() if j < len(old) else None for j in range(3)]
+            ctx.check(lib.cgd_multistep_update(ctx.h, x.data_ptr(), None, ev["x0"].data_ptr(), L.ptr(g), L.ptr(ev["scal"]), None,
+                                               (C.c_void_p * 3)(*prev), eps_new.data_ptr(), sample.data_ptr(), x0_out.data_ptr(), B, H, W,
+                                               ev["coef"], None, L.Multistep(0, k, 0.0, 0.0), s))
+            old.append(eps_new)
+            keep = (g, ev["ts"])
+        if len(old) >= order:
+            st["free"].append(old.pop(0))
+        bufs["_keep"] = keep
         return {"sample": sample, "pred_xstart": x0_out}
 
     # ---- loops ------------------------------------------------------------------------------------------
-    def _loop(self, mode, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-              randomize_class, cond_fn_with_grad):
+    @staticmethod
+    def _check_guards(clip_denoised, cond_fn, cond_fn_with_grad):
         if clip_denoised:
             raise NotImplementedError("the reference samples with clip_denoised=False (cgd.py:253)")
         if cond_fn is not None and not cond_fn_with_grad:
             raise NotImplementedError("the reference passes cond_fn_with_grad=True (cgd.py:260)")
+
+    def _loop(self, mode, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
+              randomize_class, cond_fn_with_grad, eta=0.0, plms_order=None):
+        """mode 0 p_sample, 1 DDIM (eta > 0: stochastic DDIM), 2 PLMS of order `plms_order` (no per-step noise)."""
+        self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
         device = th.device(device or f"cuda:{self.ctx.device}")
         tape = self.tape
         if noise is not None:
@@ -211,16 +281,25 @@ class GuidedSampler:
 
         draw_y.n = 0
         rand_y = bool(randomize_class and "y" in model_kwargs)
-        ahead = EmbedAhead.create(self, model, cond_fn, img, indices)
+        # PLMS: its start step evaluates the model twice, EmbedAhead's one-embedding-per-step choreography does not apply (off)
+        ahead = EmbedAhead.create(self, model, cond_fn, img, indices) if mode != 2 else None
+        plms = {"order": plms_order, "old_eps": [], "free": []} if mode == 2 else None
         for n, i in enumerate(it):
             if rand_y and (ahead is None or n == 0):
                 draw_y.n = n
                 model_kwargs["y"] = draw_y()
             if ahead is not None and n == 0:
                 ahead.launch(model, 0, model_kwargs.get("y"))
+            if plms is not None:
+                with th.no_grad():
+                    out = self._plms_step(model, img, i, cond_fn, model_kwargs, bufs, plms)
+                yield out
+                img = out["sample"]
+                continue
             step_noise = tape["noise"][n].to(device).float().contiguous() if tape is not None else None
             with th.no_grad():
-                out = self._step(model, img, i, cond_fn, model_kwargs, step_noise, mode, bufs, *((ahead,) if ahead is not None else ()))
+                out = self._step(model, img, i, cond_fn, model_kwargs, step_noise, mode, bufs, *((ahead,) if ahead is not None else ()),
+                                 **({"eta": eta} if eta else {}))
             if ahead is not None and tape is not None and rand_y and n + 1 >= len(tape["y"]):
                 ahead = None  # a replay tape shorter than the schedule (tests that run a few steps): the remaining steps run in line
             if ahead is not None and n + 1 < len(indices):
@@ -243,7 +322,25 @@ class GuidedSampler:
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None,
                                      randomize_class=False, cond_fn_with_grad=False):
-        if eta != 0.0:
-            raise NotImplementedError("the reference never passes eta (DDIM eta = 0)")
+        """eta == 0 (what the reference passes): cgd_sample_update mode 1.  eta > 0: ddim_sample_with_grad's sigma term with the
+        per-step noise draw of this loop, through cgd_multistep_update."""
+        eta = float(eta)
+        if not eta >= 0.0:
+            raise ValueError(f"eta must be >= 0, got {eta}")
         return self._loop(1, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad)
+                          randomize_class, cond_fn_with_grad, eta=eta)
+
+    def plms_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                     model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
+                                     randomize_class=False, cond_fn_with_grad=False, order=2):
+        """PLMS (pseudo linear multistep, Liu et al., ICLR 2022) as the guided_diffusion fork's `plms_sample_loop_progressive`:
+        a first step of pseudo improved Euler (two guided evaluations, at t and at t-1) when order > 1, Adams-Bashforth of up to
+        `order` eps terms afterwards.  No per-step noise.  A schedule of a single step with order > 1 would evaluate at t = -1 and is
+        refused (the fork indexes its tables with -1 there)."""
+        if isinstance(order, bool) or not isinstance(order, int) or not 1 <= order <= 4:
+            raise ValueError(f"order is invalid (should be int from 1-4): {order!r}")
+        self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
+        if order > 1 and self.num_timesteps - skip_timesteps < 2:
+            raise ValueError(f"PLMS of order {order} needs at least two timesteps: its first step also evaluates at t - 1")
+        return self._loop(2, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
+                          randomize_class, cond_fn_with_grad, plms_order=order)

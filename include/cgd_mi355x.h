@@ -249,6 +249,31 @@ int cgd_sample_update(cgd_ctx* ctx, const float* x, const float* pred_xstart, co
                       const float* g, const float* noise, const float* scalars, float* sample, float* pred_xstart_out, int B, int H,
                       int W, const cgd_step_coef* k, int mode, void* stream);
 
+/* ---- multistep samplers: PLMS (guided_diffusion's plms_sample, pseudo linear multistep of Liu et al., ICLR 2022) and DDIM with
+ *      eta > 0 (ddim_sample_with_grad's sigma term).  One call = the whole update after one guided evaluation at (x_eval, k):
+ *        eps0 = (a x_eval - pred_xstart) / b ; eps1 = eps0 - sqrt(1-abar) g ; x0c = a x_eval - b eps1 ; eps = (a x_eval - x0c) / b
+ *      (a = sqrt_recip, b = sqrt_recipm1 of k; g scaled by scalars[7] when scalars is given, as in cgd_sample_update), then per phase:
+ *        0 Adams-Bashforth: eps_out = eps; eps' = AB_order(eps, eps_hist[0] (newest), eps_hist[1], eps_hist[2]) with the weights
+ *          1 | (3, -1)/2 | (23, -16, 5)/12 | (55, -59, 37, -9)/24; x0' = a x - b eps'; mean = sqrt(abar_prev) x0' + sqrt(1-abar_prev) eps';
+ *          sample = t != 0 ? mean : x0c; pred_xstart_out = pred_xstart (the unconditioned prediction)
+ *        1 start-step predictor: eps_out = eps; sample = sqrt(abar_prev) x0c + sqrt(1-abar_prev) eps (the input of the corrector's
+ *          evaluation at t-1); pred_xstart_out = pred_xstart
+ *        2 start-step corrector (the evaluation ran at x_eval = the predictor, k = coefficients of t-1): eps' = (eps_hist[0] + eps) / 2,
+ *          then mean as in phase 0 from x with k_step (coefficients of t, t != 0 required) -> sample; eps_out and pred_xstart_out unused
+ *        3 DDIM with eta: sample = sqrt(abar_prev) x0c + dir eps + [t != 0] sigma noise; pred_xstart_out = pred_xstart
+ *      x_eval may be NULL (= x) and k_step NULL (= k) except in phase 2.  Returns -2 (cgd_last_error) for a phase outside 0..3, an order
+ *      outside 1..4 in phase 0, or a missing buffer the phase needs. ---- */
+typedef struct cgd_multistep {
+  int phase;   /* 0 Adams-Bashforth, 1 start predictor, 2 start corrector, 3 DDIM with eta                          */
+  int order;   /* phase 0: terms combined, 1..4 (this evaluation's eps and order-1 history entries)               */
+  float sigma; /* phase 3: eta sqrt((1-abar_prev)/(1-abar)) sqrt(1 - abar/abar_prev)                                */
+  float dir;   /* phase 3: sqrt(1 - abar_prev - sigma^2), the coefficient of eps in the mean                        */
+} cgd_multistep;
+int cgd_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eval, const float* pred_xstart, const float* g,
+                         const float* scalars, const float* noise, const float* const eps_hist[3], float* eps_out, float* sample,
+                         float* pred_xstart_out, int B, int H, int W, const cgd_step_coef* k, const cgd_step_coef* k_step,
+                         const cgd_multistep* m, void* stream);
+
 /* ---- single ops, exported for parity tests and for user-supplied cond_fn plumbing ---- */
 /* C[M][N] = alpha * A[M][K] B[N][K]^T (+bias[N]) (+R[M][N]); conv3x3: A is NHWC (Bn,H,W,Cin), B = [N][9*Cin].
  * force_tile: 0 auto, 64 / 128 / 256 / 257 (+1000: two-deep prefetch) igemm tiles, 513 weight GEMM kernel (B re-packed per call),

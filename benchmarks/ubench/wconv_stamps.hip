@@ -4,7 +4,6 @@
 // issued, plus XCC_ID / HW_ID, so that the workgroups a CU runs back to back can be lined up.  One extra 8-byte store per chunk.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../include wconv_stamps.hip -o wconv_stamps
 // Usage: wconv_stamps H Cin N [gn 0|1] [nb 4|2|22] [reps] [csv|-] [unused] [residual 0|1]     (nb 22 = 8-row tile x two channel blocks per wavefront)
-// -DCGD_WCONV_EXP=<bits>: ablation builds (see wconv.hip), timing only
 #define CGD_WCONV_STAMPS 1
 #include "../../clip-guided-diffusion_amd/csrc/wconv.hip"
 
@@ -164,7 +163,6 @@ int main(int argc, char** argv) {
     starts.push_back(x.start);
     ends.push_back(x.end);
   }
-  if (CGD_WCONV_EXP) printf("ABLATION %d (wrong results, timing only): ", CGD_WCONV_EXP);
   printf("wconv_kernel<%s, %d>%s  %dx%d  %d -> %d : %d workgroups, %d chunks; %.1f us per launch (events over %d launches); clock %d kHz\n",
          gn ? "true" : "false", nb, res ? " + residual" : "", H, W, Cin, N, nwg, nchunk, ms * 1e3 / reps, reps, khz);
   printf("last launch, us from the first wavefront's entry: last entry %.1f, first exit %.1f, last exit %.1f\n", vmax(starts), vmin(ends), vmax(ends));

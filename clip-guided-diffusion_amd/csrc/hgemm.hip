@@ -70,7 +70,7 @@ struct HGemmParams {
   int lep;         // hgemm2, bf16x3: 1 = output block through LDS, whole-line stores / operand reads (ctx->hgemm_epi)
   int skip_group;  // hgemm2, one slice: drop the first row of every group of this many rows, write the rest compactly (GemmParams)
   int nt;      // kgemm_kernel: weight-fragment loads with the non-temporal policy
-  int nt_out;  // hgemm2 LDS epilogue: the output is larger than the L2 (non-temporal stores under CGD_HGEMM_NT)
+  int nt_out;  // unread (non-temporal output stores measured neutral, profiles/r6_ab_nt_more.txt); kept so later fields do not move
   int nmajor;  // tile order within the XCD-contiguous runs: 0 = M-tile major (an XCD owns row panels and streams all weights),
                // 1 = N-tile major (an XCD owns weight column panels, read from HBM once and kept in its 4 MB L2; the small
                // activation matrix is what every XCD re-reads): chosen when the weights are the larger operand (N >= M)
@@ -313,24 +313,11 @@ epilogue:
 //   * the loop body covers a whole period of ring base, LDS buffer and staging set (two 64-deep chunks = 8 k-steps = one turn of the ring in
 //     the shipped configuration), so every ring slot, LDS buffer and register set is a compile-time constant; a shorter tail follows;
 //   * A staging, conversion, barrier placement and the epilogue are those of hgemm_kernel.
-// Ablation switches for benchmarks/ubench/hgemm_stamps.hip ONLY (results become wrong; the library build never defines the macro): which element
-// of the chunk loop is the exposed latency?  bit 0: no weight-fragment loads inside the loop (the ring keeps its prologue contents), bit 1: no
-// activation patch loads / conversion / LDS writes inside the loop, bit 2: no barrier inside the loop, bit 3: no A-fragment LDS reads inside the loop
-#ifndef CGD_HGEMM_EXP
-#define CGD_HGEMM_EXP 0
-#endif
-// CGD_HGEMM_BUFLOAD = 1 (round 6): hgemm2_kernel fetches both operand streams with buffer loads (resource = the tensor, per-lane byte offset in a
-// register that never changes, the chunk / k-step offset in a scalar).  What it buys: (a) the prefetches that run past the end of a slice — the weight
-// ring is 7 k-steps ahead, the activation sets up to 3 chunks — used to re-read the slice's last fragments / last chunk on clamped indices (a 4-chunk
-// slice of a split-K ViT linear issued 7 patch loads for 4 useful ones through the L2 path that bounds this class); with a resource of ZERO records
-// they are out of range, return zeros and touch no memory — no branch in the scheduled region; (b) no 64-bit per-lane address arithmetic per load.
-#ifndef CGD_HGEMM_BUFLOAD
-#define CGD_HGEMM_BUFLOAD 1
-#endif
-// CGD_HGEMM_NT (A/B builds; measured neutral, profiles/r6_ab_nt_more.txt: default 0): outputs larger than the L2 (HGemmParams::nt_out, set by the launcher from M * N) are stored with the non-temporal policy
-#ifndef CGD_HGEMM_NT
-#define CGD_HGEMM_NT 0
-#endif
+// hgemm2_kernel fetches both operand streams with buffer loads (round 6; resource = the tensor, per-lane byte offset in a register that never
+// changes, the chunk / k-step offset in a scalar).  What it buys: (a) the prefetches that run past the end of a slice — the weight ring is 7 k-steps
+// ahead, the activation sets up to 3 chunks — used to re-read the slice's last fragments / last chunk on clamped indices (a 4-chunk slice of a
+// split-K ViT linear issued 7 patch loads for 4 useful ones through the L2 path that bounds this class); with a resource of ZERO records they are
+// out of range, return zeros and touch no memory — no branch in the scheduled region; (b) no 64-bit per-lane address arithmetic per load.
 typedef int hi32x4 __attribute__((ext_vector_type(4)));
 // neg = a wave-uniform integer: < 0 -> the load is wanted, >= 0 -> it is past the end of the slice (sign bit spread by a scalar shift: a bool select
 // would be lowered through v_cndmask and put the resource into vector registers, i.e. a readfirstlane loop around every load)
@@ -394,11 +381,9 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
     aoff[j] = (ok ? r : p.M - 1) * p.lda + c4 * 4;
     amask |= ok ? (1u << j) : 0u;
   }
-#if CGD_HGEMM_BUFLOAD
   int aoffb[NPS];  // byte offsets for the buffer loads; a row beyond M is out of range: zeros without a select
 #pragma unroll
   for (int j = 0; j < NPS; ++j) aoffb[j] = (amask >> j) & 1u ? aoff[j] * 4 : H_OOB;
-#endif
   int fro[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) fro[i] = (i * 32 + l31) * GPHW + hh * 8 + kg * GK;
@@ -413,12 +398,13 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
   const int nb0 = (n0 >> 5) + wn, nbN = p.N >> 5;
   const long bstride_nb = (long)(p.K >> 5) * 4 * 64;
   // this wavefront's k-steps in its own linear order t = 4 (chunk - c0) + j: k-step (chunk * KG + kg) * 4 + j of the packed weight block
+  // Unread, but kept: without it the compiler schedules the chunk loop differently and the kernel is no longer the measured build.
   const uint4* __restrict__ Bw0 = Bg + (long)(nb0 < nbN ? nb0 : nbN - 1) * bstride_nb + lane + (long)(c0 * KG + kg) * 4 * 128;
-  // (buffer loads) the wavefront's weight block as a scalar base: column block and K-group are the same for all its lanes
+  (void)Bw0;
+  // the wavefront's weight block as a scalar base: column block and K-group are the same for all its lanes
   const int wn_s = __builtin_amdgcn_readfirstlane(wn), kg_s = __builtin_amdgcn_readfirstlane(kg);
   const int nb0_s = (n0 >> 5) + wn_s;
   const uint4* __restrict__ Bwb = Bg + (long)(nb0_s < nbN ? nb0_s : nbN - 1) * bstride_nb + (long)(c0 * KG + kg_s) * 4 * 128;
-  (void)Bw0; (void)Bwb;
   const int t_last = (c1 - c0) * 4 - 1;
 
   f32x16 acc[NI];
@@ -430,8 +416,6 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
   if (c0 < c1) {
     constexpr int AHEAD = NSET + 1;  // set (C - c0) % NSET holds chunk C + 1 while chunk C runs and is refilled with chunk C + AHEAD
     f32x4 prs[NSET][NPS];
-    const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
-#if CGD_HGEMM_BUFLOAD
 #define H2_PATCH_LOAD(PR, CH)                                                                     \
   {                                                                                               \
     const int in_ = (CH) - c1; /* < 0: inside the slice */                                        \
@@ -439,18 +423,11 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
     _Pragma("unroll") for (int j = 0; j < NPS; ++j)                                               \
         PR[j] = __builtin_bit_cast(f32x4, h_buf_load16(Ag, in_, aoffb[j], so_, 0x80000000u));     \
   }
-#else
-#define H2_PATCH_LOAD(PR, CH)                                                                     \
-  {                                                                                               \
-    const float* __restrict__ Ac = Ag + (long)((CH) < c1 ? (CH) : c1 - 1) * GKW;                  \
-    _Pragma("unroll") for (int j = 0; j < NPS; ++j) PR[j] = *(const f32x4*)(Ac + aoff[j]);        \
-  }
-#endif
 #define H2_PATCH_STORE(PR, DSTB, J0, J1)                                                          \
   {                                                                                               \
     _Pragma("unroll") for (int j = J0; j < J1; ++j) {                                             \
       const int row = r0 + 16 * j;                                                                \
-      const f32x4 v = CGD_HGEMM_BUFLOAD ? PR[j] : ((amask >> j) & 1u ? PR[j] : z4);               \
+      const f32x4 v = PR[j];                                                                      \
       if constexpr (MODE == 1) {                                                                  \
         bf16x4 hi, lo;                                                                            \
         cgd_split_quad(v, hi, lo);                                                                \
@@ -468,7 +445,6 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
       if constexpr (MODE == 1) DST[i][1] = *(const bf16x8*)&(SRCB)[PLANE + fro[i] + (Q) * 16];    \
     }                                                                                             \
   }
-#if CGD_HGEMM_BUFLOAD
 #define H2_B_LOAD(DST, T)                                                                         \
   {                                                                                               \
     const int in_ = (T) - t_last - 1; /* < 0: inside the slice */                                 \
@@ -476,15 +452,6 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
     DST[0] = __builtin_bit_cast(uint4, h_buf_load16(Bwb, in_, lane * 16, so_));                   \
     if constexpr (MODE == 1) DST[1] = __builtin_bit_cast(uint4, h_buf_load16(Bwb, in_, lane * 16 + 1024, so_)); \
   }
-#else
-#define H2_B_LOAD(DST, T)                                                                         \
-  {                                                                                               \
-    const int t_ = (T) < t_last ? (T) : t_last;                                                   \
-    const uint4* q_ = Bw0 + (long)((t_ >> 2) * (4 * KG) + (t_ & 3)) * 128;                        \
-    DST[0] = q_[0];                                                                               \
-    if constexpr (MODE == 1) DST[1] = q_[64];                                                     \
-  }
-#endif
 #define H2_MFMA(AQ, BQ)                                                                           \
   {                                                                                               \
     if constexpr (MODE == 1) {                                                                    \
@@ -511,31 +478,27 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
   }
   // one 64-deep chunk: ring slots S .. S+3 (S = 0 or 4), LDS buffers CUR -> NXT, staging registers PR (they hold chunk C+1 on
   // entry and are refilled with chunk C+AHEAD once converted)
-#define X_B(...) do { if constexpr (!(CGD_HGEMM_EXP & 1)) { __VA_ARGS__; } } while (0)
-#define X_P(...) do { if constexpr (!(CGD_HGEMM_EXP & 2)) { __VA_ARGS__; } } while (0)
-#define X_S(...) do { if constexpr (!(CGD_HGEMM_EXP & 4)) { __VA_ARGS__; } } while (0)
-#define X_A(...) do { if constexpr (!(CGD_HGEMM_EXP & 8)) { __VA_ARGS__; } } while (0)
 #define H2_CHUNK(S, CUR, NXT, C, PR)                                                              \
   {                                                                                               \
     const int kq = ((C) - c0) * 4; /* this wavefront's linear k-step index */                     \
-    X_A(H2_A_LOAD(af[1], CUR, 1));                                                                     \
-    X_B(H2_B_LOAD(bq[((S) + 0 + DIST) % RING], kq + 0 + DIST));                                        \
+    H2_A_LOAD(af[1], CUR, 1);                                                                     \
+    H2_B_LOAD(bq[((S) + 0 + DIST) % RING], kq + 0 + DIST);                                        \
     H2_MFMA(af[0], bq[(S) + 0]);                                                                  \
     H2_INTERLEAVE();                                                                              \
-    X_A(H2_A_LOAD(af[0], CUR, 2));                                                                     \
-    X_B(H2_B_LOAD(bq[((S) + 1 + DIST) % RING], kq + 1 + DIST));                                        \
+    H2_A_LOAD(af[0], CUR, 2);                                                                     \
+    H2_B_LOAD(bq[((S) + 1 + DIST) % RING], kq + 1 + DIST);                                        \
     H2_MFMA(af[1], bq[(S) + 1]);                                                                  \
-    X_P(H2_PATCH_STORE(PR, NXT, 0, NPS / 2));                                                          \
+    H2_PATCH_STORE(PR, NXT, 0, NPS / 2);                                                          \
     H2_INTERLEAVE();                                                                              \
-    X_A(H2_A_LOAD(af[1], CUR, 3));                                                                     \
-    X_B(H2_B_LOAD(bq[((S) + 2 + DIST) % RING], kq + 2 + DIST));                                        \
+    H2_A_LOAD(af[1], CUR, 3);                                                                     \
+    H2_B_LOAD(bq[((S) + 2 + DIST) % RING], kq + 2 + DIST);                                        \
     H2_MFMA(af[0], bq[(S) + 2]);                                                                  \
-    X_P(H2_PATCH_STORE(PR, NXT, NPS / 2, NPS));                                                        \
+    H2_PATCH_STORE(PR, NXT, NPS / 2, NPS);                                                        \
     H2_INTERLEAVE();                                                                              \
-    X_P(H2_PATCH_LOAD(PR, (C) + AHEAD));                                                               \
-    X_S(__syncthreads()); /* NXT fully written; every wavefront has fetched its last fragments of CUR */ \
-    X_A(H2_A_LOAD(af[0], NXT, 0));                                                                     \
-    X_B(H2_B_LOAD(bq[((S) + 3 + DIST) % RING], kq + 3 + DIST));                                        \
+    H2_PATCH_LOAD(PR, (C) + AHEAD);                                                               \
+    __syncthreads(); /* NXT fully written; every wavefront has fetched its last fragments of CUR */ \
+    H2_A_LOAD(af[0], NXT, 0);                                                                     \
+    H2_B_LOAD(bq[((S) + 3 + DIST) % RING], kq + 3 + DIST);                                        \
     H2_MFMA(af[1], bq[(S) + 3]);                                                                  \
     H2_INTERLEAVE();                                                                              \
     H_STAMP_CHUNK(2 + ((C) - c0 < 26 ? (C) - c0 : 26));                                           \
@@ -575,10 +538,6 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
 #undef H2_MFMA
 #undef H2_INTERLEAVE
 #undef H2_CHUNK
-#undef X_B
-#undef X_P
-#undef X_S
-#undef X_A
   }
 
   H_STAMP(29);
@@ -685,7 +644,7 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
           o *= d;
         }
         if (ok[u]) {
-          if (CGD_HGEMM_NT && p.nt_out) __builtin_nontemporal_store(o, (f32x4*)&Cg[row[u] * p.ldc + col]); else *(f32x4*)&Cg[row[u] * p.ldc + col] = o;
+          *(f32x4*)&Cg[row[u] * p.ldc + col] = o;
           if (p.act_out) {  // second output: the activated tensor, same arithmetic as elem.hip act_f
             f32x4 a;
 #pragma unroll
@@ -787,20 +746,15 @@ __global__ __launch_bounds__(256) void kgemm_kernel(const float* __restrict__ Ag
   const int nks = p.K >> 4;                       // 16-deep k-steps
   const int mine = (nks - w + 3) >> 2;            // k-steps w, w + 4, ... of this wavefront
   const uint4* __restrict__ Bw = Bg + ((long)nb * nks) * (2 * 64) + lane;  // k-step kq: Bw[kq * 128] (hi), Bw[kq * 128 + 64] (lo)
-  long arow[NI];
-  bool aok[NI];
+  bool aok[NI];  // unread, but kept: without it the compiler schedules the k-step loop differently (no longer the measured build)
 #pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int r = m0 + 32 * i + l31;
-    aok[i] = r < p.M;
-    arow[i] = (long)(aok[i] ? r : p.M - 1) * p.lda + 8 * hh;
-  }
-  // (buffer loads) byte offset of the lane's row, no clamp: a row beyond M lies beyond the resource of M rows
+  for (int i = 0; i < NI; ++i) aok[i] = m0 + 32 * i + l31 < p.M;
+  (void)aok;
+  // byte offset of the lane's row for the buffer loads, no clamp: a row beyond M lies beyond the resource of M rows
   int aoffb[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) aoffb[i] = ((m0 + 32 * i + l31) * p.lda + 8 * hh) * 4;
   const unsigned arec = (unsigned)p.M * (unsigned)p.lda * 4u;
-  (void)aoffb; (void)arec;
   f32x16 acc[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i)
@@ -815,20 +769,15 @@ __global__ __launch_bounds__(256) void kgemm_kernel(const float* __restrict__ Ag
     bq[SLOT][0] = p.nt ? cgd_load_nt(Bw + (long)kq_ * 128) : Bw[(long)kq_ * 128];                 \
     if constexpr (MODE == 1) bq[SLOT][1] = p.nt ? cgd_load_nt(Bw + (long)kq_ * 128 + 64) : Bw[(long)kq_ * 128 + 64]; \
     _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                              \
-      if constexpr (CGD_HGEMM_BUFLOAD) { /* rows beyond M and k-steps beyond the wavefront's last: out of range, zeros, no memory access */ \
-        aq[SLOT][i][0] = __builtin_bit_cast(f32x4, h_buf_load16(Ag, (T) - mine, aoffb[i], 64 * kq_, arec));       \
-        aq[SLOT][i][1] = __builtin_bit_cast(f32x4, h_buf_load16(Ag, (T) - mine, aoffb[i] + 16, 64 * kq_, arec));  \
-      } else {                                                                                    \
-        aq[SLOT][i][0] = *(const f32x4*)(Ag + arow[i] + 16 * kq_);                                \
-        aq[SLOT][i][1] = *(const f32x4*)(Ag + arow[i] + 16 * kq_ + 4);                            \
-      }                                                                                           \
+      /* rows beyond M and k-steps beyond the wavefront's last: out of range, zeros, no memory access */                     \
+      aq[SLOT][i][0] = __builtin_bit_cast(f32x4, h_buf_load16(Ag, (T) - mine, aoffb[i], 64 * kq_, arec));         \
+      aq[SLOT][i][1] = __builtin_bit_cast(f32x4, h_buf_load16(Ag, (T) - mine, aoffb[i] + 16, 64 * kq_, arec));    \
     }                                                                                             \
   }
 #define KG_STEP(SLOT)                                                                             \
   {                                                                                               \
     _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                              \
-      const f32x4 a0 = (CGD_HGEMM_BUFLOAD || aok[i]) ? aq[SLOT][i][0] : f32x4{0.f, 0.f, 0.f, 0.f};  \
-      const f32x4 a1 = (CGD_HGEMM_BUFLOAD || aok[i]) ? aq[SLOT][i][1] : f32x4{0.f, 0.f, 0.f, 0.f};  \
+      const f32x4 a0 = aq[SLOT][i][0], a1 = aq[SLOT][i][1];                                       \
       bf16x8 ah, al;                                                                              \
       {                                                                                           \
         const float a8_[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};            \

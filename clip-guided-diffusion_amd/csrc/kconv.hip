@@ -76,17 +76,9 @@ __device__ __forceinline__ kf32x4 k_residual4(const kf32x4 v, const kbf16x4 hi) 
   return kf32x4{v.x - (float)hi[0], v.y - (float)hi[1], v.z - (float)hi[2], v.w - (float)hi[3]};
 }
 
-// CGD_KCONV_FINE = 1 (round 6): the conversion passes of the next patch run one per k-step slot instead of two in each of the first slots (the fused
-// GroupNorm + SiLU of a pass is 8 quarter-rate transcendentals per thread, about what the 6 MFMAs of a slot cover); 0 = the order of rounds 3-5
-#ifndef CGD_KCONV_FINE
-#define CGD_KCONV_FINE 1
-#endif
-// CGD_KCONV_BUFLOAD = 1 (round 6): the patch and weight-fragment prefetches are buffer loads (scalar chunk offset, per-lane offset in a register that
-// never changes); a prefetch past the end of the slice gets a resource of zero records — out of range, returns zeros, touches no memory — where the
-// global loads re-read the slice's last chunk on a clamped index.  One copy of the chunk body (what CGD_KCONV_PEEL needs eight of).
-#ifndef CGD_KCONV_BUFLOAD
-#define CGD_KCONV_BUFLOAD 1
-#endif
+// The patch and weight-fragment prefetches are buffer loads (round 6; scalar chunk offset, per-lane offset in a register that never changes): a
+// prefetch past the end of the slice gets a resource of zero records — out of range, returns zeros, touches no memory — where global loads would
+// re-read the slice's last chunk on a clamped index.  The NT instantiations keep global loads for the non-temporal weight stream.
 typedef int ki32x4 __attribute__((ext_vector_type(4)));
 // neg: wave-uniform, < 0 = wanted (hgemm.hip h_buf_load16: the scalar shift keeps the resource in scalar registers)
 // `records`: size of the resource when the load is wanted — lanes with voffset >= records read zeros (padding pixels carry the offset K_OOB)
@@ -97,12 +89,6 @@ __device__ __forceinline__ ki32x4 k_buf_load16(const void* base, int neg, int vo
   return __builtin_amdgcn_raw_buffer_load_b128(r, voffset, soffset, 0);
 }
 constexpr int K_OOB = (int)0x80000000;
-// CGD_KCONV_PEEL = 1 (round 6 experiment, default 0): the last two chunks of a slice run copies of the chunk body without the loads / conversions nobody
-// consumes (K_CHUNK) — what pays in wconv_kernel does not here: 162 -> 226 registers for the eight copies of the body and +0.03 ms per step in four
-// same-box pairs (profiles/r6_ab_kconv_peel.txt)
-#ifndef CGD_KCONV_PEEL
-#define CGD_KCONV_PEEL 0
-#endif
 // WR = weight-fragment register sets: 2 = the next chunk's fragments are fetched while a chunk is multiplied (rounds 3-4), 3 = TWO chunks ahead
 // NT = weight-fragment loads with the non-temporal policy (single-tile maps: every fragment is read by exactly one workgroup)
 template <int MODE, bool GN, int TW, int WR = 2, bool NT = false, int TH = KTH>
@@ -182,7 +168,7 @@ __global__ __launch_bounds__(256, TW == 8 ? 2 : 1) void kconv_kernel(const float
     c1 = min(nchunk, c0 + per);
   }
   const uint4* __restrict__ Bw0 = Bg + (long)nb * nchunk * (9 * 4 * 64) + lane;
-  constexpr bool BUFL = CGD_KCONV_BUFLOAD && !NT;  // operand prefetches as buffer loads (see k_buf_load16)
+  constexpr bool BUFL = !NT;  // operand prefetches as buffer loads (see k_buf_load16)
   int poffb[KNPASS];  // byte offsets of the patch slots; padding / beyond-the-patch slots are out of range (zeros without a select)
 #pragma unroll
   for (int j = 0; j < KNPASS; ++j) poffb[j] = poff[j] >= 0 ? poff[j] * 4 : K_OOB;
@@ -294,24 +280,21 @@ __global__ __launch_bounds__(256, TW == 8 ? 2 : 1) void kconv_kernel(const float
     // chunk C (ring set S, LDS buffer CUR): fetch patch C + 2 into staging set S, write patch C + 1 (staging set S ^ 1, fetched during
     // chunk C - 1; for the first chunk a harmless rewrite of what the prologue stored) into NXT, fetch the fragments of chunk C + 1
     // (BS = weight set of chunk C = (C - c0) % WR; the fragments of chunk C + WR - 1 go into set (BS + WR - 1) % WR)
-  // LP / SP / LB (compile-time 0 / 1): fetch patch C + 2 / convert and write patch C + 1 / fetch the fragments of chunk C + WR - 1.  Round 6
-  // (CGD_KCONV_PEEL): the last chunks of a slice switch off what has no consumer — they used to run everything on clamped chunk indices, i.e. a
-  // slice of n chunks fetched (n + 1) / n of its weight fragments through the CU's vector-memory path, which is what bounds this kernel
-#define K_CHUNK(S, CUR, NXT, C, BS, LP, SP, LB)                                                     \
+    // The conversion passes of the next patch run one per k-step slot (round 6; the fused GroupNorm + SiLU of a pass is 8 quarter-rate
+    // transcendentals per thread, about what the 6 MFMAs of a slot cover).  Every chunk runs the same body: peeling the last two chunks of a
+    // slice (no loads / conversions nobody consumes) took 162 -> 226 registers and +0.03 ms per step (profiles/r6_ab_kconv_peel.txt).
+#define K_CHUNK(S, CUR, NXT, C, BS)                                                                 \
   {                                                                                                 \
     const uint4* __restrict__ nbp = Bw0 + (long)((C) + WR - 1 < c1 ? (C) + WR - 1 : c1 - 1) * (9 * 4 * 64); \
-    if constexpr (LP) K_PATCH_LOAD(S, (C) + 2);                                                     \
+    K_PATCH_LOAD(S, (C) + 2);                                                                       \
     K_A_LOAD(af[0], CUR, 0);                                                                        \
     _Pragma("unroll") for (int k = 0; k < KNQ; ++k) {                                               \
       if (k + 1 < KNQ) K_A_LOAD(af[(k + 1) & 1], CUR, k + 1);                                       \
-      if constexpr (LB && BUFL) { K_B_LOAD_BUF(bq[((BS) + WR - 1) % WR][k], (C) + WR - 1, k); }     \
-      else if constexpr (LB) { K_B_LOAD(bq[((BS) + WR - 1) % WR][k], nbp, k); }                     \
+      if constexpr (BUFL) { K_B_LOAD_BUF(bq[((BS) + WR - 1) % WR][k], (C) + WR - 1, k); }           \
+      else { K_B_LOAD(bq[((BS) + WR - 1) % WR][k], nbp, k); }                                       \
       if (k < 4 || five) K_MFMA(af[k & 1], bq[BS][k]);                                              \
-      if constexpr (!(SP)) {                                                                        \
-      } else if constexpr (CGD_KCONV_FINE && TH == KTH) { /* round 6: the passes spread evenly over the k-step slots (4 passes: 1, 1, 1, 1, 0) */ \
+      if constexpr (TH == KTH) { /* the passes spread evenly over the k-step slots (4 passes: 1, 1, 1, 1, 0) */ \
         K_PATCH_STORE((S) ^ 1, NXT, (k * KNPASS + KNQ - 1) / KNQ, ((k + 1) * KNPASS + KNQ - 1) / KNQ); \
-      } else if constexpr (TH == KTH) {                                                             \
-        if (k < KNPASS / 2) K_PATCH_STORE((S) ^ 1, NXT, 2 * k, 2 * k + 2);                          \
       } else { /* 11 passes over the 5 k-step slots: 3, 3, 3, 2 */                                  \
         if (3 * k < KNPASS) K_PATCH_STORE((S) ^ 1, NXT, 3 * k, (3 * k + 3 < KNPASS ? 3 * k + 3 : KNPASS)); \
       }                                                                                             \
@@ -329,31 +312,13 @@ __global__ __launch_bounds__(256, TW == 8 ? 2 : 1) void kconv_kernel(const float
     // the loop body covers one common period P of the LDS buffer / staging set (2) and the weight set (WR): every index is a compile-time constant
     constexpr int P = WR == 3 ? 6 : 2;
     int c = c0;
-    if constexpr (WR == 2 && TW == 8 && CGD_KCONV_PEEL) {  // (the 8 x 8 tile: the other tiles have no registers for the extra copies)
-      for (; c + 3 < c1; c += 2) {  // both chunks of the pair have two successors
-        K_CHUNK(0, buf0, buf1, c, 0, 1, 1, 1);
-        K_CHUNK(1, buf1, buf0, c + 1, 1, 1, 1, 1);
-      }
-      const int left = c1 - c;  // 1, 2 or 3 chunks: ... full, penultimate (nothing to fetch two chunks ahead), last (nothing to prepare at all)
-      if (left == 3) {
-        K_CHUNK(0, buf0, buf1, c, 0, 1, 1, 1);
-        K_CHUNK(1, buf1, buf0, c + 1, 1, 0, 1, 1);
-        K_CHUNK(0, buf0, buf1, c + 2, 0, 0, 0, 0);
-      } else if (left == 2) {
-        K_CHUNK(0, buf0, buf1, c, 0, 0, 1, 1);
-        K_CHUNK(1, buf1, buf0, c + 1, 1, 0, 0, 0);
-      } else {
-        K_CHUNK(0, buf0, buf1, c, 0, 0, 0, 0);
-      }
-    } else {
-      for (; c + P - 1 < c1; c += P) {
+    for (; c + P - 1 < c1; c += P) {
 #pragma unroll
-        for (int u = 0; u < P; ++u) K_CHUNK(u & 1, ((u & 1) ? buf1 : buf0), ((u & 1) ? buf0 : buf1), c + u, u % WR, 1, 1, 1);
-      }
-#pragma unroll
-      for (int u = 0; u < P - 1; ++u)
-        if (c + u < c1) K_CHUNK(u & 1, ((u & 1) ? buf1 : buf0), ((u & 1) ? buf0 : buf1), c + u, u % WR, 1, 1, 1);
+      for (int u = 0; u < P; ++u) K_CHUNK(u & 1, ((u & 1) ? buf1 : buf0), ((u & 1) ? buf0 : buf1), c + u, u % WR);
     }
+#pragma unroll
+    for (int u = 0; u < P - 1; ++u)
+      if (c + u < c1) K_CHUNK(u & 1, ((u & 1) ? buf1 : buf0), ((u & 1) ? buf0 : buf1), c + u, u % WR);
 #undef K_PATCH_LOAD
 #undef K_SILU
 #undef K_PATCH_STORE

@@ -10,14 +10,10 @@
 namespace {
 
 constexpr int MAXJ = 4;  // float4 column iterations per thread: C <= 4096
-// independent 16-byte loads in flight per thread and input stream in the large-map kernels {stats, apply, bwd partial, bwd apply}.
-// Negative result kept as a knob: 8,8,4,4 / 8,8,8,8 / 6,6,6,6 are all 0.2-0.3 % SLOWER on the step than 4 everywhere (same-box
-// A/B, round 2) although the kernels run at 3.4-5.9 TB/s: more bytes in flight per thread do not buy bandwidth here.
-#ifndef CGD_GN_U
-#define CGD_GN_U 4, 4, 4, 4
-#endif
-constexpr int GN_UTAB[4] = {CGD_GN_U};
-constexpr int GN_US = GN_UTAB[0], GN_UA = GN_UTAB[1], GN_UP = GN_UTAB[2], GN_UB = GN_UTAB[3];  // stats, apply, bwd partial, bwd apply
+// independent 16-byte loads in flight per thread and input stream in the large-map kernels (stats, apply, bwd partial, bwd apply).
+// 8,8,4,4 / 8,8,8,8 / 6,6,6,6 were all 0.2-0.3 % SLOWER on the step than 4 everywhere (same-box A/B, round 2) although the kernels run
+// at 3.4-5.9 TB/s: more bytes in flight per thread do not buy bandwidth here.
+constexpr int GN_U = 4;
 
 struct ColMap {
   int cq, TQ, rows, r, q0;
@@ -118,10 +114,10 @@ __global__ __launch_bounds__(256) void gn_stats_partial_kernel(const float* x, f
     float4 s = make_float4(0, 0, 0, 0), ss = make_float4(0, 0, 0, 0);
     if (m.active) {
       // 4 independent loads in flight per thread: these kernels are latency-, not bandwidth-limited per wavefront
-      for (int pb = p0 + m.r; pb < p1; pb += GN_US * m.rows) {
-        float4 v[GN_US];
+      for (int pb = p0 + m.r; pb < p1; pb += GN_U * m.rows) {
+        float4 v[GN_U];
 #pragma unroll
-        for (int u = 0; u < GN_US; ++u) {
+        for (int u = 0; u < GN_U; ++u) {
           const int p = pb + u * m.rows, pc = p < p1 ? p : pb;
           if (src.n) {
             v[u] = split_load4(src, (long)b * HW + pc, q * 4);
@@ -131,7 +127,7 @@ __global__ __launch_bounds__(256) void gn_stats_partial_kernel(const float* x, f
           }
         }
 #pragma unroll
-        for (int u = 0; u < GN_US; ++u) {
+        for (int u = 0; u < GN_U; ++u) {
           if (pb + u * m.rows < p1) {
             const float dx = v[u].x - k4.x, dy = v[u].y - k4.y, dz = v[u].z - k4.z, dw = v[u].w - k4.w;
             s.x += dx; s.y += dy; s.z += dz; s.w += dw;
@@ -324,15 +320,15 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float* __restrict__
     if (q >= m.cq) break;
     const float4* cf = (const float4*)(coef + ((long)b * C + q * 4) * 4);
     const float4 c0 = cf[0], c1 = cf[1], c2 = cf[2], c3 = cf[3];
-    for (int pb = p0 + m.r; pb < p1; pb += GN_UA * m.rows) {
-      float4 vv[GN_UA];
+    for (int pb = p0 + m.r; pb < p1; pb += GN_U * m.rows) {
+      float4 vv[GN_U];
 #pragma unroll
-      for (int u = 0; u < GN_UA; ++u) {
+      for (int u = 0; u < GN_U; ++u) {
         const int p = pb + u * m.rows;
         vv[u] = *(const float4*)(xb + (long)(p < p1 ? p : pb) * ldx + q * 4);
       }
 #pragma unroll
-      for (int u = 0; u < GN_UA; ++u) {
+      for (int u = 0; u < GN_U; ++u) {
         const int p = pb + u * m.rows;
         if (p < p1) {
           const float4 v = vv[u];
@@ -373,10 +369,10 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __rest
     const float4 c0 = cf[0], c1 = cf[1], c2 = cf[2], c3 = cf[3];
     float4 s1 = make_float4(0, 0, 0, 0), s2 = make_float4(0, 0, 0, 0);
     if (m.active) {
-      for (int pb = p0 + m.r; pb < p1; pb += GN_UP * m.rows) {
-       float4 vv[GN_UP], dd[GN_UP];
+      for (int pb = p0 + m.r; pb < p1; pb += GN_U * m.rows) {
+       float4 vv[GN_U], dd[GN_U];
 #pragma unroll
-       for (int u = 0; u < GN_UP; ++u) {
+       for (int u = 0; u < GN_U; ++u) {
          const int p = pb + u * m.rows, pc = p < p1 ? p : pb;
          vv[u] = *(const float4*)(xb + (long)pc * ldx + q * 4);
          if (src.n) {
@@ -387,7 +383,7 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __rest
          }
        }
 #pragma unroll
-       for (int u = 0; u < GN_UP; ++u) {
+       for (int u = 0; u < GN_U; ++u) {
         if (pb + u * m.rows >= p1) continue;
         const float4 v = vv[u];
         float4 d = dd[u];
@@ -508,35 +504,19 @@ __global__ __launch_bounds__(256) void gn_bwd_coef_ch_kernel(const float* __rest
   }
 }
 
-// CGD_GN_NT (round 6): bit 0 = the x / dz streams of gn_bwd_apply_kernel with the non-temporal policy (both are read here for the last time: x is the
-// forward activation, dz the upstream gradient), bit 1 = its dx store (67 MB on the 256 x 256 level: twice the L2).  Same-box: loads -0.07 ms per step,
-// store -0.035, both -0.09 (profiles/r6_ab_gn_bwd_apply_nt.txt); bit 2 = the add / add2 operands (skip-connection gradients, read here for the last
-// time as well): -0.025 (profiles/r6_ab_nt_more.txt); 0 = the default policy everywhere (rounds 1-5)
-#ifndef CGD_GN_NT
-#define CGD_GN_NT 7
-#endif
-#ifndef CGD_GN_NT_MIN_BYTES
-#define CGD_GN_NT_MIN_BYTES 0
-#endif
+// gn_bwd_apply_kernel streams x, dz and the add / add2 operands with the non-temporal policy (all are read here for the last time: x is the
+// forward activation, dz the upstream gradient, add / add2 the skip-connection gradients), and its dx store as well (67 MB on the 256 x 256
+// level: twice the L2).  Same-box: x / dz loads -0.07 ms per step, dx store -0.035, both -0.09 (profiles/r6_ab_gn_bwd_apply_nt.txt); add
+// operands -0.025 (profiles/r6_ab_nt_more.txt).
 typedef float gn_f32x4 __attribute__((ext_vector_type(4)));
-template <bool NT>
-__device__ __forceinline__ float4 gn_ld4(const float* p) {
-  if constexpr (NT) {
-    const gn_f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const gn_f32x4*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-  } else {
-    return *(const float4*)p;
-  }
+__device__ __forceinline__ float4 gn_ld4_nt(const float* p) {
+  const gn_f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const gn_f32x4*>(p));
+  return make_float4(v.x, v.y, v.z, v.w);
 }
-template <bool NT>
-__device__ __forceinline__ void gn_st4(float* p, const float4 o) {
-  if constexpr (NT) {
-    __builtin_nontemporal_store(gn_f32x4{o.x, o.y, o.z, o.w}, reinterpret_cast<gn_f32x4*>(p));
-  } else {
-    *(float4*)p = o;
-  }
+__device__ __forceinline__ void gn_st4_nt(float* p, const float4 o) {
+  __builtin_nontemporal_store(gn_f32x4{o.x, o.y, o.z, o.w}, reinterpret_cast<gn_f32x4*>(p));
 }
-template <int ACT, int NT = CGD_GN_NT>
+template <int ACT>
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ dz,
                                                            int lddz, float* __restrict__ dx, int lddx, const float* __restrict__ add,
                                                            int ldadd, const float* __restrict__ add2, int ldadd2, int HW, int C, int chunk,
@@ -557,21 +537,21 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
     const float4* bf = (const float4*)(bcoef + ((long)b * C + q * 4) * 4);
     const float4 c0 = cf[0], c1 = cf[1], c2 = cf[2], c3 = cf[3];
     const float4 b0 = bf[0], b1 = bf[1], b2 = bf[2], b3 = bf[3];
-    for (int pb = p0 + m.r; pb < p1; pb += GN_UB * m.rows) {
-     float4 vv[GN_UB], dd[GN_UB], aa[GN_UB];
+    for (int pb = p0 + m.r; pb < p1; pb += GN_U * m.rows) {
+     float4 vv[GN_U], dd[GN_U], aa[GN_U];
 #pragma unroll
-     for (int u = 0; u < GN_UB; ++u) {
+     for (int u = 0; u < GN_U; ++u) {
        const int p = pb + u * m.rows, pc = p < p1 ? p : pb;
-       vv[u] = gn_ld4<(NT & 1) != 0>(xb + (long)pc * ldx + q * 4);
-       dd[u] = gn_ld4<(NT & 1) != 0>(db + (long)pc * lddz + q * 4);
-       if (ab) aa[u] = gn_ld4<(NT & 4) != 0>(ab + (long)pc * ldadd + q * 4);
+       vv[u] = gn_ld4_nt(xb + (long)pc * ldx + q * 4);
+       dd[u] = gn_ld4_nt(db + (long)pc * lddz + q * 4);
+       if (ab) aa[u] = gn_ld4_nt(ab + (long)pc * ldadd + q * 4);
        if (ab2) {
-         const float4 a2 = gn_ld4<(NT & 4) != 0>(ab2 + (long)pc * ldadd2 + q * 4);
+         const float4 a2 = gn_ld4_nt(ab2 + (long)pc * ldadd2 + q * 4);
          if (ab) { aa[u].x += a2.x; aa[u].y += a2.y; aa[u].z += a2.z; aa[u].w += a2.w; } else aa[u] = a2;
        }
      }
 #pragma unroll
-     for (int u = 0; u < GN_UB; ++u) {
+     for (int u = 0; u < GN_U; ++u) {
       const int p = pb + u * m.rows;
       if (p >= p1) continue;
       const float4 v = vv[u];
@@ -591,7 +571,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
         const float4 a = aa[u];
         o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w;
       }
-      gn_st4<(NT & 2) != 0>(ob + (long)p * lddx + q * 4, o);
+      gn_st4_nt(ob + (long)p * lddx + q * 4, o);
      }
     }
   }
@@ -1309,18 +1289,10 @@ int cgd_launch_gn_bwd(cgd_ctx* ctx, const float* x, int ldx, const float* dz, in
     }
     CGD_LAUNCH(gn_bwd_coef_kernel, dim3(32, B), dim3(256), 0, s, part, nchunk, stats, coef, C, HW, bcoef);
   }
-  // non-temporal streams (CGD_GN_NT) from CGD_GN_NT_MIN_BYTES per tensor on (A/B builds; 0 = always)
-  const bool nt = (long)B * HW * C * 4 >= (long)CGD_GN_NT_MIN_BYTES;
   if (act) {
-    if (nt)
-      CGD_LAUNCH((gn_bwd_apply_kernel<1>), dim3(nchunk, B), dim3(256), 0, s, x, ldx, dz, lddz, dx, lddx, add, ldadd, add2, ldadd2, HW, C, chunk, coef, bcoef);
-    else
-      CGD_LAUNCH((gn_bwd_apply_kernel<1, 0>), dim3(nchunk, B), dim3(256), 0, s, x, ldx, dz, lddz, dx, lddx, add, ldadd, add2, ldadd2, HW, C, chunk, coef, bcoef);
+    CGD_LAUNCH((gn_bwd_apply_kernel<1>), dim3(nchunk, B), dim3(256), 0, s, x, ldx, dz, lddz, dx, lddx, add, ldadd, add2, ldadd2, HW, C, chunk, coef, bcoef);
   } else {
-    if (nt)
-      CGD_LAUNCH((gn_bwd_apply_kernel<0>), dim3(nchunk, B), dim3(256), 0, s, x, ldx, dz, lddz, dx, lddx, add, ldadd, add2, ldadd2, HW, C, chunk, coef, bcoef);
-    else
-      CGD_LAUNCH((gn_bwd_apply_kernel<0, 0>), dim3(nchunk, B), dim3(256), 0, s, x, ldx, dz, lddz, dx, lddx, add, ldadd, add2, ldadd2, HW, C, chunk, coef, bcoef);
+    CGD_LAUNCH((gn_bwd_apply_kernel<0>), dim3(nchunk, B), dim3(256), 0, s, x, ldx, dz, lddz, dx, lddx, add, ldadd, add2, ldadd2, HW, C, chunk, coef, bcoef);
   }
   CGD_TRY(cgd_prof_stamp(ctx, &pr, s));
   cgd_prof_push(ctx, &pr);

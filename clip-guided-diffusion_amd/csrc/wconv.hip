@@ -47,73 +47,46 @@ constexpr int WRING = 8;               // weight-fragment ring of the one-channe
 // staging schedule (steps of a chunk): task k of the NEXT chunk is loaded at step w_load_task == k into slot k & 1 and transformed in six pieces
 // (A = pixel 0, B = pixel 2 + position 0, C = pixel 1, D = positions 1 and 2, E = pixel 3, F = position 3) at the steps w_proc_task(q, piece) == k.
 // NB = 4 (16 tile rows, 12 MFMAs per step): 5 tasks, loaded every 4th step, transformed two pieces per step 5..7 steps (1920 MFMA cycles) later; the
-// two-workgroup variant likewise.  NB = 2 (8 tile rows, 6 or 12 MFMAs per step), round 6 (CGD_WCONV_FINE = 1): ONE piece per step — the fused
-// GroupNorm + SiLU of a pixel is 8 transcendentals per thread, about what a step's MFMAs cover — 3 tasks, loads at steps 0, 4 and 11 (slot 0 is free
-// after step 10), pieces at steps 5-10, 11-16 and 18-23.  CGD_WCONV_FINE = 0: the schedule of rounds 2-5 (two pieces per step from steps 10, 14, 21).
-#ifndef CGD_WCONV_FINE
-#define CGD_WCONV_FINE 1
-#endif
-// the last chunk of a workgroup runs a copy of the scheduled region without staging and without weight prefetch: 2 (default) = in every instantiation,
-// 1 = in the one-channel-block instantiations (NC = 1) only, 0 = it re-stages itself (rounds 2-5).
-// CGD_WCONV_RING2 = weight-fragment ring depth of the two-channel-block instantiations: 6 (default) frees the 32 registers the second copy of the loop
-// needs — with the 8-step ring of the other instantiations the NC = 2 kernels spill 9-20 registers, and a dispatch that needs scratch costs +3.7 us.
-// Same-box (profiles/r6_ab_wconv_peel_variants.txt): peel 0 / ring 8 18.31 ms per step, 0 / 6 18.29, 1 / 8 18.30, 2 / 8 (scratch) 18.50, 2 / 6 18.22.
-#ifndef CGD_WCONV_PEEL
-#define CGD_WCONV_PEEL 2
-#endif
-#ifndef CGD_WCONV_RING2
-#define CGD_WCONV_RING2 6
-#endif
-// CGD_WCONV_BUFLOAD = 1 (round 6): patch pixels and weight fragments come through buffer loads.  A third of the chunk loop's vector-ALU instructions were
-// address arithmetic (64-bit per-lane adds for 96 fragment loads per chunk, the in-image test + select per patch load) and 48 more zeroed the padding
-// pixels after the load: with a buffer resource the chunk / step offset is a scalar, the per-lane offsets of a thread's 12 patch pixels are computed
-// once, and a padding pixel is an out-of-range offset — the load returns zeros and touches no memory.
-#ifndef CGD_WCONV_BUFLOAD
-#define CGD_WCONV_BUFLOAD 3  // bit 0: weight fragments, bit 1: patch pixels
-#endif
-#define WBUF_W (CGD_WCONV_BUFLOAD & 1)
-#define WBUF_P (CGD_WCONV_BUFLOAD & 2)
+// two-workgroup variant likewise.  NB = 2 (8 tile rows, 6 or 12 MFMAs per step), round 6: ONE piece per step — the fused GroupNorm + SiLU of a pixel
+// is 8 transcendentals per thread, about what a step's MFMAs cover — 3 tasks, loads at steps 0, 4 and 11 (slot 0 is free after step 10), pieces at
+// steps 5-10, 11-16 and 18-23.
+// The last chunk of a workgroup runs a copy of the scheduled region without staging and without weight prefetch (round 6).  The two-channel-block
+// instantiations (NC = 2) use a 6-step weight-fragment ring, which frees the 32 registers that second copy of the loop needs: with the 8-step ring of
+// the other instantiations they spill 9-20 registers, and a dispatch that needs scratch costs +3.7 us.  Same-box (profiles/r6_ab_wconv_peel_variants.txt):
+// no peel / ring 8 18.31 ms per step, no peel / 6 18.29, NC = 1 peeled / 8 18.30, all peeled / 8 (scratch) 18.50, all peeled / 6 18.22.
+// Patch pixels and weight fragments come through buffer loads (round 6).  A third of the chunk loop's vector-ALU instructions were address arithmetic
+// (64-bit per-lane adds for 96 fragment loads per chunk, the in-image test + select per patch load) and 48 more zeroed the padding pixels after the
+// load: with a buffer resource the chunk / step offset is a scalar, the per-lane offsets of a thread's 12 patch pixels are computed once, and a padding
+// pixel is an out-of-range offset — the load returns zeros and touches no memory.
 typedef int wi32x4 __attribute__((ext_vector_type(4)));
-template <int AUX = 0>  // cache policy bits of the instruction (2 = nt)
 __device__ __forceinline__ wi32x4 w_buf_load16(const void* base, unsigned num_records, int voffset, int soffset) {
   // raw buffer, stride 0; gfx9 resource word 3 = 0x00020000 (DATA_FORMAT 32); lanes with voffset >= num_records read zeros
   const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, num_records, 0x00020000);
-  return __builtin_amdgcn_raw_buffer_load_b128(r, voffset, soffset, AUX);
+  return __builtin_amdgcn_raw_buffer_load_b128(r, voffset, soffset, 0);
 }
 constexpr int W_OOB = (int)0x80000000;
-// CGD_WCONV_NT (round 6): bit 0 = the output tile's stores with the non-temporal policy (a 256 x 256 x 256-channel output is 67 MB: twice the L2, where
-// the next kernel cannot find it anyway), bit 1 = the epilogue's second operand (residual / the norm's input of the backward sums).  Same-box
-// (profiles/r6_ab_wconv_nt.txt): stores -0.035 ms per step, second-operand loads +0.02, both +-0: default 1.  Bit 2 = the patch loads of the chunk loop: +0.09
-#ifndef CGD_WCONV_NT
-#define CGD_WCONV_NT 1
-#endif
-#ifndef CGD_WCONV_NT_MIN_BYTES
-#define CGD_WCONV_NT_MIN_BYTES 0
-#endif
-template <bool NT>
-__device__ __forceinline__ wf32x4 w_ld_out(const float* p) {
-  if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const wf32x4*>(p)); else return *(const wf32x4*)p;
-}
+// The output tile is stored with the non-temporal policy (round 6, WConvParams::nt_out; a 256 x 256 x 256-channel output is 67 MB: twice the L2,
+// where the next kernel cannot find it anyway): -0.035 ms per step.  The epilogue's second operand and the chunk loop's patch loads stay on the
+// default policy: non-temporal they cost +0.02 and +0.09 (profiles/r6_ab_wconv_nt.txt).
 template <bool NT>
 __device__ __forceinline__ void w_st_out(float* p, const wf32x4 v) {
   if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<wf32x4*>(p)); else *(wf32x4*)p = v;
-}  // per-lane offset of a padding pixel: beyond the 2^31 records of the patch resource
+}
 template <int NB, int OCC = 1>
 __host__ __device__ constexpr int w_load_task(int q) {
   if (OCC == 2) return q == 0 ? 0 : q == 8 ? 1 : q == 16 ? 2 : -1;  // one staging register set: a task is transformed before the next is loaded
   if (NB == 4) return ((q & 3) == 0 && q < 20) ? (q >> 2) : -1;
-  return q == 0 ? 0 : q == 4 ? 1 : q == (CGD_WCONV_FINE ? 11 : 13) ? 2 : -1;
+  return q == 0 ? 0 : q == 4 ? 1 : q == 11 ? 2 : -1;
 }
 template <int NB, int OCC = 1>
 __host__ __device__ constexpr int w_proc_task(int q, int piece) {
-  if (NB == 2 && OCC == 1 && CGD_WCONV_FINE) {
+  if (NB == 2 && OCC == 1) {
     const int s = q - piece;
     return s == 5 ? 0 : s == 11 ? 1 : s == 18 ? 2 : -1;
   }
   const int s = q - (piece >> 1);
   if (OCC == 2) return s == 5 ? 0 : s == 13 ? 1 : s == 21 ? 2 : -1;
-  if (NB == 4) return (s >= 5 && ((s - 5) & 3) == 0) ? ((s - 5) >> 2) : -1;
-  return s == 10 ? 0 : s == 14 ? 1 : s == 21 ? 2 : -1;
+  return (s >= 5 && ((s - 5) & 3) == 0) ? ((s - 5) >> 2) : -1;
 }
 
 // per-wavefront timeline for benchmarks/ubench/wconv_stamps.hip (which includes this file with CGD_WCONV_STAMPS defined); the library
@@ -130,35 +103,11 @@ __device__ unsigned long long* g_wstamps;  // [workgroup][wavefront][32]: 0 entr
   } while (0)
 #endif
 
-// Ablation switches for benchmarks/ubench/wconv_stamps.hip ONLY (results become wrong; the library build never defines the macro): which element of
-// the chunk loop costs what?  bit 0: no weight-fragment loads inside the loop, bit 1: no patch loads / transform / LDS writes inside the loop,
-// bit 2: no barrier per chunk, bit 3: no A-fragment LDS reads inside the loop, bit 4: no sched_group_barrier pattern (the compiler's own schedule)
-#ifndef CGD_WCONV_EXP
-#define CGD_WCONV_EXP 0
-#endif
-
-// De-phasing of the four wavefronts (round 4, profiles/r4_wconv_ablation.txt): they run the same schedule in lock-step after every barrier, so their
-// weight-fragment loads (and LDS reads) reach the CU's single vector-memory path at the same moment and each wavefront waits for the other three
-// (~60 cycles per global_load_dwordx4 with the MFMA issue of that in-order wavefront stopped).  CGD_WCONV_SKEW = n: wavefront w sleeps n * 64 * w
-// cycles after every barrier, which keeps the four schedules apart for the whole chunk.
-// fp32-product instantiations: 1 = interleave the step's loads / staging VALU behind the MFMAs by hand (with a 4-step weight ring, which frees the
-// registers that schedule needs), 0 = the compiler's own order on the 8-step ring.  Same-box A/B (profiles/r6_ab_f32_schedule.txt): 41.01 / 41.06 ms per
-// step for 0 against 41.08 / 41.17 for 1 — the 64-cycle MFMAs hide the step's loads either way; default 0, the variant stays behind the macro
-#ifndef CGD_WCONV_F32_SCHED
-#define CGD_WCONV_F32_SCHED 0
-#endif
-#ifndef CGD_WCONV_SKEW
-#define CGD_WCONV_SKEW 0
-#endif
-__device__ __forceinline__ void w_skew(int wave) {
-#if CGD_WCONV_SKEW > 0
-  if (wave == 1) __builtin_amdgcn_s_sleep(CGD_WCONV_SKEW);
-  if (wave == 2) __builtin_amdgcn_s_sleep(2 * CGD_WCONV_SKEW);
-  if (wave == 3) __builtin_amdgcn_s_sleep(3 * CGD_WCONV_SKEW);
-#else
-  (void)wave;
-#endif
-}
+// The four wavefronts run the same schedule in lock-step after every barrier.  De-phasing them (wavefront w sleeping a multiple of 64 w cycles after
+// every barrier) was within noise (round 4, profiles/r4_wconv_ablation.txt): their weight-fragment loads do not collide on the vector-memory path.
+// fp32-product instantiations keep the compiler's own order on the 8-step ring: the step's loads and staging VALU interleaved behind the MFMAs by hand
+// (with a 4-step ring for the registers) measured 41.08 / 41.17 ms per step against 41.01 / 41.06 (profiles/r6_ab_f32_schedule.txt) — the 64-cycle
+// MFMAs hide the step's loads either way.
 
 struct WConvParams {
   int lda, ldc, ldr;
@@ -171,7 +120,7 @@ struct WConvParams {
   const float* bx;     // the norm's forward input, rows like the output
   const float* bcoef;  // {a, b, gcoef, mean} per (sample, channel)
   int ldbx, bact;
-  int nt_out;  // the output tile's stores with the non-temporal policy (CGD_WCONV_NT bit 0; the launcher: outputs of at least CGD_WCONV_NT_MIN_BYTES)
+  int nt_out;  // the output tile's stores with the non-temporal policy (the launcher sets it for every output)
 };
 
 __device__ __forceinline__ wbf16x4 w_bf16x4(const wf32x4 v) {
@@ -220,10 +169,8 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
   W_STAMP(0);
 
   static_assert(OCC == 1 || (NB == 2 && NC == 1), "two workgroups per CU: 8-row tile, one channel block");
-  // weight-fragment ring (steps); the hand-interleaved fp32 schedule (CGD_WCONV_F32_SCHED) needs the registers a 4-step ring frees
-  constexpr int RING = (OCC == 2 || (F32 && CGD_WCONV_F32_SCHED)) ? 4 : (NC == 2 ? CGD_WCONV_RING2 : WRING), DIST = RING - 1;
+  constexpr int RING = OCC == 2 ? 4 : (NC == 2 ? 6 : WRING), DIST = RING - 1;  // weight-fragment ring (steps)
   static_assert(WSTEPS % RING == 0, "the ring slot of a step must not depend on the chunk");
-  constexpr bool PEEL = CGD_WCONV_PEEL > 1 || (CGD_WCONV_PEEL == 1 && NC == 1);
   constexpr int TN = 128 * NC;  // output channels per workgroup
   const int ntn = (p.N + TN - 1) / TN;
   int bid = blockIdx.x;
@@ -258,13 +205,11 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
     const int x = x0 + 2 * sp + k - 1;
     colo[k] = (unsigned)x < (unsigned)p.W ? (p.ups ? x >> 1 : x) * p.lda + c4 * 4 : -1;
   }
-#if WBUF_P
   int poffv[NTASK][4];  // byte offset of pixel k of task j inside the image, W_OOB for a padding pixel (sign bit = "padding")
 #pragma unroll
   for (int j = 0; j < NTASK; ++j)
 #pragma unroll
     for (int k = 0; k < 4; ++k) poffv[j][k] = (rowoff[j] | colo[k]) >= 0 ? (rowoff[j] + colo[k]) * 4 : W_OOB;
-#endif
   // ---- fragment reads of this lane: pair column l31 of every block = (tile row 4b + (l31 >> 3), pair l31 & 7)
   const int lr = l31 >> 3, lp = l31 & 7;
   int fro[4];
@@ -275,15 +220,14 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
   const int nb0 = (n0 >> 5) + NC * wave;  // this wavefront's NC consecutive 32-channel blocks
   const int nbN = p.N >> 5;
   const long bstride_nb = (long)nchunk * (WSTEPS * 2 * 64);
+  // Unread, but kept: without it the compiler schedules the chunk loop differently and the kernel is no longer the measured build.
   const uint4* __restrict__ Bw0 = Bg + (long)(nb0 < nbN ? nb0 : nbN - 1) * bstride_nb + lane;
-  const long bnext = (NC > 1 && nb0 + 1 < nbN) ? bstride_nb : 0;  // offset of the second block's fragments (clamped like the first)
-#if WBUF_W
+  (void)Bw0;
   // the wavefront's first weight block as a scalar base, the second block's distance in bytes (a packed tensor is far below 2^31 bytes per block pair)
   const int nb0_s = (n0 >> 5) + NC * __builtin_amdgcn_readfirstlane(wave);
   const uint4* __restrict__ Bwb = Bg + (long)(nb0_s < nbN ? nb0_s : nbN - 1) * bstride_nb;
   const int bnext_b = (NC > 1 && nb0_s + 1 < nbN) ? (int)(bstride_nb * 16) : 0;
-  (void)bnext; (void)bnext_b; (void)Bw0;
-#endif
+  (void)bnext_b;
 
   wf32x16 acc[4][NB][NC];  // [position][pixel block][channel block]
 #pragma unroll
@@ -301,22 +245,11 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
   const wf32x4 z4 = wf32x4{0.f, 0.f, 0.f, 0.f};
   const float* __restrict__ gnimg = GN ? gng + ((long)img * p.Cin + c4 * 4) * 2 : nullptr;
 
-#if WBUF_P
 #define W_TASK_LOAD(ARR, J, CH)                                                                      \
   {                                                                                                  \
     _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                    \
-        ARR[k] = __builtin_bit_cast(wf32x4, w_buf_load16<(CGD_WCONV_NT & 4) ? 2 : 0>(Aimg, 0x80000000u, poffv[J][k], (CH) * 128)); \
+        ARR[k] = __builtin_bit_cast(wf32x4, w_buf_load16(Aimg, 0x80000000u, poffv[J][k], (CH) * 128)); \
   }
-#define W_PIX_OK(J, K) (poffv[J][K] >= 0)
-#else
-#define W_TASK_LOAD(ARR, J, CH)                                                                      \
-  {                                                                                                  \
-    const float* __restrict__ Ac_ = Aimg + (CH) * 32;                                                \
-    _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                    \
-        ARR[k] = *(const wf32x4*)(Ac_ + ((rowoff[J] | colo[k]) >= 0 ? rowoff[J] + colo[k] : c4 * 4)); \
-  }
-#define W_PIX_OK(J, K) ((rowoff[J] | colo[K]) >= 0)
-#endif
 #define W_GN_LOAD(CH)                                                                                \
   if constexpr (GN) {                                                                                \
     ga[0] = *(const wf32x4*)(gnimg + (CH) * 64);                                                     \
@@ -329,8 +262,8 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
     if constexpr (GN)                                                                                \
       v_ = wf32x4{w_silu(v_.x, ga[0].x, ga[0].y), w_silu(v_.y, ga[0].z, ga[0].w), w_silu(v_.z, ga[1].x, ga[1].y),   \
                   w_silu(v_.w, ga[1].z, ga[1].w)};                                                   \
-    /* (buffer loads: a padding pixel arrives as zeros; only the fused activation has to be undone) */ \
-    if constexpr (GN || !WBUF_P) ARR[K] = W_PIX_OK(J, K) ? v_ : z4; else ARR[K] = v_;                \
+    /* (a padding pixel arrives as zeros; only the fused activation has to be undone) */            \
+    if constexpr (GN) ARR[K] = poffv[J][K] >= 0 ? v_ : z4; else ARR[K] = v_;                         \
   }
 #define W_TASK_PUT(DSTB, J, XI, V)                                                                   \
   {                                                                                                  \
@@ -363,7 +296,6 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
       DST[b][1] = *(const wbf16x8*)&(SRCB)[WPLANE + o_ + b * (4 * WROW)];                            \
     }                                                                                                \
   }
-#if WBUF_W
   // BASE = chunk index (scalar): the fragments of step Q of that chunk
 #define W_B_LOAD(DST, BASE, Q)                                                                       \
   {                                                                                                  \
@@ -375,23 +307,6 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
       DST[NC - 1][1] = __builtin_bit_cast(uint4, w_buf_load16(Bwb, 0xffffffffu, lane * 16 + 1024, so_ + bnext_b)); \
     }                                                                                                \
   }
-#else
-#define W_B_LOAD(DST, BASE, Q)                                                                       \
-  {                                                                                                  \
-    const uint4* bp_ = (BASE) + (Q) * 128;                                                           \
-    DST[0][0] = bp_[0];                                                                              \
-    DST[0][1] = bp_[64];                                                                             \
-    if constexpr (NC > 1) {                                                                          \
-      DST[NC - 1][0] = bp_[bnext];                                                                   \
-      DST[NC - 1][1] = bp_[bnext + 64];                                                              \
-    }                                                                                                \
-  }
-#endif
-#if WBUF_W
-#define W_BBASE(CH) (CH)
-#else
-#define W_BBASE(CH) (Bw0 + (long)(CH) * (WSTEPS * 128))
-#endif
 #define W_MFMA12(XI, AQ, BQ)                                                                         \
   if constexpr (F32) {                                                                               \
     _Pragma("unroll") for (int pl = 0; pl < 2; ++pl) _Pragma("unroll") for (int e = 0; e < 4; ++e)   \
@@ -413,7 +328,7 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
     // prologue: stage chunk 0 completely, start the weight ring
     W_GN_LOAD(0);
 #pragma unroll
-    for (int q = 0; q < DIST; ++q) W_B_LOAD(bq[q], W_BBASE(0), q);
+    for (int q = 0; q < DIST; ++q) W_B_LOAD(bq[q], 0, q);
     wf32x4 pro[NTASK][4];  // all tasks in flight (the accumulators are not live yet)
 #pragma unroll
     for (int j = 0; j < NTASK; ++j) W_TASK_LOAD(pro[j], j, 0);
@@ -423,50 +338,36 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
     }
   }
   __syncthreads();
-  w_skew(wave);
   W_STAMP(1);
   // Two copies of the chunk body (the unrolled `ph` loop makes `stage` a compile-time constant in each): chunks 0 .. n - 2 stage their successor's
   // patch and prefetch its first weight fragments; the LAST chunk (round 6) does neither — it used to re-stage itself into the idle buffer to keep one
   // copy of the scheduled region, i.e. 1 / nchunk of all patch loads, GroupNorm + SiLU evaluations, transforms and LDS writes were thrown away
-  // (CGD_WCONV_PEEL = 0: that variant)
 #pragma unroll
   for (int ph = 0; ph < 2; ++ph) {
-  const bool stage = PEEL ? ph == 0 : true;
-  const int cbeg = PEEL ? (ph == 0 ? 0 : (nchunk > 0 ? nchunk - 1 : 0)) : (ph == 0 ? 0 : nchunk);
-  const int cend = PEEL ? (ph == 0 ? nchunk - 1 : nchunk) : nchunk;
+  const bool stage = ph == 0;
+  const int cbeg = ph == 0 ? 0 : (nchunk > 0 ? nchunk - 1 : 0);
+  const int cend = ph == 0 ? nchunk - 1 : nchunk;
   for (int c = cbeg; c < cend; ++c) {
     const bool more = c + 1 < nchunk;
-    const int cn = more ? c + 1 : c;  // (CGD_WCONV_PEEL = 0: the last chunk re-stages itself into the idle buffer: no branch in the scheduled region)
+    const int cn = more ? c + 1 : c;
     const __bf16* cur = lds + (c & 1) * (2 * WPLANE);
     __bf16* nxt = lds + ((c & 1) ^ 1) * (2 * WPLANE);
-#if !WBUF_W
-    const uint4* __restrict__ cb = Bw0 + (long)c * (WSTEPS * 128);
-    const uint4* __restrict__ nb = Bw0 + (long)cn * (WSTEPS * 128);
-#endif
     if (stage) W_GN_LOAD(cn);
     W_A_LOAD(af[0], cur, 0);
 #pragma unroll
     for (int q = 0; q < WSTEPS; ++q) {
       // ---- issue: A fragments one step ahead, B fragments DIST steps ahead, the staging task loads of w_load_task
-      if constexpr (!(CGD_WCONV_EXP & 8))
-        if (q + 1 < WSTEPS) W_A_LOAD(af[(q + 1) & 1], cur, q + 1);
+      if (q + 1 < WSTEPS) W_A_LOAD(af[(q + 1) & 1], cur, q + 1);
       const bool bload = stage || q + DIST < WSTEPS;  // the last chunk has no successor whose fragments to prefetch
-      if constexpr (!(CGD_WCONV_EXP & 1)) {
-        if (bload) {
-          const int q2 = (q + DIST) % WSTEPS;
-#if WBUF_W
-          const int base = (q + DIST < WSTEPS) ? c : cn;
-#else
-          const uint4* __restrict__ base = (q + DIST < WSTEPS) ? cb : nb;
-#endif
-          W_B_LOAD(bq[(q + DIST) % RING], base, q2);
-        }
+      if (bload) {
+        const int q2 = (q + DIST) % WSTEPS;
+        const int base = (q + DIST < WSTEPS) ? c : cn;
+        W_B_LOAD(bq[(q + DIST) % RING], base, q2);
       }
       const int lt = stage ? w_load_task<NB, OCC>(q) : -1;  // (folded: q and stage are constants in the unrolled loops)
-      if constexpr (!(CGD_WCONV_EXP & 2))
-        if (lt >= 0) W_TASK_LOAD(pr[lt & PM], (lt < 0 ? 0 : lt), cn);
+      if (lt >= 0) W_TASK_LOAD(pr[lt & PM], (lt < 0 ? 0 : lt), cn);
       W_MFMA12((q >> 1) & 3, af[q & 1], bq[q % RING]);
-      if constexpr (!(CGD_WCONV_EXP & 2)) if (stage) {
+      if (stage) {
         const int k1 = w_proc_task<NB, OCC>(q, 0), k2 = w_proc_task<NB, OCC>(q, 1), k3 = w_proc_task<NB, OCC>(q, 2);
         const int k4 = w_proc_task<NB, OCC>(q, 3), k5 = w_proc_task<NB, OCC>(q, 4), k6 = w_proc_task<NB, OCC>(q, 5);
         if (k1 >= 0) W_TASK_PA(nxt, pr[k1 & PM], (k1 < 0 ? 0 : k1));
@@ -476,7 +377,7 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
         if (k5 >= 0) W_TASK_PE(nxt, pr[k5 & PM], (k5 < 0 ? 0 : k5));
         if (k6 >= 0) W_TASK_PF(nxt, pr[k6 & PM], (k6 < 0 ? 0 : k6));
       }
-      if constexpr (!(CGD_WCONV_EXP & 16) && !F32) {
+      if constexpr (!F32) {
         const bool loads = stage && w_load_task<NB, OCC>(q) >= 0;
         const bool puts = stage && (w_proc_task<NB, OCC>(q, 1) >= 0 || w_proc_task<NB, OCC>(q, 3) >= 0 || w_proc_task<NB, OCC>(q, 5) >= 0);
         constexpr int NM = 3 * NB * NC;  // MFMAs per step: 12 (16-row tile, or 8-row tile x 2 channel blocks) or 6
@@ -490,24 +391,9 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
           if (puts && (NM == 12 ? (r % 3) == 2 : r >= 2)) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // DS write (<= 4 per step)
         }
       }
-      if constexpr (F32 && CGD_WCONV_F32_SCHED) {
-        // fp32 products: 8 NB NC MFMAs of 64 cycles per step; the step's loads and the staging VALU (GroupNorm + SiLU: two transcendentals per
-        // element) are spread behind them instead of being left in one block, which the compiler's own order does
-        const bool loads = stage && w_load_task<NB, OCC>(q) >= 0;
-        const bool puts = stage && (w_proc_task<NB, OCC>(q, 1) >= 0 || w_proc_task<NB, OCC>(q, 3) >= 0 || w_proc_task<NB, OCC>(q, 5) >= 0);
-        constexpr int NM = 8 * NB * NC;
-#pragma unroll
-        for (int r = 0; r < NM; ++r) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                                   // MFMA
-          if (loads && r < 4) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                               // the 4 patch loads first
-          __builtin_amdgcn_sched_group_barrier(0x002, GN ? 5 : 2, 0);                                          // VALU
-          if (puts && (r & 3) == 3) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                         // DS write
-        }
-      }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (!(CGD_WCONV_EXP & 4)) __syncthreads();  // patch c consumed by every wavefront, patch c + 1 written
-    if (c + 1 < nchunk) w_skew(wave);
+    __syncthreads();  // patch c consumed by every wavefront, patch c + 1 written
     W_STAMP(2 + (c < 27 ? c : 27));
   }
   }
@@ -525,8 +411,6 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
 #undef W_A_LOAD
 #undef W_B_LOAD
 #undef W_MFMA12
-#undef W_BBASE
-#undef W_PIX_OK
 
   // ---- epilogue: output transform in registers.  D = U x V^T in the 32x32 C/D layout: column (lane & 31) = pixel pair, row =
   //      channel (r & 3) + 8 (r >> 2) + 4 hh: accumulator quad g holds channels 8g + 4hh .. + 3 of the lane's pair.
@@ -603,7 +487,7 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
     // The second operand of a group of 4 tile rows (the residual, or the norm's input x of the backward sums) comes from global memory behind a
     // ~1.5 us latency and cannot be hoisted by the compiler above the stores of the previous group (it may alias the output): it is fetched one
     // group ahead by hand (rows of different groups never overlap, also when the residual IS the output buffer)
-    constexpr int EG = (NC == 2 && CGD_WCONV_BUFLOAD == 3) ? 4 : 8;  // instructions in flight (2 per tile row); the 512-register instantiations have no room for 8
+    constexpr int EG = NC == 2 ? 4 : 8;  // instructions in flight (2 per tile row); the 512-register instantiations have no room for 8
     wf32x4 opn[EG];
     const bool second = Rg != nullptr || bs_on;
     const float* o2 = Rg ? rp : bxp;
@@ -611,7 +495,7 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
     const int o2ld = Rg ? p.ldr : p.ldbx;
     if (second) {
 #pragma unroll
-      for (int u = 0; u < EG; ++u) opn[u] = w_ld_out<(CGD_WCONV_NT & 2) != 0>(&o2[(u >> 1) * o2row + 8 * (u & 1) * o2ld]);
+      for (int u = 0; u < EG; ++u) opn[u] = *(const wf32x4*)&o2[(u >> 1) * o2row + 8 * (u & 1) * o2ld];
     }
 #pragma unroll
     for (int i0 = 0; i0 < 2 * TR; i0 += EG) {  // EG instructions = EG / 2 tile rows in flight
@@ -626,7 +510,7 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
         for (int u = 0; u < EG; ++u) op[u] = opn[u];
         if (i0 + EG < 2 * TR) {
 #pragma unroll
-          for (int u = 0; u < EG; ++u) opn[u] = w_ld_out<(CGD_WCONV_NT & 2) != 0>(&o2[((i0 + EG + u) >> 1) * o2row + 8 * (u & 1) * o2ld]);
+          for (int u = 0; u < EG; ++u) opn[u] = *(const wf32x4*)&o2[((i0 + EG + u) >> 1) * o2row + 8 * (u & 1) * o2ld];
         }
       }
       if (Rg) {
@@ -640,7 +524,7 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
         for (int u = 0; u < EG; ++u)
           if (hb) v[u] += bv;
       }
-      if ((CGD_WCONV_NT & 1) && p.nt_out) {
+      if (p.nt_out) {
 #pragma unroll
         for (int u = 0; u < EG; ++u) w_st_out<true>(&cp[((i0 + u) >> 1) * crow + 8 * (u & 1) * p.ldc], v[u]);
       } else {
@@ -839,7 +723,7 @@ int cgd_launch_wconv(cgd_ctx* ctx, const GemmParams& g, hipStream_t s) {
   if (g.gnb_x && g.gnb_coef && merges && (ctx->gn_epi & 2) && !(g.gnb_ldx & 3) && !((uintptr_t)g.gnb_x & 15) && !g.stats && !g.R)
     p.bstat = cgd_chanstats_register(ctx, g.C, g.ldc, g.N, g.M, s, 1);
   ctx->last_wconv_bstat = p.bstat != nullptr;
-  p.nt_out = (long)g.M * g.N * 4 >= (long)CGD_WCONV_NT_MIN_BYTES ? 1 : 0;
+  p.nt_out = 1;
   const int nb = cgd_wconv_nb(ctx, g), nc = cgd_wconv_nc(ctx, g);
   dim3 grid((int)cgd_wconv_tiles_m(ctx, g) * cdiv(g.N, 128 * nc));
 #define WC_LAUNCH(GN_, NB_, NC_, F32_) \

@@ -19,7 +19,11 @@ N GPUs: `python bench.py --gpus N` spawns N ranks itself (one process per GPU, R
 broadcast of the packed weights at start-up, no per-step collective.  Timing: barrier + synchronize on both sides of exactly K
 steps, max over ranks.
 
-Prints ONE JSON line (driver contract) with three extra objects:
+Prints ONE JSON line (driver contract).  A plain run does only what that line's headline needs: set-up, `--warmup` steps, the `--steps`
+timed steps, `--dump-outputs` if given, and the line itself, whose `config` also carries the figures read off the timed region (per-rank
+times, host CPU / enqueue time per step, library launch counters).  `--full` adds the measurements that take passes of their own, all
+after the timed region (`--no-profile` / `--no-cpu-baseline` leave parts of them out again):
+  host_isolated_enqueue_* (in `config`): one step enqueued on an idle queue, median of 6.
   roofline     : dominant kernel = the Winograd halo-staged MFMA 3x3 conv of the large maps (`wconv_kernel`; the direct `hconv2_kernel`
                  of the smaller maps rides along as `other_conv_kernel`): algorithmic FLOP of its launches / their summed
                  HIP-event duration (events recorded by the library on the launch stream, in a separate UNTIMED pass after the
@@ -306,9 +310,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS), help="BASELINE.json configuration (2 = headline)")
     ap.add_argument("--precision", default="bf16x3", choices=["f32", "bf16x3", "bf16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the untimed HIP-event pass (roofline / hbm objects)")
-    ap.add_argument("--profile-steps", type=int, default=20)
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure what the headline does not need: isolated "
+                                                         "enqueue, HIP-event profile pass (roofline / hbm), power / clock, the exact-fp32 "
+                                                         "mode, box calibration and the CPU oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the untimed HIP-event pass (roofline / hbm objects), "
+                                                               "power / clock, the exact-fp32 mode and box calibration")
+    ap.add_argument("--profile-steps", type=int, default=20, help="with --full: steps of the HIP-event pass")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step yielded (the sampling "
                                                            "loop's `sample` and `pred_xstart`, rank 0) as DIR/<name>.npy, float32")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
@@ -430,18 +438,21 @@ def main():
     # host cost of ONE step in isolation (untimed, after the timed region): the queue is empty and the 4-slot upload ring is free, so the
     # call returns as soon as the step is enqueued — wall time and main-thread CPU time of the enqueue, without any waiting on the GPU
     # (inside the timed loop the host is held back by that ring: it may run at most 4 steps ahead of the GPU)
-    iso_wall, iso_cpu = [], []
-    for _ in range(6):
+    iso_wall = iso_cpu = float("nan")
+    if args.full:
+        iso_wall, iso_cpu = [], []
+        for _ in range(6):
+            th.cuda.synchronize()
+            w0, u0 = time.perf_counter(), time.thread_time()
+            next(steps)
+            iso_wall.append(time.perf_counter() - w0)
+            iso_cpu.append(time.thread_time() - u0)
         th.cuda.synchronize()
-        w0, u0 = time.perf_counter(), time.thread_time()
-        next(steps)
-        iso_wall.append(time.perf_counter() - w0)
-        iso_cpu.append(time.thread_time() - u0)
-    th.cuda.synchronize()
-    iso_wall, iso_cpu = sorted(iso_wall)[len(iso_wall) // 2], sorted(iso_cpu)[len(iso_cpu) // 2]
+        iso_wall, iso_cpu = sorted(iso_wall)[len(iso_wall) // 2], sorted(iso_cpu)[len(iso_cpu) // 2]
 
+    profile = args.full and not args.no_profile
     roof = hbm = None
-    if not args.no_profile and rank == 0:
+    if profile and rank == 0:
         # separate, UNTIMED pass: per-launch HIP events perturb what they measure, so they stay out of the timed region
         ctx.check(ctx.lib.cgd_profile(ctx.h, 1))
         th.cuda.synchronize()
@@ -530,11 +541,11 @@ def main():
     # board power and shader clock while the step loop runs (rocm-smi sampled from a thread during a separate UNTIMED pass: the sampler's
     # subprocesses stay out of the timed region); the dominant kernel is power-limited (profiles/r5_wconv_power.txt), so the clock the step
     # sustains belongs next to its roofline fraction
-    if roof is not None and rank == 0 and not args.no_profile:
+    if roof is not None and rank == 0 and profile:
         roof.update(sample_power_clock(lambda: next(steps), th, seconds=2.5))
     # the exact-fp32 MFMA mode (the reference's own arithmetic) beside the headline mode: a second context + networks, short untimed pass
     precision_modes = None
-    if rank == 0 and world == 1 and args.config == 2 and args.precision == "bf16x3" and not args.no_profile:
+    if rank == 0 and world == 1 and args.config == 2 and args.precision == "bf16x3" and profile:
         try:
             ctx32 = lib.Context(local, "f32")
             unet32, _t32, smp32, guid32, x032 = build_device(ctx32, cfg, dev)
@@ -555,7 +566,7 @@ def main():
         except Exception as e:  # never lose the headline number to the side column
             precision_modes = {"f32": {"error": f"{type(e).__name__}: {e}"}}
     box = None
-    if rank == 0 and world == 1 and args.precision == "bf16x3" and not args.no_profile:
+    if rank == 0 and world == 1 and args.precision == "bf16x3" and profile:
         try:
             box = box_calibration(ctx, th, dev)
         except Exception as e:  # never lose the headline number to the side column
@@ -600,10 +611,6 @@ def main():
                        # N * host_cpu_ms_per_step / ms_per_step stays below the cores it has
                        "host_cpu_ms_per_step_per_rank": [round(h[0] / args.steps * 1e3, 3) for h in host],
                        "host_enqueue_ms_per_step_per_rank": [round(h[1] / args.steps * 1e3, 3) for h in host],
-                       # one step enqueued on an idle queue (median of 6): wall time until the call returns / CPU time of the
-                       # enqueuing thread — the host work a step really needs
-                       "host_isolated_enqueue_ms_per_rank": [round(h[2] * 1e3, 3) for h in host],
-                       "host_isolated_enqueue_cpu_ms_per_rank": [round(h[3] * 1e3, 3) for h in host],
                        "host_cores": usable_cores(1 << 20),
                        "trajectory": f"chained: every step consumes the previous step's sample; chains of {start + 1} steps from "
                                      f"x_t = q_sample(x0*, t={start}) down to t = 0 (init-image prologue, skip_timesteps {N - 1 - start})",
@@ -613,6 +620,11 @@ def main():
                        "timed_seconds": round(tmax, 3), "last_sample_peak": round(peak, 3),
                        "tflop_per_step": cfg["tflop"], "achieved_tflops_whole_step": round(cfg["tflop"] * args.steps / tmax, 2)},
         }
+        if args.full:
+            # one step enqueued on an idle queue (median of 6): wall time until the call returns / CPU time of the enqueuing thread — the
+            # host work a step really needs
+            res["config"]["host_isolated_enqueue_ms_per_rank"] = [round(h[2] * 1e3, 3) for h in host]
+            res["config"]["host_isolated_enqueue_cpu_ms_per_rank"] = [round(h[3] * 1e3, 3) for h in host]
         if precision_modes:
             res["precision_modes"] = precision_modes
         if box:
@@ -628,7 +640,7 @@ def main():
             res["roofline"] = roof
         if hbm:
             res["hbm"] = hbm
-        if world == 1 and not args.no_cpu_baseline and args.config == 2:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == 2:
             try:
                 res["cpu_baseline"] = cpu_baseline_subprocess()
             except Exception as e:  # never lose the GPU number to a host-side problem

@@ -15,7 +15,7 @@ print(json.dumps({"n_ranks": r["n_gpus"], "value_steps_per_s": r["value"], "ms_p
                   "host_isolated_enqueue_ms_per_rank": c["host_isolated_enqueue_ms_per_rank"],
                   "host_isolated_enqueue_cpu_ms_per_rank": c["host_isolated_enqueue_cpu_ms_per_rank"], "host_cores": c["host_cores"]}))'
 nproc
-timeout 300 python bench.py --gpus 1 --steps $((STEPS * 2)) --warmup 5 --no-cpu-baseline --no-profile 2>/dev/null | python -c "$pick"
+timeout 300 python bench.py --gpus 1 --steps $((STEPS * 2)) --warmup 5 --full --no-cpu-baseline --no-profile 2>/dev/null | python -c "$pick"
 for n in 2 4 8; do
-  CGD_BENCH_DEVICE=0 CGD_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus $n --steps $((STEPS / (n / 2))) --warmup 3 --no-cpu-baseline --no-profile 2>/dev/null | python -c "$pick"
+  CGD_BENCH_DEVICE=0 CGD_BENCH_BACKEND=gloo timeout 900 python bench.py --gpus $n --steps $((STEPS / (n / 2))) --warmup 3 --full --no-cpu-baseline --no-profile 2>/dev/null | python -c "$pick"
 done

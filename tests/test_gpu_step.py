@@ -348,6 +348,38 @@ def test_bench_py_two_ranks_real_flow_on_one_gpu():
     assert abs(res["value"] - 2 * 4 / (res["ms_per_step"] * 4e-3)) < 1e-2 * res["value"]  # whole-job aggregate = N * K / max time
 
 
+def test_bench_py_full_adds_what_a_plain_run_leaves_out():
+    """A plain `bench.py` run measures nothing beyond its timed region; `--full` adds the passes of their own after it: the idle-queue
+    enqueue, the HIP-event profile pass (roofline / hbm), the exact-fp32 mode and the box calibration (the CPU oracle baseline is left
+    out here with --no-cpu-baseline)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "CGD_BENCH_BACKEND", "CGD_BENCH_DEVICE")}
+
+    def run(*extra):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", *extra], env=env,
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        res = json.loads(lines[0])
+        assert res["n_gpus"] == 1 and res["steps"] == 2 and res["value"] > 0 and res["ms_per_step"] > 0
+        return res
+
+    plain = run()
+    assert "host_isolated_enqueue_ms_per_rank" not in plain["config"]
+    assert not {"roofline", "hbm", "precision_modes", "box_calibration", "cpu_baseline"} & set(plain), sorted(plain)
+    res = run("--full", "--no-cpu-baseline", "--profile-steps", "2")
+    assert "cpu_baseline" not in res
+    assert len(res["config"]["host_isolated_enqueue_ms_per_rank"]) == 1 and res["config"]["host_isolated_enqueue_cpu_ms_per_rank"][0] > 0
+    assert res["roofline"]["kernel"].startswith("wconv_kernel") and 0 < res["roofline"]["frac"] < 1
+    assert res["hbm"]["ops_per_step"] > 0 and 0 < res["hbm"]["frac"] < 1
+    assert res["precision_modes"]["f32"]["steps_per_sec"] > 0, res["precision_modes"]
+    assert res["box_calibration"]["mfma_tflops"] > 0 and res["box_calibration"]["wconv_ref_us_random"] > 0, res["box_calibration"]
+
+
 def test_rccl_single_rank_collectives_under_torchrun():
     """RCCL really executes the N > 1 flow's collectives before the first 8-GPU run does.  `bench.py --gpus 1` under
     `torch.distributed.run --nproc-per-node 1` exactly as the driver launches N > 1 (127.0.0.1 rendezvous), backend "nccl" (= RCCL on

@@ -197,6 +197,7 @@ struct VConv {
 };
 
 struct Lpips : NetBase {
+  static constexpr bool uses_frag_cache = false;  // the convs use their own pre-packed Bpk copies (NetBase::uses_frag_cache)
   VConv cv[NCONV];
   float* lin[5] = {0, 0, 0, 0, 0};
   DevBuf xs, dxs, n0[5], dtap[5], part;
@@ -391,51 +392,14 @@ struct cgd_lpips {
 static hipStream_t LS(void* s) { return (hipStream_t)s; }
 
 extern "C" {
-int cgd_lpips_create(cgd_ctx* ctx, cgd_lpips** out) {
-  if (!ctx || !out) return -3;
-  cgd_lpips* v = new cgd_lpips();
-  v->net.ctx = ctx;
-  if (v->net.build() != 0) {
-    delete v;
-    return -2;
-  }
-  *out = v;
-  return 0;
-}
-// host-only: parameter manifest (lpips package names, element counts); no GPU, no context
-int cgd_lpips_manifest(void (*cb)(const char*, int64_t, void*), void* user) {
-  cgd_ctx host;
-  Lpips net;
-  net.ctx = &host;
-  if (net.build() != 0) return -2;
-  if (cb)
-    for (const ParamSpec& p : net.params) cb(p.name.c_str(), p.numel, user);
-  return (int)net.params.size();
-}
-void cgd_lpips_destroy(cgd_lpips* v) { delete v; }
-int cgd_lpips_num_params(cgd_lpips* v) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  return (int)v->net.params.size();
-}
-int cgd_lpips_param_info(cgd_lpips* v, int i, char* buf, int len, int64_t* numel) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  if (i < 0 || i >= (int)v->net.params.size()) return -1;
-  snprintf(buf, len, "%s", v->net.params[i].name.c_str());
-  if (numel) *numel = v->net.params[i].numel;
-  return 0;
-}
-int cgd_lpips_set_param(cgd_lpips* v, const char* name, const float* data, int64_t numel) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  return v->net.set_param(name, data, numel);
-}
-int cgd_lpips_finalize(cgd_lpips* v) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  return v->net.finalize(nullptr);
-}
+int cgd_lpips_create(cgd_ctx* ctx, cgd_lpips** out) { return net_create(ctx, out); }
+// host-only: lpips package names
+int cgd_lpips_manifest(void (*cb)(const char*, int64_t, void*), void* user) { return net_manifest<Lpips>(cb, user); }
+void cgd_lpips_destroy(cgd_lpips* v) { net_destroy(v); }
+int cgd_lpips_num_params(cgd_lpips* v) { return net_num_params(v); }
+int cgd_lpips_param_info(cgd_lpips* v, int i, char* buf, int len, int64_t* numel) { return net_param_info(v, i, buf, len, numel); }
+int cgd_lpips_set_param(cgd_lpips* v, const char* name, const float* data, int64_t numel) { return net_set_param(v, name, data, numel); }
+int cgd_lpips_finalize(cgd_lpips* v) { return net_finalize(v); }
 int cgd_lpips_set_reference(cgd_lpips* v, const float* ref_nchw, int B, int H, int W, void* stream) {
   if (!v) return -3;
   DeviceScope dev_scope(v->net.ctx);

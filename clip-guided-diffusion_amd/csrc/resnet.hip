@@ -358,8 +358,7 @@ int ResNet::fold(ConvBN& c, hipStream_t s) {
   CGD_LAUNCH(rn_fold_bn_kernel, dim3(rn_grid((long)c.cout * c.cin * kk)), dim3(256), 0, s, P(c.conv + ".weight"), P(c.bn + ".weight"),
                      P(c.bn + ".bias"), P(c.bn + ".running_mean"), P(c.bn + ".running_var"), c.w, c.bias, c.cout, c.cin, c.cinP, kk);
   if (c.k == 1) {
-    if (!c.wT) CGD_TRY(alloc(&c.wT, nw));
-    CGD_TRY(cgd_launch_transpose(ctx, c.w, c.cinP, 0, c.wT, c.coutP, 0, c.coutP, c.cinP, 1, s));
+    CGD_TRY(transpose_weight(c.w, &c.wT, c.coutP, c.cinP, s));
   } else if (c.cin >= 32) {
     if (!c.wf) {
       CGD_TRY(alloc(&c.wf, nw));
@@ -396,18 +395,15 @@ int ResNet::finalize(hipStream_t s) {
   if (!kvw) {
     CGD_TRY(alloc(&kvw, (size_t)2 * E * E));
     CGD_TRY(alloc(&kvb, (size_t)2 * E));
-    CGD_TRY(alloc(&qwT, (size_t)E * E));
-    CGD_TRY(alloc(&kvwT, (size_t)2 * E * E));
-    CGD_TRY(alloc(&cwT, (size_t)cfg.out_dim * E));
   }
   // fused K|V projection [2E][E]
   CGD_HIP(ctx, hipMemcpyAsync(kvw, P("attnpool.k_proj.weight"), (size_t)E * E * sizeof(float), hipMemcpyDeviceToDevice, s));
   CGD_HIP(ctx, hipMemcpyAsync(kvw + (size_t)E * E, P("attnpool.v_proj.weight"), (size_t)E * E * sizeof(float), hipMemcpyDeviceToDevice, s));
   CGD_HIP(ctx, hipMemcpyAsync(kvb, P("attnpool.k_proj.bias"), (size_t)E * sizeof(float), hipMemcpyDeviceToDevice, s));
   CGD_HIP(ctx, hipMemcpyAsync(kvb + E, P("attnpool.v_proj.bias"), (size_t)E * sizeof(float), hipMemcpyDeviceToDevice, s));
-  CGD_TRY(cgd_launch_transpose(ctx, qw, E, 0, qwT, E, 0, E, E, 1, s));
-  CGD_TRY(cgd_launch_transpose(ctx, kvw, E, 0, kvwT, 2 * E, 0, 2 * E, E, 1, s));
-  CGD_TRY(cgd_launch_transpose(ctx, cw, E, 0, cwT, cfg.out_dim, 0, cfg.out_dim, E, 1, s));
+  CGD_TRY(transpose_weight(qw, &qwT, E, E, s));
+  CGD_TRY(transpose_weight(kvw, &kvwT, 2 * E, E, s));
+  CGD_TRY(transpose_weight(cw, &cwT, cfg.out_dim, E, s));
   CGD_HIP(ctx, hipStreamSynchronize(s));
   finalized = true;
   have_fwd = false;
@@ -567,18 +563,7 @@ struct cgd_rn {
 };
 
 extern "C" {
-int cgd_rn_create(cgd_ctx* ctx, const cgd_rn_config* cfg, cgd_rn** out) {
-  if (!ctx || !cfg || !out) return -3;
-  cgd_rn* v = new cgd_rn();
-  v->net.ctx = ctx;
-  v->net.cfg = *cfg;
-  if (v->net.build() != 0) {
-    delete v;
-    return -2;
-  }
-  *out = v;
-  return 0;
-}
+int cgd_rn_create(cgd_ctx* ctx, const cgd_rn_config* cfg, cgd_rn** out) { return net_create(ctx, out, cfg); }
 // ---- test support: mask replay (tests/parity_checks.py check_resnet_mask_replay) -----------------------------------------------
 // The input gradient of a ReLU network is discontinuous in the activations, so two fp32 implementations disagree wherever a
 // pre-activation changes sign in its last bits.  These entry points let a test overwrite the saved post-ReLU activations of the
@@ -608,47 +593,13 @@ int cgd_rn_debug_relu_set(cgd_rn* v, int index, const float* src, void* stream) 
   const auto& b = bufs[index];
   return cgd_launch_copy2d(v->net.ctx, src, b.channels, nullptr, 0, b.p, b.ld, b.rows, b.channels, (hipStream_t)stream);
 }
-// host-only: parameter manifest (OpenAI `visual.*` names without the prefix, BatchNorm statistics included); no GPU, no context
-int cgd_rn_manifest(const cgd_rn_config* cfg, void (*cb)(const char*, int64_t, void*), void* user) {
-  if (!cfg) return -3;
-  cgd_ctx host;
-  ResNet net;
-  net.ctx = &host;
-  net.cfg = *cfg;
-  if (net.build() != 0) return -2;
-  if (cb)
-    for (const ParamSpec& p : net.params) cb(p.name.c_str(), p.numel, user);
-  return (int)net.params.size();
-}
-void cgd_rn_destroy(cgd_rn* v) {
-  if (v) cgd_frag_cache_clear(v->net.ctx);
-  delete v;
-}
-int cgd_rn_num_params(cgd_rn* v) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  return (int)v->net.params.size();
-}
-int cgd_rn_param_info(cgd_rn* v, int i, char* buf, int len, int64_t* numel) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  if (i < 0 || i >= (int)v->net.params.size()) return -1;
-  snprintf(buf, len, "%s", v->net.params[i].name.c_str());
-  if (numel) *numel = v->net.params[i].numel;
-  return 0;
-}
-int cgd_rn_set_param(cgd_rn* v, const char* name, const float* data, int64_t numel) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  cgd_frag_cache_clear(v->net.ctx);
-  return v->net.set_param(name, data, numel);
-}
-int cgd_rn_finalize(cgd_rn* v) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  cgd_frag_cache_clear(v->net.ctx);
-  return v->net.finalize(nullptr);
-}
+// host-only: OpenAI `visual.*` names without the prefix, BatchNorm statistics included
+int cgd_rn_manifest(const cgd_rn_config* cfg, void (*cb)(const char*, int64_t, void*), void* user) { return net_manifest<ResNet>(cb, user, cfg); }
+void cgd_rn_destroy(cgd_rn* v) { net_destroy(v); }
+int cgd_rn_num_params(cgd_rn* v) { return net_num_params(v); }
+int cgd_rn_param_info(cgd_rn* v, int i, char* buf, int len, int64_t* numel) { return net_param_info(v, i, buf, len, numel); }
+int cgd_rn_set_param(cgd_rn* v, const char* name, const float* data, int64_t numel) { return net_set_param(v, name, data, numel); }
+int cgd_rn_finalize(cgd_rn* v) { return net_finalize(v); }
 int cgd_rn_forward(cgd_rn* v, const float* img, int N, float* emb, void* stream) {
   if (!v) return -3;
   DeviceScope dev_scope(v->net.ctx);

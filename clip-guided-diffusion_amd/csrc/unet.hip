@@ -84,7 +84,8 @@ struct AttnBlock : Module {
   float *g = 0, *b = 0, *qkvw = 0, *qkvwT = 0, *qkvb = 0, *pw = 0, *pwT = 0, *pb = 0;
   int B = 0, T = 0;
   TV x;
-  DevBuf n, qkv, a, out, sc, qkvT, P, Pt, dP, dAt, da, dqkv, dn, dx;
+  DevBuf n, qkv, a, out, sc, da, dqkv, dn, dx;
+  AttnScratch att;
   int fwd(UNet& u, TV x, int B, int& H, int& W, TV* out, hipStream_t s) override;
   int bwd(UNet& u, TV dout, TV* din, hipStream_t s) override;
 };
@@ -308,19 +309,12 @@ int AttnBlock::fwd(UNet& u, TV xin, int Bn, int& H, int& W, TV* o, hipStream_t s
   if (!dst.p) CGD_TRY(u.ensure(out, rows * C));
   float* const outp = dst.p ? dst.p : out.p;
   const int ldo = dst.p ? dst.ld : C;
-  {  // scratch of the kernel family this shape runs on (flash: row statistics + a copy of O instead of T x T probabilities)
-    const AttnShape shb{B, heads, T, d, C, legacy};
-    CGD_TRY(u.ensure(qkvT, cgd_attn_buf_floats(ctx, shb, 3 * C, C, 0)));
-    CGD_TRY(u.ensure(P, cgd_attn_buf_floats(ctx, shb, 3 * C, C, 1)));
-  }
   CGD_TRY(cgd_launch_gn_fwd(ctx, x.p, x.ld, n.p, C, B, T, C, g, b, nullptr, 0, 0, 1e-5f, sc.p, s));
   GemmParams q;
   q.A = n.p; q.lda = C; q.B = qkvw; q.ldb = C; q.C = qkv.p; q.ldc = 3 * C; q.bias = qkvb; q.M = (int)rows; q.N = 3 * C; q.K = C;
   q.weight = 1;
   CGD_TRY(cgd_launch_gemm(ctx, q, s));
-  AttnShape sh{B, heads, T, d, C, legacy};
-  AttnBufs bf{qkvT.p, P.p, nullptr, nullptr, nullptr};
-  CGD_TRY(cgd_attn_fwd(ctx, sh, qkv.p, 3 * C, a.p, C, bf, s));
+  CGD_TRY(u.attn_fwd(att, AttnShape{B, heads, T, d, C, legacy, 0}, qkv.p, 3 * C, a.p, C, s));
   GemmParams p;
   p.A = a.p; p.lda = C; p.B = pw; p.ldb = C; p.C = outp; p.ldc = ldo; p.bias = pb; p.R = x.p; p.ldr = x.ld; p.M = (int)rows; p.N = C;
   p.K = C;
@@ -338,19 +332,11 @@ int AttnBlock::bwd(UNet& u, TV dout, TV* din, hipStream_t s) {
   CGD_TRY(u.ensure(dqkv, rows * 3 * C));
   CGD_TRY(u.ensure(dn, rows * C));
   CGD_TRY(u.ensure(dx, rows * C));
-  {
-    const AttnShape shb{B, heads, T, d, C, legacy};
-    CGD_TRY(u.ensure(Pt, cgd_attn_buf_floats(ctx, shb, 3 * C, C, 2)));
-    CGD_TRY(u.ensure(dP, cgd_attn_buf_floats(ctx, shb, 3 * C, C, 3)));
-    CGD_TRY(u.ensure(dAt, cgd_attn_buf_floats(ctx, shb, 3 * C, C, 4)));
-  }
   GemmParams p;
   p.A = dout.p; p.lda = dout.ld; p.B = pwT; p.ldb = C; p.C = da.p; p.ldc = C; p.M = (int)rows; p.N = C; p.K = C;
   p.weight = 1;
   CGD_TRY(cgd_launch_gemm(ctx, p, s));
-  AttnShape sh{B, heads, T, d, C, legacy};
-  AttnBufs bf{qkvT.p, P.p, Pt.p, dP.p, dAt.p};
-  CGD_TRY(cgd_attn_bwd(ctx, sh, qkv.p, 3 * C, da.p, C, dqkv.p, 3 * C, bf, s));
+  CGD_TRY(u.attn_bwd(att, AttnShape{B, heads, T, d, C, legacy, 0}, qkv.p, 3 * C, da.p, C, dqkv.p, 3 * C, s));
   GemmParams q;
   q.A = dqkv.p; q.lda = 3 * C; q.B = qkvwT; q.ldb = 3 * C; q.C = dn.p; q.ldc = C; q.M = (int)rows; q.N = C; q.K = 3 * C;
   q.weight = 1;
@@ -366,12 +352,12 @@ int UNet::build() {
   const int mc = cfg.model_channels;
   // configuration checks first (found by the host-sanitizer driver, tests/asan_host_driver.cpp: an empty channel_mult list used to
   // "build" a model without levels): everything the plan below divides by or indexes with
-  if (cfg.n_mult < 1 || cfg.n_mult > 8) CGD_FAIL(ctx, "unet: channel_mult must list 1..8 levels");
+  if (cfg.in_channels != 3 || (cfg.out_channels != 6 && cfg.out_channels != 3)) CGD_FAIL(ctx, "unet: in_channels must be 3, out_channels 3 or 6");
+  if (cfg.n_mult < 1 || cfg.n_mult > 8) CGD_FAIL(ctx, "unet: bad channel_mult");
   if (cfg.n_att < 0 || cfg.n_att > 8) CGD_FAIL(ctx, "unet: at most 8 attention resolutions");
   if (mc <= 0 || mc % 32) CGD_FAIL(ctx, "unet: model_channels must be a positive multiple of 32 (GroupNorm32)");
   if (cfg.num_res_blocks < 1) CGD_FAIL(ctx, "unet: num_res_blocks must be >= 1");
   if (cfg.image_size <= 0 || cfg.image_size % (1 << (cfg.n_mult - 1))) CGD_FAIL(ctx, "unet: image_size must be divisible by 2^(levels-1)");
-  if (cfg.in_channels != 3 || (cfg.out_channels != 3 && cfg.out_channels != 6)) CGD_FAIL(ctx, "unet: in_channels 3, out_channels 3 or 6");
   if (cfg.num_classes < 0) CGD_FAIL(ctx, "unet: num_classes must be >= 0");
   if (cfg.num_head_channels == -1 ? cfg.num_heads <= 0 : cfg.num_head_channels <= 0) CGD_FAIL(ctx, "unet: num_heads / num_head_channels");
   for (int i = 0; i < cfg.n_mult; ++i) {
@@ -498,10 +484,6 @@ int UNet::build() {
 
 int UNet::finalize(hipStream_t s) {
   CGD_TRY(check_all_set());
-  auto tr = [&](const float* w, float** wt, int rows, int cols) -> int {  // [rows][cols] -> [cols][rows]
-    if (!*wt) CGD_TRY(alloc(wt, (size_t)rows * cols));
-    return cgd_launch_transpose(ctx, w, cols, 0, *wt, rows, 0, rows, cols, 1, s);
-  };
   if (!emb_w_all) {
     CGD_TRY(alloc(&emb_w_all, (size_t)emb_total * ted));
     CGD_TRY(alloc(&emb_b_all, (size_t)emb_total));
@@ -532,7 +514,7 @@ int UNet::finalize(hipStream_t s) {
     if (rb->skip_conv) {
       rb->skw = P(p + ".skip_connection.weight");
       rb->skb = P(p + ".skip_connection.bias");
-      CGD_TRY(tr(rb->skw, &rb->skwT, rb->cout, rb->cin));
+      CGD_TRY(transpose_weight(rb->skw, &rb->skwT, rb->cout, rb->cin, s));
     }
     CGD_HIP(ctx, hipMemcpyAsync(emb_w_all + rb->emb_off * ted, P(p + ".emb_layers.1.weight"), (size_t)2 * rb->cout * ted * sizeof(float),
                                 hipMemcpyDeviceToDevice, s));
@@ -546,8 +528,8 @@ int UNet::finalize(hipStream_t s) {
     ab->g = P(p + ".norm.weight"); ab->b = P(p + ".norm.bias");
     ab->qkvw = P(p + ".qkv.weight"); ab->qkvb = P(p + ".qkv.bias");
     ab->pw = P(p + ".proj_out.weight"); ab->pb = P(p + ".proj_out.bias");
-    CGD_TRY(tr(ab->qkvw, &ab->qkvwT, 3 * ab->C, ab->C));
-    CGD_TRY(tr(ab->pw, &ab->pwT, ab->C, ab->C));
+    CGD_TRY(transpose_weight(ab->qkvw, &ab->qkvwT, 3 * ab->C, ab->C, s));
+    CGD_TRY(transpose_weight(ab->pw, &ab->pwT, ab->C, ab->C, s));
     return 0;
   };
   for (auto& blk : in_blocks)
@@ -733,100 +715,36 @@ struct cgd_unet {
 
 extern "C" {
 
-int cgd_unet_create(cgd_ctx* ctx, const cgd_unet_config* cfg, cgd_unet** out) {
-  if (!ctx || !cfg || !out) return -3;
-  if (cfg->in_channels != 3 || (cfg->out_channels != 6 && cfg->out_channels != 3)) CGD_FAIL(ctx, "unet: in_channels must be 3, out_channels 3 or 6");
-  if (cfg->n_mult < 1 || cfg->n_mult > 8) CGD_FAIL(ctx, "unet: bad channel_mult");
-  cgd_unet* u = new cgd_unet();
-  u->net.ctx = ctx;
-  u->net.cfg = *cfg;
-  if (u->net.build() != 0) {
-    delete u;
-    return -2;
-  }
-  *out = u;
-  return 0;
-}
-// host-only: parameter manifest of a configuration (upstream state-dict names, element counts); no GPU, no context
-int cgd_unet_manifest(const cgd_unet_config* cfg, void (*cb)(const char*, int64_t, void*), void* user) {
-  if (!cfg) return -3;
-  if (cfg->in_channels != 3 || (cfg->out_channels != 6 && cfg->out_channels != 3) || cfg->n_mult < 1 || cfg->n_mult > 8) return -2;
-  cgd_ctx host;  // plain host object: build() only records names and shapes
-  UNet net;
-  net.ctx = &host;
-  net.cfg = *cfg;
-  if (net.build() != 0) return -2;
-  if (cb)
-    for (const ParamSpec& p : net.params) cb(p.name.c_str(), p.numel, user);
-  return (int)net.params.size();
-}
+int cgd_unet_create(cgd_ctx* ctx, const cgd_unet_config* cfg, cgd_unet** out) { return net_create(ctx, out, cfg); }
+// host-only: upstream state-dict names
+int cgd_unet_manifest(const cgd_unet_config* cfg, void (*cb)(const char*, int64_t, void*), void* user) { return net_manifest<UNet>(cb, user, cfg); }
 void cgd_unet_destroy(cgd_unet* u) {
-  if (u) cgd_frag_cache_clear(u->net.ctx);  // packed copies are keyed by weight pointers that die with the net
-  if (u) {  // ... and the conv-epilogue record buffers by activation pointers that do
+  if (u) {  // the conv-epilogue record buffers are keyed by activation pointers that die with the net
     DeviceScope dev_scope(u->net.ctx);
     (void)hipDeviceSynchronize();
     cgd_chanstats_clear(u->net.ctx);
   }
-  delete u;
+  net_destroy(u);
 }
-int cgd_unet_num_params(cgd_unet* u) {
-  if (!u) return -3;
-  DeviceScope dev_scope(u->net.ctx);
-  return (int)u->net.params.size();
-}
-int cgd_unet_param_info(cgd_unet* u, int i, char* buf, int len, int64_t* numel) {
-  if (!u) return -3;
-  DeviceScope dev_scope(u->net.ctx);
-  if (i < 0 || i >= (int)u->net.params.size()) return -1;
-  snprintf(buf, len, "%s", u->net.params[i].name.c_str());
-  if (numel) *numel = u->net.params[i].numel;
-  return 0;
-}
-int cgd_unet_set_param(cgd_unet* u, const char* name, const float* data, int64_t numel) {
-  if (!u) return -3;
-  DeviceScope dev_scope(u->net.ctx);
-  cgd_frag_cache_clear(u->net.ctx);
-  return u->net.set_param(name, data, numel);
-}
-int cgd_unet_finalize(cgd_unet* u) {
-  if (!u) return -3;
-  DeviceScope dev_scope(u->net.ctx);
-  cgd_frag_cache_clear(u->net.ctx);
-  return u->net.finalize(nullptr);
-}
+int cgd_unet_num_params(cgd_unet* u) { return net_num_params(u); }
+int cgd_unet_param_info(cgd_unet* u, int i, char* buf, int len, int64_t* numel) { return net_param_info(u, i, buf, len, numel); }
+int cgd_unet_set_param(cgd_unet* u, const char* name, const float* data, int64_t numel) { return net_set_param(u, name, data, numel); }
+int cgd_unet_finalize(cgd_unet* u) { return net_finalize(u); }
 int cgd_unet_forward(cgd_unet* u, const float* x, const float* t, const int64_t* y, float* out, int B, int H, int W, void* stream) {
-  if (!u) return -3;
-  DeviceScope dev_scope(u->net.ctx);
-  if (const int rc = u->net.forward(x, t, y, out, B, H, W, (hipStream_t)stream)) {
-    u->net.ctx->pending.valid = false;  // failed pass: its deferred slices must not be reduced into a stale tensor later
-    return rc;
-  }
-  return cgd_flush_pending(u->net.ctx, (hipStream_t)stream);  // nothing deferred may outlive the call
+  return net_pass(u, stream, [&](hipStream_t s) { return u->net.forward(x, t, y, out, B, H, W, s); });
 }
 int cgd_unet_embed(cgd_unet* u, const float* t, const int64_t* y, int B, int slot, void* stream) {
   if (!u) return -3;
   DeviceScope dev_scope(u->net.ctx);
-  // (nothing is deferred here: GEMVs and element-wise kernels; a pending reduction of the MAIN stream's pass is not this call's to flush —
-  // cgd_launch_gemm flushes unconditionally, so the sampler only calls this between whole passes of the main stream)
+  // not a pass (no flush): nothing is deferred here (GEMVs and element-wise kernels), and a pending reduction of the MAIN stream's pass is not this
+  // call's to flush — cgd_launch_gemm flushes unconditionally, so the sampler only calls this between whole passes of the main stream
   return u->net.embed(t, y, B, slot, (hipStream_t)stream, true);
 }
 int cgd_unet_forward_slot(cgd_unet* u, const float* x, int slot, float* out, int B, int H, int W, void* stream) {
-  if (!u) return -3;
   if (slot < 0 || slot > 1) return -3;
-  DeviceScope dev_scope(u->net.ctx);
-  if (const int rc = u->net.forward(x, nullptr, nullptr, out, B, H, W, (hipStream_t)stream, slot)) {
-    u->net.ctx->pending.valid = false;
-    return rc;
-  }
-  return cgd_flush_pending(u->net.ctx, (hipStream_t)stream);
+  return net_pass(u, stream, [&](hipStream_t s) { return u->net.forward(x, nullptr, nullptr, out, B, H, W, s, slot); });
 }
 int cgd_unet_dgrad(cgd_unet* u, const float* g_out, float* g_x, void* stream) {
-  if (!u) return -3;
-  DeviceScope dev_scope(u->net.ctx);
-  if (const int rc = u->net.dgrad(g_out, g_x, (hipStream_t)stream)) {
-    u->net.ctx->pending.valid = false;  // failed pass: its deferred slices must not be reduced into a stale tensor later
-    return rc;
-  }
-  return cgd_flush_pending(u->net.ctx, (hipStream_t)stream);
+  return net_pass(u, stream, [&](hipStream_t s) { return u->net.dgrad(g_out, g_x, s); });
 }
 }

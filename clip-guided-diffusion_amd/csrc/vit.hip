@@ -11,14 +11,70 @@
 #include "../../include/cgd_mi355x.h"
 #include "net.h"
 
+// ---- ClipBlock (net.h): also the text tower's block
+void ClipBlock::add_params(NetBase& net, const std::string& prefix, int width, int nheads) {
+  pre = prefix;
+  W = width;
+  heads = nheads;
+  net.add_param(pre + ".ln_1.weight", W);
+  net.add_param(pre + ".ln_1.bias", W);
+  net.add_param(pre + ".attn.in_proj_weight", (int64_t)3 * W * W);
+  net.add_param(pre + ".attn.in_proj_bias", 3 * W);
+  net.add_param(pre + ".attn.out_proj.weight", (int64_t)W * W);
+  net.add_param(pre + ".attn.out_proj.bias", W);
+  net.add_param(pre + ".ln_2.weight", W);
+  net.add_param(pre + ".ln_2.bias", W);
+  net.add_param(pre + ".mlp.c_fc.weight", (int64_t)4 * W * W);
+  net.add_param(pre + ".mlp.c_fc.bias", 4 * W);
+  net.add_param(pre + ".mlp.c_proj.weight", (int64_t)4 * W * W);
+  net.add_param(pre + ".mlp.c_proj.bias", W);
+}
+
+void ClipBlock::lookup(NetBase& net) {
+  ln1g = net.P(pre + ".ln_1.weight"); ln1b = net.P(pre + ".ln_1.bias");
+  inw = net.P(pre + ".attn.in_proj_weight"); inb = net.P(pre + ".attn.in_proj_bias");
+  ow = net.P(pre + ".attn.out_proj.weight"); ob = net.P(pre + ".attn.out_proj.bias");
+  ln2g = net.P(pre + ".ln_2.weight"); ln2b = net.P(pre + ".ln_2.bias");
+  fcw = net.P(pre + ".mlp.c_fc.weight"); fcb = net.P(pre + ".mlp.c_fc.bias");
+  pjw = net.P(pre + ".mlp.c_proj.weight"); pjb = net.P(pre + ".mlp.c_proj.bias");
+}
+
+int clip_block_fwd(NetBase& net, const ClipBlock& b, ClipActs& t, const float* x, float* xo, int N, int T, bool causal, hipStream_t s) {
+  cgd_ctx* ctx = net.ctx;
+  const int W = b.W;
+  const long rows = (long)N * T;
+  CGD_TRY(net.ensure(t.st1, rows * 2)); CGD_TRY(net.ensure(t.st2, rows * 2));
+  CGD_TRY(net.ensure(t.y, rows * W)); CGD_TRY(net.ensure(t.qkv, rows * 3 * W)); CGD_TRY(net.ensure(t.a, rows * W));
+  CGD_TRY(net.ensure(t.x1, rows * W)); CGD_TRY(net.ensure(t.y2, rows * W)); CGD_TRY(net.ensure(t.u, rows * 4 * W));
+  CGD_TRY(net.ensure(t.ga, rows * 4 * W));
+  CGD_TRY(cgd_launch_ln_fwd(ctx, x, W, t.y.p, W, (int)rows, W, b.ln1g, b.ln1b, 1e-5f, t.st1.p, s));
+  CGD_TRY(cgd_launch_gemm(ctx, lin(t.y.p, W, b.inw, W, t.qkv.p, 3 * W, b.inb, nullptr, 0, rows, 3 * W), s));
+  const AttnShape sh{N, b.heads, T, W / b.heads, W, 0, causal ? 1 : 0};
+  CGD_TRY(net.attn_fwd(t.att, sh, t.qkv.p, 3 * W, t.a.p, W, s));
+  CGD_TRY(cgd_launch_gemm(ctx, lin(t.a.p, W, b.ow, W, t.x1.p, W, b.ob, x, W, rows, W, 1), s));
+  CGD_TRY(cgd_launch_ln_fwd(ctx, t.x1.p, W, t.y2.p, W, (int)rows, W, b.ln2g, b.ln2b, 1e-5f, t.st2.p, s));
+  {
+    // c_fc + QuickGELU: the activation runs in the GEMM's epilogue where hgemm2 takes the launch in one slice (u is kept
+    // for the image tower's backward pass, ga feeds c_proj); otherwise the separate elementwise kernel
+    GemmParams fc = lin(t.y2.p, W, b.fcw, W, t.u.p, 4 * W, b.fcb, nullptr, 0, rows, 4 * W);
+    if (cgd_gemm_fuses_act(ctx, fc)) {
+      fc.act_out = t.ga.p; fc.ld_act = 4 * W; fc.act = 2;
+      CGD_TRY(cgd_launch_gemm(ctx, fc, s));
+    } else {
+      CGD_TRY(cgd_launch_gemm(ctx, fc, s));
+      CGD_TRY(cgd_launch_act_fwd(ctx, t.u.p, t.ga.p, rows * 4 * W, 2, s));
+    }
+  }
+  return cgd_launch_gemm(ctx, lin(t.ga.p, 4 * W, b.pjw, 4 * W, xo, W, b.pjb, t.x1.p, W, rows, W, 1), s);
+}
+
 namespace {
 
-struct Layer {
-  std::string pre;
-  float *ln1g = 0, *ln1b = 0, *inw = 0, *inwT = 0, *inb = 0, *ow = 0, *owT = 0, *ob = 0;
-  float *ln2g = 0, *ln2b = 0, *fcw = 0, *fcwT = 0, *fcb = 0, *pjw = 0, *pjwT = 0, *pjb = 0;
-  DevBuf st1, y, qkv, qkvT, P, a, x1, st2, y2, u, ga, xo;       // forward
-  DevBuf dga, du, dy2, dx1, da, dqkv, dy, dx, Pt, dP, dAt;       // backward
+struct Layer : ClipBlock {
+  float *inwT = 0, *owT = 0, *fcwT = 0, *pjwT = 0;
+  ClipActs f;                                        // forward
+  DevBuf xo;
+  DevBuf dga, du, dy2, dx1, da, dqkv, dy, dx;        // backward
 };
 
 struct ViT : NetBase {
@@ -49,22 +105,7 @@ int ViT::build() {
   add_param("ln_pre.weight", W);
   add_param("ln_pre.bias", W);
   layers.resize(cfg.layers);
-  for (int l = 0; l < cfg.layers; ++l) {
-    const std::string p = "transformer.resblocks." + std::to_string(l);
-    layers[l].pre = p;
-    add_param(p + ".ln_1.weight", W);
-    add_param(p + ".ln_1.bias", W);
-    add_param(p + ".attn.in_proj_weight", (int64_t)3 * W * W);
-    add_param(p + ".attn.in_proj_bias", 3 * W);
-    add_param(p + ".attn.out_proj.weight", (int64_t)W * W);
-    add_param(p + ".attn.out_proj.bias", W);
-    add_param(p + ".ln_2.weight", W);
-    add_param(p + ".ln_2.bias", W);
-    add_param(p + ".mlp.c_fc.weight", (int64_t)4 * W * W);
-    add_param(p + ".mlp.c_fc.bias", 4 * W);
-    add_param(p + ".mlp.c_proj.weight", (int64_t)4 * W * W);
-    add_param(p + ".mlp.c_proj.bias", W);
-  }
+  for (int l = 0; l < cfg.layers; ++l) layers[l].add_params(*this, "transformer.resblocks." + std::to_string(l), W, cfg.heads);
   add_param("ln_post.weight", W);
   add_param("ln_post.bias", W);
   add_param("proj", (int64_t)W * cfg.out_dim);
@@ -73,49 +114,28 @@ int ViT::build() {
 
 int ViT::finalize(hipStream_t s) {
   CGD_TRY(check_all_set());
-  auto tr = [&](const float* w, float** wt, int rows, int cols) -> int {
-    if (!*wt) CGD_TRY(alloc(wt, (size_t)rows * cols));
-    return cgd_launch_transpose(ctx, w, cols, 0, *wt, rows, 0, rows, cols, 1, s);
-  };
   convw = P("conv1.weight"); cls = P("class_embedding"); pos = P("positional_embedding");
   lnpre_g = P("ln_pre.weight"); lnpre_b = P("ln_pre.bias");
   lnpost_g = P("ln_post.weight"); lnpost_b = P("ln_post.bias");
   proj = P("proj");
-  CGD_TRY(tr(convw, &convwT, W, PP));
-  CGD_TRY(tr(proj, &projT, W, cfg.out_dim));
+  CGD_TRY(transpose_weight(convw, &convwT, W, PP, s));
+  CGD_TRY(transpose_weight(proj, &projT, W, cfg.out_dim, s));
   for (Layer& l : layers) {
-    const std::string& p = l.pre;
-    l.ln1g = P(p + ".ln_1.weight"); l.ln1b = P(p + ".ln_1.bias");
-    l.inw = P(p + ".attn.in_proj_weight"); l.inb = P(p + ".attn.in_proj_bias");
-    l.ow = P(p + ".attn.out_proj.weight"); l.ob = P(p + ".attn.out_proj.bias");
-    l.ln2g = P(p + ".ln_2.weight"); l.ln2b = P(p + ".ln_2.bias");
-    l.fcw = P(p + ".mlp.c_fc.weight"); l.fcb = P(p + ".mlp.c_fc.bias");
-    l.pjw = P(p + ".mlp.c_proj.weight"); l.pjb = P(p + ".mlp.c_proj.bias");
-    CGD_TRY(tr(l.inw, &l.inwT, 3 * W, W));
-    CGD_TRY(tr(l.ow, &l.owT, W, W));
-    CGD_TRY(tr(l.fcw, &l.fcwT, 4 * W, W));
-    CGD_TRY(tr(l.pjw, &l.pjwT, W, 4 * W));
+    l.lookup(*this);
+    CGD_TRY(transpose_weight(l.inw, &l.inwT, 3 * W, W, s));
+    CGD_TRY(transpose_weight(l.ow, &l.owT, W, W, s));
+    CGD_TRY(transpose_weight(l.fcw, &l.fcwT, 4 * W, W, s));
+    CGD_TRY(transpose_weight(l.pjw, &l.pjwT, W, 4 * W, s));
   }
   CGD_HIP(ctx, hipStreamSynchronize(s));
   finalized = true;
   return 0;
 }
 
-static GemmParams lin(const float* A, int lda, const float* Wt, int K, float* C, int ldc, const float* bias, const float* R, int ldr,
-                      long M, int Nn, int defer = 0) {
-  GemmParams p;
-  p.defer = defer;  // 1: the next kernel reading C is a LayerNorm that sums split-K slices itself (norm.hip)
-  p.A = A; p.lda = lda; p.B = Wt; p.ldb = K; p.C = C; p.ldc = ldc; p.bias = bias; p.R = R; p.ldr = ldr;
-  p.weight = 1;  // every B operand of the tower is a persistent (packed-at-load) weight
-  p.M = (int)M; p.N = Nn; p.K = K;
-  return p;
-}
-
 int ViT::forward(const float* img, int lay, int Nn, float* emb, hipStream_t s) {
   if (!finalized) CGD_FAIL(ctx, "vit: finalize() has not been called after the last set_param");
   N = Nn; layout = lay; have_fwd = false;
   const long rows = (long)N * L;
-  const int H = cfg.heads, d = W / H;
   const float* colp = img;
   if (layout == 0) {
     CGD_TRY(ensure(cols, (size_t)N * g * g * PP));
@@ -131,34 +151,8 @@ int ViT::forward(const float* img, int lay, int Nn, float* emb, hipStream_t s) {
   CGD_TRY(cgd_launch_ln_fwd(ctx, tok.p, W, x0.p, W, (int)rows, W, lnpre_g, lnpre_b, 1e-5f, st_pre.p, s));
   const float* x = x0.p;
   for (Layer& l : layers) {
-    CGD_TRY(ensure(l.st1, rows * 2)); CGD_TRY(ensure(l.st2, rows * 2));
-    CGD_TRY(ensure(l.y, rows * W)); CGD_TRY(ensure(l.qkv, rows * 3 * W)); CGD_TRY(ensure(l.a, rows * W));
-    CGD_TRY(ensure(l.x1, rows * W)); CGD_TRY(ensure(l.y2, rows * W)); CGD_TRY(ensure(l.u, rows * 4 * W));
-    CGD_TRY(ensure(l.ga, rows * 4 * W)); CGD_TRY(ensure(l.xo, rows * W));
-    {  // scratch of the kernel family this shape runs on (flash: row statistics + a copy of O instead of L x L probabilities)
-      const AttnShape shb{N, H, L, d, W, 0};
-      CGD_TRY(ensure(l.qkvT, cgd_attn_buf_floats(ctx, shb, 3 * W, W, 0))); CGD_TRY(ensure(l.P, cgd_attn_buf_floats(ctx, shb, 3 * W, W, 1)));
-    }
-    CGD_TRY(cgd_launch_ln_fwd(ctx, x, W, l.y.p, W, (int)rows, W, l.ln1g, l.ln1b, 1e-5f, l.st1.p, s));
-    CGD_TRY(cgd_launch_gemm(ctx, lin(l.y.p, W, l.inw, W, l.qkv.p, 3 * W, l.inb, nullptr, 0, rows, 3 * W), s));
-    AttnShape sh{N, H, L, d, W, 0};
-    AttnBufs bf{l.qkvT.p, l.P.p, nullptr, nullptr, nullptr};
-    CGD_TRY(cgd_attn_fwd(ctx, sh, l.qkv.p, 3 * W, l.a.p, W, bf, s));
-    CGD_TRY(cgd_launch_gemm(ctx, lin(l.a.p, W, l.ow, W, l.x1.p, W, l.ob, x, W, rows, W, 1), s));
-    CGD_TRY(cgd_launch_ln_fwd(ctx, l.x1.p, W, l.y2.p, W, (int)rows, W, l.ln2g, l.ln2b, 1e-5f, l.st2.p, s));
-    {
-      // c_fc + QuickGELU: the activation runs in the GEMM's epilogue where hgemm2 takes the launch in one slice (u is kept
-      // for the backward pass, ga feeds c_proj); otherwise the separate elementwise kernel
-      GemmParams fc = lin(l.y2.p, W, l.fcw, W, l.u.p, 4 * W, l.fcb, nullptr, 0, rows, 4 * W);
-      if (cgd_gemm_fuses_act(ctx, fc)) {
-        fc.act_out = l.ga.p; fc.ld_act = 4 * W; fc.act = 2;
-        CGD_TRY(cgd_launch_gemm(ctx, fc, s));
-      } else {
-        CGD_TRY(cgd_launch_gemm(ctx, fc, s));
-        CGD_TRY(cgd_launch_act_fwd(ctx, l.u.p, l.ga.p, rows * 4 * W, 2, s));
-      }
-    }
-    CGD_TRY(cgd_launch_gemm(ctx, lin(l.ga.p, 4 * W, l.pjw, 4 * W, l.xo.p, W, l.pjb, l.x1.p, W, rows, W, 1), s));
+    CGD_TRY(ensure(l.xo, rows * W));
+    CGD_TRY(clip_block_fwd(*this, l, l.f, x, l.xo.p, N, L, false, s));
     x = l.xo.p;
   }
   CGD_TRY(ensure(st_post, (size_t)N * 2));
@@ -187,33 +181,26 @@ int ViT::dgrad(const float* demb, float* dimg, hipStream_t s) {
     CGD_TRY(ensure(l.dga, rows * 4 * W)); CGD_TRY(ensure(l.du, rows * 4 * W)); CGD_TRY(ensure(l.dy2, rows * W));
     CGD_TRY(ensure(l.dx1, rows * W)); CGD_TRY(ensure(l.da, rows * W)); CGD_TRY(ensure(l.dqkv, rows * 3 * W));
     CGD_TRY(ensure(l.dy, rows * W)); CGD_TRY(ensure(l.dx, rows * W));
-    {
-      const AttnShape shb{N, H, L, d, W, 0};
-      CGD_TRY(ensure(l.Pt, cgd_attn_buf_floats(ctx, shb, 3 * W, W, 2))); CGD_TRY(ensure(l.dP, cgd_attn_buf_floats(ctx, shb, 3 * W, W, 3)));
-      CGD_TRY(ensure(l.dAt, cgd_attn_buf_floats(ctx, shb, 3 * W, W, 4)));
-    }
     // MLP
     {
       // d(c_proj) and the backward of QuickGELU: du = (dcur @ W_proj) * gelu'(u), fused like the forward
       GemmParams pj = lin(dcur, W, l.pjwT, W, l.dga.p, 4 * W, nullptr, nullptr, 0, rows, 4 * W);
       if (cgd_gemm_fuses_act(ctx, pj)) {
         pj.C = l.du.p;
-        pj.act_in = l.u.p; pj.ld_act = 4 * W; pj.act = 2;
+        pj.act_in = l.f.u.p; pj.ld_act = 4 * W; pj.act = 2;
         CGD_TRY(cgd_launch_gemm(ctx, pj, s));
       } else {
         CGD_TRY(cgd_launch_gemm(ctx, pj, s));
-        CGD_TRY(cgd_launch_act_bwd(ctx, l.u.p, l.dga.p, l.du.p, rows * 4 * W, 2, s));
+        CGD_TRY(cgd_launch_act_bwd(ctx, l.f.u.p, l.dga.p, l.du.p, rows * 4 * W, 2, s));
       }
     }
     CGD_TRY(cgd_launch_gemm(ctx, lin(l.du.p, 4 * W, l.fcwT, 4 * W, l.dy2.p, W, nullptr, nullptr, 0, rows, W, 1), s));
-    CGD_TRY(cgd_launch_ln_bwd(ctx, l.x1.p, W, l.dy2.p, W, l.dx1.p, W, dcur, W, (int)rows, W, l.ln2g, l.st2.p, s));
+    CGD_TRY(cgd_launch_ln_bwd(ctx, l.f.x1.p, W, l.dy2.p, W, l.dx1.p, W, dcur, W, (int)rows, W, l.ln2g, l.f.st2.p, s));
     // attention
     CGD_TRY(cgd_launch_gemm(ctx, lin(l.dx1.p, W, l.owT, W, l.da.p, W, nullptr, nullptr, 0, rows, W), s));
-    AttnShape sh{N, H, L, d, W, 0};
-    AttnBufs bf{l.qkvT.p, l.P.p, l.Pt.p, l.dP.p, l.dAt.p};
-    CGD_TRY(cgd_attn_bwd(ctx, sh, l.qkv.p, 3 * W, l.da.p, W, l.dqkv.p, 3 * W, bf, s));
+    CGD_TRY(attn_bwd(l.f.att, AttnShape{N, H, L, d, W, 0, 0}, l.f.qkv.p, 3 * W, l.da.p, W, l.dqkv.p, 3 * W, s));
     CGD_TRY(cgd_launch_gemm(ctx, lin(l.dqkv.p, 3 * W, l.inwT, 3 * W, l.dy.p, W, nullptr, nullptr, 0, rows, W, 1), s));
-    CGD_TRY(cgd_launch_ln_bwd(ctx, xin, W, l.dy.p, W, l.dx.p, W, l.dx1.p, W, (int)rows, W, l.ln1g, l.st1.p, s));
+    CGD_TRY(cgd_launch_ln_bwd(ctx, xin, W, l.dy.p, W, l.dx.p, W, l.dx1.p, W, (int)rows, W, l.ln1g, l.f.st1.p, s));
     dcur = l.dx.p;
   }
   CGD_TRY(ensure(dtok, rows * W));
@@ -249,75 +236,18 @@ struct cgd_vit {
 };
 
 extern "C" {
-int cgd_vit_create(cgd_ctx* ctx, const cgd_vit_config* cfg, cgd_vit** out) {
-  if (!ctx || !cfg || !out) return -3;
-  cgd_vit* v = new cgd_vit();
-  v->net.ctx = ctx;
-  v->net.cfg = *cfg;
-  if (v->net.build() != 0) {
-    delete v;
-    return -2;
-  }
-  *out = v;
-  return 0;
-}
-// host-only: parameter manifest (OpenAI `visual.*` names without the prefix, element counts); no GPU, no context
-int cgd_vit_manifest(const cgd_vit_config* cfg, void (*cb)(const char*, int64_t, void*), void* user) {
-  if (!cfg) return -3;
-  cgd_ctx host;
-  ViT net;
-  net.ctx = &host;
-  net.cfg = *cfg;
-  if (net.build() != 0) return -2;
-  if (cb)
-    for (const ParamSpec& p : net.params) cb(p.name.c_str(), p.numel, user);
-  return (int)net.params.size();
-}
-void cgd_vit_destroy(cgd_vit* v) {
-  if (v) cgd_frag_cache_clear(v->net.ctx);
-  delete v;
-}
-int cgd_vit_num_params(cgd_vit* v) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  return (int)v->net.params.size();
-}
-int cgd_vit_param_info(cgd_vit* v, int i, char* buf, int len, int64_t* numel) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  if (i < 0 || i >= (int)v->net.params.size()) return -1;
-  snprintf(buf, len, "%s", v->net.params[i].name.c_str());
-  if (numel) *numel = v->net.params[i].numel;
-  return 0;
-}
-int cgd_vit_set_param(cgd_vit* v, const char* name, const float* data, int64_t numel) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  cgd_frag_cache_clear(v->net.ctx);
-  return v->net.set_param(name, data, numel);
-}
-int cgd_vit_finalize(cgd_vit* v) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  cgd_frag_cache_clear(v->net.ctx);
-  return v->net.finalize(nullptr);
-}
+int cgd_vit_create(cgd_ctx* ctx, const cgd_vit_config* cfg, cgd_vit** out) { return net_create(ctx, out, cfg); }
+// host-only: OpenAI `visual.*` names without the prefix
+int cgd_vit_manifest(const cgd_vit_config* cfg, void (*cb)(const char*, int64_t, void*), void* user) { return net_manifest<ViT>(cb, user, cfg); }
+void cgd_vit_destroy(cgd_vit* v) { net_destroy(v); }
+int cgd_vit_num_params(cgd_vit* v) { return net_num_params(v); }
+int cgd_vit_param_info(cgd_vit* v, int i, char* buf, int len, int64_t* numel) { return net_param_info(v, i, buf, len, numel); }
+int cgd_vit_set_param(cgd_vit* v, const char* name, const float* data, int64_t numel) { return net_set_param(v, name, data, numel); }
+int cgd_vit_finalize(cgd_vit* v) { return net_finalize(v); }
 int cgd_vit_forward(cgd_vit* v, const float* img, int layout, int N, float* emb, void* stream) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  if (const int rc = v->net.forward(img, layout, N, emb, (hipStream_t)stream)) {
-    v->net.ctx->pending.valid = false;  // failed pass: its deferred slices must not be reduced into a stale tensor later
-    return rc;
-  }
-  return cgd_flush_pending(v->net.ctx, (hipStream_t)stream);
+  return net_pass(v, stream, [&](hipStream_t s) { return v->net.forward(img, layout, N, emb, s); });
 }
 int cgd_vit_dgrad(cgd_vit* v, const float* d_emb, float* d_img, void* stream) {
-  if (!v) return -3;
-  DeviceScope dev_scope(v->net.ctx);
-  if (const int rc = v->net.dgrad(d_emb, d_img, (hipStream_t)stream)) {
-    v->net.ctx->pending.valid = false;  // failed pass: its deferred slices must not be reduced into a stale tensor later
-    return rc;
-  }
-  return cgd_flush_pending(v->net.ctx, (hipStream_t)stream);
+  return net_pass(v, stream, [&](hipStream_t s) { return v->net.dgrad(d_emb, d_img, s); });
 }
 }

@@ -89,6 +89,15 @@ int main() {
     Manifest ml;
     EXPECT(cgd_lpips_manifest(collect, &ml) == 13 * 2 + 5);
   }
+  {
+    const cgd_text_config b32 = {77, 49408, 512, 12, 8, 512};  // ViT-B/32's text tower
+    Manifest m;
+    EXPECT(cgd_text_manifest(&b32, collect, &m) == 2 + 12 * 12 + 3 && m.total == 63428096LL);
+    cgd_text_config bad = b32;
+    bad.heads = 7;  // does not divide the width
+    EXPECT(cgd_text_manifest(&bad, collect, &m) < 0);
+    EXPECT(cgd_text_manifest(nullptr, collect, &m) == -3);
+  }
 
   // ---- dispatch planner (host-only): every conv / GEMM shape class of the step, several CU counts and precisions
   {
@@ -163,6 +172,15 @@ int main() {
     cgd_vit_destroy(nullptr);
     EXPECT(cgd_vit_forward(nullptr, nullptr, 1, 1, nullptr, nullptr) == -3);
     EXPECT(cgd_vit_dgrad(nullptr, nullptr, nullptr, nullptr) == -3);
+    cgd_text_config tc = {77, 49408, 512, 12, 8, 512};
+    cgd_text* t = nullptr;
+    EXPECT(cgd_text_create(ctx, &tc, &t) == -3 && t == nullptr);
+    cgd_text_destroy(nullptr);
+    EXPECT(cgd_text_num_params(nullptr) == -3);
+    EXPECT(cgd_text_param_info(nullptr, 0, nullptr, 0, nullptr) == -3);
+    EXPECT(cgd_text_set_param(nullptr, "x", (const float*)(const void*)buf, 1) == -3);
+    EXPECT(cgd_text_finalize(nullptr) == -3);
+    EXPECT(cgd_text_forward(nullptr, nullptr, 1, nullptr, nullptr) == -3);
     cgd_rn_config rc = {224, 64, {3, 4, 6, 3}, 1024, 32};
     cgd_rn* r = nullptr;
     EXPECT(cgd_rn_create(ctx, &rc, &r) == -3);

@@ -98,13 +98,14 @@ def test_null_handles_are_rejected_not_dereferenced():
     # host-only layout query: {mean, rstd} pairs sit behind the per-chunk partials of the scratch (B * ceil(HW / chunk) * 64 floats)
     assert handle.cgd_op_gn_stats_offset(2, 4096, 192) == 2 * 256 * 64 and handle.cgd_op_gn_stats_offset(1, 64, 1024) == 8 * 64
     assert handle.cgd_last_error(None) == b"null context"
-    for net in ("unet", "vit", "rn", "lpips"):
+    for net in ("unet", "vit", "text", "rn", "lpips"):
         assert getattr(handle, f"cgd_{net}_num_params")(None) == -3
         assert getattr(handle, f"cgd_{net}_finalize")(None) == -3
         getattr(handle, f"cgd_{net}_destroy")(None)  # no-op
     assert handle.cgd_unet_forward(None, None, None, None, None, 1, 64, 64, None) == -3
     assert handle.cgd_unet_dgrad(None, None, None, None) == -3
     assert handle.cgd_vit_forward(None, None, 0, 1, None, None) == -3
+    assert handle.cgd_text_forward(None, None, 1, None, None) == -3
     assert handle.cgd_rn_forward(None, None, 1, None, None) == -3
     assert handle.cgd_lpips_loss_grad(None, None, 1.0, None, None, 0, None) == -3
     handle.cgd_ctx_destroy(None)  # no-op

@@ -216,6 +216,7 @@ int cgd_launch_pool2x2(cgd_ctx* ctx, const float* in, int ldi, float* out, int l
                        int Wo, int C, float scale, hipStream_t s) {
   CGD_TRY(cgd_sync_pending(ctx, s));  // reads activations: a deferred split-K reduction must have landed
   if ((C & 3) || (ldi & 3) || (ldo & 3)) CGD_FAIL(ctx, "pool2x2: C and strides must be multiples of 4");
+  if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)add) & 15) CGD_FAIL(ctx, "pool2x2: in / out / add must be 16-byte aligned");
   cgd_chanstats_invalidate(ctx, out, (long)B * Ho * Wo, ldo, C);
   CGD_LAUNCH(pool2x2_kernel, dim3(grid_for((long)B * Ho * Wo * (C / 4))), dim3(256), 0, s, in, ldi, out, ldo, add, ldadd, B,
                      Ho, Wo, C, scale);
@@ -227,6 +228,7 @@ int cgd_launch_upsample2x(cgd_ctx* ctx, const float* in, int ldi, float* out, in
                           int Wo, int C, float scale, hipStream_t s) {
   CGD_TRY(cgd_sync_pending(ctx, s));  // reads activations: a deferred split-K reduction must have landed
   if ((C & 3) || (ldi & 3) || (ldo & 3)) CGD_FAIL(ctx, "upsample2x: C and strides must be multiples of 4");
+  if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)add) & 15) CGD_FAIL(ctx, "upsample2x: in / out / add must be 16-byte aligned");
   cgd_chanstats_invalidate(ctx, out, (long)B * Ho * Wo, ldo, C);
   CGD_LAUNCH(upsample2x_kernel, dim3(grid_for((long)B * Ho * Wo * (C / 4))), dim3(256), 0, s, in, ldi, out, ldo, add, ldadd,
                      B, Ho, Wo, C, scale);

@@ -1087,7 +1087,8 @@ template <int ACT>
 void launch_gn_small_fwd(const float* x, int ldx, float* y, int ldy, int B, int HW, int C, const float* gamma, const float* beta,
                          const float* film, int ldfilm, float eps, float* stats, float* coef, hipStream_t s, const SplitSrc& src) {
   const int cpg = C / 32;
-  const bool v4 = !(cpg & 3) && !(ldx & 3) && !(ldy & 3) && !(src.n && ((src.N | src.ldr) & 3));
+  // float4 accesses need 4-float strides AND 16-byte aligned rows (a view may start at any float): otherwise the scalar kernel
+  const bool v4 = !(cpg & 3) && !(ldx & 3) && !(ldy & 3) && !(((uintptr_t)x | (uintptr_t)y) & 15) && !(src.n && ((src.N | src.ldr) & 3));
   const int cq = v4 ? cpg / 4 : cpg;
   int lg = 0;
   while ((1 << lg) < cq) ++lg;
@@ -1106,7 +1107,8 @@ void launch_gn_small_bwd(const float* x, int ldx, const float* dz, int lddz, flo
                          const float* add2, int ldadd2, int B, int HW, int C, const float* stats, const float* coef, hipStream_t s,
                          const SplitSrc& src) {
   const int cpg = C / 32;
-  const bool v4 = !(cpg & 3) && !(ldx & 3) && !(lddz & 3) && !(lddx & 3) && !(ldadd & 3) && !(ldadd2 & 3) && !(src.n && ((src.N | src.ldr) & 3));
+  const bool v4 = !(cpg & 3) && !(ldx & 3) && !(lddz & 3) && !(lddx & 3) && !(ldadd & 3) && !(ldadd2 & 3) &&
+                  !(((uintptr_t)x | (uintptr_t)dz | (uintptr_t)dx | (uintptr_t)add | (uintptr_t)add2) & 15) && !(src.n && ((src.N | src.ldr) & 3));
   const int cq = v4 ? cpg / 4 : cpg;
   int lg = 0;
   while ((1 << lg) < cq) ++lg;
@@ -1181,6 +1183,8 @@ int cgd_launch_gn_fwd(cgd_ctx* ctx, const float* x, int ldx, float* y, int ldy, 
                       const float* beta, const float* film, int ldfilm, int act, float eps, float* scratch, hipStream_t s) {
   if (C % 32 || C > 4096) CGD_FAIL(ctx, "groupnorm: C must be a multiple of 32 and <= 4096");
   if ((ldx & 3) || (y && (ldy & 3))) CGD_FAIL(ctx, "groupnorm: row strides must be multiples of 4");
+  // the > GN_SMALL_HW kernels (and the record merge) run on float4 only; the single-launch kernels fall back to scalar accesses
+  if (HW > GN_SMALL_HW && (((uintptr_t)x | (uintptr_t)y) & 15)) CGD_FAIL(ctx, "groupnorm: x / y must be 16-byte aligned above the single-launch size");
   float* const y_written = y;
   const int ldy_written = ldy;
   if (!y) ldy = 4;  // statistics only (y == nullptr): see cgd_gn_ab
@@ -1248,6 +1252,11 @@ int cgd_launch_gn_fwd(cgd_ctx* ctx, const float* x, int ldx, float* y, int ldy, 
 
 int cgd_launch_gn_bwd(cgd_ctx* ctx, const float* x, int ldx, const float* dz, int lddz, float* dx, int lddx, const float* add,
                       int ldadd, int B, int HW, int C, int act, float* scratch, hipStream_t s, const float* add2, int ldadd2) {
+  if (C % 32 || C > 4096) CGD_FAIL(ctx, "groupnorm backward: C must be a multiple of 32 and <= 4096");
+  // the > GN_SMALL_HW kernels run on float4 only; the single-launch kernels fall back to scalar accesses for odd strides / offsets
+  if (HW > GN_SMALL_HW && (((ldx | lddz | lddx | (add ? ldadd : 0) | (add2 ? ldadd2 : 0)) & 3) ||
+                           (((uintptr_t)x | (uintptr_t)dz | (uintptr_t)dx | (uintptr_t)add | (uintptr_t)add2) & 15)))
+    CGD_FAIL(ctx, "groupnorm backward: above the single-launch size, row strides must be multiples of 4 and x / dz / dx / add 16-byte aligned");
   int chunk, nchunk;
   float *part, *stats, *coef, *bcoef;
   gn_layout(scratch, B, HW, C, &chunk, &nchunk, &part, &stats, &coef, &bcoef);

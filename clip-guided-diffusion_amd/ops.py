@@ -1,6 +1,11 @@
 """Single-op wrappers over the C ABI on PyTorch-ROCm tensors (device memory + stream plumbing only).
 
 Used by the parity tests and available to a user-supplied cond_fn.  Activations are NHWC / token-major fp32.
+
+Every operand is checked before any C call (ValueError otherwise): fp32, on the GPU, and in a layout the ABI can express.  Where the
+ABI takes a row stride (GEMM operands, conv inputs and residuals, GroupNorm operands) a view is accepted if its last dimension is
+dense and its leading dimensions collapse to one row stride -- a channel slice of an NHWC concat buffer, say -- and that stride is
+what the C call receives.  Every other operand must be contiguous.
 """
 import ctypes as C
 
@@ -8,9 +13,54 @@ import torch as th
 
 from . import lib as L
 
+_DEVICE_TYPE = "cuda"  # where every operand must live: the kernels dereference raw device pointers
+
 
 def _s():
     return L.stream_ptr()
+
+
+def _check(t, name):
+    if not isinstance(t, th.Tensor):
+        raise ValueError(f"{name}: expected a torch.Tensor, got {type(t).__name__}")
+    if t.device.type != _DEVICE_TYPE:
+        raise ValueError(f"{name}: expected a GPU tensor, got one on {t.device}")
+    if t.dtype != th.float32:
+        raise ValueError(f"{name}: expected float32, got {t.dtype}")
+
+
+def _dense(t, name):
+    """Device pointer of a contiguous fp32 GPU tensor (None passes through)."""
+    if t is None:
+        return None
+    _check(t, name)
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous tensor, got shape {tuple(t.shape)} strides {t.stride()}")
+    return t.data_ptr()
+
+
+def _rows(t, name):
+    """(device pointer, row stride) of an fp32 GPU tensor read as rows of its last dimension: the last dimension must be dense and
+    the leading dimensions must collapse to one row stride, no smaller than the row.  None gives (None, 0)."""
+    if t is None:
+        return None, 0
+    _check(t, name)
+    if t.dim() == 0:
+        raise ValueError(f"{name}: expected at least one dimension")
+    shape, strides = tuple(t.shape), t.stride()
+    width = shape[-1]
+    if width > 1 and strides[-1] != 1:
+        raise ValueError(f"{name}: the last dimension must be dense, got strides {strides}")
+    lead = [(n, s) for n, s in zip(shape[:-1], strides[:-1]) if n != 1]  # size-1 dimensions carry no layout
+    ld = lead[-1][1] if lead else width
+    expect = ld
+    for n, s in reversed(lead):
+        if s != expect:
+            raise ValueError(f"{name}: leading dimensions do not collapse to one row stride (shape {shape}, strides {strides})")
+        expect *= n
+    if lead and ld < width:
+        raise ValueError(f"{name}: row stride {ld} is smaller than the row width {width}")
+    return t.data_ptr(), ld
 
 
 def pack_conv3x3(w):
@@ -22,68 +72,83 @@ def pack_conv3x3(w):
 
 
 def gemm(ctx, A, B, bias=None, R=None, alpha=1.0, force_tile=0, splitk=1, out=None):
-    """C[M,N] = alpha * A[M,K] @ B[N,K]^T (+bias) (+R)"""
+    """C[M,N] = alpha * A[M,K] @ B[N,K]^T (+bias) (+R); A, B, R and `out` may be row-strided views"""
     M, K = A.shape
     N = B.shape[0]
+    pa, lda = _rows(A, "A")
+    pb, ldb = _rows(B, "B")
+    pbias = _dense(bias, "bias")
+    pr, ldr = _rows(R, "R")
     if out is None:
         out = th.empty((M, N), device=A.device, dtype=th.float32)
-    ctx.check(ctx.lib.cgd_op_gemm(ctx.h, A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), out.data_ptr(), out.stride(0),
-                                  L.ptr(bias), None if R is None else R.data_ptr(), 0 if R is None else R.stride(0), M, N, K,
-                                  float(alpha), force_tile, splitk, _s()))
+    pc, ldc = _rows(out, "out")
+    ctx.check(ctx.lib.cgd_op_gemm(ctx.h, pa, lda, pb, ldb, pc, ldc, pbias, pr, ldr, M, N, K, float(alpha), force_tile, splitk, _s()))
     return out
 
 
 def pack_conv3x3_frag(ctx, w, dgrad=False):
     """torch conv weight [Co][Ci][3][3] (on the GPU) -> MFMA-fragment-order bf16 hi/lo planes for the halo conv kernel."""
     co, ci = w.shape[:2]
-    out = th.empty(co * ci * 9, device=w.device, dtype=th.float32)
     wc = w.contiguous().float()
-    ctx.check(ctx.lib.cgd_op_pack_conv3x3_frag(ctx.h, wc.data_ptr(), out.data_ptr(), co, ci, int(dgrad), _s()))
+    pw = _dense(wc, "w")
+    out = th.empty(co * ci * 9, device=w.device, dtype=th.float32)
+    ctx.check(ctx.lib.cgd_op_pack_conv3x3_frag(ctx.h, pw, out.data_ptr(), co, ci, int(dgrad), _s()))
     return out
 
 
 def conv3x3(ctx, x_nhwc, w_packed, bias=None, R=None, upsample_input=False, force_tile=0, splitk=1, w_frag=None):
-    """x (B,H,W,Cin) NHWC (H,W = OUTPUT size; with upsample_input the tensor holds (B,H/2,W/2,Cin))."""
+    """x (B,H,W,Cin) NHWC (H,W = OUTPUT size; with upsample_input the tensor holds (B,H/2,W/2,Cin)); x and R may be channel slices."""
     Bn, Hs, Ws, Cin = x_nhwc.shape
     H, W = (Hs * 2, Ws * 2) if upsample_input else (Hs, Ws)
     Cout = w_packed.shape[0]
+    px, ldx = _rows(x_nhwc, "x")
+    pw, pfrag, pbias = _dense(w_packed, "w_packed"), _dense(w_frag, "w_frag"), _dense(bias, "bias")
+    pr, ldr = _rows(R, "R")
     y = th.empty((Bn, H, W, Cout), device=x_nhwc.device, dtype=th.float32)
-    ctx.check(ctx.lib.cgd_op_conv3x3(ctx.h, x_nhwc.data_ptr(), Cin, w_packed.data_ptr(), L.ptr(w_frag), y.data_ptr(), Cout, L.ptr(bias),
-                                     L.ptr(R), Cout, Bn, H, W, Cin, Cout, int(upsample_input), force_tile, splitk, _s()))
+    ctx.check(ctx.lib.cgd_op_conv3x3(ctx.h, px, ldx, pw, pfrag, y.data_ptr(), Cout, pbias, pr, ldr, Bn, H, W, Cin, Cout, int(upsample_input),
+                                     force_tile, splitk, _s()))
     return y
 
 
 def pack_conv3x3_wino(ctx, w, dgrad=False):
     """torch conv weight [Co][Ci][3][3] (on the GPU) -> Winograd F(2,3)-transformed bf16 hi/lo fragments for wconv.hip."""
     co, ci = w.shape[:2]
-    out = th.empty(co * ci * 12, device=w.device, dtype=th.float32)
     wc = w.contiguous().float()
-    ctx.check(ctx.lib.cgd_op_pack_conv3x3_wino(ctx.h, wc.data_ptr(), out.data_ptr(), co, ci, int(dgrad), _s()))
+    pw = _dense(wc, "w")
+    out = th.empty(co * ci * 12, device=w.device, dtype=th.float32)
+    ctx.check(ctx.lib.cgd_op_pack_conv3x3_wino(ctx.h, pw, out.data_ptr(), co, ci, int(dgrad), _s()))
     return out
 
 
 def conv3x3_wino(ctx, x_nhwc, w_wino, cout, bias=None, R=None, upsample_input=False, gn_ab=None):
-    """The Winograd halo conv kernel on x (B,H,W,Cin) NHWC (H, W multiples of 16); gn_ab (B,Cin,2): convolve SiLU(x * a + b)."""
+    """The Winograd halo conv kernel on x (B,H,W,Cin) NHWC (H, W multiples of 16); gn_ab (B,Cin,2): convolve SiLU(x * a + b).
+    x and R may be channel slices."""
     Bn, Hs, Ws, Cin = x_nhwc.shape
     H, W = (Hs * 2, Ws * 2) if upsample_input else (Hs, Ws)
+    px, ldx = _rows(x_nhwc, "x")
+    pw, pbias, pab = _dense(w_wino, "w_wino"), _dense(bias, "bias"), _dense(gn_ab, "gn_ab")
+    pr, ldr = _rows(R, "R")
     y = th.empty((Bn, H, W, cout), device=x_nhwc.device, dtype=th.float32)
-    ctx.check(ctx.lib.cgd_op_conv3x3_wino(ctx.h, x_nhwc.data_ptr(), Cin, w_wino.data_ptr(), y.data_ptr(), cout, L.ptr(bias), L.ptr(R), cout,
-                                          L.ptr(gn_ab), Bn, H, W, Cin, cout, int(upsample_input), _s()))
+    ctx.check(ctx.lib.cgd_op_conv3x3_wino(ctx.h, px, ldx, pw, y.data_ptr(), cout, pbias, pr, ldr, pab, Bn, H, W, Cin, cout, int(upsample_input),
+                                          _s()))
     return y
 
 
 def conv_in(ctx, x_nchw, w_packed, bias, cout):
     Bn, Cin, H, W = x_nchw.shape
+    px, pw, pbias = _dense(x_nchw, "x"), _dense(w_packed, "w_packed"), _dense(bias, "bias")
     y = th.empty((Bn, H, W, cout), device=x_nchw.device, dtype=th.float32)
-    ctx.check(ctx.lib.cgd_op_conv_in(ctx.h, x_nchw.data_ptr(), w_packed.data_ptr(), L.ptr(bias), y.data_ptr(), Bn, H, W, Cin, cout, _s()))
+    ctx.check(ctx.lib.cgd_op_conv_in(ctx.h, px, pw, pbias, y.data_ptr(), Bn, H, W, Cin, cout, _s()))
     return y
 
 
 def conv_thin_out(ctx, x_nhwc, w_packed, bias, cout):
+    """x (B,H,W,Cin) NHWC, may be a channel slice -> y (B,cout,H,W) NCHW"""
     Bn, H, W, Cin = x_nhwc.shape
+    px, ldx = _rows(x_nhwc, "x")
+    pw, pbias = _dense(w_packed, "w_packed"), _dense(bias, "bias")
     y = th.empty((Bn, cout, H, W), device=x_nhwc.device, dtype=th.float32)
-    ctx.check(ctx.lib.cgd_op_conv_thin_out(ctx.h, x_nhwc.data_ptr(), Cin, w_packed.data_ptr(), L.ptr(bias), y.data_ptr(), Bn, H, W,
-                                           Cin, cout, _s()))
+    ctx.check(ctx.lib.cgd_op_conv_thin_out(ctx.h, px, ldx, pw, pbias, y.data_ptr(), Bn, H, W, Cin, cout, _s()))
     return y
 
 
@@ -93,58 +158,70 @@ def gn_scratch(ctx, B, HW, C, device):
 
 
 def groupnorm_fwd(ctx, x, gamma, beta, film=None, act=1, eps=1e-5, scratch=None):
-    """x (B,HW,C) NHWC-flattened.  Returns (y, scratch) — scratch feeds groupnorm_bwd."""
+    """x (B,HW,C) NHWC-flattened, may be a channel slice.  Returns (y, scratch) — scratch feeds groupnorm_bwd."""
     B, HW, Cc = x.shape
+    px, ldx = _rows(x, "x")
+    pg, pb, pf = _dense(gamma, "gamma"), _dense(beta, "beta"), _dense(film, "film")
     if scratch is None:
         scratch = gn_scratch(ctx, B, HW, Cc, x.device)
-    y = th.empty_like(x)
-    ctx.check(ctx.lib.cgd_op_gn_fwd(ctx.h, x.data_ptr(), Cc, y.data_ptr(), Cc, B, HW, Cc, gamma.data_ptr(), beta.data_ptr(),
-                                    L.ptr(film), act, eps, scratch.data_ptr(), _s()))
+    ps = _dense(scratch, "scratch")
+    y = th.empty((B, HW, Cc), device=x.device, dtype=th.float32)
+    ctx.check(ctx.lib.cgd_op_gn_fwd(ctx.h, px, ldx, y.data_ptr(), Cc, B, HW, Cc, pg, pb, pf, act, eps, ps, _s()))
     return y, scratch
 
 
 def groupnorm_bwd(ctx, x, dz, scratch, act=1, add=None):
+    """x, dz and add (B,HW,C) may be channel slices"""
     B, HW, Cc = x.shape
-    dx = th.empty_like(x)
-    ctx.check(ctx.lib.cgd_op_gn_bwd(ctx.h, x.data_ptr(), Cc, dz.data_ptr(), Cc, dx.data_ptr(), Cc, L.ptr(add), Cc, B, HW, Cc, act,
-                                    scratch.data_ptr(), _s()))
+    px, ldx = _rows(x, "x")
+    pdz, lddz = _rows(dz, "dz")
+    padd, ldadd = _rows(add, "add")
+    ps = _dense(scratch, "scratch")
+    dx = th.empty((B, HW, Cc), device=x.device, dtype=th.float32)
+    ctx.check(ctx.lib.cgd_op_gn_bwd(ctx.h, px, ldx, pdz, lddz, dx.data_ptr(), Cc, padd, ldadd, B, HW, Cc, act, ps, _s()))
     return dx
 
 
 def layernorm_fwd(ctx, x, gamma, beta, eps=1e-5):
     rows, Cc = x.shape
-    y = th.empty_like(x)
+    px, pg, pb = _dense(x, "x"), _dense(gamma, "gamma"), _dense(beta, "beta")
+    y = th.empty((rows, Cc), device=x.device, dtype=th.float32)
     stats = th.empty((rows, 2), device=x.device, dtype=th.float32)
-    ctx.check(ctx.lib.cgd_op_ln_fwd(ctx.h, x.data_ptr(), y.data_ptr(), rows, Cc, gamma.data_ptr(), beta.data_ptr(), eps,
-                                    stats.data_ptr(), _s()))
+    ctx.check(ctx.lib.cgd_op_ln_fwd(ctx.h, px, y.data_ptr(), rows, Cc, pg, pb, eps, stats.data_ptr(), _s()))
     return y, stats
 
 
 def layernorm_bwd(ctx, x, dy, gamma, stats):
     rows, Cc = x.shape
-    dx = th.empty_like(x)
-    ctx.check(ctx.lib.cgd_op_ln_bwd(ctx.h, x.data_ptr(), dy.data_ptr(), dx.data_ptr(), rows, Cc, gamma.data_ptr(), stats.data_ptr(), _s()))
+    px, pdy, pg, pst = _dense(x, "x"), _dense(dy, "dy"), _dense(gamma, "gamma"), _dense(stats, "stats")
+    dx = th.empty((rows, Cc), device=x.device, dtype=th.float32)
+    ctx.check(ctx.lib.cgd_op_ln_bwd(ctx.h, px, pdy, dx.data_ptr(), rows, Cc, pg, pst, _s()))
     return dx
 
 
 def pool2x2(ctx, x_nhwc, scale=0.25):
     B, H, W, Cc = x_nhwc.shape
+    px = _dense(x_nhwc, "x")
     y = th.empty((B, H // 2, W // 2, Cc), device=x_nhwc.device, dtype=th.float32)
-    ctx.check(ctx.lib.cgd_op_pool2x2(ctx.h, x_nhwc.data_ptr(), y.data_ptr(), B, H // 2, W // 2, Cc, scale, _s()))
+    ctx.check(ctx.lib.cgd_op_pool2x2(ctx.h, px, y.data_ptr(), B, H // 2, W // 2, Cc, scale, _s()))
     return y
 
 
 def upsample2x(ctx, x_nhwc, scale=1.0):
     B, H, W, Cc = x_nhwc.shape
+    px = _dense(x_nhwc, "x")
     y = th.empty((B, H * 2, W * 2, Cc), device=x_nhwc.device, dtype=th.float32)
-    ctx.check(ctx.lib.cgd_op_upsample2x(ctx.h, x_nhwc.data_ptr(), y.data_ptr(), B, H * 2, W * 2, Cc, scale, _s()))
+    ctx.check(ctx.lib.cgd_op_upsample2x(ctx.h, px, y.data_ptr(), B, H * 2, W * 2, Cc, scale, _s()))
     return y
 
 
 def act(ctx, x, kind, dy=None):
     """kind 1 SiLU, 2 QuickGELU; with dy returns dy * act'(x)."""
-    out = th.empty_like(x)
-    ctx.check(ctx.lib.cgd_op_act(ctx.h, x.data_ptr(), L.ptr(dy), out.data_ptr(), x.numel(), kind, _s()))
+    px, pdy = _dense(x, "x"), _dense(dy, "dy")
+    if dy is not None and dy.numel() != x.numel():
+        raise ValueError(f"dy: {dy.numel()} elements, x has {x.numel()}")
+    out = th.empty(x.shape, device=x.device, dtype=th.float32)
+    ctx.check(ctx.lib.cgd_op_act(ctx.h, px, pdy, out.data_ptr(), x.numel(), kind, _s()))
     return out
 
 
@@ -158,8 +235,9 @@ class Attention:
 
     def forward(self, qkv):
         Cc = self.heads * self.d
+        pq = _dense(qkv, "qkv")
         out = th.empty((self.nb * self.T, Cc), device=qkv.device, dtype=th.float32)
-        self.ctx.check(self.ctx.lib.cgd_op_attn_fwd(self.ctx.h, qkv.data_ptr(), out.data_ptr(), self.nb, self.heads, self.T, self.d,
+        self.ctx.check(self.ctx.lib.cgd_op_attn_fwd(self.ctx.h, pq, out.data_ptr(), self.nb, self.heads, self.T, self.d,
                                                     self.legacy, self._arr, _s()))
         return out
 
@@ -168,13 +246,15 @@ class Attention:
         if self.legacy:
             raise ValueError("causal attention takes the [Q all heads | K | V] row layout (legacy=0)")
         Cc = self.heads * self.d
+        pq = _dense(qkv, "qkv")
         out = th.empty((self.nb * self.T, Cc), device=qkv.device, dtype=th.float32)
-        self.ctx.check(self.ctx.lib.cgd_op_attn_fwd_causal(self.ctx.h, qkv.data_ptr(), out.data_ptr(), self.nb, self.heads, self.T, self.d,
+        self.ctx.check(self.ctx.lib.cgd_op_attn_fwd_causal(self.ctx.h, pq, out.data_ptr(), self.nb, self.heads, self.T, self.d,
                                                            self._arr, _s()))
         return out
 
     def backward(self, qkv, dout):
-        dqkv = th.empty_like(qkv)
-        self.ctx.check(self.ctx.lib.cgd_op_attn_bwd(self.ctx.h, qkv.data_ptr(), dout.data_ptr(), dqkv.data_ptr(), self.nb, self.heads,
+        pq, pd = _dense(qkv, "qkv"), _dense(dout, "dout")
+        dqkv = th.empty(qkv.shape, device=qkv.device, dtype=th.float32)
+        self.ctx.check(self.ctx.lib.cgd_op_attn_bwd(self.ctx.h, pq, pd, dqkv.data_ptr(), self.nb, self.heads,
                                                     self.T, self.d, self.legacy, self._arr, _s()))
         return dqkv

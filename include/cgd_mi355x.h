@@ -340,6 +340,11 @@ int cgd_op_conv_in(cgd_ctx* ctx, const float* x_nchw, const float* w, const floa
 int cgd_op_conv_thin_out(cgd_ctx* ctx, const float* x_nhwc, int ldx, const float* w, const float* bias, float* y_nchw, int Bn, int H,
                          int W, int Cin, int Cout, void* stream);
 int64_t cgd_op_gn_scratch_floats(int B, int HW, int C);
+/* GroupNorm over 32 groups: C a multiple of 32 and <= 4096, forward row strides (ldx, ldy) multiples of 4.  Up to 1024 pixels per sample (the
+ * default single-launch size)
+ * any pointer and, in the backward, any stride is taken (odd strides / 16-byte misaligned views run on scalar accesses);
+ * above that the kernels run on 16-byte accesses: every row stride must be a multiple of 4 and x / y / dz / dx / add 16-byte aligned, or
+ * the call fails (CGD_FAIL) before anything is launched. */
 int cgd_op_gn_fwd(cgd_ctx* ctx, const float* x, int ldx, float* y, int ldy, int B, int HW, int C, const float* gamma,
                   const float* beta, const float* film, int act, float eps, float* scratch, void* stream);
 int cgd_op_gn_bwd(cgd_ctx* ctx, const float* x, int ldx, const float* dz, int lddz, float* dx, int lddx, const float* add, int ldadd,
@@ -348,6 +353,7 @@ int cgd_op_ln_fwd(cgd_ctx* ctx, const float* x, float* y, int rows, int C, const
                   float* stats, void* stream);
 int cgd_op_ln_bwd(cgd_ctx* ctx, const float* x, const float* dy, float* dx, int rows, int C, const float* gamma, const float* stats,
                   void* stream);
+/* pool2x2 / upsample2x: C a multiple of 4 and in / out 16-byte aligned, or the call fails before anything is launched */
 int cgd_op_pool2x2(cgd_ctx* ctx, const float* in, float* out, int B, int Ho, int Wo, int C, float scale, void* stream);
 int cgd_op_upsample2x(cgd_ctx* ctx, const float* in, float* out, int B, int Ho, int Wo, int C, float scale, void* stream);
 int cgd_op_act(cgd_ctx* ctx, const float* x, const float* dy, float* out, int64_t n, int act, void* stream);

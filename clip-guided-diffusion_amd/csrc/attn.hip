@@ -8,6 +8,7 @@
 // must be K-contiguous but is not (v for PV, P / dS for the transposed products) is produced by a tiled
 // transpose.  Rows of P are padded to a multiple of 4 floats with zeros.
 #include "common.h"
+#include "mfma_stage.h"
 #include "kernels.h"
 
 namespace {
@@ -78,8 +79,6 @@ constexpr int AS_T = 64, AS_D = 64;  // short-sequence fused kernels (attn_s64_*
 // MFMA operand k-mapping: step e of group m contracts k = 8m + e (lanes 0-31) and k = 8m + 4 + e (lanes 32-63), so an
 // operand that is k-contiguous in LDS is fetched with one ds_read_b128 per 4 MFMAs; an operand that is contiguous along
 // the lane index is fetched with ds_read_b32 (row pitch = 8 mod 16 floats keeps the two half-waves on different banks).
-typedef float am_f32x16 __attribute__((ext_vector_type(16)));
-typedef float am_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int AM_P68 = 68, AM_P72 = 72, AM_PS = 132, AM_P40 = 40;
 
 // ---- X3 = true: the same contractions on v_mfma_f32_32x32x16_bf16 with the bf16x3 split (al*bh + ah*bl + ah*bh), reading the SAME
@@ -87,16 +86,15 @@ constexpr int AM_P68 = 68, AM_P72 = 72, AM_PS = 132, AM_P40 = 40;
 // any k -> slot assignment is valid as long as both operands use it), splits them in registers and issues 3 MFMAs of 32 cycles
 // where the exact path issues 8 of 64: 5.3x fewer MFMA cycles for ~48 VALU ops per step.  Default for bf16x3 contexts since round 3
 // (strict parity on the GPU, -0.2 ms/step: profiles/r3_staged_ab.txt); CGD_ATTN_X3=0 selects the exact instantiations.
-typedef __bf16 am_bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void am_split8(const float (&v)[8], am_bf16x8& hi, am_bf16x8& lo) {
+__device__ __forceinline__ void am_split8(const float (&v)[8], cgd_bf16x8& hi, cgd_bf16x8& lo) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     hi[e] = (__bf16)v[e];
     lo[e] = (__bf16)(v[e] - (float)hi[e]);
   }
 }
-__device__ __forceinline__ void am_mma16_x3(am_f32x16& acc, const float (&a)[8], const float (&b)[8]) {
-  am_bf16x8 ah, al, bh, bl;
+__device__ __forceinline__ void am_mma16_x3(cgd_f32x16& acc, const float (&a)[8], const float (&b)[8]) {
+  cgd_bf16x8 ah, al, bh, bl;
   am_split8(a, ah, al);
   am_split8(b, bh, bl);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
@@ -106,12 +104,12 @@ __device__ __forceinline__ void am_mma16_x3(am_f32x16& acc, const float (&a)[8],
 
 // acc[32x32] += sum_{k<64} A[row][k] * B[col][k]   (both k-contiguous; As/Bs = this lane's row base)
 template <bool X3>
-__device__ __forceinline__ void am_mma_nt64(am_f32x16& acc, const float* As, const float* Bs, int hh) {
+__device__ __forceinline__ void am_mma_nt64(cgd_f32x16& acc, const float* As, const float* Bs, int hh) {
   if constexpr (X3) {
 #pragma unroll
     for (int s2 = 0; s2 < 4; ++s2) {
-      const am_f32x4 a0 = *(const am_f32x4*)(As + 16 * s2 + 4 * hh), a1 = *(const am_f32x4*)(As + 16 * s2 + 8 + 4 * hh);
-      const am_f32x4 b0 = *(const am_f32x4*)(Bs + 16 * s2 + 4 * hh), b1 = *(const am_f32x4*)(Bs + 16 * s2 + 8 + 4 * hh);
+      const cgd_f32x4 a0 = *(const cgd_f32x4*)(As + 16 * s2 + 4 * hh), a1 = *(const cgd_f32x4*)(As + 16 * s2 + 8 + 4 * hh);
+      const cgd_f32x4 b0 = *(const cgd_f32x4*)(Bs + 16 * s2 + 4 * hh), b1 = *(const cgd_f32x4*)(Bs + 16 * s2 + 8 + 4 * hh);
       const float av[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
       const float bv[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
       am_mma16_x3(acc, av, bv);
@@ -120,8 +118,8 @@ __device__ __forceinline__ void am_mma_nt64(am_f32x16& acc, const float* As, con
   }
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
-    const am_f32x4 a = *(const am_f32x4*)(As + 8 * m + 4 * hh);
-    const am_f32x4 b = *(const am_f32x4*)(Bs + 8 * m + 4 * hh);
+    const cgd_f32x4 a = *(const cgd_f32x4*)(As + 8 * m + 4 * hh);
+    const cgd_f32x4 b = *(const cgd_f32x4*)(Bs + 8 * m + 4 * hh);
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[e], acc, 0, 0, 0);
   }
@@ -130,22 +128,22 @@ __device__ __forceinline__ void am_mma_nt64(am_f32x16& acc, const float* As, con
 // kernel) is split once into registers (32 VGPRs) instead of being re-read from LDS and re-split per key block (round 4: half of the split
 // arithmetic of those products, 33 VALU per MFMA overall before; same values, same operation order: bit-identical).
 struct AmPre {
-  am_bf16x8 h[4], l[4];
+  cgd_bf16x8 h[4], l[4];
 };
 __device__ __forceinline__ void am_presplit64(AmPre& p, const float* As, int hh) {
 #pragma unroll
   for (int s2 = 0; s2 < 4; ++s2) {
-    const am_f32x4 a0 = *(const am_f32x4*)(As + 16 * s2 + 4 * hh), a1 = *(const am_f32x4*)(As + 16 * s2 + 8 + 4 * hh);
+    const cgd_f32x4 a0 = *(const cgd_f32x4*)(As + 16 * s2 + 4 * hh), a1 = *(const cgd_f32x4*)(As + 16 * s2 + 8 + 4 * hh);
     const float av[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
     am_split8(av, p.h[s2], p.l[s2]);
   }
 }
-__device__ __forceinline__ void am_mma_nt64_pre(am_f32x16& acc, const AmPre& a, const float* Bs, int hh) {
+__device__ __forceinline__ void am_mma_nt64_pre(cgd_f32x16& acc, const AmPre& a, const float* Bs, int hh) {
 #pragma unroll
   for (int s2 = 0; s2 < 4; ++s2) {
-    const am_f32x4 b0 = *(const am_f32x4*)(Bs + 16 * s2 + 4 * hh), b1 = *(const am_f32x4*)(Bs + 16 * s2 + 8 + 4 * hh);
+    const cgd_f32x4 b0 = *(const cgd_f32x4*)(Bs + 16 * s2 + 4 * hh), b1 = *(const cgd_f32x4*)(Bs + 16 * s2 + 8 + 4 * hh);
     const float bv[8] = {b0[0], b0[1], b0[2], b0[3], b1[0], b1[1], b1[2], b1[3]};
-    am_bf16x8 bh, bl;
+    cgd_bf16x8 bh, bl;
     am_split8(bv, bh, bl);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.l[s2], bh, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.h[s2], bl, acc, 0, 0, 0);
@@ -154,12 +152,12 @@ __device__ __forceinline__ void am_mma_nt64_pre(am_f32x16& acc, const AmPre& a, 
 }
 // acc += sum_{k<8*NM} A[row][k] * B[k][col]   (A k-contiguous: As = row base; B lane-contiguous: Bs = &B[0][col])
 template <int NM, bool X3>
-__device__ __forceinline__ void am_mma_nn(am_f32x16& acc, const float* As, const float* Bs, int pitchB, int hh) {
+__device__ __forceinline__ void am_mma_nn(cgd_f32x16& acc, const float* As, const float* Bs, int pitchB, int hh) {
   if constexpr (X3) {
     static_assert(NM % 2 == 0, "bf16x3 k-steps are 16 deep");
 #pragma unroll
     for (int s2 = 0; s2 < NM / 2; ++s2) {
-      const am_f32x4 a0 = *(const am_f32x4*)(As + 16 * s2 + 4 * hh), a1 = *(const am_f32x4*)(As + 16 * s2 + 8 + 4 * hh);
+      const cgd_f32x4 a0 = *(const cgd_f32x4*)(As + 16 * s2 + 4 * hh), a1 = *(const cgd_f32x4*)(As + 16 * s2 + 8 + 4 * hh);
       const float av[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
       float bv[8];
 #pragma unroll
@@ -173,14 +171,14 @@ __device__ __forceinline__ void am_mma_nn(am_f32x16& acc, const float* As, const
   }
 #pragma unroll
   for (int m = 0; m < NM; ++m) {
-    const am_f32x4 a = *(const am_f32x4*)(As + 8 * m + 4 * hh);
+    const cgd_f32x4 a = *(const cgd_f32x4*)(As + 8 * m + 4 * hh);
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], Bs[(8 * m + 4 * hh + e) * pitchB], acc, 0, 0, 0);
   }
 }
 // acc += sum_{k<8*NM} A[k][row] * B[k][col]   (both lane-contiguous: As = &A[0][row], Bs = &B[0][col])
 template <int NM, bool X3>
-__device__ __forceinline__ void am_mma_tn(am_f32x16& acc, const float* As, int pitchA, const float* Bs, int pitchB, int hh) {
+__device__ __forceinline__ void am_mma_tn(cgd_f32x16& acc, const float* As, int pitchA, const float* Bs, int pitchB, int hh) {
   if constexpr (X3) {
     static_assert(NM % 2 == 0, "bf16x3 k-steps are 16 deep");
 #pragma unroll
@@ -212,28 +210,28 @@ __device__ __forceinline__ void am_stage64(float* dst, int pitch, const float* s
 #pragma unroll
   for (int e = tid; e < ROWS * 16; e += 256) {
     const int r = e >> 4, u = e & 15;
-    am_f32x4 v = *(const am_f32x4*)(src + (long)(r < nvalid ? r : 0) * ld + 4 * u);
-    if (r >= nvalid) v = am_f32x4{0.f, 0.f, 0.f, 0.f};
-    *(am_f32x4*)&dst[r * pitch + 4 * u] = v;
+    cgd_f32x4 v = *(const cgd_f32x4*)(src + (long)(r < nvalid ? r : 0) * ld + 4 * u);
+    if (r >= nvalid) v = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
+    *(cgd_f32x4*)&dst[r * pitch + 4 * u] = v;
   }
 }
 
 // register-staged variant: issue the global loads of the next tile before computing on the current one (rows >= nvalid: 0)
 template <int ROWS>
-__device__ __forceinline__ void am_gload(am_f32x4 (&rg)[ROWS / 16], const float* src, long ld, int tid, int nvalid) {
+__device__ __forceinline__ void am_gload(cgd_f32x4 (&rg)[ROWS / 16], const float* src, long ld, int tid, int nvalid) {
 #pragma unroll
   for (int i = 0; i < ROWS / 16; ++i) {
     const int e = tid + 256 * i, r = e >> 4, u = e & 15;
-    rg[i] = *(const am_f32x4*)(src + (long)(r < nvalid ? r : 0) * ld + 4 * u);
-    if (r >= nvalid) rg[i] = am_f32x4{0.f, 0.f, 0.f, 0.f};
+    rg[i] = *(const cgd_f32x4*)(src + (long)(r < nvalid ? r : 0) * ld + 4 * u);
+    if (r >= nvalid) rg[i] = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
   }
 }
 template <int ROWS>
-__device__ __forceinline__ void am_sstore(float* dst, int pitch, const am_f32x4 (&rg)[ROWS / 16], int tid) {
+__device__ __forceinline__ void am_sstore(float* dst, int pitch, const cgd_f32x4 (&rg)[ROWS / 16], int tid) {
 #pragma unroll
   for (int i = 0; i < ROWS / 16; ++i) {
     const int e = tid + 256 * i, r = e >> 4, u = e & 15;
-    *(am_f32x4*)&dst[r * pitch + 4 * u] = rg[i];
+    *(cgd_f32x4*)&dst[r * pitch + 4 * u] = rg[i];
   }
 }
 
@@ -254,7 +252,7 @@ __global__ __launch_bounds__(256) void attn_mid_fwd_kernel(const float* __restri
   const int srow = tid >> 3, seg = tid & 7;
   float m_run = -INFINITY, l_run = 0.f;
   AmPre qpre;  // X3: this lane's Q fragments, split once (am_presplit64)
-  am_f32x4 kr[8], vr[8];
+  cgd_f32x4 kr[8], vr[8];
   am_gload<128>(kr, base + ko, ldq, tid, T);
   for (int j = 0; j < nkb; ++j) {
     __syncthreads();
@@ -264,7 +262,7 @@ __global__ __launch_bounds__(256) void attn_mid_fwd_kernel(const float* __restri
       const int jn = j + 1 < nkb ? j + 1 : 0;  // next block (wraps to pass 2's first)
       am_gload<128>(kr, base + (long)jn * 128 * ldq + ko, ldq, tid, T - jn * 128);
     }
-    am_f32x16 sacc;
+    cgd_f32x16 sacc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
     if constexpr (X3) {
@@ -311,7 +309,7 @@ __global__ __launch_bounds__(256) void attn_mid_fwd_kernel(const float* __restri
     il[r] = lrow[row];
   }
   const int fh = w & 1, kh = w >> 1;
-  am_f32x16 oacc;
+  cgd_f32x16 oacc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) oacc[e] = 0.f;
   float* Pg = P + (((long)n * H + h) * T + (long)qb * 32) * Tp + 32 * w + l31;
@@ -325,7 +323,7 @@ __global__ __launch_bounds__(256) void attn_mid_fwd_kernel(const float* __restri
       am_gload<128>(kr, base + (long)(j + 1) * 128 * ldq + ko, ldq, tid, T - (j + 1) * 128);
       am_gload<128>(vr, base + (long)(j + 1) * 128 * ldq + vo, ldq, tid, T - (j + 1) * 128);
     }
-    am_f32x16 sacc;
+    cgd_f32x16 sacc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
     if constexpr (X3)
@@ -395,12 +393,12 @@ __global__ __launch_bounds__(256) void attn_mid_bwd_dq_kernel(const float* __res
 #pragma unroll
   for (int r = 0; r < 16; ++r) dr[r] = Dr[(r & 3) + 8 * (r >> 2) + 4 * hh];
   const int fh = w & 1, kh = w >> 1, nkb = (T + 127) >> 7;
-  am_f32x16 qacc;
+  cgd_f32x16 qacc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) qacc[e] = 0.f;
   AmPre gpre;  // X3: this lane's dO fragments, split once
   const long pbase = (((long)n * H + h) * T + (long)qb * 32) * Tp + 32 * w + l31;
-  am_f32x4 kr[8], vr[8];
+  cgd_f32x4 kr[8], vr[8];
   am_gload<128>(vr, base + vo, ldq, tid, T);
   am_gload<128>(kr, base + ko, ldq, tid, T);
   for (int j = 0; j < nkb; ++j) {
@@ -421,7 +419,7 @@ __global__ __launch_bounds__(256) void attn_mid_bwd_dq_kernel(const float* __res
       am_gload<128>(vr, base + (long)(j + 1) * 128 * ldq + vo, ldq, tid, T - (j + 1) * 128);
       am_gload<128>(kr, base + (long)(j + 1) * 128 * ldq + ko, ldq, tid, T - (j + 1) * 128);
     }
-    am_f32x16 dp;
+    cgd_f32x16 dp;
 #pragma unroll
     for (int e = 0; e < 16; ++e) dp[e] = 0.f;
     if constexpr (X3) {
@@ -467,23 +465,23 @@ __global__ __launch_bounds__(256) void attn_mid_bwd_dkv_kernel(const float* __re
   const int kb = blockIdx.x, h = blockIdx.y, n = blockIdx.z;
   const float* base = qkv + (long)n * T * ldq + h * step;
   const long prow0 = ((long)n * H + h) * T;
-  am_f32x16 acc;
+  cgd_f32x16 acc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-  am_f32x4 pr4[4], sr4[4], gr[8], qr[8];
+  cgd_f32x4 pr4[4], sr4[4], gr[8], qr[8];
   const int ntb = (T + 127) >> 7;  // query rows >= T and key columns >= Tp are zero-filled
-#define DKV_LOAD(TB)                                                                              \
-  {                                                                                               \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                               \
-      const int e = tid + 256 * i, r = e >> 3, u = e & 7;                                         \
-      const bool ok = (TB) * 128 + r < T && kb * 32 + 4 * u < Tp;                                 \
-      const long g = ok ? (prow0 + (TB) * 128 + r) * Tp + kb * 32 + 4 * u : 0L;                   \
-      pr4[i] = *(const am_f32x4*)(P + g);                                                         \
-      sr4[i] = *(const am_f32x4*)(dS + g);                                                        \
-      if (!ok) pr4[i] = sr4[i] = am_f32x4{0.f, 0.f, 0.f, 0.f};                                    \
-    }                                                                                             \
+#define DKV_LOAD(TB)                                                                                 \
+  {                                                                                                  \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                  \
+      const int e = tid + 256 * i, r = e >> 3, u = e & 7;                                            \
+      const bool ok = (TB) * 128 + r < T && kb * 32 + 4 * u < Tp;                                    \
+      const long g = ok ? (prow0 + (TB) * 128 + r) * Tp + kb * 32 + 4 * u : 0L;                      \
+      pr4[i] = *(const cgd_f32x4*)(P + g);                                                           \
+      sr4[i] = *(const cgd_f32x4*)(dS + g);                                                          \
+      if (!ok) pr4[i] = sr4[i] = cgd_f32x4{0.f, 0.f, 0.f, 0.f};                                      \
+    }                                                                                                \
     am_gload<128>(gr, dout + ((long)n * T + (TB) * 128) * lddo + h * 64, lddo, tid, T - (TB) * 128); \
-    am_gload<128>(qr, base + (long)(TB) * 128 * ldq + qo, ldq, tid, T - (TB) * 128);              \
+    am_gload<128>(qr, base + (long)(TB) * 128 * ldq + qo, ldq, tid, T - (TB) * 128);                 \
   }
   DKV_LOAD(0);
   for (int tb = 0; tb < ntb; ++tb) {
@@ -491,8 +489,8 @@ __global__ __launch_bounds__(256) void attn_mid_bwd_dkv_kernel(const float* __re
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int e = tid + 256 * i, r = e >> 3, u = e & 7;
-      *(am_f32x4*)&Pt[r * AM_P40 + 4 * u] = pr4[i];
-      *(am_f32x4*)&St[r * AM_P40 + 4 * u] = sr4[i];
+      *(cgd_f32x4*)&Pt[r * AM_P40 + 4 * u] = pr4[i];
+      *(cgd_f32x4*)&St[r * AM_P40 + 4 * u] = sr4[i];
     }
     am_sstore<128>(dOs, AM_P72, gr, tid);
     am_sstore<128>(Qs, AM_P72, qr, tid);
@@ -520,9 +518,9 @@ __device__ __forceinline__ void am_stage_rows(float* dst, int pitch, const float
 #pragma unroll
   for (int i = 0; i < ROWS / 16; ++i) {
     const int e = tid + 256 * i, r = e >> 4, u = e & 15;
-    am_f32x4 v = am_f32x4{0.f, 0.f, 0.f, 0.f};
-    if (r < T) v = *(const am_f32x4*)(src + (long)r * ld + 4 * u);
-    *(am_f32x4*)&dst[r * pitch + 4 * u] = v;
+    cgd_f32x4 v = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
+    if (r < T) v = *(const cgd_f32x4*)(src + (long)r * ld + 4 * u);
+    *(cgd_f32x4*)&dst[r * pitch + 4 * u] = v;
   }
 }
 
@@ -540,7 +538,7 @@ __global__ __launch_bounds__(256) void attn_s64_fwd_kernel(const float* __restri
   am_stage_rows<64>(Vs, AM_P72, base + vo, ldq, T, tid);
   __syncthreads();
   const int ri = w >> 1, ci = w & 1;
-  am_f32x16 sacc;
+  cgd_f32x16 sacc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
   am_mma_nt64<X3>(sacc, &Qs[(32 * ri + l31) * AM_P68], &Ks[(32 * ci + l31) * AM_P68], hh);
@@ -579,7 +577,7 @@ __global__ __launch_bounds__(256) void attn_s64_fwd_kernel(const float* __restri
   }
   __syncthreads();
   const int fh = ci;
-  am_f32x16 oacc;
+  cgd_f32x16 oacc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) oacc[e] = 0.f;
   am_mma_nn<8, X3>(oacc, &Ss[(32 * ri + l31) * AM_P68], &Vs[32 * fh + l31], AM_P72, hh);
@@ -613,7 +611,7 @@ __global__ __launch_bounds__(256) void attn_s64_bwd_kernel(const float* __restri
   __syncthreads();
   const int ri = w >> 1, ci = w & 1;
   {  // dP = dO V^T
-    am_f32x16 dp;
+    cgd_f32x16 dp;
 #pragma unroll
     for (int e = 0; e < 16; ++e) dp[e] = 0.f;
     am_mma_nt64<X3>(dp, &Gs[(32 * ri + l31) * AM_P68], &Vs[(32 * ci + l31) * AM_P68], hh);
@@ -637,7 +635,7 @@ __global__ __launch_bounds__(256) void attn_s64_bwd_kernel(const float* __restri
   }
   __syncthreads();
   float* ob = dqkv + (long)n * T * lddq + h * step;
-  am_f32x16 acc;
+  cgd_f32x16 acc;
   // dQ[t][c] = alpha * sum_s dS[t][s] K[s][c]
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[e] = 0.f;

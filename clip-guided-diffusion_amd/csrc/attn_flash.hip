@@ -24,12 +24,8 @@
 //   registers) is the one whose registers feed dV^T = dO^T P and dK^T = Q^T dS.
 // All operands are converted to bf16 hi / lo planes ONCE, when a block is staged (the old kernels re-split per use: 33 VALU per MFMA).
 #include "common.h"
+#include "mfma_stage.h"
 #include "kernels.h"
-
-typedef float fa_f32x16 __attribute__((ext_vector_type(16)));
-typedef float fa_f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 fa_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 fa_bf16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -57,7 +53,6 @@ __device__ __forceinline__ int fa_row(int lane, int i) {
 // (round 6) the staging loads are buffer loads: the resource ends behind the block's last valid row, so the rows beyond T are out of range — zeros
 // without an index select and four data selects per row — and a load costs no 64-bit per-lane address arithmetic.  `src`: wave-uniform pointer to the
 // block's row 0, nvalid >= 1 rows exist.
-typedef int fa_i32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ const void* fa_uniform(const void* p) {
   const unsigned long v = (unsigned long)p;
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
@@ -65,55 +60,55 @@ __device__ __forceinline__ const void* fa_uniform(const void* p) {
 }
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t fa_rows_rsrc(const float* src, long ld, int nvalid) {
   const int nv = __builtin_amdgcn_readfirstlane(nvalid < 32 ? nvalid : 32);
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(fa_uniform(src)), 0, nv * (int)ld * 4, 0x00020000);
+  return cgd_buf_rsrc(fa_uniform(src), (unsigned)(nv * (int)ld * 4));
 }
-__device__ __forceinline__ void fa_gload(fa_f32x4 (&rg)[8], const float* __restrict__ src, long ld, int nvalid, int lane) {
+__device__ __forceinline__ void fa_gload(cgd_f32x4 (&rg)[8], const float* __restrict__ src, long ld, int nvalid, int lane) {
   const int dq = lane & 15;
   const __amdgpu_buffer_rsrc_t rs = fa_rows_rsrc(src, ld, nvalid);
 #pragma unroll
   for (int i = 0; i < 8; ++i)
-    rg[i] = __builtin_bit_cast(fa_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (fa_row(lane, i) * (int)ld + 4 * dq) * 4, 0, 0));
+    rg[i] = __builtin_bit_cast(cgd_f32x4, cgd_buf_load16(rs, (fa_row(lane, i) * (int)ld + 4 * dq) * 4, 0));
 }
-__device__ __forceinline__ void fa_store_nat(__bf16* hi, __bf16* lo, const fa_f32x4 (&rg)[8], float scale, int lane) {
+__device__ __forceinline__ void fa_store_nat(__bf16* hi, __bf16* lo, const cgd_f32x4 (&rg)[8], float scale, int lane) {
   const int dq = lane & 15;
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
-    const fa_f32x4 v = rg[i] * scale;
-    fa_bf16x4 h, l;
+    const cgd_f32x4 v = rg[i] * scale;
+    cgd_bf16x4 h, l;
     cgd_split_quad(v, h, l);
     const int off = fa_row(lane, i) * FA_NP + 4 * dq;
-    *(fa_bf16x4*)&hi[off] = h;
-    *(fa_bf16x4*)&lo[off] = l;
+    *(cgd_bf16x4*)&hi[off] = h;
+    *(cgd_bf16x4*)&lo[off] = l;
   }
 }
-__device__ __forceinline__ void fa_store_tr(__bf16* hi, __bf16* lo, const fa_f32x4 (&rg)[8], float scale, int lane) {
+__device__ __forceinline__ void fa_store_tr(__bf16* hi, __bf16* lo, const cgd_f32x4 (&rg)[8], float scale, int lane) {
   const int dq = lane & 15, qg = lane >> 4, tpos = 16 * (qg >> 1) + 8 * (qg & 1);
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    fa_bf16x8 h, l;
+    cgd_bf16x8 h, l;
     const float x8[8] = {rg[0][c] * scale, rg[1][c] * scale, rg[2][c] * scale, rg[3][c] * scale,
                          rg[4][c] * scale, rg[5][c] * scale, rg[6][c] * scale, rg[7][c] * scale};
     cgd_split_oct(x8, h, l);
     const int off = (4 * dq + c) * FA_TP + tpos;
-    *(fa_bf16x8*)&hi[off] = h;
-    *(fa_bf16x8*)&lo[off] = l;
+    *(cgd_bf16x8*)&hi[off] = h;
+    *(cgd_bf16x8*)&lo[off] = l;
   }
 }
 // fragment of the natural layout: row l31, k-step s (columns 16 s + 8 hh ..)
-__device__ __forceinline__ fa_bf16x8 fa_frag_nat(const __bf16* pl, int l31, int hh, int s) {
-  return *(const fa_bf16x8*)&pl[l31 * FA_NP + 16 * s + 8 * hh];
+__device__ __forceinline__ cgd_bf16x8 fa_frag_nat(const __bf16* pl, int l31, int hh, int s) {
+  return *(const cgd_bf16x8*)&pl[l31 * FA_NP + 16 * s + 8 * hh];
 }
 // fragment of the transposed layout: column 32 t + l31, k-step j (positions 16 j + 8 hh ..)
-__device__ __forceinline__ fa_bf16x8 fa_frag_tr(const __bf16* pl, int l31, int hh, int t, int j) {
-  return *(const fa_bf16x8*)&pl[(32 * t + l31) * FA_TP + 16 * j + 8 * hh];
+__device__ __forceinline__ cgd_bf16x8 fa_frag_tr(const __bf16* pl, int l31, int hh, int t, int j) {
+  return *(const cgd_bf16x8*)&pl[(32 * t + l31) * FA_TP + 16 * j + 8 * hh];
 }
-__device__ __forceinline__ void fa_mma3(fa_f32x16& acc, const fa_bf16x8 xh, const fa_bf16x8 xl, const fa_bf16x8 yh, const fa_bf16x8 yl) {
+__device__ __forceinline__ void fa_mma3(cgd_f32x16& acc, const cgd_bf16x8 xh, const cgd_bf16x8 xl, const cgd_bf16x8 yh, const cgd_bf16x8 yl) {
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl, yh, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, yl, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, yh, acc, 0, 0, 0);
 }
 // accumulator registers 8 j .. 8 j + 7 -> the Y operand of k-step j (hi / lo planes)
-__device__ __forceinline__ void fa_split_acc(const float (&p)[16], fa_bf16x8 (&h)[2], fa_bf16x8 (&l)[2]) {
+__device__ __forceinline__ void fa_split_acc(const float (&p)[16], cgd_bf16x8 (&h)[2], cgd_bf16x8 (&l)[2]) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const float x8[8] = {p[8 * j], p[8 * j + 1], p[8 * j + 2], p[8 * j + 3], p[8 * j + 4], p[8 * j + 5], p[8 * j + 6], p[8 * j + 7]};
@@ -122,25 +117,25 @@ __device__ __forceinline__ void fa_split_acc(const float (&p)[16], fa_bf16x8 (&h
 }
 // this lane's operand row (row l31 of the 32-row block at the wave-uniform pointer `blk`, of which nvalid >= 1 exist; columns from 8 hh) straight from
 // global memory: 4 k-steps, scaled; a row beyond the block's valid rows reads zeros (buffer resource, see fa_gload)
-__device__ __forceinline__ void fa_row_frags(fa_bf16x8 (&h)[4], fa_bf16x8 (&l)[4], const float* __restrict__ blk, long ld, int nvalid, int l31, int hh,
+__device__ __forceinline__ void fa_row_frags(cgd_bf16x8 (&h)[4], cgd_bf16x8 (&l)[4], const float* __restrict__ blk, long ld, int nvalid, int l31, int hh,
                                              float scale) {
   const __amdgpu_buffer_rsrc_t rs = fa_rows_rsrc(blk, ld, nvalid);
   const int vo = (l31 * (int)ld + 8 * hh) * 4;
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    const fa_f32x4 a = __builtin_bit_cast(fa_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo + 64 * s, 0, 0));
-    const fa_f32x4 b = __builtin_bit_cast(fa_f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, vo + 64 * s + 16, 0, 0));
+    const cgd_f32x4 a = __builtin_bit_cast(cgd_f32x4, cgd_buf_load16(rs, vo + 64 * s, 0));
+    const cgd_f32x4 b = __builtin_bit_cast(cgd_f32x4, cgd_buf_load16(rs, vo + 64 * s + 16, 0));
     const float v[8] = {a[0] * scale, a[1] * scale, a[2] * scale, a[3] * scale, b[0] * scale, b[1] * scale, b[2] * scale, b[3] * scale};
     cgd_split_oct(v, h[s], l[s]);
   }
 }
 // a wavefront parks its [64 d][32 x] accumulator pair (tiles t = 0, 1; lane = x, registers = d rows) as slab[x][d], fp32 pitch FA_OP
-__device__ __forceinline__ void fa_park(float* slab, const fa_f32x16 (&o)[2], int l31, int hh) {
+__device__ __forceinline__ void fa_park(float* slab, const cgd_f32x16 (&o)[2], int l31, int hh) {
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int g = 0; g < 4; ++g)
-      *(fa_f32x4*)&slab[l31 * FA_OP + 32 * t + 8 * g + 4 * hh] = fa_f32x4{o[t][4 * g], o[t][4 * g + 1], o[t][4 * g + 2], o[t][4 * g + 3]};
+      *(cgd_f32x4*)&slab[l31 * FA_OP + 32 * t + 8 * g + 4 * hh] = cgd_f32x4{o[t][4 * g], o[t][4 * g + 1], o[t][4 * g + 2], o[t][4 * g + 3]};
 }
 
 constexpr int FA_FWD_WAVE = 2 * FA_NPLANE + 2 * FA_TPLANE;  // K natural + V transposed, hi / lo
@@ -161,20 +156,20 @@ __global__ __launch_bounds__(256) void attn_flash_fwd_kernel(const float* __rest
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qb = blockIdx.x, h = blockIdx.y, n = blockIdx.z, q0 = qb * 32;
   const float* __restrict__ base = qkv + (long)n * T * ldq + h * step;
-  fa_bf16x8 qh[4], ql[4];
+  cgd_bf16x8 qh[4], ql[4];
   fa_row_frags(qh, ql, base + qo + (long)q0 * ldq, ldq, T - q0, l31, hh, alpha);
   __bf16* const Kh = lds + w * FA_FWD_WAVE;
   __bf16* const Kl = Kh + FA_NPLANE;
   __bf16* const Vh = Kl + FA_NPLANE;
   __bf16* const Vl = Vh + FA_TPLANE;
   const int nkb = CAUSAL ? ((T + 31) >> 5 < qb + 1 ? (T + 31) >> 5 : qb + 1) : (T + 31) >> 5;
-  fa_f32x16 o[2];
+  cgd_f32x16 o[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int e = 0; e < 16; ++e) o[t][e] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;  // l_run: this lane's keys only (the two half-waves are added at the end)
-  fa_f32x4 kr[8], vr[8];
+  cgd_f32x4 kr[8], vr[8];
   if (w < nkb) {
     fa_gload(kr, base + ko + (long)w * 32 * ldq, ldq, T - w * 32, lane);
     fa_gload(vr, base + vo + (long)w * 32 * ldq, ldq, T - w * 32, lane);
@@ -187,7 +182,7 @@ __global__ __launch_bounds__(256) void attn_flash_fwd_kernel(const float* __rest
       fa_gload(kr, base + ko + (long)(b + 4) * 32 * ldq, ldq, T - (b + 4) * 32, lane);
       fa_gload(vr, base + vo + (long)(b + 4) * 32 * ldq, ldq, T - (b + 4) * 32, lane);
     }
-    fa_f32x16 sacc;
+    cgd_f32x16 sacc;
 #pragma unroll
     for (int e = 0; e < 16; ++e) sacc[e] = 0.f;
 #pragma unroll
@@ -220,7 +215,7 @@ __global__ __launch_bounds__(256) void attn_flash_fwd_kernel(const float* __rest
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int e = 0; e < 16; ++e) o[t][e] *= corr;
-    fa_bf16x8 ph[2], pl[2];
+    cgd_bf16x8 ph[2], pl[2];
     fa_split_acc(p, ph, pl);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -245,23 +240,23 @@ __global__ __launch_bounds__(256) void attn_flash_fwd_kernel(const float* __rest
     M = fmaxf(M, mw[k]);
   }
   float L = 0.f;
-  fa_f32x4 a0 = fa_f32x4{0.f, 0.f, 0.f, 0.f}, a1 = a0;
+  cgd_f32x4 a0 = cgd_f32x4{0.f, 0.f, 0.f, 0.f}, a1 = a0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const float e = __expf(mw[k] - M);  // a wavefront without key blocks: exp(-inf) = 0
     L += e * mls[k][1][q];
     const float* sl = reinterpret_cast<const float*>(lds + k * FA_FWD_WAVE) + q * FA_OP + dc;
-    a0 += *(const fa_f32x4*)sl * e;
-    a1 += *(const fa_f32x4*)(sl + 4) * e;
+    a0 += *(const cgd_f32x4*)sl * e;
+    a1 += *(const cgd_f32x4*)(sl + 4) * e;
   }
   const float inv = 1.f / L;
   const bool qok = q0 + q < T;
   if (qok) {
     const long t = (long)n * T + q0 + q;
-    *(fa_f32x4*)&out[t * ldo + h * 64 + dc] = a0 * inv;
-    *(fa_f32x4*)&out[t * ldo + h * 64 + dc + 4] = a1 * inv;
-    *(fa_f32x4*)&Ocopy[t * ((long)H * 64) + h * 64 + dc] = a0 * inv;
-    *(fa_f32x4*)&Ocopy[t * ((long)H * 64) + h * 64 + dc + 4] = a1 * inv;
+    *(cgd_f32x4*)&out[t * ldo + h * 64 + dc] = a0 * inv;
+    *(cgd_f32x4*)&out[t * ldo + h * 64 + dc + 4] = a1 * inv;
+    *(cgd_f32x4*)&Ocopy[t * ((long)H * 64) + h * 64 + dc] = a0 * inv;
+    *(cgd_f32x4*)&Ocopy[t * ((long)H * 64) + h * 64 + dc + 4] = a1 * inv;
   }
   if ((tid & 7) == 0) lse[((long)n * H + h) * Tq + q0 + q] = qok ? M + __logf(L) : INFINITY;
 }
@@ -287,7 +282,7 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_dq_kernel(const float* __r
     const long t = (long)n * T + (rok ? q0 + q : 0);
     const float* o = Ocopy + t * ((long)H * 64) + h * 64 + seg * 8;
     const float* g = dob + (long)(rok ? q0 + q : 0) * lddo + seg * 8;
-    const fa_f32x4 o0 = *(const fa_f32x4*)o, o1 = *(const fa_f32x4*)(o + 4), g0 = *(const fa_f32x4*)g, g1 = *(const fa_f32x4*)(g + 4);
+    const cgd_f32x4 o0 = *(const cgd_f32x4*)o, o1 = *(const cgd_f32x4*)(o + 4), g0 = *(const cgd_f32x4*)g, g1 = *(const cgd_f32x4*)(g + 4);
     float a = o0[0] * g0[0] + o0[1] * g0[1] + o0[2] * g0[2] + o0[3] * g0[3] + o1[0] * g1[0] + o1[1] * g1[1] + o1[2] * g1[2] + o1[3] * g1[3];
     if (!rok) a = 0.f;
     a += __shfl_xor(a, 1, 64);
@@ -301,7 +296,7 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_dq_kernel(const float* __r
   __syncthreads();
   const float Dq = Dsh[l31];
   const float lq = lse[((long)n * H + h) * Tq + q0 + l31];  // +inf for rows >= T
-  fa_bf16x8 qh[4], ql[4], gh[4], gl[4];
+  cgd_bf16x8 qh[4], ql[4], gh[4], gl[4];
   fa_row_frags(qh, ql, base + qo + (long)q0 * ldq, ldq, T - q0, l31, hh, alpha);
   fa_row_frags(gh, gl, dob + (long)q0 * lddo, lddo, T - q0, l31, hh, 1.f);
   __bf16* const Kh = lds + w * FA_DQ_WAVE;
@@ -311,12 +306,12 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_dq_kernel(const float* __r
   __bf16* const Vh = Ktl + FA_TPLANE;
   __bf16* const Vl = Vh + FA_NPLANE;
   const int nkb = (T + 31) >> 5;
-  fa_f32x16 dq[2];
+  cgd_f32x16 dq[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int e = 0; e < 16; ++e) dq[t][e] = 0.f;
-  fa_f32x4 kr[8], vr[8];
+  cgd_f32x4 kr[8], vr[8];
   if (w < nkb) {
     fa_gload(kr, base + ko + (long)w * 32 * ldq, ldq, T - w * 32, lane);
     fa_gload(vr, base + vo + (long)w * 32 * ldq, ldq, T - w * 32, lane);
@@ -330,7 +325,7 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_dq_kernel(const float* __r
       fa_gload(kr, base + ko + (long)(b + 4) * 32 * ldq, ldq, T - (b + 4) * 32, lane);
       fa_gload(vr, base + vo + (long)(b + 4) * 32 * ldq, ldq, T - (b + 4) * 32, lane);
     }
-    fa_f32x16 sacc, dp;
+    cgd_f32x16 sacc, dp;
 #pragma unroll
     for (int e = 0; e < 16; ++e) sacc[e] = dp[e] = 0.f;
 #pragma unroll
@@ -344,7 +339,7 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_dq_kernel(const float* __r
       const float p = key < T ? __expf(sacc[r] - lq) : 0.f;  // rows >= T: exp(-inf) = 0
       ds[r] = p * (dp[r] - Dq);
     }
-    fa_bf16x8 dh[2], dl[2];
+    cgd_bf16x8 dh[2], dl[2];
     fa_split_acc(ds, dh, dl);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -356,17 +351,17 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_dq_kernel(const float* __r
   fa_park(slab, dq, l31, hh);
   __syncthreads();
   const int q = tid >> 3, dc = (tid & 7) * 8;
-  fa_f32x4 a0 = fa_f32x4{0.f, 0.f, 0.f, 0.f}, a1 = a0;
+  cgd_f32x4 a0 = cgd_f32x4{0.f, 0.f, 0.f, 0.f}, a1 = a0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const float* sl = reinterpret_cast<const float*>(lds + k * FA_DQ_WAVE) + q * FA_OP + dc;
-    a0 += *(const fa_f32x4*)sl;
-    a1 += *(const fa_f32x4*)(sl + 4);
+    a0 += *(const cgd_f32x4*)sl;
+    a1 += *(const cgd_f32x4*)(sl + 4);
   }
   if (q0 + q < T) {
     float* dst = dqkv + ((long)n * T + q0 + q) * lddq + h * step + qo + dc;
-    *(fa_f32x4*)dst = a0 * alpha;
-    *(fa_f32x4*)(dst + 4) = a1 * alpha;
+    *(cgd_f32x4*)dst = a0 * alpha;
+    *(cgd_f32x4*)(dst + 4) = a1 * alpha;
   }
 }
 
@@ -385,7 +380,7 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_dkv_kernel(const float* __
   const float* __restrict__ dob = dout + (long)n * T * lddo + h * 64;
   const float* __restrict__ lrow = lse + ((long)n * H + h) * Tq;
   const float* __restrict__ drow = Dbuf + ((long)n * H + h) * Tq;
-  fa_bf16x8 kh[4], kl[4], vh[4], vl[4];
+  cgd_bf16x8 kh[4], kl[4], vh[4], vl[4];
   fa_row_frags(kh, kl, base + ko + (long)k0 * ldq, ldq, T - k0, l31, hh, 1.f);
   fa_row_frags(vh, vl, base + vo + (long)k0 * ldq, ldq, T - k0, l31, hh, 1.f);
   __bf16* const Qh = lds + w * FA_DKV_WAVE;
@@ -397,12 +392,12 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_dkv_kernel(const float* __
   __bf16* const Gth = Gl + FA_NPLANE;
   __bf16* const Gtl = Gth + FA_TPLANE;
   const int nqb = (T + 31) >> 5;
-  fa_f32x16 dv[2], dk[2];
+  cgd_f32x16 dv[2], dk[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int e = 0; e < 16; ++e) dv[t][e] = dk[t][e] = 0.f;
-  fa_f32x4 qr[8], gr[8];
+  cgd_f32x4 qr[8], gr[8];
   if (w < nqb) {
     fa_gload(qr, base + qo + (long)w * 32 * ldq, ldq, T - w * 32, lane);
     fa_gload(gr, dob + (long)w * 32 * lddo, lddo, T - w * 32, lane);
@@ -418,13 +413,13 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_dkv_kernel(const float* __
       fa_gload(gr, dob + (long)(b + 4) * 32 * lddo, lddo, T - (b + 4) * 32, lane);
     }
     // statistics of the 16 query rows this lane's registers hold: rows 8 g + 4 hh + 0..3 (lse = +inf / D = 0 beyond T)
-    fa_f32x4 lr[4], dr[4];
+    cgd_f32x4 lr[4], dr[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      lr[g] = *(const fa_f32x4*)(lrow + b * 32 + 8 * g + 4 * hh);
-      dr[g] = *(const fa_f32x4*)(drow + b * 32 + 8 * g + 4 * hh);
+      lr[g] = *(const cgd_f32x4*)(lrow + b * 32 + 8 * g + 4 * hh);
+      dr[g] = *(const cgd_f32x4*)(drow + b * 32 + 8 * g + 4 * hh);
     }
-    fa_f32x16 sacc, dp;
+    cgd_f32x16 sacc, dp;
 #pragma unroll
     for (int e = 0; e < 16; ++e) sacc[e] = dp[e] = 0.f;
 #pragma unroll
@@ -437,7 +432,7 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_dkv_kernel(const float* __
       p[r] = __expf(sacc[r] - lr[r >> 2][r & 3]);  // query rows >= T: exp(-inf) = 0
       ds[r] = p[r] * (dp[r] - dr[r >> 2][r & 3]);
     }
-    fa_bf16x8 ph[2], pl[2], dh[2], dl[2];
+    cgd_bf16x8 ph[2], pl[2], dh[2], dl[2];
     fa_split_acc(p, ph, pl);
     fa_split_acc(ds, dh, dl);
 #pragma unroll
@@ -454,21 +449,21 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_dkv_kernel(const float* __
   fa_park(slab + 32 * FA_OP, dk, l31, hh);
   __syncthreads();
   const int key = tid >> 3, dc = (tid & 7) * 8;
-  fa_f32x4 v0 = fa_f32x4{0.f, 0.f, 0.f, 0.f}, v1 = v0, c0 = v0, c1 = v0;
+  cgd_f32x4 v0 = cgd_f32x4{0.f, 0.f, 0.f, 0.f}, v1 = v0, c0 = v0, c1 = v0;
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const float* sl = reinterpret_cast<const float*>(lds + k * FA_DKV_WAVE) + key * FA_OP + dc;
-    v0 += *(const fa_f32x4*)sl;
-    v1 += *(const fa_f32x4*)(sl + 4);
-    c0 += *(const fa_f32x4*)(sl + 32 * FA_OP);
-    c1 += *(const fa_f32x4*)(sl + 32 * FA_OP + 4);
+    v0 += *(const cgd_f32x4*)sl;
+    v1 += *(const cgd_f32x4*)(sl + 4);
+    c0 += *(const cgd_f32x4*)(sl + 32 * FA_OP);
+    c1 += *(const cgd_f32x4*)(sl + 32 * FA_OP + 4);
   }
   if (k0 + key < T) {
     float* dst = dqkv + ((long)n * T + k0 + key) * lddq + h * step;
-    *(fa_f32x4*)(dst + vo + dc) = v0;
-    *(fa_f32x4*)(dst + vo + dc + 4) = v1;
-    *(fa_f32x4*)(dst + ko + dc) = c0;  // Q was staged pre-scaled by alpha: dK = dS^T (alpha Q)
-    *(fa_f32x4*)(dst + ko + dc + 4) = c1;
+    *(cgd_f32x4*)(dst + vo + dc) = v0;
+    *(cgd_f32x4*)(dst + vo + dc + 4) = v1;
+    *(cgd_f32x4*)(dst + ko + dc) = c0;  // Q was staged pre-scaled by alpha: dK = dS^T (alpha Q)
+    *(cgd_f32x4*)(dst + ko + dc + 4) = c1;
   }
 }
 
@@ -505,7 +500,7 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_small_kernel(const float* 
     float a = 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const fa_f32x4 ov = *(const fa_f32x4*)(o + 4 * i), gv = *(const fa_f32x4*)(g + 4 * i);
+      const cgd_f32x4 ov = *(const cgd_f32x4*)(o + 4 * i), gv = *(const cgd_f32x4*)(g + 4 * i);
       a += ov[0] * gv[0] + ov[1] * gv[1] + ov[2] * gv[2] + ov[3] * gv[3];
     }
     if (!rok) a = 0.f;
@@ -519,7 +514,7 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_small_kernel(const float* 
   }
   {  // staging: wavefront 0: Q0, V0; 1: Q1, V1; 2: K0, dO0; 3: K1, dO1
     const int blk = w & 1;
-    fa_f32x4 ra[8], rb[8];
+    cgd_f32x4 ra[8], rb[8];
     const float* pa = (w < 2 ? base + qo : base + ko) + (long)blk * 32 * ldq;
     const float* pb = w < 2 ? base + vo + (long)blk * 32 * ldq : dob + (long)blk * 32 * lddo;
     if (T - blk * 32 > 0) {
@@ -527,7 +522,7 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_small_kernel(const float* 
       fa_gload(rb, pb, w < 2 ? ldq : lddo, T - blk * 32, lane);
     } else {  // T <= 32: the second row block does not exist (its base address lies beyond the sequence): zeros
 #pragma unroll
-      for (int i = 0; i < 8; ++i) ra[i] = rb[i] = fa_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int i = 0; i < 8; ++i) ra[i] = rb[i] = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
     }
     __bf16* ia = lds + (w < 2 ? FA_SM_Q : FA_SM_K) + blk * FA_SM_BLK;
     const float sa = w < 2 ? alpha : 1.f;  // Q is staged pre-scaled: S = (alpha Q) K^T, dK = dS^T (alpha Q)
@@ -551,13 +546,13 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_small_kernel(const float* 
   const __bf16* Gn = lds + FA_SM_G + qi * FA_SM_BLK;
   const __bf16* Gt = Gn + 2 * FA_NPLANE;
   const __bf16* Vn = lds + FA_SM_V + kj * (2 * FA_NPLANE);
-  fa_f32x16 dq[2], dv[2], dk[2];
+  cgd_f32x16 dq[2], dv[2], dk[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
     for (int e = 0; e < 16; ++e) dq[t][e] = dv[t][e] = dk[t][e] = 0.f;
   {  // query in the lane: dQ^T += K^T dS^T
-    fa_f32x16 st, dpt;
+    cgd_f32x16 st, dpt;
 #pragma unroll
     for (int e = 0; e < 16; ++e) st[e] = dpt[e] = 0.f;
 #pragma unroll
@@ -573,7 +568,7 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_small_kernel(const float* 
       const float p = key < T ? __expf(st[r] - lq) : 0.f;
       ds[r] = p * (dpt[r] - Dq);
     }
-    fa_bf16x8 dh[2], dl[2];
+    cgd_bf16x8 dh[2], dl[2];
     fa_split_acc(ds, dh, dl);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -581,7 +576,7 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_small_kernel(const float* 
       for (int j = 0; j < 2; ++j) fa_mma3(dq[t], fa_frag_tr(Kt, l31, hh, t, j), fa_frag_tr(Kt + FA_TPLANE, l31, hh, t, j), dh[j], dl[j]);
   }
   {  // key in the lane: dV^T += dO^T P, dK^T += Q^T dS
-    fa_f32x16 sa, dp;
+    cgd_f32x16 sa, dp;
 #pragma unroll
     for (int e = 0; e < 16; ++e) sa[e] = dp[e] = 0.f;
 #pragma unroll
@@ -592,14 +587,14 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_small_kernel(const float* 
     float p[16], ds[16];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const fa_f32x4 lr = *(const fa_f32x4*)&Lsh[qi * 32 + 8 * g + 4 * hh], dr = *(const fa_f32x4*)&Dsh[qi * 32 + 8 * g + 4 * hh];
+      const cgd_f32x4 lr = *(const cgd_f32x4*)&Lsh[qi * 32 + 8 * g + 4 * hh], dr = *(const cgd_f32x4*)&Dsh[qi * 32 + 8 * g + 4 * hh];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         p[4 * g + e] = __expf(sa[4 * g + e] - lr[e]);  // query rows >= T: exp(-inf) = 0
         ds[4 * g + e] = p[4 * g + e] * (dp[4 * g + e] - dr[e]);
       }
     }
-    fa_bf16x8 ph[2], pl[2], dh[2], dl[2];
+    cgd_bf16x8 ph[2], pl[2], dh[2], dl[2];
     fa_split_acc(p, ph, pl);
     fa_split_acc(ds, dh, dl);
 #pragma unroll
@@ -624,15 +619,15 @@ __global__ __launch_bounds__(256) void attn_flash_bwd_small_kernel(const float* 
   for (int i = 0; i < 4; ++i) {
     const int c = dc + 4 * i;
     // dQ of query block b: wavefronts (b, 0) and (b, 1); dV / dK of key block b: wavefronts (0, b) and (1, b)
-    const fa_f32x4 q0 = *(const fa_f32x4*)&sl[(2 * b + 0) * (3 * 32 * FA_OP) + r * FA_OP + c];
-    const fa_f32x4 q1 = *(const fa_f32x4*)&sl[(2 * b + 1) * (3 * 32 * FA_OP) + r * FA_OP + c];
-    const fa_f32x4 v0 = *(const fa_f32x4*)&sl[(0 + b) * (3 * 32 * FA_OP) + 32 * FA_OP + r * FA_OP + c];
-    const fa_f32x4 v1 = *(const fa_f32x4*)&sl[(2 + b) * (3 * 32 * FA_OP) + 32 * FA_OP + r * FA_OP + c];
-    const fa_f32x4 k0 = *(const fa_f32x4*)&sl[(0 + b) * (3 * 32 * FA_OP) + 2 * 32 * FA_OP + r * FA_OP + c];
-    const fa_f32x4 k1 = *(const fa_f32x4*)&sl[(2 + b) * (3 * 32 * FA_OP) + 2 * 32 * FA_OP + r * FA_OP + c];
-    *(fa_f32x4*)(dst + qo + c) = (q0 + q1) * alpha;
-    *(fa_f32x4*)(dst + vo + c) = v0 + v1;
-    *(fa_f32x4*)(dst + ko + c) = k0 + k1;
+    const cgd_f32x4 q0 = *(const cgd_f32x4*)&sl[(2 * b + 0) * (3 * 32 * FA_OP) + r * FA_OP + c];
+    const cgd_f32x4 q1 = *(const cgd_f32x4*)&sl[(2 * b + 1) * (3 * 32 * FA_OP) + r * FA_OP + c];
+    const cgd_f32x4 v0 = *(const cgd_f32x4*)&sl[(0 + b) * (3 * 32 * FA_OP) + 32 * FA_OP + r * FA_OP + c];
+    const cgd_f32x4 v1 = *(const cgd_f32x4*)&sl[(2 + b) * (3 * 32 * FA_OP) + 32 * FA_OP + r * FA_OP + c];
+    const cgd_f32x4 k0 = *(const cgd_f32x4*)&sl[(0 + b) * (3 * 32 * FA_OP) + 2 * 32 * FA_OP + r * FA_OP + c];
+    const cgd_f32x4 k1 = *(const cgd_f32x4*)&sl[(2 + b) * (3 * 32 * FA_OP) + 2 * 32 * FA_OP + r * FA_OP + c];
+    *(cgd_f32x4*)(dst + qo + c) = (q0 + q1) * alpha;
+    *(cgd_f32x4*)(dst + vo + c) = v0 + v1;
+    *(cgd_f32x4*)(dst + ko + c) = k0 + k1;
   }
 }
 

@@ -15,7 +15,7 @@ pids=()
 for src in gemm hconv kconv wconv hgemm conv_thin norm elem attn attn_flash guidance plms cutaug unet vit text resnet lpips capi; do
   obj=$OUT/$src.o
   objs+=("$obj")
-  if [[ ! -f $obj || $src.hip -nt $obj || common.h -nt $obj || kernels.h -nt $obj || net.h -nt $obj || guidance.h -nt $obj \
+  if [[ ! -f $obj || $src.hip -nt $obj || common.h -nt $obj || mfma_stage.h -nt $obj || kernels.h -nt $obj || net.h -nt $obj || guidance.h -nt $obj \
         || ../../include/cgd_mi355x.h -nt $obj || build_asan.sh -nt $obj ]]; then
     $HIPCC $FLAGS -c $src.hip -o $obj 2> $OUT/$src.log &
     pids+=($!)

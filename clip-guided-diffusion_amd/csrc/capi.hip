@@ -3,6 +3,7 @@
 #include "common.h"
 #include "guidance.h"
 #include "kernels.h"
+#include "mfma_stage.h"
 
 #define S(stream) ((hipStream_t)(stream))
 
@@ -332,14 +333,12 @@ int cgd_op_conv3x3_wino_ex(cgd_ctx* ctx, const float* x, int ldx, const float* w
 }
 }  // extern "C" (the calibration kernel below is C++)
 namespace {
-typedef __bf16 cal_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float cal_f32x16 __attribute__((ext_vector_type(16)));
 // the loop of benchmarks/ubench/mfma_peak.hip with 4 independent accumulators: 12 MFMAs per iteration, operands in registers
 __global__ __launch_bounds__(256) void mfma_peak_kernel(float* out, int iters) {
-  cal_f32x16 acc[4];
+  cgd_f32x16 acc[4];
   for (int a = 0; a < 4; ++a)
     for (int e = 0; e < 16; ++e) acc[a][e] = 0.f;
-  cal_bf16x8 x, y;
+  cgd_bf16x8 x, y;
   for (int e = 0; e < 8; ++e) {
     x[e] = (__bf16)(float)((threadIdx.x * 7 + e) % 13 - 6);
     y[e] = (__bf16)(0.001f * (float)((threadIdx.x * 3 + e) % 11 - 5));

@@ -1,6 +1,7 @@
 // Thin direct 3x3 convolutions for the 3- and 6-channel ends of the UNet (stem, head and their dgrads):
 // NCHW <-> NHWC conversion is folded into the kernels, so the public (B,3,H,W)/(B,6,H,W) tensors never get a padded copy.
 #include "common.h"
+#include "mfma_stage.h"
 
 namespace {
 
@@ -107,7 +108,6 @@ __global__ __launch_bounds__(256) void conv_thin_out_kernel(const float* __restr
 //   conv_in  (CIN -> Cout): im2col of the thin NCHW input [pix][KP] (KP = 32 / 64 >= 9*CIN), then C = A W^T on the MFMA GEMM.
 //   thin_out (Cin -> COUT): T[pix][tap*COUT + co] = sum_ci x[pix][ci] w[co][tap][ci] on the MFMA GEMM (x is read ONCE instead
 //                           of 9 times), then a 9-neighbour gather of T into the NCHW output.
-typedef float ct_f32x4 __attribute__((ext_vector_type(4)));
 
 template <int CIN, int KP>
 __global__ __launch_bounds__(256) void thin_im2col_kernel(const float* __restrict__ x, float* __restrict__ out, int Bn, int H, int W) {
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void thin_im2col_kernel(const float* __restric
     const int b = (int)(pix / ((long)H * W));
     const int rem = (int)(pix - (long)b * H * W);
     const int yy = rem / W, xx = rem - yy * W;
-    ct_f32x4 v;
+    cgd_f32x4 v;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int k = 4 * k4 + e;
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void thin_im2col_kernel(const float* __restric
       }
       v[e] = val;
     }
-    *(ct_f32x4*)(out + pix * KP + 4 * k4) = v;
+    *(cgd_f32x4*)(out + pix * KP + 4 * k4) = v;
   }
 }
 
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256) void thin_in_direct_kernel(const float* __rest
     const int sy = y0 + py - 1, sx = x0 + px - 1;
     patch[(ci * 6 + py) * PWP + px] = ((unsigned)sy < (unsigned)H && (unsigned)sx < (unsigned)W) ? xb[((long)ci * H + sy) * W + sx] : 0.f;
   }
-  ct_f32x4 wr[KK];
+  cgd_f32x4 wr[KK];
 #pragma unroll
   for (int h = 0; h < KK; h += KH) {  // CIN = 6: two slabs through the same 27 x Cout floats of LDS
     if (h) __syncthreads();
@@ -216,15 +216,15 @@ __global__ __launch_bounds__(256) void thin_in_direct_kernel(const float* __rest
     }
     __syncthreads();
 #pragma unroll
-    for (int k = 0; k < KH; ++k) wr[h + k] = *(const ct_f32x4*)&wsm[k * Cout + 4 * q];
+    for (int k = 0; k < KH; ++k) wr[h + k] = *(const cgd_f32x4*)&wsm[k * Cout + 4 * q];
   }
   const int yy = y0 + wave;
   if (pl >= ppi || yy >= H) return;
-  const ct_f32x4 bv = bias ? *(const ct_f32x4*)(bias + 4 * q) : ct_f32x4{0.f, 0.f, 0.f, 0.f};
+  const cgd_f32x4 bv = bias ? *(const cgd_f32x4*)(bias + 4 * q) : cgd_f32x4{0.f, 0.f, 0.f, 0.f};
   float* yrow = y + ((long)b * H + yy) * W * ldy + 4 * q;
   const int xend = min(TW, W - x0);
   for (int p = pl; p < xend; p += ppi) {
-    ct_f32x4 acc = bv;
+    cgd_f32x4 acc = bv;
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
@@ -234,7 +234,7 @@ __global__ __launch_bounds__(256) void thin_in_direct_kernel(const float* __rest
           const float v = patch[(ci * 6 + wave + ky) * PWP + p + kx];
           acc += v * wr[(ky * 3 + kx) * CIN + ci];
         }
-    *(ct_f32x4*)(yrow + (long)(x0 + p) * ldy) = acc;
+    *(cgd_f32x4*)(yrow + (long)(x0 + p) * ldy) = acc;
   }
 }
 

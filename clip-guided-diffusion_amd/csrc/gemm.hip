@@ -16,11 +16,7 @@
 // blockIdx -> tile mapping is XCD aware: the 8 XCDs each get a contiguous run of tiles so that the
 // N-tiles of one M-panel and the halo rows of neighbouring M-panels hit the same L2.
 #include "common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "mfma_stage.h"
 
 namespace {
 
@@ -45,18 +41,6 @@ struct Smem<2, BM, BN> {
   __bf16 ah[2][BM][PH];
   __bf16 bh[2][BN][PH];
 };
-
-__device__ __forceinline__ bf16x4 to_bf16x4(const f32x4 v) {
-  bf16x4 r;
-  r[0] = (__bf16)v.x;
-  r[1] = (__bf16)v.y;
-  r[2] = (__bf16)v.z;
-  r[3] = (__bf16)v.w;
-  return r;
-}
-__device__ __forceinline__ f32x4 residual4(const f32x4 v, const bf16x4 hi) {
-  return f32x4{v.x - (float)hi[0], v.y - (float)hi[1], v.z - (float)hi[2], v.w - (float)hi[3]};
-}
 
 template <int MODE, int BM, int BN, int WM, int WN, int PF>
 __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void igemm_kernel(const float* __restrict__ Ag, const float* __restrict__ Bg, float* Cg,
@@ -130,76 +114,76 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void igemm_kernel(const
     b_off[j] = (long)n * p.ldb;
   }
 
-  f32x4 ra0[RA], rb0[RB];
-  f32x4 ra1[PF == 2 ? RA : 1], rb1[PF == 2 ? RB : 1];
-  const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
+  cgd_f32x4 ra0[RA], rb0[RB];
+  cgd_f32x4 ra1[PF == 2 ? RA : 1], rb1[PF == 2 ? RB : 1];
+  const cgd_f32x4 z4 = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
 
   // validity bit masks of the staged rows: the zero fill is applied when the registers are written to LDS, so the
   // loads stay in flight across the MFMA block instead of being waited for by an early select
   unsigned ma0 = 0, mb0 = 0, ma1 = 0, mb1 = 0;
 
-#define GLOAD(KT, RA_, RB_, MA_, MB_)                                                              \
-  {                                                                                                \
-    const int kbase = (KT) * BK;                                                                   \
-    const int kk = kbase + c4 * 4;                                                                 \
-    MA_ = 0;                                                                                       \
-    MB_ = 0;                                                                                       \
-    if (p.conv) {                                                                                  \
-      const int tap = kbase / p.Cin, ci = kbase - tap * p.Cin + c4 * 4;                            \
-      const int ky = tap / 3, kx = tap - 3 * ky;                                                   \
-      _Pragma("unroll") for (int j = 0; j < RA; ++j) {                                             \
-        int yy = a_y[j] + ky - 1, xx = a_x[j] + kx - 1;                                            \
-        const bool ok = a_ok[j] && (unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)p.W;   \
-        if (p.ups) {                                                                               \
-          yy >>= 1;                                                                                \
-          xx >>= 1;                                                                                \
-        }                                                                                          \
-        /* always load from a valid global address, then select the VALUE: `ok ? *p : 0` would let the compiler   \
-           select between the global pointer and a stack slot holding 0 (flat_load + scratch + coupled waitcnts) */   \
-        RA_[j] = *(const f32x4*)(A + (ok ? (a_off[j] + (long)yy * Ws + xx) * p.lda + ci : 0L));    \
-        MA_ |= ok ? (1u << j) : 0u;                                                                \
-      }                                                                                            \
-    } else {                                                                                       \
-      _Pragma("unroll") for (int j = 0; j < RA; ++j) {                                             \
-        const bool ok = a_ok[j] && kk < p.K;                                                       \
-        RA_[j] = *(const f32x4*)(A + (ok ? a_off[j] + kk : 0L));                                   \
-        MA_ |= ok ? (1u << j) : 0u;                                                                \
-      }                                                                                            \
-    }                                                                                              \
-    _Pragma("unroll") for (int j = 0; j < RB; ++j) {                                               \
-      const bool ok = b_ok[j] && kk < p.K;                                                         \
-      RB_[j] = *(const f32x4*)(B + (ok ? b_off[j] + kk : 0L));                                     \
-      MB_ |= ok ? (1u << j) : 0u;                                                                  \
-    }                                                                                              \
+#define GLOAD(KT, RA_, RB_, MA_, MB_)                                                                               \
+  {                                                                                                                 \
+    const int kbase = (KT) * BK;                                                                                    \
+    const int kk = kbase + c4 * 4;                                                                                  \
+    MA_ = 0;                                                                                                        \
+    MB_ = 0;                                                                                                        \
+    if (p.conv) {                                                                                                   \
+      const int tap = kbase / p.Cin, ci = kbase - tap * p.Cin + c4 * 4;                                             \
+      const int ky = tap / 3, kx = tap - 3 * ky;                                                                    \
+      _Pragma("unroll") for (int j = 0; j < RA; ++j) {                                                              \
+        int yy = a_y[j] + ky - 1, xx = a_x[j] + kx - 1;                                                             \
+        const bool ok = a_ok[j] && (unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)p.W;                    \
+        if (p.ups) {                                                                                                \
+          yy >>= 1;                                                                                                 \
+          xx >>= 1;                                                                                                 \
+        }                                                                                                           \
+        /* always load from a valid global address, then select the VALUE: `ok ? *p : 0` would let the compiler     \
+           select between the global pointer and a stack slot holding 0 (flat_load + scratch + coupled waitcnts) */ \
+        RA_[j] = *(const cgd_f32x4*)(A + (ok ? (a_off[j] + (long)yy * Ws + xx) * p.lda + ci : 0L));                 \
+        MA_ |= ok ? (1u << j) : 0u;                                                                                 \
+      }                                                                                                             \
+    } else {                                                                                                        \
+      _Pragma("unroll") for (int j = 0; j < RA; ++j) {                                                              \
+        const bool ok = a_ok[j] && kk < p.K;                                                                        \
+        RA_[j] = *(const cgd_f32x4*)(A + (ok ? a_off[j] + kk : 0L));                                                \
+        MA_ |= ok ? (1u << j) : 0u;                                                                                 \
+      }                                                                                                             \
+    }                                                                                                               \
+    _Pragma("unroll") for (int j = 0; j < RB; ++j) {                                                                \
+      const bool ok = b_ok[j] && kk < p.K;                                                                          \
+      RB_[j] = *(const cgd_f32x4*)(B + (ok ? b_off[j] + kk : 0L));                                                  \
+      MB_ |= ok ? (1u << j) : 0u;                                                                                   \
+    }                                                                                                               \
   }
 
-#define SSTORE(BUF, RA_, RB_, MA_, MB_)                                                            \
-  {                                                                                                \
-    _Pragma("unroll") for (int j = 0; j < RA; ++j) {                                               \
-      const int row = r0 + RPP * j;                                                                \
-      const f32x4 v = (MA_ >> j) & 1u ? RA_[j] : z4;                                               \
-      if constexpr (MODE == 0) {                                                                   \
-        *(f32x4*)&sm.a[BUF][row][c4 * 4] = v;                                                      \
-      } else {                                                                                     \
-        const bf16x4 hi = to_bf16x4(v);                                                            \
-        *(bf16x4*)&sm.ah[BUF][row][c4 * 4] = hi;                                                   \
-        if constexpr (MODE == 1) *(bf16x4*)&sm.al[BUF][row][c4 * 4] = to_bf16x4(residual4(v, hi)); \
-      }                                                                                            \
-    }                                                                                              \
-    _Pragma("unroll") for (int j = 0; j < RB; ++j) {                                               \
-      const int row = r0 + RPP * j;                                                                \
-      const f32x4 v = (MB_ >> j) & 1u ? RB_[j] : z4;                                               \
-      if constexpr (MODE == 0) {                                                                   \
-        *(f32x4*)&sm.b[BUF][row][c4 * 4] = v;                                                      \
-      } else {                                                                                     \
-        const bf16x4 hi = to_bf16x4(v);                                                            \
-        *(bf16x4*)&sm.bh[BUF][row][c4 * 4] = hi;                                                   \
-        if constexpr (MODE == 1) *(bf16x4*)&sm.bl[BUF][row][c4 * 4] = to_bf16x4(residual4(v, hi)); \
-      }                                                                                            \
-    }                                                                                              \
+#define SSTORE(BUF, RA_, RB_, MA_, MB_)                                                                        \
+  {                                                                                                            \
+    _Pragma("unroll") for (int j = 0; j < RA; ++j) {                                                           \
+      const int row = r0 + RPP * j;                                                                            \
+      const cgd_f32x4 v = (MA_ >> j) & 1u ? RA_[j] : z4;                                                       \
+      if constexpr (MODE == 0) {                                                                               \
+        *(cgd_f32x4*)&sm.a[BUF][row][c4 * 4] = v;                                                              \
+      } else {                                                                                                 \
+        const cgd_bf16x4 hi = cgd_to_bf16x4(v);                                                                \
+        *(cgd_bf16x4*)&sm.ah[BUF][row][c4 * 4] = hi;                                                           \
+        if constexpr (MODE == 1) *(cgd_bf16x4*)&sm.al[BUF][row][c4 * 4] = cgd_to_bf16x4(cgd_residual4(v, hi)); \
+      }                                                                                                        \
+    }                                                                                                          \
+    _Pragma("unroll") for (int j = 0; j < RB; ++j) {                                                           \
+      const int row = r0 + RPP * j;                                                                            \
+      const cgd_f32x4 v = (MB_ >> j) & 1u ? RB_[j] : z4;                                                       \
+      if constexpr (MODE == 0) {                                                                               \
+        *(cgd_f32x4*)&sm.b[BUF][row][c4 * 4] = v;                                                              \
+      } else {                                                                                                 \
+        const cgd_bf16x4 hi = cgd_to_bf16x4(v);                                                                \
+        *(cgd_bf16x4*)&sm.bh[BUF][row][c4 * 4] = hi;                                                           \
+        if constexpr (MODE == 1) *(cgd_bf16x4*)&sm.bl[BUF][row][c4 * 4] = cgd_to_bf16x4(cgd_residual4(v, hi)); \
+      }                                                                                                        \
+    }                                                                                                          \
   }
 
-  f32x16 acc[MB][NB];
+  cgd_f32x16 acc[MB][NB];
 #pragma unroll
   for (int i = 0; i < MB; ++i)
 #pragma unroll
@@ -207,42 +191,42 @@ __global__ __launch_bounds__((BM / WM) * (BN / WN) * 64) void igemm_kernel(const
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-#define COMPUTE(BUF)                                                                                                     \
-  {                                                                                                                      \
-    if constexpr (MODE == 0) {                                                                                           \
-      f32x4 fa[MB][4], fb[NB][4];                                                                                       \
-      _Pragma("unroll") for (int i = 0; i < MB; ++i) _Pragma("unroll") for (int q = 0; q < 4; ++q)                       \
-          fa[i][q] = *(const f32x4*)&sm.a[BUF][wm * WM + i * 32 + l31][hh * 16 + q * 4];                               \
-      _Pragma("unroll") for (int j = 0; j < NB; ++j) _Pragma("unroll") for (int q = 0; q < 4; ++q)                       \
-          fb[j][q] = *(const f32x4*)&sm.b[BUF][wn * WN + j * 32 + l31][hh * 16 + q * 4];                               \
-      _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                                    \
-        _Pragma("unroll") for (int i = 0; i < MB; ++i) _Pragma("unroll") for (int j = 0; j < NB; ++j) {                  \
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][q].x, fb[j][q].x, acc[i][j], 0, 0, 0);                  \
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][q].y, fb[j][q].y, acc[i][j], 0, 0, 0);                  \
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][q].z, fb[j][q].z, acc[i][j], 0, 0, 0);                  \
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][q].w, fb[j][q].w, acc[i][j], 0, 0, 0);                  \
-        }                                                                                                                \
-      }                                                                                                                  \
-    } else {                                                                                                             \
-      _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                                 \
-        bf16x8 ah[MB], bh[NB], al[MB], bl[NB];                                                                           \
-        _Pragma("unroll") for (int i = 0; i < MB; ++i) {                                                                 \
-          ah[i] = *(const bf16x8*)&sm.ah[BUF][wm * WM + i * 32 + l31][ks * 16 + hh * 8];                                 \
-          if constexpr (MODE == 1) al[i] = *(const bf16x8*)&sm.al[BUF][wm * WM + i * 32 + l31][ks * 16 + hh * 8];       \
-        }                                                                                                                \
-        _Pragma("unroll") for (int j = 0; j < NB; ++j) {                                                                 \
-          bh[j] = *(const bf16x8*)&sm.bh[BUF][wn * WN + j * 32 + l31][ks * 16 + hh * 8];                                 \
-          if constexpr (MODE == 1) bl[j] = *(const bf16x8*)&sm.bl[BUF][wn * WN + j * 32 + l31][ks * 16 + hh * 8];       \
-        }                                                                                                                \
-        _Pragma("unroll") for (int i = 0; i < MB; ++i) _Pragma("unroll") for (int j = 0; j < NB; ++j) {                  \
-          if constexpr (MODE == 1) {                                                                                     \
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);                       \
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);                       \
-          }                                                                                                              \
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);                         \
-        }                                                                                                                \
-      }                                                                                                                  \
-    }                                                                                                                    \
+#define COMPUTE(BUF)                                                                                                  \
+  {                                                                                                                   \
+    if constexpr (MODE == 0) {                                                                                        \
+      cgd_f32x4 fa[MB][4], fb[NB][4];                                                                                 \
+      _Pragma("unroll") for (int i = 0; i < MB; ++i) _Pragma("unroll") for (int q = 0; q < 4; ++q)                    \
+          fa[i][q] = *(const cgd_f32x4*)&sm.a[BUF][wm * WM + i * 32 + l31][hh * 16 + q * 4];                          \
+      _Pragma("unroll") for (int j = 0; j < NB; ++j) _Pragma("unroll") for (int q = 0; q < 4; ++q)                    \
+          fb[j][q] = *(const cgd_f32x4*)&sm.b[BUF][wn * WN + j * 32 + l31][hh * 16 + q * 4];                          \
+      _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                                 \
+        _Pragma("unroll") for (int i = 0; i < MB; ++i) _Pragma("unroll") for (int j = 0; j < NB; ++j) {               \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][q].x, fb[j][q].x, acc[i][j], 0, 0, 0);               \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][q].y, fb[j][q].y, acc[i][j], 0, 0, 0);               \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][q].z, fb[j][q].z, acc[i][j], 0, 0, 0);               \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][q].w, fb[j][q].w, acc[i][j], 0, 0, 0);               \
+        }                                                                                                             \
+      }                                                                                                               \
+    } else {                                                                                                          \
+      _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                              \
+        cgd_bf16x8 ah[MB], bh[NB], al[MB], bl[NB];                                                                    \
+        _Pragma("unroll") for (int i = 0; i < MB; ++i) {                                                              \
+          ah[i] = *(const cgd_bf16x8*)&sm.ah[BUF][wm * WM + i * 32 + l31][ks * 16 + hh * 8];                          \
+          if constexpr (MODE == 1) al[i] = *(const cgd_bf16x8*)&sm.al[BUF][wm * WM + i * 32 + l31][ks * 16 + hh * 8]; \
+        }                                                                                                             \
+        _Pragma("unroll") for (int j = 0; j < NB; ++j) {                                                              \
+          bh[j] = *(const cgd_bf16x8*)&sm.bh[BUF][wn * WN + j * 32 + l31][ks * 16 + hh * 8];                          \
+          if constexpr (MODE == 1) bl[j] = *(const cgd_bf16x8*)&sm.bl[BUF][wn * WN + j * 32 + l31][ks * 16 + hh * 8]; \
+        }                                                                                                             \
+        _Pragma("unroll") for (int i = 0; i < MB; ++i) _Pragma("unroll") for (int j = 0; j < NB; ++j) {               \
+          if constexpr (MODE == 1) {                                                                                  \
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);                    \
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);                    \
+          }                                                                                                           \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);                      \
+        }                                                                                                             \
+      }                                                                                                               \
+    }                                                                                                                 \
   }
 
   if constexpr (PF == 1) {

@@ -14,28 +14,11 @@
 // (The first version of this kernel — 256-pixel row-segment tiles, 13 staging passes, sectioned issue — is in the history:
 //  profiles/r1_hconv_variants_microbench.json.)
 #include "common.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+#include "mfma_stage.h"
 
 namespace {
 
 constexpr int HB_M = 256, HB_N = 128, HPH = 40;  // 16x16-pixel tile, channel tile, LDS row pitch (bf16 elements)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));  // native vector: value selects stay in registers
-
-__device__ __forceinline__ bf16x4 to_bf16x4(const f32x4 v) {
-  bf16x4 r;
-  r[0] = (__bf16)v.x;
-  r[1] = (__bf16)v.y;
-  r[2] = (__bf16)v.z;
-  r[3] = (__bf16)v.w;
-  return r;
-}
-__device__ __forceinline__ f32x4 residual4(const f32x4 v, const bf16x4 hi) {
-  return f32x4{v.x - (float)hi[0], v.y - (float)hi[1], v.z - (float)hi[2], v.w - (float)hi[3]};
-}
 
 struct HConvParams {
   const float* A;
@@ -51,7 +34,6 @@ struct HConvParams {
   int nmajor;  // 1: channel-tile major order within an XCD's run of tiles (the <= 64x64-pixel levels, where the packed weights
                // are the larger operand: an XCD then owns a few output-channel panels and keeps their weights in its L2)
 };
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // hconv2_kernel
@@ -86,16 +68,8 @@ constexpr int NPASS2 = 6;   // staging passes (both tile heights)
 //     stay exact zeros (they are padding of the ACTIVATED tensor).
 // hconv2_kernel's patch pixels and weight fragments come through buffer loads (round 6, as in wconv.hip / kconv.hip): scalar chunk / k-step
 // offsets instead of 64-bit per-lane address arithmetic, a padding pixel is an out-of-range offset (zeros, no select, no memory access), and the
-// prefetches of the slice's last chunk (its own patch and fragments again, on clamped indices) get a resource of zero records.
-typedef int hci32x4 __attribute__((ext_vector_type(4)));
-// neg: wave-uniform, < 0 = the load is wanted; `records` = size of the resource when wanted (lanes with voffset >= records read zeros)
-__device__ __forceinline__ hci32x4 hc_buf_load16(const void* base, int neg, unsigned records, int voffset, int soffset) {
-  int m;
-  asm("s_ashr_i32 %0, %1, 31" : "=s"(m) : "s"(neg) : "scc");  // (a bool select would go through v_cndmask and force a readfirstlane loop per load)
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)((unsigned)m & records), 0x00020000);
-  return __builtin_amdgcn_raw_buffer_load_b128(r, voffset, soffset, 0);
-}
-constexpr int HC_OOB = (int)0x80000000;
+// prefetches of the slice's last chunk (its own patch and fragments again, on clamped indices) get a resource of zero records (mfma_stage.h
+// cgd_buf_load16_if).
 
 template <int MODE, int TH, int NJ, bool GN>
 __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict__ Ag, const uint4* __restrict__ Bg, float* Cg,
@@ -151,7 +125,7 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
   }
   int poffb[NPASS2];  // the same as byte offsets for the buffer loads: padding and beyond-the-patch slots are out of range
 #pragma unroll
-  for (int j = 0; j < NPASS2; ++j) poffb[j] = poff[j] >= 0 ? poff[j] * 4 : HC_OOB;
+  for (int j = 0; j < NPASS2; ++j) poffb[j] = poff[j] >= 0 ? poff[j] * 4 : CGD_OOB;
   // this lane's pixels (one per 32-pixel block of the wavefront's NI): patch position and output row
   int fro[NI];
   long mrow[NI];  // output row of this lane's pixel, or -1 for a tile column beyond the image (W not a multiple of 16)
@@ -182,7 +156,7 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
   const int bj1_b = (nb0_s + 1 < nbN) ? (int)(bstride_nb * 16) : 0;
   (void)bj1_b;  // (unread when NJ == 1)
 
-  f32x16 acc[NI][NJ];
+  cgd_f32x16 acc[NI][NJ];
 #pragma unroll
   for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -190,78 +164,77 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-  // cgd_split_quad (common.h) everywhere but in the largest instantiation: there the longer IR keeps the fully unrolled chunk loop from being formed
+  // cgd_split_quad (mfma_stage.h) everywhere but in the largest instantiation: there the longer IR keeps the fully unrolled chunk loop from being formed
   // before the last scalar-replacement pass and the weight ring lands in scratch memory
   constexpr bool SPLITQ = !(GN && NJ == 2 && TH == 8);
-  f32x4 pr[NPASS2];
-  f32x4 ga[GN ? 2 : 1];  // {a0, b0, a1, b1}, {a2, b2, a3, b3} of this thread's 4 channels of the chunk being staged
-  const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
+  cgd_f32x4 pr[NPASS2];
+  cgd_f32x4 ga[GN ? 2 : 1];  // {a0, b0, a1, b1}, {a2, b2, a3, b3} of this thread's 4 channels of the chunk being staged
+  const cgd_f32x4 z4 = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
   const float* __restrict__ gnimg = GN ? gng + ((long)img * p.Cin + c4 * 4) * 2 : nullptr;
 
   // CH: the chunk to fetch; WANT < 0: it exists (else: nothing is read)
-#define PATCH_LOAD2(CH, WANT)                                                                       \
-  {                                                                                                 \
-    if constexpr (GN) {                                                                             \
-      const int cg_ = (WANT) < 0 ? (CH) : (CH) - 1;                                                 \
-      ga[0] = *(const f32x4*)(gnimg + cg_ * 64);                                                    \
-      ga[1] = *(const f32x4*)(gnimg + cg_ * 64 + 4);                                                \
-    }                                                                                               \
-    _Pragma("unroll") for (int j = 0; j < NPASS2; ++j)                                              \
-        pr[j] = __builtin_bit_cast(f32x4, hc_buf_load16(Aimg, (WANT), 0x80000000u, poffb[j], (CH) * 128)); \
+#define PATCH_LOAD2(CH, WANT)                                                                                      \
+  {                                                                                                                \
+    if constexpr (GN) {                                                                                            \
+      const int cg_ = (WANT) < 0 ? (CH) : (CH) - 1;                                                                \
+      ga[0] = *(const cgd_f32x4*)(gnimg + cg_ * 64);                                                               \
+      ga[1] = *(const cgd_f32x4*)(gnimg + cg_ * 64 + 4);                                                           \
+    }                                                                                                              \
+    _Pragma("unroll") for (int j = 0; j < NPASS2; ++j)                                                             \
+        pr[j] = __builtin_bit_cast(cgd_f32x4, cgd_buf_load16_if(Aimg, 0x80000000u, (WANT), poffb[j], (CH) * 128)); \
   }
-#define GN_SILU(X, A, B) ({ const float u_ = (X) * (A) + (B); u_ * __builtin_amdgcn_rcpf(1.f + __expf(-u_)); })  /* v_rcp_f32: 1 ulp */
-#define PATCH_STORE2(DSTB, J0, J1)                                                                  \
-  {                                                                                                 \
-    _Pragma("unroll") for (int j = J0; j < J1; ++j) {                                               \
-      f32x4 v = pr[j];                                                                              \
-      if constexpr (GN)                                                                             \
-        v = f32x4{GN_SILU(v.x, ga[0].x, ga[0].y), GN_SILU(v.y, ga[0].z, ga[0].w), GN_SILU(v.z, ga[1].x, ga[1].y),  \
-                  GN_SILU(v.w, ga[1].z, ga[1].w)};                                                  \
-      if constexpr (GN) v = poff[j] >= 0 ? v : z4; /* (the loads return zeros for padding; silu(b) need not be 0) */ \
-      if constexpr (MODE == 1 && SPLITQ) {                                                          \
-        bf16x4 hi, lo;                                                                              \
-        cgd_split_quad(v, hi, lo);                                                                  \
-        *(bf16x4*)&(DSTB)[soff[j]] = hi;                                                            \
-        *(bf16x4*)&(DSTB)[PLANE + soff[j]] = lo;                                                    \
-      } else {                                                                                      \
-        const bf16x4 hi = to_bf16x4(v);                                                             \
-        *(bf16x4*)&(DSTB)[soff[j]] = hi;                                                            \
-        if constexpr (MODE == 1) *(bf16x4*)&(DSTB)[PLANE + soff[j]] = to_bf16x4(residual4(v, hi));  \
-      }                                                                                             \
-    }                                                                                               \
+#define PATCH_STORE2(DSTB, J0, J1)                                                                                                            \
+  {                                                                                                                                           \
+    _Pragma("unroll") for (int j = J0; j < J1; ++j) {                                                                                         \
+      cgd_f32x4 v = pr[j];                                                                                                                    \
+      if constexpr (GN)                                                                                                                       \
+        v = cgd_f32x4{cgd_silu_affine(v.x, ga[0].x, ga[0].y), cgd_silu_affine(v.y, ga[0].z, ga[0].w), cgd_silu_affine(v.z, ga[1].x, ga[1].y), \
+                  cgd_silu_affine(v.w, ga[1].z, ga[1].w)};                                                                                    \
+      if constexpr (GN) v = poff[j] >= 0 ? v : z4; /* (the loads return zeros for padding; silu(b) need not be 0) */                          \
+      if constexpr (MODE == 1 && SPLITQ) {                                                                                                    \
+        cgd_bf16x4 hi, lo;                                                                                                                    \
+        cgd_split_quad(v, hi, lo);                                                                                                            \
+        *(cgd_bf16x4*)&(DSTB)[soff[j]] = hi;                                                                                                  \
+        *(cgd_bf16x4*)&(DSTB)[PLANE + soff[j]] = lo;                                                                                          \
+      } else {                                                                                                                                \
+        const cgd_bf16x4 hi = cgd_to_bf16x4(v);                                                                                               \
+        *(cgd_bf16x4*)&(DSTB)[soff[j]] = hi;                                                                                                  \
+        if constexpr (MODE == 1) *(cgd_bf16x4*)&(DSTB)[PLANE + soff[j]] = cgd_to_bf16x4(cgd_residual4(v, hi));                                \
+      }                                                                                                                                       \
+    }                                                                                                                                         \
   }
   // A fragments of k-step (TAP, KS): [pixel block i][plane]
-#define A_LOAD2(DST, SRCB, TAP, KS)                                                                 \
-  {                                                                                                 \
-    constexpr int o_ = ((TAP) / 3) * HRS + ((TAP) % 3) * HPH + (KS) * 16;                           \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                \
-      DST[i][0] = *(const bf16x8*)&(SRCB)[fro[i] + o_];                                             \
-      if constexpr (MODE == 1) DST[i][1] = *(const bf16x8*)&(SRCB)[PLANE + fro[i] + o_];            \
-    }                                                                                               \
+#define A_LOAD2(DST, SRCB, TAP, KS)                                                          \
+  {                                                                                          \
+    constexpr int o_ = ((TAP) / 3) * HRS + ((TAP) % 3) * HPH + (KS) * 16;                    \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                         \
+      DST[i][0] = *(const cgd_bf16x8*)&(SRCB)[fro[i] + o_];                                  \
+      if constexpr (MODE == 1) DST[i][1] = *(const cgd_bf16x8*)&(SRCB)[PLANE + fro[i] + o_]; \
+    }                                                                                        \
   }
   // B fragments of k-step (TAP, KS) of the chunk whose block base is BASE: [channel block j][plane]
   // BASE = chunk index; WANT < 0: the chunk exists
-#define B_LOAD2(DST, BASE, WANT, TAP, KS)                                                           \
-  {                                                                                                 \
-    const int so_ = ((BASE) * (9 * 4 * 64) + ((TAP) * 4 + (KS) * 2) * 64) * 16;                     \
-    DST[0][0] = __builtin_bit_cast(uint4, hc_buf_load16(Bwb, (WANT), 0xffffffffu, lane * 16, so_)); \
-    if constexpr (MODE == 1) DST[0][1] = __builtin_bit_cast(uint4, hc_buf_load16(Bwb, (WANT), 0xffffffffu, lane * 16 + 1024, so_)); \
-    if constexpr (NJ == 2) {                                                                        \
-      DST[1][0] = __builtin_bit_cast(uint4, hc_buf_load16(Bwb, (WANT), 0xffffffffu, lane * 16, so_ + bj1_b)); \
-      if constexpr (MODE == 1) DST[1][1] = __builtin_bit_cast(uint4, hc_buf_load16(Bwb, (WANT), 0xffffffffu, lane * 16 + 1024, so_ + bj1_b)); \
-    }                                                                                               \
+#define B_LOAD2(DST, BASE, WANT, TAP, KS)                                                                                                         \
+  {                                                                                                                                               \
+    const int so_ = ((BASE) * (9 * 4 * 64) + ((TAP) * 4 + (KS) * 2) * 64) * 16;                                                                   \
+    DST[0][0] = __builtin_bit_cast(uint4, cgd_buf_load16_if(Bwb, 0xffffffffu, (WANT), lane * 16, so_));                                           \
+    if constexpr (MODE == 1) DST[0][1] = __builtin_bit_cast(uint4, cgd_buf_load16_if(Bwb, 0xffffffffu, (WANT), lane * 16 + 1024, so_));           \
+    if constexpr (NJ == 2) {                                                                                                                      \
+      DST[1][0] = __builtin_bit_cast(uint4, cgd_buf_load16_if(Bwb, 0xffffffffu, (WANT), lane * 16, so_ + bj1_b));                                 \
+      if constexpr (MODE == 1) DST[1][1] = __builtin_bit_cast(uint4, cgd_buf_load16_if(Bwb, 0xffffffffu, (WANT), lane * 16 + 1024, so_ + bj1_b)); \
+    }                                                                                                                                             \
   }
   // 12 MFMAs of one k-step; product-major so that the same accumulator recurs only every 4th instruction
-#define MFMA12(AQ, BQ)                                                                              \
-  {                                                                                                 \
-    if constexpr (MODE == 1) {                                                                      \
-      _Pragma("unroll") for (int i = 0; i < NI; ++i) _Pragma("unroll") for (int j = 0; j < NJ; ++j) \
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, BQ[j][0]), AQ[i][1], acc[i][j], 0, 0, 0); \
-      _Pragma("unroll") for (int i = 0; i < NI; ++i) _Pragma("unroll") for (int j = 0; j < NJ; ++j) \
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, BQ[j][1]), AQ[i][0], acc[i][j], 0, 0, 0); \
-    }                                                                                               \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) _Pragma("unroll") for (int j = 0; j < NJ; ++j)   \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, BQ[j][0]), AQ[i][0], acc[i][j], 0, 0, 0); \
+#define MFMA12(AQ, BQ)                                                                                                                 \
+  {                                                                                                                                    \
+    if constexpr (MODE == 1) {                                                                                                         \
+      _Pragma("unroll") for (int i = 0; i < NI; ++i) _Pragma("unroll") for (int j = 0; j < NJ; ++j)                                    \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[j][0]), AQ[i][1], acc[i][j], 0, 0, 0); \
+      _Pragma("unroll") for (int i = 0; i < NI; ++i) _Pragma("unroll") for (int j = 0; j < NJ; ++j)                                    \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[j][1]), AQ[i][0], acc[i][j], 0, 0, 0); \
+    }                                                                                                                                  \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i) _Pragma("unroll") for (int j = 0; j < NJ; ++j)                                      \
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[j][0]), AQ[i][0], acc[i][j], 0, 0, 0);   \
   }
 
   // B-fragment ring: RING slots, loads DIST = RING - 1 k-steps ahead.  RING divides the 18 k-steps of a chunk, so the slot of
@@ -269,7 +242,7 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
   // registers for 6 slots (5 k-steps ~ 2 us of slack: covers the patch loads queued in front of the B loads in the in-order
   // vmcnt counter); the 8-wavefront tile spills beyond 3.
   constexpr int RING = (TH == 8 || NJ == 1) ? 6 : 3, DIST = RING - 1;
-  bf16x8 af[2][NI][NPL];     // [pipeline slot][pixel block][plane]
+  cgd_bf16x8 af[2][NI][NPL];     // [pipeline slot][pixel block][plane]
   uint4 bq[RING][NJ][NPL];   // [ring slot][channel block][plane]
   if (c0 < c1) {
     PATCH_LOAD2(c0, -1);
@@ -327,7 +300,6 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
   }
 #undef PATCH_LOAD2
 #undef PATCH_STORE2
-#undef GN_SILU
 #undef A_LOAD2
 #undef B_LOAD2
 #undef MFMA12
@@ -344,8 +316,8 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
         if (cb0 < p.N && mrow[i] >= 0) {
 #pragma unroll
           for (int g = 0; g < 4; ++g)
-            *(f32x4*)&ws[mrow[i] * p.N + cb0 + 8 * g + 4 * hh] =
-                f32x4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+            *(cgd_f32x4*)&ws[mrow[i] * p.N + cb0 + 8 * g + 4 * hh] =
+                cgd_f32x4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
         }
       }
     return;
@@ -356,18 +328,18 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
     for (int j = 0; j < NJ; ++j) {
       const int cb0 = (nb0 + j) * 32;
       if (cb0 >= p.N || mrow[i] < 0) continue;
-      f32x4 rv[4];
+      cgd_f32x4 rv[4];
       if (Rg) {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) rv[g] = *(const f32x4*)&Rg[mrow[i] * p.ldr + cb0 + 8 * g + 4 * hh];
+        for (int g = 0; g < 4; ++g) rv[g] = *(const cgd_f32x4*)&Rg[mrow[i] * p.ldr + cb0 + 8 * g + 4 * hh];
       }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int col = cb0 + 8 * g + 4 * hh;
-        f32x4 o = f32x4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]} * p.alpha;
-        if (biasg) o += f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]};
+        cgd_f32x4 o = cgd_f32x4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]} * p.alpha;
+        if (biasg) o += cgd_f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]};
         if (Rg) o += rv[g];
-        *(f32x4*)&Cg[mrow[i] * p.ldc + col] = o;
+        *(cgd_f32x4*)&Cg[mrow[i] * p.ldc + col] = o;
       }
     }
 }

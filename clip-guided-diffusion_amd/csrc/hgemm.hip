@@ -12,13 +12,9 @@
 //   * operands are swapped (D = W_frag x A_frag^T) so a lane owns 4 consecutive output columns: 16-byte epilogue accesses.
 // 4 wavefronts (2 x 2), 64 x 64 outputs each; split-K over 64-column chunks through the shared workspace + reduce kernel.
 #include "common.h"
+#include "mfma_stage.h"
 
 #include <algorithm>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -29,35 +25,26 @@ constexpr int GPLANE = GM * GPH;
 // never defines it: H_STAMP expands to nothing there
 #ifdef CGD_HGEMM_STAMPS
 __device__ unsigned long long* g_hstamps;  // [workgroup (x + gridDim.x * z)][wavefront][32]: 0 entry, 1 first chunk staged, 2 + c chunk c done (level 2), 29 loop done, 30 stores issued, 31 HW id
-#define H_STAMP(I)                                                                                                          \
-  do {                                                                                                                      \
-    if ((threadIdx.x & 63) == 0 && threadIdx.x < 256)                                                                       \
-      g_hstamps[(((long)blockIdx.z * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)) * 32 + (I)] = wall_clock64();        \
+// (the first four wavefronts stamp: K-group 1 of the KG = 2 instantiations has no records)
+#define H_STAMP_AT(I, WHAT)                                                                                 \
+  do {                                                                                                      \
+    if (threadIdx.x < 256) WHAT(g_hstamps, (long)blockIdx.z * gridDim.x + blockIdx.x, threadIdx.x >> 6, I); \
   } while (0)
+#define H_STAMP(I) H_STAMP_AT(I, CGD_STAMP)
 #if CGD_HGEMM_STAMPS >= 2  // a store per chunk slows the 0.75 us chunks by ~30 %: level 1 stamps only around the loop
 #define H_STAMP_CHUNK(I) H_STAMP(I)
 #else
-#define H_STAMP_CHUNK(I) \
-  do {                   \
-  } while (0)
+#define H_STAMP_CHUNK(I) CGD_NO_STAMP
 #endif
-#define H_STAMP_END()                                                                                                       \
-  do {                                                                                                                      \
-    H_STAMP(30);                                                                                                            \
-    if ((threadIdx.x & 63) == 0 && threadIdx.x < 256)                                                                       \
-      g_hstamps[(((long)blockIdx.z * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)) * 32 + 31] =                         \
-          ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4); \
+#define H_STAMP_END()                \
+  do {                               \
+    H_STAMP(30);                     \
+    H_STAMP_AT(31, CGD_STAMP_HW_ID); \
   } while (0)
 #else
-#define H_STAMP(I) \
-  do {             \
-  } while (0)
-#define H_STAMP_CHUNK(I) \
-  do {                   \
-  } while (0)
-#define H_STAMP_END() \
-  do {                \
-  } while (0)
+#define H_STAMP(I) CGD_NO_STAMP
+#define H_STAMP_CHUNK(I) CGD_NO_STAMP
+#define H_STAMP_END() CGD_NO_STAMP
 #endif
 
 struct HGemmParams {
@@ -75,18 +62,6 @@ struct HGemmParams {
                // 1 = N-tile major (an XCD owns weight column panels, read from HBM once and kept in its 4 MB L2; the small
                // activation matrix is what every XCD re-reads): chosen when the weights are the larger operand (N >= M)
 };
-
-__device__ __forceinline__ bf16x4 g_to_bf16x4(const f32x4 v) {
-  bf16x4 r;
-  r[0] = (__bf16)v.x;
-  r[1] = (__bf16)v.y;
-  r[2] = (__bf16)v.z;
-  r[3] = (__bf16)v.w;
-  return r;
-}
-__device__ __forceinline__ f32x4 g_residual4(const f32x4 v, const bf16x4 hi) {
-  return f32x4{v.x - (float)hi[0], v.y - (float)hi[1], v.z - (float)hi[2], v.w - (float)hi[3]};
-}
 
 template <int MODE>
 __global__ __launch_bounds__(256) void hgemm_kernel(const float* __restrict__ Ag, const uint4* __restrict__ Bg, float* Cg,
@@ -136,7 +111,7 @@ __global__ __launch_bounds__(256) void hgemm_kernel(const float* __restrict__ Ag
   const uint4* __restrict__ Bw0 = Bg + (long)nbc * bstride_nb + lane;
   const int kq_last = c1 * 4 - 1;
 
-  f32x16 acc[2][2];
+  cgd_f32x16 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -146,29 +121,29 @@ __global__ __launch_bounds__(256) void hgemm_kernel(const float* __restrict__ Ag
   if (c0 >= c1) goto epilogue;  // empty split-K slice: contributes zeros
 
   {
-    f32x4 pr[8];
-    const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
-#define G_PATCH_LOAD(CH)                                                                          \
-  {                                                                                               \
-    const float* __restrict__ Ac = Ag + (long)((CH) < c1 ? (CH) : c1 - 1) * GK;                   \
-    _Pragma("unroll") for (int j = 0; j < 8; ++j) pr[j] = *(const f32x4*)(Ac + aoff[j]);          \
+    cgd_f32x4 pr[8];
+    const cgd_f32x4 z4 = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
+#define G_PATCH_LOAD(CH)                                                                     \
+  {                                                                                          \
+    const float* __restrict__ Ac = Ag + (long)((CH) < c1 ? (CH) : c1 - 1) * GK;              \
+    _Pragma("unroll") for (int j = 0; j < 8; ++j) pr[j] = *(const cgd_f32x4*)(Ac + aoff[j]); \
   }
-#define G_PATCH_STORE(DSTB, J0, J1)                                                               \
-  {                                                                                               \
-    _Pragma("unroll") for (int j = J0; j < J1; ++j) {                                             \
-      const int row = r0 + 16 * j;                                                                \
-      const f32x4 v = (amask >> j) & 1u ? pr[j] : z4;                                             \
-      const bf16x4 hi = g_to_bf16x4(v);                                                           \
-      *(bf16x4*)&(DSTB)[row * GPH + c4 * 4] = hi;                                                 \
-      if constexpr (MODE == 1) *(bf16x4*)&(DSTB)[GPLANE + row * GPH + c4 * 4] = g_to_bf16x4(g_residual4(v, hi)); \
-    }                                                                                             \
+#define G_PATCH_STORE(DSTB, J0, J1)                                                                                      \
+  {                                                                                                                      \
+    _Pragma("unroll") for (int j = J0; j < J1; ++j) {                                                                    \
+      const int row = r0 + 16 * j;                                                                                       \
+      const cgd_f32x4 v = (amask >> j) & 1u ? pr[j] : z4;                                                                \
+      const cgd_bf16x4 hi = cgd_to_bf16x4(v);                                                                            \
+      *(cgd_bf16x4*)&(DSTB)[row * GPH + c4 * 4] = hi;                                                                    \
+      if constexpr (MODE == 1) *(cgd_bf16x4*)&(DSTB)[GPLANE + row * GPH + c4 * 4] = cgd_to_bf16x4(cgd_residual4(v, hi)); \
+    }                                                                                                                    \
   }
-#define G_A_LOAD(DST, SRCB, Q)                                                                    \
-  {                                                                                               \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                               \
-      if constexpr (MODE == 1) DST[i][1] = *(const bf16x8*)&(SRCB)[GPLANE + fro[i] + (Q) * 16];   \
-      DST[i][0] = *(const bf16x8*)&(SRCB)[fro[i] + (Q) * 16];                                     \
-    }                                                                                             \
+#define G_A_LOAD(DST, SRCB, Q)                                                                      \
+  {                                                                                                 \
+    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                 \
+      if constexpr (MODE == 1) DST[i][1] = *(const cgd_bf16x8*)&(SRCB)[GPLANE + fro[i] + (Q) * 16]; \
+      DST[i][0] = *(const cgd_bf16x8*)&(SRCB)[fro[i] + (Q) * 16];                                   \
+    }                                                                                               \
   }
 #define G_B_LOAD(DST, KQ)                                                                         \
   {                                                                                               \
@@ -179,16 +154,16 @@ __global__ __launch_bounds__(256) void hgemm_kernel(const float* __restrict__ Ag
     DST[1][0] = q_[bj1];                                                                          \
     if constexpr (MODE == 1) DST[1][1] = q_[bj1 + 64];                                            \
   }
-#define G_MFMA12(AQ, BQ)                                                                          \
-  {                                                                                               \
-    if constexpr (MODE == 1) {                                                                    \
-      _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j) \
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, BQ[j][0]), AQ[i][1], acc[i][j], 0, 0, 0); \
-      _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j) \
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, BQ[j][1]), AQ[i][0], acc[i][j], 0, 0, 0); \
-    }                                                                                             \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)   \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, BQ[j][0]), AQ[i][0], acc[i][j], 0, 0, 0); \
+#define G_MFMA12(AQ, BQ)                                                                                                               \
+  {                                                                                                                                    \
+    if constexpr (MODE == 1) {                                                                                                         \
+      _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                                      \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[j][0]), AQ[i][1], acc[i][j], 0, 0, 0); \
+      _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                                      \
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[j][1]), AQ[i][0], acc[i][j], 0, 0, 0); \
+    }                                                                                                                                  \
+    _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)                                        \
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[j][0]), AQ[i][0], acc[i][j], 0, 0, 0);   \
   }
   // one MFMA, then one LDS read / one global read / a few conversion VALU ops / one LDS write: the own MFMA queue never drains
 #define G_INTERLEAVE()                                                                            \
@@ -203,7 +178,7 @@ __global__ __launch_bounds__(256) void hgemm_kernel(const float* __restrict__ Ag
     __builtin_amdgcn_sched_barrier(0);                                                            \
   }
 
-    bf16x8 af[2][2][NPL];  // [pipeline slot][row block][plane]
+    cgd_bf16x8 af[2][2][NPL];  // [pipeline slot][row block][plane]
     uint4 bq[4][2][NPL];   // [ring slot][column block][plane]
     // prologue: chunk c0 into buffer 0, chunk c0+1 in registers, B fragments of the first two k-steps
     G_PATCH_LOAD(c0);
@@ -270,8 +245,8 @@ epilogue:
         if (cb0 < p.N && mok[i]) {
 #pragma unroll
           for (int g = 0; g < 4; ++g)
-            *(f32x4*)&ws[mrow[i] * p.N + cb0 + 8 * g + 4 * hh] =
-                f32x4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
+            *(cgd_f32x4*)&ws[mrow[i] * p.N + cb0 + 8 * g + 4 * hh] =
+                cgd_f32x4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
         }
       }
     return;
@@ -282,18 +257,18 @@ epilogue:
     for (int j = 0; j < 2; ++j) {
       const int cb0 = n0 + wn * 64 + j * 32;
       if (cb0 >= p.N || !mok[i]) continue;
-      f32x4 rv[4];
+      cgd_f32x4 rv[4];
       if (Rg) {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) rv[g] = *(const f32x4*)&Rg[mrow[i] * p.ldr + cb0 + 8 * g + 4 * hh];
+        for (int g = 0; g < 4; ++g) rv[g] = *(const cgd_f32x4*)&Rg[mrow[i] * p.ldr + cb0 + 8 * g + 4 * hh];
       }
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int col = cb0 + 8 * g + 4 * hh;
-        f32x4 o = f32x4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]} * p.alpha;
-        if (biasg) o += f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]};
+        cgd_f32x4 o = cgd_f32x4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]} * p.alpha;
+        if (biasg) o += cgd_f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]};
         if (Rg) o += rv[g];
-        *(f32x4*)&Cg[mrow[i] * p.ldc + col] = o;
+        *(cgd_f32x4*)&Cg[mrow[i] * p.ldc + col] = o;
       }
     }
 }
@@ -318,18 +293,7 @@ epilogue:
 // ahead, the activation sets up to 3 chunks — used to re-read the slice's last fragments / last chunk on clamped indices (a 4-chunk slice of a
 // split-K ViT linear issued 7 patch loads for 4 useful ones through the L2 path that bounds this class); with a resource of ZERO records they are
 // out of range, return zeros and touch no memory — no branch in the scheduled region; (b) no 64-bit per-lane address arithmetic per load.
-typedef int hi32x4 __attribute__((ext_vector_type(4)));
-// neg = a wave-uniform integer: < 0 -> the load is wanted, >= 0 -> it is past the end of the slice (sign bit spread by a scalar shift: a bool select
-// would be lowered through v_cndmask and put the resource into vector registers, i.e. a readfirstlane loop around every load)
-// `records`: size of the resource when the load is wanted — lanes with voffset >= records read zeros (rows beyond M carry the offset H_OOB)
-__device__ __forceinline__ hi32x4 h_buf_load16(const void* base, int neg, int voffset, int soffset, unsigned records = 0xffffffffu) {
-  // raw buffer, stride 0; gfx9 resource word 3 = 0x00020000 (DATA_FORMAT 32); num_records 0: every lane is out of range
-  int num;
-  asm("s_ashr_i32 %0, %1, 31" : "=s"(num) : "s"(neg) : "scc");  // (plain C++ is re-written into a compare + select by the optimiser)
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)((unsigned)num & records), 0x00020000);
-  return __builtin_amdgcn_raw_buffer_load_b128(r, voffset, soffset, 0);
-}
-constexpr int H_OOB = (int)0x80000000;
+// The loads are mfma_stage.h's cgd_buf_load16_if: its `neg` < 0 = inside the slice; rows beyond M carry the offset CGD_OOB.
 
 constexpr int h2_gcd(int a, int b) { return b ? h2_gcd(b, a % b) : a; }
 constexpr int h2_lcm(int a, int b) { return a / h2_gcd(a, b) * b; }
@@ -383,7 +347,7 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
   }
   int aoffb[NPS];  // byte offsets for the buffer loads; a row beyond M is out of range: zeros without a select
 #pragma unroll
-  for (int j = 0; j < NPS; ++j) aoffb[j] = (amask >> j) & 1u ? aoff[j] * 4 : H_OOB;
+  for (int j = 0; j < NPS; ++j) aoffb[j] = (amask >> j) & 1u ? aoff[j] * 4 : CGD_OOB;
   int fro[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) fro[i] = (i * 32 + l31) * GPHW + hh * 8 + kg * GK;
@@ -407,7 +371,7 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
   const uint4* __restrict__ Bwb = Bg + (long)(nb0_s < nbN ? nb0_s : nbN - 1) * bstride_nb + (long)(c0 * KG + kg_s) * 4 * 128;
   const int t_last = (c1 - c0) * 4 - 1;
 
-  f32x16 acc[NI];
+  cgd_f32x16 acc[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -415,53 +379,53 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
 
   if (c0 < c1) {
     constexpr int AHEAD = NSET + 1;  // set (C - c0) % NSET holds chunk C + 1 while chunk C runs and is refilled with chunk C + AHEAD
-    f32x4 prs[NSET][NPS];
-#define H2_PATCH_LOAD(PR, CH)                                                                     \
-  {                                                                                               \
-    const int in_ = (CH) - c1; /* < 0: inside the slice */                                        \
-    const int so_ = (CH) * (GKW * 4);                                                             \
-    _Pragma("unroll") for (int j = 0; j < NPS; ++j)                                               \
-        PR[j] = __builtin_bit_cast(f32x4, h_buf_load16(Ag, in_, aoffb[j], so_, 0x80000000u));     \
+    cgd_f32x4 prs[NSET][NPS];
+#define H2_PATCH_LOAD(PR, CH)                                                                          \
+  {                                                                                                    \
+    const int in_ = (CH) - c1; /* < 0: inside the slice */                                             \
+    const int so_ = (CH) * (GKW * 4);                                                                  \
+    _Pragma("unroll") for (int j = 0; j < NPS; ++j)                                                    \
+        PR[j] = __builtin_bit_cast(cgd_f32x4, cgd_buf_load16_if(Ag, 0x80000000u, in_, aoffb[j], so_)); \
   }
-#define H2_PATCH_STORE(PR, DSTB, J0, J1)                                                          \
-  {                                                                                               \
-    _Pragma("unroll") for (int j = J0; j < J1; ++j) {                                             \
-      const int row = r0 + 16 * j;                                                                \
-      const f32x4 v = PR[j];                                                                      \
-      if constexpr (MODE == 1) {                                                                  \
-        bf16x4 hi, lo;                                                                            \
-        cgd_split_quad(v, hi, lo);                                                                \
-        *(bf16x4*)&(DSTB)[row * GPHW + c4 * 4] = hi;                                              \
-        *(bf16x4*)&(DSTB)[PLANE + row * GPHW + c4 * 4] = lo;                                      \
-      } else {                                                                                    \
-        *(bf16x4*)&(DSTB)[row * GPHW + c4 * 4] = g_to_bf16x4(v);                                  \
-      }                                                                                           \
-    }                                                                                             \
+#define H2_PATCH_STORE(PR, DSTB, J0, J1)                               \
+  {                                                                    \
+    _Pragma("unroll") for (int j = J0; j < J1; ++j) {                  \
+      const int row = r0 + 16 * j;                                     \
+      const cgd_f32x4 v = PR[j];                                       \
+      if constexpr (MODE == 1) {                                       \
+        cgd_bf16x4 hi, lo;                                             \
+        cgd_split_quad(v, hi, lo);                                     \
+        *(cgd_bf16x4*)&(DSTB)[row * GPHW + c4 * 4] = hi;               \
+        *(cgd_bf16x4*)&(DSTB)[PLANE + row * GPHW + c4 * 4] = lo;       \
+      } else {                                                         \
+        *(cgd_bf16x4*)&(DSTB)[row * GPHW + c4 * 4] = cgd_to_bf16x4(v); \
+      }                                                                \
+    }                                                                  \
   }
-#define H2_A_LOAD(DST, SRCB, Q)                                                                   \
-  {                                                                                               \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                              \
-      DST[i][0] = *(const bf16x8*)&(SRCB)[fro[i] + (Q) * 16];                                     \
-      if constexpr (MODE == 1) DST[i][1] = *(const bf16x8*)&(SRCB)[PLANE + fro[i] + (Q) * 16];    \
-    }                                                                                             \
+#define H2_A_LOAD(DST, SRCB, Q)                                                                    \
+  {                                                                                                \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                               \
+      DST[i][0] = *(const cgd_bf16x8*)&(SRCB)[fro[i] + (Q) * 16];                                  \
+      if constexpr (MODE == 1) DST[i][1] = *(const cgd_bf16x8*)&(SRCB)[PLANE + fro[i] + (Q) * 16]; \
+    }                                                                                              \
   }
-#define H2_B_LOAD(DST, T)                                                                         \
-  {                                                                                               \
-    const int in_ = (T) - t_last - 1; /* < 0: inside the slice */                                 \
-    const int so_ = (((T) >> 2) * (4 * KG) + ((T) & 3)) * (128 * 16);                             \
-    DST[0] = __builtin_bit_cast(uint4, h_buf_load16(Bwb, in_, lane * 16, so_));                   \
-    if constexpr (MODE == 1) DST[1] = __builtin_bit_cast(uint4, h_buf_load16(Bwb, in_, lane * 16 + 1024, so_)); \
+#define H2_B_LOAD(DST, T)                                                                                                         \
+  {                                                                                                                               \
+    const int in_ = (T) - t_last - 1; /* < 0: inside the slice */                                                                 \
+    const int so_ = (((T) >> 2) * (4 * KG) + ((T) & 3)) * (128 * 16);                                                             \
+    DST[0] = __builtin_bit_cast(uint4, cgd_buf_load16_if(Bwb, 0xffffffffu, in_, lane * 16, so_));                                 \
+    if constexpr (MODE == 1) DST[1] = __builtin_bit_cast(uint4, cgd_buf_load16_if(Bwb, 0xffffffffu, in_, lane * 16 + 1024, so_)); \
   }
-#define H2_MFMA(AQ, BQ)                                                                           \
-  {                                                                                               \
-    if constexpr (MODE == 1) {                                                                    \
-      _Pragma("unroll") for (int i = 0; i < NI; ++i)                                              \
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, BQ[0]), AQ[i][1], acc[i], 0, 0, 0); \
-      _Pragma("unroll") for (int i = 0; i < NI; ++i)                                              \
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, BQ[1]), AQ[i][0], acc[i], 0, 0, 0); \
-    }                                                                                             \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i)                                                \
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, BQ[0]), AQ[i][0], acc[i], 0, 0, 0); \
+#define H2_MFMA(AQ, BQ)                                                                                                       \
+  {                                                                                                                           \
+    if constexpr (MODE == 1) {                                                                                                \
+      _Pragma("unroll") for (int i = 0; i < NI; ++i)                                                                          \
+          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[0]), AQ[i][1], acc[i], 0, 0, 0); \
+      _Pragma("unroll") for (int i = 0; i < NI; ++i)                                                                          \
+          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[1]), AQ[i][0], acc[i], 0, 0, 0); \
+    }                                                                                                                         \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i)                                                                            \
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[0]), AQ[i][0], acc[i], 0, 0, 0);   \
   }
   // after every MFMA: LDS fragment reads (NI * NPL per k-step), the two global fragment loads, a few conversion VALU ops and
   // the LDS writes of the next chunk's patch
@@ -504,7 +468,7 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
     H_STAMP_CHUNK(2 + ((C) - c0 < 26 ? (C) - c0 : 26));                                           \
   }
 
-    bf16x8 af[2][NI][NPL];  // [pipeline slot][row block][plane]
+    cgd_bf16x8 af[2][NI][NPL];  // [pipeline slot][row block][plane]
     uint4 bq[RING][NPL];    // [ring slot][plane]
     __bf16* const buf0 = lds;
     __bf16* const buf1 = lds + NPL * PLANE;
@@ -560,7 +524,7 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
         for (int i = 0; i < NI; ++i)
 #pragma unroll
           for (int g = 0; g < 4; ++g)
-            *(f32x4*)&slab[((i * 4 + g) * 64 + lane) * 4] = f32x4{acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
+            *(cgd_f32x4*)&slab[((i * 4 + g) * 64 + lane) * 4] = cgd_f32x4{acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
       }
       __syncthreads();
       if (kg == 1) return;
@@ -568,7 +532,7 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
       for (int i = 0; i < NI; ++i)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-          const f32x4 o = *(const f32x4*)&slab[((i * 4 + g) * 64 + lane) * 4];
+          const cgd_f32x4 o = *(const cgd_f32x4*)&slab[((i * 4 + g) * 64 + lane) * 4];
           acc[i][4 * g] += o[0]; acc[i][4 * g + 1] += o[1]; acc[i][4 * g + 2] += o[2]; acc[i][4 * g + 3] += o[3];
         }
       // (the slab is rewritten below by this same wavefront: LDS operations of a wavefront complete in order)
@@ -579,7 +543,7 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
       const int rl = i * 32 + l31;
 #pragma unroll
       for (int g = 0; g < 4; ++g)
-        *(f32x4*)&slab[rl * 32 + (((2 * g + hh) ^ rl) & 7) * 4] = f32x4{acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
+        *(cgd_f32x4*)&slab[rl * 32 + (((2 * g + hh) ^ rl) & 7) * 4] = cgd_f32x4{acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -591,25 +555,25 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
 #pragma unroll
       for (int it = 0; it < TM / 8; ++it) {
         const long row = m0 + 8 * it + rsub;
-        const f32x4 v = *(const f32x4*)&sl[it * 256];
-        if (row < p.M) *(f32x4*)&ws[row * p.N + col] = v;
+        const cgd_f32x4 v = *(const cgd_f32x4*)&sl[it * 256];
+        if (row < p.M) *(cgd_f32x4*)&ws[row * p.N + col] = v;
       }
       H_STAMP_END();
       return;
     }
     const bool hb = biasg != nullptr;
-    const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
-    const f32x4 bv = hb ? f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]} : z4;
+    const cgd_f32x4 z4 = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
+    const cgd_f32x4 bv = hb ? cgd_f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]} : z4;
     const float ka = p.act == 2 ? 1.702f : 1.f;  // QuickGELU x * sigmoid(1.702 x) / SiLU
     constexpr int EB = TM == 64 ? 8 : 4;         // rows in flight per lane (the 96- / 128-row instantiations must stay within 256 registers)
 #pragma unroll
     for (int i0 = 0; i0 < TM / 8; i0 += EB) {
-      f32x4 v[EB], rv[EB], uv[EB];
+      cgd_f32x4 v[EB], rv[EB], uv[EB];
       long row[EB];
       bool ok[EB];
 #pragma unroll
       for (int u = 0; u < EB; ++u) {
-        v[u] = *(const f32x4*)&sl[(i0 + u) * 256];
+        v[u] = *(const cgd_f32x4*)&sl[(i0 + u) * 256];
         long r = m0 + 8 * (i0 + u) + rsub;
         ok[u] = r < p.M;
         if (!ok[u]) r = p.M - 1;
@@ -623,19 +587,19 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
       }
       if (Rg) {
 #pragma unroll
-        for (int u = 0; u < EB; ++u) rv[u] = *(const f32x4*)&Rg[row[u] * p.ldr + col];
+        for (int u = 0; u < EB; ++u) rv[u] = *(const cgd_f32x4*)&Rg[row[u] * p.ldr + col];
       }
       if (p.act_in) {
 #pragma unroll
-        for (int u = 0; u < EB; ++u) uv[u] = *(const f32x4*)&p.act_in[row[u] * p.ld_act + col];
+        for (int u = 0; u < EB; ++u) uv[u] = *(const cgd_f32x4*)&p.act_in[row[u] * p.ld_act + col];
       }
 #pragma unroll
       for (int u = 0; u < EB; ++u) {
-        f32x4 o = v[u] * p.alpha;
+        cgd_f32x4 o = v[u] * p.alpha;
         if (hb) o += bv;
         if (Rg) o += rv[u];
         if (p.act_in) {  // backward through the activation: multiply by act'(u), same arithmetic as elem.hip dact_f
-          f32x4 d;
+          cgd_f32x4 d;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const float sg = 1.f / (1.f + __expf(-ka * uv[u][e]));
@@ -644,12 +608,12 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
           o *= d;
         }
         if (ok[u]) {
-          *(f32x4*)&Cg[row[u] * p.ldc + col] = o;
+          *(cgd_f32x4*)&Cg[row[u] * p.ldc + col] = o;
           if (p.act_out) {  // second output: the activated tensor, same arithmetic as elem.hip act_f
-            f32x4 a;
+            cgd_f32x4 a;
 #pragma unroll
             for (int e = 0; e < 4; ++e) a[e] = o[e] / (1.f + __expf(-ka * o[e]));
-            *(f32x4*)&p.act_out[row[u] * p.ld_act + col] = a;
+            *(cgd_f32x4*)&p.act_out[row[u] * p.ld_act + col] = a;
           }
         }
       }
@@ -666,7 +630,7 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
       if (row < p.M) {
 #pragma unroll
         for (int g = 0; g < 4; ++g)
-          *(f32x4*)&ws[row * p.N + cb0 + 8 * g + 4 * hh] = f32x4{acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
+          *(cgd_f32x4*)&ws[row * p.N + cb0 + 8 * g + 4 * hh] = cgd_f32x4{acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
       }
     }
     return;
@@ -680,25 +644,25 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
       if (row == grp * p.skip_group) continue;
       row -= grp + 1;
     }
-    f32x4 rv[4];
+    cgd_f32x4 rv[4];
     if (Rg) {
 #pragma unroll
-      for (int g = 0; g < 4; ++g) rv[g] = *(const f32x4*)&Rg[row * p.ldr + cb0 + 8 * g + 4 * hh];
+      for (int g = 0; g < 4; ++g) rv[g] = *(const cgd_f32x4*)&Rg[row * p.ldr + cb0 + 8 * g + 4 * hh];
     }
-    f32x4 uv[4];
+    cgd_f32x4 uv[4];
     if (p.act_in) {
 #pragma unroll
-      for (int g = 0; g < 4; ++g) uv[g] = *(const f32x4*)&p.act_in[row * p.ld_act + cb0 + 8 * g + 4 * hh];
+      for (int g = 0; g < 4; ++g) uv[g] = *(const cgd_f32x4*)&p.act_in[row * p.ld_act + cb0 + 8 * g + 4 * hh];
     }
     const float ka = p.act == 2 ? 1.702f : 1.f;  // QuickGELU x * sigmoid(1.702 x) / SiLU
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int col = cb0 + 8 * g + 4 * hh;
-      f32x4 o = f32x4{acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]} * p.alpha;
-      if (biasg) o += f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]};
+      cgd_f32x4 o = cgd_f32x4{acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]} * p.alpha;
+      if (biasg) o += cgd_f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]};
       if (Rg) o += rv[g];
       if (p.act_in) {  // backward through the activation: multiply by act'(u), same arithmetic as elem.hip dact_f
-        f32x4 d;
+        cgd_f32x4 d;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float sg = 1.f / (1.f + __expf(-ka * uv[g][e]));
@@ -706,12 +670,12 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
         }
         o *= d;
       }
-      *(f32x4*)&Cg[row * p.ldc + col] = o;
+      *(cgd_f32x4*)&Cg[row * p.ldc + col] = o;
       if (p.act_out) {  // second output: the activated tensor, same arithmetic as elem.hip act_f
-        f32x4 a;
+        cgd_f32x4 a;
 #pragma unroll
         for (int e = 0; e < 4; ++e) a[e] = o[e] / (1.f + __expf(-ka * o[e]));
-        *(f32x4*)&p.act_out[row * p.ld_act + col] = a;
+        *(cgd_f32x4*)&p.act_out[row * p.ld_act + col] = a;
       }
     }
   }
@@ -755,40 +719,40 @@ __global__ __launch_bounds__(256) void kgemm_kernel(const float* __restrict__ Ag
 #pragma unroll
   for (int i = 0; i < NI; ++i) aoffb[i] = ((m0 + 32 * i + l31) * p.lda + 8 * hh) * 4;
   const unsigned arec = (unsigned)p.M * (unsigned)p.lda * 4u;
-  f32x16 acc[NI];
+  cgd_f32x16 acc[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i)
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
   uint4 bq[RING][NPL];
-  f32x4 aq[RING][NI][2];
-#define KG_LOAD(SLOT, T)                                                                          \
-  {                                                                                               \
-    const int t_ = (T) < mine ? (T) : mine - 1; /* clamped: the loads stay unconditional */       \
-    const int kq_ = w + 4 * t_;                                                                   \
-    bq[SLOT][0] = p.nt ? cgd_load_nt(Bw + (long)kq_ * 128) : Bw[(long)kq_ * 128];                 \
-    if constexpr (MODE == 1) bq[SLOT][1] = p.nt ? cgd_load_nt(Bw + (long)kq_ * 128 + 64) : Bw[(long)kq_ * 128 + 64]; \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                              \
-      /* rows beyond M and k-steps beyond the wavefront's last: out of range, zeros, no memory access */                     \
-      aq[SLOT][i][0] = __builtin_bit_cast(f32x4, h_buf_load16(Ag, (T) - mine, aoffb[i], 64 * kq_, arec));         \
-      aq[SLOT][i][1] = __builtin_bit_cast(f32x4, h_buf_load16(Ag, (T) - mine, aoffb[i] + 16, 64 * kq_, arec));    \
-    }                                                                                             \
+  cgd_f32x4 aq[RING][NI][2];
+#define KG_LOAD(SLOT, T)                                                                                                \
+  {                                                                                                                     \
+    const int t_ = (T) < mine ? (T) : mine - 1; /* clamped: the loads stay unconditional */                             \
+    const int kq_ = w + 4 * t_;                                                                                         \
+    bq[SLOT][0] = p.nt ? cgd_load_nt(Bw + (long)kq_ * 128) : Bw[(long)kq_ * 128];                                       \
+    if constexpr (MODE == 1) bq[SLOT][1] = p.nt ? cgd_load_nt(Bw + (long)kq_ * 128 + 64) : Bw[(long)kq_ * 128 + 64];    \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                                    \
+      /* rows beyond M and k-steps beyond the wavefront's last: out of range, zeros, no memory access */                \
+      aq[SLOT][i][0] = __builtin_bit_cast(cgd_f32x4, cgd_buf_load16_if(Ag, arec, (T) - mine, aoffb[i], 64 * kq_));      \
+      aq[SLOT][i][1] = __builtin_bit_cast(cgd_f32x4, cgd_buf_load16_if(Ag, arec, (T) - mine, aoffb[i] + 16, 64 * kq_)); \
+    }                                                                                                                   \
   }
-#define KG_STEP(SLOT)                                                                             \
-  {                                                                                               \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                              \
-      const f32x4 a0 = aq[SLOT][i][0], a1 = aq[SLOT][i][1];                                       \
-      bf16x8 ah, al;                                                                              \
-      {                                                                                           \
-        const float a8_[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};            \
-        cgd_split_oct(a8_, ah, al);                                                               \
-      }                                                                                           \
-      if constexpr (MODE == 1) {                                                                  \
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bq[SLOT][0]), al, acc[i], 0, 0, 0); \
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bq[SLOT][1]), ah, acc[i], 0, 0, 0); \
-      }                                                                                           \
-      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bq[SLOT][0]), ah, acc[i], 0, 0, 0); \
-    }                                                                                             \
+#define KG_STEP(SLOT)                                                                                                       \
+  {                                                                                                                         \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                                        \
+      const cgd_f32x4 a0 = aq[SLOT][i][0], a1 = aq[SLOT][i][1];                                                             \
+      cgd_bf16x8 ah, al;                                                                                                    \
+      {                                                                                                                     \
+        const float a8_[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};                                      \
+        cgd_split_oct(a8_, ah, al);                                                                                         \
+      }                                                                                                                     \
+      if constexpr (MODE == 1) {                                                                                            \
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, bq[SLOT][0]), al, acc[i], 0, 0, 0); \
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, bq[SLOT][1]), ah, acc[i], 0, 0, 0); \
+      }                                                                                                                     \
+      acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, bq[SLOT][0]), ah, acc[i], 0, 0, 0);   \
+    }                                                                                                                       \
   }
   if (mine > 0) {
 #pragma unroll
@@ -818,11 +782,11 @@ __global__ __launch_bounds__(256) void kgemm_kernel(const float* __restrict__ Ag
     for (int r = 0; r < 16; ++r) red[((w * NI + i) * 16 + r) * 64 + lane] = acc[i][r];
   __syncthreads();
   const int col = nb * 32 + 8 * w + 4 * hh;
-  f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (biasg) bv = *(const f32x4*)(biasg + col);
+  cgd_f32x4 bv = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
+  if (biasg) bv = *(const cgd_f32x4*)(biasg + col);
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
-    f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+    cgd_f32x4 o = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
@@ -831,8 +795,8 @@ __global__ __launch_bounds__(256) void kgemm_kernel(const float* __restrict__ Ag
     if (row < p.M) {
       o = o * p.alpha;
       if (biasg) o += bv;
-      if (Rg) o += *(const f32x4*)(Rg + row * p.ldr + col);
-      *(f32x4*)(Cg + row * p.ldc + col) = o;
+      if (Rg) o += *(const cgd_f32x4*)(Rg + row * p.ldr + col);
+      *(cgd_f32x4*)(Cg + row * p.ldc + col) = o;
     }
   }
 }

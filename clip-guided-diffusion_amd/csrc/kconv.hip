@@ -25,11 +25,7 @@
 // Supports what hconv2 supports at TH = 8: W multiple of 16 or W = 8 (half-filled tile), nearest-2x upsampled input view, fused
 // GroupNorm+SiLU on the staged input (gn pairs), split-K.  Packed weights: the layout of cgd_pack_conv3x3_frag (hconv.hip).
 #include "common.h"
-
-typedef __bf16 kbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 kbf16x4 __attribute__((ext_vector_type(4)));
-typedef float kf32x16 __attribute__((ext_vector_type(16)));
-typedef float kf32x4 __attribute__((ext_vector_type(4)));
+#include "mfma_stage.h"
 
 namespace {
 
@@ -64,31 +60,10 @@ struct KConvParams {
   float alpha;
 };
 
-__device__ __forceinline__ kbf16x4 k_bf16x4(const kf32x4 v) {
-  kbf16x4 r;
-  r[0] = (__bf16)v.x;
-  r[1] = (__bf16)v.y;
-  r[2] = (__bf16)v.z;
-  r[3] = (__bf16)v.w;
-  return r;
-}
-__device__ __forceinline__ kf32x4 k_residual4(const kf32x4 v, const kbf16x4 hi) {
-  return kf32x4{v.x - (float)hi[0], v.y - (float)hi[1], v.z - (float)hi[2], v.w - (float)hi[3]};
-}
-
 // The patch and weight-fragment prefetches are buffer loads (round 6; scalar chunk offset, per-lane offset in a register that never changes): a
 // prefetch past the end of the slice gets a resource of zero records — out of range, returns zeros, touches no memory — where global loads would
-// re-read the slice's last chunk on a clamped index.  The NT instantiations keep global loads for the non-temporal weight stream.
-typedef int ki32x4 __attribute__((ext_vector_type(4)));
-// neg: wave-uniform, < 0 = wanted (hgemm.hip h_buf_load16: the scalar shift keeps the resource in scalar registers)
-// `records`: size of the resource when the load is wanted — lanes with voffset >= records read zeros (padding pixels carry the offset K_OOB)
-__device__ __forceinline__ ki32x4 k_buf_load16(const void* base, int neg, int voffset, int soffset, unsigned records = 0xffffffffu) {
-  int num;
-  asm("s_ashr_i32 %0, %1, 31" : "=s"(num) : "s"(neg) : "scc");
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)((unsigned)num & records), 0x00020000);
-  return __builtin_amdgcn_raw_buffer_load_b128(r, voffset, soffset, 0);
-}
-constexpr int K_OOB = (int)0x80000000;
+// re-read the slice's last chunk on a clamped index (mfma_stage.h cgd_buf_load16_if; padding pixels carry the offset CGD_OOB).  The NT instantiations
+// keep global loads for the non-temporal weight stream.
 // WR = weight-fragment register sets: 2 = the next chunk's fragments are fetched while a chunk is multiplied (rounds 3-4), 3 = TWO chunks ahead
 // NT = weight-fragment loads with the non-temporal policy (single-tile maps: every fragment is read by exactly one workgroup)
 template <int MODE, bool GN, int TW, int WR = 2, bool NT = false, int TH = KTH>
@@ -168,15 +143,15 @@ __global__ __launch_bounds__(256, TW == 8 ? 2 : 1) void kconv_kernel(const float
     c1 = min(nchunk, c0 + per);
   }
   const uint4* __restrict__ Bw0 = Bg + (long)nb * nchunk * (9 * 4 * 64) + lane;
-  constexpr bool BUFL = !NT;  // operand prefetches as buffer loads (see k_buf_load16)
+  constexpr bool BUFL = !NT;  // operand prefetches as buffer loads (mfma_stage.h cgd_buf_load16_if)
   int poffb[KNPASS];  // byte offsets of the patch slots; padding / beyond-the-patch slots are out of range (zeros without a select)
 #pragma unroll
-  for (int j = 0; j < KNPASS; ++j) poffb[j] = poff[j] >= 0 ? poff[j] * 4 : K_OOB;
+  for (int j = 0; j < KNPASS; ++j) poffb[j] = poff[j] >= 0 ? poff[j] * 4 : CGD_OOB;
   (void)poffb;
   const uint4* __restrict__ Bwb = Bg + (long)nb * nchunk * (9 * 4 * 64);  // the workgroup's weight block as a scalar base
   (void)Bwb;
 
-  kf32x16 acc[NPB];
+  cgd_f32x16 acc[NPB];
 #pragma unroll
   for (int i = 0; i < NPB; ++i)
 #pragma unroll
@@ -186,51 +161,50 @@ __global__ __launch_bounds__(256, TW == 8 ? 2 : 1) void kconv_kernel(const float
     // staging registers: two sets.  The patch of chunk j + 2 is fetched during chunk j (a whole chunk ~ 1.9k MFMA cycles ahead of its
     // conversion: the activations come from L2 / MALL behind the weight stream), converted and written during chunk j + 1 into the
     // LDS buffer chunk j has just released.
-    kf32x4 pr[2][KNPASS];
-    kf32x4 ga[2][GN ? 2 : 1];
-    const kf32x4 z4 = kf32x4{0.f, 0.f, 0.f, 0.f};
+    cgd_f32x4 pr[2][KNPASS];
+    cgd_f32x4 ga[2][GN ? 2 : 1];
+    const cgd_f32x4 z4 = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
     const float* __restrict__ gnimg = GN ? gng + ((long)img * p.Cin + c4 * 4) * 2 : nullptr;
-#define K_PATCH_LOAD(S, CH)                                                                         \
-  {                                                                                                 \
-    const int ch_ = (CH) < c1 ? (CH) : c1 - 1; /* clamped: loads stay unconditional */              \
-    const float* __restrict__ Ac = Aimg + ch_ * 32;                                                 \
-    if constexpr (GN) {                                                                             \
-      ga[S][0] = *(const kf32x4*)(gnimg + ch_ * 64);                                                \
-      ga[S][1] = *(const kf32x4*)(gnimg + ch_ * 64 + 4);                                            \
-    }                                                                                               \
-    if constexpr (BUFL) { /* a chunk past the end of the slice: out of range, no memory touched */  \
-      _Pragma("unroll") for (int j = 0; j < KNPASS; ++j)                                            \
-          pr[S][j] = __builtin_bit_cast(kf32x4, k_buf_load16(Aimg, (CH) - c1, poffb[j], (CH) * 128, 0x80000000u)); \
-    } else {                                                                                        \
-      _Pragma("unroll") for (int j = 0; j < KNPASS; ++j)                                            \
-          pr[S][j] = *(const kf32x4*)(Ac + (poff[j] > 0 ? poff[j] : c4 * 4));                       \
-    }                                                                                               \
+#define K_PATCH_LOAD(S, CH)                                                                                                \
+  {                                                                                                                        \
+    const int ch_ = (CH) < c1 ? (CH) : c1 - 1; /* clamped: loads stay unconditional */                                     \
+    const float* __restrict__ Ac = Aimg + ch_ * 32;                                                                        \
+    if constexpr (GN) {                                                                                                    \
+      ga[S][0] = *(const cgd_f32x4*)(gnimg + ch_ * 64);                                                                    \
+      ga[S][1] = *(const cgd_f32x4*)(gnimg + ch_ * 64 + 4);                                                                \
+    }                                                                                                                      \
+    if constexpr (BUFL) { /* a chunk past the end of the slice: out of range, no memory touched */                         \
+      _Pragma("unroll") for (int j = 0; j < KNPASS; ++j)                                                                   \
+          pr[S][j] = __builtin_bit_cast(cgd_f32x4, cgd_buf_load16_if(Aimg, 0x80000000u, (CH) - c1, poffb[j], (CH) * 128)); \
+    } else {                                                                                                               \
+      _Pragma("unroll") for (int j = 0; j < KNPASS; ++j)                                                                   \
+          pr[S][j] = *(const cgd_f32x4*)(Ac + (poff[j] > 0 ? poff[j] : c4 * 4));                                           \
+    }                                                                                                                      \
   }
-#define K_SILU(X, A, B) ({ const float u_ = (X) * (A) + (B); u_ * __builtin_amdgcn_rcpf(1.f + __expf(-u_)); })
-#define K_PATCH_STORE(S, DSTB, J0, J1)                                                              \
-  {                                                                                                 \
-    _Pragma("unroll") for (int j = J0; j < J1; ++j) {                                               \
-      kf32x4 v = pr[S][j];                                                                          \
-      if constexpr (GN)                                                                             \
-        v = kf32x4{K_SILU(v.x, ga[S][0].x, ga[S][0].y), K_SILU(v.y, ga[S][0].z, ga[S][0].w), K_SILU(v.z, ga[S][1].x, ga[S][1].y), \
-                   K_SILU(v.w, ga[S][1].z, ga[S][1].w)};                                            \
-      if constexpr (GN || !BUFL) v = poff[j] >= 0 ? v : z4; /* (buffer loads: padding arrives as zeros) */ \
-      if constexpr (MODE == 1) {                                                                    \
-        kbf16x4 hi, lo;                                                                             \
-        cgd_split_quad(v, hi, lo);                                                                  \
-        *(kbf16x4*)&(DSTB)[soff[j]] = hi;                                                           \
-        *(kbf16x4*)&(DSTB)[KPLANE + soff[j]] = lo;                                                  \
-      } else {                                                                                      \
-        *(kbf16x4*)&(DSTB)[soff[j]] = k_bf16x4(v);                                                  \
-      }                                                                                             \
-    }                                                                                               \
+#define K_PATCH_STORE(S, DSTB, J0, J1)                                                                                                                          \
+  {                                                                                                                                                             \
+    _Pragma("unroll") for (int j = J0; j < J1; ++j) {                                                                                                           \
+      cgd_f32x4 v = pr[S][j];                                                                                                                                   \
+      if constexpr (GN)                                                                                                                                         \
+        v = cgd_f32x4{cgd_silu_affine(v.x, ga[S][0].x, ga[S][0].y), cgd_silu_affine(v.y, ga[S][0].z, ga[S][0].w), cgd_silu_affine(v.z, ga[S][1].x, ga[S][1].y), \
+                   cgd_silu_affine(v.w, ga[S][1].z, ga[S][1].w)};                                                                                               \
+      if constexpr (GN || !BUFL) v = poff[j] >= 0 ? v : z4; /* (buffer loads: padding arrives as zeros) */                                                      \
+      if constexpr (MODE == 1) {                                                                                                                                \
+        cgd_bf16x4 hi, lo;                                                                                                                                      \
+        cgd_split_quad(v, hi, lo);                                                                                                                              \
+        *(cgd_bf16x4*)&(DSTB)[soff[j]] = hi;                                                                                                                    \
+        *(cgd_bf16x4*)&(DSTB)[KPLANE + soff[j]] = lo;                                                                                                           \
+      } else {                                                                                                                                                  \
+        *(cgd_bf16x4*)&(DSTB)[soff[j]] = cgd_to_bf16x4(v);                                                                                                      \
+      }                                                                                                                                                         \
+    }                                                                                                                                                           \
   }
-#define K_A_LOAD(DST, SRCB, K)                                                                      \
-  {                                                                                                 \
-    _Pragma("unroll") for (int i = 0; i < NPB; ++i) {                                               \
-      DST[i][0] = *(const kbf16x8*)&(SRCB)[fro[i] + aoff[K]];                                       \
-      if constexpr (MODE == 1) DST[i][1] = *(const kbf16x8*)&(SRCB)[KPLANE + fro[i] + aoff[K]];    \
-    }                                                                                               \
+#define K_A_LOAD(DST, SRCB, K)                                                                     \
+  {                                                                                                \
+    _Pragma("unroll") for (int i = 0; i < NPB; ++i) {                                              \
+      DST[i][0] = *(const cgd_bf16x8*)&(SRCB)[fro[i] + aoff[K]];                                   \
+      if constexpr (MODE == 1) DST[i][1] = *(const cgd_bf16x8*)&(SRCB)[KPLANE + fro[i] + aoff[K]]; \
+    }                                                                                              \
   }
 #define K_B_LOAD(DST, BASE, K)                                                                      \
   {                                                                                                 \
@@ -239,26 +213,26 @@ __global__ __launch_bounds__(256, TW == 8 ? 2 : 1) void kconv_kernel(const float
     if constexpr (MODE == 1) DST[1] = NT ? cgd_load_nt(bp_ + 64) : bp_[64];                         \
   }
   // (buffer loads) the fragments of chunk CH for k-step slot K: scalar offset, out of range past the end of the slice
-#define K_B_LOAD_BUF(DST, CH, K)                                                                    \
-  {                                                                                                 \
-    const int so_ = ((CH) * (9 * 4 * 64) + boff[K]) * 16;                                           \
-    DST[0] = __builtin_bit_cast(uint4, k_buf_load16(Bwb, (CH) - c1, lane * 16, so_));               \
-    if constexpr (MODE == 1) DST[1] = __builtin_bit_cast(uint4, k_buf_load16(Bwb, (CH) - c1, lane * 16 + 1024, so_)); \
+#define K_B_LOAD_BUF(DST, CH, K)                                                                                                        \
+  {                                                                                                                                     \
+    const int so_ = ((CH) * (9 * 4 * 64) + boff[K]) * 16;                                                                               \
+    DST[0] = __builtin_bit_cast(uint4, cgd_buf_load16_if(Bwb, 0xffffffffu, (CH) - c1, lane * 16, so_));                                 \
+    if constexpr (MODE == 1) DST[1] = __builtin_bit_cast(uint4, cgd_buf_load16_if(Bwb, 0xffffffffu, (CH) - c1, lane * 16 + 1024, so_)); \
   }
-#define K_MFMA(AQ, BQ)                                                                              \
-  {                                                                                                 \
-    if constexpr (MODE == 1) {                                                                      \
-      _Pragma("unroll") for (int i = 0; i < NPB; ++i)                                               \
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(kbf16x8, BQ[0]), AQ[i][1], acc[i], 0, 0, 0); \
-      _Pragma("unroll") for (int i = 0; i < NPB; ++i)                                               \
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(kbf16x8, BQ[1]), AQ[i][0], acc[i], 0, 0, 0); \
-    }                                                                                               \
-    _Pragma("unroll") for (int i = 0; i < NPB; ++i)                                                 \
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(kbf16x8, BQ[0]), AQ[i][0], acc[i], 0, 0, 0); \
+#define K_MFMA(AQ, BQ)                                                                                                        \
+  {                                                                                                                           \
+    if constexpr (MODE == 1) {                                                                                                \
+      _Pragma("unroll") for (int i = 0; i < NPB; ++i)                                                                         \
+          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[0]), AQ[i][1], acc[i], 0, 0, 0); \
+      _Pragma("unroll") for (int i = 0; i < NPB; ++i)                                                                         \
+          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[1]), AQ[i][0], acc[i], 0, 0, 0); \
+    }                                                                                                                         \
+    _Pragma("unroll") for (int i = 0; i < NPB; ++i)                                                                           \
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[0]), AQ[i][0], acc[i], 0, 0, 0);   \
   }
     // weight-fragment ring: two sets of KNQ slots; set S holds the chunk being multiplied, the other is filled with the next chunk's
     // fragments meanwhile (one whole chunk of lead: HBM latency under load)
-    kbf16x8 af[2][NPB][NPL];
+    cgd_bf16x8 af[2][NPB][NPL];
     uint4 bq[WR][KNQ][NPL];
     __bf16* const buf0 = lds;
     __bf16* const buf1 = lds + NPL * KPLANE;
@@ -320,7 +294,6 @@ __global__ __launch_bounds__(256, TW == 8 ? 2 : 1) void kconv_kernel(const float
     for (int u = 0; u < P - 1; ++u)
       if (c + u < c1) K_CHUNK(u & 1, ((u & 1) ? buf1 : buf0), ((u & 1) ? buf0 : buf1), c + u, u % WR);
 #undef K_PATCH_LOAD
-#undef K_SILU
 #undef K_PATCH_STORE
 #undef K_A_LOAD
 #undef K_B_LOAD
@@ -371,15 +344,15 @@ __global__ __launch_bounds__(256, TW == 8 ? 2 : 1) void kconv_kernel(const float
     if (x0 + tx >= p.W) continue;
     const long mrow = (long)img * HW + (long)(y0 + ty) * p.W + x0 + tx;
     const int col = cb0 + 8 * g + 4 * hh;
-    kf32x4 v = kf32x4{o[4 * qd], o[4 * qd + 1], o[4 * qd + 2], o[4 * qd + 3]};
+    cgd_f32x4 v = cgd_f32x4{o[4 * qd], o[4 * qd + 1], o[4 * qd + 2], o[4 * qd + 3]};
     if (p.splitk > 1) {
-      *(kf32x4*)&ws[mrow * p.N + col] = v;
+      *(cgd_f32x4*)&ws[mrow * p.N + col] = v;
       continue;
     }
     v = v * p.alpha;
-    if (biasg) v += kf32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]};
-    if (Rg) v += *(const kf32x4*)&Rg[mrow * p.ldr + col];
-    *(kf32x4*)&Cg[mrow * p.ldc + col] = v;
+    if (biasg) v += cgd_f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]};
+    if (Rg) v += *(const cgd_f32x4*)&Rg[mrow * p.ldr + col];
+    *(cgd_f32x4*)&Cg[mrow * p.ldc + col] = v;
   }
 }
 

@@ -29,13 +29,9 @@
 // split-K over 64-deep chunks through the shared workspace, epilogue = hgemm2's block-through-LDS epilogue (bias, residual, activation operands,
 // dropped class rows) plus bf16 hi / lo PLANE outputs for the next GEMM.  Same products in the same order as hgemm2_kernel: bit-identical results.
 #include "common.h"
+#include "mfma_stage.h"
 
 #include <algorithm>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -104,16 +100,11 @@ __device__ __forceinline__ void lg_wait_allow(int k) {
   lg_vmcnt<0>();
 }
 
-__device__ __forceinline__ bf16x4 lg_to_bf16x4(const f32x4 v) {
-  bf16x4 r;
-  r[0] = (__bf16)v.x; r[1] = (__bf16)v.y; r[2] = (__bf16)v.z; r[3] = (__bf16)v.w;
-  return r;
-}
-__device__ __forceinline__ void lg_store_planes(__bf16* pl, long ps, long off, const f32x4 v) {
-  const bf16x4 hi = lg_to_bf16x4(v);
-  const f32x4 r = f32x4{v.x - (float)hi[0], v.y - (float)hi[1], v.z - (float)hi[2], v.w - (float)hi[3]};
-  *(bf16x4*)(pl + off) = hi;
-  *(bf16x4*)(pl + ps + off) = lg_to_bf16x4(r);
+__device__ __forceinline__ void lg_store_planes(__bf16* pl, long ps, long off, const cgd_f32x4 v) {
+  const cgd_bf16x4 hi = cgd_to_bf16x4(v);
+  const cgd_f32x4 r = cgd_f32x4{v.x - (float)hi[0], v.y - (float)hi[1], v.z - (float)hi[2], v.w - (float)hi[3]};
+  *(cgd_bf16x4*)(pl + off) = hi;
+  *(cgd_bf16x4*)(pl + ps + off) = cgd_to_bf16x4(r);
 }
 
 // DMA instructions T0 .. T1-1 of one chunk: 0 .. 2 NJ - 1 = the A pieces (plane, 8-row group), the rest = 1 KiB pieces of the four
@@ -235,7 +226,7 @@ __global__ __launch_bounds__(256 + 64 * NLD) void lgemm_kernel(const uint4* __re
 
   // ---------------- MFMA wavefronts ----------------
   const int wn = wave;
-  f32x16 acc[NI];
+  cgd_f32x16 acc[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i)
 #pragma unroll
@@ -247,30 +238,30 @@ __global__ __launch_bounds__(256 + 64 * NLD) void lgemm_kernel(const uint4* __re
 #pragma unroll
     for (int q = 0; q < 4; ++q) uo[q] = l31 * 128 + (((2 * q + hh) ^ f) << 4);
     const int bo = A_BYTES + wn * 8192 + lane * 16;
-    bf16x8 af[2][NI][2];
+    cgd_bf16x8 af[2][NI][2];
     uint4 bq[2][2];
-#define LG_LOAD(S, BUFP, Q)                                                                                      \
-  if constexpr (!(CGD_LGEMM_EXP & 8) || (Q) == 0) {                                                              \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                             \
-      af[S][i][0] = *(const bf16x8*)((BUFP) + i * 4096 + uo[Q]);                                                 \
-      af[S][i][1] = *(const bf16x8*)((BUFP) + TM * 128 + i * 4096 + uo[Q]);                                      \
-    }                                                                                                            \
-    bq[S][0] = *(const uint4*)((BUFP) + bo + (2 * (Q)) * 1024);                                                  \
-    bq[S][1] = *(const uint4*)((BUFP) + bo + (2 * (Q) + 1) * 1024);                                              \
+#define LG_LOAD(S, BUFP, Q)                                                     \
+  if constexpr (!(CGD_LGEMM_EXP & 8) || (Q) == 0) {                             \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                            \
+      af[S][i][0] = *(const cgd_bf16x8*)((BUFP) + i * 4096 + uo[Q]);            \
+      af[S][i][1] = *(const cgd_bf16x8*)((BUFP) + TM * 128 + i * 4096 + uo[Q]); \
+    }                                                                           \
+    bq[S][0] = *(const uint4*)((BUFP) + bo + (2 * (Q)) * 1024);                 \
+    bq[S][1] = *(const uint4*)((BUFP) + bo + (2 * (Q) + 1) * 1024);             \
   }
-#define LG_MFMA(S)                                                                                               \
-  if constexpr (CGD_LGEMM_EXP & 4) {                                                                             \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                             \
-      asm volatile("" ::"v"(__builtin_bit_cast(cgd_u32x4, af[S][i][0])), "v"(__builtin_bit_cast(cgd_u32x4, af[S][i][1]))); \
-    }                                                                                                            \
-    asm volatile("" ::"v"(__builtin_bit_cast(cgd_u32x4, bq[S][0])), "v"(__builtin_bit_cast(cgd_u32x4, bq[S][1])));       \
-  } else {                                                                                                       \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i)                                                               \
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bq[S][0]), af[S][i][1], acc[i], 0, 0, 0); \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i)                                                               \
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bq[S][1]), af[S][i][0], acc[i], 0, 0, 0); \
-    _Pragma("unroll") for (int i = 0; i < NI; ++i)                                                               \
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, bq[S][0]), af[S][i][0], acc[i], 0, 0, 0); \
+#define LG_MFMA(S)                                                                                                                \
+  if constexpr (CGD_LGEMM_EXP & 4) {                                                                                              \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i) {                                                                              \
+      asm volatile("" ::"v"(__builtin_bit_cast(cgd_u32x4, af[S][i][0])), "v"(__builtin_bit_cast(cgd_u32x4, af[S][i][1])));        \
+    }                                                                                                                             \
+    asm volatile("" ::"v"(__builtin_bit_cast(cgd_u32x4, bq[S][0])), "v"(__builtin_bit_cast(cgd_u32x4, bq[S][1])));                \
+  } else {                                                                                                                        \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i)                                                                                \
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, bq[S][0]), af[S][i][1], acc[i], 0, 0, 0); \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i)                                                                                \
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, bq[S][1]), af[S][i][0], acc[i], 0, 0, 0); \
+    _Pragma("unroll") for (int i = 0; i < NI; ++i)                                                                                \
+        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, bq[S][0]), af[S][i][0], acc[i], 0, 0, 0); \
   }
   // one LDS fragment read behind every MFMA (2 NI + 2 reads against 3 NI MFMAs per k-step)
 #define LG_INTERLEAVE()                                                                                          \
@@ -322,7 +313,7 @@ __global__ __launch_bounds__(256 + 64 * NLD) void lgemm_kernel(const uint4* __re
     const int rl = i * 32 + l31;
 #pragma unroll
     for (int g = 0; g < 4; ++g)
-      *(f32x4*)&slab[rl * 32 + (((2 * g + hh) ^ rl) & 7) * 4] = f32x4{acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
+      *(cgd_f32x4*)&slab[rl * 32 + (((2 * g + hh) ^ rl) & 7) * 4] = cgd_f32x4{acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -334,24 +325,24 @@ __global__ __launch_bounds__(256 + 64 * NLD) void lgemm_kernel(const uint4* __re
 #pragma unroll
     for (int it = 0; it < TM / 8; ++it) {
       const long row = m0 + 8 * it + rsub;
-      const f32x4 v = *(const f32x4*)&sl[it * 256];
-      if (row < p.M) *(f32x4*)&ws[row * p.N + col] = v;
+      const cgd_f32x4 v = *(const cgd_f32x4*)&sl[it * 256];
+      if (row < p.M) *(cgd_f32x4*)&ws[row * p.N + col] = v;
     }
     return;
   }
   const bool hb = biasg != nullptr;
-  const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
-  const f32x4 bv = hb ? f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]} : z4;
+  const cgd_f32x4 z4 = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
+  const cgd_f32x4 bv = hb ? cgd_f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]} : z4;
   const float ka = p.act == 2 ? 1.702f : 1.f;  // QuickGELU x * sigmoid(1.702 x) / SiLU
   constexpr int EB = 4;                         // rows in flight per lane
 #pragma unroll
   for (int i0 = 0; i0 < TM / 8; i0 += EB) {
-    f32x4 v[EB], rv[EB], uv[EB];
+    cgd_f32x4 v[EB], rv[EB], uv[EB];
     long row[EB];
     bool ok[EB];
 #pragma unroll
     for (int u = 0; u < EB; ++u) {
-      v[u] = *(const f32x4*)&sl[(i0 + u) * 256];
+      v[u] = *(const cgd_f32x4*)&sl[(i0 + u) * 256];
       long r = m0 + 8 * (i0 + u) + rsub;
       ok[u] = r < p.M;
       if (!ok[u]) r = p.M - 1;
@@ -365,19 +356,19 @@ __global__ __launch_bounds__(256 + 64 * NLD) void lgemm_kernel(const uint4* __re
     }
     if (Rg) {
 #pragma unroll
-      for (int u = 0; u < EB; ++u) rv[u] = *(const f32x4*)&Rg[row[u] * p.ldr + col];
+      for (int u = 0; u < EB; ++u) rv[u] = *(const cgd_f32x4*)&Rg[row[u] * p.ldr + col];
     }
     if (p.act_in) {
 #pragma unroll
-      for (int u = 0; u < EB; ++u) uv[u] = *(const f32x4*)&p.act_in[row[u] * p.ld_act + col];
+      for (int u = 0; u < EB; ++u) uv[u] = *(const cgd_f32x4*)&p.act_in[row[u] * p.ld_act + col];
     }
 #pragma unroll
     for (int u = 0; u < EB; ++u) {
-      f32x4 o = v[u] * p.alpha;
+      cgd_f32x4 o = v[u] * p.alpha;
       if (hb) o += bv;
       if (Rg) o += rv[u];
       if (p.act_in) {  // backward through the activation: multiply by act'(u), same arithmetic as elem.hip dact_f
-        f32x4 d;
+        cgd_f32x4 d;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float sg = 1.f / (1.f + __expf(-ka * uv[u][e]));
@@ -386,13 +377,13 @@ __global__ __launch_bounds__(256 + 64 * NLD) void lgemm_kernel(const uint4* __re
         o *= d;
       }
       if (ok[u]) {
-        if (Cg) *(f32x4*)&Cg[row[u] * p.ldc + col] = o;
+        if (Cg) *(cgd_f32x4*)&Cg[row[u] * p.ldc + col] = o;
         if (p.Cpl) lg_store_planes(p.Cpl, p.cps, row[u] * p.ldcp + col, o);
         if (p.act_out || p.Opl) {  // second output: the activated tensor, same arithmetic as elem.hip act_f
-          f32x4 a;
+          cgd_f32x4 a;
 #pragma unroll
           for (int e = 0; e < 4; ++e) a[e] = o[e] / (1.f + __expf(-ka * o[e]));
-          if (p.act_out) *(f32x4*)&p.act_out[row[u] * p.ld_act + col] = a;
+          if (p.act_out) *(cgd_f32x4*)&p.act_out[row[u] * p.ld_act + col] = a;
           if (p.Opl) lg_store_planes(p.Opl, p.ops, row[u] * p.ldop + col, a);
         }
       }
@@ -407,7 +398,7 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
   for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
     const long r = t / cols4;
     const int c = (int)(t - r * cols4) * 4;
-    const f32x4 v = *(const f32x4*)(x + r * ldx + c);
+    const cgd_f32x4 v = *(const cgd_f32x4*)(x + r * ldx + c);
     lg_store_planes(pl, ps, r * ldp + c, v);
   }
 }

@@ -17,10 +17,9 @@
 
 #include "../../include/cgd_mi355x.h"
 #include "net.h"
+#include "mfma_stage.h"
 
 namespace {
-
-typedef float lp_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int NCONV = 13;
 // slice, index inside torchvision's vgg16.features, Cin, Cout
@@ -48,18 +47,18 @@ __global__ __launch_bounds__(256) void lp_scaling_bwd_kernel(const float* __rest
 }
 __global__ __launch_bounds__(256) void lp_relu_kernel(float* __restrict__ x, long n4) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-    lp_f32x4 v = ((lp_f32x4*)x)[i];
+    cgd_f32x4 v = ((cgd_f32x4*)x)[i];
     v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-    ((lp_f32x4*)x)[i] = v;
+    ((cgd_f32x4*)x)[i] = v;
   }
 }
 // dz = da where the stored post-ReLU activation is positive (in place on da)
 __global__ __launch_bounds__(256) void lp_relu_bwd_kernel(const float* __restrict__ a, float* __restrict__ da, long n4) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-    const lp_f32x4 v = ((const lp_f32x4*)a)[i];
-    lp_f32x4 d = ((lp_f32x4*)da)[i];
+    const cgd_f32x4 v = ((const cgd_f32x4*)a)[i];
+    cgd_f32x4 d = ((cgd_f32x4*)da)[i];
     d.x = v.x > 0.f ? d.x : 0.f; d.y = v.y > 0.f ? d.y : 0.f; d.z = v.z > 0.f ? d.z : 0.f; d.w = v.w > 0.f ? d.w : 0.f;
-    ((lp_f32x4*)da)[i] = d;
+    ((cgd_f32x4*)da)[i] = d;
   }
 }
 __global__ __launch_bounds__(256) void lp_maxpool_fwd_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int Ho, int Wo,
@@ -74,12 +73,12 @@ __global__ __launch_bounds__(256) void lp_maxpool_fwd_kernel(const float* __rest
     const long t = pix / Wo;
     const int y = (int)(t % Ho), b = (int)(t / Ho);
     const float* p = in + (((long)b * 2 * Ho + 2 * y) * Wi + 2 * x) * C + q * 4;
-    const lp_f32x4 a = *(const lp_f32x4*)p, c = *(const lp_f32x4*)(p + C), d = *(const lp_f32x4*)(p + Wi * C),
-                   e = *(const lp_f32x4*)(p + Wi * C + C);
-    lp_f32x4 o;
+    const cgd_f32x4 a = *(const cgd_f32x4*)p, c = *(const cgd_f32x4*)(p + C), d = *(const cgd_f32x4*)(p + Wi * C),
+                   e = *(const cgd_f32x4*)(p + Wi * C + C);
+    cgd_f32x4 o;
 #pragma unroll
     for (int k = 0; k < 4; ++k) o[k] = fmaxf(fmaxf(a[k], c[k]), fmaxf(d[k], e[k]));
-    *(lp_f32x4*)(out + pix * C + q * 4) = o;
+    *(cgd_f32x4*)(out + pix * C + q * 4) = o;
   }
 }
 // gradient of the 2x2 max-pool routed to the FIRST maximum of each window (scan order (0,0),(0,1),(1,0),(1,1)), plus the
@@ -98,13 +97,13 @@ __global__ __launch_bounds__(256) void lp_maxpool_bwd_kernel(const float* __rest
     const int y = (int)(t % Ho), b = (int)(t / Ho);
     const long o00 = (((long)b * 2 * Ho + 2 * y) * Wi + 2 * x) * C + q * 4;
     const long off[4] = {o00, o00 + C, o00 + Wi * C, o00 + Wi * C + C};
-    lp_f32x4 v[4], g[4];
+    cgd_f32x4 v[4], g[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      v[k] = *(const lp_f32x4*)(in + off[k]);
-      g[k] = add ? *(const lp_f32x4*)(add + off[k]) : lp_f32x4{0.f, 0.f, 0.f, 0.f};
+      v[k] = *(const cgd_f32x4*)(in + off[k]);
+      g[k] = add ? *(const cgd_f32x4*)(add + off[k]) : cgd_f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    const lp_f32x4 d = *(const lp_f32x4*)(dout + pix * C + q * 4);
+    const cgd_f32x4 d = *(const cgd_f32x4*)(dout + pix * C + q * 4);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       int am = 0;
@@ -119,7 +118,7 @@ __global__ __launch_bounds__(256) void lp_maxpool_bwd_kernel(const float* __rest
       for (int k = 0; k < 4; ++k) g[k][e] += (k == am) ? d[e] : 0.f;
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) *(lp_f32x4*)(din + off[k]) = g[k];
+    for (int k = 0; k < 4; ++k) *(cgd_f32x4*)(din + off[k]) = g[k];
   }
 }
 

@@ -5,6 +5,7 @@
 // Replaces guided_diffusion's GroupNorm32 -> SiLU (ResBlock.in_layers), out_norm(h)*(1+scale)+shift -> SiLU
 // (ResBlock.out_layers with use_scale_shift_norm) and clip's fp32 LayerNorm.
 #include "common.h"
+#include "mfma_stage.h"
 #include "kernels.h"
 
 namespace {
@@ -508,13 +509,12 @@ __global__ __launch_bounds__(256) void gn_bwd_coef_ch_kernel(const float* __rest
 // forward activation, dz the upstream gradient, add / add2 the skip-connection gradients), and its dx store as well (67 MB on the 256 x 256
 // level: twice the L2).  Same-box: x / dz loads -0.07 ms per step, dx store -0.035, both -0.09 (profiles/r6_ab_gn_bwd_apply_nt.txt); add
 // operands -0.025 (profiles/r6_ab_nt_more.txt).
-typedef float gn_f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 gn_ld4_nt(const float* p) {
-  const gn_f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const gn_f32x4*>(p));
+  const cgd_f32x4 v = cgd_ld16_nt<cgd_f32x4>(p);
   return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ void gn_st4_nt(float* p, const float4 o) {
-  __builtin_nontemporal_store(gn_f32x4{o.x, o.y, o.z, o.w}, reinterpret_cast<gn_f32x4*>(p));
+  cgd_st16_nt(p, cgd_f32x4{o.x, o.y, o.z, o.w});
 }
 template <int ACT>
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ dz,
@@ -759,7 +759,7 @@ struct VecT<1> {
 };
 template <>
 struct VecT<4> {
-  typedef float __attribute__((ext_vector_type(4))) T;
+  typedef cgd_f32x4 T;
 };
 template <int VEC>
 __device__ __forceinline__ float vget(const typename VecT<VEC>::T& v, int i) {

@@ -13,10 +13,9 @@
 
 #include "../../include/cgd_mi355x.h"
 #include "net.h"
+#include "mfma_stage.h"
 
 namespace {
-
-typedef float rn_f32x4 __attribute__((ext_vector_type(4)));
 
 int rn_grid(long n) { return (int)std::min<long>((n + 255) / 256, 16384); }
 
@@ -60,7 +59,7 @@ __global__ __launch_bounds__(256) void rn_stem_im2col_kernel(const float* __rest
     const int n = (int)(pix / ((long)Ro * Ro));
     const int rem = (int)(pix - (long)n * Ro * Ro);
     const int oy = rem / Ro, ox = rem - oy * Ro;
-    rn_f32x4 v;
+    cgd_f32x4 v;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int k = 4 * k4 + e;
@@ -72,7 +71,7 @@ __global__ __launch_bounds__(256) void rn_stem_im2col_kernel(const float* __rest
       }
       v[e] = val;
     }
-    *(rn_f32x4*)(out + pix * 32 + 4 * k4) = v;
+    *(cgd_f32x4*)(out + pix * 32 + 4 * k4) = v;
   }
 }
 // adjoint of the stride-2 im2col: d_img[n][c][y][x] = sum over taps with (y+1-ky), (x+1-kx) even of T[(n, ., .)][tap*3 + c]
@@ -105,18 +104,18 @@ __global__ __launch_bounds__(256) void rn_stem_gather_kernel(const float* __rest
 }
 __global__ __launch_bounds__(256) void rn_relu_kernel(float* __restrict__ x, long n4) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-    rn_f32x4 v = ((rn_f32x4*)x)[i];
+    cgd_f32x4 v = ((cgd_f32x4*)x)[i];
     v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-    ((rn_f32x4*)x)[i] = v;
+    ((cgd_f32x4*)x)[i] = v;
   }
 }
 // in place on da: gradient passes where the stored post-ReLU activation is positive
 __global__ __launch_bounds__(256) void rn_relu_bwd_kernel(const float* __restrict__ a, float* __restrict__ da, long n4) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-    const rn_f32x4 v = ((const rn_f32x4*)a)[i];
-    rn_f32x4 d = ((rn_f32x4*)da)[i];
+    const cgd_f32x4 v = ((const cgd_f32x4*)a)[i];
+    cgd_f32x4 d = ((cgd_f32x4*)da)[i];
     d.x = v.x > 0.f ? d.x : 0.f; d.y = v.y > 0.f ? d.y : 0.f; d.z = v.z > 0.f ? d.z : 0.f; d.w = v.w > 0.f ? d.w : 0.f;
-    ((rn_f32x4*)da)[i] = d;
+    ((cgd_f32x4*)da)[i] = d;
   }
 }
 // tokens S[n][0] = mean_p X[n][p] + pos[0], S[n][1+p] = X[n][p] + pos[1+p]   (X: [N][P][E] rows)

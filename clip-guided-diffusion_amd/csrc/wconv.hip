@@ -32,11 +32,7 @@
 // No split-K; W a multiple of 16, H of 8: the launcher (gemm.hip) uses it for M >= ctx->wino_min_m pixels (default 16384).
 // benchmarks/emulate_wconv.py replays the index plumbing below on the CPU (tests/test_wconv_layout.py).
 #include "common.h"
-
-typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wbf16x4 __attribute__((ext_vector_type(4)));
-typedef float wf32x16 __attribute__((ext_vector_type(16)));
-typedef float wf32x4 __attribute__((ext_vector_type(4)));
+#include "mfma_stage.h"
 
 namespace {
 
@@ -57,20 +53,13 @@ constexpr int WRING = 8;               // weight-fragment ring of the one-channe
 // Patch pixels and weight fragments come through buffer loads (round 6).  A third of the chunk loop's vector-ALU instructions were address arithmetic
 // (64-bit per-lane adds for 96 fragment loads per chunk, the in-image test + select per patch load) and 48 more zeroed the padding pixels after the
 // load: with a buffer resource the chunk / step offset is a scalar, the per-lane offsets of a thread's 12 patch pixels are computed once, and a padding
-// pixel is an out-of-range offset — the load returns zeros and touches no memory.
-typedef int wi32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ wi32x4 w_buf_load16(const void* base, unsigned num_records, int voffset, int soffset) {
-  // raw buffer, stride 0; gfx9 resource word 3 = 0x00020000 (DATA_FORMAT 32); lanes with voffset >= num_records read zeros
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, num_records, 0x00020000);
-  return __builtin_amdgcn_raw_buffer_load_b128(r, voffset, soffset, 0);
-}
-constexpr int W_OOB = (int)0x80000000;
+// pixel is an out-of-range offset (CGD_OOB, mfma_stage.h) — the load returns zeros and touches no memory.
 // The output tile is stored with the non-temporal policy (round 6, WConvParams::nt_out; a 256 x 256 x 256-channel output is 67 MB: twice the L2,
 // where the next kernel cannot find it anyway): -0.035 ms per step.  The epilogue's second operand and the chunk loop's patch loads stay on the
 // default policy: non-temporal they cost +0.02 and +0.09 (profiles/r6_ab_wconv_nt.txt).
 template <bool NT>
-__device__ __forceinline__ void w_st_out(float* p, const wf32x4 v) {
-  if constexpr (NT) __builtin_nontemporal_store(v, reinterpret_cast<wf32x4*>(p)); else *(wf32x4*)p = v;
+__device__ __forceinline__ void w_st_out(float* p, const cgd_f32x4 v) {
+  if constexpr (NT) cgd_st16_nt(p, v); else *(cgd_f32x4*)p = v;
 }
 template <int NB, int OCC = 1>
 __host__ __device__ constexpr int w_load_task(int q) {
@@ -93,14 +82,15 @@ __host__ __device__ constexpr int w_proc_task(int q, int piece) {
 // build never defines it: W_STAMP expands to nothing there
 #ifdef CGD_WCONV_STAMPS
 __device__ unsigned long long* g_wstamps;  // [workgroup][wavefront][32]: 0 entry, 1 chunk 0 staged, 2 + c chunk c done, 30 stores issued, 31 HW id
-#define W_STAMP(I)                                                                                   \
-  do {                                                                                               \
-    if (lane == 0) g_wstamps[((long)blockIdx.x * 4 + wave) * 32 + (I)] = wall_clock64();            \
+#define W_STAMP(I) CGD_STAMP(g_wstamps, blockIdx.x, wave, I)
+#define W_STAMP_END()                                 \
+  do {                                                \
+    W_STAMP(30);                                      \
+    CGD_STAMP_HW_ID(g_wstamps, blockIdx.x, wave, 31); \
   } while (0)
 #else
-#define W_STAMP(I) \
-  do {             \
-  } while (0)
+#define W_STAMP(I) CGD_NO_STAMP
+#define W_STAMP_END() CGD_NO_STAMP
 #endif
 
 // The four wavefronts run the same schedule in lock-step after every barrier.  De-phasing them (wavefront w sleeping a multiple of 64 w cycles after
@@ -123,22 +113,6 @@ struct WConvParams {
   int nt_out;  // the output tile's stores with the non-temporal policy (the launcher sets it for every output)
 };
 
-__device__ __forceinline__ wbf16x4 w_bf16x4(const wf32x4 v) {
-  wbf16x4 r;
-  r[0] = (__bf16)v.x;
-  r[1] = (__bf16)v.y;
-  r[2] = (__bf16)v.z;
-  r[3] = (__bf16)v.w;
-  return r;
-}
-__device__ __forceinline__ wf32x4 w_residual4(const wf32x4 v, const wbf16x4 hi) {
-  return wf32x4{v.x - (float)hi[0], v.y - (float)hi[1], v.z - (float)hi[2], v.w - (float)hi[3]};
-}
-__device__ __forceinline__ float w_silu(float x, float a, float b) {
-  const float u = x * a + b;
-  return u * __builtin_amdgcn_rcpf(1.f + __expf(-u));  // v_rcp_f32 (1 ulp) instead of the 10-instruction IEEE division
-}
-
 // NC (round 4) = 32-channel output blocks per wavefront.  NC = 2 on 8-row tiles (NB = 2): the workgroup covers 8 x 16 pixels x 256 channels with the
 // same 256 accumulators as the 16 x 16 x 128 tile, but every A fragment read from LDS now feeds two MFMA sets (4 ds_read_b128 per 12 MFMAs instead
 // of 8: the 16-row tile keeps the LDS pipe ~2/3 busy with fragment reads alone), and a pixel tile's patch is staged — loaded, normalised, SiLU'd,
@@ -149,7 +123,7 @@ __device__ __forceinline__ float w_silu(float x, float a, float b) {
 // are exactly half of the CU's 160 KB of LDS and its 128 accumulators leave 128 registers per wavefront: the weight ring shrinks to 4 steps
 // (the other workgroup's MFMAs cover the shorter prefetch distance).
 // F32 (round 6): the same kernel on EXACT fp32 products (v_mfma_f32_32x32x2_f32) for precision-0 contexts — the reference's own arithmetic
-// (/root/reference/cgd/cgd.py:61 runs the diffusion model in fp32 on the CPU path).  An fp32 value is as wide as a bf16 hi / lo pair, so nothing about
+// (the reference runs the diffusion model in fp32 on its CPU path).  An fp32 value is as wide as a bf16 hi / lo pair, so nothing about
 // the data movement changes: the LDS image keeps its two planes and every address, a lane's 16 bytes of "plane P" of logical unit u now hold the four
 // fp32 values of channels 8 u + 4 P .. + 3 (where the split build keeps 8 bf16 hi or lo values of channels 8 u .. 8 u + 7), the weight fragments are
 // packed the same way (pack_wino_kernel<true>), and a 16-channel k-step becomes 8 MFMAs of depth 2: MFMA e of plane P contracts channels
@@ -205,11 +179,11 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
     const int x = x0 + 2 * sp + k - 1;
     colo[k] = (unsigned)x < (unsigned)p.W ? (p.ups ? x >> 1 : x) * p.lda + c4 * 4 : -1;
   }
-  int poffv[NTASK][4];  // byte offset of pixel k of task j inside the image, W_OOB for a padding pixel (sign bit = "padding")
+  int poffv[NTASK][4];  // byte offset of pixel k of task j inside the image, CGD_OOB for a padding pixel (sign bit = "padding")
 #pragma unroll
   for (int j = 0; j < NTASK; ++j)
 #pragma unroll
-    for (int k = 0; k < 4; ++k) poffv[j][k] = (rowoff[j] | colo[k]) >= 0 ? (rowoff[j] + colo[k]) * 4 : W_OOB;
+    for (int k = 0; k < 4; ++k) poffv[j][k] = (rowoff[j] | colo[k]) >= 0 ? (rowoff[j] + colo[k]) * 4 : CGD_OOB;
   // ---- fragment reads of this lane: pair column l31 of every block = (tile row 4b + (l31 >> 3), pair l31 & 7)
   const int lr = l31 >> 3, lp = l31 & 7;
   int fro[4];
@@ -229,7 +203,7 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
   const int bnext_b = (NC > 1 && nb0_s + 1 < nbN) ? (int)(bstride_nb * 16) : 0;
   (void)bnext_b;
 
-  wf32x16 acc[4][NB][NC];  // [position][pixel block][channel block]
+  cgd_f32x16 acc[4][NB][NC];  // [position][pixel block][channel block]
 #pragma unroll
   for (int x = 0; x < 4; ++x)
 #pragma unroll
@@ -239,43 +213,43 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[x][b][c][e] = 0.f;
 
-  wf32x4 pr[OCC == 2 ? 1 : 2][4];  // two tasks in flight (one with two workgroups per CU)
+  cgd_f32x4 pr[OCC == 2 ? 1 : 2][4];  // two tasks in flight (one with two workgroups per CU)
   constexpr int PM = OCC == 2 ? 0 : 1;  // staging set of task k = pr[k & PM]
-  wf32x4 ga[2];     // GN: {a0, b0, a1, b1}, {a2, b2, a3, b3} of this thread's channels in the chunk being staged
-  const wf32x4 z4 = wf32x4{0.f, 0.f, 0.f, 0.f};
+  cgd_f32x4 ga[2];     // GN: {a0, b0, a1, b1}, {a2, b2, a3, b3} of this thread's channels in the chunk being staged
+  const cgd_f32x4 z4 = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
   const float* __restrict__ gnimg = GN ? gng + ((long)img * p.Cin + c4 * 4) * 2 : nullptr;
 
-#define W_TASK_LOAD(ARR, J, CH)                                                                      \
-  {                                                                                                  \
-    _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                    \
-        ARR[k] = __builtin_bit_cast(wf32x4, w_buf_load16(Aimg, 0x80000000u, poffv[J][k], (CH) * 128)); \
+#define W_TASK_LOAD(ARR, J, CH)                                                                             \
+  {                                                                                                         \
+    _Pragma("unroll") for (int k = 0; k < 4; ++k)                                                           \
+        ARR[k] = __builtin_bit_cast(cgd_f32x4, cgd_buf_load16(Aimg, 0x80000000u, poffv[J][k], (CH) * 128)); \
   }
-#define W_GN_LOAD(CH)                                                                                \
-  if constexpr (GN) {                                                                                \
-    ga[0] = *(const wf32x4*)(gnimg + (CH) * 64);                                                     \
-    ga[1] = *(const wf32x4*)(gnimg + (CH) * 64 + 4);                                                 \
+#define W_GN_LOAD(CH)                                   \
+  if constexpr (GN) {                                   \
+    ga[0] = *(const cgd_f32x4*)(gnimg + (CH) * 64);     \
+    ga[1] = *(const cgd_f32x4*)(gnimg + (CH) * 64 + 4); \
   }
   // activation (fused GroupNorm) and zero padding of pixel K of the task held in ARR
-#define W_TASK_PIX(ARR, J, K)                                                                        \
-  {                                                                                                  \
-    wf32x4 v_ = ARR[K];                                                                              \
-    if constexpr (GN)                                                                                \
-      v_ = wf32x4{w_silu(v_.x, ga[0].x, ga[0].y), w_silu(v_.y, ga[0].z, ga[0].w), w_silu(v_.z, ga[1].x, ga[1].y),   \
-                  w_silu(v_.w, ga[1].z, ga[1].w)};                                                   \
-    /* (a padding pixel arrives as zeros; only the fused activation has to be undone) */            \
-    if constexpr (GN) ARR[K] = poffv[J][K] >= 0 ? v_ : z4; else ARR[K] = v_;                         \
+#define W_TASK_PIX(ARR, J, K)                                                                                                                   \
+  {                                                                                                                                             \
+    cgd_f32x4 v_ = ARR[K];                                                                                                                      \
+    if constexpr (GN)                                                                                                                           \
+      v_ = cgd_f32x4{cgd_silu_affine(v_.x, ga[0].x, ga[0].y), cgd_silu_affine(v_.y, ga[0].z, ga[0].w), cgd_silu_affine(v_.z, ga[1].x, ga[1].y), \
+                  cgd_silu_affine(v_.w, ga[1].z, ga[1].w)};                                                                                     \
+    /* (a padding pixel arrives as zeros; only the fused activation has to be undone) */                                                        \
+    if constexpr (GN) ARR[K] = poffv[J][K] >= 0 ? v_ : z4; else ARR[K] = v_;                                                                    \
   }
-#define W_TASK_PUT(DSTB, J, XI, V)                                                                   \
-  {                                                                                                  \
-    const wf32x4 t_ = (V);                                                                           \
-    if constexpr (F32) {                                                                             \
-      *(wf32x4*)&(DSTB)[wbase[J] + (XI) * 256] = t_;                                                 \
-    } else {                                                                                         \
-      wbf16x4 hi_, lo_;                                                                              \
-      cgd_split_quad(t_, hi_, lo_);                                                                  \
-      *(wbf16x4*)&(DSTB)[wbase[J] + (XI) * 256] = hi_;                                               \
-      *(wbf16x4*)&(DSTB)[WPLANE + wbase[J] + (XI) * 256] = lo_;                                      \
-    }                                                                                                \
+#define W_TASK_PUT(DSTB, J, XI, V)                                 \
+  {                                                                \
+    const cgd_f32x4 t_ = (V);                                      \
+    if constexpr (F32) {                                           \
+      *(cgd_f32x4*)&(DSTB)[wbase[J] + (XI) * 256] = t_;            \
+    } else {                                                       \
+      cgd_bf16x4 hi_, lo_;                                         \
+      cgd_split_quad(t_, hi_, lo_);                                \
+      *(cgd_bf16x4*)&(DSTB)[wbase[J] + (XI) * 256] = hi_;          \
+      *(cgd_bf16x4*)&(DSTB)[WPLANE + wbase[J] + (XI) * 256] = lo_; \
+    }                                                              \
   }
   // a task is transformed in six pieces (w_proc_task)
 #define W_TASK_PA(DSTB, ARR, J) { W_TASK_PIX(ARR, J, 0) }
@@ -287,49 +261,49 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
 #define W_TASK_ALL(DSTB, ARR, J) \
   { W_TASK_PA(DSTB, ARR, J) W_TASK_PB(DSTB, ARR, J) W_TASK_PC(DSTB, ARR, J) W_TASK_PD(DSTB, ARR, J) W_TASK_PE(DSTB, ARR, J) W_TASK_PF(DSTB, ARR, J) }
   // A fragments of step Q = (ky * 4 + xi) * 2 + ks: [block][plane]
-#define W_A_LOAD(DST, SRCB, Q)                                                                       \
-  {                                                                                                  \
-    const int ky_ = (Q) >> 3, xi_ = ((Q) >> 1) & 3, ks_ = (Q) & 1;                                   \
-    const int o_ = fro[(2 * ks_ + ky_) & 3] + ky_ * WROW + xi_ * 256;                                \
-    _Pragma("unroll") for (int b = 0; b < NB; ++b) {                                                 \
-      DST[b][0] = *(const wbf16x8*)&(SRCB)[o_ + b * (4 * WROW)];                                     \
-      DST[b][1] = *(const wbf16x8*)&(SRCB)[WPLANE + o_ + b * (4 * WROW)];                            \
-    }                                                                                                \
+#define W_A_LOAD(DST, SRCB, Q)                                               \
+  {                                                                          \
+    const int ky_ = (Q) >> 3, xi_ = ((Q) >> 1) & 3, ks_ = (Q) & 1;           \
+    const int o_ = fro[(2 * ks_ + ky_) & 3] + ky_ * WROW + xi_ * 256;        \
+    _Pragma("unroll") for (int b = 0; b < NB; ++b) {                         \
+      DST[b][0] = *(const cgd_bf16x8*)&(SRCB)[o_ + b * (4 * WROW)];          \
+      DST[b][1] = *(const cgd_bf16x8*)&(SRCB)[WPLANE + o_ + b * (4 * WROW)]; \
+    }                                                                        \
   }
   // BASE = chunk index (scalar): the fragments of step Q of that chunk
-#define W_B_LOAD(DST, BASE, Q)                                                                       \
-  {                                                                                                  \
-    const int so_ = ((BASE) * (WSTEPS * 128) + (Q) * 128) * 16;                                      \
-    DST[0][0] = __builtin_bit_cast(uint4, w_buf_load16(Bwb, 0xffffffffu, lane * 16, so_));           \
-    DST[0][1] = __builtin_bit_cast(uint4, w_buf_load16(Bwb, 0xffffffffu, lane * 16 + 1024, so_));    \
-    if constexpr (NC > 1) {                                                                          \
-      DST[NC - 1][0] = __builtin_bit_cast(uint4, w_buf_load16(Bwb, 0xffffffffu, lane * 16, so_ + bnext_b));        \
-      DST[NC - 1][1] = __builtin_bit_cast(uint4, w_buf_load16(Bwb, 0xffffffffu, lane * 16 + 1024, so_ + bnext_b)); \
-    }                                                                                                \
+#define W_B_LOAD(DST, BASE, Q)                                                                                       \
+  {                                                                                                                  \
+    const int so_ = ((BASE) * (WSTEPS * 128) + (Q) * 128) * 16;                                                      \
+    DST[0][0] = __builtin_bit_cast(uint4, cgd_buf_load16(Bwb, 0xffffffffu, lane * 16, so_));                         \
+    DST[0][1] = __builtin_bit_cast(uint4, cgd_buf_load16(Bwb, 0xffffffffu, lane * 16 + 1024, so_));                  \
+    if constexpr (NC > 1) {                                                                                          \
+      DST[NC - 1][0] = __builtin_bit_cast(uint4, cgd_buf_load16(Bwb, 0xffffffffu, lane * 16, so_ + bnext_b));        \
+      DST[NC - 1][1] = __builtin_bit_cast(uint4, cgd_buf_load16(Bwb, 0xffffffffu, lane * 16 + 1024, so_ + bnext_b)); \
+    }                                                                                                                \
   }
-#define W_MFMA12(XI, AQ, BQ)                                                                         \
-  if constexpr (F32) {                                                                               \
-    _Pragma("unroll") for (int pl = 0; pl < 2; ++pl) _Pragma("unroll") for (int e = 0; e < 4; ++e)   \
-    _Pragma("unroll") for (int c = 0; c < NC; ++c) _Pragma("unroll") for (int b = 0; b < NB; ++b)    \
-        acc[XI][b][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(__builtin_bit_cast(wf32x4, BQ[c][pl])[e], __builtin_bit_cast(wf32x4, AQ[b][pl])[e], \
-                                                             acc[XI][b][c], 0, 0, 0);                \
-  } else {                                                                                           \
-    _Pragma("unroll") for (int c = 0; c < NC; ++c) _Pragma("unroll") for (int b = 0; b < NB; ++b)    \
-        acc[XI][b][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wbf16x8, BQ[c][0]), AQ[b][1], acc[XI][b][c], 0, 0, 0); \
-    _Pragma("unroll") for (int c = 0; c < NC; ++c) _Pragma("unroll") for (int b = 0; b < NB; ++b)    \
-        acc[XI][b][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wbf16x8, BQ[c][1]), AQ[b][0], acc[XI][b][c], 0, 0, 0); \
-    _Pragma("unroll") for (int c = 0; c < NC; ++c) _Pragma("unroll") for (int b = 0; b < NB; ++b)    \
-        acc[XI][b][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wbf16x8, BQ[c][0]), AQ[b][0], acc[XI][b][c], 0, 0, 0); \
+#define W_MFMA12(XI, AQ, BQ)                                                                                                                           \
+  if constexpr (F32) {                                                                                                                                 \
+    _Pragma("unroll") for (int pl = 0; pl < 2; ++pl) _Pragma("unroll") for (int e = 0; e < 4; ++e)                                                     \
+    _Pragma("unroll") for (int c = 0; c < NC; ++c) _Pragma("unroll") for (int b = 0; b < NB; ++b)                                                      \
+        acc[XI][b][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(__builtin_bit_cast(cgd_f32x4, BQ[c][pl])[e], __builtin_bit_cast(cgd_f32x4, AQ[b][pl])[e], \
+                                                             acc[XI][b][c], 0, 0, 0);                                                                  \
+  } else {                                                                                                                                             \
+    _Pragma("unroll") for (int c = 0; c < NC; ++c) _Pragma("unroll") for (int b = 0; b < NB; ++b)                                                      \
+        acc[XI][b][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[c][0]), AQ[b][1], acc[XI][b][c], 0, 0, 0);           \
+    _Pragma("unroll") for (int c = 0; c < NC; ++c) _Pragma("unroll") for (int b = 0; b < NB; ++b)                                                      \
+        acc[XI][b][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[c][1]), AQ[b][0], acc[XI][b][c], 0, 0, 0);           \
+    _Pragma("unroll") for (int c = 0; c < NC; ++c) _Pragma("unroll") for (int b = 0; b < NB; ++b)                                                      \
+        acc[XI][b][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(cgd_bf16x8, BQ[c][0]), AQ[b][0], acc[XI][b][c], 0, 0, 0);           \
   }
 
-  wbf16x8 af[2][NB][2];  // [pipeline slot][block][plane]
+  cgd_bf16x8 af[2][NB][2];  // [pipeline slot][block][plane]
   uint4 bq[RING][NC][2];  // [ring slot][channel block][plane]
   {
     // prologue: stage chunk 0 completely, start the weight ring
     W_GN_LOAD(0);
 #pragma unroll
     for (int q = 0; q < DIST; ++q) W_B_LOAD(bq[q], 0, q);
-    wf32x4 pro[NTASK][4];  // all tasks in flight (the accumulators are not live yet)
+    cgd_f32x4 pro[NTASK][4];  // all tasks in flight (the accumulators are not live yet)
 #pragma unroll
     for (int j = 0; j < NTASK; ++j) W_TASK_LOAD(pro[j], j, 0);
 #pragma unroll
@@ -445,12 +419,12 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
         // (accumulator quads are copied out of the AGPRs one group at a time: left alone, the scheduler hoists every v_accvgpr_read of the block to the
         // top of the epilogue and the 512-register instantiations park accumulators in scratch memory — a dispatch with scratch costs +3.7 us)
         __builtin_amdgcn_sched_barrier(0);
-        wf32x4 m[4];
+        cgd_f32x4 m[4];
 #pragma unroll
-        for (int x = 0; x < 4; ++x) m[x] = wf32x4{acc[x][b][cj][4 * g], acc[x][b][cj][4 * g + 1], acc[x][b][cj][4 * g + 2], acc[x][b][cj][4 * g + 3]};
+        for (int x = 0; x < 4; ++x) m[x] = cgd_f32x4{acc[x][b][cj][4 * g], acc[x][b][cj][4 * g + 1], acc[x][b][cj][4 * g + 2], acc[x][b][cj][4 * g + 3]};
         const int u = ((2 * g + hh) ^ lp) * 4;
-        *(wf32x4*)&slab[pe * 32 + u] = (m[0] + m[1] + m[2]) * p.alpha;
-        *(wf32x4*)&slab[(pe + 1) * 32 + u] = (m[1] - m[2] - m[3]) * p.alpha;
+        *(cgd_f32x4*)&slab[pe * 32 + u] = (m[0] + m[1] + m[2]) * p.alpha;
+        *(cgd_f32x4*)&slab[(pe + 1) * 32 + u] = (m[1] - m[2] - m[3]) * p.alpha;
       }
     }
     // the slab is private to the wavefront and its LDS operations execute in order: only the compiler must not move the reads up
@@ -466,21 +440,21 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
     const float* rp = Rg ? Rg + m00 * p.ldr + col : nullptr;
     const long crow = (long)p.W * p.ldc, rrow = (long)p.W * p.ldr;
     const bool hb = biasg != nullptr;
-    const wf32x4 bv = hb ? wf32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]} : z4;
+    const cgd_f32x4 bv = hb ? cgd_f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]} : z4;
     // GroupNorm statistics of the finished tensor (p.stat, round 4): the lane sees 16 of the 128 pixels of every 8-row half tile for its 4 channels;
     // sums shifted by the half tile's first pixel (robust when |mean| >> std, like norm.hip), merged over the 8 lanes of a channel quad with three
     // xor-shuffles, written by the psub == 0 lanes as (mean, M2) per channel: 256 contiguous bytes per wavefront and half tile
     const bool st_on = p.stat != nullptr;
-    wf32x4 s1 = z4, s2 = z4, kk = z4;
+    cgd_f32x4 s1 = z4, s2 = z4, kk = z4;
     const bool bs_on = p.bstat != nullptr;
-    wf32x4 q1 = z4, q2 = z4, cfa = z4, cfb = z4, cfg_ = z4, cfm = z4;
+    cgd_f32x4 q1 = z4, q2 = z4, cfa = z4, cfb = z4, cfg_ = z4, cfm = z4;
     const float* bxp = nullptr;
     const long xrow = (long)p.W * p.ldbx;
     if (bs_on) {
       bxp = p.bx + m00 * p.ldbx + col;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const wf32x4 c_ = *(const wf32x4*)(p.bcoef + ((long)img * p.N + col + e) * 4);
+        const cgd_f32x4 c_ = *(const cgd_f32x4*)(p.bcoef + ((long)img * p.N + col + e) * 4);
         cfa[e] = c_[0]; cfb[e] = c_[1]; cfg_[e] = c_[2]; cfm[e] = c_[3];
       }
     }
@@ -488,29 +462,29 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
     // ~1.5 us latency and cannot be hoisted by the compiler above the stores of the previous group (it may alias the output): it is fetched one
     // group ahead by hand (rows of different groups never overlap, also when the residual IS the output buffer)
     constexpr int EG = NC == 2 ? 4 : 8;  // instructions in flight (2 per tile row); the 512-register instantiations have no room for 8
-    wf32x4 opn[EG];
+    cgd_f32x4 opn[EG];
     const bool second = Rg != nullptr || bs_on;
     const float* o2 = Rg ? rp : bxp;
     const long o2row = Rg ? rrow : xrow;
     const int o2ld = Rg ? p.ldr : p.ldbx;
     if (second) {
 #pragma unroll
-      for (int u = 0; u < EG; ++u) opn[u] = *(const wf32x4*)&o2[(u >> 1) * o2row + 8 * (u & 1) * o2ld];
+      for (int u = 0; u < EG; ++u) opn[u] = *(const cgd_f32x4*)&o2[(u >> 1) * o2row + 8 * (u & 1) * o2ld];
     }
 #pragma unroll
     for (int i0 = 0; i0 < 2 * TR; i0 += EG) {  // EG instructions = EG / 2 tile rows in flight
       // (the groups of 4 rows stay apart in the instruction stream: merged by the scheduler they need more registers than the 512-register
       // instantiations have left next to their accumulators — the allocator then parks accumulators in scratch memory)
       __builtin_amdgcn_sched_barrier(0);
-      wf32x4 v[EG], op[EG];
+      cgd_f32x4 v[EG], op[EG];
 #pragma unroll
-      for (int u = 0; u < EG; ++u) v[u] = *(const wf32x4*)&((u & 1) ? sl1 : sl0)[(i0 + u) * 256];
+      for (int u = 0; u < EG; ++u) v[u] = *(const cgd_f32x4*)&((u & 1) ? sl1 : sl0)[(i0 + u) * 256];
       if (second) {
 #pragma unroll
         for (int u = 0; u < EG; ++u) op[u] = opn[u];
         if (i0 + EG < 2 * TR) {
 #pragma unroll
-          for (int u = 0; u < EG; ++u) opn[u] = *(const wf32x4*)&o2[((i0 + EG + u) >> 1) * o2row + 8 * (u & 1) * o2ld];
+          for (int u = 0; u < EG; ++u) opn[u] = *(const cgd_f32x4*)&o2[((i0 + EG + u) >> 1) * o2row + 8 * (u & 1) * o2ld];
         }
       }
       if (Rg) {
@@ -534,17 +508,17 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
       if (bs_on) {
         // du = dz * SiLU'(x a + b); sums of du and du (x - mean) over the half tile (norm.hip gn_bwd_partial_kernel's arithmetic, v_rcp for the
         // division); x is read like a residual would be (whole lines)
-        const wf32x4(&xv)[EG] = op;  // (a launch has a residual or the backward sums, never both: the launcher checks)
+        const cgd_f32x4(&xv)[EG] = op;  // (a launch has a residual or the backward sums, never both: the launcher checks)
         if ((i0 & 15) == 0) q1 = q2 = z4;
         // (vector arithmetic: the compiler packs it into v_pk_fma / v_pk_mul / v_pk_add; the two transcendentals per element dominate)
 #pragma unroll
         for (int u = 0; u < EG; ++u) {
-          wf32x4 d = v[u];
+          cgd_f32x4 d = v[u];
           if (p.bact) {
-            const wf32x4 uu = xv[u] * cfa + cfb;
-            wf32x4 sg;
+            const cgd_f32x4 uu = xv[u] * cfa + cfb;
+            cgd_f32x4 sg;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) sg[e] = __builtin_amdgcn_rcpf(1.f + __expf(-uu[e]));
+            for (int e = 0; e < 4; ++e) sg[e] = cgd_sigmoid_rcp(uu[e]);
             d *= sg * (1.f + uu * (1.f - sg));
           }
           q1 += d;
@@ -561,8 +535,8 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
           if (psub == 0) {
             const long pt = ((long)img * (p.H >> 3) + (y0 >> 3) + (i0 >> 4)) * (p.W >> 4) + (x0 >> 4);
             float* so = p.bstat + (pt * p.N + col) * 2;
-            *(wf32x4*)so = wf32x4{cfg_[0] * q1[0], cfg_[0] * q2[0], cfg_[1] * q1[1], cfg_[1] * q2[1]};
-            *(wf32x4*)(so + 4) = wf32x4{cfg_[2] * q1[2], cfg_[2] * q2[2], cfg_[3] * q1[3], cfg_[3] * q2[3]};
+            *(cgd_f32x4*)so = cgd_f32x4{cfg_[0] * q1[0], cfg_[0] * q2[0], cfg_[1] * q1[1], cfg_[1] * q2[1]};
+            *(cgd_f32x4*)(so + 4) = cgd_f32x4{cfg_[2] * q1[2], cfg_[2] * q2[2], cfg_[3] * q1[3], cfg_[3] * q2[3]};
           }
         }
       }
@@ -574,7 +548,7 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
         }
 #pragma unroll
         for (int u = 0; u < EG; ++u) {
-          const wf32x4 d = v[u] - kk;
+          const cgd_f32x4 d = v[u] - kk;
           s1 += d;
           s2 += d * d;
         }
@@ -589,9 +563,9 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
           if (psub == 0) {
             const long pt = ((long)img * (p.H >> 3) + (y0 >> 3) + (i0 >> 4)) * (p.W >> 4) + (x0 >> 4);
             float* so = p.stat + (pt * p.N + col) * 2;
-            const wf32x4 mean = kk + s1 * (1.f / 128.f), m2 = s2 - s1 * s1 * (1.f / 128.f);
-            *(wf32x4*)so = wf32x4{mean[0], m2[0], mean[1], m2[1]};
-            *(wf32x4*)(so + 4) = wf32x4{mean[2], m2[2], mean[3], m2[3]};
+            const cgd_f32x4 mean = kk + s1 * (1.f / 128.f), m2 = s2 - s1 * s1 * (1.f / 128.f);
+            *(cgd_f32x4*)so = cgd_f32x4{mean[0], m2[0], mean[1], m2[1]};
+            *(cgd_f32x4*)(so + 4) = cgd_f32x4{mean[2], m2[2], mean[3], m2[3]};
           }
         }
       }
@@ -599,12 +573,7 @@ __global__ __launch_bounds__(256, OCC) void wconv_kernel(const float* __restrict
   }
   }  // cj
   }
-  W_STAMP(30);
-#ifdef CGD_WCONV_STAMPS
-  if (lane == 0)
-    g_wstamps[((long)blockIdx.x * 4 + wave) * 32 + 31] =
-        ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 4);  // XCC_ID | HW_ID
-#endif
+  W_STAMP_END();
 }
 
 // w: torch conv weight [Co][Ci][3][3].  dgrad = 0: g[kx] = w[n][k][ky][kx]; dgrad = 1: g[kx] = w[k][n][2-ky][2-kx].

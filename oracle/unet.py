@@ -24,10 +24,16 @@ def default_channel_mult(image_size):
     return {512: (0.5, 1, 1, 2, 2, 4, 4), 256: (1, 1, 2, 2, 4, 4), 128: (1, 1, 2, 3, 4), 64: (1, 2, 3, 4)}[image_size]
 
 
+def _f32(x):
+    """upstream's casts to float32 (GroupNorm32, the attention softmax, the timestep embedding) — except for a float64 tensor, which stays
+    float64: a model moved to double is the float64 reference of the same network (tests/value_regime_checks.py)"""
+    return x if x.dtype == th.float64 else x.float()
+
+
 def timestep_embedding(t, dim, max_period=10000):
     half = dim // 2
     freqs = th.exp(-math.log(max_period) * th.arange(half, dtype=th.float32) / half).to(t.device)
-    args = t[:, None].float() * freqs[None]
+    args = _f32(t[:, None]) * freqs[None]
     emb = th.cat([th.cos(args), th.sin(args)], dim=-1)
     if dim % 2:
         emb = th.cat([emb, th.zeros_like(emb[:, :1])], dim=-1)
@@ -36,7 +42,7 @@ def timestep_embedding(t, dim, max_period=10000):
 
 class GroupNorm32(nn.GroupNorm):
     def forward(self, x):
-        return super().forward(x.float()).type(x.dtype)
+        return super().forward(_f32(x)).type(x.dtype)
 
 
 class Resample(nn.Module):
@@ -109,7 +115,7 @@ class AttentionBlock(nn.Module):
             q, k, v = qkv.reshape(bs * nh, ch * 3, length).split(ch, dim=1)
         scale = 1 / math.sqrt(math.sqrt(ch))
         w = th.einsum("bct,bcs->bts", q * scale, k * scale)
-        w = th.softmax(w.float(), dim=-1).type(w.dtype)
+        w = th.softmax(_f32(w), dim=-1).type(w.dtype)
         a = th.einsum("bts,bcs->bct", w, v).reshape(bs, -1, length)
         h = self.proj_out(a)
         return (x + h).reshape(b, c, *spatial)

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Kernel-by-kernel comparison of the gfx950 code of two builds: the evidence for a refactor that must not change machine code (the
-timing counterpart is benchmarks/ab.sh).  Usage: benchmarks/isa_diff.py A B [-v]   (A, B: two libcgd_mi355x.so, or two executables
-such as the benchmarks/ubench programs).
+timing counterpart is benchmarks/ab.sh).  Usage: benchmarks/isa_diff.py A B [-v] [--map A_SYMBOL=B_SYMBOL ...]   (A, B: two
+libcgd_mi355x.so, or two executables such as the benchmarks/ubench programs).  --map compares a kernel of A with a kernel of B that carries
+another name (a kernel that became a template instantiation: same code expected, other mangled name).
 
 Extracts every gfx950 code object of both files (llvm-objdump --offloading, as tests/test_cabi.py does), disassembles them and reports,
 per kernel symbol, whether the instruction stream (mnemonics, operands and encodings; load addresses are dropped) is identical, and
@@ -55,17 +56,33 @@ def load(path):
                     while sym in out and out[sym][2] != o:  # same internal-linkage name in two translation units
                         sym += "'"
                     out[sym] = ([], meta.get(m.group(1)), o)
-                elif sym and line.strip():
+                elif sym and line.strip() and line.strip() != "...":  # "...": the zero fill up to the next symbol's alignment
                     out[sym][0].append(re.sub(r"//\s*[0-9A-Fa-f]+:\s*", "// ", line.strip()))
     return {k: (v[0], v[1]) for k, v in out.items()}
 
 
 def main(argv):
     verbose = "-v" in argv
-    paths = [a for a in argv if a != "-v"]
+    argv = [a for a in argv if a != "-v"]
+    renames, paths = {}, []
+    while argv:
+        arg = argv.pop(0)
+        if arg == "--map":
+            old, _, new = (argv.pop(0) if argv else "").partition("=")
+            if not old or not new:
+                sys.exit(__doc__)
+            renames[old] = new
+        else:
+            paths.append(arg)
     if len(paths) != 2:
         sys.exit(__doc__)
     a, b = load(paths[0]), load(paths[1])
+    for old, new in renames.items():
+        if old not in a or new not in b:
+            sys.exit(f"--map {old}={new}: {'A' if old not in a else 'B'} has no such symbol")
+        ia, ma = a.pop(old)
+        a[new] = ([line.replace(f"<{old}", f"<{new}") for line in ia], ma)  # branch targets are printed as <symbol+offset>
+        print(f"A's {old} is compared with B's {new}")
     print(f"A = {paths[0]}: {len(a)} symbols, {sum(m is not None for _, m in a.values())} kernels")
     print(f"B = {paths[1]}: {len(b)} symbols, {sum(m is not None for _, m in b.values())} kernels")
     bad = 0

@@ -212,7 +212,7 @@ _CLI_SPEC = f"""
 --timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', or 'plmsN' for PLMS (e.g. -respace plms50)
 --num_cutouts -cutn int 16 | random cutouts shown to CLIP per step
 --cutout_power -cutpow float 1.0 | exponent of the cutout size distribution
---clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, or 'A+B' to sum two towers
+--clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, ARCH=FILE for an open_clip ViT checkpoint (ARCH: ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14, optional -quickgelu suffix), or 'A+B' to sum two towers
 --uncond -uncond flag | use the unconditional 256 / 512 checkpoints
 --noise_schedule -sched str linear | 'linear' or 'cosine'
 --dropout -drop float 0.0 | dropout of the diffusion model (inference: keep 0)

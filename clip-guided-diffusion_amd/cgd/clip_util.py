@@ -117,6 +117,60 @@ def _text_config_from_state_dict(sd):
             sd["text_projection"].shape[1])
 
 
+def parse_clip_model_name(model_name):
+    """One `--clip_model` entry (after the 'A+B' split) -> (arch, activation, path).  open_clip architecture names are dash-spelled
+    (`cgd_amd.nets.OPENCLIP_CONFIGS`, optional `-quickgelu` suffix): 'ARCH=PATH' loads the checkpoint PATH as that architecture, 'ARCH' alone is
+    for CGD_SYNTHETIC_WEIGHTS=1.  Everything else — OpenAI's slash-spelled names, plain checkpoint paths — is (None, 'quick_gelu', model_name):
+    today's behaviour."""
+    head, sep, path = model_name.partition("=")
+    arch = _nets.openclip_arch(head.strip())
+    if arch is None:
+        return None, "quick_gelu", model_name
+    if sep and not path.strip():
+        raise ValueError(f"{model_name}: 'ARCH=PATH' needs a checkpoint path after '='")
+    return arch[0], arch[1], (path.strip() if sep else None)
+
+
+def _openclip_clean_state_dict(sd):
+    """open_clip training checkpoints wrap the weights ({'state_dict': ...}) and DataParallel prefixes every key with 'module.'; entries that are
+    not tensors go (epoch counters and the like).  `logit_scale`, `attn_mask` and other tensors no tower asks for are simply never read."""
+    if isinstance(sd, dict) and isinstance(sd.get("state_dict"), dict):
+        sd = sd["state_dict"]
+    return {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items() if isinstance(v, th.Tensor)}
+
+
+def openclip_configs_from_state_dict(arch, sd):
+    """The tower configurations of an open_clip checkpoint loaded as architecture `arch`: every dimension is inferred from tensor shapes as for
+    OpenAI's checkpoints, except the head counts, which no shape reveals (ViT-H-14: width 1280, 16 heads of 80) and which come from the table.
+    The inferred dimensions must equal the table's (ValueError names the first that does not); a tower whose MLP is not 4 x width (g-14,
+    bigG-14) is refused.  -> (cleaned state dict, image tower config, text tower config or None)."""
+    sd = _openclip_clean_state_dict(sd)
+    if "visual.proj" not in sd or "visual.conv1.weight" not in sd:
+        raise NotImplementedError(f"{arch}: the checkpoint has no ViT image tower in open_clip's native key scheme (visual.conv1 / visual.proj)")
+    vit_table, text_table = _nets.OPENCLIP_CONFIGS[arch]
+    towers = [("image", "visual.transformer.resblocks.0.mlp.c_fc.weight", sd["visual.conv1.weight"].shape[0])]
+    have_text = "text_projection" in sd
+    if have_text:
+        towers.append(("text", "transformer.resblocks.0.mlp.c_fc.weight", sd["ln_final.weight"].shape[0]))
+    for tower, key, width in towers:
+        if key in sd and tuple(sd[key].shape) != (4 * width, width):
+            raise NotImplementedError(f"{arch}: the {tower} tower's mlp.c_fc.weight is {tuple(sd[key].shape)}, not 4 x width = {(4 * width, width)}: "
+                                      "towers with another MLP ratio (ViT-g-14, ViT-bigG-14) are not supported")
+    vit = _vit_config_from_state_dict(sd)
+    vit = vit[:4] + (vit_table[4],) + vit[5:]
+    text = None
+    if have_text:
+        text = _text_config_from_state_dict(sd)
+        text = text[:4] + (text_table[4],) + text[5:]
+    fields = {"image": ("resolution", "patch", "width", "layers", "heads", "out_dim"),
+              "text": ("context_length", "vocab_size", "width", "layers", "heads", "out_dim")}
+    for tower, got, want in (("image", vit, vit_table), ("text", text, text_table)):
+        for name, g, w in zip(fields[tower], got or (), want):
+            if int(g) != int(w):
+                raise ValueError(f"{arch}: the checkpoint's {tower} tower has {name} {int(g)}, the architecture has {int(w)}")
+    return sd, tuple(int(v) for v in vit), (tuple(int(v) for v in text) if text else None)
+
+
 def _is_text_key(k):
     return k.startswith(("token_embedding.", "transformer.", "ln_final.")) or k in ("positional_embedding", "text_projection")
 
@@ -144,6 +198,9 @@ def load_clip(model_name="ViT-B/32", device="cpu"):
     if device == "cpu" or "cuda" not in device:
         raise ValueError("Invalid or unspecified device: {} (the MI355X path needs 'cuda[:N]'; no CPU fallback)".format(device))
     ctx = script_util.get_context(device)
+    arch, activation, arch_path = parse_clip_model_name(model_name)
+    if arch is not None:
+        return _load_openclip(ctx, model_name, arch, activation, arch_path, device)
     model_path = download_clip_model(model_name) if model_name in CLIP_MODEL_URLS else model_name
     if os.path.isfile(model_path):
         held = {}
@@ -186,6 +243,39 @@ def load_clip(model_name="ViT-B/32", device="cpu"):
             raise NotImplementedError(f"{model_name}: supported towers are {sorted(_nets.VIT_CONFIGS) + sorted(_nets.RN_CONFIGS)}")
         return ClipModel(tower, None, model_name), tower.input_resolution
     raise FileNotFoundError(f"{model_path} not found (set CGD_SYNTHETIC_WEIGHTS=1 for seeded random weights)")
+
+
+def _load_openclip(ctx, model_name, arch, activation, path, device):
+    """An open_clip (LAION) ViT: 'ARCH=PATH' reads the checkpoint into the native image and text towers (the `clip` package cannot build these
+    models, so prompts always go through the native text tower), 'ARCH' alone draws seeded random weights under CGD_SYNTHETIC_WEIGHTS=1."""
+    dev = f"cuda:{ctx.device}"
+    if path is None:
+        if not script_util.synthetic_weights_enabled():
+            raise FileNotFoundError(f"{model_name}: give the checkpoint as '{model_name}=PATH' (or set CGD_SYNTHETIC_WEIGHTS=1 for seeded random weights)")
+        tower = _nets.ClipImageTower(ctx, config=_nets.OPENCLIP_CONFIGS[arch][0], activation=activation)
+        _shard.load_broadcast(tower, lambda: _synthetic.synthetic_state_dict(tower, seed=4321, device=dev), dev)
+        return ClipModel(tower, None, model_name), tower.input_resolution
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path} not found")
+    held = {}
+
+    def probe():  # rank 0 only: the other ranks receive the configurations, never the file
+        try:
+            sd = th.jit.load(path, map_location="cpu").state_dict()
+        except RuntimeError:
+            sd = th.load(path, map_location="cpu")
+        held["sd"], cfg, text_cfg = openclip_configs_from_state_dict(arch, sd)
+        return cfg, text_cfg
+
+    cfg, text_cfg = _shard.on_rank0(probe)
+    tower = _nets.ClipImageTower(ctx, config=cfg, activation=activation)
+    _shard.load_broadcast(tower, lambda: {k: v.float() for k, v in held["sd"].items() if k.startswith("visual.")}, dev, prefix="visual.")
+    text_model = None
+    if text_cfg is not None:
+        text_model = _nets.ClipTextTower(ctx, config=text_cfg, activation=activation)  # the same activation as its image tower
+        _shard.load_broadcast(text_model, lambda: {k: v.float() for k, v in held["sd"].items() if _is_text_key(k)}, dev)
+    held.clear()
+    return ClipModel(tower, text_model, model_name), tower.input_resolution
 
 
 def _synthetic_text_embedding(txt, dim, device):

@@ -674,7 +674,7 @@ bool attn_mid_ok(const AttnShape& sh, int ldq, int ldo) { return sh.d == 64 && s
 // stays on attn_s64_*: no workload of the path has it, and below T = 8 the statistics (2 x 32 floats per head) would not fit the T x T scratch a
 // caller sized for the probabilities.
 bool attn_flash_selected(const cgd_ctx* ctx, const AttnShape& sh, int ldq, int ldo, bool x3) {
-  if (!x3 || sh.d != AS_D || (ldq & 3) || (ldo & 3)) return false;
+  if (!x3 || (sh.d != AS_D && sh.d != 80) || (ldq & 3) || (ldo & 3)) return false;  // d = 80: open_clip's ViT-H-14 (T <= 32 stays on the GEMM path)
   return sh.T > AS_T ? ctx->attn_flash >= 1 : (sh.T > 32 && ctx->attn_flash >= 2);
 }
 
@@ -932,6 +932,6 @@ extern "C" int cgd_op_attn_plan(int T, int d, int ldq, int ldo, int precision, i
   const bool x3 = ctx.attn_x3 && precision == CGD_PREC_BF16X3;
   const AttnPath path = attn_select(&ctx, sh, ldq, ldo, x3);
   out2[0] = (int)path;
-  out2[1] = path == ATTN_S64 ? 1 : path == ATTN_MID ? 2 : path == ATTN_FLASH ? ((T <= AS_T && ctx.attn_flash >= 3) ? 1 : 2) : 0;
+  out2[1] = path == ATTN_S64 ? 1 : path == ATTN_MID ? 2 : path == ATTN_FLASH ? ((T <= AS_T && ctx.attn_flash >= 3 && d == AS_D) ? 1 : 2) : 0;
   return 0;
 }

@@ -274,7 +274,7 @@ struct GemmParams {
   //   act_in : C[m][n] = (alpha * acc + bias + R) * act'(U[m][n]) (backward through the activation whose input was U)
   float* act_out = nullptr;
   const float* act_in = nullptr;
-  int ld_act = 0, act = 0;  // act: 1 SiLU, 2 QuickGELU
+  int ld_act = 0, act = 0;  // act: 1 SiLU, 2 QuickGELU, 3 exact (erf) GELU
   int skip_group = 0;  // hgemm2 in one slice only (cgd_gemm_fuses_act): rows come in groups of `skip_group`; the FIRST row of every group is
                        // computed but not written and the others are written compactly (output row = row - group - 1).  The ViT's
                        // patch-embedding dgrad: 16 x 50 token rows in, 16 x 49 patch rows out, as ONE weight GEMM instead of 16 batched

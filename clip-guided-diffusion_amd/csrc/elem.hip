@@ -118,11 +118,14 @@ __global__ __launch_bounds__(256) void concat2_kernel(const float* __restrict__ 
   }
 }
 
+// act 3: exact GELU 0.5 u (1 + erf(u / sqrt 2)) (the open_clip towers); 1 / 2: u sigmoid(k u) with k = 1 (SiLU) / 1.702 (QuickGELU)
 __device__ __forceinline__ float act_f(float u, int act) {
+  if (act == 3) return 0.5f * u * (1.f + erff(u * 0.70710678f));
   const float k = act == 2 ? 1.702f : 1.f;
   return u / (1.f + __expf(-k * u));
 }
 __device__ __forceinline__ float dact_f(float u, int act) {
+  if (act == 3) return 0.5f * (1.f + erff(u * 0.70710678f)) + u * 0.3989422804f * __expf(-0.5f * u * u);
   const float k = act == 2 ? 1.702f : 1.f;
   const float s = 1.f / (1.f + __expf(-k * u));
   return s * (1.f + k * u * (1.f - s));
@@ -282,6 +285,7 @@ static void flat_invalidate(cgd_ctx* ctx, const float* p, long n) {
 }
 
 int cgd_launch_act_fwd(cgd_ctx* ctx, const float* x, float* y, long n, int act, hipStream_t s) {
+  if (act < 1 || act > 3) CGD_FAIL(ctx, "activation code must be 1 (SiLU), 2 (QuickGELU) or 3 (GELU)");
   CGD_TRY(cgd_sync_pending(ctx, s));  // reads activations: a deferred split-K reduction must have landed
   flat_invalidate(ctx, y, n);
   CGD_LAUNCH(act_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, y, n, act);
@@ -289,6 +293,7 @@ int cgd_launch_act_fwd(cgd_ctx* ctx, const float* x, float* y, long n, int act, 
   return 0;
 }
 int cgd_launch_act_bwd(cgd_ctx* ctx, const float* x, const float* dy, float* dx, long n, int act, hipStream_t s) {
+  if (act < 1 || act > 3) CGD_FAIL(ctx, "activation code must be 1 (SiLU), 2 (QuickGELU) or 3 (GELU)");
   CGD_TRY(cgd_sync_pending(ctx, s));  // reads activations: a deferred split-K reduction must have landed
   flat_invalidate(ctx, dx, n);
   CGD_LAUNCH(act_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, dy, dx, n, act);

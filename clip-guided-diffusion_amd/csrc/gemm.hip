@@ -703,6 +703,7 @@ int cgd_launch_gemm(cgd_ctx* ctx, GemmParams p, hipStream_t s) {
   if (p.gn_ab && !use_h) CGD_FAIL(ctx, "cgd_launch_gemm: only the halo conv kernel applies a GroupNorm on the fly (cgd_conv_uses_hconv)");
   if (p.a_mode && kernel != 3) CGD_FAIL(ctx, "cgd_launch_gemm: only the GEMV kernel forms its A rows on the fly (cgd_gemm_is_gemv)");
   if (p.skip_group && !(use_g && p.splitk == 1)) CGD_FAIL(ctx, "cgd_launch_gemm: skip_group needs the weight GEMM kernel in one slice (cgd_gemm_fuses_act)");
+  if ((p.act_out || p.act_in) && (p.act < 1 || p.act > 3)) CGD_FAIL(ctx, "cgd_launch_gemm: activation code must be 1 (SiLU), 2 (QuickGELU) or 3 (GELU)");
   if ((p.act_out || p.act_in) && !(use_g && p.splitk == 1 && ctx->hgemm_var != 0))
     CGD_FAIL(ctx, "cgd_launch_gemm: only hgemm2 in one slice fuses an activation into its epilogue (cgd_gemm_fuses_act)");
   if (p.splitk > 1) p.ws = ctx->ws;

@@ -274,6 +274,21 @@ epilogue:
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// exact (erf) GELU, activation code 3 of the fused epilogues, and its derivative: same arithmetic as elem.hip act_f / dact_f.  The k-scaled sigmoid of
+// codes 1 / 2 cannot express it: hgemm2_kernel's GELU instantiations.
+__device__ __forceinline__ cgd_f32x4 hg_gelu4(const cgd_f32x4 u) {
+  cgd_f32x4 a;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) a[e] = 0.5f * u[e] * (1.f + erff(u[e] * 0.70710678f));
+  return a;
+}
+__device__ __forceinline__ cgd_f32x4 hg_dgelu4(const cgd_f32x4 u) {
+  cgd_f32x4 d;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) d[e] = 0.5f * (1.f + erff(u[e] * 0.70710678f)) + u[e] * 0.3989422804f * __expf(-0.5f * u[e] * u[e]);
+  return d;
+}
+
 // hgemm2_kernel: the same GEMM with the wave -> sub-tile mapping and the weight-fragment pipeline of hconv2_kernel.
 //   * Why: the rocprofv3 trace of round 2 (profiles/r2_trace_step_a.txt) shows the step's kernels running back to back, i.e.
 //     the time of the ViT linears (M = 800 token rows, 13-28 us for 1-4 GFLOP) is INSIDE hgemm_kernel: one workgroup per CU,
@@ -308,7 +323,9 @@ constexpr int h2_lcm(int a, int b) { return a / h2_gcd(a, b) * b; }
 // The workgroup becomes 8 wavefronts = 2 K-groups x 4 column blocks over a 128-deep chunk: group kg multiplies k-steps 4 kg .. 4 kg + 3
 // of every chunk (its own weight fragments, its own accumulators), the 512 threads stage the 64 x 128 patch together, and group 1 hands
 // its partial block to group 0 through LDS before the epilogue.  Per wavefront the instruction stream of a chunk is unchanged.
-template <int MODE, int TM, int RING = 8, int NSET = (TM == 64 ? 2 : 1), int KG = 1>
+// GELU: the fused activation (act_out / act_in) is the exact GELU, code 3.  A template parameter, not a branch on p.act: erff inlined into the unrolled
+// epilogues nearly triples the kernel (8363 -> 22573 instructions at TM = 128), and the instantiations every other launch runs stay as they were.
+template <int MODE, int TM, int RING = 8, int NSET = (TM == 64 ? 2 : 1), int KG = 1, bool GELU = false>
 __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restrict__ Ag, const uint4* __restrict__ Bg, float* Cg,
                                                      const float* __restrict__ biasg, const float* Rg, float* __restrict__ wsg,
                                                      const HGemmParams p) {
@@ -600,10 +617,14 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
         if (Rg) o += rv[u];
         if (p.act_in) {  // backward through the activation: multiply by act'(u), same arithmetic as elem.hip dact_f
           cgd_f32x4 d;
+          if constexpr (GELU) {
+            d = hg_dgelu4(uv[u]);
+          } else {
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float sg = 1.f / (1.f + __expf(-ka * uv[u][e]));
-            d[e] = sg * (1.f + ka * uv[u][e] * (1.f - sg));
+            for (int e = 0; e < 4; ++e) {
+              const float sg = 1.f / (1.f + __expf(-ka * uv[u][e]));
+              d[e] = sg * (1.f + ka * uv[u][e] * (1.f - sg));
+            }
           }
           o *= d;
         }
@@ -611,8 +632,12 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
           *(cgd_f32x4*)&Cg[row[u] * p.ldc + col] = o;
           if (p.act_out) {  // second output: the activated tensor, same arithmetic as elem.hip act_f
             cgd_f32x4 a;
+            if constexpr (GELU) {
+              a = hg_gelu4(o);
+            } else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) a[e] = o[e] / (1.f + __expf(-ka * o[e]));
+              for (int e = 0; e < 4; ++e) a[e] = o[e] / (1.f + __expf(-ka * o[e]));
+            }
             *(cgd_f32x4*)&p.act_out[row[u] * p.ld_act + col] = a;
           }
         }
@@ -663,18 +688,26 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
       if (Rg) o += rv[g];
       if (p.act_in) {  // backward through the activation: multiply by act'(u), same arithmetic as elem.hip dact_f
         cgd_f32x4 d;
+        if constexpr (GELU) {
+          d = hg_dgelu4(uv[g]);
+        } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float sg = 1.f / (1.f + __expf(-ka * uv[g][e]));
-          d[e] = sg * (1.f + ka * uv[g][e] * (1.f - sg));
+          for (int e = 0; e < 4; ++e) {
+            const float sg = 1.f / (1.f + __expf(-ka * uv[g][e]));
+            d[e] = sg * (1.f + ka * uv[g][e] * (1.f - sg));
+          }
         }
         o *= d;
       }
       *(cgd_f32x4*)&Cg[row * p.ldc + col] = o;
       if (p.act_out) {  // second output: the activated tensor, same arithmetic as elem.hip act_f
         cgd_f32x4 a;
+        if constexpr (GELU) {
+          a = hg_gelu4(o);
+        } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) a[e] = o[e] / (1.f + __expf(-ka * o[e]));
+          for (int e = 0; e < 4; ++e) a[e] = o[e] / (1.f + __expf(-ka * o[e]));
+        }
         *(cgd_f32x4*)&p.act_out[row * p.ld_act + col] = a;
       }
     }
@@ -960,6 +993,8 @@ int cgd_launch_hgemm(cgd_ctx* ctx, const GemmParams& g, hipStream_t s) {
   const bool v2 = ctx->hgemm_var != 0 && (long)g.M * g.lda < (1L << 29);
   if (g.skip_group && (!v2 || g.splitk > 1 || g.R || g.act_out || g.act_in))
     CGD_FAIL(ctx, "hgemm: skip_group needs hgemm2 in one slice without residual / activation operands");
+  const bool gelu = (g.act_out || g.act_in) && g.act == 3;
+  if (gelu && !v2) CGD_FAIL(ctx, "hgemm: only hgemm2 fuses the GELU activation");
 #define HG_ARGS grid, dim3(256), 0, s, g.A, (const uint4*)packed, g.C, g.bias, g.R, g.ws, p
   if (!v2) {
     if (x3) CGD_LAUNCH((hgemm_kernel<1>), HG_ARGS); else CGD_LAUNCH((hgemm_kernel<2>), HG_ARGS);
@@ -968,7 +1003,16 @@ int cgd_launch_hgemm(cgd_ctx* ctx, const GemmParams& g, hipStream_t s) {
     // two K-groups of wavefronts per workgroup (512 threads): see hgemm2_kernel; always on the LDS epilogue.  Automatic only where the
     // micro-benchmark shows a gain (profiles/r4_hgemm_kgroups.txt): one workgroup per CU at most (an 8-wavefront workgroup has a CU to itself,
     // a second round of workgroups costs more than the loop gains) and >= 8 64-deep chunks per slice (the prologue / hand-over are longer)
-    CGD_LAUNCH((hgemm2_kernel<1, 64, 8, 2, 2>), grid, dim3(512), 0, s, g.A, (const uint4*)packed, g.C, g.bias, g.R, g.ws, p);
+    if (gelu) CGD_LAUNCH((hgemm2_kernel<1, 64, 8, 2, 2, true>), grid, dim3(512), 0, s, g.A, (const uint4*)packed, g.C, g.bias, g.R, g.ws, p);
+    else CGD_LAUNCH((hgemm2_kernel<1, 64, 8, 2, 2>), grid, dim3(512), 0, s, g.A, (const uint4*)packed, g.C, g.bias, g.R, g.ws, p);
+  } else if (gelu) {  // the exact-GELU epilogues (the open_clip towers' c_fc and its backward)
+    if (tm == 96) {
+      if (x3) CGD_LAUNCH((hgemm2_kernel<1, 96, 8, 2, 1, true>), HG_ARGS); else CGD_LAUNCH((hgemm2_kernel<2, 96, 8, 2, 1, true>), HG_ARGS);
+    } else if (tm == 64) {
+      if (x3) CGD_LAUNCH((hgemm2_kernel<1, 64, 8, 2, 1, true>), HG_ARGS); else CGD_LAUNCH((hgemm2_kernel<2, 64, 8, 2, 1, true>), HG_ARGS);
+    } else {
+      if (x3) CGD_LAUNCH((hgemm2_kernel<1, 128, 8, 1, 1, true>), HG_ARGS); else CGD_LAUNCH((hgemm2_kernel<2, 128, 8, 1, 1, true>), HG_ARGS);
+    }
   } else if (tm == 96) {
     if (x3) CGD_LAUNCH((hgemm2_kernel<1, 96, 8, 2>), HG_ARGS); else CGD_LAUNCH((hgemm2_kernel<2, 96, 8, 2>), HG_ARGS);
   } else if (tm == 64) {

@@ -43,7 +43,7 @@ int cgd_launch_copy2d(cgd_ctx* ctx, const float* a, int lda, const float* b, int
 // out[:, 0:Ca] = a, out[:, Ca:Ca+Cb] = b
 int cgd_launch_concat2(cgd_ctx* ctx, const float* a, int lda, int Ca, const float* b, int ldb, int Cb, float* out, int ldo, long rows,
                        hipStream_t s);
-// act: 1 SiLU, 2 QuickGELU.   fwd: y = act(x);  bwd: dx = dy * act'(x)
+// act: 1 SiLU, 2 QuickGELU, 3 exact (erf) GELU; any other code fails.   fwd: y = act(x);  bwd: dx = dy * act'(x)
 int cgd_launch_act_fwd(cgd_ctx* ctx, const float* x, float* y, long n, int act, hipStream_t s);
 int cgd_launch_act_bwd(cgd_ctx* ctx, const float* x, const float* dy, float* dx, long n, int act, hipStream_t s);
 // batched transpose: out[z][c][r] = in[z][r][c]  (in: [R][ldi], out: [Cc][ldo]); pad columns r in [R, ldo) are zeroed
@@ -93,7 +93,7 @@ int cgd_attn_fwd(cgd_ctx* ctx, const AttnShape& sh, const float* qkv, int ldq, f
 int cgd_attn_bwd(cgd_ctx* ctx, const AttnShape& sh, const float* qkv, int ldq, const float* dout, int lddo, float* dqkv, int lddq,
                  const AttnBufs& bufs, hipStream_t s);
 
-// attn_flash.hip (round 5): d = 64, T > 32 in bf16x3 contexts (T > 64 only at CGD_ATTN_FLASH=1); P is never materialised, bufs.P holds the row statistics (LSE | D),
+// attn_flash.hip (round 5): d = 64 or 80, T > 32 in bf16x3 contexts (T > 64 only at CGD_ATTN_FLASH=1); P is never materialised, bufs.P holds the row statistics (LSE | D),
 // bufs.qkvT a copy of O for the backward's D = rowsum(dO * O).  qo / ko / vo / step: column offsets of head 0 and the per-head step
 // (sh.causal: the causal instantiation)
 int cgd_attn_flash_fwd(cgd_ctx* ctx, const AttnShape& sh, const float* qkv, int ldq, float* out, int ldo, const AttnBufs& bufs, long qo,

@@ -121,10 +121,11 @@ static inline GemmParams lin(const float* A, int lda, const float* Wt, int K, fl
 }
 
 // ---- CLIP's ResidualAttentionBlock (clip.model), shared by the image tower (vit.hip) and the text tower (text.hip):
-//   x1 = x + out_proj(MHA(ln_1(x))),  x_out = x1 + c_proj(QuickGELU(c_fc(ln_2(x1))))
+//   x1 = x + out_proj(MHA(ln_1(x))),  x_out = x1 + c_proj(act(c_fc(ln_2(x1)))), act = QuickGELU or GELU
 struct ClipBlock {
   std::string pre;  // parameter prefix, "transformer.resblocks.{l}"
   int W = 0, heads = 0;
+  int act = 2;  // activation between c_fc and c_proj: 2 QuickGELU (OpenAI's towers), 3 exact GELU (open_clip's); cgd_vit_set_activation / cgd_text_set_activation
   float *ln1g = 0, *ln1b = 0, *inw = 0, *inb = 0, *ow = 0, *ob = 0;
   float *ln2g = 0, *ln2b = 0, *fcw = 0, *fcb = 0, *pjw = 0, *pjb = 0;
   void add_params(NetBase& net, const std::string& prefix, int width, int nheads);  // build(): registers the twelve parameters
@@ -135,6 +136,13 @@ struct ClipActs {
   DevBuf st1, y, qkv, a, x1, st2, y2, u, ga;
   AttnScratch att;
 };
+// the towers' cgd_*_set_activation: any time after create
+template <class Blocks>
+int clip_set_activation(cgd_ctx* ctx, Blocks& blocks, int act) {
+  if (act != 2 && act != 3) CGD_FAIL(ctx, "set_activation: act must be 2 (QuickGELU) or 3 (GELU)");
+  for (auto& b : blocks) b.act = act;
+  return 0;
+}
 // x [N*T][W] -> xo [N*T][W] (xo != x); causal: key j > query i is masked (the text tower)
 int clip_block_fwd(NetBase& net, const ClipBlock& b, ClipActs& t, const float* x, float* xo, int N, int T, bool causal, hipStream_t s);
 

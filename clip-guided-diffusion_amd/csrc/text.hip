@@ -130,6 +130,7 @@ int cgd_text_num_params(cgd_text* t) { return net_num_params(t); }
 int cgd_text_param_info(cgd_text* t, int i, char* buf, int len, int64_t* numel) { return net_param_info(t, i, buf, len, numel); }
 int cgd_text_set_param(cgd_text* t, const char* name, const float* data, int64_t numel) { return net_set_param(t, name, data, numel); }
 int cgd_text_finalize(cgd_text* t) { return net_finalize(t); }
+int cgd_text_set_activation(cgd_text* t, int act) { return t ? clip_set_activation(t->net.ctx, t->net.layers, act) : -3; }
 int cgd_text_forward(cgd_text* t, const int64_t* tokens, int N, float* emb, void* stream) {
   if (!tokens || !emb) return -3;
   return net_pass(t, stream, [&](hipStream_t s) { return t->net.forward(tokens, N, emb, s); });

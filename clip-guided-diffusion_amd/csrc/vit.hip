@@ -54,15 +54,15 @@ int clip_block_fwd(NetBase& net, const ClipBlock& b, ClipActs& t, const float* x
   CGD_TRY(cgd_launch_gemm(ctx, lin(t.a.p, W, b.ow, W, t.x1.p, W, b.ob, x, W, rows, W, 1), s));
   CGD_TRY(cgd_launch_ln_fwd(ctx, t.x1.p, W, t.y2.p, W, (int)rows, W, b.ln2g, b.ln2b, 1e-5f, t.st2.p, s));
   {
-    // c_fc + QuickGELU: the activation runs in the GEMM's epilogue where hgemm2 takes the launch in one slice (u is kept
+    // c_fc + QuickGELU / GELU (b.act): the activation runs in the GEMM's epilogue where hgemm2 takes the launch in one slice (u is kept
     // for the image tower's backward pass, ga feeds c_proj); otherwise the separate elementwise kernel
     GemmParams fc = lin(t.y2.p, W, b.fcw, W, t.u.p, 4 * W, b.fcb, nullptr, 0, rows, 4 * W);
     if (cgd_gemm_fuses_act(ctx, fc)) {
-      fc.act_out = t.ga.p; fc.ld_act = 4 * W; fc.act = 2;
+      fc.act_out = t.ga.p; fc.ld_act = 4 * W; fc.act = b.act;
       CGD_TRY(cgd_launch_gemm(ctx, fc, s));
     } else {
       CGD_TRY(cgd_launch_gemm(ctx, fc, s));
-      CGD_TRY(cgd_launch_act_fwd(ctx, t.u.p, t.ga.p, rows * 4 * W, 2, s));
+      CGD_TRY(cgd_launch_act_fwd(ctx, t.u.p, t.ga.p, rows * 4 * W, b.act, s));
     }
   }
   return cgd_launch_gemm(ctx, lin(t.ga.p, 4 * W, b.pjw, 4 * W, xo, W, b.pjb, t.x1.p, W, rows, W, 1), s);
@@ -183,15 +183,15 @@ int ViT::dgrad(const float* demb, float* dimg, hipStream_t s) {
     CGD_TRY(ensure(l.dy, rows * W)); CGD_TRY(ensure(l.dx, rows * W));
     // MLP
     {
-      // d(c_proj) and the backward of QuickGELU: du = (dcur @ W_proj) * gelu'(u), fused like the forward
+      // d(c_proj) and the backward of the activation: du = (dcur @ W_proj) * gelu'(u), fused like the forward
       GemmParams pj = lin(dcur, W, l.pjwT, W, l.dga.p, 4 * W, nullptr, nullptr, 0, rows, 4 * W);
       if (cgd_gemm_fuses_act(ctx, pj)) {
         pj.C = l.du.p;
-        pj.act_in = l.f.u.p; pj.ld_act = 4 * W; pj.act = 2;
+        pj.act_in = l.f.u.p; pj.ld_act = 4 * W; pj.act = l.act;
         CGD_TRY(cgd_launch_gemm(ctx, pj, s));
       } else {
         CGD_TRY(cgd_launch_gemm(ctx, pj, s));
-        CGD_TRY(cgd_launch_act_bwd(ctx, l.f.u.p, l.dga.p, l.du.p, rows * 4 * W, 2, s));
+        CGD_TRY(cgd_launch_act_bwd(ctx, l.f.u.p, l.dga.p, l.du.p, rows * 4 * W, l.act, s));
       }
     }
     CGD_TRY(cgd_launch_gemm(ctx, lin(l.du.p, 4 * W, l.fcwT, 4 * W, l.dy2.p, W, nullptr, nullptr, 0, rows, W, 1), s));
@@ -244,6 +244,11 @@ int cgd_vit_num_params(cgd_vit* v) { return net_num_params(v); }
 int cgd_vit_param_info(cgd_vit* v, int i, char* buf, int len, int64_t* numel) { return net_param_info(v, i, buf, len, numel); }
 int cgd_vit_set_param(cgd_vit* v, const char* name, const float* data, int64_t numel) { return net_set_param(v, name, data, numel); }
 int cgd_vit_finalize(cgd_vit* v) { return net_finalize(v); }
+int cgd_vit_set_activation(cgd_vit* v, int act) {
+  if (!v) return -3;
+  v->net.have_fwd = false;  // a dgrad after the switch needs a forward that ran with it
+  return clip_set_activation(v->net.ctx, v->net.layers, act);
+}
 int cgd_vit_forward(cgd_vit* v, const float* img, int layout, int N, float* emb, void* stream) {
   return net_pass(v, stream, [&](hipStream_t s) { return v->net.forward(img, layout, N, emb, s); });
 }

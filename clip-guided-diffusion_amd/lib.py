@@ -88,6 +88,7 @@ _SIGS = {
     "cgd_vit_param_info": (i32, [vp, i32, C.c_char_p, i32, C.POINTER(i64)]),
     "cgd_vit_set_param": (i32, [vp, C.c_char_p, vp, i64]),
     "cgd_vit_finalize": (i32, [vp]),
+    "cgd_vit_set_activation": (i32, [vp, i32]),
     "cgd_vit_forward": (i32, [vp, vp, i32, i32, vp, vp]),
     "cgd_vit_dgrad": (i32, [vp, vp, vp, vp]),
     "cgd_text_create": (i32, [vp, C.POINTER(TextConfig), C.POINTER(vp)]),
@@ -96,6 +97,7 @@ _SIGS = {
     "cgd_text_param_info": (i32, [vp, i32, C.c_char_p, i32, C.POINTER(i64)]),
     "cgd_text_set_param": (i32, [vp, C.c_char_p, vp, i64]),
     "cgd_text_finalize": (i32, [vp]),
+    "cgd_text_set_activation": (i32, [vp, i32]),
     "cgd_text_forward": (i32, [vp, vp, i32, vp, vp]),
     "cgd_rn_create": (i32, [vp, C.POINTER(RNConfig), C.POINTER(vp)]),
     "cgd_rn_destroy": (None, [vp]),

@@ -34,6 +34,32 @@ TEXT_CONFIGS = {
 }
 
 
+OPENCLIP_CONFIGS = {
+    # open_clip (LAION) ViT architectures, dash-spelled as open_clip spells them (OpenAI's names are slash-spelled: no collision):
+    # name: (image tower (resolution, patch, width, layers, heads, out_dim), text tower (context_length, vocab_size, width, layers, heads, out_dim)).
+    # Written from memory of open_clip's model configs; loading a checkpoint cross-checks every dimension a shape reveals (cgd.clip_util).
+    # All four were trained with the exact GELU; "<name>-quickgelu" (open_clip's own suffix) selects QuickGELU.  ViT-H-14: head dim 80.
+    "ViT-B-32": ((224, 32, 768, 12, 12, 512), (77, 49408, 512, 12, 8, 512)),
+    "ViT-B-16": ((224, 16, 768, 12, 12, 512), (77, 49408, 512, 12, 8, 512)),
+    "ViT-L-14": ((224, 14, 1024, 24, 16, 768), (77, 49408, 768, 12, 12, 768)),
+    "ViT-H-14": ((224, 14, 1280, 32, 16, 1024), (77, 49408, 1024, 24, 16, 1024)),
+}
+
+ACTIVATIONS = {"quick_gelu": 2, "gelu": 3}  # the codes of cgd_vit_set_activation / cgd_text_set_activation / cgd_op_act
+
+
+def openclip_arch(name):
+    """'ViT-H-14' -> ('ViT-H-14', 'gelu'); 'ViT-B-32-quickgelu' -> ('ViT-B-32', 'quick_gelu'); anything else -> None."""
+    base, act = (name[:-len("-quickgelu")], "quick_gelu") if name.endswith("-quickgelu") else (name, "gelu")
+    return (base, act) if base in OPENCLIP_CONFIGS else None
+
+
+def _activation_code(activation):
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"activation must be one of {sorted(ACTIVATIONS)}, got {activation!r}")
+    return ACTIVATIONS[activation]
+
+
 class _Net:
     _prefix = None
 
@@ -185,8 +211,10 @@ class UNetFunction(th.autograd.Function):
 class ClipImageTower(_Net):
     _prefix = "vit"
 
-    def __init__(self, ctx, name="ViT-B/32", config=None):
+    def __init__(self, ctx, name="ViT-B/32", config=None, activation="quick_gelu"):
+        """activation: "quick_gelu" (OpenAI's checkpoints) or "gelu" (the exact GELU of the open_clip / LAION checkpoints)."""
         self.ctx = ctx
+        act = _activation_code(activation)
         res, patch, width, layers, heads, out = config or VIT_CONFIGS[name]
         cfg = L.ViTConfig(res, patch, width, layers, heads, out)
         self.cfg = cfg
@@ -195,6 +223,9 @@ class ClipImageTower(_Net):
         h = C.c_void_p()
         ctx.check(ctx.lib.cgd_vit_create(ctx.h, C.byref(cfg), C.byref(h)))
         self._adopt(h)
+        self.activation = activation
+        if act != ACTIVATIONS["quick_gelu"]:
+            ctx.check(ctx.lib.cgd_vit_set_activation(h, act))
         self._layout = 0
         self._n = 0
 
@@ -239,14 +270,18 @@ class ClipTextTower(_Net):
     """`clip_model.encode_text(tokens)` (clip.model.CLIP.encode_text) on the device: forward only, in the context's precision mode."""
     _prefix = "text"
 
-    def __init__(self, ctx, name="ViT-B/32", config=None):
+    def __init__(self, ctx, name="ViT-B/32", config=None, activation="quick_gelu"):
         self.ctx = ctx
+        act = _activation_code(activation)
         T, vocab, width, layers, heads, out = config or TEXT_CONFIGS[name]
         self.cfg = L.TextConfig(T, vocab, width, layers, heads, out)
         self.context_length, self.vocab_size, self.width, self.out_dim = T, vocab, width, out
         h = C.c_void_p()
         ctx.check(ctx.lib.cgd_text_create(ctx.h, C.byref(self.cfg), C.byref(h)))
         self._adopt(h)
+        self.activation = activation
+        if act != ACTIVATIONS["quick_gelu"]:
+            ctx.check(ctx.lib.cgd_text_set_activation(h, act))
 
     def load_clip_state_dict(self, sd):
         """An OpenAI CLIP state dict: the text tower's keys are top-level (`visual.*` and `logit_scale` are not read)."""

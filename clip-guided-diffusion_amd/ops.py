@@ -216,7 +216,7 @@ def upsample2x(ctx, x_nhwc, scale=1.0):
 
 
 def act(ctx, x, kind, dy=None):
-    """kind 1 SiLU, 2 QuickGELU; with dy returns dy * act'(x)."""
+    """kind 1 SiLU, 2 QuickGELU, 3 exact (erf) GELU; with dy returns dy * act'(x)."""
     px, pdy = _dense(x, "x"), _dense(dy, "dy")
     if dy is not None and dy.numel() != x.numel():
         raise ValueError(f"dy: {dy.numel()} elements, x has {x.numel()}")

@@ -110,6 +110,9 @@ int cgd_vit_num_params(cgd_vit* v);
 int cgd_vit_param_info(cgd_vit* v, int index, char* name_buf, int buf_len, int64_t* numel);
 int cgd_vit_set_param(cgd_vit* v, const char* name, const float* data, int64_t numel);
 int cgd_vit_finalize(cgd_vit* v);
+/* activation between c_fc and c_proj of every block: 2 QuickGELU x sigmoid(1.702 x) (the default: OpenAI's checkpoints), 3 exact GELU
+ * 0.5 x (1 + erf(x / sqrt 2)) (the open_clip / LAION checkpoints).  Any time after create; another value returns -2 (cgd_last_error). */
+int cgd_vit_set_activation(cgd_vit* v, int act);
 /* layout 0: img (N,3,res,res) NCHW; layout 1: patch rows [N*g*g][3*patch*patch] (what cgd_cutouts_fwd layout 1 writes) */
 int cgd_vit_forward(cgd_vit* v, const float* img, int layout, int N, float* emb /* (N,out_dim) */, void* stream);
 int cgd_vit_dgrad(cgd_vit* v, const float* d_emb, float* d_img /* same layout as the forward input */, void* stream);
@@ -130,6 +133,7 @@ int cgd_text_num_params(cgd_text* t);
 int cgd_text_param_info(cgd_text* t, int index, char* name_buf, int buf_len, int64_t* numel);
 int cgd_text_set_param(cgd_text* t, const char* name, const float* data, int64_t numel);
 int cgd_text_finalize(cgd_text* t);
+int cgd_text_set_activation(cgd_text* t, int act); /* as cgd_vit_set_activation */
 /* tokens: DEVICE int64 (N, context_length), ids in [0, vocab_size) (an id outside that range reads nothing and makes its row NaN);
  * emb: (N, out_dim) */
 int cgd_text_forward(cgd_text* t, const int64_t* tokens, int N, float* emb, void* stream);
@@ -356,6 +360,7 @@ int cgd_op_ln_bwd(cgd_ctx* ctx, const float* x, const float* dy, float* dx, int 
 /* pool2x2 / upsample2x: C a multiple of 4 and in / out 16-byte aligned, or the call fails before anything is launched */
 int cgd_op_pool2x2(cgd_ctx* ctx, const float* in, float* out, int B, int Ho, int Wo, int C, float scale, void* stream);
 int cgd_op_upsample2x(cgd_ctx* ctx, const float* in, float* out, int B, int Ho, int Wo, int C, float scale, void* stream);
+/* act: 1 SiLU, 2 QuickGELU, 3 exact (erf) GELU; any other code fails (-2).  dy null: out = act(x); else out = dy * act'(x) */
 int cgd_op_act(cgd_ctx* ctx, const float* x, const float* dy, float* out, int64_t n, int act, void* stream);
 /* upper bound over all kernel families (the GEMM path's T x T probabilities); the networks size their own scratch per family (flash: row statistics) */
 int64_t cgd_op_attn_buf_floats(int nb, int heads, int T, int d, int which);

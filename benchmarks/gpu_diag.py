@@ -1,4 +1,4 @@
-"""One-shot GPU parity report: runs every check of tests/parity_checks.py, keeps going after failures and writes
+"""One-shot GPU parity report: runs every check of tests/parity_checks.py and tests/lifecycle_checks.py (groups life_*), keeps going after failures and writes
 gpurun_out/diag_<tag>.json + a readable table on stdout.  Usage: python benchmarks/gpu_diag.py [tag] [group ...]"""
 import json
 import os
@@ -9,6 +9,7 @@ import traceback
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch as th  # noqa: E402
 
+from tests import lifecycle_checks as lc  # noqa: E402
 from tests import parity_checks as pc  # noqa: E402
 
 GROUPS = {
@@ -45,6 +46,7 @@ GROUPS = {
     "headline": [lambda: _sc().check_headline_step(1)],
     "cfg5": [lambda: _sc().check_step("cfg256", 1, steps=1, hw=(256, 288), respacing="500", P=3, cutn=4)],
 }
+GROUPS.update({"life_" + name: fns for name, fns in lc.GROUPS.items()})  # handles across call sequences (tests/lifecycle_checks.py)
 
 
 def _sc():

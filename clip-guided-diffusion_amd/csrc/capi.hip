@@ -102,6 +102,7 @@ int cgd_set_precision(cgd_ctx* ctx, int mode) {
   return 0;
 }
 int cgd_get_precision(cgd_ctx* ctx) { return ctx ? ctx->precision : -3; }
+int64_t cgd_ctx_device_allocs(cgd_ctx* ctx) { return ctx ? (int64_t)ctx->device_allocs : -3; }
 
 int cgd_set_tiles(cgd_ctx* ctx, int large, int small) {
   CGD_NEED_CTX(ctx);

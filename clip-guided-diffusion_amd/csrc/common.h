@@ -172,6 +172,8 @@ struct cgd_ctx {
   std::vector<float*> chanstats_retired;  // record buffers that were outgrown: kept until cgd_chanstats_clear (a kernel in flight may still read them;
                                           // no synchronisation and no hipFree inside a network pass)
   unsigned long long stats_serial = 1;    // current network pass (cgd_unet_forward and cgd_unet_dgrad increment it)
+  unsigned long long device_allocs = 0;     // device allocations on behalf of network passes: NetBase::alloc, the packed-weight cache, the conv-epilogue record
+                                            // buffers (cgd_ctx_device_allocs: tests assert that a warm handle allocates nothing)
   unsigned long long gn_record_merges = 0;  // GroupNorm launches that merged epilogue records instead of sweeping (cgd_op_gn_record_merges: tests)
   bool last_wconv_bstat = false;          // did the last cgd_launch_wconv take a GroupNorm's backward sums in its epilogue? (profiling: kind 5)
   int gn_epi = 3;      // bit 0: GroupNorm forward statistics of conv-produced tensors come from the conv epilogue; bit 1: the backward sums of a

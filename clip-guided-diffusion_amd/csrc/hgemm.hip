@@ -873,6 +873,7 @@ static const void* cgd_frag_cache_get(cgd_ctx* ctx, const float* w, int N, int K
   FragEntry e;
   e.w = w; e.N = N; e.K = K; e.ldw = ldw; e.packed = nullptr;
   if (hipMalloc(&e.packed, (size_t)N * K * sizeof(float)) != hipSuccess) return nullptr;
+  ++ctx->device_allocs;
   const long total = (long)N * K;
   CGD_LAUNCH(pack_frag_linear_kernel, dim3((int)std::min<long>(cdiv(total, 256), 4096)), dim3(256), 0, s, w, ldw, (__bf16*)e.packed, N, K);
   ctx->frag_cache.push_back(e);

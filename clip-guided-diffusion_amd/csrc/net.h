@@ -62,6 +62,7 @@ struct NetBase {
   int alloc(float** out, size_t n) {
     void* p = nullptr;
     CGD_HIP(ctx, hipMalloc(&p, (n ? n : 1) * sizeof(float)));
+    ++ctx->device_allocs;
     allocs.push_back(p);
     *out = (float*)p;
     return 0;

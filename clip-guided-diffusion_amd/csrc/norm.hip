@@ -1402,6 +1402,7 @@ float* cgd_chanstats_register(cgd_ctx* ctx, const float* C, int ldc, int N, long
       e->serial = 0;
       return nullptr;
     }
+    ++ctx->device_allocs;
     e->buf = (float*)p;
     e->cap = need;
   }

@@ -480,6 +480,7 @@ int ResNet::forward(const float* img, int Nn, float* emb, hipStream_t s) {
 }
 
 int ResNet::dgrad(const float* demb, float* dimg, hipStream_t s) {
+  if (!finalized) CGD_FAIL(ctx, "resnet: weights not finalized");
   if (!have_fwd) CGD_FAIL(ctx, "resnet: dgrad without a forward");
   const int wh = s1.coutP, w = s3.coutP, R2 = R / 2, R4 = R / 4;
   // attention pool backward

@@ -107,6 +107,7 @@ struct UNet : NetBase {
   // runtime
   int B = 0, H = 0, W = 0;
   bool have_fwd = false;
+  int fwd_prec = 0;             // precision mode the saved activations of the last forward were computed under
   DevBuf temb, e1, e1s, e2, e2s, emb_all, h0, headn, head_s, dheadn, dhead;
   DevBuf emb_slot1;             // second FiLM-projection buffer: embed() for step n + 1 may run (on another stream) while step n's forward reads slot n & 1
   const float* emb_cur = nullptr;  // the slot the running forward reads
@@ -555,6 +556,8 @@ int UNet::finalize(hipStream_t s) {
   }
   CGD_HIP(ctx, hipStreamSynchronize(s));
   finalized = true;
+  have_fwd = false;  // the saved activations belong to the previous weights
+  emb_B[0] = emb_B[1] = 0;  // ... and so do the FiLM projections of both slots
   return 0;
 }
 
@@ -623,6 +626,7 @@ int UNet::forward(const float* x, const float* t, const int64_t* y, float* out, 
   emb_cur = slot ? emb_slot1.p : emb_all.p;
   B = Bn; H = Hh; W = Ww;
   have_fwd = false;
+  fwd_prec = ctx->precision;
   ++ctx->stats_serial;  // conv-epilogue statistics of earlier passes are dead from here on (ChanStatsEntry)
   // ---- skip-concat buffers: output block k reads cat([h, hs[n-1-k]]) = cats[k] ([pixels][c1 + skip channels]).  The producers
   //      of the two halves (the previous output-side module / the input-side block or the stem) write straight into their
@@ -676,7 +680,10 @@ int UNet::forward(const float* x, const float* t, const int64_t* y, float* out, 
 }
 
 int UNet::dgrad(const float* gout, float* gx, hipStream_t s) {
+  if (!finalized) CGD_FAIL(ctx, "unet: finalize() has not been called after the last set_param");
   if (!have_fwd) CGD_FAIL(ctx, "unet: dgrad() needs a preceding forward()");
+  // the saved activations, the attention scratch and the Winograd copies belong to the mode the forward ran under: refused here, before any launch
+  if (fwd_prec != ctx->precision) CGD_FAIL(ctx, "unet: dgrad() under another precision mode than its forward()");
   ++ctx->stats_serial;  // backward-sum records of an earlier dgrad() (and the forward's statistics, which only the forward reads) are dead from here on
   // head
   CGD_TRY(ensure(dheadn, (size_t)B * H * W * ch0));

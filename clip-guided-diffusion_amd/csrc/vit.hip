@@ -84,6 +84,7 @@ struct ViT : NetBase {
   float *convw = 0, *convwT = 0, *cls = 0, *pos = 0, *lnpre_g = 0, *lnpre_b = 0, *lnpost_g = 0, *lnpost_b = 0, *proj = 0, *projT = 0;
   int N = 0, layout = 0;
   bool have_fwd = false;
+  int fwd_prec = 0;  // precision mode the saved activations of the last forward were computed under
   DevBuf cols, pe, tok, st_pre, x0, st_post, clsn, dclsn, dxl, dtok, dcols;
 
   int build();
@@ -129,12 +130,14 @@ int ViT::finalize(hipStream_t s) {
   }
   CGD_HIP(ctx, hipStreamSynchronize(s));
   finalized = true;
+  have_fwd = false;  // the saved activations belong to the previous weights
   return 0;
 }
 
 int ViT::forward(const float* img, int lay, int Nn, float* emb, hipStream_t s) {
   if (!finalized) CGD_FAIL(ctx, "vit: finalize() has not been called after the last set_param");
   N = Nn; layout = lay; have_fwd = false;
+  fwd_prec = ctx->precision;
   const long rows = (long)N * L;
   const float* colp = img;
   if (layout == 0) {
@@ -164,7 +167,10 @@ int ViT::forward(const float* img, int lay, int Nn, float* emb, hipStream_t s) {
 }
 
 int ViT::dgrad(const float* demb, float* dimg, hipStream_t s) {
+  if (!finalized) CGD_FAIL(ctx, "vit: finalize() has not been called after the last set_param");
   if (!have_fwd) CGD_FAIL(ctx, "vit: dgrad() needs a preceding forward()");
+  // the saved activations and the attention scratch belong to the mode the forward ran under: refused here, before any launch
+  if (fwd_prec != ctx->precision) CGD_FAIL(ctx, "vit: dgrad() under another precision mode than its forward()");
   const long rows = (long)N * L;
   const int H = cfg.heads, d = W / H;
   CGD_TRY(ensure(dclsn, (size_t)N * W));

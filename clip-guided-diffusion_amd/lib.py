@@ -66,6 +66,7 @@ _SIGS = {
     "cgd_last_error": (C.c_char_p, [vp]),
     "cgd_set_precision": (i32, [vp, i32]),
     "cgd_get_precision": (i32, [vp]),
+    "cgd_ctx_device_allocs": (i64, [vp]),
     "cgd_set_tiles": (i32, [vp, i32, i32]),
     "cgd_set_hgemm": (i32, [vp, i32, i32, i32]),
     "cgd_profile": (i32, [vp, i32]),

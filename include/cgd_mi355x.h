@@ -35,6 +35,9 @@ void cgd_ctx_destroy(cgd_ctx* ctx);
 const char* cgd_last_error(cgd_ctx* ctx);
 int cgd_set_precision(cgd_ctx* ctx, int mode);
 int cgd_get_precision(cgd_ctx* ctx);
+/* read-only: device allocations made since context creation on behalf of network passes (activation buffers and weight copies of every handle,
+ * the packed-weight cache, the conv-epilogue record buffers).  A handle that has seen its largest shape must leave it unchanged. */
+int64_t cgd_ctx_device_allocs(cgd_ctx* ctx);
 const char* cgd_version(void);
 /* tuning knob: GEMM tile codes for the automatic selection (64, 128, 256 = 256x128, 257 = 128x256; +1000 = 2-deep prefetch) */
 int cgd_set_tiles(cgd_ctx* ctx, int large_tile, int small_tile);

@@ -152,6 +152,7 @@ int main() {
     EXPECT(cgd_set_precision(nullptr, 1) == -3);
     EXPECT(cgd_op_new_pass(nullptr) == -3);  // round-5 test-support entry points
     EXPECT(cgd_op_gn_record_merges(nullptr) == -3);
+    EXPECT(cgd_ctx_device_allocs(nullptr) == -3);
     EXPECT(cgd_op_gn_stats_offset(2, 4096, 192) == 2 * 256 * 64);
     EXPECT(cgd_op_conv3x3_wino_ex(nullptr, nullptr, 32, nullptr, nullptr, 32, nullptr, nullptr, 0, nullptr, 1, 16, 16, 32, 32, 0, 1, nullptr, 0, nullptr, nullptr) == -3);
     EXPECT(cgd_profile(nullptr, 1) == -3);

@@ -675,19 +675,28 @@ UNET_CASES = {
 }
 
 
-def build_unet_pair(ctx, case, seed=1234, head_scale=1.0):
-    from cgd_amd import nets
+def oracle_unet(case, seed=1234, head_scale=1.0):
     from oracle.unet import UNetModel, synthetic_init_
-    kw = UNET_CASES[case]
-    ref = synthetic_init_(UNetModel(**kw), seed=seed).eval()
+    ref = synthetic_init_(UNetModel(**UNET_CASES[case]), seed=seed).eval()
     if head_scale != 1.0:  # small eps-hat / variance head (tests/step_checks.py explains the tame scenario)
         with th.no_grad():
             ref.out[2].weight.mul_(head_scale)
             ref.out[2].bias.mul_(head_scale)
     for p in ref.parameters():
         p.requires_grad_(False)
-    dev = nets.UNet(ctx, **kw)
-    dev.load_state_dict({k: v.to(DEV) for k, v in ref.state_dict().items()})
+    return ref
+
+
+def device_sd(ref):
+    """the oracle module's state dict as the device handles take it (fp32, on the GPU; BatchNorm's step counters dropped)"""
+    return {k: v.float().to(DEV) for k, v in ref.state_dict().items() if "num_batches_tracked" not in k}
+
+
+def build_unet_pair(ctx, case, seed=1234, head_scale=1.0):
+    from cgd_amd import nets
+    ref = oracle_unet(case, seed, head_scale)
+    dev = nets.UNet(ctx, **UNET_CASES[case])
+    dev.load_state_dict(device_sd(ref))
     return ref, dev
 
 
@@ -763,26 +772,58 @@ def check_unet_knob_toggle():
             rec("unet dgrad with the Winograd kernel switched off between forward and dgrad (unit peak)", g2 * sd, g1 * sd)]
 
 
-def build_vit_pair(ctx, name="ViT-B/32", seed=4321):
-    from cgd_amd import nets
+def oracle_vit(name="ViT-B/32", seed=4321):
     from oracle.clip_vit import ClipImageModel, synthetic_init_
     ref = synthetic_init_(ClipImageModel(name), seed=seed).eval().float()
     for p in ref.parameters():
         p.requires_grad_(False)
+    return ref
+
+
+def build_vit_pair(ctx, name="ViT-B/32", seed=4321):
+    from cgd_amd import nets
+    ref = oracle_vit(name, seed)
     dev = nets.ClipImageTower(ctx, name)
-    dev.load_clip_state_dict({k: v.to(DEV) for k, v in ref.state_dict().items()})
+    dev.load_clip_state_dict(device_sd(ref))
+    return ref, dev
+
+
+def oracle_lpips(seed=777):
+    from oracle import lpips_vgg as olp
+    return olp.synthetic_init_(olp.LpipsVGG(), seed=seed).double().eval()
+
+
+def lpips_sd(orc):
+    return {k: v.float().to(DEV) for k, v in orc.lpips_state_dict().items()}
+
+
+def build_lpips_pair(ctx, seed=777):
+    from cgd_amd import nets
+    orc = oracle_lpips(seed)
+    return orc, nets.LpipsVGG(ctx).load_state_dict(lpips_sd(orc))
+
+
+def oracle_resnet(name, config=None, seed=2468):
+    from oracle import clip_resnet as ocr
+    ref = ocr.synthetic_init_(ocr.ClipResNetImageModel(name, config), seed=seed).double().eval()
+    for prm in ref.parameters():
+        prm.requires_grad_(False)
+    return ref
+
+
+def build_resnet_pair(ctx, name, config=None, seed=2468):
+    from cgd_amd import nets
+    ref = oracle_resnet(name, config, seed)
+    dev = nets.ClipResNetTower(ctx, name, config)
+    dev.load_clip_state_dict(device_sd(ref))
     return ref, dev
 
 
 def check_lpips(precision):
     """LPIPS-VGG16 init loss: per-sample value and gradient w.r.t. x against the CPU oracle (autograd)."""
-    from cgd_amd import nets
-    from oracle import lpips_vgg as olp
     ctx = _ctx(precision)
     out = []
-    orc = olp.synthetic_init_(olp.LpipsVGG()).double().eval()
-    dev_net = nets.LpipsVGG(ctx)
-    dev_net.load_state_dict({k: v.float().to(DEV) for k, v in orc.lpips_state_dict().items()})
+    orc, dev_net = build_lpips_pair(ctx)
     for (B, H, W) in [(2, 64, 64), (1, 96, 128)]:
         ref = (th.rand(B, 3, H, W, generator=g(70)) * 2 - 1)
         x = (ref + 0.3 * th.randn(B, 3, H, W, generator=g(71))).clamp(-1.2, 1.2)
@@ -818,14 +859,8 @@ def check_vit(name, precision, N=3):
 
 def check_resnet(name, precision, N=2, config=None):
     """CLIP ModifiedResNet tower: embedding and d(sum(emb*de))/d(image) against the CPU oracle (float64 autograd)."""
-    from cgd_amd import nets
-    from oracle import clip_resnet as ocr
     ctx = _ctx(precision)
-    ref = ocr.synthetic_init_(ocr.ClipResNetImageModel(name, config)).double().eval()
-    for prm in ref.parameters():
-        prm.requires_grad_(False)
-    dev = nets.ClipResNetTower(ctx, name, config)
-    dev.load_clip_state_dict({k: v.float().to(DEV) for k, v in ref.state_dict().items() if "num_batches_tracked" not in k})
+    ref, dev = build_resnet_pair(ctx, name, config)
     res = ref.visual.input_resolution
     img = th.randn(N, 3, res, res, generator=g(75))
     de = th.randn(N, ref.visual.output_dim, generator=g(76))

@@ -272,13 +272,22 @@ class Scenario:
         return out
 
     # ---- device ----------------------------------------------------------------------------------------------------------------
-    def run_device(self, precision):
-        """Generator of (out dict, guidance object) per step; the caller synchronises and reads the buffers of the step."""
+    def run_device(self, precision, reuse=None):
+        """Generator of (out dict, guidance object) per step; the caller synchronises and reads the buffers of the step.
+        `reuse`: the `dev_objs` of an earlier scenario with the same networks and schedule (tests/lifecycle_checks.py) — its context,
+        network handles and sampler are run again instead of fresh ones; the guidance object is always this scenario's own."""
+        if reuse is not None:
+            ctx, dev_unet, dev_clip, dev_clip2, d_lp, smp = (reuse[k] for k in ("ctx", "unet", "clip", "clip2", "lpips", "smp"))
+            assert ctx.precision == precision and (d_lp is not None) == bool(self.init_scale) and (dev_clip2 is not None) == self.dual
+        else:
+            ctx, dev_unet, dev_clip, dev_clip2, d_lp, smp = self._make_device(precision)
+        self.dev_objs = dict(ctx=ctx, unet=dev_unet, clip=dev_clip, clip2=dev_clip2, lpips=d_lp, smp=smp)
+        yield from self._run_device(ctx, dev_unet, dev_clip, dev_clip2, d_lp, smp)
+
+    def _make_device(self, precision):
         from cgd_amd import diffusion as dd
-        from cgd_amd import guidance as dg
         from cgd_amd import lib, nets, sampler
         ctx = lib.Context(0, precision)
-        B, H, W = self.B, self.H, self.W
         dev_unet = nets.UNet(ctx, **self.kw)
         dev_unet.load_state_dict({k: v.to(DEV) for k, v in self.ref_unet.state_dict().items()})
         if self.rn_cfg is not None:
@@ -297,6 +306,11 @@ class Scenario:
             d_lp = nets.LpipsVGG(ctx).load_state_dict({k: v.float().to(DEV) for k, v in self.o_lp.lpips_state_dict().items()})
         d_tab = dd.create_gaussian_diffusion(1000, self.schedule, self.spec, self.rescale)
         smp = sampler.GuidedSampler(ctx, d_tab)
+        return ctx, dev_unet, dev_clip, dev_clip2, d_lp, smp
+
+    def _run_device(self, ctx, dev_unet, dev_clip, dev_clip2, d_lp, smp):
+        from cgd_amd import guidance as dg
+        B, H, W = self.B, self.H, self.W
         cgs, tvs, rs = self.scales
         d_towers = [dev_clip, dev_clip2] if self.dual else dev_clip
         d_targets = [self.targets.to(DEV), self.targets2.to(DEV)] if self.dual else self.targets.to(DEV)

@@ -86,6 +86,7 @@ def test_null_handles_are_rejected_not_dereferenced():
     handle = lib.load()
     assert handle.cgd_set_precision(None, 1) == -3
     assert handle.cgd_get_precision(None) == -3
+    assert handle.cgd_ctx_device_allocs(None) == -3
     assert handle.cgd_profile(None, 1) == -3
     assert handle.cgd_set_hconv(None, 1, 256) == -3
     assert handle.cgd_set_wino(None, 1, 0) == -3

@@ -85,12 +85,17 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
     if cached_cutouts:
         make_cutouts.cache_coordinates(image_size + width_offset, image_size + height_offset)
 
-    init_tensor = None
+    init_tensor, mask_tensor = None, None
     if init_image:
         import numpy as np
         from PIL import Image
+        # "IMAGE::MASK" (an extension like "plmsN"): masked sampling, the white part of MASK is regenerated and the black part kept
+        init_image, mask_image = script_util.split_init_mask(init_image)
         pil = Image.open(script_util.fetch(init_image)).convert("RGB").resize((image_size, image_size))
         init_tensor = th.from_numpy(np.array(pil)).float().div(255).permute(2, 0, 1).to(device).unsqueeze(0).mul(2).sub(1)
+        if mask_image is not None:
+            pil = Image.open(script_util.fetch(mask_image)).convert("L").resize((image_size, image_size))
+            mask_tensor = th.from_numpy(np.array(pil)).float().div(255).to(device)[None, None]
 
     # Multi-GPU (cgd_amd.launch: one process per GPU, torch.distributed initialised): the batch is sharded by samples, one (or
     # a contiguous block) per rank; every rank draws the GLOBAL random tensors from the same seed and keeps its rows, so the
@@ -132,7 +137,7 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
     try:
         samples = loop(gd_model, (local_batch, 3, image_size + height_offset, image_size + width_offset), clip_denoised=False,
                        model_kwargs=model_kwargs, cond_fn=cond_fn, progress=progress, skip_timesteps=skip_timesteps, init_image=init_tensor,
-                       randomize_class=randomize_class, cond_fn_with_grad=True)
+                       randomize_class=randomize_class, cond_fn_with_grad=True, **({} if mask_tensor is None else {"mask": mask_tensor}))
         cond_fn.current_timestep = diffusion.num_timesteps - 1
 
         # Output path (reference cgd.py:180-186,234-238,265-270), software-pipelined by one timestep: the GPU work of timestep
@@ -196,7 +201,7 @@ _CLI_SPEC = f"""
 --prompts -txts str "" | text prompts with optional weights, pipe-separated: 'a cat:0.5|a dog:-0.5'
 --image_prompts -imgs str "" | image prompts (paths or URLs) with optional weights, pipe-separated
 --image_size -size int 128 | resolution of the diffusion checkpoint: 64, 128, 256 or 512
---init_image -init str "" | start from this image (needs --skip_timesteps)
+--init_image -init str "" | start from this image (needs --skip_timesteps); IMAGE::MASK regenerates the white part of MASK and keeps the black part of IMAGE
 --init_scale -is int 0 | weight of the LPIPS-VGG16 term that keeps the sample close to the init image
 --skip_timesteps -skip int 0 | how many of the (respaced) timesteps to skip at the noisy end
 --prefix -dir path outputs | directory for the PNG frames

@@ -45,6 +45,18 @@ def parse_prompt(prompt):
     return text, weight
 
 
+def split_init_mask(value):
+    """'IMAGE::MASK' -> (IMAGE, MASK), split at the last '::'; a value without '::' -> (value, None).  The mask of masked sampling rides
+    on --init_image / init_image= (white regenerates, black keeps).  The '://' of a URL is no separator."""
+    value = str(value)
+    image, sep, mask = value.rpartition("::")
+    if not sep:
+        return value, None
+    if not image or not mask:
+        raise ValueError(f"init image {value!r}: 'IMAGE::MASK' needs both an image and a mask")
+    return image, mask
+
+
 def fetch(url_or_path):
     if str(url_or_path).startswith(("http://", "https://")):
         import requests

@@ -270,6 +270,14 @@ int cgd_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eval, cons
   return cgd_launch_multistep_update(ctx, x, x_eval, x0, g, scalars, noise, eps_hist, eps_out, sample, x0_out, B, H, W, *k, k_step, *m,
                                      S(stream));
 }
+int cgd_masked_merge(cgd_ctx* ctx, float* sample, float* x0, const float* init, const float* mask, const float* n_known, const float* n_re,
+                     float* x_re, int B, int H, int W, int init_batch, int mask_batch, int mask_channels, const cgd_mask_coef* k,
+                     void* stream) {
+  CGD_NEED_CTX(ctx);
+  if (!k) return -3;
+  return cgd_launch_masked_merge(ctx, sample, x0, init, mask, n_known, n_re, x_re, B, H, W, init_batch, mask_batch, mask_channels, *k,
+                                 S(stream));
+}
 
 // ---- single ops -------------------------------------------------------------------------------------------------
 int cgd_op_gemm(cgd_ctx* ctx, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias, const float* R,

@@ -122,6 +122,12 @@ int cgd_launch_cutouts_aug_bwd(cgd_ctx* ctx, const float* dout, const int* coord
 size_t cgd_cutouts_aug_scratch(int B, int H, int W, int cutn);
 // host: per output pixel of an h x w crop, the affine nearest source index (-1: fill) and the perspective's 4 taps / weights
 int cgd_aug_sample_map(const float* params, int h, int w, int32_t* affine_src, int32_t* persp_idx, float* persp_w);
+// mask.hip: the merge of masked sampling after a sampler update (include/cgd_mi355x.h: cgd_masked_merge); sample and x0 (or null) are merged
+// in place, x_re (with n_re, or both null) receives the merged sample taken back up one level
+struct cgd_mask_coef;
+int cgd_launch_masked_merge(cgd_ctx* ctx, float* sample, float* x0, const float* init, const float* mask, const float* n_known,
+                            const float* n_re, float* x_re, int B, int H, int W, int init_batch, int mask_batch, int mask_channels,
+                            const cgd_mask_coef& k, hipStream_t s);
 // spherical-distance loss and its gradient w.r.t. the cutout embeddings
 //   emb [cutn*B][D] (row = cut*B + b), targets [P][D], weights [B][P] (dense per-sample prompt weights, see
 //   host-side broadcast rules), loss_part: per-(cut,b) partial losses [cutn*B] (already * scale / cutn)

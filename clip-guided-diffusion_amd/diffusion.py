@@ -107,6 +107,19 @@ class SpacedDiffusion:
         k.nonzero = int(i != 0)
         return k
 
+    def mask_coef(self, i):
+        """Coefficients of the masked-sampling merge after the update of step index i (sampler.py, csrc/mask.hip): the known region
+        lives at level i - 1, known = sqrt(abar_prev) init + sqrt(1 - abar_prev) noise (the init image itself at i = 0), and a
+        resampling repeat goes back up with x_i = sqrt(abar / abar_prev) x_{i-1} + sqrt(1 - abar / abar_prev) noise."""
+        k = L.MaskCoef()
+        ab, abp = self.alphas_cumprod[i], self.alphas_cumprod_prev[i]
+        k.sqrt_ab_prev = math.sqrt(abp)
+        k.sqrt_one_minus_ab_prev = math.sqrt(1.0 - abp)
+        k.renoise_x = math.sqrt(ab / abp)
+        k.renoise_n = math.sqrt(1.0 - ab / abp)
+        k.flags = 0
+        return k
+
 
 def create_gaussian_diffusion(steps=1000, noise_schedule="linear", timestep_respacing="", rescale_timesteps=False):
     betas = named_beta_schedule(noise_schedule, steps)

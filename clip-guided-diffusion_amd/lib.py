@@ -51,6 +51,13 @@ class Multistep(C.Structure):
     _fields_ = [("phase", i32), ("order", i32), ("sigma", f32), ("dir", f32)]
 
 
+class MaskCoef(C.Structure):
+    """cgd_mask_coef: coefficients of cgd_masked_merge at one step index; flags = the optional buffers passed (MASK_*)"""
+    _fields_ = [("sqrt_ab_prev", f32), ("sqrt_one_minus_ab_prev", f32), ("renoise_x", f32), ("renoise_n", f32), ("flags", i32)]
+
+
+MASK_PRED_XSTART, MASK_N_KNOWN, MASK_RENOISE = 1, 2, 4
+
 MANIFEST_CB = C.CFUNCTYPE(None, C.c_char_p, i64, vp)
 
 # name -> (restype, argtypes).  Pointers to device memory are passed as integers (tensor.data_ptr()).
@@ -135,6 +142,7 @@ _SIGS = {
     "cgd_sample_update": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), i32, vp]),
     "cgd_multistep_update": (i32, [vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef),
                                     C.POINTER(StepCoef), C.POINTER(Multistep), vp]),
+    "cgd_masked_merge": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(MaskCoef), vp]),
     "cgd_op_gemm": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
     "cgd_op_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
     "cgd_op_pack_conv3x3_frag": (i32, [vp, vp, vp, i32, i32, i32, vp]),

@@ -8,6 +8,9 @@ With a `ClipGuidance` cond_fn everything stays native; any other Python callable
 through autograd Functions whose forward/backward call the same C ABI (`UNetFunction`).
 PLMS (`plms_sample_loop_progressive`, from the fork's history) and DDIM with eta > 0 reuse the same guided evaluation and finish
 it with one cgd_multistep_update launch per evaluation; PLMS draws no per-step noise.
+Masked sampling (`mask=`, with an init image: 1 regenerates, 0 keeps) adds one cgd_masked_merge launch after every update, which puts the
+init image, noised to the level the update produced, back into the kept region; `resamples=r` repeats every step r times (RePaint with
+jump length 1).  Without a mask nothing of it runs.
 """
 import ctypes as C
 import math
@@ -111,9 +114,10 @@ class GuidedSampler:
         return th.randn((gb,) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype)[idx].contiguous()
 
     # ---- one step -------------------------------------------------------------------------------------
-    def _evaluate(self, model, x, i, cond_fn, model_kwargs, noise, bufs, ahead=None, draw_noise=True):
+    def _evaluate(self, model, x, i, cond_fn, model_kwargs, noise, bufs, ahead=None, draw_noise=True, draw_known=False):
         """One guided evaluation at (x, i): UNet forward -> p_mean_variance tail + blend -> (noise draw) -> cond_fn.  Returns the pieces
-        the update kernels read; nothing of the update itself."""
+        the update kernels read; nothing of the update itself.  `draw_known`: masked sampling in a stochastic loop, the noise of the
+        kept region is drawn right after the step's own."""
         ctx, lib = self.ctx, self.ctx.lib
         B, _, H, W = x.shape
         dev = x.device
@@ -147,6 +151,7 @@ class GuidedSampler:
                                         xin.data_ptr(), B, H, W, coef, s))
             if noise is None and draw_noise:
                 noise = self._draw_like(x)  # drawn before cond_fn, as in p_sample_with_grad
+            n_known = self._draw_like(x) if draw_known else None
             g = cond_fn.native(x, x0, xin, coef) if native else None
             scal = cond_fn.scalars if (native and g is not None and cond_fn.use_magnitude) else None
         else:
@@ -161,20 +166,80 @@ class GuidedSampler:
                 mu = coef.coef1 * p0 + coef.coef2 * xr
                 if noise is None and draw_noise:
                     noise = self._draw_like(x)
+                n_known = self._draw_like(x) if draw_known else None
                 t_idx = th.full((B,), i, device=dev, dtype=th.long)
                 p = {"mean": mu, "variance": th.exp(lv), "log_variance": lv, "pred_xstart": p0}
                 g = cond_fn(xr, t_idx, p, **(model_kwargs or {}))
             g = g.detach().float().contiguous()
             x0.copy_(p0.detach()); mean.copy_(mu.detach()); logvar.copy_(lv.detach())
         return {"x0": x0, "mean": mean, "logvar": logvar, "g": g, "scal": scal, "noise": noise, "coef": coef, "ts": ts,
-                "fac_index": fac_index}
+                "fac_index": fac_index, "n_known": n_known}
 
-    def _step(self, model, x, i, cond_fn, model_kwargs, noise, mode, bufs, ahead=None, eta=0.0):
+    # ---- masked sampling ------------------------------------------------------------------------------
+    def _known_noise(self, masked, x):
+        """Noise of the kept region for the next merge: the loop's initial noise in the deterministic loops (the tensor that q_sampled
+        the init image at the first index: the kept region follows one trajectory and nothing is drawn); in the stochastic loops the
+        tape's next entry, or None = a fresh draw that _evaluate takes right after the step's own noise."""
+        if not masked["stochastic"]:
+            return masked["x_T"]
+        if self.tape is None:
+            return None
+        masked["known"] += 1
+        return self.tape["known_noise"][masked["known"] - 1].to(x.device).float().contiguous()
+
+    def _renoise(self, masked, x):
+        """The draw that takes a merged state back up one level (resamples > 1): the tape's next entry or a fresh one."""
+        if self.tape is None:
+            return self._draw_like(x)
+        masked["re"] += 1
+        return self.tape["renoise"][masked["re"] - 1].to(x.device).float().contiguous()
+
+    def _merge(self, masked, i, sample, x0_out, n_known, n_re=None):
+        """cgd_masked_merge after the update of step index i: `sample` (the state at level i - 1) and `x0_out` (or None) are merged in
+        place.  With `n_re` the same launch writes the merged sample taken back up to level i, which is returned."""
+        ctx = self.ctx
+        B, _, H, W = sample.shape
+        k = self.tables.mask_coef(i)
+        if k.sqrt_one_minus_ab_prev == 0.0:
+            n_known = None  # i == 0: the known region is the init image itself
+        x_re = th.empty_like(sample) if n_re is not None else None
+        k.flags = (L.MASK_PRED_XSTART if x0_out is not None else 0) | (L.MASK_N_KNOWN if n_known is not None else 0) | \
+            (L.MASK_RENOISE if n_re is not None else 0)
+        init, mask = masked["init"], masked["mask"]
+        ctx.check(ctx.lib.cgd_masked_merge(ctx.h, sample.data_ptr(), L.ptr(x0_out), init.data_ptr(), mask.data_ptr(), L.ptr(n_known),
+                                           L.ptr(n_re), L.ptr(x_re), B, H, W, init.shape[0], mask.shape[0], mask.shape[1], k, ctx.stream()))
+        masked["_keep"] = (n_known, n_re)
+        return x_re
+
+    @staticmethod
+    def _check_mask(shape, init_image, mask, resamples, plms=False):
+        if isinstance(resamples, bool) or not isinstance(resamples, int) or resamples < 1:
+            raise ValueError(f"resamples must be an int >= 1, got {resamples!r}")
+        if resamples > 1 and plms:
+            raise ValueError("PLMS cannot resample: its eps history would mix noise levels (use the p_sample or DDIM loop)")
+        if mask is None:
+            if resamples > 1:
+                raise ValueError("resamples > 1 needs a mask: the repeats re-run the merge of masked sampling")
+            return
+        if init_image is None:
+            raise ValueError("a mask needs an init image: the kept region is taken from it")
+        B, H, W = shape[0], shape[2], shape[3]
+        if init_image.dim() != 4 or init_image.shape[0] not in (1, B) or tuple(init_image.shape[1:]) != (3, H, W):
+            raise ValueError(f"init_image must be (1 or {B}, 3, {H}, {W}) under a mask, got {tuple(init_image.shape)}")
+        if mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, 3) or tuple(mask.shape[2:]) != (H, W):
+            raise ValueError(f"mask must be (1 or {B}, 1 or 3, {H}, {W}), got {tuple(mask.shape)}")
+        lo, hi = float(mask.min()), float(mask.max())
+        if not (lo >= 0.0 and hi <= 1.0):
+            raise ValueError(f"mask values must lie in [0, 1] (1 regenerates, 0 keeps), got [{lo}, {hi}]")
+
+    def _step(self, model, x, i, cond_fn, model_kwargs, noise, mode, bufs, ahead=None, eta=0.0, masked=None, again=False):
         """One step of the p_sample (mode 0) or DDIM (mode 1) loop.  DDIM with eta > 0 runs its update through
-        cgd_multistep_update (phase 3); eta == 0 keeps cgd_sample_update mode 1."""
+        cgd_multistep_update (phase 3); eta == 0 keeps cgd_sample_update mode 1.  `masked`: the state of masked sampling, the update is
+        followed by the merge; `again`: this step index runs once more, the merge also leaves the re-noised state in bufs['_x_re']."""
         ctx, lib = self.ctx, self.ctx.lib
         B, _, H, W = x.shape
-        ev = self._evaluate(model, x, i, cond_fn, model_kwargs, noise, bufs, ahead)
+        n_known = self._known_noise(masked, x) if masked is not None else None
+        ev = self._evaluate(model, x, i, cond_fn, model_kwargs, noise, bufs, ahead, draw_known=masked is not None and n_known is None)
         noise, g, coef = ev["noise"], ev["g"], ev["coef"]
         sample, x0_out = th.empty_like(x), th.empty_like(x)
         if eta:
@@ -189,11 +254,16 @@ class GuidedSampler:
                                             L.ptr(g), noise.data_ptr(), L.ptr(ev["scal"]), sample.data_ptr(), x0_out.data_ptr(), B, H,
                                             W, coef, mode, ctx.stream()))
         bufs["_keep"] = (noise, g, ev["ts"])
+        if masked is not None:
+            bufs["_x_re"] = self._merge(masked, i, sample, x0_out, n_known if n_known is not None else ev["n_known"],
+                                        self._renoise(masked, x) if again else None)
         return {"sample": sample, "pred_xstart": x0_out}
 
-    def _plms_step(self, model, x, i, cond_fn, model_kwargs, bufs, st):
+    def _plms_step(self, model, x, i, cond_fn, model_kwargs, bufs, st, masked=None):
         """One PLMS step (plms_sample of the guided_diffusion fork).  `st`: {'order', 'old_eps': history buffers (oldest first),
-        'free': spare buffers}.  The history rotates by pointer: the buffer dropped from the front is the next step's eps_out."""
+        'free': spare buffers}.  The history rotates by pointer: the buffer dropped from the front is the next step's eps_out.
+        `masked`: the start step's predictor (level i - 1, the input of the second evaluation) is merged before that evaluation, and
+        every step's result afterwards; the eps history stays as evaluated."""
         ctx, lib = self.ctx, self.ctx.lib
         B, _, H, W = x.shape
         s = ctx.stream()
@@ -211,6 +281,8 @@ class GuidedSampler:
                                                eps_new.data_ptr(), xp.data_ptr(), x0_out.data_ptr(), B, H, W, ev["coef"], None,
                                                L.Multistep(1, 0, 0.0, 0.0), s))
             old.append(eps_new)
+            if masked is not None:
+                self._merge(masked, i, xp, None, masked["x_T"])
             ev2 = self._evaluate(model, xp, i - 1, cond_fn, model_kwargs, None, bufs, draw_noise=False)
             hist = (C.c_void_p * 3)(eps_new.data_ptr(), None, None)
             k_t = self.tables.step_coef(i, ev["fac_index"])
@@ -230,6 +302,8 @@ class GuidedSampler:
         if len(old) >= order:
             st["free"].append(old.pop(0))
         bufs["_keep"] = keep
+        if masked is not None:
+            self._merge(masked, i, sample, x0_out, masked["x_T"])
         return {"sample": sample, "pred_xstart": x0_out}
 
     # ---- loops ------------------------------------------------------------------------------------------
@@ -241,8 +315,9 @@ class GuidedSampler:
             raise NotImplementedError("the reference passes cond_fn_with_grad=True (cgd.py:260)")
 
     def _loop(self, mode, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-              randomize_class, cond_fn_with_grad, eta=0.0, plms_order=None):
-        """mode 0 p_sample, 1 DDIM (eta > 0: stochastic DDIM), 2 PLMS of order `plms_order` (no per-step noise)."""
+              randomize_class, cond_fn_with_grad, eta=0.0, plms_order=None, mask=None, resamples=1):
+        """mode 0 p_sample, 1 DDIM (eta > 0: stochastic DDIM), 2 PLMS of order `plms_order` (no per-step noise).  `mask` (with
+        `init_image`): masked sampling, every step index > 0 `resamples` times."""
         self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
         device = th.device(device or f"cuda:{self.ctx.device}")
         tape = self.tape
@@ -258,6 +333,11 @@ class GuidedSampler:
             img = th.randn(*shape, device=device)
         if skip_timesteps and init_image is None:
             init_image = th.zeros_like(img)
+        masked = None
+        if mask is not None:
+            # 'stochastic': the kept region gets a fresh noise per merge; otherwise it keeps the loop's initial noise, img as it is here
+            masked = {"init": init_image.to(device).float().contiguous(), "mask": mask.to(device).float().contiguous(),
+                      "x_T": img.contiguous(), "stochastic": mode == 0 or (mode == 1 and bool(eta)), "known": 0, "re": 0}
         indices = list(range(self.num_timesteps - skip_timesteps))[::-1]
         if init_image is not None:
             t0 = indices[0]
@@ -281,8 +361,10 @@ class GuidedSampler:
 
         draw_y.n = 0
         rand_y = bool(randomize_class and "y" in model_kwargs)
-        # PLMS: its start step evaluates the model twice, EmbedAhead's one-embedding-per-step choreography does not apply (off)
-        ahead = EmbedAhead.create(self, model, cond_fn, img, indices) if mode != 2 else None
+        # PLMS: its start step evaluates the model twice, EmbedAhead's one-embedding-per-step choreography does not apply (off);
+        # neither does it to the repeated evaluations of resamples > 1
+        ahead = EmbedAhead.create(self, model, cond_fn, img, indices) if (mode != 2 and resamples == 1) else None
+        evals = 0  # evaluations of the p_sample / DDIM loops so far: the tape's step noise is consumed per evaluation
         plms = {"order": plms_order, "old_eps": [], "free": []} if mode == 2 else None
         for n, i in enumerate(it):
             if rand_y and (ahead is None or n == 0):
@@ -292,14 +374,22 @@ class GuidedSampler:
                 ahead.launch(model, 0, model_kwargs.get("y"))
             if plms is not None:
                 with th.no_grad():
-                    out = self._plms_step(model, img, i, cond_fn, model_kwargs, bufs, plms)
+                    out = self._plms_step(model, img, i, cond_fn, model_kwargs, bufs, plms, *((masked,) if masked is not None else ()))
                 yield out
                 img = out["sample"]
                 continue
-            step_noise = tape["noise"][n].to(device).float().contiguous() if tape is not None else None
-            with th.no_grad():
-                out = self._step(model, img, i, cond_fn, model_kwargs, step_noise, mode, bufs, *((ahead,) if ahead is not None else ()),
-                                 **({"eta": eta} if eta else {}))
+            # masked sampling with resamples = r: step index i > 0 runs r times; after each of the first r - 1 merges the state goes back
+            # up one level (bufs['_x_re'], written by the merge's launch) and the step runs again.  One yield per step index.
+            repeats = resamples if (masked is not None and i > 0) else 1
+            for r in range(repeats):
+                step_noise = tape["noise"][evals].to(device).float().contiguous() if tape is not None else None
+                evals += 1
+                with th.no_grad():
+                    out = self._step(model, img, i, cond_fn, model_kwargs, step_noise, mode, bufs, *((ahead,) if ahead is not None else ()),
+                                     **({"eta": eta} if eta else {}),
+                                     **({"masked": masked, "again": r + 1 < repeats} if masked is not None else {}))
+                if r + 1 < repeats:
+                    img = bufs.pop("_x_re")
             if ahead is not None and tape is not None and rand_y and n + 1 >= len(tape["y"]):
                 ahead = None  # a replay tape shorter than the schedule (tests that run a few steps): the remaining steps run in line
             if ahead is not None and n + 1 < len(indices):
@@ -315,32 +405,39 @@ class GuidedSampler:
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                   model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
-                                  randomize_class=False, cond_fn_with_grad=False):
+                                  randomize_class=False, cond_fn_with_grad=False, mask=None, resamples=1):
+        """`mask` ((1 or B, 1 or 3, H, W) in [0, 1], with `init_image`): masked sampling, 1 regenerates and 0 keeps the init image;
+        `resamples`: how often every step index > 0 runs (RePaint with jump length 1)."""
+        self._check_mask(shape, init_image, mask, resamples)
         return self._loop(0, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad)
+                          randomize_class, cond_fn_with_grad, mask=mask, resamples=resamples)
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None,
-                                     randomize_class=False, cond_fn_with_grad=False):
+                                     randomize_class=False, cond_fn_with_grad=False, mask=None, resamples=1):
         """eta == 0 (what the reference passes): cgd_sample_update mode 1.  eta > 0: ddim_sample_with_grad's sigma term with the
-        per-step noise draw of this loop, through cgd_multistep_update."""
+        per-step noise draw of this loop, through cgd_multistep_update.  `mask`, `resamples`: as in p_sample_loop_progressive; with
+        eta == 0 the kept region is noised with the loop's initial noise throughout and a masked run stays deterministic."""
         eta = float(eta)
         if not eta >= 0.0:
             raise ValueError(f"eta must be >= 0, got {eta}")
+        self._check_mask(shape, init_image, mask, resamples)
         return self._loop(1, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad, eta=eta)
+                          randomize_class, cond_fn_with_grad, eta=eta, mask=mask, resamples=resamples)
 
     def plms_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
-                                     randomize_class=False, cond_fn_with_grad=False, order=2):
+                                     randomize_class=False, cond_fn_with_grad=False, order=2, mask=None, resamples=1):
         """PLMS (pseudo linear multistep, Liu et al., ICLR 2022) as the guided_diffusion fork's `plms_sample_loop_progressive`:
         a first step of pseudo improved Euler (two guided evaluations, at t and at t-1) when order > 1, Adams-Bashforth of up to
         `order` eps terms afterwards.  No per-step noise.  A schedule of a single step with order > 1 would evaluate at t = -1 and is
-        refused (the fork indexes its tables with -1 there)."""
+        refused (the fork indexes its tables with -1 there).  `mask`: masked sampling as in p_sample_loop_progressive, the kept region
+        noised with the loop's initial noise; `resamples` > 1 is refused (the eps history would mix noise levels)."""
         if isinstance(order, bool) or not isinstance(order, int) or not 1 <= order <= 4:
             raise ValueError(f"order is invalid (should be int from 1-4): {order!r}")
         self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
         if order > 1 and self.num_timesteps - skip_timesteps < 2:
             raise ValueError(f"PLMS of order {order} needs at least two timesteps: its first step also evaluates at t - 1")
+        self._check_mask(shape, init_image, mask, resamples, plms=True)
         return self._loop(2, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad, plms_order=order)
+                          randomize_class, cond_fn_with_grad, plms_order=order, mask=mask)

@@ -281,6 +281,32 @@ int cgd_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eval, cons
                          float* pred_xstart_out, int B, int H, int W, const cgd_step_coef* k, const cgd_step_coef* k_step,
                          const cgd_multistep* m, void* stream);
 
+/* ---- masked sampling (inpainting / outpainting of an init image): the merge after a sampler update at step index t, in one launch.
+ *      The update left `sample` (the state at level t-1) and `pred_xstart`; with m = mask (1 regenerate, 0 keep the init image):
+ *        known       = sqrt(abar_prev) init + sqrt(1 - abar_prev) n_known   (two rounded products and a rounded sum, not fused)
+ *        sample      = m == 0 ? known : m == 1 ? sample      : m sample      + (1 - m) known
+ *        pred_xstart = m == 0 ? init  : m == 1 ? pred_xstart : m pred_xstart + (1 - m) init
+ *      both in place.  The endpoints are selects: where m == 0 nothing of sample / pred_xstart reaches the output, non-finite values
+ *      included; where m == 1 the two keep their bits.  With n_re and x_re the launch also writes the merged sample taken back up one
+ *      level (RePaint's resampling with jump length 1): x_re = renoise_x sample + renoise_n n_re.
+ *      sample, pred_xstart, n_known, n_re, x_re: (B,3,H,W); init: (init_batch,3,H,W), init_batch 1 or B; mask: (mask_batch,
+ *      mask_channels,H,W), mask_batch 1 or B, mask_channels 1 or 3.  pred_xstart may be NULL; n_known only when
+ *      sqrt_one_minus_ab_prev == 0 (t == 0); n_re and x_re are both given or both NULL.  `flags` names the optional buffers that are
+ *      passed and must agree with the pointers.  Any 4-byte-aligned pointers and any H * W are accepted (16-byte accesses when every
+ *      pointer is 16-byte aligned and 4 | H * W).  Returns -2 (cgd_last_error) for a missing buffer, flags that disagree with the
+ *      pointers, a broadcast extent other than the ones above, or a non-positive size. ---- */
+enum { CGD_MASK_PRED_XSTART = 1, CGD_MASK_N_KNOWN = 2, CGD_MASK_RENOISE = 4 };
+typedef struct cgd_mask_coef {
+  float sqrt_ab_prev;           /* sqrt(abar_{t-1}): the init image's share of the known region                 */
+  float sqrt_one_minus_ab_prev; /* sqrt(1 - abar_{t-1}): the share of n_known (0 at t == 0)                     */
+  float renoise_x;              /* sqrt(abar_t / abar_{t-1}): x_{t-1}'s share of the re-noised x_t               */
+  float renoise_n;              /* sqrt(1 - abar_t / abar_{t-1}): the share of n_re                              */
+  int flags;                    /* CGD_MASK_PRED_XSTART | CGD_MASK_N_KNOWN | CGD_MASK_RENOISE: buffers passed   */
+} cgd_mask_coef;
+int cgd_masked_merge(cgd_ctx* ctx, float* sample, float* pred_xstart, const float* init, const float* mask, const float* n_known,
+                     const float* n_re, float* x_re, int B, int H, int W, int init_batch, int mask_batch, int mask_channels,
+                     const cgd_mask_coef* k, void* stream);
+
 /* ---- single ops, exported for parity tests and for user-supplied cond_fn plumbing ---- */
 /* C[M][N] = alpha * A[M][K] B[N][K]^T (+bias[N]) (+R[M][N]); conv3x3: A is NHWC (Bn,H,W,Cin), B = [N][9*Cin].
  * force_tile: 0 auto, 64 / 128 / 256 / 257 (+1000: two-deep prefetch) igemm tiles, 513 weight GEMM kernel (B re-packed per call),

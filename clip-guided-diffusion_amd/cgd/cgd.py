@@ -34,6 +34,14 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         print(f"device: {device}")
     if "cuda" not in device:
         raise ValueError(f"device {device!r}: this build runs the sampling step on an MI355X only (PyTorch-ROCm reports 'cuda')")
+    if init_image and script_util.split_init_invert(script_util.split_init_mask(init_image)[0])[1]:
+        # refused before anything is loaded
+        if not str(timestep_respacing).startswith(("ddim", "plms")):  # the inverted latent is a start state of the deterministic loops only
+            raise ValueError(f"init image 'invert=...' needs a deterministic sampler: timestep_respacing must start with 'ddim' or 'plms', "
+                             f"got {timestep_respacing!r}")
+        if height_offset or width_offset:  # the init image is image_size x image_size, and so is the latent inverted from it
+            raise ValueError(f"init image 'invert=...' needs height_offset = width_offset = 0, got {height_offset} and {width_offset}: the "
+                             "inverted latent has the init image's size")
 
     wandb_run = None
     if wandb_project is not None:
@@ -85,12 +93,14 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
     if cached_cutouts:
         make_cutouts.cache_coordinates(image_size + width_offset, image_size + height_offset)
 
-    init_tensor, mask_tensor = None, None
+    init_tensor, mask_tensor, invert = None, None, False
     if init_image:
         import numpy as np
         from PIL import Image
         # "IMAGE::MASK" (an extension like "plmsN"): masked sampling, the white part of MASK is regenerated and the black part kept
         init_image, mask_image = script_util.split_init_mask(init_image)
+        # "invert=IMAGE": start from the image's own DDIM-inverted latent instead of the image plus random noise
+        init_image, invert = script_util.split_init_invert(init_image)
         pil = Image.open(script_util.fetch(init_image)).convert("RGB").resize((image_size, image_size))
         init_tensor = th.from_numpy(np.array(pil)).float().div(255).permute(2, 0, 1).to(device).unsqueeze(0).mul(2).sub(1)
         if mask_image is not None:
@@ -119,6 +129,14 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         if progress:
             tqdm.write(f"--reduce-clip: the first {skip_timesteps} timesteps are skipped")
 
+    invert_kw = {}
+    if invert:
+        # once, at batch 1, unguided, with class 0 where the model is class-conditional; every sample of the batch starts from that latent.
+        # A run reproduces the image only with the class held fixed (--uncond, or randomize_class=False)
+        _, inv_noise = diffusion.ddim_invert(gd_model, init_tensor, clip_denoised=False, progress=progress, skip_timesteps=skip_timesteps,
+                                             model_kwargs={"y": th.zeros([1], device=device, dtype=th.long)} if class_cond else {})
+        invert_kw["noise"] = inv_noise.expand(local_batch, -1, -1, -1).contiguous()
+
     cond_fn = ClipGuidance(
         gd_model.ctx, gd_model, [cm.tower for cm in clip_models], diffusion, target_embeds, weight_t, num_cutouts, cutout_power=cutout_power,
         clip_guidance_scale=clip_guidance_scale, tv_scale=tv_scale, range_scale=range_scale, sat_scale=sat_scale, use_magnitude=use_magnitude,
@@ -137,7 +155,8 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
     try:
         samples = loop(gd_model, (local_batch, 3, image_size + height_offset, image_size + width_offset), clip_denoised=False,
                        model_kwargs=model_kwargs, cond_fn=cond_fn, progress=progress, skip_timesteps=skip_timesteps, init_image=init_tensor,
-                       randomize_class=randomize_class, cond_fn_with_grad=True, **({} if mask_tensor is None else {"mask": mask_tensor}))
+                       randomize_class=randomize_class, cond_fn_with_grad=True, **({} if mask_tensor is None else {"mask": mask_tensor}),
+                       **invert_kw)
         cond_fn.current_timestep = diffusion.num_timesteps - 1
 
         # Output path (reference cgd.py:180-186,234-238,265-270), software-pipelined by one timestep: the GPU work of timestep
@@ -201,7 +220,7 @@ _CLI_SPEC = f"""
 --prompts -txts str "" | text prompts with optional weights, pipe-separated: 'a cat:0.5|a dog:-0.5'
 --image_prompts -imgs str "" | image prompts (paths or URLs) with optional weights, pipe-separated
 --image_size -size int 128 | resolution of the diffusion checkpoint: 64, 128, 256 or 512
---init_image -init str "" | start from this image (needs --skip_timesteps); IMAGE::MASK regenerates the white part of MASK and keeps the black part of IMAGE
+--init_image -init str "" | start from this image (needs --skip_timesteps); IMAGE::MASK regenerates the white part of MASK and keeps the black part of IMAGE; invert=IMAGE (or invert=IMAGE::MASK, with -respace ddimN / plmsN) starts from the DDIM-inverted latent of IMAGE
 --init_scale -is int 0 | weight of the LPIPS-VGG16 term that keeps the sample close to the init image
 --skip_timesteps -skip int 0 | how many of the (respaced) timesteps to skip at the noisy end
 --prefix -dir path outputs | directory for the PNG frames

@@ -57,6 +57,21 @@ def split_init_mask(value):
     return image, mask
 
 
+INVERT_PREFIX = "invert="
+
+
+def split_init_invert(image_part):
+    """'invert=IMAGE' -> (IMAGE, True); anything else -> (value, False).  Takes the image part split_init_mask returns: the request to
+    start from the image's own DDIM-inverted latent rides on --init_image / init_image=, like the mask ('invert=IMAGE::MASK')."""
+    image_part = str(image_part)
+    if not image_part.startswith(INVERT_PREFIX):
+        return image_part, False
+    image = image_part[len(INVERT_PREFIX):]
+    if not image:
+        raise ValueError(f"init image {image_part!r}: 'invert=IMAGE' needs an image")
+    return image, True
+
+
 def fetch(url_or_path):
     if str(url_or_path).startswith(("http://", "https://")):
         import requests

@@ -279,6 +279,13 @@ int cgd_masked_merge(cgd_ctx* ctx, float* sample, float* x0, const float* init, 
                                  S(stream));
 }
 
+int cgd_ddim_reverse_update(cgd_ctx* ctx, const float* x, const float* out6, const float* init, float* x_next, float* x0, float* noise_out,
+                            int B, int H, int W, int init_batch, const cgd_reverse_coef* k, void* stream) {
+  CGD_NEED_CTX(ctx);
+  if (!k) return -3;
+  return cgd_launch_ddim_reverse_update(ctx, x, out6, init, x_next, x0, noise_out, B, H, W, init_batch, *k, S(stream));
+}
+
 // ---- single ops -------------------------------------------------------------------------------------------------
 int cgd_op_gemm(cgd_ctx* ctx, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias, const float* R,
                 int ldr, int M, int N, int K, float alpha, int force_tile, int splitk, void* stream) {

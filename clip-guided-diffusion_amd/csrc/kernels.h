@@ -128,6 +128,11 @@ struct cgd_mask_coef;
 int cgd_launch_masked_merge(cgd_ctx* ctx, float* sample, float* x0, const float* init, const float* mask, const float* n_known,
                             const float* n_re, float* x_re, int B, int H, int W, int init_batch, int mask_batch, int mask_channels,
                             const cgd_mask_coef& k, hipStream_t s);
+// invert.hip: the update of one DDIM inversion step (include/cgd_mi355x.h: cgd_ddim_reverse_update); eps is read in place from the model's
+// 6-channel output, x0 and noise_out (with init) may be null
+struct cgd_reverse_coef;
+int cgd_launch_ddim_reverse_update(cgd_ctx* ctx, const float* x, const float* out6, const float* init, float* x_next, float* x0,
+                                   float* noise_out, int B, int H, int W, int init_batch, const cgd_reverse_coef& k, hipStream_t s);
 // spherical-distance loss and its gradient w.r.t. the cutout embeddings
 //   emb [cutn*B][D] (row = cut*B + b), targets [P][D], weights [B][P] (dense per-sample prompt weights, see
 //   host-side broadcast rules), loss_part: per-(cut,b) partial losses [cutn*B] (already * scale / cutn)

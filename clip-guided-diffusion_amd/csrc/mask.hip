@@ -6,11 +6,14 @@
 // sample, pred_xstart, n_known, n_re, x_re: NCHW fp32 (B,3,H,W); init (1 or B,3,H,W); mask (1 or B, 1 or 3, H, W).
 #include "../../include/cgd_mi355x.h"
 #include "common.h"
+#include "elem_pack.h"
 #include "kernels.h"
 
 #include <algorithm>
 
 namespace {
+
+using namespace elem_pack;
 
 struct MergeArgs {
   float* sample;
@@ -23,34 +26,6 @@ struct MergeArgs {
   float sa, sb;        // sqrt(abar_prev), sqrt(1 - abar_prev)
   float ra, rb;        // sqrt(abar / abar_prev), sqrt(1 - abar / abar_prev)
 };
-
-template <int V>
-struct Pack;
-template <>
-struct Pack<1> {
-  typedef float type;
-};
-template <>
-struct Pack<4> {
-  typedef float4 type;
-};
-
-template <int V>
-__device__ __forceinline__ void load(const float* p, float (&v)[V]) {
-  const typename Pack<V>::type t = *reinterpret_cast<const typename Pack<V>::type*>(p);
-  const float* f = reinterpret_cast<const float*>(&t);
-#pragma unroll
-  for (int e = 0; e < V; ++e) v[e] = f[e];
-}
-
-template <int V>
-__device__ __forceinline__ void store(float* p, const float (&v)[V]) {
-  typename Pack<V>::type t;
-  float* f = reinterpret_cast<float*>(&t);
-#pragma unroll
-  for (int e = 0; e < V; ++e) f[e] = v[e];
-  *reinterpret_cast<typename Pack<V>::type*>(p) = t;
-}
 
 // The known region, sa * init (+ sb * n_known): two rounded products and a rounded sum.  Contraction into a fused multiply-add is switched off
 // here, so the kept region is the fp32 value of the formula as written and a host can reproduce it bit for bit.
@@ -99,8 +74,6 @@ __global__ __launch_bounds__(256) void masked_merge_kernel(MergeArgs a, int plan
     }
   }
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

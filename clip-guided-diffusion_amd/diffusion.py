@@ -120,6 +120,20 @@ class SpacedDiffusion:
         k.flags = 0
         return k
 
+    def reverse_coef(self, i):
+        """Coefficients of the DDIM inversion step at index i (sampler.py, csrc/invert.hip), which takes the state from level i up to level
+        i + 1: pred_xstart = sqrt_recip x - sqrt_recipm1 eps, x_next = sqrt(abar_next) pred_xstart + sqrt(1 - abar_next) eps.  abar_next of
+        the last index is 0 (x_next = eps there; the inversion loop stops one index earlier).  The inverse of sqrt(1 - abar_next) is 0
+        where that root is 0, i.e. where the next level carries no noise and none can be implied."""
+        k = L.ReverseCoef()
+        abn = self.alphas_cumprod_next[i]
+        k.sqrt_recip = self.sqrt_recip_alphas_cumprod[i]
+        k.sqrt_recipm1 = self.sqrt_recipm1_alphas_cumprod[i]
+        k.sqrt_ab_next = math.sqrt(abn)
+        k.sqrt_one_minus_ab_next = math.sqrt(1.0 - abn)
+        k.inv_sqrt_one_minus_ab_next = 1.0 / math.sqrt(1.0 - abn) if abn < 1.0 else 0.0
+        return k
+
 
 def create_gaussian_diffusion(steps=1000, noise_schedule="linear", timestep_respacing="", rescale_timesteps=False):
     betas = named_beta_schedule(noise_schedule, steps)

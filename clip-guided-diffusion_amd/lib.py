@@ -58,6 +58,13 @@ class MaskCoef(C.Structure):
 
 MASK_PRED_XSTART, MASK_N_KNOWN, MASK_RENOISE = 1, 2, 4
 
+
+class ReverseCoef(C.Structure):
+    """cgd_reverse_coef: coefficients of cgd_ddim_reverse_update, the DDIM inversion step from level i up to level i + 1"""
+    _fields_ = [("sqrt_recip", f32), ("sqrt_recipm1", f32), ("sqrt_ab_next", f32), ("sqrt_one_minus_ab_next", f32),
+                ("inv_sqrt_one_minus_ab_next", f32)]
+
+
 MANIFEST_CB = C.CFUNCTYPE(None, C.c_char_p, i64, vp)
 
 # name -> (restype, argtypes).  Pointers to device memory are passed as integers (tensor.data_ptr()).
@@ -143,6 +150,7 @@ _SIGS = {
     "cgd_multistep_update": (i32, [vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef),
                                     C.POINTER(StepCoef), C.POINTER(Multistep), vp]),
     "cgd_masked_merge": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(MaskCoef), vp]),
+    "cgd_ddim_reverse_update": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(ReverseCoef), vp]),
     "cgd_op_gemm": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
     "cgd_op_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
     "cgd_op_pack_conv3x3_frag": (i32, [vp, vp, vp, i32, i32, i32, vp]),

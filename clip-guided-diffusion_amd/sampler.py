@@ -11,6 +11,9 @@ it with one cgd_multistep_update launch per evaluation; PLMS draws no per-step n
 Masked sampling (`mask=`, with an init image: 1 regenerates, 0 keeps) adds one cgd_masked_merge launch after every update, which puts the
 init image, noised to the level the update produced, back into the kept region; `resamples=r` repeats every step r times (RePaint with
 jump length 1).  Without a mask nothing of it runs.
+DDIM inversion (`ddim_reverse_sample_loop_progressive`, `ddim_invert`; guided_diffusion's ddim_reverse_sample) runs the deterministic DDIM ODE
+upwards from an image: per step one UNet forward and one cgd_ddim_reverse_update launch.  `ddim_invert` returns the latent and the noise that
+q_samples the image to it, so every loop above starts from the latent when called with `noise=noise, init_image=image, skip_timesteps=s`.
 """
 import ctypes as C
 import math
@@ -441,3 +444,68 @@ class GuidedSampler:
         self._check_mask(shape, init_image, mask, resamples, plms=True)
         return self._loop(2, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
                           randomize_class, cond_fn_with_grad, plms_order=order, mask=mask)
+
+    # ---- DDIM inversion ---------------------------------------------------------------------------------
+    def ddim_reverse_sample_loop_progressive(self, model, image, clip_denoised=False, model_kwargs=None, device=None, progress=False,
+                                             skip_timesteps=0):
+        """guided_diffusion's `ddim_reverse_sample_loop`, progressive: the deterministic DDIM ODE (eta 0) upwards from `image` ((B,3,H,W)
+        in [-1, 1]), step indices 0 .. t0 - 1 with t0 = num_timesteps - 1 - skip_timesteps, so that the last state sits at level t0, the
+        first index of a sampling loop called with the same `skip_timesteps`.  Per step: model.forward at the index's model timestep and
+        one cgd_ddim_reverse_update launch; eps is the model's output (csrc/invert.hip).  Yields {"sample", "pred_xstart"} per step; the
+        last yield also carries "noise", the tensor for which q_sample(image, t0, noise) == sample.  Unguided; `y` is taken from
+        `model_kwargs` as given; nothing random is drawn.
+        Level offset (upstream's, kept): the clean image is treated as the state at level 0, although a state at level 0 carries
+        1 - abar_0 of noise.  A sampling run from the latent therefore reproduces the image as the state ENTERING step index 0, not as that
+        step's pred_xstart, which differs from it by sqrt_recipm1[0] eps."""
+        if clip_denoised:
+            raise NotImplementedError("DDIM inversion runs with clip_denoised=False: clamping pred_xstart breaks the ODE the sampling loops "
+                                      "run back down (the reference samples with clip_denoised=False, cgd.py:253)")
+        if isinstance(skip_timesteps, bool) or not isinstance(skip_timesteps, int) or skip_timesteps < 0:
+            raise ValueError(f"skip_timesteps must be an int >= 0, got {skip_timesteps!r}")
+        t0 = self.num_timesteps - 1 - skip_timesteps
+        if t0 < 1:
+            raise ValueError(f"DDIM inversion needs at least one step below level num_timesteps - 1 - skip_timesteps = {t0}: "
+                             f"{self.num_timesteps} timesteps, {skip_timesteps} skipped")
+        if not th.is_tensor(image) or image.dim() != 4 or image.shape[1] != 3 or 0 in image.shape:
+            raise ValueError(f"image must be (B, 3, H, W), got {tuple(image.shape) if th.is_tensor(image) else type(image).__name__}")
+        return self._reverse_loop(model, image, dict(model_kwargs or {}), th.device(device or f"cuda:{self.ctx.device}"), progress, t0)
+
+    def _reverse_loop(self, model, image, model_kwargs, device, progress, t0):
+        ctx, lib = self.ctx, self.ctx.lib
+        init = image.to(device).float().contiguous()
+        B, _, H, W = init.shape
+        tt = th.tensor([float(self.tables.model_timestep(k)) for k in range(t0)], dtype=th.float32,
+                       device=device).view(-1, 1).repeat(1, B).contiguous()
+        y = model_kwargs.get("y")
+        out6 = th.empty((B, 6, H, W), device=device, dtype=th.float32)
+        it = range(t0)
+        if progress:
+            from tqdm.auto import tqdm
+            it = tqdm(it, desc="DDIM inversion")
+        x = init
+        for i in it:
+            last = i == t0 - 1
+            with th.no_grad():
+                o6 = model.forward(x, tt[i], y, out=out6)
+                x_next, x0 = th.empty_like(init), th.empty_like(init)
+                noise = th.empty_like(init) if last else None
+                ctx.check(lib.cgd_ddim_reverse_update(ctx.h, x.data_ptr(), o6.data_ptr(), init.data_ptr() if last else None,
+                                                      x_next.data_ptr(), x0.data_ptr(), L.ptr(noise), B, H, W, B,
+                                                      self.tables.reverse_coef(i), ctx.stream()))
+            out = {"sample": x_next, "pred_xstart": x0}
+            if last:
+                out["noise"] = noise
+            yield out
+            x = x_next
+
+    def ddim_invert(self, model, image, clip_denoised=False, model_kwargs=None, device=None, progress=False, skip_timesteps=0):
+        """Drains ddim_reverse_sample_loop_progressive -> (latent, noise): the state at level t0 = num_timesteps - 1 - skip_timesteps and
+        the tensor for which q_sample(image, t0, noise) == latent.  Any sampling loop of this class, masked or not, sharded or not, starts
+        from the latent when called with `noise=noise, init_image=image, skip_timesteps=skip_timesteps`; under a mask the deterministic
+        loops re-noise the kept region with that same tensor, consistent with the start state.  Reconstructing the image needs the class
+        fixed over the run (an unconditional model, or randomize_class=False with the `y` given here)."""
+        out = None
+        for out in self.ddim_reverse_sample_loop_progressive(model, image, clip_denoised=clip_denoised, model_kwargs=model_kwargs,
+                                                             device=device, progress=progress, skip_timesteps=skip_timesteps):
+            pass
+        return out["sample"], out["noise"]

@@ -307,6 +307,29 @@ int cgd_masked_merge(cgd_ctx* ctx, float* sample, float* pred_xstart, const floa
                      const float* n_re, float* x_re, int B, int H, int W, int init_batch, int mask_batch, int mask_channels,
                      const cgd_mask_coef* k, void* stream);
 
+/* ---- DDIM inversion of an init image (guided_diffusion's ddim_reverse_sample, unguided, clip_denoised=False): the update of one inversion
+ *      step, from level t up to level t+1 along the deterministic DDIM ODE, in one launch after the UNet forward:
+ *        eps         = model_out6[:, 0:3]                 (read in place: plane b * 6 + c; the variance planes 3..5 are never touched)
+ *        pred_xstart = sqrt_recip x - sqrt_recipm1 eps
+ *        x_next      = sqrt_ab_next pred_xstart + sqrt_one_minus_ab_next eps
+ *        noise_out   = (x_next - sqrt_ab_next init) inv_sqrt_one_minus_ab_next     (the tensor that q_samples init to x_next at level t+1)
+ *      eps is the model's output, not upstream's (sqrt_recip x - pred_xstart) / sqrt_recipm1: equal in exact arithmetic, but that form
+ *      divides by sqrt_recipm1 ~ 0.01 at t = 0 and costs an fp32 round trip 2e-4.
+ *      x, x_next, pred_xstart, noise_out: (B,3,H,W); model_out6: (B,6,H,W); init: (init_batch,3,H,W), init_batch 1 or B.  x_next is
+ *      required; no output may alias x and the outputs must be distinct buffers; pred_xstart and noise_out may be NULL; noise_out needs init, and init is read only for noise_out.
+ *      Any 4-byte-aligned pointers and any H * W are accepted (16-byte accesses when every pointer is 16-byte aligned and 4 | H * W).
+ *      Returns -2 (cgd_last_error), before any launch, for a non-positive size, a missing required buffer, an output that aliases x or another output, noise_out without
+ *      init, an init batch other than 1 or B, or noise_out where sqrt_one_minus_ab_next (or its inverse) is 0: abar_next = 1, no noise at that level. ---- */
+typedef struct cgd_reverse_coef {
+  float sqrt_recip;                 /* sqrt(1/abar_t)                                                        */
+  float sqrt_recipm1;               /* sqrt(1/abar_t - 1)                                                    */
+  float sqrt_ab_next;               /* sqrt(abar_{t+1}) (0 at the last index)                                */
+  float sqrt_one_minus_ab_next;     /* sqrt(1 - abar_{t+1})                                                  */
+  float inv_sqrt_one_minus_ab_next; /* 1 / sqrt(1 - abar_{t+1}), or 0 where it is undefined                  */
+} cgd_reverse_coef;
+int cgd_ddim_reverse_update(cgd_ctx* ctx, const float* x, const float* model_out6, const float* init, float* x_next, float* pred_xstart,
+                            float* noise_out, int B, int H, int W, int init_batch, const cgd_reverse_coef* k, void* stream);
+
 /* ---- single ops, exported for parity tests and for user-supplied cond_fn plumbing ---- */
 /* C[M][N] = alpha * A[M][K] B[N][K]^T (+bias[N]) (+R[M][N]); conv3x3: A is NHWC (Bn,H,W,Cin), B = [N][9*Cin].
  * force_tile: 0 auto, 64 / 128 / 256 / 257 (+1000: two-deep prefetch) igemm tiles, 513 weight GEMM kernel (B re-packed per call),

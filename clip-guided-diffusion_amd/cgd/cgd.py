@@ -43,6 +43,9 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
             raise ValueError(f"init image 'invert=...' needs height_offset = width_offset = 0, got {height_offset} and {width_offset}: the "
                              "inverted latent has the init image's size")
 
+    # "A+secondary=FILE" (an extension like "plmsN"): the guidance gradient returns through the secondary model instead of through the UNet
+    clip_names, secondary_path = clip_util.split_secondary(clip_model_name, image_size, height_offset, width_offset)  # refuses before any load
+
     wandb_run = None
     if wandb_project is not None:
         import wandb  # optional observability hook, outside the hot path
@@ -60,7 +63,6 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
 
     # CLIP tower(s), prompt embeddings and weights.  "A+B" (e.g. "RN50+ViT-L/14", BASELINE config 5) sums the CLIP losses of
     # several towers: a build extension, the reference takes a single name.
-    clip_names = [n.strip() for n in clip_model_name.split("+")]
     clip_models, clip_size = [], None
     for name in clip_names:
         cm, size = clip_util.load_clip(name, device)
@@ -120,6 +122,8 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
     gd_model, diffusion = script_util.load_guided_diffusion(
         checkpoint_path=diffusion_path, image_size=image_size, class_cond=class_cond, diffusion_steps=diffusion_steps,
         timestep_respacing=timestep_respacing, use_fp16=True, device=device, noise_schedule=noise_schedule, dropout=dropout)
+    # (a collective like the loads above: before the early return of a rank without samples)
+    secondary = clip_util.load_secondary(gd_model.ctx, secondary_path, device) if secondary_path is not None else None
 
     if local_batch == 0:
         return  # more ranks than samples: this rank only took part in the weight broadcasts above (they are collectives)
@@ -143,7 +147,8 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         reduce_clip=reduce_clip, progressive_cutout=progressive_cutout, cached_cutouts=cached_cutouts, make_cutouts=make_cutouts,
         # "initialized lazily as it can use a bit of VRAM" (reference cgd.py:146-148): only with an init image and a non-zero scale
         lpips=script_util.load_lpips(gd_model.ctx, checkpoints_dir, device) if (init_tensor is not None and init_scale != 0) else None,
-        init_tensor=init_tensor, init_scale=init_scale)
+        init_tensor=init_tensor, init_scale=init_scale,
+        secondary=secondary)
     if nranks > 1:
         cond_fn.shard = diffusion.shard = (mine, batch_size)
 
@@ -236,7 +241,7 @@ _CLI_SPEC = f"""
 --timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', or 'plmsN' for PLMS (e.g. -respace plms50)
 --num_cutouts -cutn int 16 | random cutouts shown to CLIP per step
 --cutout_power -cutpow float 1.0 | exponent of the cutout size distribution
---clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, ARCH=FILE for an open_clip ViT checkpoint (ARCH: ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14, optional -quickgelu suffix), or 'A+B' to sum two towers
+--clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, ARCH=FILE for an open_clip ViT checkpoint (ARCH: ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14, optional -quickgelu suffix), 'A+B' to sum two towers, or 'A+secondary=FILE' to guide through the secondary model FILE
 --uncond -uncond flag | use the unconditional 256 / 512 checkpoints
 --noise_schedule -sched str linear | 'linear' or 'cosine'
 --dropout -drop float 0.0 | dropout of the diffusion model (inference: keep 0)

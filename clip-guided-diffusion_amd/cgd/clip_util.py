@@ -131,6 +131,48 @@ def parse_clip_model_name(model_name):
     return arch[0], arch[1], (path.strip() if sep else None)
 
 
+def split_secondary(clip_model_name, image_size=None, height_offset=0, width_offset=0):
+    """The '+'-separated `--clip_model` list -> (CLIP tower entries, secondary-model checkpoint path or None).  A `secondary=FILE` entry switches
+    the secondary model on (`cgd_amd.nets.SecondaryModel`: the guidance gradient returns to x through it instead of through the UNet); it is a
+    value like 'plmsN' and 'ARCH=FILE', counts as no tower, and FILE is not read under CGD_SYNTHETIC_WEIGHTS=1.  Refused here, before
+    anything is loaded: a list with a secondary model but no CLIP tower, more than one secondary model, an empty FILE, and — when
+    `image_size` is given — an image whose height or width (image_size + offset) is not a multiple of 32."""
+    names, secondary = [], None
+    for entry in (n.strip() for n in clip_model_name.split("+")):
+        head, sep, path = entry.partition("=")
+        if sep and head.strip() == "secondary":
+            if secondary is not None:
+                raise ValueError(f"{clip_model_name}: more than one 'secondary=FILE' entry")
+            if not path.strip():
+                raise ValueError(f"{entry}: 'secondary=FILE' needs a checkpoint path after '='")
+            secondary = path.strip()
+        else:
+            names.append(entry)
+    if secondary is not None:
+        if not any(names):
+            raise ValueError(f"{clip_model_name}: 'secondary=FILE' needs a CLIP tower beside it, e.g. 'ViT-B/32+secondary=FILE'")
+        if image_size is not None:
+            for what, size in (("height", image_size + height_offset), ("width", image_size + width_offset)):
+                if size % 32:
+                    raise ValueError(f"the secondary model needs an image {what} that is a multiple of 32, got {size} "
+                                     f"(image_size {image_size} + offset {size - image_size})")
+    return names, secondary
+
+
+def load_secondary(ctx, path, device):
+    """The device secondary model (`secondary=FILE`): FILE is the published secondary_model_imagenet_2.pth state dict (or a checkpoint that
+    wraps it as {'state_dict': ...}), read on rank 0 and broadcast; with CGD_SYNTHETIC_WEIGHTS=1 seeded random weights, FILE is not read."""
+    dev = f"cuda:{ctx.device}"
+    net = _nets.SecondaryModel(ctx)
+    if script_util.synthetic_weights_enabled():
+        _shard.load_broadcast(net, lambda: _synthetic.secondary_state_dict(device=dev), dev)
+        return net
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path} not found (set CGD_SYNTHETIC_WEIGHTS=1 for seeded random weights)")
+    _shard.load_broadcast(net, lambda: _openclip_clean_state_dict(th.load(path, map_location="cpu")), dev)
+    return net
+
+
 def _openclip_clean_state_dict(sd):
     """open_clip training checkpoints wrap the weights ({'state_dict': ...}) and DataParallel prefixes every key with 'module.'; entries that are
     not tensors go (epoch counters and the like).  `logit_scale`, `attn_mask` and other tensors no tower asks for are simply never read."""

@@ -397,7 +397,7 @@ class ClipGuidance:
     def __init__(self, ctx, unet, clip_tower, diffusion, target_embeds, weights, num_cutouts, cutout_power=1.0,
                  clip_guidance_scale=1000.0, tv_scale=150.0, range_scale=50.0, sat_scale=0.0, use_magnitude=False,
                  reduce_clip=False, progressive_cutout=False, cached_cutouts=False, make_cutouts=None, lpips=None, init_tensor=None,
-                 init_scale=0.0):
+                 init_scale=0.0, secondary=None):
         # Multi-CLIP (BASELINE config 5, a build extension: the reference takes one clip_model_name): `clip_tower` / `target_embeds`
         # may be lists; the CLIP losses of the towers are summed (same cutout boxes, prompt weights and guidance scale).
         self.towers = list(clip_tower) if isinstance(clip_tower, (list, tuple)) else [clip_tower]
@@ -419,6 +419,9 @@ class ClipGuidance:
         if lpips is not None and init_tensor is not None and init_scale != 0:
             self.lpips, self.init_tensor = lpips, init_tensor.float()
         self._lpips_ref_batch = 0
+        # secondary model (nets.SecondaryModel) or None: with one, pred / x_in of the guidance losses come from it and the gradient returns to x
+        # through it; the UNet's backward pass is not run (its forward still gives the update's mean, variance and the yielded pred_xstart)
+        self.secondary = secondary
         self.lpips_loss = None
         self.current_timestep = None  # closure counter of cgd.py:149,265-267
         self.scalars = None
@@ -473,10 +476,19 @@ class ClipGuidance:
     def fac_index(self):
         return self.current_timestep
 
+    def secondary_level(self):
+        """(alpha, sigma, t) of the secondary model at this step: sqrt(abar) and sqrt(1 - abar) at the table row `fac_index()` that `fac` comes
+        from, and the model's own time t = atan2(sigma, alpha) 2 / pi (alpha = cos(t pi / 2), sigma = sin(t pi / 2))."""
+        tables = getattr(self.diffusion, "tables", self.diffusion)
+        i = self.fac_index()
+        alpha, sigma = float(tables.sqrt_alphas_cumprod[i]), float(tables.sqrt_one_minus_alphas_cumprod[i])
+        return alpha, sigma, math.atan2(sigma, alpha) * 2.0 / math.pi
+
     # -- the native gradient ---------------------------------------------------------------------------
     def native(self, x, x0, x_in, coef):
         """x, x0 = pred_xstart, x_in = blend: (B,3,H,W) on the GPU.  Returns g (B,3,H,W) or None when the
-        reduce_clip gate skips this step (the reference returns zeros_like(x))."""
+        reduce_clip gate skips this step (the reference returns zeros_like(x)).  With a secondary model, x0 and x_in are replaced by
+        its prediction from x and the blend of that, and g = -dL/dx runs back through it instead of through the UNet."""
         skip, cutn = self.schedule()
         self.last_ran = not skip
         if skip:
@@ -501,6 +513,11 @@ class ClipGuidance:
             else:  # the B <-> P broadcast rule is decided on the GLOBAL batch (sample b <-> prompt b when B == P)
                 wm = prompt_weight_matrix(self.weights.cpu(), self.shard[1], dev)[self.shard[0]].contiguous()
             self._wm[B] = wm
+        sec = self.secondary
+        if sec is not None:
+            alpha, sigma, t_sec = self.secondary_level()
+            x0, x_in = sec.forward(x, self._b("sec_t", (B,), dev).fill_(t_sec), fac=coef.fac, pred=self._b("sec_pred", (B, 3, H, W), dev),
+                                   x_in=self._b("sec_xin", (B, 3, H, W), dev))
         gclip = self._b("gclip", (B, 3, H, W), dev)
         acc = 0
         if self.lpips is not None:
@@ -540,11 +557,18 @@ class ClipGuidance:
         # it so that its per-sample gradient equals the batched run's (the logged value is then this rank's share of the loss)
         sats = self.sats if self.shard is None else self.sats * (B / float(self.shard[1]))
         gdir = self._b("gdir", (B, 3, H, W), dev)
-        seed6 = self._b("seed6", (B, 6, H, W), dev)
         lpart = self._b("lpart", (nblk, 3), dev)
-        ctx.check(lib.cgd_guidance_combine(ctx.h, gclip.data_ptr(), x_in.data_ptr(), x0.data_ptr(), gdir.data_ptr(), seed6.data_ptr(),
-                                           lpart.data_ptr(), B, H, W, coef, self.tvs, self.rs, sats, s))
-        gunet = self.unet.dgrad(seed6, self._b("gunet", (B, 3, H, W), dev))
+        if sec is not None:
+            # pred = alpha x - sigma v: the direct part and the seed dL/dv, which the secondary net's dgrad turns into the rest
+            seed3 = self._b("seed3", (B, 3, H, W), dev)
+            ctx.check(lib.cgd_secondary_combine(ctx.h, gclip.data_ptr(), x_in.data_ptr(), x0.data_ptr(), gdir.data_ptr(), seed3.data_ptr(),
+                                                lpart.data_ptr(), B, H, W, coef.fac, alpha, sigma, self.tvs, self.rs, sats, s))
+            gunet = sec.dgrad(seed3, self._b("gsec", (B, 3, H, W), dev))
+        else:
+            seed6 = self._b("seed6", (B, 6, H, W), dev)
+            ctx.check(lib.cgd_guidance_combine(ctx.h, gclip.data_ptr(), x_in.data_ptr(), x0.data_ptr(), gdir.data_ptr(), seed6.data_ptr(),
+                                               lpart.data_ptr(), B, H, W, coef, self.tvs, self.rs, sats, s))
+            gunet = self.unet.dgrad(seed6, self._b("gunet", (B, 3, H, W), dev))
         g = self._b("g", (B, 3, H, W), dev)
         gpart = self._b("gpart", (nblk, 2), dev)
         ctx.check(lib.cgd_grad_finish(ctx.h, gdir.data_ptr(), gunet.data_ptr(), g.data_ptr(), gpart.data_ptr(), B, H, W, s))

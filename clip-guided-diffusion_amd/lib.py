@@ -134,6 +134,21 @@ _SIGS = {
     "cgd_lpips_set_reference": (i32, [vp, vp, i32, i32, i32, vp]),
     "cgd_lpips_loss_grad": (i32, [vp, vp, f32, vp, vp, i32, vp]),
     "cgd_lpips_debug_replay": (i32, [vp, C.POINTER(vp)]),
+    "cgd_secondary_manifest": (i32, [MANIFEST_CB, vp]),
+    "cgd_secondary_create": (i32, [vp, C.POINTER(vp)]),
+    "cgd_secondary_destroy": (None, [vp]),
+    "cgd_secondary_num_params": (i32, [vp]),
+    "cgd_secondary_param_info": (i32, [vp, i32, C.c_char_p, i32, C.POINTER(i64)]),
+    "cgd_secondary_set_param": (i32, [vp, C.c_char_p, vp, i64]),
+    "cgd_secondary_finalize": (i32, [vp]),
+    "cgd_secondary_forward": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+    "cgd_secondary_forward_blend": (i32, [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp]),
+    "cgd_secondary_dgrad": (i32, [vp, vp, vp, vp]),
+    "cgd_secondary_debug_replay": (i32, [vp, C.POINTER(vp)]),
+    "cgd_secondary_head": (i32, [vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, vp]),
+    "cgd_secondary_combine": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, f32, vp]),
+    "cgd_op_secondary_pack": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "cgd_op_bilinear_up2x": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_cutouts_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_cutouts_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_cutouts_aug_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),

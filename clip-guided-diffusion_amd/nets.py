@@ -396,12 +396,74 @@ class LpipsVGG(_Net):
         return loss, g
 
 
+class SecondaryModel(_Net):
+    """The secondary diffusion model (SecondaryDiffusionImageNet2 of Katherine Crowson's CLIP-guided diffusion notebooks, also shipped with
+    Disco Diffusion): a small convolutional denoiser whose prediction of the clean image stands in for the UNet's in the guidance losses, so
+    that their gradient returns to `x` through this net instead of through the UNet.  `load_state_dict` takes the module's own keys
+    (`net.0.0.weight` ... `net.4.bias`, `timestep_embed.weight`): the published secondary_model_imagenet_2.pth loads by name.  H and W must be
+    multiples of 32."""
+    _prefix = "secondary"
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        h = C.c_void_p()
+        ctx.check(ctx.lib.cgd_secondary_create(ctx.h, C.byref(h)))
+        self._adopt(h)
+        self.dgrad_calls = 0
+
+    @staticmethod
+    def model_time(alpha, sigma):
+        """The model's time t in [0, 1] of a noise level: x_t = alpha x_0 + sigma eps with alpha = cos(t pi / 2), sigma = sin(t pi / 2)."""
+        import math
+        return math.atan2(float(sigma), float(alpha)) * 2.0 / math.pi
+
+    def forward(self, x, t, fac=None, pred=None, x_in=None):
+        """x (B,3,H,W) fp32 NCHW on the GPU, t (B,) the model's time -> pred; with `fac` also x_in = pred fac + x (1 - fac), from the same
+        launch: returns (pred, x_in)."""
+        x = x.contiguous().float()
+        B, _, H, W = x.shape
+        t = t.to(device=x.device, dtype=th.float32).contiguous()
+        if pred is None:
+            pred = th.empty_like(x)
+        if fac is None:
+            self.ctx.check(self.ctx.lib.cgd_secondary_forward(self.h, x.data_ptr(), t.data_ptr(), B, H, W, pred.data_ptr(), self.ctx.stream()))
+            self._keep = (x, t)  # inputs must outlive the enqueued work
+            return pred
+        if x_in is None:
+            x_in = th.empty_like(x)
+        self.ctx.check(self.ctx.lib.cgd_secondary_forward_blend(self.h, x.data_ptr(), t.data_ptr(), B, H, W, float(fac), pred.data_ptr(),
+                                                                x_in.data_ptr(), self.ctx.stream()))
+        self._keep = (x, t)
+        return pred, x_in
+
+    def dgrad(self, dv, dx=None):
+        """d(sum(v * dv))/dx of the last forward, v = the net's raw output (pred = x alpha - v sigma)."""
+        dv = dv.contiguous().float()
+        if dx is None:
+            dx = th.empty_like(dv)
+        self.ctx.check(self.ctx.lib.cgd_secondary_dgrad(self.h, dv.data_ptr(), dx.data_ptr(), self.ctx.stream()))
+        self._keep_g = dv
+        self.dgrad_calls += 1
+        return dx
+
+    def debug_replay(self, acts):
+        """Test support (cgd_secondary_debug_replay): 23 post-ReLU activations as dense NHWC rows on the device, or None to switch it off."""
+        if acts is None:
+            self._replay = None
+            self.ctx.check(self.ctx.lib.cgd_secondary_debug_replay(self.h, None))
+            return
+        self._replay = [a.contiguous().float() for a in acts]
+        arr = (C.c_void_p * len(self._replay))(*[a.data_ptr() for a in self._replay])
+        assert len(self._replay) == 23
+        self.ctx.check(self.ctx.lib.cgd_secondary_debug_replay(self.h, arr))
+
+
 def manifest(kind, cfg=None):
     """[(name, numel)] of a network configuration from the library's host-only manifest functions (no GPU, no context)."""
     out = []
     cb = L.MANIFEST_CB(lambda name, numel, user: out.append((name.decode(), int(numel))))
     lib = L.load()
-    n = lib.cgd_lpips_manifest(cb, None) if kind == "lpips" else getattr(lib, f"cgd_{kind}_manifest")(C.byref(cfg), cb, None)
+    n = getattr(lib, f"cgd_{kind}_manifest")(cb, None) if kind in ("lpips", "secondary") else getattr(lib, f"cgd_{kind}_manifest")(C.byref(cfg), cb, None)
     if n < 0:
         raise ValueError(f"{kind}: invalid configuration (status {n})")
     return out

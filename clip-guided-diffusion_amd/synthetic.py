@@ -103,3 +103,24 @@ def resnet_state_dict(net, seed=2468, device="cuda"):
             t = (2.0 / fan_in) ** 0.5 * th.randn(numel, device=device, generator=g)
         sd[name] = t
     return sd
+
+
+def secondary_state_dict(seed=9753, device="cpu"):
+    """Seeded stand-in for the secondary model's weights (`nets.SecondaryModel`) under its state-dict names, from the library's manifest: He-scaled
+    3x3 convolutions (23 ReLU layers deep: a smaller gain would let the activations die out), small biases, N(0, 1) Fourier frequencies (the
+    module's own initialisation of `timestep_embed.weight`)."""
+    from . import nets
+    g = th.Generator().manual_seed(seed)
+    specs = dict(nets.manifest("secondary"))
+    sd = {}
+    for name, numel in specs.items():
+        if name == "timestep_embed.weight":
+            t = th.randn(numel, 1, generator=g)
+        elif name.endswith(".bias"):
+            t = 0.05 * th.randn(numel, generator=g)
+        else:
+            cout = specs[name[:-len("weight")] + "bias"]
+            cin = numel // (9 * cout)
+            t = (2.0 / (9 * cin)) ** 0.5 * th.randn(cout, cin, 3, 3, generator=g)
+        sd[name] = t.to(device)
+    return sd

@@ -185,6 +185,52 @@ int cgd_lpips_loss_grad(cgd_lpips* v, const float* x_nchw, float grad_scale, flo
  * call continues from these activations, so taps, ReLU masks and max-pool arg-max are the caller's (the oracle's). */
 int cgd_lpips_debug_replay(cgd_lpips* v, const float* const* acts);
 
+/* ---- Secondary diffusion model (SecondaryDiffusionImageNet2 of Katherine Crowson's CLIP-guided diffusion notebooks / Disco Diffusion): a
+ *      small convolutional denoiser that predicts the clean image for the guidance losses, so that their gradient returns to x through ~50
+ *      GFLOP of 3x3 convolutions instead of through the UNet (no reference counterpart: the reference differentiates the UNet).
+ *      Parameters use the module's state-dict names (net.0.0.weight ... net.4.bias, timestep_embed.weight [8][1]).  x (B,3,H,W) NCHW, H and W
+ *      multiples of 32 (anything else fails, -2, before any launch); t (B) device fp32 in [0,1]: the model's own time, atan2(sigma, alpha) 2/pi.
+ *        forward:       pred = x cos(t pi/2) - v sin(t pi/2), v = net(cat(x, Fourier planes of t)); keeps the activations for dgrad
+ *        forward_blend: the same, and x_in = pred fac + x (1 - fac) in the head's launch
+ *        dgrad:         dx (B,3,H,W) = d(sum(v * dv_seed))/dx of the LAST forward; dv_seed (B,3,H,W).  The caller chains pred and x_in
+ *                       (cgd_secondary_combine).  Fails (-2) without a forward since the last finalize / failed forward.
+ *      The trunk always runs on exact-fp32 products (as LPIPS). ---- */
+typedef struct cgd_secondary cgd_secondary;
+int cgd_secondary_manifest(cgd_manifest_cb cb, void* user);
+int cgd_secondary_create(cgd_ctx* ctx, cgd_secondary** out);
+void cgd_secondary_destroy(cgd_secondary* v);
+int cgd_secondary_num_params(cgd_secondary* v);
+int cgd_secondary_param_info(cgd_secondary* v, int index, char* name_buf, int buf_len, int64_t* numel);
+int cgd_secondary_set_param(cgd_secondary* v, const char* name, const float* data, int64_t numel);
+int cgd_secondary_finalize(cgd_secondary* v);
+int cgd_secondary_forward(cgd_secondary* v, const float* x, const float* t, int B, int H, int W, float* pred, void* stream);
+int cgd_secondary_forward_blend(cgd_secondary* v, const float* x, const float* t, int B, int H, int W, float fac, float* pred, float* x_in,
+                                void* stream);
+int cgd_secondary_dgrad(cgd_secondary* v, const float* dv_seed, float* dx, void* stream);
+/* Test support, not on the product path: mask replay.  acts = 23 device pointers (post-ReLU activations of the 23 ConvBlocks in execution
+ * order, [B*h_l*w_l][cout_l] dense NHWC rows, for the input the following forward calls are given) or NULL to switch it off: each forward
+ * continues from these activations, so the ReLU masks of its dgrad are the caller's (the oracle's). */
+int cgd_secondary_debug_replay(cgd_secondary* v, const float* const* acts);
+/* the head alone (what forward / forward_blend launch last): v, x, pred, x_in (or NULL) (B,3,H,W), 16-byte aligned */
+int cgd_secondary_head(cgd_ctx* ctx, const float* v, const float* x, const float* t, float fac, float* pred, float* x_in, int B, int H, int W,
+                       void* stream);
+/* The secondary-path counterpart of cgd_guidance_combine.  g_in = dL/dx_in of the CLIP / LPIPS legs (or NULL); the tv and saturation terms
+ * are taken on x_in, the range term on pred.  With G_in = g_in + tv + sat and G_pred = fac G_in + range:
+ *   g_direct = (1 - fac) G_in + alpha G_pred  (dL/dx not through the net);  seed3 = -sigma G_pred  (dL/dv, the seed of cgd_secondary_dgrad);
+ * loss_part [cgd_guidance_part_blocks][3] = partial (tv, range, sat) losses.  cgd_grad_finish / cgd_scalars take it from there. */
+int cgd_secondary_combine(cgd_ctx* ctx, const float* g_in, const float* x_in, const float* pred, float* g_direct, float* seed3,
+                          float* loss_part, int B, int H, int W, float fac, float alpha, float sigma, float tv_scale, float range_scale,
+                          float sat_scale, void* stream);
+/* single ops of the secondary model, exported for parity tests.  pack: NCHW x + the 16 Fourier planes [cos f | sin f], f = 2 pi t[b]
+ * embed_weight[j] -> NHWC rows [B*H*W][32] (channels 0..2 x, 3..18 the planes, 19..31 zero).  bilinear_up2x (align_corners = False):
+ * adjoint 0: in [B][Hi][Wi] rows of C channels at stride ldi -> out [B][2Hi][2Wi] rows at stride ldo; adjoint 1: in = gradient of the
+ * (2Hi, 2Wi) map at stride ldi -> out = gradient of the (Hi, Wi) map at stride ldo (gather form).  C and the strides multiples of 4,
+ * pointers 16-byte aligned, or the call fails (-2) before anything is launched. */
+int cgd_op_secondary_pack(cgd_ctx* ctx, const float* x, const float* t, const float* embed_weight, float* out, int B, int H, int W,
+                          void* stream);
+int cgd_op_bilinear_up2x(cgd_ctx* ctx, const float* in, int ldi, float* out, int ldo, int B, int Hi, int Wi, int C, int adjoint,
+                         void* stream);
+
 /* ---- cutouts: replaces MakeCutouts.forward (cgd/modules.py:50-66) + x.add(1).div(2) (cgd.py:190) + CLIP_NORMALIZE
  *      (clip_util.py:45).  coords: device int32 [cutn][4] = (oy, ox, h, w) of each (possibly truncated) crop. ---- */
 int cgd_cutouts_fwd(cgd_ctx* ctx, const float* x_in, const int32_t* coords, float* out, int B, int H, int W, int cutn, int cut_size,

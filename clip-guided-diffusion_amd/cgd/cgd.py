@@ -43,8 +43,10 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
             raise ValueError(f"init image 'invert=...' needs height_offset = width_offset = 0, got {height_offset} and {width_offset}: the "
                              "inverted latent has the init image's size")
 
-    # "A+secondary=FILE" (an extension like "plmsN"): the guidance gradient returns through the secondary model instead of through the UNet
-    clip_names, secondary_path = clip_util.split_secondary(clip_model_name, image_size, height_offset, width_offset)  # refuses before any load
+    # "A+cuts=OV:IN" (an extension like "plmsN"): overview + inner cutouts through the antialiased cubic resize instead of pooled crops
+    towers_and_secondary, cuts = clip_util.split_cuts(clip_model_name, progressive_cutout, use_augs)  # refuses before any load
+    # "A+secondary=FILE" (likewise): the guidance gradient returns through the secondary model instead of through the UNet
+    clip_names, secondary_path = clip_util.split_secondary(towers_and_secondary, image_size, height_offset, width_offset)  # refuses before any load
 
     wandb_run = None
     if wandb_project is not None:
@@ -90,8 +92,11 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
 
     if use_augs:
         tqdm.write("cutout augmentations requested")
-    make_cutouts = clip_util.MakeCutouts(cut_size=clip_size, num_cutouts=num_cutouts, cutout_size_power=cutout_power, use_augs=use_augs,
-                                         ctx=clip_model.tower.ctx)
+    if cuts is not None:  # --num_cutouts then only sizes the image prompts' cutouts above
+        make_cutouts = clip_util.MakeCutoutsResized(clip_size, overview=cuts[0], inner=cuts[1], schedule=cuts[2], ctx=clip_model.tower.ctx)
+    else:
+        make_cutouts = clip_util.MakeCutouts(cut_size=clip_size, num_cutouts=num_cutouts, cutout_size_power=cutout_power, use_augs=use_augs,
+                                             ctx=clip_model.tower.ctx)
     if cached_cutouts:
         make_cutouts.cache_coordinates(image_size + width_offset, image_size + height_offset)
 
@@ -241,7 +246,7 @@ _CLI_SPEC = f"""
 --timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', or 'plmsN' for PLMS (e.g. -respace plms50)
 --num_cutouts -cutn int 16 | random cutouts shown to CLIP per step
 --cutout_power -cutpow float 1.0 | exponent of the cutout size distribution
---clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, ARCH=FILE for an open_clip ViT checkpoint (ARCH: ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14, optional -quickgelu suffix), 'A+B' to sum two towers, or 'A+secondary=FILE' to guide through the secondary model FILE
+--clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, ARCH=FILE for an open_clip ViT checkpoint (ARCH: ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14, optional -quickgelu suffix), 'A+B' to sum two towers, 'A+secondary=FILE' to guide through the secondary model FILE, or 'A+cuts=OV:IN' (or 'cuts=OV:IN/OV2:IN2': the second pair once 40 percent of the run is done) for OV whole-frame and IN random cutouts per step through the antialiased cubic resize (--num_cutouts then only affects image prompts)
 --uncond -uncond flag | use the unconditional 256 / 512 checkpoints
 --noise_schedule -sched str linear | 'linear' or 'cosine'
 --dropout -drop float 0.0 | dropout of the diffusion model (inference: keep 0)

@@ -17,7 +17,7 @@ from cgd_amd import nets as _nets
 from cgd_amd import shard as _shard
 from cgd_amd import synthetic as _synthetic
 from cgd_amd import tokenizer as _tokenizer
-from cgd_amd.guidance import CLIP_MEAN, CLIP_STD, MakeCutouts  # noqa: F401
+from cgd_amd.guidance import CLIP_MEAN, CLIP_STD, MakeCutouts, MakeCutoutsResized  # noqa: F401
 
 from . import script_util
 
@@ -157,6 +157,46 @@ def split_secondary(clip_model_name, image_size=None, height_offset=0, width_off
                     raise ValueError(f"the secondary model needs an image {what} that is a multiple of 32, got {size} "
                                      f"(image_size {image_size} + offset {size - image_size})")
     return names, secondary
+
+
+CUTS_SWITCH_FRACTION = 0.4  # 'cuts=A:B/C:D': the first pair while less than this fraction of the run is done, the second afterwards
+
+
+def split_cuts(clip_model_name, progressive_cutout=False, use_augs=False):
+    """The '+'-separated `--clip_model` list -> (the list without its `cuts=` entry, None or (overview, inner, schedule)).  A `cuts=OV:IN`
+    entry switches the resized overview + inner cutouts on (`cgd_amd.guidance.MakeCutoutsResized(cut_size, overview, inner, schedule=schedule)`);
+    `cuts=OV:IN/OV2:IN2` uses the first pair while less than 40 % of the run is done and the second afterwards.  It is a value like 'plmsN' and
+    'secondary=FILE' and counts as no tower.  Refused here, before anything is loaded: a malformed value (counts that are not non-negative
+    integers, a pair without a cut, more than two pairs, more than one entry), a list with no tower beside it, and the entry together with
+    progressive cutouts or cutout augmentations (the cut counts follow the entry's own schedule, and the resized cutter has no augmentations)."""
+    names, cuts = [], None
+    for entry in (n.strip() for n in clip_model_name.split("+")):
+        head, sep, value = entry.partition("=")
+        if not (sep and head.strip() == "cuts"):
+            names.append(entry)
+            continue
+        if cuts is not None:
+            raise ValueError(f"{clip_model_name}: more than one 'cuts=' entry")
+        pairs = []
+        for part in value.split("/"):
+            fields = part.strip().split(":")
+            if len(fields) != 2 or not all(f.strip().isdigit() for f in fields):
+                raise ValueError(f"{entry}: expected 'cuts=OV:IN' or 'cuts=OV:IN/OV2:IN2' with non-negative integer counts")
+            ov, inn = int(fields[0]), int(fields[1])
+            if ov + inn < 1:
+                raise ValueError(f"{entry}: a pair needs at least one cut")
+            pairs.append((ov, inn))
+        if len(pairs) > 2:
+            raise ValueError(f"{entry}: at most two OV:IN pairs")
+        cuts = (*pairs[-1], [(CUTS_SWITCH_FRACTION, *pairs[0])] if len(pairs) == 2 else None)
+    if cuts is not None:
+        if not any(n and not n.startswith("secondary=") for n in names):
+            raise ValueError(f"{clip_model_name}: 'cuts=' needs a CLIP tower beside it, e.g. 'ViT-B/32+cuts=4:12'")
+        if progressive_cutout:
+            raise ValueError("'cuts=' sets the cut counts of every step itself: it cannot be combined with --progressive-cutout")
+        if use_augs:
+            raise ValueError("'cuts=' selects the resized cutouts, which have no use_augs augmentations")
+    return "+".join(names), cuts
 
 
 def load_secondary(ctx, path, device):

@@ -229,6 +229,19 @@ int64_t cgd_cutouts_aug_scratch_floats(int B, int H, int W, int cutn) { return (
 int cgd_op_aug_sample_map(const float* params, int h, int w, int32_t* affine_src, int32_t* persp_idx, float* persp_w) {
   return cgd_aug_sample_map(params, h, w, affine_src, persp_idx, persp_w);
 }
+int cgd_cutouts_resize_fwd(cgd_ctx* ctx, const float* x_in, const int32_t* coords, const int32_t* flags, float* out, int B, int H, int W,
+                           int cutn, int cut_size, int layout, int patch, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_cutouts_resize_fwd(ctx, x_in, coords, flags, out, B, H, W, cutn, cut_size, layout, patch, S(stream));
+}
+int cgd_cutouts_resize_bwd(cgd_ctx* ctx, const float* d_out, const int32_t* coords, const int32_t* flags, float* g_in, float* scratch, int B,
+                           int H, int W, int cutn, int cut_size, int layout, int patch, int accumulate, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_cutouts_resize_bwd(ctx, d_out, coords, flags, g_in, scratch, B, H, W, cutn, cut_size, layout, patch, accumulate,
+                                       S(stream));
+}
+int64_t cgd_cutouts_resize_scratch_floats(int B, int H, int W, int cutn) { return (int64_t)cgd_cutouts_resize_scratch(B, H, W, cutn); }
+int cgd_cutouts_resize_weights(int n, int m, float* w, int32_t* left, int* taps) { return cgd_resize_weights(n, m, w, left, taps); }
 int cgd_spherical_loss(cgd_ctx* ctx, const float* emb, const float* targets_n, const float* weights, float* d_emb, float* loss_part,
                        int cutn, int B, int P, int D, float scale, void* stream) {
   CGD_NEED_CTX(ctx);

@@ -122,6 +122,15 @@ int cgd_launch_cutouts_aug_bwd(cgd_ctx* ctx, const float* dout, const int* coord
 size_t cgd_cutouts_aug_scratch(int B, int H, int W, int cutn);
 // host: per output pixel of an h x w crop, the affine nearest source index (-1: fill) and the perspective's 4 taps / weights
 int cgd_aug_sample_map(const float* params, int h, int w, int32_t* affine_src, int32_t* persp_idx, float* persp_w);
+// cutresize.hip: cutouts through the antialiased cubic resize (flags: device int32 [cutn], bit 0 luma before the resize, bit 1 flip along
+// W after it); scratch: cgd_cutouts_resize_scratch(B, H, W, cutn) floats
+int cgd_launch_cutouts_resize_fwd(cgd_ctx* ctx, const float* x_in, const int* coords, const int* flags, float* out, int B, int H, int W,
+                                  int cutn, int cs, int layout, int P, hipStream_t s);
+int cgd_launch_cutouts_resize_bwd(cgd_ctx* ctx, const float* dout, const int* coords, const int* flags, float* G, float* scratch, int B,
+                                  int H, int W, int cutn, int cs, int layout, int P, int accumulate, hipStream_t s);
+size_t cgd_cutouts_resize_scratch(int B, int H, int W, int cutn);
+// host: weights [m][taps], first taps [m] and the tap count of an n -> m resize, from the routine the kernels run
+int cgd_resize_weights(int n, int m, float* w, int32_t* left, int* taps);
 // mask.hip: the merge of masked sampling after a sampler update (include/cgd_mi355x.h: cgd_masked_merge); sample and x0 (or null) are merged
 // in place, x_re (with n_re, or both null) receives the merged sample taken back up one level
 struct cgd_mask_coef;

@@ -10,6 +10,7 @@ Cutout coordinates are drawn exactly like the reference does (three CPU-generato
 /root/reference/cgd/modules.py:44-46).  With `use_augs=True` the cutouts are augmented (flip / nearest affine / bilinear
 perspective / grayscale / additive noise) inside the cutaug HIP kernels, whose adjoint is a deterministic gather; the parameters
 are drawn like reference_augs draws them (draw_aug_params), the noise on the device generator in its randn_like order.
+`MakeCutoutsResized` is a second cutter: overview + inner cuts through an antialiased cubic resize (the cutresize HIP kernels).
 """
 import math
 
@@ -359,6 +360,181 @@ class _CutoutsFunction(th.autograd.Function):
         return g * 2, None, None, None
 
 
+RESIZE_GRAY, RESIZE_FLIP = 1, 2  # flag bits of a resized cutout: grayscale before the resize, horizontal flip after it
+
+
+def _resize_cubic(d):
+    a = d.abs()
+    return th.where(a <= 1, (1.5 * a - 2.5) * a * a + 1, th.where(a <= 2, ((-0.5 * a + 2.5) * a - 4) * a + 2, th.zeros_like(a)))
+
+
+def resize_matrix(n, m, dtype=th.float32, device=None):
+    """Dense (m, n) matrix of the antialiased cubic resize of an extent n to m (include/cgd_mi355x.h, cgd_cutouts_resize_fwd): centres
+    c_o = ((2o+1) n - m) / (2m), T = ceil(S) taps from ceil(c_o - S / 2) with S = 4 (m >= n) or 4n / m, weights cubic(c_o - j) (or
+    s cubic(s (c_o - j)), s = m / n < 1) over their sum over all T taps; taps outside [0, n) are dropped, not renormalised.  Integer
+    geometry, float64 polynomial: the CPU restatement of the kernels' weight rows."""
+    if m == n:
+        return th.eye(n, dtype=dtype, device=device)
+    big = max(m, n)
+    T = 4 if m >= n else -(-4 * n // m)
+    o = th.arange(m, dtype=th.int64)
+    num = (2 * o + 1) * n - m
+    left = -((4 * big - num) // (2 * m))  # ceil((num - 4 big) / (2m))
+    j = left[:, None] + th.arange(T, dtype=th.int64)
+    k = _resize_cubic((num[:, None] - 2 * m * j).double() / (2 * big))  # c_o - j for m >= n, s (c_o - j) for m < n (s cancels below)
+    tot = k.sum(1, keepdim=True)
+    w = k / th.where(tot == 0, th.ones_like(tot), tot)
+    inside = (j >= 0) & (j < n)
+    M = th.zeros(m, n, dtype=th.float64)
+    M.scatter_add_(1, j.clamp(0, n - 1), th.where(inside, w, th.zeros_like(w)))
+    return M.to(dtype=dtype, device=device)
+
+
+def resize_table(records, H, W):
+    """(ox, oy, w, h, flags) records -> the int32 rows a step uploads: len(records) rows (oy, ox, h, w), then the flags packed four to a
+    row.  A box with an extent below 1 or outside the H x W image is refused here: the kernels only see the table on the device."""
+    rows, flags = [], []
+    for ox, oy, w, h, fl in records:
+        if h < 1 or w < 1 or ox < 0 or oy < 0 or oy + h > H or ox + w > W:
+            raise ValueError(f"cutout box (ox {ox}, oy {oy}, w {w}, h {h}) is empty or outside the {H} x {W} image")
+        rows.append((oy, ox, h, w))
+        flags.append(int(fl))
+    flags += [0] * (-len(flags) % 4)
+    return rows + [tuple(flags[i:i + 4]) for i in range(0, len(flags), 4)]
+
+
+class MakeCutoutsResized(th.nn.Module):
+    """The cutout scheme of the CLIP-guided-diffusion notebooks: `overview` cuts of the whole frame (for overview <= 4: plain, grayscale,
+    mirrored, grayscale + mirrored, in that order; all plain beyond 4) followed by `inner` random square crops, every cut brought to
+    cut_size x cut_size by the antialiased cubic resize (resize_matrix) instead of adaptive average pooling.  Inner cut i has
+    size = int(rand() ** ic_size_pow * (max_size - min_size) + min_size) with max_size = min(H, W), min_size = min(H, W, cut_size), then
+    ox = randint(0, W - size + 1), oy = randint(0, H - size + 1) (three CPU-generator draws per cut, in generate_coords' order), and is
+    grayscale when i <= int(ic_gray_p * inner).  `schedule`: optional rows (until_fraction_done, overview, inner); the first row whose
+    bound exceeds the fraction of the run that is done gives the step's counts (the constructor's counts when none does).
+    A cut is the record (ox, oy, w, h, flags)."""
+    augs = None  # no `use_augs` pipeline on this cutter
+
+    def __init__(self, cut_size, overview=4, inner=12, ic_size_pow=0.5, ic_gray_p=0.2, schedule=None, ctx=None):
+        super().__init__()
+        self.cut_size, self.overview, self.inner = cut_size, int(overview), int(inner)
+        self.ic_size_pow, self.ic_gray_p = ic_size_pow, ic_gray_p
+        self.schedule = [(float(u), int(ov), int(inn)) for (u, ov, inn) in schedule] if schedule else None
+        for ov, inn in [(self.overview, self.inner)] + [r[1:] for r in self.schedule or []]:
+            if ov < 0 or inn < 0 or ov + inn < 1:
+                raise ValueError(f"overview / inner cut counts must be >= 0 with at least one cut, got {ov}:{inn}")
+        self.cached_coords = None
+        self.ctx = ctx
+        self.last_coords = None
+
+    @property
+    def cutn(self):
+        return self.overview + self.inner
+
+    def counts(self, fraction_done=0.0):
+        """(overview, inner) at this point of the run."""
+        for until, ov, inn in self.schedule or []:
+            if fraction_done < until:
+                return ov, inn
+        return self.overview, self.inner
+
+    def _counts(self, override):
+        if override is None:
+            return self.overview, self.inner
+        if isinstance(override, (tuple, list)):
+            return int(override[0]), int(override[1])
+        ov = min(self.overview, int(override))  # a plain count keeps the overview cuts and trims the inner ones
+        return ov, int(override) - ov
+
+    def _inner_boxes(self, side_x, side_y, count):
+        max_size = min(side_x, side_y)
+        min_size = min(side_x, side_y, self.cut_size)
+        boxes = []
+        for _ in range(count):
+            size = int(th.rand([]) ** self.ic_size_pow * (max_size - min_size) + min_size)
+            ox = th.randint(0, side_x - size + 1, ()).item()
+            oy = th.randint(0, side_y - size + 1, ()).item()
+            boxes.append((ox, oy, size, size))
+        return boxes
+
+    def cache_coordinates(self, side_x, side_y):
+        """Draw the inner boxes once (as many as the largest count of the schedule) for draw(..., use_cache=True)."""
+        most = max([self.inner] + [r[2] for r in self.schedule or []])
+        self.cached_coords = self._inner_boxes(side_x, side_y, most)
+
+    def draw(self, side_x, side_y, use_cache=False, num_cutouts_override=None):
+        """The records of one step on a side_x (width) x side_y (height) image.  num_cutouts_override: (overview, inner), or one count."""
+        ov, inn = self._counts(num_cutouts_override)
+        flags = [0, RESIZE_GRAY, RESIZE_FLIP, RESIZE_GRAY | RESIZE_FLIP][:ov] if ov <= 4 else [0] * ov
+        recs = [(0, 0, side_x, side_y, fl) for fl in flags]
+        if use_cache and self.cached_coords is not None:
+            boxes = self.cached_coords[:inn]
+        else:
+            boxes = self._inner_boxes(side_x, side_y, inn)
+        gray_upto = int(self.ic_gray_p * inn)
+        return recs + [(ox, oy, w, h, RESIZE_GRAY if i <= gray_upto else 0) for i, (ox, oy, w, h) in enumerate(boxes)]
+
+    def forward(self, input, use_cache=False, num_cutouts_override=None):
+        """input (B,3,H,W) in [0,1] -> (n*B,3,cut,cut) NCHW, not normalised.  On a GPU input the resize runs in the cutresize HIP kernels
+        (an autograd node over cgd_cutouts_resize_fwd / _bwd when `input` requires grad), on a CPU input as torch ops (`resized`)."""
+        _, _, H, W = input.shape
+        recs = self.draw(W, H, use_cache, num_cutouts_override)
+        self.last_coords = recs
+        if input.device.type != "cuda":
+            return self.resized(input, recs)
+        if self.ctx is None:
+            self.ctx = L.Context(input.device.index or 0)
+        table = th.tensor(resize_table(recs, H, W), dtype=th.int32, device=input.device)
+        if input.requires_grad and th.is_grad_enabled():
+            return _ResizedCutoutsFunction.apply(input, self, table, len(recs))
+        return self._resize(input, table, len(recs))
+
+    def resized(self, input, records, cut_size=None):
+        """crop -> (grayscale) -> Wy crop Wx^T -> (flip) -> cat: the torch restatement, with autograd."""
+        cs = cut_size or self.cut_size
+        outs = []
+        for ox, oy, w, h, fl in records:
+            z = input[:, :, oy:oy + h, ox:ox + w]
+            if fl & RESIZE_GRAY:
+                z = aug_grayscale(z)
+            r = resize_matrix(h, cs, input.dtype, input.device) @ z @ resize_matrix(w, cs, input.dtype, input.device).t()
+            outs.append(r.flip(-1) if fl & RESIZE_FLIP else r)
+        return th.cat(outs)
+
+    def _resize(self, input, table, ncut):
+        B, _, H, W = input.shape
+        # the kernel resizes (x+1)/2 and applies the CLIP normalisation; undo the latter to return the raw resized crop
+        x_pm1 = (input.detach().float() * 2 - 1).contiguous()
+        out = th.empty((ncut * B, 3, self.cut_size, self.cut_size), device=input.device, dtype=th.float32)
+        self.ctx.check(self.ctx.lib.cgd_cutouts_resize_fwd(self.ctx.h, x_pm1.data_ptr(), table.data_ptr(), table.data_ptr() + 16 * ncut,
+                                                           out.data_ptr(), B, H, W, ncut, self.cut_size, 0, 0, self.ctx.stream()))
+        mean = th.tensor(CLIP_MEAN, device=input.device).view(1, 3, 1, 1)
+        std = th.tensor(CLIP_STD, device=input.device).view(1, 3, 1, 1)
+        return out * std + mean
+
+
+class _ResizedCutoutsFunction(th.autograd.Function):
+    """MakeCutoutsResized.forward on a GPU input as an autograd node; its backward is cgd_cutouts_resize_bwd."""
+
+    @staticmethod
+    def forward(ctx, input, mk, table, ncut):
+        ctx.mk, ctx.table, ctx.ncut, ctx.in_shape = mk, table, ncut, tuple(input.shape)
+        return mk._resize(input, table, ncut)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        mk = ctx.mk
+        B, _, H, W = ctx.in_shape
+        # as in _CutoutsFunction: the kernel's convention is out = (resize((x+1)/2) - mean) / std
+        std = th.tensor(CLIP_STD, device=d_out.device).view(1, 3, 1, 1)
+        d = (d_out.float() * std).contiguous()
+        g = th.empty(ctx.in_shape, device=d_out.device, dtype=th.float32)
+        lib = mk.ctx.lib
+        scratch = th.empty(max(1, lib.cgd_cutouts_resize_scratch_floats(B, H, W, ctx.ncut)), device=d_out.device)
+        mk.ctx.check(lib.cgd_cutouts_resize_bwd(mk.ctx.h, d.data_ptr(), ctx.table.data_ptr(), ctx.table.data_ptr() + 16 * ctx.ncut,
+                                                g.data_ptr(), scratch.data_ptr(), B, H, W, ctx.ncut, mk.cut_size, 0, 0, 0, mk.ctx.stream()))
+        return g * 2, None, None, None
+
+
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
@@ -414,6 +590,8 @@ class ClipGuidance:
         self.use_magnitude = bool(use_magnitude)
         self.reduce_clip, self.progressive_cutout, self.cached_cutouts = reduce_clip, progressive_cutout, cached_cutouts
         self.make_cutouts = make_cutouts or MakeCutouts(clip_tower.input_resolution, num_cutouts, cutout_power, ctx=ctx)
+        if isinstance(self.make_cutouts, MakeCutoutsResized) and progressive_cutout:
+            raise ValueError("progressive_cutout does not apply to MakeCutoutsResized: its cut counts come from its own schedule")
         # init-image perceptual term (cgd.py:147-148,220-224): `lpips` is a nets.LpipsVGG, its reference = the init image
         self.lpips, self.init_scale, self.init_tensor = None, float(init_scale), None
         if lpips is not None and init_tensor is not None and init_scale != 0:
@@ -497,14 +675,17 @@ class ClipGuidance:
         B, _, H, W = x.shape
         dev = x.device
         s = ctx.stream()
+        resized = isinstance(self.make_cutouts, MakeCutoutsResized)
         if self.coords_tape is not None:
             coords = self.coords_tape[self.calls]
+        elif resized:  # (ox, oy, w, h, flags) records; this step's counts from the cutter's own schedule
+            coords = self.make_cutouts.draw(W, H, self.cached_cutouts, self.make_cutouts.counts(self.fraction_done()))
         else:
             coords = self.make_cutouts.draw(H, W, self.cached_cutouts, cutn)
         self.calls += 1
         self.make_cutouts.last_coords = coords
         cutn = len(coords)
-        geo = self._upload_geometry(crop_geometry(coords, H, W), dev)
+        geo = self._upload_geometry(resize_table(coords, H, W) if resized else crop_geometry(coords, H, W), dev)
         N = cutn * B
         wm = self._wm.get(B)
         if wm is None:
@@ -529,10 +710,12 @@ class ClipGuidance:
                                                       loss=self._b("lpips_loss", (B,), dev))
             acc = 1
         clip_part = self._b("clip_part", (len(self.towers) * N,), dev)
-        if self.make_cutouts.augs is not None:
+        if resized:
+            self._clip_leg_resized(x_in, geo, cutn, wm, gclip, clip_part, acc)
+        elif self.make_cutouts.augs is not None:
             self._clip_leg_with_augs(x_in, coords, wm, gclip, clip_part, acc)
         for k, (tower, targets) in enumerate(zip(self.towers, self.targets_list)):
-            if self.make_cutouts.augs is not None:
+            if resized or self.make_cutouts.augs is not None:
                 break
             cs, patch = tower.input_resolution, tower.patch
             if patch:  # ViT towers: the cutout kernel writes the patch rows of the patch-embedding GEMM directly (layout 1)
@@ -577,6 +760,72 @@ class ClipGuidance:
                                   int(self.use_magnitude), self.scalars.data_ptr(), s))
         self._keep = geo
         return g
+
+    def fraction_done(self):
+        """Fraction of the run that is done, from the closure counter (as guidance_schedule measures it)."""
+        total = self.diffusion.num_timesteps
+        return (total - self.current_timestep) / total
+
+    def _clip_leg_resized(self, x_in, table, cutn, wm, gclip, clip_part, accumulate):
+        """MakeCutoutsResized: per tower, in tower order, on the same boxes and flags (`table`: the uploaded resize_table) at the tower's
+        own cut size: resized cutouts (cgd_cutouts_resize_fwd, patch rows for ViT towers, images for ResNet towers) -> tower forward ->
+        spherical loss (mean over this step's cutn cuts, per-row partials into clip_part) -> tower dgrad -> the resize's gather-form
+        adjoint (cgd_cutouts_resize_bwd) into gclip.  _clip_leg_resized_torch is the same leg in torch ops with autograd."""
+        ctx, lib = self.ctx, self.ctx.lib
+        B, _, H, W = x_in.shape
+        dev = x_in.device
+        s = ctx.stream()
+        N = cutn * B
+        geo_p, flags_p = table.data_ptr(), table.data_ptr() + 16 * cutn
+        scratch = self._b("resize_scratch", (max(1, lib.cgd_cutouts_resize_scratch_floats(B, H, W, cutn)),), dev)
+        acc = accumulate
+        for k, (tower, targets) in enumerate(zip(self.towers, self.targets_list)):
+            cs, patch = tower.input_resolution, tower.patch
+            if patch:
+                gsz = cs // patch
+                clip_in = self._b(f"patches{k}", (N * gsz * gsz, 3 * patch * patch), dev)
+                layout = 1
+            else:
+                clip_in = self._b(f"cut_images{k}", (N, 3, cs, cs), dev)
+                layout = 0
+            ctx.check(lib.cgd_cutouts_resize_fwd(ctx.h, x_in.data_ptr(), geo_p, flags_p, clip_in.data_ptr(), B, H, W, cutn, cs, layout, patch, s))
+            emb = tower.encode_image(clip_in, layout=layout, n=N, out=self._b(f"emb{k}", (N, tower.out_dim), dev))
+            demb = self._b(f"demb{k}", (N, tower.out_dim), dev)
+            ctx.check(lib.cgd_spherical_loss(ctx.h, emb.data_ptr(), targets.data_ptr(), wm.data_ptr(), demb.data_ptr(),
+                                             clip_part[k * N:].data_ptr(), cutn, B, targets.shape[0], tower.out_dim, self.cgs, s))
+            dclip_in = tower.dgrad(demb, self._b(f"dclip_in{k}", tuple(clip_in.shape), dev))
+            ctx.check(lib.cgd_cutouts_resize_bwd(ctx.h, dclip_in.data_ptr(), geo_p, flags_p, gclip.data_ptr(), scratch.data_ptr(), B, H, W,
+                                                 cutn, cs, layout, patch, acc, s))
+            acc = 1
+            if k == 0:
+                self.emb = emb
+
+    def _clip_leg_resized_torch(self, x_in, records, wm, gclip, clip_part, accumulate):
+        """The torch restatement of _clip_leg_resized (the equivalence reference of the tests): crop / resize / normalise in torch
+        (MakeCutoutsResized.resized), the CLIP tower as the autograd node over cgd_*_forward / _dgrad."""
+        from .nets import EncodeImageFunction
+        B = x_in.shape[0]
+        mean = th.tensor(CLIP_MEAN, device=x_in.device).view(1, 3, 1, 1)
+        std = th.tensor(CLIP_STD, device=x_in.device).view(1, 3, 1, 1)
+        n = len(records)
+        with th.enable_grad():
+            xr = x_in.detach().requires_grad_()
+            total = 0
+            for tower, targets in zip(self.towers, self.targets_list):
+                cut = self.make_cutouts.resized(xr.add(1).div(2), records, tower.input_resolution)
+                emb = EncodeImageFunction.apply(((cut - mean) / std).contiguous(), tower).view(n, B, 1, -1)
+                en = F.normalize(emb, dim=-1)
+                d = (en - targets.view(1, 1, -1, targets.shape[-1])).norm(dim=-1).div(2).arcsin().pow(2).mul(2)  # (n, B, P)
+                total = total + (d * wm.view(1, B, -1)).sum(2).mean(0).sum() * self.cgs
+                if tower is self.towers[0]:
+                    self.emb = emb.detach().view(n * B, -1)
+            g_in, = th.autograd.grad(total, xr)
+        if accumulate:
+            gclip.add_(g_in)
+        else:
+            gclip.copy_(g_in)
+        clip_part.zero_()
+        clip_part[0] = total.detach()
 
     def _clip_leg_with_augs(self, x_in, coords, wm, gclip, clip_part, accumulate):
         """`use_augs=True`: the augmentations sit between the crop and the pool.  Per tower, in tower order, with fresh parameter

@@ -155,6 +155,10 @@ _SIGS = {
     "cgd_cutouts_aug_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_cutouts_aug_scratch_floats": (i64, [i32, i32, i32, i32]),
     "cgd_op_aug_sample_map": (i32, [vp, i32, i32, vp, vp, vp]),
+    "cgd_cutouts_resize_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "cgd_cutouts_resize_bwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "cgd_cutouts_resize_scratch_floats": (i64, [i32, i32, i32, i32]),
+    "cgd_cutouts_resize_weights": (i32, [i32, i32, vp, vp, C.POINTER(i32)]),
     "cgd_spherical_loss": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
     "cgd_pmv_blend": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), vp]),
     "cgd_guidance_part_blocks": (i32, [i32, i32, i32]),

@@ -260,6 +260,29 @@ int64_t cgd_cutouts_aug_scratch_floats(int B, int H, int W, int cutn); /* host-o
  * weights persp_w[4p..4p+3] (0 for a fill tap), whatever the record's flags say */
 int cgd_op_aug_sample_map(const float* params, int h, int w, int32_t* affine_src, int32_t* persp_idx, float* persp_w);
 
+/* ---- resized cutouts (the overview + inner cut scheme of the CLIP-guided-diffusion notebooks): per cutout k and sample b, in [0,1] space,
+ *      z = (x_in[b, :, oy:oy+h, ox:ox+w] + 1) / 2; z = 3-channel grayscale(z) if flags[k] & 1 (ITU-R 601-2 luma, as the augmented cutouts);
+ *      r = Wy z Wx^T per channel; r = flip along W (r) if flags[k] & 2; out = (r - mean) / std, layouts as cgd_cutouts_fwd.
+ *      W (m x n, m = cut_size, n = the crop's extent along the axis, s = m / n) is ResizeRight's antialiased cubic resize with zero padding:
+ *      centre c_o = ((2o+1) n - m) / (2m); k(d) = cubic(d), support S = 4 for s >= 1, k(d) = s cubic(s d), S = 4n / m for s < 1;
+ *      T = ceil(S) taps j = left_o .. left_o + T - 1, left_o = ceil(c_o - S / 2); w_oj = k(c_o - j) / sum of k over all T taps (a zero
+ *      sum divides by 1).  Taps outside [0, n) read zero (black in [0,1] space), whatever the image holds beyond the box, and the weights
+ *      are not renormalised over the taps inside: rows at the box border sum to less than 1.  m == n is the identity.  left_o, T and the tap
+ *      distances are integer arithmetic, the cubic polynomial float32.
+ *      coords as above, every box with h, w >= 1 inside the image (the table lives on the device: callers check it before the upload; a
+ *      box that is not reads nothing, gives a NaN row and no gradient); flags: device int32 [cutn].  Host-checkable arguments (sizes,
+ *      cut_size not a multiple of patch in layout 1, an image whose weight rows do not fit the LDS) fail with -2 before any launch.
+ *      The adjoint is deterministic (gather form, no atomics) and needs `scratch` of cgd_cutouts_resize_scratch_floats(B, H, W, cutn)
+ *      floats; accumulate as in cgd_cutouts_bwd. ---- */
+int cgd_cutouts_resize_fwd(cgd_ctx* ctx, const float* x_in, const int32_t* coords, const int32_t* flags, float* out, int B, int H, int W,
+                           int cutn, int cut_size, int layout, int patch, void* stream);
+int cgd_cutouts_resize_bwd(cgd_ctx* ctx, const float* d_out, const int32_t* coords, const int32_t* flags, float* g_in, float* scratch, int B,
+                           int H, int W, int cutn, int cut_size, int layout, int patch, int accumulate, void* stream);
+int64_t cgd_cutouts_resize_scratch_floats(int B, int H, int W, int cutn); /* host-only */
+/* host-only, test support: the weights of an n -> m resize from the routine the kernels run: *taps = T; w [m][T] and left [m] when both are
+ * given (both NULL: only *taps, to size them) */
+int cgd_cutouts_resize_weights(int n, int m, float* w, int32_t* left, int* taps);
+
 /* ---- losses.spherical_dist_loss (cgd/losses.py:10-14) weighted as at cgd.py:196-204, with its gradient.
  *      emb (cutn*B, D) row = cut*B+b; targets_n (P, D) L2-normalised; weights (B, P) dense per-sample prompt
  *      weights; d_emb (cutn*B, D); loss_part (cutn*B) partial losses (sum = 'CLIP Loss'). ---- */

@@ -36,9 +36,10 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         raise ValueError(f"device {device!r}: this build runs the sampling step on an MI355X only (PyTorch-ROCm reports 'cuda')")
     if init_image and script_util.split_init_invert(script_util.split_init_mask(init_image)[0])[1]:
         # refused before anything is loaded
-        if not str(timestep_respacing).startswith(("ddim", "plms")):  # the inverted latent is a start state of the deterministic loops only
-            raise ValueError(f"init image 'invert=...' needs a deterministic sampler: timestep_respacing must start with 'ddim' or 'plms', "
-                             f"got {timestep_respacing!r}")
+        # the inverted latent is a start state of the deterministic loops only ('dpmsdeN' draws a noise per step; tested before 'dpm')
+        if str(timestep_respacing).startswith("dpmsde") or not str(timestep_respacing).startswith(("ddim", "plms", "dpm")):
+            raise ValueError(f"init image 'invert=...' needs a deterministic sampler: timestep_respacing must start with 'ddim' or 'plms' "
+                             f"(or 'dpm', but not 'dpmsde'), got {timestep_respacing!r}")
         if height_offset or width_offset:  # the init image is image_size x image_size, and so is the latent inverted from it
             raise ValueError(f"init image 'invert=...' needs height_offset = width_offset = 0, got {height_offset} and {width_offset}: the "
                              "inverted latent has the init image's size")
@@ -160,6 +161,11 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
     # "plmsN" (PLMS of order 2, spaced like "ddimN") extends what the reference accepts, like the "A+B" CLIP names
     if timestep_respacing.startswith("plms"):
         loop = functools.partial(diffusion.plms_sample_loop_progressive, order=2)
+    # "dpmN" / "dpmsdeN" (likewise): DPM-Solver++(2M), deterministic / SDE, on at most N levels uniform in logSNR
+    elif timestep_respacing.startswith("dpmsde"):
+        loop = functools.partial(diffusion.dpmpp_sample_loop_progressive, order=2, eta=1.0)
+    elif timestep_respacing.startswith("dpm"):
+        loop = functools.partial(diffusion.dpmpp_sample_loop_progressive, order=2, eta=0.0)
     else:
         loop = diffusion.ddim_sample_loop_progressive if timestep_respacing.startswith("ddim") else diffusion.p_sample_loop_progressive
     try:
@@ -230,7 +236,7 @@ _CLI_SPEC = f"""
 --prompts -txts str "" | text prompts with optional weights, pipe-separated: 'a cat:0.5|a dog:-0.5'
 --image_prompts -imgs str "" | image prompts (paths or URLs) with optional weights, pipe-separated
 --image_size -size int 128 | resolution of the diffusion checkpoint: 64, 128, 256 or 512
---init_image -init str "" | start from this image (needs --skip_timesteps); IMAGE::MASK regenerates the white part of MASK and keeps the black part of IMAGE; invert=IMAGE (or invert=IMAGE::MASK, with -respace ddimN / plmsN) starts from the DDIM-inverted latent of IMAGE
+--init_image -init str "" | start from this image (needs --skip_timesteps); IMAGE::MASK regenerates the white part of MASK and keeps the black part of IMAGE; invert=IMAGE (or invert=IMAGE::MASK, with -respace ddimN / plmsN / dpmN) starts from the DDIM-inverted latent of IMAGE
 --init_scale -is int 0 | weight of the LPIPS-VGG16 term that keeps the sample close to the init image
 --skip_timesteps -skip int 0 | how many of the (respaced) timesteps to skip at the noisy end
 --prefix -dir path outputs | directory for the PNG frames
@@ -243,7 +249,7 @@ _CLI_SPEC = f"""
 --seed -seed int 0 | RNG seed
 --save_frequency -freq int 1 | write a frame every N steps
 --diffusion_steps -steps int 1000 | length of the training schedule
---timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', or 'plmsN' for PLMS (e.g. -respace plms50)
+--timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', 'plmsN' for PLMS (e.g. -respace plms50), or 'dpmN' / 'dpmsdeN' for DPM-Solver++(2M) / its SDE form on at most N logSNR-uniform levels (e.g. -respace dpm20)
 --num_cutouts -cutn int 16 | random cutouts shown to CLIP per step
 --cutout_power -cutpow float 1.0 | exponent of the cutout size distribution
 --clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, ARCH=FILE for an open_clip ViT checkpoint (ARCH: ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14, optional -quickgelu suffix), 'A+B' to sum two towers, 'A+secondary=FILE' to guide through the secondary model FILE, or 'A+cuts=OV:IN' (or 'cuts=OV:IN/OV2:IN2': the second pair once 40 percent of the run is done) for OV whole-frame and IN random cutouts per step through the antialiased cubic resize (--num_cutouts then only affects image prompts)

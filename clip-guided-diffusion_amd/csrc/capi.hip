@@ -283,6 +283,13 @@ int cgd_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eval, cons
   return cgd_launch_multistep_update(ctx, x, x_eval, x0, g, scalars, noise, eps_hist, eps_out, sample, x0_out, B, H, W, *k, k_step, *m,
                                      S(stream));
 }
+int cgd_dpmpp_update(cgd_ctx* ctx, const float* x, const float* x0, const float* g, const float* scalars, const float* noise,
+                     const float* x0_hist, float* x0c_out, float* sample, float* x0_out, int B, int H, int W, const cgd_step_coef* k,
+                     const cgd_dpmpp* d, void* stream) {
+  CGD_NEED_CTX(ctx);
+  if (!k || !d) return -3;
+  return cgd_launch_dpmpp_update(ctx, x, x0, g, scalars, noise, x0_hist, x0c_out, sample, x0_out, B, H, W, *k, *d, S(stream));
+}
 int cgd_masked_merge(cgd_ctx* ctx, float* sample, float* x0, const float* init, const float* mask, const float* n_known, const float* n_re,
                      float* x_re, int B, int H, int W, int init_batch, int mask_batch, int mask_channels, const cgd_mask_coef* k,
                      void* stream) {

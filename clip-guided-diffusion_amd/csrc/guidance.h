@@ -5,6 +5,15 @@
 
 typedef cgd_step_coef StepCoef;
 
+// The guided pred_xstart of one evaluation at (xv, k), condition_score_with_grad: eps of the model's prediction x0v, shifted by the guidance
+// gradient gv (already scaled by the magnitude clamp), and the pred_xstart that eps implies.  Shared by the multistep update (plms.hip) and
+// the DPM-Solver++ update (dpm.hip); the same lines as mode 1 of sample_update_kernel (guidance.hip).
+__device__ __forceinline__ float guided_x0(const StepCoef& k, float xv, float x0v, float gv) {
+  float e = (k.sqrt_recip * xv - x0v) / k.sqrt_recipm1;
+  e -= k.sqrt_one_minus_ab * gv;
+  return k.sqrt_recip * xv - k.sqrt_recipm1 * e;
+}
+
 int cgd_launch_pmv_blend(cgd_ctx* ctx, const float* x, const float* out6, float* x0, float* mean, float* logvar, float* xin, int B,
                          int H, int W, const StepCoef& k, hipStream_t s);
 int cgd_launch_guidance_combine(cgd_ctx* ctx, const float* gclip, const float* xin, const float* x0, float* gdir, float* seed6,
@@ -21,3 +30,7 @@ int cgd_launch_sample_update(cgd_ctx* ctx, const float* x, const float* x0, cons
 int cgd_launch_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eval, const float* x0, const float* g, const float* scalars,
                                 const float* noise, const float* const* eps_hist, float* eps_out, float* sample, float* x0_out, int B,
                                 int H, int W, const StepCoef& k, const StepCoef* k_step, const cgd_multistep& m, hipStream_t s);
+// dpm.hip
+int cgd_launch_dpmpp_update(cgd_ctx* ctx, const float* x, const float* x0, const float* g, const float* scalars, const float* noise,
+                            const float* x0_hist, float* x0c_out, float* sample, float* x0_out, int B, int H, int W, const StepCoef& k,
+                            const cgd_dpmpp& d, hipStream_t s);

@@ -29,9 +29,7 @@ __global__ __launch_bounds__(256) void multistep_update_kernel(const float* __re
     // guided eps of the evaluation at (xe, k): exactly the arithmetic of sample_update_kernel mode 1
     const float xv = xe[i], x0v = x0[i];
     const float gv = g ? g[i] * fct : 0.f;
-    float e = (k.sqrt_recip * xv - x0v) / k.sqrt_recipm1;
-    e -= k.sqrt_one_minus_ab * gv;
-    const float x0c = k.sqrt_recip * xv - k.sqrt_recipm1 * e;
+    const float x0c = guided_x0(k, xv, x0v, gv);
     const float eps = (k.sqrt_recip * xv - x0c) / k.sqrt_recipm1;
     if (phase == 3) {
       const float s = x0c * k.sqrt_ab_prev + dir * eps;

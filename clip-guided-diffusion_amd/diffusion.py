@@ -24,10 +24,27 @@ def named_beta_schedule(name, steps):
     raise NotImplementedError(f"unknown beta schedule: {name}")
 
 
-def space_timesteps(num_timesteps, spec):
-    """'ddimN' (and 'plmsN', spaced the same way) -> fixed integer stride with exactly N steps; 'a,b,c' -> per-section even
-    spacing (rounded)."""
+def logsnr_timesteps(betas, count):
+    """The timesteps of 'dpmN': `count` targets uniform in lambda = log(alpha / sigma) = 0.5 log(abar / (1 - abar)) between the two ends of
+    the base schedule, each replaced by the nearest timestep (ties go to the lower one).  The distinct picks are kept: always 0 and
+    T - 1, and fewer than `count` where the schedule is coarser in lambda than the targets (49 of 50 on the linear schedule of 1000)."""
+    if count < 2:
+        raise ValueError(f"a logSNR-uniform spacing needs at least 2 levels (the two ends of the schedule), got {count}")
+    ab = np.cumprod(1.0 - np.asarray(betas, dtype=np.float64))
+    lam = 0.5 * np.log(ab / (1.0 - ab))
+    return {int(np.argmin(np.abs(lam - target))) for target in np.linspace(lam[0], lam[-1], count)}
+
+
+def space_timesteps(num_timesteps, spec, betas=None):
+    """'ddimN' (and 'plmsN', spaced the same way) -> fixed integer stride with exactly N steps; 'dpmN' / 'dpmsdeN' -> at most N timesteps
+    uniform in logSNR (logsnr_timesteps; needs the base schedule `betas`); 'a,b,c' -> per-section even spacing (rounded)."""
     if isinstance(spec, str):
+        if spec.startswith("dpm"):
+            if betas is None:
+                raise ValueError(f"timestep spacing {spec!r} is uniform in logSNR and needs the base schedule: pass betas=")
+            if len(betas) != num_timesteps:
+                raise ValueError(f"betas has {len(betas)} entries for {num_timesteps} timesteps")
+            return logsnr_timesteps(betas, int(spec[6 if spec.startswith("dpmsde") else 3:]))
         if spec.startswith(("ddim", "plms")):
             want = int(spec[4:])
             for stride in range(1, num_timesteps):
@@ -107,6 +124,40 @@ class SpacedDiffusion:
         k.nonzero = int(i != 0)
         return k
 
+    def dpmpp_coef_f64(self, i, order, eta=0.0):
+        """(c_x, c_d, c_r, c_n) of the DPM-Solver++ step from level i to level i - 1 (Lu et al., 2022; data prediction, multistep), float64:
+            sample = c_x x + c_d D + c_n noise,  D = x0c + c_r (x0c - x0c of the step before)
+        with alpha = sqrt(abar), sigma = sqrt(1 - abar), lambda = log(alpha / sigma), 'prev' = level i - 1, h = lambda_prev - lambda_i:
+            c_x = sigma_prev / sigma_i e^(-eta h),  c_d = -alpha_prev expm1(-(1 + eta) h),  c_n = sigma_prev sqrt(-expm1(-2 eta h)),
+            c_r = h / (2 h_last), h_last = lambda_i - lambda_(i+1), for order 2; 0 for order 1.
+        eta = 0 is the deterministic solver (order 1: DDIM), eta = 1 the SDE solver (order 1: DDIM with eta = 1).  At i = 0 the step ends
+        at the clean image, h is infinite and the values are their limits: c_x = 0, c_d = 1, c_n = c_r = 0 (lower order final)."""
+        if order not in (1, 2):
+            raise ValueError(f"order must be 1 or 2, got {order!r}")
+        if not eta >= 0.0:
+            raise ValueError(f"eta must be >= 0, got {eta}")
+        if i == 0:
+            return 0.0, 1.0, 0.0, 0.0
+        ab, abp = self.alphas_cumprod[i], self.alphas_cumprod_prev[i]
+
+        def lam(v):
+            return 0.5 * math.log(v / (1.0 - v))
+
+        h = lam(abp) - lam(ab)
+        c_r = 0.0
+        if order == 2:
+            if i + 1 >= self.num_timesteps:
+                raise ValueError("a second-order step needs the step before it: the first index of the schedule has none")
+            c_r = h / (2.0 * (lam(ab) - lam(self.alphas_cumprod[i + 1])))
+        return (math.sqrt((1.0 - abp) / (1.0 - ab)) * math.exp(-eta * h), -math.sqrt(abp) * math.expm1(-(1.0 + eta) * h), c_r,
+                math.sqrt(1.0 - abp) * math.sqrt(-math.expm1(-2.0 * eta * h)) if eta else 0.0)
+
+    def dpmpp_coef(self, i, order, eta=0.0):
+        """dpmpp_coef_f64 as the cgd_dpmpp struct of cgd_dpmpp_update (csrc/dpm.hip)."""
+        k = L.Dpmpp()
+        k.c_x, k.c_d, k.c_r, k.c_n = self.dpmpp_coef_f64(i, order, eta)
+        return k
+
     def mask_coef(self, i):
         """Coefficients of the masked-sampling merge after the update of step index i (sampler.py, csrc/mask.hip): the known region
         lives at level i - 1, known = sqrt(abar_prev) init + sqrt(1 - abar_prev) noise (the init image itself at i = 0), and a
@@ -139,4 +190,4 @@ def create_gaussian_diffusion(steps=1000, noise_schedule="linear", timestep_resp
     betas = named_beta_schedule(noise_schedule, steps)
     if not timestep_respacing:
         timestep_respacing = [steps]
-    return SpacedDiffusion(space_timesteps(steps, timestep_respacing), betas, rescale_timesteps=rescale_timesteps)
+    return SpacedDiffusion(space_timesteps(steps, timestep_respacing, betas=betas), betas, rescale_timesteps=rescale_timesteps)

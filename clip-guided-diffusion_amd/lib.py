@@ -65,6 +65,11 @@ class ReverseCoef(C.Structure):
                 ("inv_sqrt_one_minus_ab_next", f32)]
 
 
+class Dpmpp(C.Structure):
+    """cgd_dpmpp: coefficients of cgd_dpmpp_update, the DPM-Solver++ step from level i to level i - 1 (diffusion.dpmpp_coef)"""
+    _fields_ = [("c_x", f32), ("c_d", f32), ("c_r", f32), ("c_n", f32)]
+
+
 MANIFEST_CB = C.CFUNCTYPE(None, C.c_char_p, i64, vp)
 
 # name -> (restype, argtypes).  Pointers to device memory are passed as integers (tensor.data_ptr()).
@@ -168,6 +173,7 @@ _SIGS = {
     "cgd_sample_update": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), i32, vp]),
     "cgd_multistep_update": (i32, [vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef),
                                     C.POINTER(StepCoef), C.POINTER(Multistep), vp]),
+    "cgd_dpmpp_update": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), C.POINTER(Dpmpp), vp]),
     "cgd_masked_merge": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(MaskCoef), vp]),
     "cgd_ddim_reverse_update": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(ReverseCoef), vp]),
     "cgd_op_gemm": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp]),

@@ -11,6 +11,9 @@ it with one cgd_multistep_update launch per evaluation; PLMS draws no per-step n
 Masked sampling (`mask=`, with an init image: 1 regenerates, 0 keeps) adds one cgd_masked_merge launch after every update, which puts the
 init image, noised to the level the update produced, back into the kept region; `resamples=r` repeats every step r times (RePaint with
 jump length 1).  Without a mask nothing of it runs.
+DPM-Solver++(2M) (`dpmpp_sample_loop_progressive`, Lu et al., 2022; eta = 0 the ODE solver, eta > 0 the SDE solver) runs on the levels of
+'dpmN' (uniform in logSNR, diffusion.logsnr_timesteps): one guided evaluation per step and one cgd_dpmpp_update launch, which combines the
+evaluation's guided pred_xstart with the one of the step before; the two history buffers rotate by pointer.
 DDIM inversion (`ddim_reverse_sample_loop_progressive`, `ddim_invert`; guided_diffusion's ddim_reverse_sample) runs the deterministic DDIM ODE
 upwards from an image: per step one UNet forward and one cgd_ddim_reverse_update launch.  `ddim_invert` returns the latent and the noise that
 q_samples the image to it, so every loop above starts from the latent when called with `noise=noise, init_image=image, skip_timesteps=s`.
@@ -309,6 +312,33 @@ class GuidedSampler:
             self._merge(masked, i, sample, x0_out, masked["x_T"])
         return {"sample": sample, "pred_xstart": x0_out}
 
+    def _dpmpp_step(self, model, x, i, cond_fn, model_kwargs, noise, bufs, st, ahead=None, eta=0.0, masked=None):
+        """One DPM-Solver++(2M) step.  `st`: {'order', 'hist': the guided pred_xstart of the step before (None on the first step, which
+        therefore runs at order 1), 'free': the spare buffer}.  The history rotates by pointer: the entry the launch has read is the
+        buffer the next launch writes.  Step index 0 runs at order 1 (diffusion.dpmpp_coef) and nothing reads the entry of step
+        index 1 or 0, so those are not written.  `masked`: the result is merged after the update; the history stays as evaluated."""
+        ctx, lib = self.ctx, self.ctx.lib
+        B, _, H, W = x.shape
+        n_known = self._known_noise(masked, x) if masked is not None else None
+        ev = self._evaluate(model, x, i, cond_fn, model_kwargs, noise, bufs, ahead, draw_noise=bool(eta),
+                            draw_known=masked is not None and n_known is None)
+        noise, g, hist = ev["noise"], ev["g"], st["hist"]
+        d = self.tables.dpmpp_coef(i, 2 if (st["order"] == 2 and hist is not None) else 1, eta)
+        x0c = None
+        if st["order"] == 2 and i > 1:
+            x0c = st["free"].pop() if st["free"] else th.empty_like(x)
+        sample, x0_out = th.empty_like(x), th.empty_like(x)
+        ctx.check(lib.cgd_dpmpp_update(ctx.h, x.data_ptr(), ev["x0"].data_ptr(), L.ptr(g), L.ptr(ev["scal"]), L.ptr(noise),
+                                       L.ptr(hist) if d.c_r else None, L.ptr(x0c), sample.data_ptr(), x0_out.data_ptr(), B, H, W,
+                                       ev["coef"], d, ctx.stream()))
+        if hist is not None:
+            st["free"].append(hist)
+        st["hist"] = x0c
+        bufs["_keep"] = (noise, g, ev["ts"])
+        if masked is not None:
+            self._merge(masked, i, sample, x0_out, n_known if n_known is not None else ev["n_known"])
+        return {"sample": sample, "pred_xstart": x0_out}
+
     # ---- loops ------------------------------------------------------------------------------------------
     @staticmethod
     def _check_guards(clip_denoised, cond_fn, cond_fn_with_grad):
@@ -318,9 +348,10 @@ class GuidedSampler:
             raise NotImplementedError("the reference passes cond_fn_with_grad=True (cgd.py:260)")
 
     def _loop(self, mode, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-              randomize_class, cond_fn_with_grad, eta=0.0, plms_order=None, mask=None, resamples=1):
-        """mode 0 p_sample, 1 DDIM (eta > 0: stochastic DDIM), 2 PLMS of order `plms_order` (no per-step noise).  `mask` (with
-        `init_image`): masked sampling, every step index > 0 `resamples` times."""
+              randomize_class, cond_fn_with_grad, eta=0.0, plms_order=None, mask=None, resamples=1, dpm_order=None):
+        """mode 0 p_sample, 1 DDIM (eta > 0: stochastic DDIM), 2 PLMS of order `plms_order` (no per-step noise), 3 DPM-Solver++(2M) of
+        order `dpm_order` (eta > 0: the SDE solver, with a per-step noise).  `mask` (with `init_image`): masked sampling, every step
+        index > 0 `resamples` times."""
         self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
         device = th.device(device or f"cuda:{self.ctx.device}")
         tape = self.tape
@@ -340,7 +371,7 @@ class GuidedSampler:
         if mask is not None:
             # 'stochastic': the kept region gets a fresh noise per merge; otherwise it keeps the loop's initial noise, img as it is here
             masked = {"init": init_image.to(device).float().contiguous(), "mask": mask.to(device).float().contiguous(),
-                      "x_T": img.contiguous(), "stochastic": mode == 0 or (mode == 1 and bool(eta)), "known": 0, "re": 0}
+                      "x_T": img.contiguous(), "stochastic": mode == 0 or (mode in (1, 3) and bool(eta)), "known": 0, "re": 0}
         indices = list(range(self.num_timesteps - skip_timesteps))[::-1]
         if init_image is not None:
             t0 = indices[0]
@@ -369,6 +400,7 @@ class GuidedSampler:
         ahead = EmbedAhead.create(self, model, cond_fn, img, indices) if (mode != 2 and resamples == 1) else None
         evals = 0  # evaluations of the p_sample / DDIM loops so far: the tape's step noise is consumed per evaluation
         plms = {"order": plms_order, "old_eps": [], "free": []} if mode == 2 else None
+        dpm = {"order": dpm_order, "hist": None, "free": []} if mode == 3 else None
         for n, i in enumerate(it):
             if rand_y and (ahead is None or n == 0):
                 draw_y.n = n
@@ -385,6 +417,15 @@ class GuidedSampler:
             # up one level (bufs['_x_re'], written by the merge's launch) and the step runs again.  One yield per step index.
             repeats = resamples if (masked is not None and i > 0) else 1
             for r in range(repeats):
+                if dpm is not None:
+                    # one evaluation per step (resamples is 1); the tape's step noise is read only where a noise is drawn (eta > 0)
+                    step_noise = tape["noise"][evals].to(device).float().contiguous() if (tape is not None and eta) else None
+                    evals += 1
+                    with th.no_grad():
+                        out = self._dpmpp_step(model, img, i, cond_fn, model_kwargs, step_noise, bufs, dpm,
+                                               *((ahead,) if ahead is not None else ()), **({"eta": eta} if eta else {}),
+                                               **({"masked": masked} if masked is not None else {}))
+                    continue
                 step_noise = tape["noise"][evals].to(device).float().contiguous() if tape is not None else None
                 evals += 1
                 with th.no_grad():
@@ -444,6 +485,28 @@ class GuidedSampler:
         self._check_mask(shape, init_image, mask, resamples, plms=True)
         return self._loop(2, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
                           randomize_class, cond_fn_with_grad, plms_order=order, mask=mask)
+
+    def dpmpp_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
+                                      model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
+                                      randomize_class=False, cond_fn_with_grad=False, order=2, eta=0.0, mask=None, resamples=1):
+        """DPM-Solver++(2M) (Lu et al., 2022: data prediction, multistep): one guided evaluation per step; the update extrapolates the guided
+        pred_xstart with the one of the step before (`order` 2; the first step and step index 0 run at order 1; `order` 1 is DDIM with the
+        same eta for eta in {0, 1}).  eta == 0: the deterministic solver, no per-step noise.  eta > 0: the SDE solver (eta = 1 is
+        SDE-DPM-Solver++(2M)), one noise draw per evaluation before cond_fn, as in DDIM with eta.  Meant for tables spaced uniformly in
+        logSNR (timestep_respacing 'dpmN'); on the integer-stride levels of 'ddimN' the second order gains nothing below about 50 steps
+        (DESIGN.md).  `mask`: masked sampling as in ddim_sample_loop_progressive (eta == 0: the kept region is noised with the loop's
+        initial noise); `resamples` > 1 is refused: a resampled history would mix noise levels."""
+        if isinstance(order, bool) or not isinstance(order, int) or order not in (1, 2):
+            raise ValueError(f"order is invalid (should be 1 or 2): {order!r}")
+        if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not eta >= 0.0:
+            raise ValueError(f"eta must be a number >= 0, got {eta!r}")
+        self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
+        if isinstance(resamples, int) and not isinstance(resamples, bool) and resamples > 1:
+            raise ValueError("DPM-Solver++ cannot resample: its pred_xstart history would mix noise levels (use the DDIM loop, "
+                             "ddim_sample_loop_progressive, for resamples > 1)")
+        self._check_mask(shape, init_image, mask, resamples)
+        return self._loop(3, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
+                          randomize_class, cond_fn_with_grad, eta=float(eta), mask=mask, dpm_order=order)
 
     # ---- DDIM inversion ---------------------------------------------------------------------------------
     def ddim_reverse_sample_loop_progressive(self, model, image, clip_denoised=False, model_kwargs=None, device=None, progress=False,

@@ -350,6 +350,33 @@ int cgd_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eval, cons
                          float* pred_xstart_out, int B, int H, int W, const cgd_step_coef* k, const cgd_step_coef* k_step,
                          const cgd_multistep* m, void* stream);
 
+/* ---- DPM-Solver++(2M) (Lu et al., 2022: data prediction, multistep; deterministic and SDE): the whole update after one guided evaluation
+ *      at (x, k), from level t to level t-1, in one launch.  With x0c the guided pred_xstart exactly as in cgd_multistep_update,
+ *        eps0 = (a x - pred_xstart) / b ; eps1 = eps0 - sqrt(1-abar) g ; x0c = a x - b eps1
+ *      (a = sqrt_recip, b = sqrt_recipm1 of k; g scaled by scalars[7] when scalars is given; g may be NULL):
+ *        D               = c_r != 0 ? x0c + c_r (x0c - x0_hist) : x0c          (x0_hist: the x0c_out of the step before)
+ *        sample          = t != 0 ? c_x x + c_d D (+ c_n noise when c_n != 0) : x0c     (a select: nothing is multiplied at the clean end)
+ *        x0c_out         = x0c                                                 (the next step's x0_hist)
+ *        pred_xstart_out = pred_xstart                                         (the unconditioned prediction)
+ *      alpha = sqrt(abar), sigma = sqrt(1-abar), lambda = log(alpha / sigma), h = lambda_{t-1} - lambda_t, eta = 0 (ODE) or > 0 (SDE):
+ *        c_x = sigma_{t-1} / sigma_t e^(-eta h) ; c_d = -alpha_{t-1} expm1(-(1 + eta) h) ; c_n = sigma_{t-1} sqrt(-expm1(-2 eta h)) ;
+ *        c_r = h / (2 h_last), h_last = lambda_t - lambda_{t+1}, for a second-order step, 0 for a first-order one
+ *      (first order: DDIM with the same eta for eta in {0, 1}); at t == 0, where h is infinite: c_x = 0, c_d = 1, c_n = c_r = 0.
+ *      x, pred_xstart, g, noise, x0_hist and the outputs: (B,3,H,W).  x, pred_xstart and sample are required; x0c_out and pred_xstart_out
+ *      may be NULL and are then not written; x0_hist is read only when c_r != 0, noise only when c_n != 0 and t != 0.  Any
+ *      4-byte-aligned pointers and any H * W are accepted (16-byte accesses when every pointer is 16-byte aligned and 4 | H * W).
+ *      Returns -2 (cgd_last_error), before any launch, for a non-positive size, a missing required buffer, c_r != 0 without x0_hist,
+ *      c_n != 0 at t != 0 without noise, or an output that aliases x or another output. ---- */
+typedef struct cgd_dpmpp {
+  float c_x; /* coefficient of x                                                         */
+  float c_d; /* coefficient of D, the (extrapolated) guided pred_xstart                  */
+  float c_r; /* second order: h / (2 h_last), the weight of x0c - x0_hist in D; else 0   */
+  float c_n; /* SDE: coefficient of the step noise; 0 for the deterministic solver       */
+} cgd_dpmpp;
+int cgd_dpmpp_update(cgd_ctx* ctx, const float* x, const float* pred_xstart, const float* g, const float* scalars, const float* noise,
+                     const float* x0_hist, float* x0c_out, float* sample, float* pred_xstart_out, int B, int H, int W,
+                     const cgd_step_coef* k, const cgd_dpmpp* d, void* stream);
+
 /* ---- masked sampling (inpainting / outpainting of an init image): the merge after a sampler update at step index t, in one launch.
  *      The update left `sample` (the state at level t-1) and `pred_xstart`; with m = mask (1 regenerate, 0 keep the init image):
  *        known       = sqrt(abar_prev) init + sqrt(1 - abar_prev) n_known   (two rounded products and a rounded sum, not fused)

@@ -34,6 +34,9 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         print(f"device: {device}")
     if "cuda" not in device:
         raise ValueError(f"device {device!r}: this build runs the sampling step on an MI355X only (PyTorch-ROCm reports 'cuda')")
+    # "dpmN+thr=P[:CAP]" (an extension like "plmsN"): dynamic thresholding of the guided pred_xstart; refused on any other spacing, before
+    # anything is loaded.  The tables are built from the spacing without the suffix
+    timestep_respacing, threshold = script_util.split_threshold(timestep_respacing)
     if init_image and script_util.split_init_invert(script_util.split_init_mask(init_image)[0])[1]:
         # refused before anything is loaded
         # the inverted latent is a start state of the deterministic loops only ('dpmsdeN' draws a noise per step; tested before 'dpm')
@@ -168,6 +171,8 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         loop = functools.partial(diffusion.dpmpp_sample_loop_progressive, order=2, eta=0.0)
     else:
         loop = diffusion.ddim_sample_loop_progressive if timestep_respacing.startswith("ddim") else diffusion.p_sample_loop_progressive
+    if threshold is not None:  # only with 'dpmN' / 'dpmsdeN' (split_threshold)
+        loop = functools.partial(loop, threshold=threshold[0] if threshold[1] is None else threshold)
     try:
         samples = loop(gd_model, (local_batch, 3, image_size + height_offset, image_size + width_offset), clip_denoised=False,
                        model_kwargs=model_kwargs, cond_fn=cond_fn, progress=progress, skip_timesteps=skip_timesteps, init_image=init_tensor,
@@ -249,7 +254,7 @@ _CLI_SPEC = f"""
 --seed -seed int 0 | RNG seed
 --save_frequency -freq int 1 | write a frame every N steps
 --diffusion_steps -steps int 1000 | length of the training schedule
---timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', 'plmsN' for PLMS (e.g. -respace plms50), or 'dpmN' / 'dpmsdeN' for DPM-Solver++(2M) / its SDE form on at most N logSNR-uniform levels (e.g. -respace dpm20)
+--timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', 'plmsN' for PLMS (e.g. -respace plms50), or 'dpmN' / 'dpmsdeN' for DPM-Solver++(2M) / its SDE form on at most N logSNR-uniform levels (e.g. -respace dpm20); 'dpmN+thr=P' or 'dpmsdeN+thr=P:CAP' adds dynamic thresholding of the guided prediction: per sample it is clamped to its own P-quantile of absolute values s (at least 1, at most CAP) and divided by s (e.g. -respace dpm20+thr=0.995; CAP 1 is the static clip to [-1, 1])
 --num_cutouts -cutn int 16 | random cutouts shown to CLIP per step
 --cutout_power -cutpow float 1.0 | exponent of the cutout size distribution
 --clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, ARCH=FILE for an open_clip ViT checkpoint (ARCH: ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14, optional -quickgelu suffix), 'A+B' to sum two towers, 'A+secondary=FILE' to guide through the secondary model FILE, or 'A+cuts=OV:IN' (or 'cuts=OV:IN/OV2:IN2': the second pair once 40 percent of the run is done) for OV whole-frame and IN random cutouts per step through the antialiased cubic resize (--num_cutouts then only affects image prompts)

@@ -57,6 +57,33 @@ def split_init_mask(value):
     return image, mask
 
 
+THRESHOLD_SEP = "+thr="
+
+
+def split_threshold(respacing):
+    """'dpmN+thr=P' or 'dpmsdeN+thr=P:CAP' -> (the spacing without the suffix, (P, CAP)); CAP is None when not given; a value without
+    '+thr=' -> (value, None).  Dynamic thresholding of the guided pred_xstart (GuidedSampler.dpmpp_sample_loop_progressive, threshold=)
+    rides on --timestep_respacing / timestep_respacing=, and only the DPM-Solver++ spacings 'dpmN' / 'dpmsdeN' take it."""
+    respacing = str(respacing)
+    spec, sep, value = respacing.partition(THRESHOLD_SEP)
+    if not sep:
+        return respacing, None
+    if not spec.startswith("dpm"):
+        raise ValueError(f"timestep_respacing {respacing!r}: '+thr=' needs a DPM-Solver++ spacing, 'dpmN' or 'dpmsdeN'")
+    parts = value.split(":")
+    try:
+        if len(parts) not in (1, 2):
+            raise ValueError(value)
+        p, cap = float(parts[0]), (float(parts[1]) if len(parts) == 2 else None)
+    except ValueError:
+        raise ValueError(f"timestep_respacing {respacing!r}: '+thr=' takes P or P:CAP (e.g. dpmN+thr=0.995 or dpmN+thr=0.995:1.5)") from None
+    if not 0.0 < p <= 1.0:
+        raise ValueError(f"timestep_respacing {respacing!r}: the quantile P of '+thr=' must lie in (0, 1]")
+    if cap is not None and not cap >= 1.0:
+        raise ValueError(f"timestep_respacing {respacing!r}: the CAP of '+thr=' must be >= 1")
+    return spec, (p, cap)
+
+
 INVERT_PREFIX = "invert="
 
 

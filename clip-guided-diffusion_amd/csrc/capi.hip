@@ -290,6 +290,25 @@ int cgd_dpmpp_update(cgd_ctx* ctx, const float* x, const float* x0, const float*
   if (!k || !d) return -3;
   return cgd_launch_dpmpp_update(ctx, x, x0, g, scalars, noise, x0_hist, x0c_out, sample, x0_out, B, H, W, *k, *d, S(stream));
 }
+int cgd_op_abs_quantile(cgd_ctx* ctx, const float* v, int B, int64_t n, int64_t k, float frac, float floor, float cap, float* out3,
+                        void* scratch, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_abs_quantile(ctx, v, B, n, k, frac, floor, cap, out3, scratch, S(stream));
+}
+int cgd_dpmpp_threshold(cgd_ctx* ctx, const float* x, const float* x0, const float* g, const float* scalars, float* x0c, int B, int H, int W,
+                        const cgd_step_coef* k_coef, int64_t k, float frac, float floor, float cap, float* thr3, void* scratch,
+                        void* stream) {
+  CGD_NEED_CTX(ctx);
+  if (!k_coef) return -3;
+  return cgd_launch_dpmpp_threshold(ctx, x, x0, g, scalars, x0c, B, H, W, *k_coef, k, frac, floor, cap, thr3, scratch, S(stream));
+}
+int cgd_dpmpp_update_thr(cgd_ctx* ctx, const float* x, const float* x0, const float* x0c, const float* thr3, const float* noise,
+                         const float* x0_hist, float* x0c_out, float* sample, float* x0_out, int B, int H, int W, const cgd_step_coef* k_coef,
+                         const cgd_dpmpp* d, void* stream) {
+  CGD_NEED_CTX(ctx);
+  if (!k_coef || !d) return -3;
+  return cgd_launch_dpmpp_update_thr(ctx, x, x0, x0c, thr3, noise, x0_hist, x0c_out, sample, x0_out, B, H, W, *k_coef, *d, S(stream));
+}
 int cgd_masked_merge(cgd_ctx* ctx, float* sample, float* x0, const float* init, const float* mask, const float* n_known, const float* n_re,
                      float* x_re, int B, int H, int W, int init_batch, int mask_batch, int mask_channels, const cgd_mask_coef* k,
                      void* stream) {

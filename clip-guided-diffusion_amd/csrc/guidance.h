@@ -34,3 +34,12 @@ int cgd_launch_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eva
 int cgd_launch_dpmpp_update(cgd_ctx* ctx, const float* x, const float* x0, const float* g, const float* scalars, const float* noise,
                             const float* x0_hist, float* x0c_out, float* sample, float* x0_out, int B, int H, int W, const StepCoef& k,
                             const cgd_dpmpp& d, hipStream_t s);
+// threshold.hip
+int cgd_launch_abs_quantile(cgd_ctx* ctx, const float* v, int B, long n, long k, float frac, float floor, float cap, float* out3,
+                            void* scratch, hipStream_t s);
+int cgd_launch_dpmpp_threshold(cgd_ctx* ctx, const float* x, const float* x0, const float* g, const float* scalars, float* x0c, int B, int H,
+                               int W, const StepCoef& kc, long k, float frac, float floor, float cap, float* thr3, void* scratch,
+                               hipStream_t s);
+int cgd_launch_dpmpp_update_thr(cgd_ctx* ctx, const float* x, const float* x0, const float* x0c, const float* thr3, const float* noise,
+                                const float* x0_hist, float* x0c_out, float* sample, float* x0_out, int B, int H, int W, const StepCoef& k,
+                                const cgd_dpmpp& d, hipStream_t s);

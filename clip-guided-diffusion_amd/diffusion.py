@@ -158,6 +158,19 @@ class SpacedDiffusion:
         k.c_x, k.c_d, k.c_r, k.c_n = self.dpmpp_coef_f64(i, order, eta)
         return k
 
+    @staticmethod
+    def threshold_rank(p, n):
+        """(k, frac) of the p-quantile of n values under torch.quantile's 'linear' rule, float64: pos = p (n - 1), k = floor(pos),
+        frac = pos - k, so that the quantile is v_k + (v_{k+1} - v_k) frac with v_j the j-th smallest value (k + 1 clamped to n - 1).
+        What cgd_dpmpp_threshold takes (csrc/threshold.hip); p in (0, 1], p = 1 is the maximum."""
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0.0 < p <= 1.0:
+            raise ValueError(f"the quantile p must be a number in (0, 1], got {p!r}")
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"n must be an int >= 1, got {n!r}")
+        pos = float(p) * (n - 1)
+        k = min(int(math.floor(pos)), n - 1)
+        return k, pos - k
+
     def mask_coef(self, i):
         """Coefficients of the masked-sampling merge after the update of step index i (sampler.py, csrc/mask.hip): the known region
         lives at level i - 1, known = sqrt(abar_prev) init + sqrt(1 - abar_prev) noise (the init image itself at i = 0), and a

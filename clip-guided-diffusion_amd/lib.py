@@ -174,6 +174,11 @@ _SIGS = {
     "cgd_multistep_update": (i32, [vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef),
                                     C.POINTER(StepCoef), C.POINTER(Multistep), vp]),
     "cgd_dpmpp_update": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), C.POINTER(Dpmpp), vp]),
+    "cgd_abs_quantile_scratch_bytes": (i64, [i32, i64]),
+    "cgd_abs_quantile_slice": (i32, []),
+    "cgd_op_abs_quantile": (i32, [vp, vp, i32, i64, i64, f32, f32, f32, vp, vp, vp]),
+    "cgd_dpmpp_threshold": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), i64, f32, f32, f32, vp, vp, vp]),
+    "cgd_dpmpp_update_thr": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), C.POINTER(Dpmpp), vp]),
     "cgd_masked_merge": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(MaskCoef), vp]),
     "cgd_ddim_reverse_update": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(ReverseCoef), vp]),
     "cgd_op_gemm": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp]),

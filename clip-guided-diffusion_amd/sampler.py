@@ -13,7 +13,9 @@ init image, noised to the level the update produced, back into the kept region; 
 jump length 1).  Without a mask nothing of it runs.
 DPM-Solver++(2M) (`dpmpp_sample_loop_progressive`, Lu et al., 2022; eta = 0 the ODE solver, eta > 0 the SDE solver) runs on the levels of
 'dpmN' (uniform in logSNR, diffusion.logsnr_timesteps): one guided evaluation per step and one cgd_dpmpp_update launch, which combines the
-evaluation's guided pred_xstart with the one of the step before; the two history buffers rotate by pointer.
+evaluation's guided pred_xstart with the one of the step before; the two history buffers rotate by pointer.  With `threshold=` the guided
+pred_xstart is thresholded dynamically first (per sample: clamped to its own quantile of absolute values and rescaled): cgd_dpmpp_threshold
+selects the quantile on the device and cgd_dpmpp_update_thr updates (csrc/threshold.hip); without it nothing of that runs.
 DDIM inversion (`ddim_reverse_sample_loop_progressive`, `ddim_invert`; guided_diffusion's ddim_reverse_sample) runs the deterministic DDIM ODE
 upwards from an image: per step one UNet forward and one cgd_ddim_reverse_update launch.  `ddim_invert` returns the latent and the noise that
 q_samples the image to it, so every loop above starts from the latent when called with `noise=noise, init_image=image, skip_timesteps=s`.
@@ -312,11 +314,14 @@ class GuidedSampler:
             self._merge(masked, i, sample, x0_out, masked["x_T"])
         return {"sample": sample, "pred_xstart": x0_out}
 
-    def _dpmpp_step(self, model, x, i, cond_fn, model_kwargs, noise, bufs, st, ahead=None, eta=0.0, masked=None):
+    def _dpmpp_step(self, model, x, i, cond_fn, model_kwargs, noise, bufs, st, ahead=None, eta=0.0, masked=None, threshold=None):
         """One DPM-Solver++(2M) step.  `st`: {'order', 'hist': the guided pred_xstart of the step before (None on the first step, which
         therefore runs at order 1), 'free': the spare buffer}.  The history rotates by pointer: the entry the launch has read is the
         buffer the next launch writes.  Step index 0 runs at order 1 (diffusion.dpmpp_coef) and nothing reads the entry of step
-        index 1 or 0, so those are not written.  `masked`: the result is merged after the update; the history stays as evaluated."""
+        index 1 or 0, so those are not written.  `masked`: the result is merged after the update; the history stays as evaluated.
+        `threshold` (p, cap): dynamic thresholding of the guided pred_xstart (csrc/threshold.hip): cgd_dpmpp_threshold writes it to a buffer and
+        selects the sample's scale s on the device, cgd_dpmpp_update_thr clamps, rescales and updates; the history then holds the thresholded
+        predictions.  The buffer, the (B, 3) result and the selection's scratch live in `bufs`, allocated once per loop."""
         ctx, lib = self.ctx, self.ctx.lib
         B, _, H, W = x.shape
         n_known = self._known_noise(masked, x) if masked is not None else None
@@ -328,9 +333,23 @@ class GuidedSampler:
         if st["order"] == 2 and i > 1:
             x0c = st["free"].pop() if st["free"] else th.empty_like(x)
         sample, x0_out = th.empty_like(x), th.empty_like(x)
-        ctx.check(lib.cgd_dpmpp_update(ctx.h, x.data_ptr(), ev["x0"].data_ptr(), L.ptr(g), L.ptr(ev["scal"]), L.ptr(noise),
-                                       L.ptr(hist) if d.c_r else None, L.ptr(x0c), sample.data_ptr(), x0_out.data_ptr(), B, H, W,
-                                       ev["coef"], d, ctx.stream()))
+        if threshold is not None:
+            p, cap = threshold
+            if "_thr" not in bufs:
+                n = 3 * H * W
+                # cap == 1: every scale is 1 (the static clip), nothing is selected and no scratch is needed
+                scratch = th.empty(int(lib.cgd_abs_quantile_scratch_bytes(B, n)), dtype=th.uint8, device=x.device) if cap > 1.0 else None
+                bufs["_thr"] = (th.empty_like(x), th.empty((B, 3), dtype=th.float32, device=x.device), scratch, self.tables.threshold_rank(p, n))
+            raw, thr3, scratch, (rank, frac) = bufs["_thr"]
+            ctx.check(lib.cgd_dpmpp_threshold(ctx.h, x.data_ptr(), ev["x0"].data_ptr(), L.ptr(g), L.ptr(ev["scal"]), raw.data_ptr(), B, H, W,
+                                              ev["coef"], rank, frac, 1.0, cap, thr3.data_ptr(), L.ptr(scratch), ctx.stream()))
+            ctx.check(lib.cgd_dpmpp_update_thr(ctx.h, x.data_ptr(), ev["x0"].data_ptr(), raw.data_ptr(), thr3.data_ptr(), L.ptr(noise),
+                                               L.ptr(hist) if d.c_r else None, L.ptr(x0c), sample.data_ptr(), x0_out.data_ptr(), B, H, W,
+                                               ev["coef"], d, ctx.stream()))
+        else:
+            ctx.check(lib.cgd_dpmpp_update(ctx.h, x.data_ptr(), ev["x0"].data_ptr(), L.ptr(g), L.ptr(ev["scal"]), L.ptr(noise),
+                                           L.ptr(hist) if d.c_r else None, L.ptr(x0c), sample.data_ptr(), x0_out.data_ptr(), B, H, W,
+                                           ev["coef"], d, ctx.stream()))
         if hist is not None:
             st["free"].append(hist)
         st["hist"] = x0c
@@ -348,9 +367,9 @@ class GuidedSampler:
             raise NotImplementedError("the reference passes cond_fn_with_grad=True (cgd.py:260)")
 
     def _loop(self, mode, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-              randomize_class, cond_fn_with_grad, eta=0.0, plms_order=None, mask=None, resamples=1, dpm_order=None):
+              randomize_class, cond_fn_with_grad, eta=0.0, plms_order=None, mask=None, resamples=1, dpm_order=None, threshold=None):
         """mode 0 p_sample, 1 DDIM (eta > 0: stochastic DDIM), 2 PLMS of order `plms_order` (no per-step noise), 3 DPM-Solver++(2M) of
-        order `dpm_order` (eta > 0: the SDE solver, with a per-step noise).  `mask` (with `init_image`): masked sampling, every step
+        order `dpm_order` (eta > 0: the SDE solver, with a per-step noise; `threshold` (p, cap): dynamic thresholding).  `mask` (with `init_image`): masked sampling, every step
         index > 0 `resamples` times."""
         self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
         device = th.device(device or f"cuda:{self.ctx.device}")
@@ -424,7 +443,8 @@ class GuidedSampler:
                     with th.no_grad():
                         out = self._dpmpp_step(model, img, i, cond_fn, model_kwargs, step_noise, bufs, dpm,
                                                *((ahead,) if ahead is not None else ()), **({"eta": eta} if eta else {}),
-                                               **({"masked": masked} if masked is not None else {}))
+                                               **({"masked": masked} if masked is not None else {}),
+                                               **({"threshold": threshold} if threshold is not None else {}))
                     continue
                 step_noise = tape["noise"][evals].to(device).float().contiguous() if tape is not None else None
                 evals += 1
@@ -488,14 +508,19 @@ class GuidedSampler:
 
     def dpmpp_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                       model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
-                                      randomize_class=False, cond_fn_with_grad=False, order=2, eta=0.0, mask=None, resamples=1):
+                                      randomize_class=False, cond_fn_with_grad=False, order=2, eta=0.0, mask=None, resamples=1, threshold=None):
         """DPM-Solver++(2M) (Lu et al., 2022: data prediction, multistep): one guided evaluation per step; the update extrapolates the guided
         pred_xstart with the one of the step before (`order` 2; the first step and step index 0 run at order 1; `order` 1 is DDIM with the
         same eta for eta in {0, 1}).  eta == 0: the deterministic solver, no per-step noise.  eta > 0: the SDE solver (eta = 1 is
         SDE-DPM-Solver++(2M)), one noise draw per evaluation before cond_fn, as in DDIM with eta.  Meant for tables spaced uniformly in
         logSNR (timestep_respacing 'dpmN'); on the integer-stride levels of 'ddimN' the second order gains nothing below about 50 steps
         (DESIGN.md).  `mask`: masked sampling as in ddim_sample_loop_progressive (eta == 0: the kept region is noised with the loop's
-        initial noise); `resamples` > 1 is refused: a resampled history would mix noise levels."""
+        initial noise); `resamples` > 1 is refused: a resampled history would mix noise levels.
+        `threshold`: None, p, or (p, cap): dynamic thresholding of the guided pred_xstart (Saharia et al., 2022).  Per sample, s = the
+        p-quantile of |guided pred_xstart| (p in (0, 1]; torch.quantile's 'linear' rule, selected exactly on the device), raised to at least 1
+        and lowered to at most `cap` (>= 1; none when not given); the prediction is clamped to [-s, s] and divided by s before the update, and
+        the history holds the thresholded predictions.  cap = 1 is the static clip of the guided prediction to [-1, 1].  With order 1 this
+        is thresholded DDIM.  The yielded pred_xstart stays the unguided prediction."""
         if isinstance(order, bool) or not isinstance(order, int) or order not in (1, 2):
             raise ValueError(f"order is invalid (should be 1 or 2): {order!r}")
         if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not eta >= 0.0:
@@ -505,8 +530,25 @@ class GuidedSampler:
             raise ValueError("DPM-Solver++ cannot resample: its pred_xstart history would mix noise levels (use the DDIM loop, "
                              "ddim_sample_loop_progressive, for resamples > 1)")
         self._check_mask(shape, init_image, mask, resamples)
+        threshold = self._check_threshold(threshold)
         return self._loop(3, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad, eta=float(eta), mask=mask, dpm_order=order)
+                          randomize_class, cond_fn_with_grad, eta=float(eta), mask=mask, dpm_order=order,
+                          **({"threshold": threshold} if threshold is not None else {}))
+
+    @staticmethod
+    def _check_threshold(threshold):
+        """None | p | (p, cap) -> None | (p, cap) as floats, cap = inf when not given"""
+        if threshold is None:
+            return None
+        p, cap = threshold if isinstance(threshold, (tuple, list)) and len(threshold) == 2 else (threshold, math.inf)
+        for v in (p, cap):
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError(f"threshold must be None, p or (p, cap) with numbers, got {threshold!r}")
+        if not 0.0 < p <= 1.0:
+            raise ValueError(f"threshold: the quantile p must lie in (0, 1], got {p!r}")
+        if not cap >= 1.0:
+            raise ValueError(f"threshold: cap must be >= 1 (1 is the static clip to [-1, 1]), got {cap!r}")
+        return float(p), float(cap)
 
     # ---- DDIM inversion ---------------------------------------------------------------------------------
     def ddim_reverse_sample_loop_progressive(self, model, image, clip_denoised=False, model_kwargs=None, device=None, progress=False,

@@ -377,6 +377,40 @@ int cgd_dpmpp_update(cgd_ctx* ctx, const float* x, const float* pred_xstart, con
                      const float* x0_hist, float* x0c_out, float* sample, float* pred_xstart_out, int B, int H, int W,
                      const cgd_step_coef* k, const cgd_dpmpp* d, void* stream);
 
+/* ---- dynamic thresholding of the guided pred_xstart under DPM-Solver++ (Saharia et al., 2022; Lu et al., 2022).  Per sample b, with
+ *      a_b = |x0c_b| flattened to n = 3 H W values (|-0| = +0) and v_j the j-th smallest of them:
+ *        q_b = v_k + (v_{k+1} - v_k) frac      (torch.quantile's 'linear' rule: pos = p (n - 1), k = floor(pos), frac = pos - k, computed by
+ *                                               the host in float64; k + 1 is clamped to n - 1)
+ *        s_b = min(max(q_b, floor), cap)       (floor = 1 and cap = +inf: dynamic thresholding; cap == floor: the static clip to +-cap)
+ *        x0t = clamp(x0c, -s_b, s_b) / s_b     (a true division)
+ *      and x0t takes x0c's place in cgd_dpmpp_update: D = c_r != 0 ? x0t + c_r (x0t - x0_hist) : x0t; sample = t != 0 ? c_x x + c_d D
+ *      (+ c_n noise) : x0t; x0c_out = x0t (so x0_hist is the x0t of the step before); pred_xstart_out = pred_xstart.
+ *      v_k and v_{k+1} are exact: radix selection on the bit patterns with the sign cleared, integer histograms per workgroup, partial counts
+ *      in `scratch` summed in a fixed order by the next launch, no synchronisation between workgroups inside a launch; the same bits on every
+ *      run.  A row that holds a non-finite value does not fault and does not disturb the other rows; its own result is unspecified.
+ *      cgd_abs_quantile_scratch_bytes: bytes of `scratch` for B rows of n values (host only; -1 for a non-positive size or n > 2^31 - 1);
+ *      cgd_abs_quantile_slice: the values one workgroup counts (a row runs on ceil(n / slice) workgroups).
+ *      cgd_op_abs_quantile: the selection on a plain array v [B][n]; out3 [B][3] = {v_k, v_{k+1}, s}.  Five launches.
+ *      cgd_dpmpp_threshold: the first launch computes x0c from x, pred_xstart, g and scalars exactly as cgd_dpmpp_update does and WRITES it
+ *      to x0c (B,3,H,W); the later launches and cgd_dpmpp_update_thr read that buffer, so the selected and the clamped values are the same
+ *      bits.  thr3 [B][3] = {v_k, v_{k+1}, s}.  With cap == floor every s_b is cap: one launch writes x0c and thr3 = {0, 0, cap}, nothing is
+ *      selected and scratch may be NULL.  x0c may not alias x, pred_xstart or g.
+ *      cgd_dpmpp_update_thr: cgd_dpmpp_update with x0c read from the buffer and s_b from thr3[b * 3 + 2] in device memory (the host never
+ *      reads it); one launch.  The same optional buffers and aliasing rules as cgd_dpmpp_update; in addition x0c may not alias any output.
+ *      Any 4-byte-aligned pointers and any sizes are accepted (16-byte accesses when every pointer is 16-byte aligned and 4 | n, 4 | H * W).
+ *      All return -2 (cgd_last_error), before any launch, for a non-positive size, k outside [0, n), frac outside [0, 1], cap < floor, a
+ *      missing required buffer or missing scratch, or an aliased output. ---- */
+int64_t cgd_abs_quantile_scratch_bytes(int B, int64_t n);
+int cgd_abs_quantile_slice(void);
+int cgd_op_abs_quantile(cgd_ctx* ctx, const float* v, int B, int64_t n, int64_t k, float frac, float floor, float cap, float* out3,
+                        void* scratch, void* stream);
+int cgd_dpmpp_threshold(cgd_ctx* ctx, const float* x, const float* pred_xstart, const float* g, const float* scalars, float* x0c, int B,
+                        int H, int W, const cgd_step_coef* k_coef, int64_t k, float frac, float floor, float cap, float* thr3, void* scratch,
+                        void* stream);
+int cgd_dpmpp_update_thr(cgd_ctx* ctx, const float* x, const float* pred_xstart, const float* x0c, const float* thr3, const float* noise,
+                         const float* x0_hist, float* x0c_out, float* sample, float* pred_xstart_out, int B, int H, int W,
+                         const cgd_step_coef* k_coef, const cgd_dpmpp* d, void* stream);
+
 /* ---- masked sampling (inpainting / outpainting of an init image): the merge after a sampler update at step index t, in one launch.
  *      The update left `sample` (the state at level t-1) and `pred_xstart`; with m = mask (1 regenerate, 0 keep the init image):
  *        known       = sqrt(abar_prev) init + sqrt(1 - abar_prev) n_known   (two rounded products and a rounded sum, not fused)

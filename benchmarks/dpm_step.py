@@ -11,13 +11,9 @@ at the same shape, from HIP events, --launch-repeats times each in turn.  Synthe
 about image quality.  Prints one JSON line.  Usage: python benchmarks/dpm_step.py [--runs 3]"""
 import argparse
 import json
-import os
 import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import steplib
 
 
 def main():
@@ -27,16 +23,10 @@ def main():
     ap.add_argument("--launch-repeats", type=int, default=5)
     args = ap.parse_args()
     import torch as th
-
-    import bench
-    import cgd_amd  # noqa: F401
     from cgd_amd import diffusion as dd
-    from cgd_amd import lib as L
     from cgd_amd import sampler
-    dev = "cuda:0"
-    cfg = bench.CONFIGS[2]
-    ctx = L.Context(0, 1)
-    unet, towers, smp250, guid, _ = bench.build_device(ctx, cfg, dev)
+    dev = steplib.DEV
+    cfg, ctx, (unet, towers, smp250, guid, _) = steplib.setup()
     smps = {"respace-250": smp250,
             "plms50": sampler.GuidedSampler(ctx, dd.create_gaussian_diffusion(1000, "linear", "plms50", False)),
             "dpm20": sampler.GuidedSampler(ctx, dd.create_gaussian_diffusion(1000, "linear", "dpm20", False))}
@@ -54,25 +44,13 @@ def main():
             gen = smp.plms_sample_loop_progressive(unet, (1, 3, H, W), order=2, **kw)
         else:
             gen = smp.dpmpp_sample_loop_progressive(unet, (1, 3, H, W), order=2, eta=0.0, **kw)
-        th.cuda.synchronize()
-        t0 = time.perf_counter()
-        n = 0
-        for out in gen:
-            guid.current_timestep -= 1
-            n += 1
-        th.cuda.synchronize()
-        return time.perf_counter() - t0, n, bool(th.isfinite(out["sample"]).all())
+        t, n, out = steplib.drain(gen, guid)
+        return t, n, bool(th.isfinite(out["sample"]).all())
 
-    th.manual_seed(1000)
     modes = list(smps)
-    times, steps, finite = {m: [] for m in modes}, {}, {}
-    for m in modes:
-        run(m)  # warm-up: buffers, first-touch of the kernels
-    for _ in range(args.runs):
-        for m in modes:
-            t, n, ok = run(m)
-            times[m].append(t)
-            steps[m], finite[m] = n, ok
+    res = steplib.alternate(modes, run, args.runs)
+    times = {m: [t for t, _, _ in v] for m, v in res.items()}
+    steps, finite = {m: v[-1][1] for m, v in res.items()}, {m: v[-1][2] for m, v in res.items()}
 
     # per-launch cost of the updates at the headline shape
     x, x0, g, noise, hist = (th.randn(1, 3, H, W, device=dev) for _ in range(5))
@@ -96,22 +74,8 @@ def main():
                                                ctx.stream()))
         return fn
 
-    def per_launch(fn):
-        for _ in range(20):
-            fn()
-        e0, e1 = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.launch_iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / args.launch_iters * 1e3
-
     fns = {"cgd_sample_update_mode1": sample_update, "cgd_dpmpp_update_2m_eta0": dpmpp(0.0), "cgd_dpmpp_update_2m_eta1": dpmpp(1.0)}
-    launch = {n: [] for n in fns}
-    for _ in range(args.launch_repeats):  # the three in turn, so that a drift of the clocks lands on all of them
-        for n, fn in fns.items():
-            launch[n].append(per_launch(fn))
+    launch = steplib.per_launch(fns, args.launch_iters, args.launch_repeats)
     med = {m: statistics.median(v) for m, v in times.items()}
     print(json.dumps({"what": "seconds per full guided sampling run, bench.py config 2 (256x256, cutn 16, ViT-B/32, batch 1, synthetic "
                               f"weights), median of {args.runs} runs", "s_per_run": {m: round(v, 3) for m, v in med.items()},
@@ -119,8 +83,7 @@ def main():
                       "ms_per_yielded_step": {m: round(med[m] / steps[m] * 1e3, 3) for m in modes},
                       "dpm20_over_respace250": round(med["dpm20"] / med["respace-250"], 4),
                       "dpm20_over_plms50": round(med["dpm20"] / med["plms50"], 4),
-                      "update_launch_us": {n: {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
-                                           for n, v in launch.items()}, "device": th.cuda.get_device_name(0)}))
+                      "update_launch_us": {n: steplib.stats(v) for n, v in launch.items()}, "device": th.cuda.get_device_name(0)}))
 
 
 if __name__ == "__main__":

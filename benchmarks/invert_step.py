@@ -11,13 +11,9 @@ Every figure is the median of --repeats measurements (taken alternately, after o
 Prints one JSON line.  Usage: python benchmarks/invert_step.py [--repeats 5]"""
 import argparse
 import json
-import os
-import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import steplib
 
 
 def main():
@@ -26,14 +22,8 @@ def main():
     ap.add_argument("--launch-iters", type=int, default=500)
     args = ap.parse_args()
     import torch as th
-
-    import bench
-    import cgd_amd  # noqa: F401
-    from cgd_amd import lib as L
-    dev = "cuda:0"
-    cfg = dict(bench.CONFIGS[2], spec="ddim50")
-    ctx = L.Context(0, 1)
-    unet, towers, smp, guid, image = bench.build_device(ctx, cfg, dev)
+    dev = steplib.DEV
+    cfg, ctx, (unet, towers, smp, guid, image) = steplib.setup(spec="ddim50")
     H, W = cfg["hw"]
     y = {"y": th.zeros(1, dtype=th.long, device=dev)}
     skip = smp.num_timesteps // 2
@@ -51,14 +41,8 @@ def main():
         it = smp.ddim_sample_loop_progressive(unet, (1, 3, H, W), noise=noise, clip_denoised=False, cond_fn=guid, model_kwargs=dict(y),
                                               device=dev, skip_timesteps=skip, init_image=image, randomize_class=False,
                                               cond_fn_with_grad=True)
-        th.cuda.synchronize()
-        t = time.perf_counter()
-        n = 0
-        for out in it:
-            guid.current_timestep -= 1
-            n += 1
-        th.cuda.synchronize()
-        return (time.perf_counter() - t) / n * 1e3, n, bool(th.isfinite(out["sample"]).all())
+        t, n, out = steplib.drain(it, guid)
+        return t / n * 1e3, n, bool(th.isfinite(out["sample"]).all())
 
     th.manual_seed(1000)
     _, noise, _ = invert()  # warm-up: buffers, first touch of the kernels
@@ -93,27 +77,10 @@ def main():
                                                       1, H, W, 1, rk, ctx.stream()))
         return fn
 
-    def per_launch(fn):
-        e0, e1 = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.launch_iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / args.launch_iters * 1e3
-
     fns = {"cgd_sample_update_mode1": sample_update, "cgd_ddim_reverse_update": reverse(False),
            "cgd_ddim_reverse_update_noise_out": reverse(True)}
-    for fn in fns.values():
-        for _ in range(20):
-            fn()
-    launch = {n: [] for n in fns}
-    for _ in range(args.repeats):
-        for n, fn in fns.items():
-            launch[n].append(per_launch(fn))
-
-    def stat(v, nd):
-        return {"median": round(statistics.median(v), nd), "min": round(min(v), nd), "max": round(max(v), nd)}
+    launch = steplib.per_launch(fns, args.launch_iters, args.repeats)
+    stat = steplib.stats
 
     print(json.dumps({"what": "DDIM inversion at 256x256, batch 1, synthetic weights, ddim50, bench.py config 2's networks; median / min / max of "
                               f"{args.repeats} alternating repeats",

@@ -11,30 +11,22 @@ The unmasked and masked runs alternate, --runs of each after one untimed warm-up
 synchronise.  Prints one JSON line.  Usage: python benchmarks/masked_step.py [--runs 3]"""
 import argparse
 import json
-import os
 import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import steplib
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--launch-iters", type=int, default=500)
+    ap.add_argument("--launch-repeats", type=int, default=5)
     ap.add_argument("--no-resamples", action="store_true", help="skip the resamples=2 run")
     args = ap.parse_args()
     import torch as th
-
-    import bench
-    import cgd_amd  # noqa: F401
     from cgd_amd import lib as L
-    dev = "cuda:0"
-    cfg = bench.CONFIGS[2]
-    ctx = L.Context(0, 1)
-    unet, towers, smp, guid, _ = bench.build_device(ctx, cfg, dev)
+    dev = steplib.DEV
+    cfg, ctx, (unet, towers, smp, guid, _) = steplib.setup()
     H, W = cfg["hw"]
     y = {"y": th.zeros(1, dtype=th.long, device=dev)}
     gen = th.Generator().manual_seed(5)
@@ -51,27 +43,16 @@ def main():
         if mode == "resamples2":
             kw["resamples"] = 2
         it = smp.p_sample_loop_progressive(unet, (1, 3, H, W), **kw)
-        th.cuda.synchronize()
-        t0 = time.perf_counter()
-        n = 0
-        for out in it:
-            guid.current_timestep -= 1
-            n += 1
-        th.cuda.synchronize()
+        t, n, out = steplib.drain(it, guid)
         kept = bool(th.equal(out["pred_xstart"][..., :W // 2], init[..., :W // 2]))
-        return time.perf_counter() - t0, n, bool(th.isfinite(out["sample"]).all()), kept
+        return t, n, bool(th.isfinite(out["sample"]).all()), kept
 
-    th.manual_seed(1000)
     modes = ["unmasked", "masked"]
-    times, steps, finite, kept = {m: [] for m in modes}, {}, {}, {}
-    for m in modes:
-        run(m)  # warm-up: buffers, first touch of the kernels
-    for _ in range(args.runs):
-        for m in modes:
-            t, n, ok, kp = run(m)
-            times[m].append(t)
-            steps[m], finite[m], kept[m] = n, ok, kp
+    res = steplib.alternate(modes, run, args.runs)
+    times = {m: [v[0] for v in r] for m, r in res.items()}
+    steps, finite, kept = ({m: r[-1][j] for m, r in res.items()} for j in (1, 2, 3))
     if not args.no_resamples:
+        th.manual_seed(2000)
         t, n, ok, kp = run("resamples2")
         times["resamples2"], steps["resamples2"], finite["resamples2"], kept["resamples2"] = [t], n, ok, kp
 
@@ -97,28 +78,17 @@ def main():
                                                x_re.data_ptr() if renoise else None, 1, H, W, 1, 1, 1, mk, ctx.stream()))
         return fn
 
-    def per_launch(fn):
-        for _ in range(20):
-            fn()
-        e0, e1 = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.launch_iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / args.launch_iters * 1e3
-
     sample.copy_(x)
     x0_out.copy_(x0)
-    launch_us = {"cgd_sample_update_mode0": per_launch(sample_update), "cgd_masked_merge": per_launch(merge(False)),
-                 "cgd_masked_merge_renoise": per_launch(merge(True))}
+    launch_us = steplib.per_launch({"cgd_sample_update_mode0": sample_update, "cgd_masked_merge": merge(False),
+                                    "cgd_masked_merge_renoise": merge(True)}, args.launch_iters, args.launch_repeats)
     med = {m: statistics.median(v) for m, v in times.items()}
     print(json.dumps({"what": "seconds per full guided p_sample run from an init image, bench.py config 2 (256x256, cutn 16, ViT-B/32, batch 1, "
                               f"synthetic weights, -respace 250), median of {args.runs} alternating runs (resamples2: one run)",
                       "s_per_run": {m: round(v, 3) for m, v in med.items()}, "runs_s": {m: [round(t, 3) for t in v] for m, v in times.items()},
                       "steps_yielded": steps, "finite": finite, "kept_half_is_init": kept,
                       "masked_over_unmasked": round(med["masked"] / med["unmasked"], 4),
-                      "launch_us": {n: round(v, 2) for n, v in launch_us.items()}, "device": th.cuda.get_device_name(0)}))
+                      "launch_us": {n: steplib.stats(v) for n, v in launch_us.items()}, "device": th.cuda.get_device_name(0)}))
 
 
 if __name__ == "__main__":

@@ -10,31 +10,23 @@ at the same shape, from HIP events.  Prints one JSON line.  Usage: python benchm
 import argparse
 import ctypes as C
 import json
-import os
 import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import steplib
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--launch-iters", type=int, default=500)
+    ap.add_argument("--launch-repeats", type=int, default=5)
     args = ap.parse_args()
     import torch as th
-
-    import bench
-    import cgd_amd  # noqa: F401
     from cgd_amd import diffusion as dd
     from cgd_amd import lib as L
     from cgd_amd import sampler
-    dev = "cuda:0"
-    cfg = bench.CONFIGS[2]
-    ctx = L.Context(0, 1)
-    unet, towers, smp250, guid, _ = bench.build_device(ctx, cfg, dev)
+    dev = steplib.DEV
+    cfg, ctx, (unet, towers, smp250, guid, _) = steplib.setup()
     smp_plms = sampler.GuidedSampler(ctx, dd.create_gaussian_diffusion(1000, "linear", "plms50", False))
     H, W = cfg["hw"]
     y = {"y": th.zeros(1, dtype=th.long, device=dev)}
@@ -46,25 +38,13 @@ def main():
         kw = dict(clip_denoised=False, cond_fn=guid, model_kwargs=dict(y), device=dev, randomize_class=True, cond_fn_with_grad=True)
         gen = smp.p_sample_loop_progressive(unet, (1, 3, H, W), **kw) if mode == "respace-250" else \
             smp.plms_sample_loop_progressive(unet, (1, 3, H, W), order=2, **kw)
-        th.cuda.synchronize()
-        t0 = time.perf_counter()
-        n = 0
-        for out in gen:
-            guid.current_timestep -= 1
-            n += 1
-        th.cuda.synchronize()
-        return time.perf_counter() - t0, n, bool(th.isfinite(out["sample"]).all())
+        t, n, out = steplib.drain(gen, guid)
+        return t, n, bool(th.isfinite(out["sample"]).all())
 
-    th.manual_seed(1000)
     modes = ["respace-250", "plms50"]
-    times, steps, finite = {m: [] for m in modes}, {}, {}
-    for m in modes:
-        run(m)  # warm-up: buffers, first-touch of the kernels
-    for _ in range(args.runs):
-        for m in modes:
-            t, n, ok = run(m)
-            times[m].append(t)
-            steps[m], finite[m] = n, ok
+    res = steplib.alternate(modes, run, args.runs)
+    times = {m: [t for t, _, _ in v] for m, v in res.items()}
+    steps, finite = {m: v[-1][1] for m, v in res.items()}, {m: v[-1][2] for m, v in res.items()}
 
     # per-launch cost of the updates at the headline shape
     x, x0, g, noise = (th.randn(1, 3, H, W, device=dev) for _ in range(4))
@@ -89,27 +69,16 @@ def main():
                                                    ctx.stream()))
         return fn
 
-    def per_launch(fn):
-        for _ in range(20):
-            fn()
-        e0, e1 = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.launch_iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / args.launch_iters * 1e3
-
-    launch_us = {"cgd_sample_update_mode1": per_launch(sample_update), "cgd_multistep_update_plms_order4": per_launch(multistep(0, 4)),
-                 "cgd_multistep_update_plms_order2": per_launch(multistep(0, 2)),
-                 "cgd_multistep_update_ddim_eta": per_launch(multistep(3, 0, 0.1, 0.9))}
+    launch_us = steplib.per_launch({"cgd_sample_update_mode1": sample_update, "cgd_multistep_update_plms_order4": multistep(0, 4),
+                                    "cgd_multistep_update_plms_order2": multistep(0, 2),
+                                    "cgd_multistep_update_ddim_eta": multistep(3, 0, 0.1, 0.9)}, args.launch_iters, args.launch_repeats)
     med = {m: statistics.median(v) for m, v in times.items()}
     print(json.dumps({"what": "seconds per full guided sampling run, bench.py config 2 (256x256, cutn 16, ViT-B/32, batch 1, synthetic "
                               f"weights), median of {args.runs} runs", "s_per_run": {m: round(v, 3) for m, v in med.items()},
                       "runs_s": {m: [round(t, 3) for t in v] for m, v in times.items()}, "steps_yielded": steps, "finite": finite,
                       "ms_per_yielded_step": {m: round(med[m] / steps[m] * 1e3, 3) for m in modes},
                       "plms50_over_respace250": round(med["plms50"] / med["respace-250"], 4),
-                      "update_launch_us": {n: round(v, 2) for n, v in launch_us.items()}, "device": th.cuda.get_device_name(0)}))
+                      "update_launch_us": {n: steplib.stats(v) for n, v in launch_us.items()}, "device": th.cuda.get_device_name(0)}))
 
 
 if __name__ == "__main__":

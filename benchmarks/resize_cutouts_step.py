@@ -10,13 +10,10 @@ synchronise.  Then the microseconds per launch of cgd_cutouts_resize_fwd / _bwd 
 Prints one JSON line.  Usage: python benchmarks/resize_cutouts_step.py [--steps 40] [--warmup 5] [--rounds 3]"""
 import argparse
 import json
-import os
 import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import steplib
 
 
 def main():
@@ -25,17 +22,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--launch-iters", type=int, default=200)
+    ap.add_argument("--launch-repeats", type=int, default=5)
     args = ap.parse_args()
     import torch as th
-
-    import bench
-    import cgd_amd  # noqa: F401
     from cgd_amd import guidance as dg
-    from cgd_amd import lib
-    dev = "cuda:0"
-    cfg = bench.CONFIGS[2]
-    ctx = lib.Context(0, 1)
-    unet, towers, smp, guid, x0_star = bench.build_device(ctx, cfg, dev)
+    dev = steplib.DEV
+    cfg, ctx, (unet, towers, smp, guid, x0_star) = steplib.setup()
     H, W = cfg["hw"]
     N, start = smp.num_timesteps, cfg["start"]
     pooled_mk = guid.make_cutouts
@@ -104,19 +96,9 @@ def main():
         ctx.check(ctx.lib.cgd_cutouts_aug_bwd(ctx.h, clip_in.data_ptr(), aug.geo.data_ptr(), aug.params.data_ptr(), g.data_ptr(),
                                               aug_scratch.data_ptr(), B, H, W, cutn, cs, 1, patch, 0, ctx.stream()))
 
-    def per_launch(fn):
-        for _ in range(10):
-            fn()
-        e0, e1 = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.launch_iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / args.launch_iters * 1e3
-
-    launches = {name: round(per_launch(fn), 2) for name, fn in (("cutouts_resize_fwd_us", rs_fwd), ("cutouts_resize_bwd_us", rs_bwd),
-                                                                 ("cutouts_aug_fwd_us", aug_fwd), ("cutouts_aug_bwd_us", aug_bwd))}
+    us = steplib.per_launch({"cutouts_resize_fwd_us": rs_fwd, "cutouts_resize_bwd_us": rs_bwd, "cutouts_aug_fwd_us": aug_fwd,
+                             "cutouts_aug_bwd_us": aug_bwd}, args.launch_iters, args.launch_repeats)
+    launches = {name: steplib.stats(v) for name, v in us.items()}
     med = {m: statistics.median(v) for m, v in times.items()}
     print(json.dumps({"what": "ms per guided step, bench.py config 2 (256x256, 16 cuts, ViT-B/32, batch 1, respace 250, p_sample), "
                               f"median of {args.rounds} rounds x {args.steps} steps",

@@ -9,15 +9,9 @@ ViT-B/32, batch 1, synthetic weights, respace 250, p_sample), in one process:
 Every figure is the median of --repeats measurements (the two paths taken alternately, after one untimed warm-up each) with their minimum and
 maximum beside it.  Prints one JSON line.  Usage: python benchmarks/secondary_step.py [--repeats 5] [--steps 40]"""
 import argparse
-import ctypes
 import json
-import os
-import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import steplib
 
 
 def main():
@@ -27,25 +21,14 @@ def main():
     ap.add_argument("--trunk-iters", type=int, default=20)
     args = ap.parse_args()
     import torch as th
-
-    import bench
-    import cgd_amd  # noqa: F401
-    from cgd_amd import lib as L
     from cgd_amd import nets, synthetic
-    dev = "cuda:0"
-    cfg = dict(bench.CONFIGS[2])
-    ctx = L.Context(0, 1)
-    unet, towers, smp, guid, image = bench.build_device(ctx, cfg, dev)
+    dev = steplib.DEV
+    cfg, ctx, (unet, towers, smp, guid, image) = steplib.setup()
     sec = nets.SecondaryModel(ctx).load_state_dict(synthetic.secondary_state_dict(device=dev))
     H, W = cfg["hw"]
     y = {"y": th.zeros(1, dtype=th.long, device=dev)}
     start = cfg["start"]
     skip = smp.num_timesteps - 1 - start
-    counts = (ctypes.c_uint64 * 2)()
-
-    def launches():
-        ctx.lib.cgd_launch_counts(counts)
-        return counts[0]
 
     def guided(secondary):
         guid.secondary = secondary
@@ -53,15 +36,9 @@ def main():
         th.manual_seed(1000)
         it = smp.p_sample_loop_progressive(unet, (1, 3, H, W), clip_denoised=False, cond_fn=guid, model_kwargs=dict(y), device=dev,
                                            skip_timesteps=skip, init_image=image, randomize_class=False, cond_fn_with_grad=True)
-        th.cuda.synchronize()
-        n0, t, n = launches(), time.perf_counter(), 0
-        for out in it:
-            guid.current_timestep -= 1
-            n += 1
-            if n == args.steps:
-                break
-        th.cuda.synchronize()
-        return (time.perf_counter() - t) / n * 1e3, (launches() - n0) / n, bool(th.isfinite(out["sample"]).all())
+        n0 = steplib.launch_count(ctx)
+        t, n, out = steplib.drain(it, guid, args.steps)
+        return t / n * 1e3, (steplib.launch_count(ctx) - n0) / n, bool(th.isfinite(out["sample"]).all())
 
     guided(None)
     guided(sec)
@@ -78,25 +55,9 @@ def main():
     dv = th.randn(1, 3, H, W, device=dev)
     pred, dx = th.empty_like(x), th.empty_like(x)
 
-    def timed(fn):
-        e0, e1 = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.trunk_iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / args.trunk_iters * 1e3
-
     fns = {"forward": lambda: sec.forward(x, tt, pred=pred), "dgrad": lambda: sec.dgrad(dv, dx)}
-    for fn in fns.values():
-        fn()
-    trunk = {n: [] for n in fns}
-    for _ in range(args.repeats):
-        for n, fn in fns.items():
-            trunk[n].append(timed(fn))
-
-    def stat(v, nd):
-        return {"median": round(statistics.median(v), nd), "min": round(min(v), nd), "max": round(max(v), nd)}
+    trunk = steplib.per_launch(fns, args.trunk_iters, args.repeats)
+    stat = steplib.stats
 
     print(json.dumps({"what": "guided step with / without the secondary model at 256x256, batch 1, synthetic weights, bench.py config 2's networks; "
                               f"median / min / max of {args.repeats} alternating repeats of {args.steps} steps",

@@ -11,16 +11,11 @@ cgd_dpmpp_threshold + cgd_dpmpp_update_thr against cgd_dpmpp_update at the headl
 turn.  Synthetic weights: the runs time the work, they say nothing about image quality.  Prints one JSON line.
 Usage: python benchmarks/threshold_step.py [--runs 3]"""
 import argparse
-import ctypes as C
 import json
 import math
-import os
 import statistics
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import steplib
 
 
 def main():
@@ -30,61 +25,30 @@ def main():
     ap.add_argument("--launch-repeats", type=int, default=5)
     args = ap.parse_args()
     import torch as th
-
-    import bench
-    import cgd_amd  # noqa: F401
     from cgd_amd import diffusion as dd
-    from cgd_amd import lib as L
     from cgd_amd import sampler
-    dev = "cuda:0"
-    cfg = bench.CONFIGS[2]
-    ctx = L.Context(0, 1)
-    unet, towers, _, guid, _ = bench.build_device(ctx, cfg, dev)
+    dev = steplib.DEV
+    cfg, ctx, (unet, towers, _, guid, _) = steplib.setup()
     smp = sampler.GuidedSampler(ctx, dd.create_gaussian_diffusion(1000, "linear", "dpm20", False))
     H, W = cfg["hw"]
     y = {"y": th.zeros(1, dtype=th.long, device=dev)}
 
     def launches():
-        c = (C.c_uint64 * 2)()
-        ctx.lib.cgd_launch_counts(c)
-        return int(c[0])
+        return steplib.launch_count(ctx)
 
     def run(mode):
         guid.diffusion = smp
         guid.current_timestep = smp.num_timesteps - 1
         kw = dict(clip_denoised=False, cond_fn=guid, model_kwargs=dict(y), device=dev, randomize_class=True, cond_fn_with_grad=True)
         gen = smp.dpmpp_sample_loop_progressive(unet, (1, 3, H, W), order=2, eta=0.0, **({"threshold": 0.995} if mode == "dpm20+thr" else {}), **kw)
-        th.cuda.synchronize()
-        l0, t0 = launches(), time.perf_counter()
-        n = 0
-        for out in gen:
-            guid.current_timestep -= 1
-            n += 1
-        th.cuda.synchronize()
-        return time.perf_counter() - t0, n, bool(th.isfinite(out["sample"]).all()), launches() - l0
+        l0 = launches()
+        t, n, out = steplib.drain(gen, guid)
+        return t, n, bool(th.isfinite(out["sample"]).all()), launches() - l0
 
     modes = ["dpm20", "dpm20+thr"]
-    times, steps, finite, lcount = {m: [] for m in modes}, {}, {}, {}
-    for m in modes:
-        th.manual_seed(1000)
-        run(m)  # warm-up: buffers, first-touch of the kernels
-    for r in range(args.runs):
-        for m in modes:
-            th.manual_seed(2000 + r)
-            t, n, ok, lc = run(m)
-            times[m].append(t)
-            steps[m], finite[m], lcount[m] = n, ok, lc
-
-    def per_call(fn):
-        for _ in range(20):
-            fn()
-        e0, e1 = th.cuda.Event(enable_timing=True), th.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.launch_iters):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / args.launch_iters * 1e3
+    res = steplib.alternate(modes, run, args.runs)
+    times = {m: [v[0] for v in r] for m, r in res.items()}
+    steps, finite, lcount = ({m: r[-1][j] for m, r in res.items()} for j in (1, 2, 3))
 
     tab = smp.tables
     fns = {}
@@ -125,10 +89,7 @@ def main():
     l0 = launches()
     thresholded()
     thr_launches = launches() - l0
-    call = {name: [] for name in fns}
-    for _ in range(args.launch_repeats):  # in turn, so that a drift of the clocks lands on all of them
-        for name, fn in fns.items():
-            call[name].append(per_call(fn))
+    call = steplib.per_launch(fns, args.launch_iters, args.launch_repeats)
     med = {m: statistics.median(v) for m, v in times.items()}
     ms = {m: med[m] / steps[m] * 1e3 for m in modes}
     print(json.dumps({"what": "DPM-Solver++(2M) on 'dpm20' with and without threshold=0.995, bench.py config 2 (256x256, cutn 16, ViT-B/32, "
@@ -138,8 +99,7 @@ def main():
                       "thr_over_plain": round(med["dpm20+thr"] / med["dpm20"], 5),
                       "launches_per_run": lcount, "added_launches_per_step": (lcount["dpm20+thr"] - lcount["dpm20"]) / steps["dpm20"],
                       "launches_of_threshold_plus_update_thr": thr_launches,
-                      "call_us": {name: {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
-                                  for name, v in call.items()}, "device": th.cuda.get_device_name(0)}))
+                      "call_us": {name: steplib.stats(v) for name, v in call.items()}, "device": th.cuda.get_device_name(0)}))
 
 
 if __name__ == "__main__":

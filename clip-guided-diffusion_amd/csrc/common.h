@@ -243,6 +243,11 @@ void cgd_prof_push(cgd_ctx* ctx, ProfRec* pr);
   } while (0)
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// workgroups of 256 threads for a grid-stride walk over n elements
+static inline int grid_for(long n, int cap = 1024) {
+  const int g = cdiv(n, 256);
+  return g < cap ? g : cap;
+}
 
 // ---- GEMM / implicit-GEMM conv ---------------------------------------------------------------
 // C[M][N] = alpha * sum_k A[m][k] * B[n][k] (+ bias[n]) (+ R[m][n]);  A and B are K-contiguous fp32.

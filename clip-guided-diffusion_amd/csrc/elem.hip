@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void fill_kernel(float* __restrict__ p, long n
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = v;
 }
 
-inline int grid_for(long n) { return (int)std::min<long>(cdiv(n, 256), 4096); }
+inline int elem_grid(long n) { return grid_for(n, 4096); }
 
 }  // namespace
 
@@ -221,7 +221,7 @@ int cgd_launch_pool2x2(cgd_ctx* ctx, const float* in, int ldi, float* out, int l
   if ((C & 3) || (ldi & 3) || (ldo & 3)) CGD_FAIL(ctx, "pool2x2: C and strides must be multiples of 4");
   if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)add) & 15) CGD_FAIL(ctx, "pool2x2: in / out / add must be 16-byte aligned");
   cgd_chanstats_invalidate(ctx, out, (long)B * Ho * Wo, ldo, C);
-  CGD_LAUNCH(pool2x2_kernel, dim3(grid_for((long)B * Ho * Wo * (C / 4))), dim3(256), 0, s, in, ldi, out, ldo, add, ldadd, B,
+  CGD_LAUNCH(pool2x2_kernel, dim3(elem_grid((long)B * Ho * Wo * (C / 4))), dim3(256), 0, s, in, ldi, out, ldo, add, ldadd, B,
                      Ho, Wo, C, scale);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
@@ -233,7 +233,7 @@ int cgd_launch_upsample2x(cgd_ctx* ctx, const float* in, int ldi, float* out, in
   if ((C & 3) || (ldi & 3) || (ldo & 3)) CGD_FAIL(ctx, "upsample2x: C and strides must be multiples of 4");
   if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)add) & 15) CGD_FAIL(ctx, "upsample2x: in / out / add must be 16-byte aligned");
   cgd_chanstats_invalidate(ctx, out, (long)B * Ho * Wo, ldo, C);
-  CGD_LAUNCH(upsample2x_kernel, dim3(grid_for((long)B * Ho * Wo * (C / 4))), dim3(256), 0, s, in, ldi, out, ldo, add, ldadd,
+  CGD_LAUNCH(upsample2x_kernel, dim3(elem_grid((long)B * Ho * Wo * (C / 4))), dim3(256), 0, s, in, ldi, out, ldo, add, ldadd,
                      B, Ho, Wo, C, scale);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
@@ -248,7 +248,7 @@ int cgd_launch_resample2x_pair(cgd_ctx* ctx, int up, const float* in0, int ldi0,
   ResamplePair pp;
   pp.in[0] = in0; pp.in[1] = in1; pp.out[0] = out0; pp.out[1] = out1;
   pp.ldi[0] = ldi0; pp.ldi[1] = ldi1; pp.ldo[0] = ldo0; pp.ldo[1] = ldo1;
-  const dim3 grid(grid_for((long)B * Ho * Wo * (C / 4)), 2);
+  const dim3 grid(elem_grid((long)B * Ho * Wo * (C / 4)), 2);
   if (up)
     CGD_LAUNCH((resample2x_pair_kernel<1>), grid, dim3(256), 0, s, pp, B, Ho, Wo, C, scale);
   else
@@ -262,7 +262,7 @@ int cgd_launch_copy2d(cgd_ctx* ctx, const float* a, int lda, const float* b, int
   CGD_TRY(cgd_sync_pending(ctx, s));  // reads activations: a deferred split-K reduction must have landed
   if ((C & 3) || (lda & 3) || (ldo & 3) || (b && (ldb & 3))) CGD_FAIL(ctx, "copy2d: C and strides must be multiples of 4");
   cgd_chanstats_invalidate(ctx, out, rows, ldo, C);
-  CGD_LAUNCH(copy2d_kernel, dim3(grid_for(rows * (C / 4))), dim3(256), 0, s, a, lda, b, ldb, out, ldo, rows, C);
+  CGD_LAUNCH(copy2d_kernel, dim3(elem_grid(rows * (C / 4))), dim3(256), 0, s, a, lda, b, ldb, out, ldo, rows, C);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }
@@ -272,7 +272,7 @@ int cgd_launch_concat2(cgd_ctx* ctx, const float* a, int lda, int Ca, const floa
   CGD_TRY(cgd_sync_pending(ctx, s));  // reads activations: a deferred split-K reduction must have landed
   if ((Ca & 3) || (Cb & 3) || (lda & 3) || (ldb & 3) || (ldo & 3)) CGD_FAIL(ctx, "concat2: channels and strides must be multiples of 4");
   cgd_chanstats_invalidate(ctx, out, rows, ldo, Ca + Cb);
-  CGD_LAUNCH(concat2_kernel, dim3(grid_for(rows * ((Ca + Cb) / 4))), dim3(256), 0, s, a, lda, Ca, b, ldb, Cb, out, ldo, rows);
+  CGD_LAUNCH(concat2_kernel, dim3(elem_grid(rows * ((Ca + Cb) / 4))), dim3(256), 0, s, a, lda, Ca, b, ldb, Cb, out, ldo, rows);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }
@@ -288,7 +288,7 @@ int cgd_launch_act_fwd(cgd_ctx* ctx, const float* x, float* y, long n, int act, 
   if (act < 1 || act > 3) CGD_FAIL(ctx, "activation code must be 1 (SiLU), 2 (QuickGELU) or 3 (GELU)");
   CGD_TRY(cgd_sync_pending(ctx, s));  // reads activations: a deferred split-K reduction must have landed
   flat_invalidate(ctx, y, n);
-  CGD_LAUNCH(act_fwd_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, y, n, act);
+  CGD_LAUNCH(act_fwd_kernel, dim3(elem_grid(n)), dim3(256), 0, s, x, y, n, act);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }
@@ -296,7 +296,7 @@ int cgd_launch_act_bwd(cgd_ctx* ctx, const float* x, const float* dy, float* dx,
   if (act < 1 || act > 3) CGD_FAIL(ctx, "activation code must be 1 (SiLU), 2 (QuickGELU) or 3 (GELU)");
   CGD_TRY(cgd_sync_pending(ctx, s));  // reads activations: a deferred split-K reduction must have landed
   flat_invalidate(ctx, dx, n);
-  CGD_LAUNCH(act_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, s, x, dy, dx, n, act);
+  CGD_LAUNCH(act_bwd_kernel, dim3(elem_grid(n)), dim3(256), 0, s, x, dy, dx, n, act);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }
@@ -323,24 +323,24 @@ int cgd_launch_embedding_add(cgd_ctx* ctx, const float* table, const int64_t* id
 
 int cgd_launch_vit_tokens(cgd_ctx* ctx, const float* patch, const float* cls, const float* pos, float* tok, int N, int L, int W,
                           hipStream_t s) {
-  CGD_LAUNCH(vit_tokens_kernel, dim3(grid_for((long)N * L * W)), dim3(256), 0, s, patch, cls, pos, tok, N, L, W);
+  CGD_LAUNCH(vit_tokens_kernel, dim3(elem_grid((long)N * L * W)), dim3(256), 0, s, patch, cls, pos, tok, N, L, W);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }
 
 int cgd_launch_patchify(cgd_ctx* ctx, const float* img, float* cols, int N, int res, int P, hipStream_t s) {
-  CGD_LAUNCH(patchify_kernel, dim3(grid_for((long)N * 3 * res * res)), dim3(256), 0, s, (float*)img, cols, N, res, P, 0);
+  CGD_LAUNCH(patchify_kernel, dim3(elem_grid((long)N * 3 * res * res)), dim3(256), 0, s, (float*)img, cols, N, res, P, 0);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }
 int cgd_launch_unpatchify(cgd_ctx* ctx, const float* cols, float* img, int N, int res, int P, hipStream_t s) {
-  CGD_LAUNCH(patchify_kernel, dim3(grid_for((long)N * 3 * res * res)), dim3(256), 0, s, img, (float*)cols, N, res, P, 1);
+  CGD_LAUNCH(patchify_kernel, dim3(elem_grid((long)N * 3 * res * res)), dim3(256), 0, s, img, (float*)cols, N, res, P, 1);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }
 
 int cgd_launch_fill(cgd_ctx* ctx, float* p, long n, float v, hipStream_t s) {
-  CGD_LAUNCH(fill_kernel, dim3(grid_for(n)), dim3(256), 0, s, p, n, v);
+  CGD_LAUNCH(fill_kernel, dim3(elem_grid(n)), dim3(256), 0, s, p, n, v);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }

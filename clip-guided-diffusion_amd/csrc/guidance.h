@@ -6,8 +6,8 @@
 typedef cgd_step_coef StepCoef;
 
 // The guided pred_xstart of one evaluation at (xv, k), condition_score_with_grad: eps of the model's prediction x0v, shifted by the guidance
-// gradient gv (already scaled by the magnitude clamp), and the pred_xstart that eps implies.  Shared by the multistep update (plms.hip) and
-// the DPM-Solver++ update (dpm.hip); the same lines as mode 1 of sample_update_kernel (guidance.hip).
+// gradient gv (already scaled by the magnitude clamp), and the pred_xstart that eps implies.  Shared by mode 1 of sample_update_kernel
+// (guidance.hip), the multistep update (plms.hip), the DPM-Solver++ update (dpm.hip) and the first launch of its thresholding (threshold.hip).
 __device__ __forceinline__ float guided_x0(const StepCoef& k, float xv, float x0v, float gv) {
   float e = (k.sqrt_recip * xv - x0v) / k.sqrt_recipm1;
   e -= k.sqrt_one_minus_ab * gv;
@@ -34,12 +34,12 @@ int cgd_launch_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eva
 int cgd_launch_dpmpp_update(cgd_ctx* ctx, const float* x, const float* x0, const float* g, const float* scalars, const float* noise,
                             const float* x0_hist, float* x0c_out, float* sample, float* x0_out, int B, int H, int W, const StepCoef& k,
                             const cgd_dpmpp& d, hipStream_t s);
+int cgd_launch_dpmpp_update_thr(cgd_ctx* ctx, const float* x, const float* x0, const float* x0c, const float* thr3, const float* noise,
+                                const float* x0_hist, float* x0c_out, float* sample, float* x0_out, int B, int H, int W, const StepCoef& k,
+                                const cgd_dpmpp& d, hipStream_t s);
 // threshold.hip
 int cgd_launch_abs_quantile(cgd_ctx* ctx, const float* v, int B, long n, long k, float frac, float floor, float cap, float* out3,
                             void* scratch, hipStream_t s);
 int cgd_launch_dpmpp_threshold(cgd_ctx* ctx, const float* x, const float* x0, const float* g, const float* scalars, float* x0c, int B, int H,
                                int W, const StepCoef& kc, long k, float frac, float floor, float cap, float* thr3, void* scratch,
                                hipStream_t s);
-int cgd_launch_dpmpp_update_thr(cgd_ctx* ctx, const float* x, const float* x0, const float* x0c, const float* thr3, const float* noise,
-                                const float* x0_hist, float* x0c_out, float* sample, float* x0_out, int B, int H, int W, const StepCoef& k,
-                                const cgd_dpmpp& d, hipStream_t s);

@@ -325,17 +325,13 @@ __global__ __launch_bounds__(256) void sample_update_kernel(const float* __restr
       x0_out[i] = x0[i];
     } else {
       const float xv = x[i];
-      float eps = (k.sqrt_recip * xv - x0[i]) / k.sqrt_recipm1;
-      eps -= k.sqrt_one_minus_ab * gv;
-      const float p0 = k.sqrt_recip * xv - k.sqrt_recipm1 * eps;
+      const float p0 = guided_x0(k, xv, x0[i], gv);
       const float eps2 = (k.sqrt_recip * xv - p0) / k.sqrt_recipm1;
       sample[i] = p0 * k.sqrt_ab_prev + k.sqrt_one_minus_ab_prev * eps2;
       x0_out[i] = x0[i];  // [3P] ddim_sample_with_grad yields out_orig["pred_xstart"]: the UNCONDITIONED prediction; x0' only builds the sample
     }
   }
 }
-
-inline int grid_for(long n, int cap = 1024) { return (int)std::min<long>(cdiv(n, 256), cap); }
 
 }  // namespace
 

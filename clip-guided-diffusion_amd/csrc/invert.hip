@@ -14,8 +14,6 @@
 #include "elem_pack.h"
 #include "kernels.h"
 
-#include <algorithm>
-
 namespace {
 
 using namespace elem_pack;
@@ -77,14 +75,9 @@ int cgd_launch_ddim_reverse_update(cgd_ctx* ctx, const float* x, const float* ou
   ReverseArgs a = {x, out6, noise_out ? init : nullptr, x_next, x0, noise_out, k.sqrt_recip, k.sqrt_recipm1, k.sqrt_ab_next,
                    k.sqrt_one_minus_ab_next, k.inv_sqrt_one_minus_ab_next};
   const int planes = B * 3, HW = H * W;
-  const bool vec = HW % 4 == 0 && aligned16(x) && aligned16(out6) && aligned16(a.init) && aligned16(x_next) && aligned16(x0) &&
-                   aligned16(noise_out);
-  const int units = vec ? HW / 4 : HW;
-  const dim3 grid(std::min(cdiv(units, 256), 1024), std::min(planes, 65535));
-  if (vec)
-    CGD_LAUNCH(ddim_reverse_kernel<4>, grid, dim3(256), 0, s, a, planes, HW, init_batch);
-  else
-    CGD_LAUNCH(ddim_reverse_kernel<1>, grid, dim3(256), 0, s, a, planes, HW, init_batch);
+  plane_walk(HW, planes, [&](auto v, dim3 grid) {
+    CGD_LAUNCH(ddim_reverse_kernel<decltype(v)::value>, grid, dim3(256), 0, s, a, planes, HW, init_batch);
+  }, x, out6, a.init, x_next, x0, noise_out);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }

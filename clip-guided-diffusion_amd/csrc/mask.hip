@@ -9,8 +9,6 @@
 #include "elem_pack.h"
 #include "kernels.h"
 
-#include <algorithm>
-
 namespace {
 
 using namespace elem_pack;
@@ -92,14 +90,9 @@ int cgd_launch_masked_merge(cgd_ctx* ctx, float* sample, float* x0, const float*
   if ((long)H * W > INT32_MAX || (long)B * 3 > INT32_MAX) CGD_FAIL(ctx, "masked merge: a plane or the plane count exceeds 2^31 - 1");
   MergeArgs a = {sample, x0, init, mask, n_known, n_re, x_re, k.sqrt_ab_prev, k.sqrt_one_minus_ab_prev, k.renoise_x, k.renoise_n};
   const int planes = B * 3, HW = H * W;
-  const bool vec = HW % 4 == 0 && aligned16(sample) && aligned16(x0) && aligned16(init) && aligned16(mask) && aligned16(n_known) &&
-                   aligned16(n_re) && aligned16(x_re);
-  const int units = vec ? HW / 4 : HW;
-  const dim3 grid(std::min(cdiv(units, 256), 1024), std::min(planes, 65535));
-  if (vec)
-    CGD_LAUNCH(masked_merge_kernel<4>, grid, dim3(256), 0, s, a, planes, HW, init_batch, mask_batch, mask_channels);
-  else
-    CGD_LAUNCH(masked_merge_kernel<1>, grid, dim3(256), 0, s, a, planes, HW, init_batch, mask_batch, mask_channels);
+  plane_walk(HW, planes, [&](auto v, dim3 grid) {
+    CGD_LAUNCH(masked_merge_kernel<decltype(v)::value>, grid, dim3(256), 0, s, a, planes, HW, init_batch, mask_batch, mask_channels);
+  }, sample, x0, init, mask, n_known, n_re, x_re);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }

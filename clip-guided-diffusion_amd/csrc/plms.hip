@@ -67,8 +67,6 @@ __global__ __launch_bounds__(256) void multistep_update_kernel(const float* __re
   }
 }
 
-inline int grid_for(long n, int cap = 1024) { return (int)std::min<long>(cdiv(n, 256), cap); }
-
 }  // namespace
 
 int cgd_launch_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eval, const float* x0, const float* g, const float* scalars,

@@ -3,8 +3,9 @@
 //   q_b = v_k + (v_{k+1} - v_k) frac        (torch.quantile's 'linear' rule; k, frac from the host: SpacedDiffusion.threshold_rank)
 //   s_b = min(max(q_b, floor), cap)
 //   x0t = clamp(x0c, -s_b, s_b) / s_b       (a true division), and x0t takes x0c's place in the update of dpm.hip.
-// Two kernel families:
-//   1. Selection: exact v_k and v_{k+1} by radix selection on the bit patterns with the sign cleared (non-negative IEEE floats order like
+// This file holds the selection; the thresholded update is the THR instantiation of dpmpp_update_kernel (dpm.hip), which reads the x0c buffer
+// and thr3[b * 3 + 2] written here.
+//      Selection: exact v_k and v_{k+1} by radix selection on the bit patterns with the sign cleared (non-negative IEEE floats order like
 //      their unsigned bits), four 8-bit digits from the top.  A row is cut into slices of kSlice values, one workgroup of 256 threads per
 //      (slice, row).  Launch p (p = 0 .. 3) counts digit p of the values whose higher digits equal the bins found so far in an integer LDS
 //      histogram (1 KB) and writes its 256 counts to the caller's scratch with plain stores.  The NEXT launch sums the slices' counts in
@@ -21,8 +22,6 @@
 //      dpm.hip does) and WRITES it to a (B,3,H,W) buffer; the later launches and the update read that buffer, so the selected and the
 //      clamped values are the same bits.  cgd_op_abs_quantile runs the same kernels on a plain [B][n] array.
 //      With cap == floor every s_b is known (= cap): one launch writes x0c and thr3, and no selection launch runs.
-//   2. Thresholded update: dpmpp_update_kernel of dpm.hip reading x0c from the buffer and s_b from thr3[b * 3 + 2] (device memory: the host
-//      never reads it and nothing synchronises); one launch, the same plane / unit walk.
 // Scratch: (2 * B * S * 256 + 6 * B + B * S) uint32 with S = ceil(n / kSlice) (cgd_abs_quantile_scratch_bytes).  LDS: 1 KB histogram +
 // 48 bytes.  All tensors fp32; any 4-byte-aligned pointers and any n (16-byte accesses when every pointer is 16-byte aligned and 4 | n).
 #include "../../include/cgd_mi355x.h"
@@ -206,50 +205,6 @@ __global__ __launch_bounds__(256) void thr_finish_kernel(SelArgs a) {
   a.thr[b * 3 + 2] = fminf(fmaxf(q, a.floor), a.cap);
 }
 
-struct ThrArgs {
-  const float* x;
-  const float* x0;
-  const float* x0c;
-  const float* thr;
-  const float* noise;  // or null, read only when c_n != 0 and t != 0
-  const float* hist;   // or null, read only when c_r != 0
-  float* x0c_out;      // or null
-  float* sample;
-  float* x0o;          // or null
-  float cx, cd, cr, cn;
-};
-
-// dpmpp_update_kernel of dpm.hip with the thresholded x0c: grid.y walks the B * 3 planes, grid.x the plane in units of V floats
-template <int V>
-__global__ __launch_bounds__(256) void dpmpp_update_thr_kernel(ThrArgs a, StepCoef k, int planes, int HW) {
-  const int units = HW / V;
-  const bool second = a.cr != 0.f, noisy = a.cn != 0.f && k.nonzero;
-  for (int p = blockIdx.y; p < planes; p += gridDim.y) {
-    const long po = (long)p * HW;
-    const float sb = a.thr[(p / 3) * 3 + 2];
-    for (long u = blockIdx.x * blockDim.x + threadIdx.x; u < units; u += gridDim.x * blockDim.x) {
-      const long o = po + u * V;
-      float x[V], x0[V], nz[V], hs[V], x0c[V], s[V];
-      load<V>(a.x + o, x);
-      load<V>(a.x0c + o, x0c);
-      if (a.x0o) load<V>(a.x0 + o, x0);
-      if (second) load<V>(a.hist + o, hs);
-      if (noisy) load<V>(a.noise + o, nz);
-#pragma unroll
-      for (int e = 0; e < V; ++e) {
-        x0c[e] = fminf(fmaxf(x0c[e], -sb), sb) / sb;
-        const float d = second ? x0c[e] + a.cr * (x0c[e] - hs[e]) : x0c[e];
-        float m = a.cx * x[e] + a.cd * d;
-        if (noisy) m += a.cn * nz[e];
-        s[e] = k.nonzero ? m : x0c[e];
-      }
-      store<V>(a.sample + o, s);
-      if (a.x0c_out) store<V>(a.x0c_out + o, x0c);
-      if (a.x0o) store<V>(a.x0o + o, x0);
-    }
-  }
-}
-
 int slices_of(long n) { return (int)((n + kSlice - 1) / kSlice); }
 
 // the checks the two selecting entry points share; B and n are known to be positive
@@ -338,36 +293,6 @@ int cgd_launch_dpmpp_threshold(cgd_ctx* ctx, const float* x, const float* x0, co
     CGD_LAUNCH((thr_select_kernel<1, true, true>), grid, dim3(256), 0, s, a, kc, 0);
     launch_rest<1>(a, B, s);
   }
-  CGD_HIP(ctx, hipGetLastError());
-  return 0;
-}
-
-int cgd_launch_dpmpp_update_thr(cgd_ctx* ctx, const float* x, const float* x0, const float* x0c, const float* thr3, const float* noise,
-                                const float* x0_hist, float* x0c_out, float* sample, float* x0_out, int B, int H, int W, const StepCoef& k,
-                                const cgd_dpmpp& d, hipStream_t s) {
-  if (B <= 0 || H <= 0 || W <= 0) CGD_FAIL(ctx, "dpmpp thresholded update: empty shape");
-  if (!x || !x0 || !sample) CGD_FAIL(ctx, "dpmpp thresholded update: x, pred_xstart and sample are required");
-  if (!x0c || !thr3) CGD_FAIL(ctx, "dpmpp thresholded update: the x0c buffer and thr3 of cgd_dpmpp_threshold are required");
-  if (d.c_r != 0.f && !x0_hist)
-    CGD_FAIL(ctx, "dpmpp thresholded update: a second-order step (c_r != 0) needs the thresholded pred_xstart of the step before");
-  if (d.c_n != 0.f && k.nonzero && !noise) CGD_FAIL(ctx, "dpmpp thresholded update: the SDE step (c_n != 0) needs the step noise");
-  if (sample == x || (x0c_out && x0c_out == x) || (x0_out && x0_out == x)) CGD_FAIL(ctx, "dpmpp thresholded update: no output may alias x");
-  if ((x0c_out && x0c_out == sample) || (x0_out && (x0_out == sample || x0_out == x0c_out)))
-    CGD_FAIL(ctx, "dpmpp thresholded update: sample, x0c_out and pred_xstart_out must be distinct buffers");
-  if (sample == x0c || (x0c_out && x0c_out == x0c) || (x0_out && x0_out == x0c))
-    CGD_FAIL(ctx, "dpmpp thresholded update: no output may alias x0c");
-  if ((long)H * W > INT32_MAX || (long)B * 3 > INT32_MAX)
-    CGD_FAIL(ctx, "dpmpp thresholded update: a plane or the plane count exceeds 2^31 - 1");
-  ThrArgs a = {x, x0, x0c, thr3, noise, x0_hist, x0c_out, sample, x0_out, d.c_x, d.c_d, d.c_r, d.c_n};
-  const int planes = B * 3, HW = H * W;
-  const bool vec = HW % 4 == 0 && aligned16(x) && aligned16(x0) && aligned16(x0c) && aligned16(noise) && aligned16(x0_hist) &&
-                   aligned16(x0c_out) && aligned16(sample) && aligned16(x0_out);
-  const int units = vec ? HW / 4 : HW;
-  const dim3 grid(std::min(cdiv(units, 256), 1024), std::min(planes, 65535));
-  if (vec)
-    CGD_LAUNCH(dpmpp_update_thr_kernel<4>, grid, dim3(256), 0, s, a, k, planes, HW);
-  else
-    CGD_LAUNCH(dpmpp_update_thr_kernel<1>, grid, dim3(256), 0, s, a, k, planes, HW);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }

@@ -15,7 +15,7 @@ DPM-Solver++(2M) (`dpmpp_sample_loop_progressive`, Lu et al., 2022; eta = 0 the 
 'dpmN' (uniform in logSNR, diffusion.logsnr_timesteps): one guided evaluation per step and one cgd_dpmpp_update launch, which combines the
 evaluation's guided pred_xstart with the one of the step before; the two history buffers rotate by pointer.  With `threshold=` the guided
 pred_xstart is thresholded dynamically first (per sample: clamped to its own quantile of absolute values and rescaled): cgd_dpmpp_threshold
-selects the quantile on the device and cgd_dpmpp_update_thr updates (csrc/threshold.hip); without it nothing of that runs.
+selects the quantile on the device (csrc/threshold.hip) and cgd_dpmpp_update_thr updates (csrc/dpm.hip); without it nothing of that runs.
 DDIM inversion (`ddim_reverse_sample_loop_progressive`, `ddim_invert`; guided_diffusion's ddim_reverse_sample) runs the deterministic DDIM ODE
 upwards from an image: per step one UNet forward and one cgd_ddim_reverse_update launch.  `ddim_invert` returns the latent and the noise that
 q_samples the image to it, so every loop above starts from the latent when called with `noise=noise, init_image=image, skip_timesteps=s`.
@@ -185,15 +185,16 @@ class GuidedSampler:
 
     # ---- masked sampling ------------------------------------------------------------------------------
     def _known_noise(self, masked, x):
-        """Noise of the kept region for the next merge: the loop's initial noise in the deterministic loops (the tensor that q_sampled
-        the init image at the first index: the kept region follows one trajectory and nothing is drawn); in the stochastic loops the
-        tape's next entry, or None = a fresh draw that _evaluate takes right after the step's own noise."""
-        if not masked["stochastic"]:
-            return masked["x_T"]
+        """Before a step's evaluation -> (noise of the kept region for the next merge, whether _evaluate draws it instead): the loop's
+        initial noise in the deterministic loops (the tensor that q_sampled the init image at the first index: the kept region follows one
+        trajectory and nothing is drawn); in the stochastic loops the tape's next entry, or a fresh draw that _evaluate takes right after
+        the step's own noise.  (None, False) without a mask."""
+        if masked is None or not masked["stochastic"]:
+            return (masked["x_T"] if masked is not None else None), False
         if self.tape is None:
-            return None
+            return None, True
         masked["known"] += 1
-        return self.tape["known_noise"][masked["known"] - 1].to(x.device).float().contiguous()
+        return self.tape["known_noise"][masked["known"] - 1].to(x.device).float().contiguous(), False
 
     def _renoise(self, masked, x):
         """The draw that takes a merged state back up one level (resamples > 1): the tape's next entry or a fresh one."""
@@ -218,6 +219,13 @@ class GuidedSampler:
                                            L.ptr(n_re), L.ptr(x_re), B, H, W, init.shape[0], mask.shape[0], mask.shape[1], k, ctx.stream()))
         masked["_keep"] = (n_known, n_re)
         return x_re
+
+    def _masked_end(self, masked, ev, i, sample, x0_out, n_known, again=False):
+        """After a step's update: the merge with the kept region's noise (`n_known`, or the one `ev` drew).  `again`: this step index runs
+        once more, the re-noised state is returned; otherwise (and without a mask, where nothing runs) None."""
+        if masked is not None:
+            return self._merge(masked, i, sample, x0_out, n_known if n_known is not None else ev["n_known"],
+                               self._renoise(masked, sample) if again else None)
 
     @staticmethod
     def _check_mask(shape, init_image, mask, resamples, plms=False):
@@ -246,8 +254,8 @@ class GuidedSampler:
         followed by the merge; `again`: this step index runs once more, the merge also leaves the re-noised state in bufs['_x_re']."""
         ctx, lib = self.ctx, self.ctx.lib
         B, _, H, W = x.shape
-        n_known = self._known_noise(masked, x) if masked is not None else None
-        ev = self._evaluate(model, x, i, cond_fn, model_kwargs, noise, bufs, ahead, draw_known=masked is not None and n_known is None)
+        n_known, draw_known = self._known_noise(masked, x)
+        ev = self._evaluate(model, x, i, cond_fn, model_kwargs, noise, bufs, ahead, draw_known=draw_known)
         noise, g, coef = ev["noise"], ev["g"], ev["coef"]
         sample, x0_out = th.empty_like(x), th.empty_like(x)
         if eta:
@@ -263,8 +271,7 @@ class GuidedSampler:
                                             W, coef, mode, ctx.stream()))
         bufs["_keep"] = (noise, g, ev["ts"])
         if masked is not None:
-            bufs["_x_re"] = self._merge(masked, i, sample, x0_out, n_known if n_known is not None else ev["n_known"],
-                                        self._renoise(masked, x) if again else None)
+            bufs["_x_re"] = self._masked_end(masked, ev, i, sample, x0_out, n_known, again)
         return {"sample": sample, "pred_xstart": x0_out}
 
     def _plms_step(self, model, x, i, cond_fn, model_kwargs, bufs, st, masked=None):
@@ -278,6 +285,7 @@ class GuidedSampler:
         order, old = st["order"], st["old_eps"]
         eps_new = st["free"].pop() if st["free"] else th.empty_like(x)
         sample, x0_out = th.empty_like(x), th.empty_like(x)
+        n_known, _ = self._known_noise(masked, x)  # never stochastic: the loop's initial noise
         ev = self._evaluate(model, x, i, cond_fn, model_kwargs, None, bufs, draw_noise=False)
         g = ev["g"]
         if order > 1 and not old:
@@ -289,8 +297,7 @@ class GuidedSampler:
                                                eps_new.data_ptr(), xp.data_ptr(), x0_out.data_ptr(), B, H, W, ev["coef"], None,
                                                L.Multistep(1, 0, 0.0, 0.0), s))
             old.append(eps_new)
-            if masked is not None:
-                self._merge(masked, i, xp, None, masked["x_T"])
+            self._masked_end(masked, ev, i, xp, None, n_known)
             ev2 = self._evaluate(model, xp, i - 1, cond_fn, model_kwargs, None, bufs, draw_noise=False)
             hist = (C.c_void_p * 3)(eps_new.data_ptr(), None, None)
             k_t = self.tables.step_coef(i, ev["fac_index"])
@@ -310,8 +317,7 @@ class GuidedSampler:
         if len(old) >= order:
             st["free"].append(old.pop(0))
         bufs["_keep"] = keep
-        if masked is not None:
-            self._merge(masked, i, sample, x0_out, masked["x_T"])
+        self._masked_end(masked, ev, i, sample, x0_out, n_known)
         return {"sample": sample, "pred_xstart": x0_out}
 
     def _dpmpp_step(self, model, x, i, cond_fn, model_kwargs, noise, bufs, st, ahead=None, eta=0.0, masked=None, threshold=None):
@@ -324,9 +330,8 @@ class GuidedSampler:
         predictions.  The buffer, the (B, 3) result and the selection's scratch live in `bufs`, allocated once per loop."""
         ctx, lib = self.ctx, self.ctx.lib
         B, _, H, W = x.shape
-        n_known = self._known_noise(masked, x) if masked is not None else None
-        ev = self._evaluate(model, x, i, cond_fn, model_kwargs, noise, bufs, ahead, draw_noise=bool(eta),
-                            draw_known=masked is not None and n_known is None)
+        n_known, draw_known = self._known_noise(masked, x)
+        ev = self._evaluate(model, x, i, cond_fn, model_kwargs, noise, bufs, ahead, draw_noise=bool(eta), draw_known=draw_known)
         noise, g, hist = ev["noise"], ev["g"], st["hist"]
         d = self.tables.dpmpp_coef(i, 2 if (st["order"] == 2 and hist is not None) else 1, eta)
         x0c = None
@@ -354,8 +359,7 @@ class GuidedSampler:
             st["free"].append(hist)
         st["hist"] = x0c
         bufs["_keep"] = (noise, g, ev["ts"])
-        if masked is not None:
-            self._merge(masked, i, sample, x0_out, n_known if n_known is not None else ev["n_known"])
+        self._masked_end(masked, ev, i, sample, x0_out, n_known)
         return {"sample": sample, "pred_xstart": x0_out}
 
     # ---- loops ------------------------------------------------------------------------------------------
@@ -417,41 +421,36 @@ class GuidedSampler:
         # PLMS: its start step evaluates the model twice, EmbedAhead's one-embedding-per-step choreography does not apply (off);
         # neither does it to the repeated evaluations of resamples > 1
         ahead = EmbedAhead.create(self, model, cond_fn, img, indices) if (mode != 2 and resamples == 1) else None
-        evals = 0  # evaluations of the p_sample / DDIM loops so far: the tape's step noise is consumed per evaluation
-        plms = {"order": plms_order, "old_eps": [], "free": []} if mode == 2 else None
-        dpm = {"order": dpm_order, "hist": None, "free": []} if mode == 3 else None
+        # The step of this loop, chosen once.  `st`: the multistep history of PLMS / DPM-Solver++.  `tape_noise`: whether an evaluation
+        # consumes the replay tape's next step noise (where a step noise is drawn at all).  `ahead` is read at call time: the loop may drop it.
+        tape_noise = mode in (0, 1) or (mode == 3 and bool(eta))
+        if mode == 2:
+            st = {"order": plms_order, "old_eps": [], "free": []}
+            def step(x, i, noise, again):  # noqa: E306
+                return self._plms_step(model, x, i, cond_fn, model_kwargs, bufs, st, masked=masked)
+        elif mode == 3:
+            st = {"order": dpm_order, "hist": None, "free": []}
+            def step(x, i, noise, again):  # noqa: E306
+                return self._dpmpp_step(model, x, i, cond_fn, model_kwargs, noise, bufs, st, ahead=ahead, eta=eta, masked=masked,
+                                        threshold=threshold)
+        else:
+            def step(x, i, noise, again):
+                return self._step(model, x, i, cond_fn, model_kwargs, noise, mode, bufs, ahead=ahead, eta=eta, masked=masked, again=again)
+        evals = 0  # evaluations so far: the tape's step noise is consumed per evaluation
         for n, i in enumerate(it):
             if rand_y and (ahead is None or n == 0):
                 draw_y.n = n
                 model_kwargs["y"] = draw_y()
             if ahead is not None and n == 0:
                 ahead.launch(model, 0, model_kwargs.get("y"))
-            if plms is not None:
-                with th.no_grad():
-                    out = self._plms_step(model, img, i, cond_fn, model_kwargs, bufs, plms, *((masked,) if masked is not None else ()))
-                yield out
-                img = out["sample"]
-                continue
             # masked sampling with resamples = r: step index i > 0 runs r times; after each of the first r - 1 merges the state goes back
             # up one level (bufs['_x_re'], written by the merge's launch) and the step runs again.  One yield per step index.
             repeats = resamples if (masked is not None and i > 0) else 1
             for r in range(repeats):
-                if dpm is not None:
-                    # one evaluation per step (resamples is 1); the tape's step noise is read only where a noise is drawn (eta > 0)
-                    step_noise = tape["noise"][evals].to(device).float().contiguous() if (tape is not None and eta) else None
-                    evals += 1
-                    with th.no_grad():
-                        out = self._dpmpp_step(model, img, i, cond_fn, model_kwargs, step_noise, bufs, dpm,
-                                               *((ahead,) if ahead is not None else ()), **({"eta": eta} if eta else {}),
-                                               **({"masked": masked} if masked is not None else {}),
-                                               **({"threshold": threshold} if threshold is not None else {}))
-                    continue
-                step_noise = tape["noise"][evals].to(device).float().contiguous() if tape is not None else None
+                step_noise = tape["noise"][evals].to(device).float().contiguous() if (tape is not None and tape_noise) else None
                 evals += 1
                 with th.no_grad():
-                    out = self._step(model, img, i, cond_fn, model_kwargs, step_noise, mode, bufs, *((ahead,) if ahead is not None else ()),
-                                     **({"eta": eta} if eta else {}),
-                                     **({"masked": masked, "again": r + 1 < repeats} if masked is not None else {}))
+                    out = step(img, i, step_noise, r + 1 < repeats)
                 if r + 1 < repeats:
                     img = bufs.pop("_x_re")
             if ahead is not None and tape is not None and rand_y and n + 1 >= len(tape["y"]):
@@ -532,8 +531,7 @@ class GuidedSampler:
         self._check_mask(shape, init_image, mask, resamples)
         threshold = self._check_threshold(threshold)
         return self._loop(3, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad, eta=float(eta), mask=mask, dpm_order=order,
-                          **({"threshold": threshold} if threshold is not None else {}))
+                          randomize_class, cond_fn_with_grad, eta=float(eta), mask=mask, dpm_order=order, threshold=threshold)
 
     @staticmethod
     def _check_threshold(threshold):

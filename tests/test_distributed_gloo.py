@@ -149,7 +149,7 @@ def test_sampler_sharded_draws_are_rows_of_the_global_draws(monkeypatch):
         smp.shard = shard
         seen = []
 
-        def fake_step(model, x, i, cond_fn, model_kwargs, noise, mode, bufs):
+        def fake_step(model, x, i, cond_fn, model_kwargs, noise, mode, bufs, **kw):
             seen.append((x.clone(), smp._draw_like(x), model_kwargs["y"].clone()))
             return {"sample": x * 0.5, "pred_xstart": x}
 

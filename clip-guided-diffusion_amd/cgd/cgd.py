@@ -48,7 +48,9 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
                              "inverted latent has the init image's size")
 
     # "A+cuts=OV:IN" (an extension like "plmsN"): overview + inner cutouts through the antialiased cubic resize instead of pooled crops
-    towers_and_secondary, cuts = clip_util.split_cuts(clip_model_name, progressive_cutout, use_augs)  # refuses before any load
+    # "A+classifier=FILE:CLASS[:SCALE]" (likewise): classifier guidance with guided-diffusion's noisy ImageNet classifier
+    without_classifier, classifier_spec = clip_util.split_classifier(clip_model_name, height_offset, width_offset)  # refuses before any load
+    towers_and_secondary, cuts = clip_util.split_cuts(without_classifier, progressive_cutout, use_augs)  # refuses before any load
     # "A+secondary=FILE" (likewise): the guidance gradient returns through the secondary model instead of through the UNet
     clip_names, secondary_path = clip_util.split_secondary(towers_and_secondary, image_size, height_offset, width_offset)  # refuses before any load
 
@@ -133,6 +135,18 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         timestep_respacing=timestep_respacing, use_fp16=True, device=device, noise_schedule=noise_schedule, dropout=dropout)
     # (a collective like the loads above: before the early return of a rank without samples)
     secondary = clip_util.load_secondary(gd_model.ctx, secondary_path, device) if secondary_path is not None else None
+    classifier = None
+    if classifier_spec is not None:  # (a collective too)
+        classifier = clip_util.load_classifier(gd_model.ctx, classifier_spec[0], device, image_size)
+        if classifier.image_size != image_size:
+            raise ValueError(f"{classifier_spec[0]} is the {classifier.image_size}x{classifier.image_size} classifier, the run is {image_size}x{image_size}")
+        if not (0 <= classifier_spec[1] < classifier.out_channels):
+            raise ValueError(f"classifier=...:{classifier_spec[1]}: CLASS must be in [0, {classifier.out_channels})")
+        if class_cond:  # the diffusion model is steered toward the same class for the whole run
+            model_kwargs["y"] = th.full([local_batch], classifier_spec[1], device=device, dtype=th.long)
+            if randomize_class:
+                randomize_class = False
+                tqdm.write(f"classifier guidance: y is held at class {classifier_spec[1]} (randomize_class switched off)")
 
     if local_batch == 0:
         return  # more ranks than samples: this rank only took part in the weight broadcasts above (they are collectives)
@@ -157,7 +171,8 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         # "initialized lazily as it can use a bit of VRAM" (reference cgd.py:146-148): only with an init image and a non-zero scale
         lpips=script_util.load_lpips(gd_model.ctx, checkpoints_dir, device) if (init_tensor is not None and init_scale != 0) else None,
         init_tensor=init_tensor, init_scale=init_scale,
-        secondary=secondary)
+        secondary=secondary,
+        **({} if classifier is None else {"classifier": classifier, "classifier_scale": classifier_spec[2], "classifier_class": classifier_spec[1]}))
     if nranks > 1:
         cond_fn.shard = diffusion.shard = (mine, batch_size)
 
@@ -257,7 +272,7 @@ _CLI_SPEC = f"""
 --timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', 'plmsN' for PLMS (e.g. -respace plms50), or 'dpmN' / 'dpmsdeN' for DPM-Solver++(2M) / its SDE form on at most N logSNR-uniform levels (e.g. -respace dpm20); 'dpmN+thr=P' or 'dpmsdeN+thr=P:CAP' adds dynamic thresholding of the guided prediction: per sample it is clamped to its own P-quantile of absolute values s (at least 1, at most CAP) and divided by s (e.g. -respace dpm20+thr=0.995; CAP 1 is the static clip to [-1, 1])
 --num_cutouts -cutn int 16 | random cutouts shown to CLIP per step
 --cutout_power -cutpow float 1.0 | exponent of the cutout size distribution
---clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, ARCH=FILE for an open_clip ViT checkpoint (ARCH: ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14, optional -quickgelu suffix), 'A+B' to sum two towers, 'A+secondary=FILE' to guide through the secondary model FILE, or 'A+cuts=OV:IN' (or 'cuts=OV:IN/OV2:IN2': the second pair once 40 percent of the run is done) for OV whole-frame and IN random cutouts per step through the antialiased cubic resize (--num_cutouts then only affects image prompts)
+--clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, ARCH=FILE for an open_clip ViT checkpoint (ARCH: ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14, optional -quickgelu suffix), 'A+B' to sum two towers, 'A+secondary=FILE' to guide through the secondary model FILE, 'A+classifier=FILE:CLASS[:SCALE]' for classifier guidance toward ImageNet class CLASS with the noisy classifier FILE (weight SCALE, default 1; with a class-conditional model y is held at CLASS; needs zero height / width offsets), or 'A+cuts=OV:IN' (or 'cuts=OV:IN/OV2:IN2': the second pair once 40 percent of the run is done) for OV whole-frame and IN random cutouts per step through the antialiased cubic resize (--num_cutouts then only affects image prompts)
 --uncond -uncond flag | use the unconditional 256 / 512 checkpoints
 --noise_schedule -sched str linear | 'linear' or 'cosine'
 --dropout -drop float 0.0 | dropout of the diffusion model (inference: keep 0)

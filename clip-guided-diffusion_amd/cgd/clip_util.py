@@ -213,6 +213,159 @@ def load_secondary(ctx, path, device):
     return net
 
 
+def split_classifier(clip_model_name, height_offset=0, width_offset=0):
+    """The '+'-separated `--clip_model` list -> (the list without its `classifier=` entry, None or (FILE, CLASS, SCALE)).  A
+    `classifier=FILE:CLASS[:SCALE]` entry switches classifier guidance on (`cgd_amd.nets.NoisyClassifier`: the guidance loss gains
+    -SCALE * sum_b log p(CLASS | x_t, t), SCALE defaults to 1); it is a value like 'secondary=FILE' and 'cuts=OV:IN' and counts as no tower.
+    FILE may contain colons of its own: CLASS and SCALE are taken from the right.  Refused here, before anything is loaded (FILE is never
+    opened): more than one entry, an empty FILE, a missing or non-integer CLASS, a negative CLASS, SCALE <= 0 or not a number, a list with no
+    tower beside it, and a non-zero height or width offset (the classifier's positional embedding fixes the map size)."""
+    names, found = [], None
+    for entry in (n.strip() for n in clip_model_name.split("+")):
+        head, sep, value = entry.partition("=")
+        if not (sep and head.strip() == "classifier"):
+            names.append(entry)
+            continue
+        if found is not None:
+            raise ValueError(f"{clip_model_name}: more than one 'classifier=' entry")
+        usage = f"{entry}: expected 'classifier=FILE:CLASS' or 'classifier=FILE:CLASS:SCALE' (CLASS an integer class id, SCALE > 0)"
+        fields = [f.strip() for f in value.strip().split(":")]
+
+        def is_int(f):
+            return f.isdigit() or (f[:1] in "+-" and f[1:].isdigit())
+
+        def is_number(f):
+            try:
+                float(f)
+            except ValueError:
+                return False
+            return True
+
+        # taken from the right: two trailing numeric fields with an integer first are CLASS:SCALE, one trailing integer is CLASS
+        if len(fields) >= 3 and is_int(fields[-2]) and is_number(fields[-1]):
+            path, cls, scale = ":".join(fields[:-2]), int(fields[-2]), float(fields[-1])
+        elif len(fields) >= 2 and is_int(fields[-1]):
+            path, cls, scale = ":".join(fields[:-1]), int(fields[-1]), 1.0
+        else:
+            raise ValueError(usage)
+        if not path:
+            raise ValueError(usage)
+        if cls < 0:
+            raise ValueError(f"{entry}: CLASS must be a non-negative class id")
+        if not (0.0 < scale < float("inf")):
+            raise ValueError(f"{entry}: SCALE must be a positive number, got {fields[-1]}")
+        found = (path, cls, scale)
+    if found is not None:
+        if not any(n and not n.startswith(("secondary=", "cuts=")) for n in names):
+            raise ValueError(f"{clip_model_name}: 'classifier=' needs a CLIP tower beside it, e.g. 'ViT-B/32+classifier=FILE:207'")
+        if height_offset or width_offset:
+            raise ValueError("'classifier=' needs height_offset = width_offset = 0: the classifier's positional embedding fixes the map size "
+                             f"(got {height_offset}, {width_offset})")
+    return "+".join(names), found
+
+
+def classifier_config_from_state_dict(sd, num_head_channels=None):
+    """The configuration of a noisy-classifier checkpoint (guided-diffusion's `EncoderUNetModel`, pool="attention"), as the keyword arguments
+    of `cgd_amd.nets.NoisyClassifier`, and the cleaned state dict: -> (state dict, kwargs).  Every dimension is inferred from shapes and the
+    key set: the width from `time_embed.0.weight` / `input_blocks.0.0.weight`, the final map S from the positional embedding (S*S + 1
+    positions), the classes from `out.2.c_proj`, levels and depth from the numbered input blocks (the one split of them into `levels` runs of
+    `depth` blocks with a `down` block between runs in which every run has one width and one attention flag and no `down` block attends or
+    changes the width), image_size = S * 2^(levels-1), channel_mult and the attention resolutions from the runs.  The head width is in no
+    shape: it comes from `nets.CLASSIFIER_CONFIGS[image_size]`, else from `num_head_channels`, else 64.  For a published size everything
+    inferred must equal the table's entry.  A `{'state_dict': ...}` wrapper and `module.` prefixes are removed.  ValueError names what does
+    not fit."""
+    sd = _openclip_clean_state_dict(sd)
+    for key in ("input_blocks.0.0.weight", "out.2.positional_embedding", "out.2.qkv_proj.weight", "out.2.c_proj.weight", "time_embed.0.weight"):
+        if key not in sd:
+            raise ValueError(f"classifier checkpoint: no '{key}' (not an EncoderUNetModel with pool='attention')")
+    if any(k.startswith(("output_blocks.", "label_emb.")) for k in sd):
+        raise ValueError("classifier checkpoint: it has output_blocks / label_emb — a diffusion UNet, not a classifier")
+    ch0 = int(sd["input_blocks.0.0.weight"].shape[0])
+    width = int(sd["time_embed.0.weight"].shape[1])
+    idx = sorted({int(k.split(".")[1]) for k in sd if k.startswith("input_blocks.")})
+    if idx != list(range(len(idx))):
+        raise ValueError(f"classifier checkpoint: input_blocks are not numbered 0..{len(idx) - 1} (a level is missing)")
+    widths, att = [], []
+    for i in idx[1:]:
+        k = f"input_blocks.{i}.0.in_layers.2.weight"
+        if k not in sd:
+            raise ValueError(f"classifier checkpoint: no '{k}'")
+        widths.append(int(sd[k].shape[0]))
+        att.append(f"input_blocks.{i}.1.qkv.weight" in sd)
+    C, T = (int(v) for v in sd["out.2.positional_embedding"].shape)
+    S = round((T - 1) ** 0.5)
+    if S < 1 or S * S + 1 != T:
+        raise ValueError(f"classifier checkpoint: positional_embedding has {T} positions, not S*S + 1")
+    if tuple(sd["out.2.qkv_proj.weight"].shape[:2]) != (3 * C, C):
+        raise ValueError(f"classifier checkpoint: qkv_proj.weight is {tuple(sd['out.2.qkv_proj.weight'].shape)}, not (3C, C) with C = {C}")
+    out_channels = int(sd["out.2.c_proj.weight"].shape[0])
+    n = len(widths)
+    fits = []
+    for depth in range(1, n + 1):
+        if (n + 1) % (depth + 1):
+            continue
+        levels = (n + 1) // (depth + 1)
+        runs, ok, prev = [], levels <= 8, ch0
+        for level in range(levels):
+            lo = level * (depth + 1)
+            run_w, run_a = widths[lo:lo + depth], att[lo:lo + depth]
+            ok = ok and len(set(run_w)) == 1 and len(set(run_a)) == 1
+            if level != levels - 1:  # the `down` block behind the run: same width, no attention
+                ok = ok and widths[lo + depth] == run_w[0] and not att[lo + depth]
+            runs.append((run_w[0], run_a[0]))
+        if ok:
+            fits.append((levels, depth, runs))
+    if len(fits) != 1:
+        raise ValueError(f"classifier checkpoint: the {n} input blocks after the stem split into levels of equal depth in {len(fits)} ways "
+                         "(a level is missing, or the block widths / attention blocks are not an EncoderUNetModel's)")
+    levels, depth, runs = fits[0]
+    if runs[0][0] != ch0 or runs[-1][0] != C:
+        raise ValueError(f"classifier checkpoint: first / last level widths {runs[0][0]} / {runs[-1][0]} against the stem's {ch0} and the pool's {C}")
+    if width <= 0 or any(w * 2 % width for w, _ in runs):
+        raise ValueError(f"classifier checkpoint: level widths {[w for w, _ in runs]} are not multiples of half the width {width}")
+    size = S * 2 ** (levels - 1)
+    mult = tuple((w // width) if w % width == 0 else w / width for w, _ in runs)
+    res = [size >> level for level, (_, a) in enumerate(runs) if a]
+    if not res:
+        raise ValueError("classifier checkpoint: no level carries attention")
+    table = _nets.CLASSIFIER_CONFIGS.get(size)
+    kw = dict(image_size=size, model_channels=width, num_res_blocks=depth, attention_resolutions=",".join(str(r) for r in res),
+              channel_mult=mult, num_head_channels=int(table["num_head_channels"] if table else (num_head_channels or 64)), out_channels=out_channels)
+    if table:
+        for name in ("model_channels", "num_res_blocks", "attention_resolutions", "channel_mult", "out_channels"):
+            got, want = kw[name], table[name]
+            if (tuple(float(v) for v in got) != tuple(float(v) for v in want)) if name == "channel_mult" else got != want:
+                raise ValueError(f"classifier checkpoint ({size}x{size}): {name} {got}, the published architecture has {want}")
+    if C % kw["num_head_channels"]:
+        raise ValueError(f"classifier checkpoint: final width {C} is not a whole number of {kw['num_head_channels']}-wide heads")
+    return sd, kw
+
+
+def load_classifier(ctx, path, device, image_size=None):
+    """The device classifier (`classifier=FILE:CLASS[:SCALE]`): FILE is a published NxN_classifier.pt state dict, read on rank 0 and
+    broadcast; with CGD_SYNTHETIC_WEIGHTS=1 seeded random weights of the `image_size` classifier, FILE is not read."""
+    dev = f"cuda:{ctx.device}"
+    if script_util.synthetic_weights_enabled():
+        if image_size not in _nets.CLASSIFIER_CONFIGS:
+            raise ValueError(f"no published classifier for image size {image_size}: {sorted(_nets.CLASSIFIER_CONFIGS)}")
+        net = _nets.NoisyClassifier(ctx, **_nets.CLASSIFIER_CONFIGS[image_size])
+        _shard.load_broadcast(net, lambda: _synthetic.classifier_state_dict(net.cfg, device=dev), dev)
+        return net
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path} not found (set CGD_SYNTHETIC_WEIGHTS=1 for seeded random weights)")
+    held = {}
+
+    def probe():  # rank 0 only: the other ranks receive the configuration, never the file
+        held["sd"], kw = classifier_config_from_state_dict(th.load(path, map_location="cpu"))
+        return kw
+
+    kw = _shard.on_rank0(probe)
+    net = _nets.NoisyClassifier(ctx, **kw)
+    _shard.load_broadcast(net, lambda: {k: v.float() for k, v in held["sd"].items()}, dev)
+    held.clear()
+    return net
+
+
 def _openclip_clean_state_dict(sd):
     """open_clip training checkpoints wrap the weights ({'state_dict': ...}) and DataParallel prefixes every key with 'module.'; entries that are
     not tensors go (epoch counters and the like).  `logit_scale`, `attn_mask` and other tensors no tower asks for are simply never read."""

@@ -147,3 +147,34 @@ int cgd_launch_ddim_reverse_update(cgd_ctx* ctx, const float* x, const float* ou
 //   host-side broadcast rules), loss_part: per-(cut,b) partial losses [cutn*B] (already * scale / cutn)
 int cgd_launch_spherical_loss(cgd_ctx* ctx, const float* emb, const float* targets, const float* weights, float* demb,
                               float* loss_part, int cutn, int B, int P, int D, float scale, hipStream_t s);
+
+// ---- classifier.hip: the head of the noisy ImageNet classifier (guided_diffusion.unet.AttentionPool2d + log-softmax-select) -------------
+// h [B * S2][C] NHWC rows (the SiLU(GroupNorm) output) -> tokens [mean | h_0 .. h_{S2-1}] + positional embedding (T = S2 + 1) -> qkv_proj ->
+// attention of token 0's query over all T keys per head (new order: [Q all heads | K | V]) -> c_proj -> logits -> log-softmax-select.
+struct AttnPoolShape {
+  int B, S2, C, d, out;  // samples, spatial positions, channels, head width (heads = C / d), classes
+  int weight;            // 1: the weights are persistent (a network handle's): the GEMM launcher may cache packed copies of them
+};
+struct AttnPoolWeights {
+  const float* posT;   // [T][C]: positional_embedding [C][T] transposed
+  const float* qkvw;   // [3C][C]
+  const float* qkvb;   // [3C]
+  const float* qkvwT;  // [C][3C]
+  const float* cw;     // [out][C]
+  const float* cb;     // [out]
+  const float* cwT;    // [C][outP], outP = out rounded up to 4, pad columns zero (cgd_attnpool_pack_cwT)
+};
+// floats of the scratch of one call shape (activations kept for the backward + the backward's temporaries)
+size_t cgd_attnpool_scratch_floats(const AttnPoolShape& sh);
+// the largest (T, d) the single-query attention kernels keep in LDS
+bool cgd_attnpool_supported(int S2, int C, int d, int out);
+int cgd_attnpool_pack_cwT(cgd_ctx* ctx, const float* cw, float* cwT, int out, int C, hipStream_t s);
+// y [B] class ids; logits [B][out] or null; logp [B] or null (logp[b] = log_softmax(logits[b])[y[b]]); pooled [B][C] or null: the attention
+// output of token 0 in front of c_proj
+int cgd_attnpool_fwd(cgd_ctx* ctx, const AttnPoolShape& sh, const AttnPoolWeights& w, const float* h, int ldh, const int64_t* y, float* pooled,
+                     float* logits, float* logp, float* scratch, hipStream_t s);
+// dh [B * S2][C] (row stride lddh) = scale * d(sum_b logp[b]) / dh of the forward that filled `scratch`
+int cgd_attnpool_bwd(cgd_ctx* ctx, const AttnPoolShape& sh, const AttnPoolWeights& w, float scale, float* dh, int lddh, float* scratch,
+                     hipStream_t s);
+// g += d (n floats, n a multiple of 4, 16-byte aligned)
+int cgd_launch_accumulate(cgd_ctx* ctx, float* g, const float* d, long n, hipStream_t s);

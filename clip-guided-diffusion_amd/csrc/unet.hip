@@ -42,6 +42,8 @@ int cgd_pack_conv3x3(cgd_ctx* ctx, const float* w, float* wf, float* wd, int Co,
   return 0;
 }
 
+int cgd_plan_gemm(cgd_ctx* ctx, GemmParams& p, int* tile_out, int* kernel_out);  // gemm.hip: the launcher's host-only kernel selection
+
 namespace {
 
 struct UNet;
@@ -93,6 +95,7 @@ struct AttnBlock : Module {
 struct UNet : NetBase {
   int ensure_wino(ResBlock* rb, long pixels, hipStream_t s);
   cgd_unet_config cfg;
+  bool encoder_only = false;  // the noisy classifier's trunk (Classifier below): build() stops after middle_block, no decoder and no conv head
   int ted = 0, ch0 = 0, ch_last = 0;
   long emb_total = 0;
   std::vector<std::vector<std::unique_ptr<Module>>> in_blocks;  // in_blocks[0] is the stem conv (empty vector)
@@ -353,7 +356,7 @@ int UNet::build() {
   const int mc = cfg.model_channels;
   // configuration checks first (found by the host-sanitizer driver, tests/asan_host_driver.cpp: an empty channel_mult list used to
   // "build" a model without levels): everything the plan below divides by or indexes with
-  if (cfg.in_channels != 3 || (cfg.out_channels != 6 && cfg.out_channels != 3)) CGD_FAIL(ctx, "unet: in_channels must be 3, out_channels 3 or 6");
+  if (cfg.in_channels != 3 || (!encoder_only && cfg.out_channels != 6 && cfg.out_channels != 3)) CGD_FAIL(ctx, "unet: in_channels must be 3, out_channels 3 or 6");
   if (cfg.n_mult < 1 || cfg.n_mult > 8) CGD_FAIL(ctx, "unet: bad channel_mult");
   if (cfg.n_att < 0 || cfg.n_att > 8) CGD_FAIL(ctx, "unet: at most 8 attention resolutions");
   if (mc <= 0 || mc % 32) CGD_FAIL(ctx, "unet: model_channels must be a positive multiple of 32 (GroupNorm32)");
@@ -452,6 +455,10 @@ int UNet::build() {
   mid.push_back(make_rb("middle_block.0", ch, ch, false, false));
   mid.push_back(make_att("middle_block.1", ch));
   mid.push_back(make_rb("middle_block.2", ch, ch, false, false));
+  if (encoder_only) {
+    ch_last = ch;
+    return 0;
+  }
   std::vector<int> chans = in_chans;
   int oidx = 0;
   for (int level = cfg.n_mult - 1; level >= 0; --level) {
@@ -542,11 +549,13 @@ int UNet::finalize(hipStream_t s) {
   if (!stem_wf) {
     CGD_TRY(alloc(&stem_wf, (size_t)ch0 * cfg.in_channels * 9));
     CGD_TRY(alloc(&stem_wd, (size_t)ch0 * cfg.in_channels * 9));
-    CGD_TRY(alloc(&head_wf, (size_t)ch0 * cfg.out_channels * 9));
-    CGD_TRY(alloc(&head_wd, (size_t)ch0 * cfg.out_channels * 9));
+    if (!encoder_only) {
+      CGD_TRY(alloc(&head_wf, (size_t)ch0 * cfg.out_channels * 9));
+      CGD_TRY(alloc(&head_wd, (size_t)ch0 * cfg.out_channels * 9));
+    }
   }
   CGD_TRY(cgd_pack_conv3x3(ctx, P("input_blocks.0.0.weight"), stem_wf, stem_wd, ch0, cfg.in_channels, s));
-  CGD_TRY(cgd_pack_conv3x3(ctx, P("out.2.weight"), head_wf, head_wd, cfg.out_channels, ch0, s));
+  if (!encoder_only) CGD_TRY(cgd_pack_conv3x3(ctx, P("out.2.weight"), head_wf, head_wd, cfg.out_channels, ch0, s));
   if (!freqs) {
     const int half = cfg.model_channels / 2;
     std::vector<float> f(half);
@@ -714,10 +723,146 @@ int UNet::dgrad(const float* gout, float* gx, hipStream_t s) {
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The noisy ImageNet classifier of guided-diffusion (EncoderUNetModel, pool="attention"): the encoder half of the UNet above — same time embedding
+// (no label_emb), stem, ResBlocks, AttentionBlocks (legacy order) and middle_block, built by UNet::build() in its encoder-only form — followed by
+// out.0 (GroupNorm32) -> SiLU -> out.2 (AttentionPool2d, classifier.hip).  dgrad returns d(sum_b log p(y_b | x_b, t_b)) / dx.
+struct Classifier : UNet {
+  cgd_classifier_config cfg;  // (hides UNet::cfg, which build() fills from it)
+  int S = 0, Cl = 0;          // side of the final map and its channels
+  float *posT = 0, *qkvwT = 0, *cwT = 0;
+  DevBuf pool, dxb;
+  int build();
+  int finalize(hipStream_t s);
+  int forward(const float* x, const float* t, const int64_t* y, float* logits, float* logp, int Bn, int Hh, int Ww, hipStream_t s);
+  int dgrad(float scale, float* gx, int accumulate, hipStream_t s);
+  AttnPoolShape shape() const { return AttnPoolShape{B, S * S, Cl, cfg.num_head_channels, cfg.out_channels, 1}; }
+  AttnPoolWeights weights() {
+    return AttnPoolWeights{posT, P("out.2.qkv_proj.weight"), P("out.2.qkv_proj.bias"), qkvwT, P("out.2.c_proj.weight"), P("out.2.c_proj.bias"), cwT};
+  }
+};
+
+int Classifier::build() {
+  if (cfg.n_mult < 1 || cfg.n_mult > 8) CGD_FAIL(ctx, "classifier: bad channel_mult");
+  if (cfg.out_channels <= 0) CGD_FAIL(ctx, "classifier: out_channels must be positive");
+  if (cfg.num_head_channels <= 0) CGD_FAIL(ctx, "classifier: num_head_channels must be positive");
+  cgd_unet_config& u = UNet::cfg;
+  u = cgd_unet_config{};
+  u.image_size = cfg.image_size; u.model_channels = cfg.model_channels; u.num_res_blocks = cfg.num_res_blocks; u.n_mult = cfg.n_mult;
+  for (int i = 0; i < 8; ++i) {
+    u.channel_mult[i] = cfg.channel_mult[i];
+    u.attention_ds[i] = cfg.attention_ds[i];
+  }
+  u.n_att = cfg.n_att; u.num_classes = 0; u.num_heads = 1; u.num_head_channels = cfg.num_head_channels; u.use_new_attention_order = 0;
+  u.in_channels = 3; u.out_channels = cfg.out_channels;
+  encoder_only = true;
+  CGD_TRY(UNet::build());
+  // the middle_block and the pool always attend: their width must be a whole number of heads
+  Cl = ch_last;
+  S = cfg.image_size >> (cfg.n_mult - 1);
+  if (Cl % cfg.num_head_channels) CGD_FAIL(ctx, "classifier: the width of the last level must be divisible by num_head_channels");
+  if (!cgd_attnpool_supported(S * S, Cl, cfg.num_head_channels, cfg.out_channels))
+    CGD_FAIL(ctx, "classifier: the final map (" + std::to_string(S) + " x " + std::to_string(S) + " positions, head width " +
+                      std::to_string(cfg.num_head_channels) + ") does not fit the attention-pool kernels (K and V of one head in 64 KB of LDS)");
+  // every 3x3 conv of the trunk at the configuration's own resolution against what the conv launcher accepts (host-only planning)
+  for (size_t i = 1; i < in_blocks.size(); ++i)
+    for (auto& m : in_blocks[i]) {
+      const ResBlock* rb = dynamic_cast<const ResBlock*>(m.get());
+      if (!rb) continue;
+      const int res = cfg.image_size / in_ds[i];  // resolution of the block's convs (a `down` block convolves at its output size)
+      for (int k = 0; k < 2; ++k) {
+        GemmParams p;
+        float* const dummy = (float*)(uintptr_t)4096;  // only the alignment of the pointers is inspected
+        p.A = p.B = dummy; p.C = dummy; p.Bpk = p.Bwk = dummy;
+        p.conv = 1; p.H = p.W = res; p.M = res * res; p.N = rb->cout; p.Cin = k ? rb->cout : rb->cin;
+        p.lda = p.Cin; p.ldb = 9 * p.Cin; p.ldc = p.N;
+        int tile = 0, kernel = 0;
+        if (cgd_plan_gemm(ctx, p, &tile, &kernel) != 0)
+          CGD_FAIL(ctx, "classifier: the conv kernels cannot run " + rb->pre + " (" + std::to_string(p.Cin) + " -> " + std::to_string(p.N) + " channels at " +
+                            std::to_string(res) + " x " + std::to_string(res) + "): " + ctx->err);
+      }
+    }
+  add_param("out.0.weight", Cl);
+  add_param("out.0.bias", Cl);
+  add_param("out.2.positional_embedding", (int64_t)Cl * (S * S + 1));
+  add_param("out.2.qkv_proj.weight", (int64_t)3 * Cl * Cl);
+  add_param("out.2.qkv_proj.bias", 3 * Cl);
+  add_param("out.2.c_proj.weight", (int64_t)cfg.out_channels * Cl);
+  add_param("out.2.c_proj.bias", cfg.out_channels);
+  return 0;
+}
+
+int Classifier::finalize(hipStream_t s) {
+  CGD_TRY(UNet::finalize(s));
+  finalized = false;
+  CGD_TRY(transpose_weight(P("out.2.positional_embedding"), &posT, Cl, S * S + 1, s));
+  CGD_TRY(transpose_weight(P("out.2.qkv_proj.weight"), &qkvwT, 3 * Cl, Cl, s));
+  if (!cwT) CGD_TRY(alloc(&cwT, (size_t)Cl * ((cfg.out_channels + 3) & ~3)));
+  CGD_TRY(cgd_attnpool_pack_cwT(ctx, P("out.2.c_proj.weight"), cwT, cfg.out_channels, Cl, s));
+  CGD_HIP(ctx, hipStreamSynchronize(s));
+  finalized = true;
+  return 0;
+}
+
+int Classifier::forward(const float* x, const float* t, const int64_t* y, float* logits, float* logp, int Bn, int Hh, int Ww, hipStream_t s) {
+  have_fwd = false;  // a refused or failed forward leaves nothing a dgrad could belong to
+  if (!finalized) CGD_FAIL(ctx, "classifier: finalize() has not been called after the last set_param");
+  if (!x || !t || !y) CGD_FAIL(ctx, "classifier: x, timesteps and y are required");
+  if (Bn <= 0 || Hh != cfg.image_size || Ww != cfg.image_size)
+    CGD_FAIL(ctx, "classifier: H and W must equal image_size (" + std::to_string(cfg.image_size) + "): the positional embedding fixes the map size");
+  CGD_TRY(embed(t, nullptr, Bn, 0, s));
+  emb_cur = emb_all.p;
+  B = Bn; H = Hh; W = Ww;
+  fwd_prec = ctx->precision;
+  ++ctx->stats_serial;  // conv-epilogue statistics of earlier passes are dead from here on (ChanStatsEntry)
+  CGD_TRY(ensure(h0, (size_t)B * H * W * ch0));
+  CGD_TRY(cgd_launch_conv_in(ctx, x, stem_wf, P("input_blocks.0.0.bias"), h0.p, B, H, W, 3, ch0, s));
+  TV h{h0.p, ch0, ch0};
+  int ch = H, cw = W;
+  for (size_t i = 1; i < in_blocks.size(); ++i)
+    for (auto& m : in_blocks[i]) CGD_TRY(m->fwd(*this, h, B, ch, cw, &h, s));
+  for (auto& m : mid) CGD_TRY(m->fwd(*this, h, B, ch, cw, &h, s));
+  if (ch != S || cw != S || h.C != Cl) CGD_FAIL(ctx, "classifier: map bookkeeping mismatch");
+  // ---- head: GN -> SiLU -> AttentionPool2d -> log-softmax-select ----
+  head_in = h;
+  CGD_TRY(ensure(head_s, cgd_gn_scratch_floats(B, S * S, Cl)));
+  CGD_TRY(ensure(headn, (size_t)B * S * S * Cl));
+  CGD_TRY(ensure(pool, cgd_attnpool_scratch_floats(shape())));
+  CGD_TRY(ensure(dxb, (size_t)B * 3 * H * W));  // (an accumulating dgrad's buffer: here, so that no dgrad of a seen shape allocates)
+  CGD_TRY(cgd_launch_gn_fwd(ctx, h.p, h.ld, headn.p, Cl, B, S * S, Cl, P("out.0.weight"), P("out.0.bias"), nullptr, 0, 1, 1e-5f, head_s.p, s));
+  CGD_TRY(cgd_attnpool_fwd(ctx, shape(), weights(), headn.p, Cl, y, nullptr, logits, logp, pool.p, s));
+  have_fwd = true;
+  return 0;
+}
+
+int Classifier::dgrad(float scale, float* gx, int accumulate, hipStream_t s) {
+  if (!finalized) CGD_FAIL(ctx, "classifier: finalize() has not been called after the last set_param");
+  if (!have_fwd) CGD_FAIL(ctx, "classifier: dgrad() needs a preceding forward()");
+  if (fwd_prec != ctx->precision) CGD_FAIL(ctx, "classifier: dgrad() under another precision mode than its forward()");
+  if (!gx) CGD_FAIL(ctx, "classifier: g_x is required");
+  ++ctx->stats_serial;
+  CGD_TRY(ensure(dheadn, (size_t)B * S * S * Cl));
+  CGD_TRY(ensure(dhead, (size_t)B * S * S * Cl));
+  CGD_TRY(cgd_attnpool_bwd(ctx, shape(), weights(), scale, dheadn.p, Cl, pool.p, s));
+  CGD_TRY(cgd_launch_gn_bwd(ctx, head_in.p, head_in.ld, dheadn.p, Cl, dhead.p, Cl, nullptr, 0, B, S * S, Cl, 1, head_s.p, s));
+  TV d{dhead.p, Cl, Cl};
+  for (int j = (int)mid.size() - 1; j >= 0; --j) CGD_TRY(mid[j]->bwd(*this, d, &d, s));
+  for (int i = (int)in_blocks.size() - 1; i >= 1; --i)
+    for (int j = (int)in_blocks[i].size() - 1; j >= 0; --j) CGD_TRY(in_blocks[i][j]->bwd(*this, d, &d, s));
+  // stem dgrad: NHWC (ch0) -> NCHW (3), straight into g_x or, accumulating, through a buffer of its own
+  float* const dst = accumulate ? dxb.p : gx;
+  CGD_TRY(cgd_launch_conv_thin_out(ctx, d.p, d.ld, stem_wd, nullptr, dst, B, H, W, ch0, 3, s));
+  if (accumulate) CGD_TRY(cgd_launch_accumulate(ctx, gx, dxb.p, (long)B * 3 * H * W, s));
+  return 0;
+}
+
 }  // namespace
 
 struct cgd_unet {
   UNet net;
+};
+struct cgd_classifier {
+  Classifier net;
 };
 
 extern "C" {
@@ -753,5 +898,31 @@ int cgd_unet_forward_slot(cgd_unet* u, const float* x, int slot, float* out, int
 }
 int cgd_unet_dgrad(cgd_unet* u, const float* g_out, float* g_x, void* stream) {
   return net_pass(u, stream, [&](hipStream_t s) { return u->net.dgrad(g_out, g_x, s); });
+}
+}
+
+extern "C" {
+int cgd_classifier_create(cgd_ctx* ctx, const cgd_classifier_config* cfg, cgd_classifier** out) { return net_create(ctx, out, cfg); }
+int cgd_classifier_manifest(const cgd_classifier_config* cfg, void (*cb)(const char*, int64_t, void*), void* user) {
+  return net_manifest<Classifier>(cb, user, cfg);
+}
+void cgd_classifier_destroy(cgd_classifier* c) {
+  if (c) {  // as cgd_unet_destroy: the conv-epilogue record buffers are keyed by activation pointers that die with the net
+    DeviceScope dev_scope(c->net.ctx);
+    (void)hipDeviceSynchronize();
+    cgd_chanstats_clear(c->net.ctx);
+  }
+  net_destroy(c);
+}
+int cgd_classifier_num_params(cgd_classifier* c) { return net_num_params(c); }
+int cgd_classifier_param_info(cgd_classifier* c, int i, char* buf, int len, int64_t* numel) { return net_param_info(c, i, buf, len, numel); }
+int cgd_classifier_set_param(cgd_classifier* c, const char* name, const float* data, int64_t numel) { return net_set_param(c, name, data, numel); }
+int cgd_classifier_finalize(cgd_classifier* c) { return net_finalize(c); }
+int cgd_classifier_forward(cgd_classifier* c, const float* x, const float* t, const int64_t* y, float* logits, float* logp, int B, int H, int W,
+                           void* stream) {
+  return net_pass(c, stream, [&](hipStream_t s) { return c->net.forward(x, t, y, logits, logp, B, H, W, s); });
+}
+int cgd_classifier_dgrad(cgd_classifier* c, float scale, float* g_x, int accumulate, void* stream) {
+  return net_pass(c, stream, [&](hipStream_t s) { return c->net.dgrad(scale, g_x, accumulate, s); });
 }
 }

@@ -573,7 +573,7 @@ class ClipGuidance:
     def __init__(self, ctx, unet, clip_tower, diffusion, target_embeds, weights, num_cutouts, cutout_power=1.0,
                  clip_guidance_scale=1000.0, tv_scale=150.0, range_scale=50.0, sat_scale=0.0, use_magnitude=False,
                  reduce_clip=False, progressive_cutout=False, cached_cutouts=False, make_cutouts=None, lpips=None, init_tensor=None,
-                 init_scale=0.0, secondary=None):
+                 init_scale=0.0, secondary=None, classifier=None, classifier_scale=1.0, classifier_class=None):
         # Multi-CLIP (BASELINE config 5, a build extension: the reference takes one clip_model_name): `clip_tower` / `target_embeds`
         # may be lists; the CLIP losses of the towers are summed (same cutout boxes, prompt weights and guidance scale).
         self.towers = list(clip_tower) if isinstance(clip_tower, (list, tuple)) else [clip_tower]
@@ -600,6 +600,17 @@ class ClipGuidance:
         # secondary model (nets.SecondaryModel) or None: with one, pred / x_in of the guidance losses come from it and the gradient returns to x
         # through it; the UNet's backward pass is not run (its forward still gives the update's mean, variance and the yielded pred_xstart)
         self.secondary = secondary
+        # noisy classifier (nets.NoisyClassifier) or None: with one, the loss gains -classifier_scale * sum_b log p(classifier_class | x_t, t),
+        # evaluated on the step's x at the model timesteps the UNet's forward received; its gradient joins the direct part of g
+        self.classifier, self.classifier_scale, self.classifier_class = classifier, float(classifier_scale), classifier_class
+        if classifier is not None:
+            if classifier_class is None or not (0 <= int(classifier_class) < classifier.out_channels):
+                raise ValueError(f"classifier_class must be a class id in [0, {classifier.out_channels}), got {classifier_class}")
+            if not (self.classifier_scale > 0):
+                raise ValueError(f"classifier_scale must be positive, got {classifier_scale}")
+            self.classifier_class = int(classifier_class)
+        self.classifier_logp = None
+        self.step_ts = None      # set by the sampler before native(): the model timesteps of the step's UNet forward
         self.lpips_loss = None
         self.current_timestep = None  # closure counter of cgd.py:149,265-267
         self.scalars = None
@@ -663,10 +674,11 @@ class ClipGuidance:
         return alpha, sigma, math.atan2(sigma, alpha) * 2.0 / math.pi
 
     # -- the native gradient ---------------------------------------------------------------------------
-    def native(self, x, x0, x_in, coef):
+    def native(self, x, x0, x_in, coef, ts=None):
         """x, x0 = pred_xstart, x_in = blend: (B,3,H,W) on the GPU.  Returns g (B,3,H,W) or None when the
         reduce_clip gate skips this step (the reference returns zeros_like(x)).  With a secondary model, x0 and x_in are replaced by
-        its prediction from x and the blend of that, and g = -dL/dx runs back through it instead of through the UNet."""
+        its prediction from x and the blend of that, and g = -dL/dx runs back through it instead of through the UNet.  `ts` (B,): the model
+        timesteps the UNet's forward received at this step (default: `step_ts`, which the sampler sets); only a classifier reads them."""
         skip, cutn = self.schedule()
         self.last_ran = not skip
         if skip:
@@ -752,6 +764,18 @@ class ClipGuidance:
             ctx.check(lib.cgd_guidance_combine(ctx.h, gclip.data_ptr(), x_in.data_ptr(), x0.data_ptr(), gdir.data_ptr(), seed6.data_ptr(),
                                                lpart.data_ptr(), B, H, W, coef, self.tvs, self.rs, sats, s))
             gunet = self.unet.dgrad(seed6, self._b("gunet", (B, 3, H, W), dev))
+        if self.classifier is not None:
+            # L += -scale * sum_b log p(class | x_b, t_b): dL/dx joins the direct part, so the logged Grad, the magnitude clamp and scalars[7]
+            # below see the sum and the sampler's update needs no change
+            ts = self.step_ts if ts is None else ts
+            if ts is None:
+                raise ValueError("classifier guidance needs the step's model timesteps: native(..., ts=...) or step_ts")
+            ycls = self._buf.get("cls_y")
+            if ycls is None or ycls.shape[0] != B or ycls.device != dev:
+                ycls = self._buf["cls_y"] = th.full((B,), self.classifier_class, dtype=th.int64, device=dev)
+            _, self.classifier_logp = self.classifier.forward(x, ts, ycls, logits=self._b("cls_logits", (B, self.classifier.out_channels), dev),
+                                                              logp=self._b("cls_logp", (B,), dev))
+            self.classifier.dgrad(-self.classifier_scale, gdir, accumulate=True)
         g = self._b("g", (B, 3, H, W), dev)
         gpart = self._b("gpart", (nblk, 2), dev)
         ctx.check(lib.cgd_grad_finish(ctx.h, gdir.data_ptr(), gunet.data_ptr(), g.data_ptr(), gpart.data_ptr(), B, H, W, s))
@@ -891,7 +915,10 @@ class ClipGuidance:
     def snapshot(self):
         """Asynchronous host copies of the last call's scalars: `log(snapshot)` later costs no wait on newer GPU work."""
         from .hostcopy import HostCopy
-        return {"scalars": HostCopy(self.scalars.clone()), "lpips": HostCopy(self.lpips_loss.clone()) if self.lpips is not None else None}
+        snap = {"scalars": HostCopy(self.scalars.clone()), "lpips": HostCopy(self.lpips_loss.clone()) if self.lpips is not None else None}
+        if self.classifier is not None:
+            snap["classifier"] = HostCopy(self.classifier_logp.clone())
+        return snap
 
     def log(self, snapshot=None):
         """Scalar log of the last call (or of a `snapshot()`) with the reference's keys (one host sync; call lazily)."""
@@ -904,6 +931,10 @@ class ClipGuidance:
         if self.lpips is not None:
             out["Init VGG Loss"] = float(lpips_loss.sum().item()) * self.init_scale
             out["Total Loss"] += out["Init VGG Loss"]
+        if self.classifier is not None:
+            logp = snapshot["classifier"].get() if snapshot is not None else self.classifier_logp
+            out["Classifier Loss"] = -self.classifier_scale * float(logp.sum().item())
+            out["Total Loss"] += out["Classifier Loss"]
         if self.use_magnitude:
             out["Magnitude"] = v[5]
         out["Grad"] = v[6]
@@ -916,7 +947,11 @@ class ClipGuidance:
         x = x.detach().contiguous().float()
         x0 = out["pred_xstart"].detach().contiguous().float()
         x_in = (x0 * coef.fac + x * (1 - coef.fac)).contiguous()
-        g = self.native(x, x0, x_in, coef)
+        ts = None
+        if self.classifier is not None:  # the model timestep of index t, as the sampler hands it to the UNet
+            tables = getattr(self.diffusion, "tables", self.diffusion)
+            ts = th.tensor([float(tables.model_timestep(int(k))) for k in t.flatten().tolist()], dtype=th.float32, device=x.device)
+        g = self.native(x, x0, x_in, coef, ts=ts)
         if g is None:
             return th.zeros_like(x)
         if self.use_magnitude:

@@ -27,6 +27,14 @@ class UNetConfig(C.Structure):
     ]
 
 
+class ClassifierConfig(C.Structure):
+    """cgd_classifier_config"""
+    _fields_ = [
+        ("image_size", i32), ("model_channels", i32), ("num_res_blocks", i32), ("n_mult", i32),
+        ("channel_mult", f32 * 8), ("n_att", i32), ("attention_ds", i32 * 8), ("num_head_channels", i32), ("out_channels", i32),
+    ]
+
+
 class ViTConfig(C.Structure):
     _fields_ = [("resolution", i32), ("patch", i32), ("width", i32), ("layers", i32), ("heads", i32), ("out_dim", i32)]
 
@@ -154,6 +162,18 @@ _SIGS = {
     "cgd_secondary_combine": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, f32, vp]),
     "cgd_op_secondary_pack": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "cgd_op_bilinear_up2x": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "cgd_classifier_manifest": (i32, [C.POINTER(ClassifierConfig), MANIFEST_CB, vp]),
+    "cgd_classifier_create": (i32, [vp, C.POINTER(ClassifierConfig), C.POINTER(vp)]),
+    "cgd_classifier_destroy": (None, [vp]),
+    "cgd_classifier_num_params": (i32, [vp]),
+    "cgd_classifier_param_info": (i32, [vp, i32, C.c_char_p, i32, C.POINTER(i64)]),
+    "cgd_classifier_set_param": (i32, [vp, C.c_char_p, vp, i64]),
+    "cgd_classifier_finalize": (i32, [vp]),
+    "cgd_classifier_forward": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "cgd_classifier_dgrad": (i32, [vp, f32, vp, i32, vp]),
+    "cgd_op_attnpool_scratch_floats": (i64, [i32, i32, i32, i32, i32]),
+    "cgd_op_attnpool_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "cgd_op_attnpool_bwd": (i32, [vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, i32, vp]),
     "cgd_cutouts_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_cutouts_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_cutouts_aug_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),

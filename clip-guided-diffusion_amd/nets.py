@@ -458,6 +458,80 @@ class SecondaryModel(_Net):
         self.ctx.check(self.ctx.lib.cgd_secondary_debug_replay(self.h, arr))
 
 
+CLASSIFIER_CONFIGS = {
+    # guided-diffusion's create_classifier defaults by image size (64x64_classifier.pt ... 512x512_classifier.pt): width 128, depth 2 (4 at
+    # 64x64), attention at resolutions 32,16,8, 64-channel heads, the UNet's channel_mult by size, 1000 classes.  Written from the published
+    # source; loading a checkpoint cross-checks every dimension a shape reveals (cgd.clip_util.classifier_config_from_state_dict).
+    size: dict(image_size=size, model_channels=128, num_res_blocks=4 if size == 64 else 2, attention_resolutions="32,16,8",
+               channel_mult=DEFAULT_CHANNEL_MULT[size], num_head_channels=64, out_channels=1000)
+    for size in (64, 128, 256, 512)
+}
+
+
+class NoisyClassifier(_Net):
+    """guided-diffusion's noise-aware ImageNet classifier (`EncoderUNetModel`, pool="attention"): `forward` gives the logits and
+    log p(y | x_t, t), `dgrad` the gradient of sum_b log p(y_b | x_b, t_b) w.r.t. x — classifier guidance.  `load_state_dict` takes the
+    module's own keys (`time_embed.*`, `input_blocks.*`, `middle_block.*`, `out.0.*`, `out.2.*`)."""
+    _prefix = "classifier"
+
+    def __init__(self, ctx, image_size, model_channels=128, num_res_blocks=2, attention_resolutions="32,16,8", channel_mult=None,
+                 num_head_channels=64, out_channels=1000):
+        self.ctx = ctx
+        self.cfg = self.make_config(image_size, model_channels, num_res_blocks, attention_resolutions, channel_mult, num_head_channels,
+                                    out_channels)
+        self.image_size, self.out_channels = image_size, out_channels
+        h = C.c_void_p()
+        ctx.check(ctx.lib.cgd_classifier_create(ctx.h, C.byref(self.cfg), C.byref(h)))
+        self._adopt(h)
+        self.dgrad_calls = 0
+
+    @staticmethod
+    def make_config(image_size, model_channels=128, num_res_blocks=2, attention_resolutions="32,16,8", channel_mult=None,
+                    num_head_channels=64, out_channels=1000):
+        """guided_diffusion's create_classifier arguments -> the C struct (host-only: also feeds cgd_classifier_manifest)."""
+        if channel_mult is None:
+            channel_mult = DEFAULT_CHANNEL_MULT[image_size]
+        att = [image_size // int(r) for r in str(attention_resolutions).split(",")]
+        if len(channel_mult) > 8 or len(att) > 8:
+            raise ValueError("classifier: at most 8 levels and 8 attention resolutions")
+        cfg = L.ClassifierConfig()
+        cfg.image_size, cfg.model_channels, cfg.num_res_blocks = image_size, model_channels, num_res_blocks
+        cfg.n_mult = len(channel_mult)
+        for i, m in enumerate(channel_mult):
+            cfg.channel_mult[i] = float(m)
+        cfg.n_att = len(att)
+        for i, a in enumerate(att):
+            cfg.attention_ds[i] = a
+        cfg.num_head_channels, cfg.out_channels = num_head_channels, out_channels
+        return cfg
+
+    def forward(self, x, timesteps, y, logits=None, logp=None):
+        """x (B,3,S,S) fp32 NCHW on the GPU, S = image_size; timesteps (B,) (converted to fp32); y (B,) class ids.
+        Returns (logits (B,out_channels), logp (B,)) with logp[b] = log_softmax(logits[b])[y[b]]."""
+        B, _, H, W = x.shape
+        x = x.contiguous().float()
+        t = timesteps.to(device=x.device, dtype=th.float32).contiguous()
+        y = y.to(device=x.device, dtype=th.int64).contiguous()
+        if logits is None:
+            logits = th.empty((B, self.out_channels), device=x.device, dtype=th.float32)
+        if logp is None:
+            logp = th.empty((B,), device=x.device, dtype=th.float32)
+        self.ctx.check(self.ctx.lib.cgd_classifier_forward(self.h, x.data_ptr(), t.data_ptr(), y.data_ptr(), logits.data_ptr(), logp.data_ptr(),
+                                                           B, H, W, self.ctx.stream()))
+        self._keep = (x, t, y)  # inputs must outlive the enqueued work
+        return logits, logp
+
+    def dgrad(self, scale=1.0, g=None, accumulate=False):
+        """g (+)= scale * d(sum_b logp[b])/dx of the last forward."""
+        if g is None:
+            x = self._keep[0]
+            g = th.zeros_like(x) if accumulate else th.empty_like(x)
+        assert g.is_contiguous() and g.dtype == th.float32, "g must be a contiguous fp32 tensor of x's shape"
+        self.ctx.check(self.ctx.lib.cgd_classifier_dgrad(self.h, float(scale), g.data_ptr(), int(bool(accumulate)), self.ctx.stream()))
+        self.dgrad_calls += 1
+        return g
+
+
 def manifest(kind, cfg=None):
     """[(name, numel)] of a network configuration from the library's host-only manifest functions (no GPU, no context)."""
     out = []

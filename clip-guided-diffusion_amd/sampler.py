@@ -160,6 +160,8 @@ class GuidedSampler:
             if noise is None and draw_noise:
                 noise = self._draw_like(x)  # drawn before cond_fn, as in p_sample_with_grad
             n_known = self._draw_like(x) if draw_known else None
+            if native:
+                cond_fn.step_ts = ts  # the model timesteps this forward received: a classifier term is evaluated at them
             g = cond_fn.native(x, x0, xin, coef) if native else None
             scal = cond_fn.scalars if (native and g is not None and cond_fn.use_magnitude) else None
         else:

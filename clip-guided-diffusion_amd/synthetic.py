@@ -124,3 +124,29 @@ def secondary_state_dict(seed=9753, device="cpu"):
             t = (2.0 / (9 * cin)) ** 0.5 * th.randn(cout, cin, 3, 3, generator=g)
         sd[name] = t.to(device)
     return sd
+
+
+def classifier_state_dict(cfg, seed=8642, device="cpu"):
+    """Seeded stand-in for a noisy classifier's weights (`nets.NoisyClassifier`) under its state-dict names, from the library's manifest of
+    `cfg` (a `lib.ClassifierConfig`, or the keyword arguments of `nets.NoisyClassifier.make_config` as a dict).  The recipe of
+    `oracle/unet.py:synthetic_init_`: fan-in init U(+-sqrt(3 / fan_in)) for every conv / linear — upstream's `zero_module` layers (ResBlock out
+    conv, attention proj_out) included, so no gradient path is dead — N(0, 0.02) biases, 1 + N(0, 0.02) norm gains; the positional embedding
+    as AttentionPool2d draws it, N(0, 1 / C)."""
+    from . import nets
+    if isinstance(cfg, dict):
+        cfg = nets.NoisyClassifier.make_config(**cfg)
+    g = th.Generator().manual_seed(seed)
+    specs = dict(nets.manifest("classifier", cfg))
+    width = specs["out.0.weight"]
+    sd = {}
+    for name, numel in specs.items():
+        leaf = name.rsplit(".", 1)[-1]
+        is_norm = any(k in name for k in (".in_layers.0.", ".out_layers.0.", ".norm.", "out.0."))
+        if is_norm or leaf == "bias":
+            t = 0.02 * th.randn(numel, generator=g) + (1.0 if (is_norm and leaf == "weight") else 0.0)
+        elif leaf == "positional_embedding":
+            t = width ** -0.5 * th.randn(numel, generator=g)
+        else:
+            t = (th.rand(numel, generator=g) * 2 - 1) * (3.0 / _fan_in(name, numel, specs)) ** 0.5
+        sd[name] = t.to(device)
+    return sd

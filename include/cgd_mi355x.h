@@ -231,6 +231,49 @@ int cgd_op_secondary_pack(cgd_ctx* ctx, const float* x, const float* t, const fl
 int cgd_op_bilinear_up2x(cgd_ctx* ctx, const float* in, int ldi, float* out, int ldo, int B, int Hi, int Wi, int C, int adjoint,
                          void* stream);
 
+/* ---- Noisy ImageNet classifier of guided-diffusion (EncoderUNetModel with pool="attention": 64x64_classifier.pt ... 512x512_classifier.pt):
+ *      the encoder half of the ADM UNet (time_embed, input_blocks, middle_block: same ResBlocks and legacy-order AttentionBlocks, no label_emb,
+ *      no output blocks), then out.0 (GroupNorm32) -> SiLU -> out.2 (AttentionPool2d: positional_embedding (C, S*S+1), qkv_proj, c_proj; new
+ *      attention order, token 0 kept), S = image_size / 2^(n_mult-1), heads = C / num_head_channels.  Classifier guidance adds
+ *      scale * d(sum_b log p(y_b | x_b, t_b))/dx to the guidance gradient.  Parameters use the module's state-dict names.
+ *        forward: x (B,3,H,W) NCHW with H = W = image_size (anything else fails, -2, before any launch), timesteps (B) fp32, y (B) int64 ->
+ *                 logits (B,out_channels) (or NULL) and, if logp != NULL, logp[b] = log_softmax(logits[b])[y[b]] (NaN for a y outside the
+ *                 classes); keeps the activations for dgrad
+ *        dgrad:   g_x (B,3,H,W) (+)= scale * d(sum_b logp[b])/dx of the LAST forward; accumulate 0 / 1
+ *      A configuration the conv kernels or the pool kernels cannot run is refused at create (-2). ---- */
+typedef struct cgd_classifier cgd_classifier;
+typedef struct cgd_classifier_config {
+  int image_size;
+  int model_channels;
+  int num_res_blocks;
+  int n_mult;
+  float channel_mult[8];
+  int n_att;
+  int attention_ds[8];
+  int num_head_channels;
+  int out_channels;        /* 1000 */
+} cgd_classifier_config;
+int cgd_classifier_manifest(const cgd_classifier_config* cfg, cgd_manifest_cb cb, void* user);
+int cgd_classifier_create(cgd_ctx* ctx, const cgd_classifier_config* cfg, cgd_classifier** out);
+void cgd_classifier_destroy(cgd_classifier* c);
+int cgd_classifier_num_params(cgd_classifier* c);
+int cgd_classifier_param_info(cgd_classifier* c, int index, char* name_buf, int buf_len, int64_t* numel);
+int cgd_classifier_set_param(cgd_classifier* c, const char* name, const float* data, int64_t numel);
+int cgd_classifier_finalize(cgd_classifier* c);
+int cgd_classifier_forward(cgd_classifier* c, const float* x, const float* timesteps, const int64_t* y, float* logits, float* logp, int B, int H,
+                           int W, void* stream);
+int cgd_classifier_dgrad(cgd_classifier* c, float scale, float* g_x, int accumulate, void* stream);
+/* The classifier's head alone, exported for parity tests and benchmarks.  h [B*S*S][C] dense NHWC rows (the SiLU(GroupNorm) output), the four
+ * parameters as the checkpoint holds them, y (B) int64 -> pooled [B][C] (token 0 of the attention output in front of c_proj; or NULL),
+ * logits [B][out] (or NULL), logp [B] (or NULL).  scratch: cgd_op_attnpool_scratch_floats floats, 16-byte aligned; it keeps what the backward
+ * needs.  bwd: dh [B*S*S][C] = scale * d(sum_b logp[b])/dh of the forward that filled `scratch` (same weights, same shape). */
+int64_t cgd_op_attnpool_scratch_floats(int B, int S, int C, int d, int out);
+int cgd_op_attnpool_fwd(cgd_ctx* ctx, const float* h, const float* pos, const float* qkv_w, const float* qkv_b, const float* c_w, const float* c_b,
+                        const int64_t* y, float* pooled, float* logits, float* logp, float* scratch, int B, int S, int C, int d, int out,
+                        void* stream);
+int cgd_op_attnpool_bwd(cgd_ctx* ctx, const float* qkv_w, const float* qkv_b, const float* c_w, const float* c_b, float scale, float* dh,
+                        float* scratch, int B, int S, int C, int d, int out, void* stream);
+
 /* ---- cutouts: replaces MakeCutouts.forward (cgd/modules.py:50-66) + x.add(1).div(2) (cgd.py:190) + CLIP_NORMALIZE
  *      (clip_util.py:45).  coords: device int32 [cutn][4] = (oy, ox, h, w) of each (possibly truncated) crop. ---- */
 int cgd_cutouts_fwd(cgd_ctx* ctx, const float* x_in, const int32_t* coords, float* out, int B, int H, int W, int cutn, int cut_size,

@@ -585,10 +585,95 @@ def check_attn_family_guard():
     return msg, bool(th.isfinite(ok).all())
 
 
-def check_cutouts_loss():
-    import ctypes as C
+def pool_cutouts_grouped(x, coords, cs):
+    """oracle MakeCutouts.forward for given coords, with one adaptive_avg_pool2d per distinct crop extent instead of one per crop (thousands
+    of cutouts stay within seconds on the CPU); tests/test_tail_host.py holds it equal to the oracle's loop"""
+    H, W = x.shape[2:4]
+    groups = {}
+    for k, (ox, oy, s) in enumerate(coords):
+        groups.setdefault((min(s, H - oy), min(s, W - ox)), []).append(k)
+    pooled, order = [], []
+    for (h, w), ks in groups.items():
+        crops = th.stack([x[:, :, coords[k][1]:coords[k][1] + h, coords[k][0]:coords[k][0] + w] for k in ks])  # (n, B, 3, h, w)
+        pooled.append(F.adaptive_avg_pool2d(crops.flatten(0, 1), cs).unflatten(0, crops.shape[:2]))
+        order += ks
+    inv = th.empty(len(order), dtype=th.long)
+    inv[th.tensor(order)] = th.arange(len(order))
+    return th.cat(pooled)[inv].flatten(0, 1)
+
+
+def _cutouts_case(ctx, out, B, H, W, cutn, cs, patch, coords, grouped=False, accumulate=False):
+    """cgd_cutouts_fwd / _bwd of one case against oracle MakeCutouts + clip_normalize in float64 (autograd for the adjoint, unit seed), in the
+    NCHW layout and, where `patch` is given, the patch-row layout.  Output buffers are pre-filled with NaN: an element no launch wrote fails.
+    `accumulate`: the adjoint also runs with accumulate = 1 into a pre-filled g_in, twice, and must give pre-fill + gradient bit-identically."""
     from cgd_amd import lib as L
     from oracle import guidance as og
+    x = th.rand(B, 3, H, W, generator=g(50)) * 2.4 - 1.2
+    xr = x.double().requires_grad_()
+    if grouped:
+        cut = og.clip_normalize(pool_cutouts_grouped((xr + 1) / 2, coords, cs))
+    else:
+        cut = og.clip_normalize(og.MakeCutouts(cs, cutn)((xr + 1) / 2, coords=coords))
+    dy = th.randn(cut.shape, generator=g(51)).double()
+    (cut * dy).sum().backward()
+    dy = dy * unit_seed(xr.grad)
+    xr.grad.mul_(unit_seed(xr.grad))
+    geo = []
+    for (ox, oy, s) in coords:
+        geo.append((oy, ox, min(s, H - oy), min(s, W - ox)))
+    cd = th.tensor(geo, dtype=th.int32, device=DEV)
+    xd = x.to(DEV)
+    nan = float("nan")
+    lays = [(0, 0, "", cut.float(), dy.float().to(DEV))]
+    if patch:  # patch-row layout = patchify(NCHW)
+        gsz = cs // patch
+        rows = lambda t: t.float().reshape(cutn * B, 3, gsz, patch, gsz, patch).permute(0, 2, 4, 1, 3, 5).reshape(cutn * B * gsz * gsz, -1)  # noqa: E731
+        lays.append((1, patch, " patch-layout", rows(cut), rows(dy).contiguous().to(DEV)))
+    for layout, P, tag, ref, dyd in lays:
+        o = th.full(ref.shape, nan, device=DEV)
+        ctx.check(ctx.lib.cgd_cutouts_fwd(ctx.h, xd.data_ptr(), cd.data_ptr(), o.data_ptr(), B, H, W, cutn, cs, layout, P, L.stream_ptr()))
+        out.append(rec(f"cutouts fwd{tag} B{B} {H}x{W}" + ("" if layout else f" cutn{cutn} cs{cs}"), o, ref))
+        gx = th.full((B, 3, H, W), nan, device=DEV)
+        ctx.check(ctx.lib.cgd_cutouts_bwd(ctx.h, dyd.data_ptr(), cd.data_ptr(), gx.data_ptr(), B, H, W, cutn, cs, layout, P, 0, L.stream_ptr()))
+        out.append(rec(f"cutouts bwd{tag} B{B} {H}x{W}" + ("" if layout else f" cutn{cutn} cs{cs}"), gx, xr.grad.float()))
+        if accumulate:
+            pre = th.randn(B, 3, H, W, generator=g(54))
+            runs = []
+            for _ in range(2):
+                ga = pre.to(DEV)
+                ctx.check(ctx.lib.cgd_cutouts_bwd(ctx.h, dyd.data_ptr(), cd.data_ptr(), ga.data_ptr(), B, H, W, cutn, cs, layout, P, 1, L.stream_ptr()))
+                runs.append(ga)
+            out.append(rec(f"cutouts bwd{tag} accumulate B{B} {H}x{W} cutn{cutn} cs{cs}", runs[0], pre.double() + xr.grad))
+            out.append(_flag(f"cutouts bwd{tag} accumulate B{B} {H}x{W} cutn{cutn} cs{cs}: two runs bit-identical", th.equal(runs[0], runs[1])))
+
+
+def _spherical_case(ctx, out, cutn, B, P, D):
+    """cgd_spherical_loss against oracle spherical_dist_loss in float64 (+ broadcast rules of cgd.py:196-200)"""
+    from cgd_amd import lib as L
+    from oracle import guidance as og
+    emb = th.randn(cutn * B, D, generator=g(52))
+    tg = th.randn(P, D, generator=g(53))
+    wts = th.tensor([1.0, 0.5, -0.3][:P])
+    wts = wts / wts.sum().abs()
+    er = emb.double().requires_grad_()
+    d = og.spherical_dist_loss(er.view(cutn, B, D).unsqueeze(0), tg.double().unsqueeze(0)).view(cutn, B, -1)
+    loss = d.mul(wts.double()).sum(2).mean(0).sum() * 1000.0
+    loss.backward()
+    if B == 1 or P == 1:
+        wm = wts.view(1, P).expand(B, P).contiguous()
+    else:
+        wm = th.eye(B) * wts.sum()
+    demb = th.full(emb.shape, float("nan"), device=DEV)
+    part = th.full((cutn * B,), float("nan"), device=DEV)
+    ed, tn, wd_ = emb.to(DEV), F.normalize(tg, dim=-1).to(DEV), wm.float().contiguous().to(DEV)
+    ctx.check(ctx.lib.cgd_spherical_loss(ctx.h, ed.data_ptr(), tn.data_ptr(), wd_.data_ptr(), demb.data_ptr(), part.data_ptr(), cutn, B, P,
+                                         D, 1000.0, L.stream_ptr()))
+    tag = f"cutn{cutn} B{B} P{P}" + ("" if D in (512, 768) else f" D{D}")
+    out.append(rec(f"spherical loss value {tag}", part.sum().reshape(1), loss.detach().float().reshape(1)))
+    out.append(rec(f"spherical loss grad {tag}", demb, er.grad.float()))
+
+
+def check_cutouts_loss():
     ctx = _ctx(1)
     out = []
     for (B, H, W, cutn, cs, patch, coords) in [
@@ -599,58 +684,85 @@ def check_cutouts_loss():
         # more cutouts than the backward kernel's 256-entry table of division constants (chunked launches that accumulate)
         (1, 40, 48, 300, 16, 8, [((7 * k) % 17, (5 * k) % 13, 20 + k % 21) for k in range(300)]),
     ]:
-        x = th.rand(B, 3, H, W, generator=g(50)) * 2.4 - 1.2
-        xr = x.double().requires_grad_()
-        mk = og.MakeCutouts(cs, cutn)
-        cut = og.clip_normalize(mk((xr + 1) / 2, coords=coords))
-        dy = th.randn(cut.shape, generator=g(51)).double()
-        (cut * dy).sum().backward()
-        dy = dy * unit_seed(xr.grad)
-        xr.grad.mul_(unit_seed(xr.grad))
-        geo = []
-        for (ox, oy, s) in coords:
-            geo.append((oy, ox, min(s, H - oy), min(s, W - ox)))
-        cd = th.tensor(geo, dtype=th.int32, device=DEV)
-        xd = x.to(DEV)
-        o = th.empty((cutn * B, 3, cs, cs), device=DEV)
-        ctx.check(ctx.lib.cgd_cutouts_fwd(ctx.h, xd.data_ptr(), cd.data_ptr(), o.data_ptr(), B, H, W, cutn, cs, 0, 0, L.stream_ptr()))
-        out.append(rec(f"cutouts fwd B{B} {H}x{W} cutn{cutn} cs{cs}", o, cut.float()))
-        gx = th.empty((B, 3, H, W), device=DEV)
-        dyd = dy.float().to(DEV)
-        ctx.check(ctx.lib.cgd_cutouts_bwd(ctx.h, dyd.data_ptr(), cd.data_ptr(), gx.data_ptr(), B, H, W, cutn, cs, 0, 0, 0, L.stream_ptr()))
-        out.append(rec(f"cutouts bwd B{B} {H}x{W} cutn{cutn} cs{cs}", gx, xr.grad.float()))
-        # patch-row layout = patchify(NCHW)
-        gsz = cs // patch
-        o1 = th.empty((cutn * B * gsz * gsz, 3 * patch * patch), device=DEV)
-        ctx.check(ctx.lib.cgd_cutouts_fwd(ctx.h, xd.data_ptr(), cd.data_ptr(), o1.data_ptr(), B, H, W, cutn, cs, 1, patch, L.stream_ptr()))
-        refp = cut.float().reshape(cutn * B, 3, gsz, patch, gsz, patch).permute(0, 2, 4, 1, 3, 5).reshape(cutn * B * gsz * gsz, -1)
-        out.append(rec(f"cutouts fwd patch-layout B{B} {H}x{W}", o1, refp))
-        dyp = dy.float().reshape(cutn * B, 3, gsz, patch, gsz, patch).permute(0, 2, 4, 1, 3, 5).reshape(cutn * B * gsz * gsz, -1).contiguous().to(DEV)
-        gx1 = th.empty((B, 3, H, W), device=DEV)
-        ctx.check(ctx.lib.cgd_cutouts_bwd(ctx.h, dyp.data_ptr(), cd.data_ptr(), gx1.data_ptr(), B, H, W, cutn, cs, 1, patch, 0, L.stream_ptr()))
-        out.append(rec(f"cutouts bwd patch-layout B{B} {H}x{W}", gx1, xr.grad.float()))
-    # spherical loss (+ broadcast rules of cgd.py:196-200)
+        _cutouts_case(ctx, out, B, H, W, cutn, cs, patch, coords)
     for (cutn, B, P, D) in [(4, 1, 3, 512), (5, 2, 1, 512), (3, 2, 2, 768)]:
-        emb = th.randn(cutn * B, D, generator=g(52))
-        tg = th.randn(P, D, generator=g(53))
-        wts = th.tensor([1.0, 0.5, -0.3][:P])
-        wts = wts / wts.sum().abs()
-        er = emb.double().requires_grad_()
-        d = og.spherical_dist_loss(er.view(cutn, B, D).unsqueeze(0), tg.double().unsqueeze(0)).view(cutn, B, -1)
-        loss = d.mul(wts.double()).sum(2).mean(0).sum() * 1000.0
-        loss.backward()
-        if B == 1 or P == 1:
-            wm = wts.view(1, P).expand(B, P).contiguous()
-        else:
-            wm = th.eye(B) * wts.sum()
-        demb = th.empty_like(emb, device=DEV)
-        part = th.empty(cutn * B, device=DEV)
-        ed, tn, wd_ = emb.to(DEV), F.normalize(tg, dim=-1).to(DEV), wm.float().contiguous().to(DEV)
-        ctx.check(ctx.lib.cgd_spherical_loss(ctx.h, ed.data_ptr(), tn.data_ptr(), wd_.data_ptr(), demb.data_ptr(), part.data_ptr(), cutn, B, P,
-                                             D, 1000.0, L.stream_ptr()))
-        out.append(rec(f"spherical loss value cutn{cutn} B{B} P{P}", part.sum().reshape(1), loss.detach().float().reshape(1)))
-        out.append(rec(f"spherical loss grad cutn{cutn} B{B} P{P}", demb, er.grad.float()))
+        _spherical_case(ctx, out, cutn, B, P, D)
     return out
+
+
+# (ox, oy, size) on a (24, 20) image: crop extents, truncation included, of (1, w), (h, 1), (1, 1), (2, 3), the full frame and one 7-pixel crop
+CUTOUT_EXTENT_COORDS = [(3, 23, 5), (19, 2, 6), (19, 23, 4), (17, 22, 5), (0, 0, 24), (5, 9, 7)]
+
+
+def cutout_edge_cases():
+    """(B, H, W, cutn, cs, patch, coords) of check_cutouts_edges; patch 0 = NCHW layout only"""
+    spread = lambda n, lim, lo, span: [((7 * k) % (lim - lo - span + 1), (5 * k) % (lim - lo - span + 1), lo + k % span) for k in range(n)]  # noqa: E731
+    return [
+        # non-power-of-two patch divisor: ViT-L/14 and ViT-L/14@336; 7x upsampling in the NCHW layout
+        (1, 64, 64, 2, 224, 14, [(0, 0, 64), (5, 9, 50)]),
+        (1, 96, 80, 2, 336, 14, [(0, 0, 96), (10, 20, 61)]),
+        (1, 64, 64, 2, 448, 0, [(0, 0, 64), (11, 2, 37)]),
+        # non-integer bins of 2 to 3 rows, the production maximum of the bin numerators
+        (1, 512, 512, 2, 224, 32, [(0, 0, 512), (100, 150, 300)]),
+        # extents of 1 (the d == 1 branch of the exact division) and 1-row bins under 8x upsampling
+        (2, 24, 20, 6, 8, 4, CUTOUT_EXTENT_COORDS),
+        # the adjoint's table of 256 cutouts: exactly full, and a second launch that carries one cutout
+        (1, 24, 24, 256, 8, 4, spread(256, 24, 5, 13)),
+        (1, 24, 24, 257, 8, 4, spread(257, 24, 5, 13)),
+        # B * 3 * cutn = 65544 planes: the forward's second grid.y chunk of one cutout
+        (4, 16, 16, 5462, 4, 2, spread(5462, 16, 3, 6)),
+    ]
+
+
+def check_cutouts_edges():
+    """Plain cutouts and the spherical loss where the existing cases do not reach: see cutout_edge_cases; accumulate = 1 on two of the shapes;
+    embedding widths that are no multiple of the 64 lanes, and the widest the kernel holds in registers."""
+    ctx = _ctx(1)
+    out = []
+    for (B, H, W, cutn, cs, patch, coords) in cutout_edge_cases():
+        _cutouts_case(ctx, out, B, H, W, cutn, cs, patch, coords, grouped=cutn > 1000, accumulate=(cutn in (6, 257)))
+    for (cutn, B, P, D) in [(3, 1, 2, 1024), (2, 2, 1, 640), (2, 1, 2, 100), (1, 1, 1, 2048)]:
+        _spherical_case(ctx, out, cutn, B, P, D)
+    return out
+
+
+def check_cutouts_refusals():
+    """Sizes the launchers must refuse before any launch, with every buffer allocated at its true size (a missing guard costs nothing):
+    returns (status, error text, output untouched) per call."""
+    from cgd_amd import lib as L
+    ctx = _ctx(1)
+    nan = float("nan")
+    res = {}
+
+    def call(name, fn, *bufs_and_args):
+        rc = fn(ctx.h, *bufs_and_args, L.stream_ptr())
+        th.cuda.synchronize()
+        res[name] = [rc, ctx.lib.cgd_last_error(ctx.h).decode() if rc else ""]
+
+    # grid.y = B * 3 planes per cutout = 65538
+    B = 21846
+    x, o, gx = th.zeros(B, 3, 1, 1, device=DEV), th.full((B, 3, 1, 1), nan, device=DEV), th.full((B, 3, 1, 1), nan, device=DEV)
+    cd = th.tensor([[0, 0, 1, 1]], dtype=th.int32, device=DEV)
+    call("fwd B21846", ctx.lib.cgd_cutouts_fwd, x.data_ptr(), cd.data_ptr(), o.data_ptr(), B, 1, 1, 1, 1, 0, 0)
+    call("bwd B21846", ctx.lib.cgd_cutouts_bwd, x.data_ptr(), cd.data_ptr(), gx.data_ptr(), B, 1, 1, 1, 1, 0, 0, 0)
+    res["fwd B21846"].append(bool(th.isnan(o).all()))
+    res["bwd B21846"].append(bool(th.isnan(gx).all()))
+    # cut size 225 is no multiple of patch 32
+    x = th.zeros(1, 3, 32, 32, device=DEV)
+    cd = th.tensor([[0, 0, 32, 32]], dtype=th.int32, device=DEV)
+    o, gx = th.full((1, 3, 225, 225), nan, device=DEV), th.full((1, 3, 32, 32), nan, device=DEV)
+    dy = th.zeros(1, 3, 225, 225, device=DEV)
+    call("fwd cs225 patch32", ctx.lib.cgd_cutouts_fwd, x.data_ptr(), cd.data_ptr(), o.data_ptr(), 1, 32, 32, 1, 225, 1, 32)
+    call("bwd cs225 patch32", ctx.lib.cgd_cutouts_bwd, dy.data_ptr(), cd.data_ptr(), gx.data_ptr(), 1, 32, 32, 1, 225, 1, 32, 0)
+    res["fwd cs225 patch32"].append(bool(th.isnan(o).all()))
+    res["bwd cs225 patch32"].append(bool(th.isnan(gx).all()))
+    # an embedding wider than the kernel's 32 registers x 64 lanes
+    D = 2049
+    emb, tn, wm = th.randn(2, D, device=DEV), F.normalize(th.randn(1, D), dim=-1).to(DEV), th.ones(1, 1, device=DEV)
+    demb, part = th.full((2, D), nan, device=DEV), th.full((2,), nan, device=DEV)
+    call("spherical D2049", ctx.lib.cgd_spherical_loss, emb.data_ptr(), tn.data_ptr(), wm.data_ptr(), demb.data_ptr(), part.data_ptr(), 2, 1, 1, D, 1000.0)
+    res["spherical D2049"].append(bool(th.isnan(demb).all() and th.isnan(part).all()))
+    return res
 
 
 # ---- networks --------------------------------------------------------------------------------------------

@@ -182,6 +182,21 @@ def test_cutouts_and_spherical_loss():
     _assert_all(pc.check_cutouts_loss())
 
 
+def test_cutouts_and_spherical_loss_edge_shapes():
+    """patch 14 (ViT-L/14, @336), cut size 448, 512 x 512 frames, crop extents of 1, the adjoint's 256 / 257-cutout table boundary, the
+    forward's second grid.y chunk, accumulate = 1; embedding widths 100 / 640 / 1024 / 2048"""
+    _assert_all(pc.check_cutouts_edges())
+
+
+def test_cutouts_and_spherical_loss_refuse_sizes_out_of_range():
+    res = pc.check_cutouts_refusals()
+    for name, text in (("fwd B21846", "size out of range"), ("bwd B21846", "size out of range"),
+                       ("fwd cs225 patch32", "multiple of the patch size"), ("bwd cs225 patch32", "multiple of the patch size"),
+                       ("spherical D2049", "embedding dim > 2048")):
+        rc, msg, untouched = res[name]
+        assert rc == -2 and text in msg and untouched, (name, res[name])
+
+
 @pytest.mark.parametrize("case,precision,B,hw", [("mini", 0, 1, None), ("mini", 1, 1, None), ("mini128", 1, 1, None), ("mini64", 1, 1, None),
                                                  ("mini", 1, 2, (32, 48))])
 def test_unet_small(case, precision, B, hw):

@@ -47,6 +47,12 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
             raise ValueError(f"init image 'invert=...' needs height_offset = width_offset = 0, got {height_offset} and {width_offset}: the "
                              "inverted latent has the init image's size")
 
+    # "SOURCE=>TARGET[:weight]" among the prompts (an extension like "plmsN"): a direction prompt, scored by the directional CLIP loss against
+    # the init image; refused before anything is loaded when malformed or without an init image
+    direction_pairs = script_util.direction_prompts(prompts, image_prompts, init_image, height_offset, width_offset)
+    if use_augs and any(pair is not None for pair in direction_pairs):
+        raise ValueError("'SOURCE=>TARGET' prompts do not work with use_augs: the random warp of every cut would have to be replayed on the init image")
+
     # "A+cuts=OV:IN" (an extension like "plmsN"): overview + inner cutouts through the antialiased cubic resize instead of pooled crops
     # "A+classifier=FILE:CLASS[:SCALE]" (likewise): classifier guidance with guided-diffusion's noisy ImageNet classifier
     without_classifier, classifier_spec = clip_util.split_classifier(clip_model_name, height_offset, width_offset)  # refuses before any load
@@ -78,11 +84,21 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         clip_size = clip_size or size
     clip_model = clip_models[0]
     embeds_per_tower, weights = [[] for _ in clip_names], []
-    for prompt in prompts:
+    # direction prompts: per tower normalize(E(target caption)) - normalize(E(source caption)); their places in the weight list, which holds
+    # targets and directions alike in the order given
+    dirs_per_tower, direction_columns = [[] for _ in clip_names], []
+    for prompt, pair in zip(prompts, direction_pairs):
         text, weight = script_util.parse_prompt(prompt)
         for k, name in enumerate(clip_names):
+            if pair is not None:
+                e_src, _ = clip_util.encode_text_prompt(pair[0], weight, name, device)
+                e_tgt, w_k = clip_util.encode_text_prompt(pair[1], weight, name, device)
+                dirs_per_tower[k].append(th.nn.functional.normalize(e_tgt.float(), dim=-1) - th.nn.functional.normalize(e_src.float(), dim=-1))
+                continue
             embed, w_k = clip_util.encode_text_prompt(text, weight, name, device)
             embeds_per_tower[k].append(embed)
+        if pair is not None:
+            direction_columns.append(len(weights))
         weights.append(w_k)
     for image_prompt in image_prompts:
         img, weight = script_util.parse_prompt(image_prompt)
@@ -90,11 +106,18 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
             embed, batched = clip_util.encode_image_prompt(img, weight, image_size, num_cutouts=num_cutouts, clip_model_name=name, device=device)
             embeds_per_tower[k].append(embed)
         weights.extend(batched)
-    target_embeds = [th.cat(e) for e in embeds_per_tower]
+    # (a run with direction prompts only has no target embeddings: ClipGuidance then makes no spherical launch)
+    target_embeds = [th.cat(e) for e in embeds_per_tower] if (embeds_per_tower[0] or not direction_columns) else None
     weight_t = th.tensor(weights, device=device)
     if weight_t.sum().abs() < 1e-3:
         raise RuntimeError("The weights must not sum to 0.")
     weight_t = weight_t / weight_t.sum().abs()
+    direction_kw = {}
+    if direction_columns:  # normalised together above; ClipGuidance builds the B x P matrix over the whole list and splits its columns
+        target_columns = [c for c in range(len(weights)) if c not in direction_columns]
+        direction_kw = dict(direction_embeds=[th.cat(e) for e in dirs_per_tower], direction_weights=weight_t[direction_columns],
+                            direction_columns=direction_columns)
+        weight_t = weight_t[target_columns]
 
     if use_augs:
         tqdm.write("cutout augmentations requested")
@@ -172,6 +195,7 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         lpips=script_util.load_lpips(gd_model.ctx, checkpoints_dir, device) if (init_tensor is not None and init_scale != 0) else None,
         init_tensor=init_tensor, init_scale=init_scale,
         secondary=secondary,
+        **({"direction_source": init_tensor, **direction_kw} if direction_kw else {}),
         **({} if classifier is None else {"classifier": classifier, "classifier_scale": classifier_spec[2], "classifier_class": classifier_spec[1]}))
     if nranks > 1:
         cond_fn.shard = diffusion.shard = (mine, batch_size)
@@ -253,10 +277,10 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
 # The reference CLI, flag for flag (cgd.py:290-357): "long alias kind default | help".  kind: str / int / float / path, or "flag"
 # for store_true switches.  Only names, aliases, types and defaults are contract (tests/golden/reference_host.json).
 _CLI_SPEC = f"""
---prompts -txts str "" | text prompts with optional weights, pipe-separated: 'a cat:0.5|a dog:-0.5'
+--prompts -txts str "" | text prompts with optional weights, pipe-separated: 'a cat:0.5|a dog:-0.5'; 'SOURCE CAPTION=>TARGET CAPTION[:weight]' is a direction prompt (needs --init_image): the change of the image's CLIP embedding relative to the init image is steered along the change from the source to the target caption (e.g. 'a photo of a cat=>a photo of a dog:1.5'); weights of all prompts are normalised together
 --image_prompts -imgs str "" | image prompts (paths or URLs) with optional weights, pipe-separated
 --image_size -size int 128 | resolution of the diffusion checkpoint: 64, 128, 256 or 512
---init_image -init str "" | start from this image (needs --skip_timesteps); IMAGE::MASK regenerates the white part of MASK and keeps the black part of IMAGE; invert=IMAGE (or invert=IMAGE::MASK, with -respace ddimN / plmsN / dpmN) starts from the DDIM-inverted latent of IMAGE
+--init_image -init str "" | start from this image (needs --skip_timesteps); IMAGE::MASK regenerates the white part of MASK and keeps the black part of IMAGE; invert=IMAGE (or invert=IMAGE::MASK, with -respace ddimN / plmsN / dpmN) starts from the DDIM-inverted latent of IMAGE; in every form IMAGE is also the source image of 'SOURCE=>TARGET' direction prompts
 --init_scale -is int 0 | weight of the LPIPS-VGG16 term that keeps the sample close to the init image
 --skip_timesteps -skip int 0 | how many of the (respaced) timesteps to skip at the noisy end
 --prefix -dir path outputs | directory for the PNG frames

@@ -99,6 +99,42 @@ def split_init_invert(image_part):
     return image, True
 
 
+DIRECTION_SEP = "=>"
+
+
+def split_direction(text):
+    """'SOURCE CAPTION=>TARGET CAPTION' -> (source, target), split at the first '=>' and stripped; a text without '=>' -> None.  Takes the
+    text parse_prompt returns (the weight is already off).  A direction prompt rides on --prompts / prompts=: the change of the image
+    embedding relative to the init image is steered along E(target) - E(source) instead of the image toward one caption."""
+    source, sep, target = str(text).partition(DIRECTION_SEP)
+    if not sep:
+        return None
+    source, target = source.strip(), target.strip()
+    if not source or not target:
+        raise ValueError(f"prompt {text!r}: 'SOURCE=>TARGET' needs a caption on both sides")
+    return source, target
+
+
+def direction_prompts(prompts, image_prompts=(), init_image=None, height_offset=0, width_offset=0):
+    """Per entry of `prompts`: None, or the (source, target) captions of a direction prompt.  Refuses, before anything is loaded: a malformed
+    entry, an image prompt with '=>', direction prompts without an init image (it is their source image) or with height / width offsets
+    (the init image has the checkpoint's size), and weights that sum to zero over all prompts (the reference's rule, cgd.py:103-105)."""
+    pairs = [split_direction(parse_prompt(p)[0]) for p in prompts]
+    for p in image_prompts:
+        if DIRECTION_SEP in parse_prompt(p)[0]:
+            raise ValueError(f"image prompt {p!r}: only text prompts can be 'SOURCE=>TARGET' directions")
+    if any(pair is not None for pair in pairs):
+        if not init_image:
+            raise ValueError("a 'SOURCE=>TARGET' prompt needs an init image (--init_image IMAGE, IMAGE::MASK or invert=IMAGE): it is the source "
+                             "image the edit is measured from")
+        if height_offset or width_offset:
+            raise ValueError(f"a 'SOURCE=>TARGET' prompt needs height_offset = width_offset = 0, got {height_offset} and {width_offset}: the "
+                             "source image has the init image's size")
+        if abs(sum(parse_prompt(p)[1] for p in list(prompts) + list(image_prompts))) < 1e-3:
+            raise RuntimeError("The weights must not sum to 0.")
+    return pairs
+
+
 def fetch(url_or_path):
     if str(url_or_path).startswith(("http://", "https://")):
         import requests

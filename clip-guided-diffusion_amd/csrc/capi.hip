@@ -247,6 +247,11 @@ int cgd_spherical_loss(cgd_ctx* ctx, const float* emb, const float* targets_n, c
   CGD_NEED_CTX(ctx);
   return cgd_launch_spherical_loss(ctx, emb, targets_n, weights, d_emb, loss_part, cutn, B, P, D, scale, S(stream));
 }
+int cgd_directional_loss(cgd_ctx* ctx, const float* emb, const float* src_emb, const float* dirs_n, const float* weights, float* d_emb,
+                         float* loss_part, int cutn, int B, int Bs, int P, int D, float scale, int accumulate, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_directional_loss(ctx, emb, src_emb, dirs_n, weights, d_emb, loss_part, cutn, B, Bs, P, D, scale, accumulate, S(stream));
+}
 int cgd_pmv_blend(cgd_ctx* ctx, const float* x, const float* out6, float* x0, float* mean, float* logvar, float* xin, int B, int H, int W,
                   const cgd_step_coef* k, void* stream) {
   CGD_NEED_CTX(ctx);

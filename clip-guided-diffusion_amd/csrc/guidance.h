@@ -26,6 +26,9 @@ int cgd_launch_scalars(cgd_ctx* ctx, const float* clip_part, int n_clip, const f
 int cgd_launch_sample_update(cgd_ctx* ctx, const float* x, const float* x0, const float* mean, const float* logvar, const float* g,
                              const float* noise, const float* scalars, float* sample, float* x0_out, int B, int H, int W,
                              const StepCoef& k, int mode, hipStream_t s);
+// direction.hip
+int cgd_launch_directional_loss(cgd_ctx* ctx, const float* emb, const float* src_emb, const float* dirs_n, const float* weights, float* demb,
+                                float* loss_part, int cutn, int B, int Bs, int P, int D, float scale, int accumulate, hipStream_t s);
 // plms.hip
 int cgd_launch_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eval, const float* x0, const float* g, const float* scalars,
                                 const float* noise, const float* const* eps_hist, float* eps_out, float* sample, float* x0_out, int B,

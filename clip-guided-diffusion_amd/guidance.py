@@ -11,6 +11,7 @@ Cutout coordinates are drawn exactly like the reference does (three CPU-generato
 perspective / grayscale / additive noise) inside the cutaug HIP kernels, whose adjoint is a deterministic gather; the parameters
 are drawn like reference_augs draws them (draw_aug_params), the noise on the device generator in its randn_like order.
 `MakeCutoutsResized` is a second cutter: overview + inner cuts through an antialiased cubic resize (the cutresize HIP kernels).
+With `direction_embeds` the CLIP leg also scores the directional loss of prompt-pair edits against a source image (the direction HIP kernel).
 """
 import math
 
@@ -573,10 +574,23 @@ class ClipGuidance:
     def __init__(self, ctx, unet, clip_tower, diffusion, target_embeds, weights, num_cutouts, cutout_power=1.0,
                  clip_guidance_scale=1000.0, tv_scale=150.0, range_scale=50.0, sat_scale=0.0, use_magnitude=False,
                  reduce_clip=False, progressive_cutout=False, cached_cutouts=False, make_cutouts=None, lpips=None, init_tensor=None,
-                 init_scale=0.0, secondary=None, classifier=None, classifier_scale=1.0, classifier_class=None):
+                 init_scale=0.0, secondary=None, classifier=None, classifier_scale=1.0, classifier_class=None, direction_embeds=None,
+                 direction_weights=None, direction_source=None, direction_columns=None):
         # Multi-CLIP (BASELINE config 5, a build extension: the reference takes one clip_model_name): `clip_tower` / `target_embeds`
         # may be lists; the CLIP losses of the towers are summed (same cutout boxes, prompt weights and guidance scale).
         self.towers = list(clip_tower) if isinstance(clip_tower, (list, tuple)) else [clip_tower]
+        # directional loss of prompt-pair edits (csrc/direction.hip), off without `direction_embeds`: one (P_d, D) tensor of raw text
+        # differences E(target caption) - E(source caption) per tower, `direction_weights` (P_d,) and `direction_source`, the source image
+        # (1 or B, 3, H, W) in [-1, 1].  The B x P weight matrix is built over the P_t + P_d prompts together, the directions in the columns
+        # `direction_columns` of that list (default: behind the targets) and `weights` in the others in order, and then split into the
+        # two groups.  `target_embeds` may be None (or empty tensors) when there are only directions: the spherical launch is then not made
+        has_dir = direction_embeds is not None
+        if has_dir:
+            dirs = list(direction_embeds) if isinstance(direction_embeds, (list, tuple)) else [direction_embeds]
+            assert len(dirs) == len(self.towers), "one direction-embedding tensor per CLIP tower"
+            if target_embeds is None:
+                target_embeds = [d.new_zeros((0, d.shape[-1])) for d in dirs]
+                weights = []
         embeds = list(target_embeds) if isinstance(target_embeds, (list, tuple)) else [target_embeds]
         assert len(embeds) == len(self.towers), "one target-embedding tensor per CLIP tower"
         self.ctx, self.unet, self.clip, self.diffusion = ctx, unet, self.towers[0], diffusion
@@ -585,6 +599,24 @@ class ClipGuidance:
         self.targets_list = [F.normalize(e.float(), dim=-1).contiguous() for e in embeds]
         self.targets_n = self.targets_list[0]
         self.weights = th.as_tensor(weights, dtype=th.float32, device=dev).flatten()
+        self.dirs_list = self.direction_weights = self.direction_source = self.direction_columns = None
+        self._src_emb = {}       # (cutn, B) -> (boxes, per-tower source embeddings): reused while cached_cutouts keeps the boxes
+        self.clip_part = None
+        if has_dir:
+            if direction_source is None:
+                raise ValueError("direction_embeds needs direction_source: the image whose embedding the edit starts from")
+            if direction_source.dim() != 4 or direction_source.shape[1] != 3:
+                raise ValueError(f"direction_source must be (1 or B, 3, H, W), got {tuple(direction_source.shape)}")
+            self.dirs_list = [F.normalize(d.float(), dim=-1).contiguous() for d in dirs]
+            pd, pt = self.dirs_list[0].shape[0], self.weights.numel()
+            self.direction_weights = th.as_tensor(th.ones(pd) if direction_weights is None else direction_weights, dtype=th.float32).flatten()
+            cols = list(range(pt, pt + pd)) if direction_columns is None else [int(c) for c in direction_columns]
+            if self.direction_weights.numel() != pd or len(cols) != pd or len(set(cols)) != pd or not all(0 <= c < pt + pd for c in cols):
+                raise ValueError(f"{pd} direction prompts need {pd} direction_weights and {pd} distinct direction_columns below {pt + pd}")
+            if any(t.shape[0] != pt for t in self.targets_list) or any(d.shape[0] != pd for d in self.dirs_list):
+                raise ValueError("every tower needs the same number of target and of direction embeddings as there are weights")
+            self.direction_columns = cols
+            self.direction_source = direction_source.detach().float().contiguous()
         self.num_cutouts = num_cutouts
         self.cgs, self.tvs, self.rs, self.sats = float(clip_guidance_scale), float(tv_scale), float(range_scale), float(sat_scale)
         self.use_magnitude = bool(use_magnitude)
@@ -592,6 +624,9 @@ class ClipGuidance:
         self.make_cutouts = make_cutouts or MakeCutouts(clip_tower.input_resolution, num_cutouts, cutout_power, ctx=ctx)
         if isinstance(self.make_cutouts, MakeCutoutsResized) and progressive_cutout:
             raise ValueError("progressive_cutout does not apply to MakeCutoutsResized: its cut counts come from its own schedule")
+        if has_dir and self.make_cutouts.augs is not None:
+            raise ValueError("direction prompts do not work with use_augs cutouts: the random warp of every cut would have to be replayed on "
+                             "the source image")
         # init-image perceptual term (cgd.py:147-148,220-224): `lpips` is a nets.LpipsVGG, its reference = the init image
         self.lpips, self.init_scale, self.init_tensor = None, float(init_scale), None
         if lpips is not None and init_tensor is not None and init_scale != 0:
@@ -619,6 +654,7 @@ class ClipGuidance:
         self.last_ran = False    # did the last call evaluate the guidance (False on a --reduce-clip gated step)?
         self.shard = None        # (indices of the global batch on this rank, global batch size): rows of the B x P weight matrix
         self._wm = {}
+        self._wmd = {}           # the direction columns of the weight matrix, per batch size
         self._buf = {}
 
     # -- helpers ------------------------------------------------------------------------------------
@@ -688,6 +724,8 @@ class ClipGuidance:
         dev = x.device
         s = ctx.stream()
         resized = isinstance(self.make_cutouts, MakeCutoutsResized)
+        if self.dirs_list is not None:
+            self._direction_source_on(dev, B, H, W)  # refuses a source of another size before anything is drawn or launched
         if self.coords_tape is not None:
             coords = self.coords_tape[self.calls]
         elif resized:  # (ox, oy, w, h, flags) records; this step's counts from the cutter's own schedule
@@ -700,6 +738,8 @@ class ClipGuidance:
         geo = self._upload_geometry(resize_table(coords, H, W) if resized else crop_geometry(coords, H, W), dev)
         N = cutn * B
         wm = self._wm.get(B)
+        if wm is None and self.dirs_list is not None:
+            wm = self._split_weight_matrix(B, dev)
         if wm is None:
             if self.shard is None:
                 wm = prompt_weight_matrix(self.weights.cpu(), B, dev)
@@ -721,13 +761,16 @@ class ClipGuidance:
             self.lpips_loss, _ = self.lpips.loss_grad(x_in, grad_scale=self.init_scale, g=gclip, accumulate=False,
                                                       loss=self._b("lpips_loss", (B,), dev))
             acc = 1
-        clip_part = self._b("clip_part", (len(self.towers) * N,), dev)
-        if resized:
+        clip_part = self._b("clip_part", (len(self.towers) * N * self._clip_kinds(),), dev)
+        self.clip_part = clip_part
+        if self.dirs_list is not None:
+            self._clip_leg_direction(x_in, geo, coords, wm, self._wmd[B], gclip, clip_part, acc)
+        elif resized:
             self._clip_leg_resized(x_in, geo, cutn, wm, gclip, clip_part, acc)
         elif self.make_cutouts.augs is not None:
             self._clip_leg_with_augs(x_in, coords, wm, gclip, clip_part, acc)
         for k, (tower, targets) in enumerate(zip(self.towers, self.targets_list)):
-            if resized or self.make_cutouts.augs is not None:
+            if resized or self.make_cutouts.augs is not None or self.dirs_list is not None:
                 break
             cs, patch = tower.input_resolution, tower.patch
             if patch:  # ViT towers: the cutout kernel writes the patch rows of the patch-embedding GEMM directly (layout 1)
@@ -780,7 +823,7 @@ class ClipGuidance:
         gpart = self._b("gpart", (nblk, 2), dev)
         ctx.check(lib.cgd_grad_finish(ctx.h, gdir.data_ptr(), gunet.data_ptr(), g.data_ptr(), gpart.data_ptr(), B, H, W, s))
         self.scalars = self._b("scalars", (8,), dev)
-        ctx.check(lib.cgd_scalars(ctx.h, clip_part.data_ptr(), len(self.towers) * N, lpart.data_ptr(), gpart.data_ptr(), B, H, W,
+        ctx.check(lib.cgd_scalars(ctx.h, clip_part.data_ptr(), clip_part.numel(), lpart.data_ptr(), gpart.data_ptr(), B, H, W,
                                   int(self.use_magnitude), self.scalars.data_ptr(), s))
         self._keep = geo
         return g
@@ -789,6 +832,164 @@ class ClipGuidance:
         """Fraction of the run that is done, from the closure counter (as guidance_schedule measures it)."""
         total = self.diffusion.num_timesteps
         return (total - self.current_timestep) / total
+
+    # -- directional loss ------------------------------------------------------------------------------
+    def _clip_kinds(self):
+        """Partial-loss rows per (tower, cut, sample): 2 when target prompts and direction prompts are both present, else 1."""
+        return 2 if self.dirs_list is not None and self.targets_list[0].shape[0] > 0 else 1
+
+    def _split_weight_matrix(self, B, dev):
+        """The B x P matrix of prompt_weight_matrix over targets and directions together (the B <-> P pairing rule sees the whole list,
+        rows as `shard` takes them), split by column into the target part (returned, kept in _wm) and the direction part (_wmd)."""
+        cols = self.direction_columns
+        P = self.weights.numel() + len(cols)
+        tcols = [c for c in range(P) if c not in cols]
+        full = th.zeros(P)
+        full[tcols] = self.weights.cpu()
+        full[cols] = self.direction_weights.cpu()
+        if self.shard is None:
+            m = prompt_weight_matrix(full, B, dev)
+        else:
+            m = prompt_weight_matrix(full, self.shard[1], dev)[self.shard[0]]
+        self._wm[B], self._wmd[B] = m[:, tcols].contiguous(), m[:, cols].contiguous()
+        return self._wm[B]
+
+    def _direction_source_on(self, dev, B, H, W):
+        """The source image on the device, (1 or B, 3, H, W): a (1, ...) source is shared by all samples, one with the run's global batch
+        gives this rank its rows."""
+        hit = self._buf.get("_direction_src")
+        if hit is not None and hit[0] == (dev, B, H, W):
+            return hit[1]
+        src = self.direction_source
+        if tuple(src.shape[-2:]) != (H, W):
+            raise ValueError(f"direction_source is {src.shape[-2]} x {src.shape[-1]}, the sample is {H} x {W}")
+        if self.shard is not None and src.shape[0] == self.shard[1] and src.shape[0] > 1:
+            src = src[self.shard[0]]
+        if src.shape[0] not in (1, B):
+            raise ValueError(f"direction_source holds {src.shape[0]} images, the batch has {B}: give one image or one per sample")
+        src = src.to(dev).contiguous()
+        self._buf["_direction_src"] = ((dev, B, H, W), src)
+        return src
+
+    def _clip_leg_direction(self, x_in, geo, coords, wm, wmd, gclip, clip_part, accumulate):
+        """The CLIP leg with direction prompts, for the plain and the resized cutter.  Per tower, in tower order, on this step's uploaded boxes
+        (and flags): cutouts of the source image -> tower forward (into buffers of their own: the tower keeps its last input for dgrad, and
+        dgrad differentiates the LAST forward, so the source goes first) -> cutouts of x_in -> tower forward -> spherical loss (only with
+        target prompts) -> directional loss (accumulating onto the spherical gradient when that ran) -> tower dgrad -> the cutouts' adjoint
+        into gclip.  Partials: per tower the spherical rows (if any), then the directional rows.  With cached_cutouts the boxes do not
+        change, and the source embeddings of a cut count are computed once.  _clip_leg_direction_torch is the same leg with autograd."""
+        ctx, lib = self.ctx, self.ctx.lib
+        B, _, H, W = x_in.shape
+        dev = x_in.device
+        s = ctx.stream()
+        resized = isinstance(self.make_cutouts, MakeCutoutsResized)
+        cutn = len(coords)
+        N = cutn * B
+        src = self._direction_source_on(dev, B, H, W)
+        Bs = src.shape[0]
+        kinds, has_t = self._clip_kinds(), int(self.targets_list[0].shape[0] > 0)
+        if resized:
+            flags_p = geo.data_ptr() + 16 * cutn
+            scratch = self._b("resize_scratch", (max(1, lib.cgd_cutouts_resize_scratch_floats(B, H, W, cutn)),), dev)
+
+        def cut_fwd(img, nb, out, cs, layout, patch):
+            if resized:
+                ctx.check(lib.cgd_cutouts_resize_fwd(ctx.h, img.data_ptr(), geo.data_ptr(), flags_p, out.data_ptr(), nb, H, W, cutn, cs, layout, patch, s))
+            else:
+                ctx.check(lib.cgd_cutouts_fwd(ctx.h, img.data_ptr(), geo.data_ptr(), out.data_ptr(), nb, H, W, cutn, cs, layout, patch, s))
+
+        boxes = [tuple(c) for c in coords]
+        hit = self._src_emb.get((cutn, B)) if self.cached_cutouts else None
+        src_embs = hit[1] if hit is not None and hit[0] == boxes else None
+        fresh = []
+        acc = accumulate
+        for k, (tower, targets, dirs) in enumerate(zip(self.towers, self.targets_list, self.dirs_list)):
+            cs, patch = tower.input_resolution, tower.patch
+            layout = 1 if patch else 0
+            gsz = cs // patch if patch else 0
+            shape = (lambda n: (n * gsz * gsz, 3 * patch * patch)) if patch else (lambda n: (n, 3, cs, cs))
+            kind = "patches" if patch else "cut_images"
+            if src_embs is None:
+                src_in = self._b(f"src_{kind}{k}", shape(cutn * Bs), dev)
+                cut_fwd(src, Bs, src_in, cs, layout, patch)
+                name = f"src_emb{k}_{cutn}" if self.cached_cutouts else f"src_emb{k}"
+                semb = tower.encode_image(src_in, layout=layout, n=cutn * Bs, out=self._b(name, (cutn * Bs, tower.out_dim), dev))
+                fresh.append(semb)
+            else:
+                semb = src_embs[k]
+            clip_in = self._b(f"{kind}{k}", shape(N), dev)
+            cut_fwd(x_in, B, clip_in, cs, layout, patch)
+            emb = tower.encode_image(clip_in, layout=layout, n=N, out=self._b(f"emb{k}", (N, tower.out_dim), dev))
+            demb = self._b(f"demb{k}", (N, tower.out_dim), dev)
+            base = k * N * kinds
+            if has_t:
+                ctx.check(lib.cgd_spherical_loss(ctx.h, emb.data_ptr(), targets.data_ptr(), wm.data_ptr(), demb.data_ptr(),
+                                                 clip_part[base:].data_ptr(), cutn, B, targets.shape[0], tower.out_dim, self.cgs, s))
+            ctx.check(lib.cgd_directional_loss(ctx.h, emb.data_ptr(), semb.data_ptr(), dirs.data_ptr(), wmd.data_ptr(), demb.data_ptr(),
+                                               clip_part[base + N * has_t:].data_ptr(), cutn, B, Bs, dirs.shape[0], tower.out_dim, self.cgs,
+                                               has_t, s))
+            dclip_in = tower.dgrad(demb, self._b(f"dclip_in{k}", tuple(clip_in.shape), dev))
+            if resized:
+                ctx.check(lib.cgd_cutouts_resize_bwd(ctx.h, dclip_in.data_ptr(), geo.data_ptr(), flags_p, gclip.data_ptr(), scratch.data_ptr(),
+                                                     B, H, W, cutn, cs, layout, patch, acc, s))
+            else:
+                ctx.check(lib.cgd_cutouts_bwd(ctx.h, dclip_in.data_ptr(), geo.data_ptr(), gclip.data_ptr(), B, H, W, cutn, cs, layout, patch, acc, s))
+            acc = 1
+            if k == 0:
+                self.emb = emb
+        if self.cached_cutouts and src_embs is None:
+            self._src_emb[(cutn, B)] = (boxes, fresh)
+
+    def _clip_leg_direction_torch(self, x_in, geo, coords, wm, wmd, gclip, clip_part, accumulate):
+        """The torch restatement of _clip_leg_direction (the equivalence reference of the tests): crop / pool or resize / normalise in torch,
+        the CLIP tower as the autograd node over cgd_*_forward / _dgrad, both losses in torch ops.  The source forward runs first here too."""
+        from .nets import EncodeImageFunction
+        B, _, H, W = x_in.shape
+        dev = x_in.device
+        mean = th.tensor(CLIP_MEAN, device=dev).view(1, 3, 1, 1)
+        std = th.tensor(CLIP_STD, device=dev).view(1, 3, 1, 1)
+        resized = isinstance(self.make_cutouts, MakeCutoutsResized)
+        n = len(coords)
+        N = n * B
+        src = self._direction_source_on(dev, B, H, W)
+        kinds, has_t = self._clip_kinds(), int(self.targets_list[0].shape[0] > 0)
+
+        def cuts(img, cs):
+            img = img.add(1).div(2)
+            if resized:
+                out = self.make_cutouts.resized(img, coords, cs)
+            else:
+                out = th.cat([F.adaptive_avg_pool2d(img[:, :, oy:oy + size, ox:ox + size], cs) for ox, oy, size in coords])
+            return ((out - mean) / std).contiguous()
+
+        clip_part.zero_()
+        with th.enable_grad():
+            xr = x_in.detach().requires_grad_()
+            total = 0
+            for k, (tower, targets, dirs) in enumerate(zip(self.towers, self.targets_list, self.dirs_list)):
+                with th.no_grad():
+                    sn = F.normalize(tower.encode_image(cuts(src, tower.input_resolution)).clone().view(n, src.shape[0], -1), dim=-1)
+                emb = EncodeImageFunction.apply(cuts(xr, tower.input_resolution), tower).view(n, B, -1)
+                en = F.normalize(emb, dim=-1)
+                delta = en - sn
+                live = delta.norm(dim=-1, keepdim=True) > 1e-6
+                safe = th.where(live, delta, th.ones_like(delta))
+                cos = th.where(live, (safe / safe.norm(dim=-1, keepdim=True)) @ dirs.t(), th.zeros((), device=dev))  # (n, B, P_d)
+                l_dir = ((1 - cos) * wmd.view(1, B, -1)).sum(2).mean(0).sum() * self.cgs
+                total = total + l_dir
+                clip_part[k * N * kinds + N * has_t] = l_dir.detach()
+                if has_t:
+                    d = (en.unsqueeze(2) - targets.view(1, 1, -1, targets.shape[-1])).norm(dim=-1).div(2).arcsin().pow(2).mul(2)  # (n, B, P)
+                    l_sph = (d * wm.view(1, B, -1)).sum(2).mean(0).sum() * self.cgs
+                    total = total + l_sph
+                    clip_part[k * N * kinds] = l_sph.detach()
+                if k == 0:
+                    self.emb = emb.detach().view(N, -1)
+            g_in, = th.autograd.grad(total, xr)
+        if accumulate:
+            gclip.add_(g_in)
+        else:
+            gclip.copy_(g_in)
 
     def _clip_leg_resized(self, x_in, table, cutn, wm, gclip, clip_part, accumulate):
         """MakeCutoutsResized: per tower, in tower order, on the same boxes and flags (`table`: the uploaded resize_table) at the tower's
@@ -918,13 +1119,21 @@ class ClipGuidance:
         snap = {"scalars": HostCopy(self.scalars.clone()), "lpips": HostCopy(self.lpips_loss.clone()) if self.lpips is not None else None}
         if self.classifier is not None:
             snap["classifier"] = HostCopy(self.classifier_logp.clone())
+        if self.dirs_list is not None:
+            snap["direction"] = HostCopy(self.clip_part.clone())
         return snap
+
+    def _direction_share(self, clip_part):
+        """The directional rows of the per-tower partials (towers, kinds, N): their sum is the directional share of 'CLIP Loss'."""
+        return float(clip_part.double().view(len(self.towers), self._clip_kinds(), -1)[:, -1].sum().item())
 
     def log(self, snapshot=None):
         """Scalar log of the last call (or of a `snapshot()`) with the reference's keys (one host sync; call lazily)."""
         v = (snapshot["scalars"].get() if snapshot is not None else self.scalars).tolist()
         lpips_loss = snapshot["lpips"].get() if (snapshot is not None and snapshot["lpips"] is not None) else self.lpips_loss
         out = {"CLIP Loss": v[0], "Range Loss": v[2], "TV Loss": v[1]}
+        if self.dirs_list is not None:  # already part of 'CLIP Loss' and 'Total Loss' (cgd_scalars sums every partial row)
+            out["Direction Loss"] = self._direction_share(snapshot["direction"].get() if snapshot is not None else self.clip_part)
         if self.sats != 0:
             out["Saturation Loss"] = v[3]
         out["Total Loss"] = v[4]

@@ -332,6 +332,16 @@ int cgd_cutouts_resize_weights(int n, int m, float* w, int32_t* left, int* taps)
 int cgd_spherical_loss(cgd_ctx* ctx, const float* emb, const float* targets_n, const float* weights, float* d_emb, float* loss_part,
                        int cutn, int B, int P, int D, float clip_guidance_scale, void* stream);
 
+/* ---- directional CLIP loss of a prompt-pair edit, with its gradient.  emb (cutn*B, D) row = cut*B+b: the generated image;
+ *      src_emb (cutn*Bs, D), Bs = 1 or B, row = cut*Bs + (Bs == 1 ? 0 : b): the source image through the same cutout (no gradient);
+ *      dirs_n (P, D) L2-normalised text directions; weights (B, P) dense, zero columns are skipped.  With e^ = e / max(|e|, 1e-12),
+ *      s^ likewise, delta = e^ - s^, n = |delta| and cos_p = delta . d_p / n (0 when n <= 1e-6: such a row has no gradient),
+ *      loss_part[cut*B+b] = c sum_p w_bp (1 - cos_p), c = clip_guidance_scale / cutn, and d_emb (cutn*B, D) is set to (accumulate 0) or
+ *      increased by (accumulate 1: the spherical launch of the same step wrote it) d loss_part / d emb.  D > 2048, Bs other than 1 or B,
+ *      a count below 1 or a null pointer fail with -2 before any launch. ---- */
+int cgd_directional_loss(cgd_ctx* ctx, const float* emb, const float* src_emb, const float* dirs_n, const float* weights, float* d_emb,
+                         float* loss_part, int cutn, int B, int Bs, int P, int D, float clip_guidance_scale, int accumulate, void* stream);
+
 /* per-timestep scalars of the (respaced) diffusion process, float64 tables evaluated on the host */
 typedef struct cgd_step_coef {
   float sqrt_recip;             /* sqrt(1/abar_t)                                  */

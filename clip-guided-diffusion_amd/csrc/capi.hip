@@ -356,6 +356,37 @@ int cgd_op_gemm(cgd_ctx* ctx, const float* A, int lda, const float* B, int ldb, 
   }
   return cgd_launch_gemm(ctx, p, S(stream));
 }
+static GemmParams gemm_gn_bwd_params(const float* A, int lda, const float* Wt, int ldw, float* dx, int lddx, const float* x, int ldx, const float* dz,
+                                     int lddz, const float* add, int ldadd, const float* coef, const float* bcoef, int Bn, int HW, int N, int K) {
+  GemmParams p;
+  p.A = A; p.lda = lda; p.B = Wt; p.ldb = ldw; p.C = dx; p.ldc = lddx;
+  p.M = Bn * HW; p.N = N; p.K = K; p.force_tile = 513; p.no_split = 1;
+  p.gnf_x = x; p.gnf_ldx = ldx; p.gnf_dz = dz; p.gnf_lddz = lddz; p.gnf_add = add; p.gnf_ldadd = ldadd;
+  p.gnf_coef = coef; p.gnf_bcoef = bcoef; p.gnf_hw = HW;
+  return p;
+}
+int cgd_op_gemm_gn_bwd_accepts(int precision, int lda, int ldw, int lddx, int ldx, int lddz, int ldadd, int x_misalign, int Bn, int HW, int N, int K) {
+  if (Bn <= 0 || HW <= 0 || (long)Bn * HW > 0x7fffffffL) return 0;
+  cgd_ctx ctx;  // plain host object: defaults of cgd_ctx_create, nothing allocated (as in cgd_op_plan)
+  ctx.precision = precision;
+  float* const dummy = (float*)(uintptr_t)4096;  // only the alignment of the pointers is inspected
+  const float* xs = (const float*)((uintptr_t)4096 + (uintptr_t)x_misalign);
+  return cgd_gemm_fuses_gnb(&ctx, gemm_gn_bwd_params(dummy, lda, dummy, ldw, dummy, lddx, xs, ldx, dummy, lddz, ldadd ? dummy : nullptr, ldadd, dummy, dummy,
+                                                     Bn, HW, N, K)) ? 1 : 0;
+}
+int cgd_op_gemm_gn_bwd(cgd_ctx* ctx, const float* A, int lda, const float* Wt, int ldw, float* dx, int lddx, const float* x, int ldx,
+                       const float* dz, int lddz, const float* add, int ldadd, const float* coef, const float* bcoef, int Bn, int HW, int N, int K,
+                       void* stream) {
+  CGD_NEED_CTX(ctx);
+  if (Bn <= 0 || HW <= 0 || (long)Bn * HW > 0x7fffffffL) CGD_FAIL(ctx, "cgd_op_gemm_gn_bwd: bad sample count / rows per sample");
+  const GemmParams p = gemm_gn_bwd_params(A, lda, Wt, ldw, dx, lddx, x, ldx, dz, lddz, add, ldadd, coef, bcoef, Bn, HW, N, K);
+  // refuse here, with a message, what the kernel cannot run: no other kernel stands in for it
+  if (!x || !dz || !coef || !bcoef) CGD_FAIL(ctx, "cgd_op_gemm_gn_bwd: x, dz, coef and bcoef are required");
+  if (!cgd_gemm_fuses_gnb(ctx, p))
+    CGD_FAIL(ctx, "cgd_op_gemm_gn_bwd: needs a bf16x3 context, K a multiple of 64, N of 32, row strides multiples of 4, 16-byte aligned operands and "
+                  "samples of a multiple of 128 rows (or one sample)");
+  return cgd_launch_gemm(ctx, p, S(stream));
+}
 int cgd_op_pack_conv3x3_frag(cgd_ctx* ctx, const float* w, float* out, int Co, int Ci, int dgrad, void* stream) {
   CGD_NEED_CTX(ctx);
   return cgd_pack_conv3x3_frag(ctx, w, out, Co, Ci, dgrad, S(stream));

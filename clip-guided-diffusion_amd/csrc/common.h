@@ -305,6 +305,15 @@ struct GemmParams {
   const float* a_freqs = nullptr;
   const float* a_table = nullptr;
   const int64_t* a_idx = nullptr;
+  // weight GEMM on hgemm2 in bf16x3 mode, one slice (cgd_gemm_fuses_gnb): the epilogue adds the backward of a GroupNorm + SiLU over the output's own
+  // pixels: C = alpha A W^T (+ bias + R) (+ gnf_add) + gn_bwd(gnf_x, gnf_dz), i.e. gn_bwd_apply_kernel<1> with this GEMM's result as its `add` operand.
+  // gnf_coef / gnf_bcoef = the norm's [sample][N][4] tables (kernels.h cgd_gn_coef / cgd_gn_bcoef), gnf_hw = rows per sample
+  const float* gnf_x = nullptr;
+  const float* gnf_dz = nullptr;
+  const float* gnf_add = nullptr;
+  const float* gnf_coef = nullptr;
+  const float* gnf_bcoef = nullptr;
+  int gnf_ldx = 0, gnf_lddz = 0, gnf_ldadd = 0, gnf_hw = 0;
   int defer = 0;       // 1: if the launch splits K, leave the slices in the workspace (ctx->pending): the caller guarantees that the
                        // next kernel reading C is one that consumes a SplitSrc (cgd_take_pending); anything else flushes first
 };
@@ -374,6 +383,9 @@ int cgd_launch_gemm(cgd_ctx* ctx, GemmParams p, hipStream_t s);
 bool cgd_conv_uses_hconv(cgd_ctx* ctx, GemmParams p);
 // would cgd_launch_gemm run this GEMM on hgemm2 in one slice (the only path that fuses an activation into its epilogue)?
 bool cgd_gemm_fuses_act(cgd_ctx* ctx, GemmParams p);
+bool cgd_gemm_fuses_gnb(cgd_ctx* ctx, GemmParams p);  // ... or a GroupNorm's backward (GemmParams::gnf_*)
+bool cgd_conv_takes_gnb(cgd_ctx* ctx, GemmParams p);  // a dgrad conv that will leave the backward records of the GroupNorm in its gnb_* fields
+bool cgd_wconv_takes_gnb(const cgd_ctx* ctx, const GemmParams& g);
 // would cgd_launch_gemm run this GEMM on the GEMV kernel (the only one that forms its A rows on the fly: GemmParams::a_mode)?
 bool cgd_gemm_is_gemv(cgd_ctx* ctx, GemmParams p);
 

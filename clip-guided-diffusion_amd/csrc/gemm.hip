@@ -663,6 +663,29 @@ bool cgd_gemm_fuses_act(cgd_ctx* ctx, GemmParams p) {
   return ok;
 }
 
+// the weight GEMM whose epilogue also applies a GroupNorm's backward (GemmParams::gnf_*): hgemm2 on 128-row tiles in bf16x3 mode, one slice
+bool cgd_gemm_fuses_gnb(cgd_ctx* ctx, GemmParams p) {
+  int tile = 0, kernel = 0;
+  const std::string keep = ctx->err;
+  p.no_split = 1;
+  const bool shape_ok = !p.conv && p.gnf_x && p.gnf_dz && p.gnf_coef && p.gnf_bcoef && p.gnf_hw > 0 && p.M % p.gnf_hw == 0 &&
+                        (p.gnf_hw % 128 == 0 || p.gnf_hw == p.M) && !((p.gnf_ldx | p.gnf_lddz | (p.gnf_add ? p.gnf_ldadd : 0)) & 3) &&
+                        !(((uintptr_t)p.gnf_x | (uintptr_t)p.gnf_dz | (uintptr_t)p.gnf_add | (uintptr_t)p.gnf_coef | (uintptr_t)p.gnf_bcoef) & 15);
+  const bool ok = shape_ok && ctx->precision == CGD_PREC_BF16X3 && ctx->hgemm_var != 0 && (long)p.M * p.lda < (1L << 29) && !p.act_out && !p.act_in &&
+                  !p.skip_group && cgd_plan_gemm(ctx, p, &tile, &kernel) == 0 && kernel == 2 && p.splitk == 1;
+  ctx->err = keep;
+  return ok;
+}
+
+// a dgrad conv that will run on wconv_kernel in one slice and take a GroupNorm's backward sums in its epilogue (GemmParams::gnb_*)
+bool cgd_conv_takes_gnb(cgd_ctx* ctx, GemmParams p) {
+  int tile = 0, kernel = 0;
+  const std::string keep = ctx->err;
+  const bool ok = p.conv && cgd_plan_gemm(ctx, p, &tile, &kernel) == 0 && tile == 515 && p.splitk == 1 && cgd_wconv_takes_gnb(ctx, p);
+  ctx->err = keep;
+  return ok;
+}
+
 int cgd_flush_pending(cgd_ctx* ctx, hipStream_t s) {
   if (!ctx->pending.valid) return 0;
   const PendingReduce& q = ctx->pending;
@@ -706,6 +729,8 @@ int cgd_launch_gemm(cgd_ctx* ctx, GemmParams p, hipStream_t s) {
   if ((p.act_out || p.act_in) && (p.act < 1 || p.act > 3)) CGD_FAIL(ctx, "cgd_launch_gemm: activation code must be 1 (SiLU), 2 (QuickGELU) or 3 (GELU)");
   if ((p.act_out || p.act_in) && !(use_g && p.splitk == 1 && ctx->hgemm_var != 0))
     CGD_FAIL(ctx, "cgd_launch_gemm: only hgemm2 in one slice fuses an activation into its epilogue (cgd_gemm_fuses_act)");
+  if (p.gnf_x && !(use_g && p.splitk == 1))
+    CGD_FAIL(ctx, "cgd_launch_gemm: only hgemm2 in one slice applies a GroupNorm's backward in its epilogue (cgd_gemm_fuses_gnb)");
   if (p.splitk > 1) p.ws = ctx->ws;
   ProfRec pr;
   CGD_TRY(cgd_prof_begin(ctx, &pr, use_h ? (tile == 515 ? CGD_PROF_WCONV : (tile == 516 ? CGD_PROF_KCONV : CGD_PROF_HCONV)) : CGD_PROF_GEMM, 2.0 * p.M * p.N * p.K * p.nbatch, s));

@@ -61,6 +61,14 @@ struct HGemmParams {
   int nmajor;  // tile order within the XCD-contiguous runs: 0 = M-tile major (an XCD owns row panels and streams all weights),
                // 1 = N-tile major (an XCD owns weight column panels, read from HBM once and kept in its 4 MB L2; the small
                // activation matrix is what every XCD re-reads): chosen when the weights are the larger operand (N >= M)
+  // hgemm2 GNB instantiation (GemmParams::gnf_*): the epilogue adds the backward of a GroupNorm + SiLU over the output's own pixels
+  const float* gnf_x;      // the norm's forward input, row stride gnf_ldx
+  const float* gnf_dz;     // its upstream gradient, row stride gnf_lddz
+  const float* gnf_add;    // optional further addend, row stride gnf_ldadd
+  const float* gnf_coef;   // [sample][N][4] {a, b, gcoef, mean}
+  const float* gnf_bcoef;  // [sample][N][4] {rstd gcoef, A2, A3, 0}
+  int gnf_ldx, gnf_lddz, gnf_ldadd;
+  int gnf_hw;              // rows per sample (a multiple of the 128-row tile, or all M rows)
 };
 
 template <int MODE>
@@ -325,7 +333,11 @@ constexpr int h2_lcm(int a, int b) { return a / h2_gcd(a, b) * b; }
 // its partial block to group 0 through LDS before the epilogue.  Per wavefront the instruction stream of a chunk is unchanged.
 // GELU: the fused activation (act_out / act_in) is the exact GELU, code 3.  A template parameter, not a branch on p.act: erff inlined into the unrolled
 // epilogues nearly triples the kernel (8363 -> 22573 instructions at TM = 128), and the instantiations every other launch runs stay as they were.
-template <int MODE, int TM, int RING = 8, int NSET = (TM == 64 ? 2 : 1), int KG = 1, bool GELU = false>
+// GNB (128-row tiles, bf16x3): the LDS epilogue also applies the backward of the GroupNorm + SiLU that read the same pixels (the 1x1 skip dgrad of a
+// ResBlock and GN1's backward both end in the block's dx): C = alpha acc (+ bias + R) (+ add) + dz silu'(x a + b) A1 - (x - mean) A2 - A3, the
+// arithmetic of gn_bwd_apply_kernel<1> (norm.hip) with this GEMM's block as its `add` operand.  x / dz / add are read and C is written once, as
+// whole 128-byte lines with the non-temporal policy: the GEMM's C write, its read-back and the norm's launch go away.
+template <int MODE, int TM, int RING = 8, int NSET = (TM == 64 ? 2 : 1), int KG = 1, bool GELU = false, bool GNB = false>
 __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restrict__ Ag, const uint4* __restrict__ Bg, float* Cg,
                                                      const float* __restrict__ biasg, const float* Rg, float* __restrict__ wsg,
                                                      const HGemmParams p) {
@@ -338,6 +350,7 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
   constexpr int DIST = RING - 1;
   static_assert(RING % 4 == 0 && RING >= 8 && NSET >= 1, "hgemm2: ring depth in whole chunks, at least two");
   static_assert(KG == 1 || (KG == 2 && MODE == 1), "hgemm2: K-groups need the LDS epilogue of the bf16x3 mode");
+  static_assert(!GNB || (MODE == 1 && TM == 128 && KG == 1 && !GELU), "hgemm2: the GroupNorm-backward epilogue is the LDS epilogue of the 128-row tile");
   __shared__ __attribute__((aligned(16))) __bf16 lds[2 * NPL * PLANE];
   const int tid = threadIdx.x, lane = tid & 63, wn = (tid >> 6) & 3, kg = tid >> 8;
   const int l31 = lane & 31, hh = lane >> 5;
@@ -524,7 +537,7 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
   H_STAMP(29);
   // ---- epilogue: D = W x A^T in the 32x32 C/D layout: column (lane & 31) = row m of C, accumulator quad g = columns 8g + 4hh ..
   const int cb0 = n0 + wn * 32;
-  if (MODE == 1 && (p.lep || KG == 2)) {
+  if (MODE == 1 && (p.lep || KG == 2 || GNB)) {
     // Stores straight from that layout are 16-byte pieces of 64 different rows per instruction, bound by the CU's store path (the finding
     // of profiles/r3_wconv_timeline.txt for the same layout in wconv_kernel).  The staging buffers are free after the last chunk: each
     // wavefront parks its TM x 32 block in its own slab (16-byte unit q of row r at q ^ (r & 7): conflict-free both ways), reads it
@@ -582,10 +595,21 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
     const cgd_f32x4 z4 = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
     const cgd_f32x4 bv = hb ? cgd_f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]} : z4;
     const float ka = p.act == 2 ? 1.702f : 1.f;  // QuickGELU x * sigmoid(1.702 x) / SiLU
-    constexpr int EB = TM == 64 ? 8 : 4;         // rows in flight per lane (the 96- / 128-row instantiations must stay within 256 registers)
+    constexpr int EB = (TM == 64 || GNB) ? 8 : 4;  // rows in flight per lane (the 96- / 128-row instantiations must stay within 256 registers)
+    // GNB: the lane's four channels of the tile's sample (a tile never straddles two samples: the launcher checks)
+    cgd_f32x4 gcf[4], gbf[4];
+    if constexpr (GNB) {
+      const long cb = ((long)(m0 / p.gnf_hw) * p.N + col) * 4;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        gcf[e] = *(const cgd_f32x4*)&p.gnf_coef[cb + 4 * e];
+        gbf[e] = *(const cgd_f32x4*)&p.gnf_bcoef[cb + 4 * e];
+      }
+    }
 #pragma unroll
     for (int i0 = 0; i0 < TM / 8; i0 += EB) {
       cgd_f32x4 v[EB], rv[EB], uv[EB];
+      cgd_f32x4 gx[EB], gd[EB], ga[EB];
       long row[EB];
       bool ok[EB];
 #pragma unroll
@@ -610,11 +634,33 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
 #pragma unroll
         for (int u = 0; u < EB; ++u) uv[u] = *(const cgd_f32x4*)&p.act_in[row[u] * p.ld_act + col];
       }
+      if constexpr (GNB) {
+#pragma unroll
+        for (int u = 0; u < EB; ++u) {
+          gx[u] = cgd_ld16_nt<cgd_f32x4>(&p.gnf_x[row[u] * p.gnf_ldx + col]);
+          gd[u] = cgd_ld16_nt<cgd_f32x4>(&p.gnf_dz[row[u] * p.gnf_lddz + col]);
+          if (p.gnf_add) ga[u] = cgd_ld16_nt<cgd_f32x4>(&p.gnf_add[row[u] * p.gnf_ldadd + col]);
+        }
+      }
 #pragma unroll
       for (int u = 0; u < EB; ++u) {
         cgd_f32x4 o = v[u] * p.alpha;
         if (hb) o += bv;
         if (Rg) o += rv[u];
+        if constexpr (GNB) {  // same operations in the same order as gn_bwd_apply_kernel<1> with o (+ add) as its addend
+          if (p.gnf_add) o += ga[u];
+          cgd_f32x4 t;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float un = gx[u][e] * gcf[e][0] + gcf[e][1];
+            const float sg = 1.f / (1.f + __expf(-un));
+            const float d = gd[u][e] * (sg * (1.f + un * (1.f - sg)));
+            t[e] = d * gbf[e][0] - (gx[u][e] - gcf[e][3]) * gbf[e][1] - gbf[e][2];
+          }
+          o = t + o;
+          if (ok[u]) cgd_st16_nt(&Cg[row[u] * p.ldc + col], o);
+          continue;
+        }
         if (p.act_in) {  // backward through the activation: multiply by act'(u), same arithmetic as elem.hip dact_f
           cgd_f32x4 d;
           if constexpr (GELU) {
@@ -888,6 +934,7 @@ void cgd_frag_cache_clear(cgd_ctx* ctx) {
 // rows per workgroup tile: hgemm_var 0 = hgemm_kernel (128 x 128, 64 x 64 per wavefront); 1 = hgemm2_kernel with 64-row tiles
 // while 128-row tiles would not give every CU a workgroup, 128 rows otherwise; 2 / 3 force hgemm2 with 128 / 64 rows
 int cgd_hgemm_tile_m(const cgd_ctx* ctx, const GemmParams& p) {
+  if (p.gnf_x) return GM;  // the GroupNorm-backward epilogue exists for the 128-row tile only
   if (ctx->hgemm_var == 3) return 64;
   if (ctx->hgemm_var == 1 && (long)cdiv(p.M, GM) * cdiv(p.N, GN) < ctx->num_cu) {
     // (round 5) 96-row tiles where 64-row tiles need more workgroups than the chip has CUs but 96-row tiles do not: the ViT's M = 800,
@@ -906,7 +953,7 @@ int cgd_hgemm_chunks(const GemmParams& p) { return p.K / GK; }
 // a forced launch used to fail with "does not support this problem" when a policy knob said no)
 bool cgd_kgemm_capable(const cgd_ctx* ctx, const GemmParams& p) {
   if ((uintptr_t)p.bias & 15) return false;  // the epilogue reads the bias 16 bytes at a time
-  return p.weight && p.M > 4 && cgd_hgemm_supported(ctx, p) && !p.act_out && !p.act_in && !p.skip_group && p.splitk <= 1 && (long)p.M * p.lda < (1L << 29);
+  return p.weight && p.M > 4 && cgd_hgemm_supported(ctx, p) && !p.act_out && !p.act_in && !p.skip_group && !p.gnf_x && p.splitk <= 1 && (long)p.M * p.lda < (1L << 29);
 }
 bool cgd_kgemm_supported(const cgd_ctx* ctx, const GemmParams& p) {
   const bool rows_ok = p.M <= ctx->kgemm_max_m || (p.M <= ctx->kgemm_big_m && p.N <= ctx->kgemm_big_n);
@@ -979,7 +1026,7 @@ int cgd_launch_hgemm(cgd_ctx* ctx, const GemmParams& g, hipStream_t s) {
     packed = ctx->frag_tmp;
   }
   if (!packed) CGD_FAIL(ctx, "hgemm: out of memory for the packed weight copy");
-  HGemmParams p;
+  HGemmParams p = {};
   p.lda = g.lda; p.ldc = g.ldc; p.ldr = g.ldr;
   p.M = g.M; p.N = g.N; p.K = g.K; p.splitk = g.splitk; p.alpha = g.alpha;
   p.nmajor = (ctx->tile_order == 1 || (ctx->tile_order == 0 && g.N >= g.M)) ? 1 : 0;
@@ -996,8 +1043,22 @@ int cgd_launch_hgemm(cgd_ctx* ctx, const GemmParams& g, hipStream_t s) {
     CGD_FAIL(ctx, "hgemm: skip_group needs hgemm2 in one slice without residual / activation operands");
   const bool gelu = (g.act_out || g.act_in) && g.act == 3;
   if (gelu && !v2) CGD_FAIL(ctx, "hgemm: only hgemm2 fuses the GELU activation");
+  if (g.gnf_x) {
+    // (cgd_gemm_fuses_gnb is the callers' question; this is the kernel's own list)
+    if (!v2 || !x3 || g.splitk > 1 || g.act_out || g.act_in || g.skip_group || !g.gnf_dz || !g.gnf_coef || !g.gnf_bcoef)
+      CGD_FAIL(ctx, "hgemm: the GroupNorm-backward epilogue needs hgemm2 in bf16x3 mode, one slice, no activation operands");
+    if (g.gnf_hw <= 0 || g.M % g.gnf_hw || ((g.gnf_hw % GM) && g.gnf_hw != g.M))
+      CGD_FAIL(ctx, "hgemm: the GroupNorm-backward epilogue needs samples of a multiple of 128 rows (or one sample)");
+    if (((g.gnf_ldx | g.gnf_lddz | (g.gnf_add ? g.gnf_ldadd : 0)) & 3) ||
+        (((uintptr_t)g.gnf_x | (uintptr_t)g.gnf_dz | (uintptr_t)g.gnf_add | (uintptr_t)g.gnf_coef | (uintptr_t)g.gnf_bcoef) & 15))
+      CGD_FAIL(ctx, "hgemm: the GroupNorm-backward epilogue needs row strides that are multiples of 4 and 16-byte aligned operands");
+    p.gnf_x = g.gnf_x; p.gnf_dz = g.gnf_dz; p.gnf_add = g.gnf_add; p.gnf_coef = g.gnf_coef; p.gnf_bcoef = g.gnf_bcoef;
+    p.gnf_ldx = g.gnf_ldx; p.gnf_lddz = g.gnf_lddz; p.gnf_ldadd = g.gnf_ldadd; p.gnf_hw = g.gnf_hw;
+  }
 #define HG_ARGS grid, dim3(256), 0, s, g.A, (const uint4*)packed, g.C, g.bias, g.R, g.ws, p
-  if (!v2) {
+  if (g.gnf_x) {
+    CGD_LAUNCH((hgemm2_kernel<1, 128, 8, 1, 1, false, true>), HG_ARGS);
+  } else if (!v2) {
     if (x3) CGD_LAUNCH((hgemm_kernel<1>), HG_ARGS); else CGD_LAUNCH((hgemm_kernel<2>), HG_ARGS);
   } else if (tm == 64 && x3 && g.K % (2 * GK) == 0 &&
              (ctx->hgemm_kg == 2 || (ctx->hgemm_kg == 0 && (long)grid.x * grid.z <= ctx->num_cu && g.K / (2 * GK) / (int)grid.z >= 4))) {

@@ -22,6 +22,12 @@ size_t cgd_gn_stats_offset(int B, int HW, int C);  // float offset of the {mean,
 int cgd_launch_gn_bwd(cgd_ctx* ctx, const float* x, int ldx, const float* dz, int lddz, float* dx, int lddx, const float* add,
                       int ldadd, int B, int HW, int C, int act, float* scratch, hipStream_t s, const float* add2 = nullptr,
                       int ldadd2 = 0);
+// The same for a GroupNorm + SiLU whose `add` operand is the weight GEMM `sk` (C = dx, same pixels: a ResBlock's 1x1 skip dgrad): ONE launch of
+// that GEMM whose epilogue applies the norm's backward (GemmParams::gnf_*) instead of the GEMM, its dx write, the read-back and the apply pass.
+// Only when the norm's backward sums come from epilogue records of the conv that produced dz and the GEMM kernel takes the operands
+// (cgd_gemm_fuses_gnb); otherwise *done = false, nothing is launched and the caller runs the two launches.
+int cgd_launch_gn_bwd_skip_gemm(cgd_ctx* ctx, GemmParams sk, const float* x, int ldx, const float* dz, int lddz, const float* add2, int ldadd2,
+                                int B, int HW, int C, float* scratch, hipStream_t s, bool* done);
 int cgd_launch_ln_fwd(cgd_ctx* ctx, const float* x, int ldx, float* y, int ldy, int rows, int C, const float* gamma,
                       const float* beta, float eps, float* stats, hipStream_t s);
 int cgd_launch_ln_bwd(cgd_ctx* ctx, const float* x, int ldx, const float* dy, int lddy, float* dx, int lddx, const float* add,

@@ -1323,6 +1323,34 @@ int cgd_launch_gn_bwd(cgd_ctx* ctx, const float* x, int ldx, const float* dz, in
   return 0;
 }
 
+int cgd_launch_gn_bwd_skip_gemm(cgd_ctx* ctx, GemmParams sk, const float* x, int ldx, const float* dz, int lddz, const float* add2, int ldadd2,
+                                int B, int HW, int C, float* scratch, hipStream_t s, bool* done) {
+  *done = false;
+  if (C % 32 || C > 4096 || sk.N != C || sk.M != B * HW || HW <= GN_SMALL_HW || (HW & 127) || !(ctx->gn_epi & 2)) return 0;
+  if (ctx->pending.valid) return 0;  // dz (or anything else) still lies in split-K slices: the two-launch path sums or flushes them
+  int chunk, nchunk;
+  float *part, *stats, *coef, *bcoef;
+  gn_layout(scratch, B, HW, C, &chunk, &nchunk, &part, &stats, &coef, &bcoef);
+  sk.gnf_x = x; sk.gnf_ldx = ldx; sk.gnf_dz = dz; sk.gnf_lddz = lddz; sk.gnf_add = add2; sk.gnf_ldadd = ldadd2;
+  sk.gnf_coef = coef; sk.gnf_bcoef = bcoef; sk.gnf_hw = HW;
+  sk.no_split = 1;
+  if (!cgd_gemm_fuses_gnb(ctx, sk)) return 0;
+  ChanSrc cs;
+  if (!(cgd_chanstats_find(ctx, dz, lddz, (long)B * HW, C, s, &cs, 1) && cs.n0 == C)) return 0;
+  ProfRec pr;  // the norm's algorithmic bytes as in cgd_launch_gn_bwd (x, dz, the skip gradient as `add`, dx); the GEMM files its FLOP itself
+  CGD_TRY(cgd_prof_begin(ctx, &pr, CGD_PROF_GN, (16.0 + (add2 ? 4.0 : 0.0)) * B * HW * C, s));
+  ++ctx->gn_record_merges;
+  int lg = 0;
+  while ((1 << lg) < C / 32) ++lg;
+  CGD_LAUNCH(gn_bwd_coef_ch_kernel, dim3(32, B), dim3(256), 0, s, cs.p0, HW / 128, lg, stats, coef, C, HW, bcoef);
+  CGD_TRY(cgd_launch_gemm(ctx, sk, s));  // (kills the records of an earlier content of dx like every GEMM)
+  CGD_TRY(cgd_prof_stamp(ctx, &pr, s));
+  cgd_prof_push(ctx, &pr);
+  CGD_HIP(ctx, hipGetLastError());
+  *done = true;
+  return 0;
+}
+
 int cgd_launch_ln_fwd(cgd_ctx* ctx, const float* x, int ldx, float* y, int ldy, int rows, int C, const float* gamma,
                       const float* beta, float eps, float* stats, hipStream_t s) {
   const bool vec = C % 256 == 0 && C <= 1024 && !(ldx & 3) && !(ldy & 3) && !(((uintptr_t)x | (uintptr_t)y | (uintptr_t)gamma | (uintptr_t)beta) & 15);

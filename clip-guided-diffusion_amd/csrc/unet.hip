@@ -262,16 +262,27 @@ int ResBlock::bwd(UNet& u, TV dout, TV* din, hipStream_t s) {
   // skip path into dx first (GN1's backward accumulates on top of it further down)
   const float* add = nullptr;
   int ldadd = 0;
+  GemmParams sk;
+  bool fuse_skip = false;
   if (down || up) {
     // identity skip of a resampling block: x_upd = AvgPool2d(2) (adjoint = nearest upsample * 0.25) or nearest upsample (adjoint = 2 x 2 sum) of dout
     // into dx — launched together with the same resampling of d1 behind conv1's dgrad below (round 6: one launch for the two)
     add = dx.p; ldadd = cin;
   } else if (skip_conv) {
-    GemmParams sk;
     sk.A = dout.p; sk.lda = dout.ld; sk.B = skwT; sk.ldb = cout; sk.C = dx.p; sk.ldc = cin;
     sk.M = (int)npo; sk.N = cin; sk.K = cout;
     sk.weight = 1;
-    CGD_TRY(cgd_launch_gemm(ctx, sk, s));
+    // On the large maps the skip dgrad runs BEHIND conv1's dgrad, as one launch whose epilogue applies GN1's backward (cgd_launch_gn_bwd_skip_gemm):
+    // tried only where conv1's dgrad will leave GN1's backward records and the GEMM kernel takes the operands
+    GemmParams probe = sk;
+    probe.gnf_x = x.p; probe.gnf_ldx = x.ld; probe.gnf_dz = d1.p; probe.gnf_lddz = cin; probe.gnf_add = add_skip.p; probe.gnf_ldadd = add_skip.ld;
+    probe.gnf_coef = probe.gnf_bcoef = cgd_gn_coef(s1.p, B, H * W, cin); probe.gnf_hw = H * W;
+    GemmParams c1p;
+    c1p.A = d2.p; c1p.lda = cout; c1p.B = cw1d; c1p.Bpk = cw1dp; c1p.Bwk = wino_ready ? cw1wd : nullptr; c1p.bwk_prec = wino_prec; c1p.ldb = 9 * cout; c1p.C = d1.p; c1p.ldc = cin;
+    c1p.M = (int)npo; c1p.N = cin; c1p.conv = 1; c1p.H = Ho; c1p.W = Wo; c1p.Cin = cout; c1p.defer = 1;
+    c1p.gnb_x = x.p; c1p.gnb_ldx = x.ld; c1p.gnb_coef = cgd_gn_coef(s1.p, B, H * W, cin); c1p.gnb_act = 1;
+    fuse_skip = !(H * W & 127) && cgd_gemm_fuses_gnb(ctx, probe) && cgd_conv_takes_gnb(ctx, c1p);
+    if (!fuse_skip) CGD_TRY(cgd_launch_gemm(ctx, sk, s));
     add = dx.p; ldadd = cin;
   } else {
     add = dout.p; ldadd = dout.ld;
@@ -294,6 +305,15 @@ int ResBlock::bwd(UNet& u, TV dout, TV* din, hipStream_t s) {
     CGD_TRY(u.ensure(d1f, npi * cin));
     CGD_TRY(cgd_launch_resample2x_pair(ctx, 0, d1.p, cin, d1f.p, cin, dout.p, dout.ld, dx.p, cin, B, H, W, cin, 1.f, s));
     dh1 = d1f.p;
+  }
+  if (fuse_skip) {
+    bool done = false;
+    CGD_TRY(cgd_launch_gn_bwd_skip_gemm(ctx, sk, x.p, x.ld, d1.p, cin, add_skip.p, add_skip.ld, B, H * W, cin, s1.p, s, &done));
+    if (done) {
+      *din = TV{dx.p, cin, cin};
+      return 0;
+    }
+    CGD_TRY(cgd_launch_gemm(ctx, sk, s));  // the records did not materialise: the two launches
   }
   // + the gradient of the skip connection that read this block's input (fused here instead of a separate add pass)
   CGD_TRY(cgd_launch_gn_bwd(ctx, x.p, x.ld, dh1, cin, dx.p, cin, add, ldadd, B, H * W, cin, 1, s1.p, s, add_skip.p, add_skip.ld));

@@ -678,6 +678,11 @@ long cgd_wconv_tiles_m(const cgd_ctx* ctx, const GemmParams& p) {
   return (long)(p.M / (p.H * p.W)) * (p.H / (4 * cgd_wconv_nb(ctx, p))) * (p.W >> 4);
 }
 
+// will a launch of this (dgrad) conv take the backward sums of the GroupNorm named by its gnb_* fields in its epilogue?
+bool cgd_wconv_takes_gnb(const cgd_ctx* ctx, const GemmParams& g) {
+  return g.gnb_x && g.gnb_coef && cgd_gn_merges_records(g.H * g.W) && (ctx->gn_epi & 2) && !(g.gnb_ldx & 3) && !((uintptr_t)g.gnb_x & 15) && !g.stats && !g.R;
+}
+
 int cgd_launch_wconv(cgd_ctx* ctx, const GemmParams& g, hipStream_t s) {
   WConvParams p;
   p.lda = g.lda; p.ldc = g.ldc; p.ldr = g.ldr;
@@ -689,7 +694,7 @@ int cgd_launch_wconv(cgd_ctx* ctx, const GemmParams& g, hipStream_t s) {
   const bool merges = cgd_gn_merges_records(g.H * g.W);
   p.stat = (g.stats && merges && (ctx->gn_epi & 1)) ? cgd_chanstats_register(ctx, g.C, g.ldc, g.N, g.M, s) : nullptr;
   p.bstat = nullptr; p.bx = g.gnb_x; p.bcoef = g.gnb_coef; p.ldbx = g.gnb_ldx; p.bact = g.gnb_act;
-  if (g.gnb_x && g.gnb_coef && merges && (ctx->gn_epi & 2) && !(g.gnb_ldx & 3) && !((uintptr_t)g.gnb_x & 15) && !g.stats && !g.R)
+  if (cgd_wconv_takes_gnb(ctx, g))
     p.bstat = cgd_chanstats_register(ctx, g.C, g.ldc, g.N, g.M, s, 1);
   ctx->last_wconv_bstat = p.bstat != nullptr;
   p.nt_out = 1;

@@ -86,6 +86,24 @@ def gemm(ctx, A, B, bias=None, R=None, alpha=1.0, force_tile=0, splitk=1, out=No
     return out
 
 
+def gemm_gn_bwd(ctx, A, W, x, dz, coef, bcoef, add=None, out=None):
+    """dx[B,HW,N] = A[B,HW,K] @ W[N,K]^T (+add) + GroupNorm+SiLU backward of (x, dz) with the per-(sample, channel) tables coef [B,N,4] =
+    {a, b, -, mean} and bcoef [B,N,4] = {A1, A2, A3, -}, in one launch.  A, W, x, dz, add and `out` may be row-strided views."""
+    B, HW, K = A.shape
+    N = W.shape[0]
+    pa, lda = _rows(A, "A")
+    pw, ldw = _rows(W, "W")
+    px, ldx = _rows(x, "x")
+    pdz, lddz = _rows(dz, "dz")
+    padd, ldadd = _rows(add, "add")
+    pc, pbc = _dense(coef, "coef"), _dense(bcoef, "bcoef")
+    if out is None:
+        out = th.empty((B, HW, N), device=A.device, dtype=th.float32)
+    po, ldo = _rows(out, "out")
+    ctx.check(ctx.lib.cgd_op_gemm_gn_bwd(ctx.h, pa, lda, pw, ldw, po, ldo, px, ldx, pdz, lddz, padd, ldadd, pc, pbc, B, HW, N, K, _s()))
+    return out
+
+
 def pack_conv3x3_frag(ctx, w, dgrad=False):
     """torch conv weight [Co][Ci][3][3] (on the GPU) -> MFMA-fragment-order bf16 hi/lo planes for the halo conv kernel."""
     co, ci = w.shape[:2]

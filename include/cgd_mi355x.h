@@ -522,6 +522,16 @@ int cgd_ddim_reverse_update(cgd_ctx* ctx, const float* x, const float* model_out
  * CGD_KGEMM policy knobs.  splitk: >= 1 slices (1 = automatic), -1 = one slice, never split automatically. */
 int cgd_op_gemm(cgd_ctx* ctx, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias, const float* R,
                 int ldr, int M, int N, int K, float alpha, int force_tile, int splitk, void* stream);
+/* dx[M][N] = A[M][K] W[N][K]^T (+ add[M][N]) + the backward of a GroupNorm + SiLU over the same M = B * HW rows: dz silu'(x a + b) A1 - (x - mean) A2 - A3
+ * per element, coef = [B][N][4] {a, b, unused, mean}, bcoef = [B][N][4] {A1, A2, A3, unused} (what cgd_op_gn_bwd computes internally).  One launch of
+ * the weight GEMM kernel (W re-packed per call) whose epilogue applies the norm: a ResBlock's 1x1 skip dgrad and GN1's backward.  bf16x3 contexts only;
+ * K % 64 == 0, N % 32 == 0, every row stride a multiple of 4, operands 16-byte aligned, HW % 128 == 0 or B == 1: anything else is an error. */
+int cgd_op_gemm_gn_bwd(cgd_ctx* ctx, const float* A, int lda, const float* W, int ldw, float* dx, int lddx, const float* x, int ldx,
+                       const float* dz, int lddz, const float* add, int ldadd, const float* coef, const float* bcoef, int B, int HW, int N, int K,
+                       void* stream);
+/* host-only (no GPU, no context): 1 if cgd_op_gemm_gn_bwd runs a problem with these strides on a context of this precision mode, 0 if it returns an
+ * error (the same predicate).  x_misalign: byte offset of x from a 16-byte boundary; ldadd = 0: no `add` operand. */
+int cgd_op_gemm_gn_bwd_accepts(int precision, int lda, int ldw, int lddx, int ldx, int lddz, int ldadd, int x_misalign, int B, int HW, int N, int K);
 /* w_packed: [Cout][9*Cin] fp32 (generic kernel); w_frag (optional): the same weights in MFMA-fragment order, bf16 hi/lo planes,
  * produced by cgd_op_pack_conv3x3_frag from the torch layout [Co][Ci][3][3] (dgrad=1: rotated/transposed) — enables the
  * halo-staged kernel (force_tile 512 or automatic for large images) */

@@ -1,8 +1,8 @@
 """Cost of `use_augs=True` per guided step at the headline shape (bench.py config 2: 256x256, cutn 16, CLIP ViT-B/32, batch 1,
 respace 250, p_sample, synthetic weights), in one process with one seed:
 
-  augs-native  ClipGuidance._clip_leg_with_augs (the cutaug kernels)
-  augs-torch   the same leg through _clip_leg_with_augs_torch (crop / augment / pool in torch ops with autograd)
+  augs-native  ClipGuidance._clip_leg with use_augs cutouts (the cutaug kernels)
+  augs-torch   the same leg through _clip_leg_torch (crop / augment / pool in torch ops with autograd)
   augs-off     the plain guided step (the floor)
 
 The three modes alternate in rounds of --steps timed steps (after --warmup steps each), wall clock around work that ends in a device
@@ -46,9 +46,9 @@ def main():
     def set_mode(mode):
         guid.make_cutouts = plain_mk if mode == "augs-off" else aug_mk
         if mode == "augs-torch":
-            guid._clip_leg_with_augs = guid._clip_leg_with_augs_torch
+            guid._clip_leg = guid._clip_leg_torch
         else:
-            guid.__dict__.pop("_clip_leg_with_augs", None)
+            guid.__dict__.pop("_clip_leg", None)
 
     modes = ["augs-native", "augs-torch", "augs-off"]
     th.manual_seed(1000)

@@ -1,7 +1,7 @@
 """Cost of the resized cutouts (`cuts=4:12`) per guided step at the headline shape (bench.py config 2: 256x256, CLIP ViT-B/32, batch 1,
 respace 250, p_sample, synthetic weights), in one process with one seed:
 
-  resized   ClipGuidance._clip_leg_resized with MakeCutoutsResized(224, overview=4, inner=12) (the cutresize kernels), 16 cuts
+  resized   ClipGuidance._clip_leg with MakeCutoutsResized(224, overview=4, inner=12) (the cutresize kernels), 16 cuts
   pooled    the plain guided step with 16 pooled cutouts (the default path, unchanged)
 
 The two modes alternate in rounds of --steps timed steps (after --warmup steps each), wall clock around work that ends in a device

@@ -12,6 +12,8 @@ perspective / grayscale / additive noise) inside the cutaug HIP kernels, whose a
 are drawn like reference_augs draws them (draw_aug_params), the noise on the device generator in its randn_like order.
 `MakeCutoutsResized` is a second cutter: overview + inner cuts through an antialiased cubic resize (the cutresize HIP kernels).
 With `direction_embeds` the CLIP leg also scores the directional loss of prompt-pair edits against a source image (the direction HIP kernel).
+Every cutter reaches the kernels through one per-step launch object (_CutLaunch, _AugLaunch: forward, backward, and torch_cuts, the same
+cutouts in torch ops), so there is one CLIP leg (ClipGuidance._clip_leg) and one torch restatement of it (_clip_leg_torch) for all of them.
 """
 import math
 
@@ -173,6 +175,14 @@ def reference_augs(x):
     return noise(x)
 
 
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def _clip_mean_std(dev):
+    return [th.tensor(c, device=dev).view(1, 3, 1, 1) for c in (CLIP_MEAN, CLIP_STD)]
+
+
 AUG_GROUP_FLOATS = 1 << 25  # cutouts per launch group of the native `use_augs` path: noise + adjoint scratch of a group <= 128 MiB
 
 
@@ -193,6 +203,7 @@ class _AugLaunch:
     def __init__(self, lib, coords, B, H, W, dev):
         self.lib, self.B, self.H, self.W = lib, B, H, W
         self.geo_list = crop_geometry(coords, H, W)
+        self.n = len(self.geo_list)
         recs = [draw_aug_params(h, w).record() for (_, _, h, w) in self.geo_list]
         self.geo = _upload(th.tensor(self.geo_list, dtype=th.int32).view(-1, 4), dev)
         self.params = _upload(th.tensor(recs, dtype=th.float32).view(-1, 16), dev)
@@ -244,6 +255,99 @@ class _AugLaunch:
                                                    int(bool(accumulate) or k0 > 0), ctx.stream()))
 
 
+class _AugCuts:
+    """The `use_augs` cutter of one step as the CLIP leg takes it: every tower gets an _AugLaunch of its own, and so parameter draws of
+    its own, made right before its forward launch."""
+
+    def __init__(self, lib, coords, B, H, W, dev):
+        self.coords, self.args = coords, (lib, coords, B, H, W, dev)
+
+    def per_tower(self):
+        return _AugLaunch(*self.args)
+
+    def torch_cuts(self, img01, cs):
+        """The cutouts of img01 (B,3,H,W in [0,1]) at cut size cs in torch ops (fresh draws, in _AugLaunch's order), not normalised."""
+        return MakeCutouts(cs, len(self.coords), use_augs=True).augmented(img01, self.coords)
+
+
+class _CutLaunch:
+    """The plain cutter (crop + adaptive average pool, cgd_cutouts_*) or the resized one (cgd_cutouts_resize_*) on one step's uploaded
+    table `geo`, with _AugLaunch's two methods: crop_geometry rows of the (ox, oy, size) `coords`, or the resize_table of the
+    (ox, oy, w, h, flags) records (boxes, then flags).  `scratch`: the resized adjoint's buffer (allocated at the first backward if None)."""
+
+    def __init__(self, lib, coords, geo, resized=False, scratch=None):
+        self.lib, self.coords, self.geo, self.n, self.resized, self.scratch = lib, coords, geo, len(coords), resized, scratch
+        self.flags_p = geo.data_ptr() + 16 * self.n if resized else None
+
+    def per_tower(self):
+        return self
+
+    def forward(self, ctx, x_pm1, out, cs, layout, patch):
+        """out rows (cut*B + b) of the cutouts of x_pm1 (any B,3,H,W in [-1,1]), layout 0 or 1, CLIP-normalised."""
+        B, _, H, W = x_pm1.shape
+        if self.resized:
+            ctx.check(self.lib.cgd_cutouts_resize_fwd(ctx.h, x_pm1.data_ptr(), self.geo.data_ptr(), self.flags_p, out.data_ptr(), B, H, W,
+                                                      self.n, cs, layout, patch, ctx.stream()))
+        else:
+            ctx.check(self.lib.cgd_cutouts_fwd(ctx.h, x_pm1.data_ptr(), self.geo.data_ptr(), out.data_ptr(), B, H, W, self.n, cs, layout, patch,
+                                               ctx.stream()))
+
+    def backward(self, ctx, d_out, g, cs, layout, patch, accumulate):
+        """g (B,3,H,W) (+)= d/dx_pm1 of <forward(x_pm1), d_out>."""
+        B, _, H, W = g.shape
+        if not self.resized:
+            ctx.check(self.lib.cgd_cutouts_bwd(ctx.h, d_out.data_ptr(), self.geo.data_ptr(), g.data_ptr(), B, H, W, self.n, cs, layout, patch,
+                                               int(accumulate), ctx.stream()))
+            return
+        if self.scratch is None:
+            self.scratch = th.empty(max(1, self.lib.cgd_cutouts_resize_scratch_floats(B, H, W, self.n)), device=g.device)
+        ctx.check(self.lib.cgd_cutouts_resize_bwd(ctx.h, d_out.data_ptr(), self.geo.data_ptr(), self.flags_p, g.data_ptr(), self.scratch.data_ptr(),
+                                                  B, H, W, self.n, cs, layout, patch, int(accumulate), ctx.stream()))
+
+    def torch_cuts(self, img01, cs):
+        """The cutouts of img01 (any B,3,H,W in [0,1]) at cut size cs in torch ops with autograd, not normalised."""
+        if self.resized:
+            return MakeCutoutsResized(cs).resized(img01, self.coords)
+        return th.cat([F.adaptive_avg_pool2d(img01[:, :, oy:oy + size, ox:ox + size], cs) for ox, oy, size in self.coords])
+
+
+def _cutouts(mk, input, launch):
+    """The cutouts of `input` (B,3,H,W in [0,1]) of the cutter module `mk` through `launch` (_CutLaunch or _AugLaunch), NCHW and not
+    normalised; an autograd node over launch.backward when `input` requires grad."""
+    if input.requires_grad and th.is_grad_enabled():
+        return _CutoutsFunction.apply(input, mk.ctx, launch, mk.cut_size)
+    return _cut_pool(input, mk.ctx, launch, mk.cut_size)
+
+
+def _cut_pool(input, ctx, launch, cs):
+    # the kernels cut (x+1)/2 and apply the CLIP normalisation; undo both to return the raw cutouts
+    x_pm1 = (input.detach().float() * 2 - 1).contiguous()
+    out = th.empty((launch.n * input.shape[0], 3, cs, cs), device=input.device, dtype=th.float32)
+    launch.forward(ctx, x_pm1, out, cs, 0, 0)
+    mean, std = _clip_mean_std(input.device)
+    return out * std + mean
+
+
+class _CutoutsFunction(th.autograd.Function):
+    """_cut_pool as an autograd node (user-supplied cond_fns that follow the reference recipe, cgd.py:190-194); its backward is the
+    launch's adjoint kernel."""
+
+    @staticmethod
+    def forward(ctx, input, lctx, launch, cs):
+        ctx.args, ctx.in_shape = (lctx, launch, cs), tuple(input.shape)
+        return _cut_pool(input, lctx, launch, cs)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        lctx, launch, cs = ctx.args
+        # the adjoint kernels return d/dx of their own convention, out = (cut((x+1)/2) - mean) / std: feed them d_out * std and double the
+        # result to get the adjoint of the plain cutouts
+        d = (d_out.float() * th.tensor(CLIP_STD, device=d_out.device).view(1, 3, 1, 1)).contiguous()
+        g = th.empty(ctx.in_shape, device=d_out.device, dtype=th.float32)
+        launch.backward(lctx, d, g, cs, 0, 0, accumulate=False)
+        return g * 2, None, None, None
+
+
 class MakeCutouts(th.nn.Module):
     """Drop-in for cgd.modules.MakeCutouts (modules.py:5-66): same constructor, forward(input, use_cache,
     num_cutouts_override) and cache_coordinates(side_x, side_y); the crop+pool runs in one HIP kernel.
@@ -280,14 +384,9 @@ class MakeCutouts(th.nn.Module):
         if self.ctx is None:
             self.ctx = L.Context(input.device.index or 0)
         if self.augs is not None:
-            aug = _AugLaunch(self.ctx.lib, coords, input.shape[0], H, W, input.device)
-            if input.requires_grad and th.is_grad_enabled():
-                return _AugCutoutsFunction.apply(input, self, aug)
-            return self._aug_pool(input, aug)
+            return _cutouts(self, input, _AugLaunch(self.ctx.lib, coords, input.shape[0], H, W, input.device))
         geo = th.tensor(crop_geometry(coords, H, W), dtype=th.int32, device=input.device)
-        if input.requires_grad and th.is_grad_enabled():
-            return _CutoutsFunction.apply(input, self, geo, len(coords))
-        return self._pool(input, geo, len(coords))
+        return _cutouts(self, input, _CutLaunch(self.ctx.lib, coords, geo))
 
     def augmented(self, input, coords):
         """crop -> augment -> adaptive average pool -> cat, as modules.py:58-66 does with `self.augs` set: torch ops with autograd."""
@@ -296,69 +395,6 @@ class MakeCutouts(th.nn.Module):
             cut = self.augs(input[:, :, oy:oy + size, ox:ox + size])
             outs.append(F.adaptive_avg_pool2d(cut, self.cut_size))
         return th.cat(outs)
-
-    def _pool(self, input, geo, ncut):
-        B, _, H, W = input.shape
-        # the kernel pools (x+1)/2 and applies the CLIP normalisation; undo both to return the raw pooled crop
-        x_pm1 = (input.detach().float() * 2 - 1).contiguous()
-        out = th.empty((ncut * B, 3, self.cut_size, self.cut_size), device=input.device, dtype=th.float32)
-        self.ctx.check(self.ctx.lib.cgd_cutouts_fwd(self.ctx.h, x_pm1.data_ptr(), geo.data_ptr(), out.data_ptr(), B, H, W, ncut,
-                                                    self.cut_size, 0, 0, self.ctx.stream()))
-        mean = th.tensor(CLIP_MEAN, device=input.device).view(1, 3, 1, 1)
-        std = th.tensor(CLIP_STD, device=input.device).view(1, 3, 1, 1)
-        return out * std + mean
-
-
-    def _aug_pool(self, input, aug):
-        """The augmented cutouts of `input` (B,3,H,W in [0,1]) through cgd_cutouts_aug_fwd, not normalised (like _pool)."""
-        B = input.shape[0]
-        x_pm1 = (input.detach().float() * 2 - 1).contiguous()
-        out = th.empty((len(aug.geo_list) * B, 3, self.cut_size, self.cut_size), device=input.device, dtype=th.float32)
-        aug.forward(self.ctx, x_pm1, out, self.cut_size, 0, 0)
-        mean = th.tensor(CLIP_MEAN, device=input.device).view(1, 3, 1, 1)
-        std = th.tensor(CLIP_STD, device=input.device).view(1, 3, 1, 1)
-        return out * std + mean
-
-
-class _AugCutoutsFunction(th.autograd.Function):
-    """MakeCutouts(use_augs=True).forward on a GPU input as an autograd node; its backward is cgd_cutouts_aug_bwd."""
-
-    @staticmethod
-    def forward(ctx, input, mk, aug):
-        ctx.mk, ctx.aug, ctx.in_shape = mk, aug, tuple(input.shape)
-        return mk._aug_pool(input, aug)
-
-    @staticmethod
-    def backward(ctx, d_out):
-        mk = ctx.mk
-        # as in _CutoutsFunction: the kernel's convention is out = (pool(aug((x+1)/2)) - mean) / std
-        std = th.tensor(CLIP_STD, device=d_out.device).view(1, 3, 1, 1)
-        d = (d_out.float() * std).contiguous()
-        g = th.empty(ctx.in_shape, device=d_out.device, dtype=th.float32)
-        ctx.aug.backward(mk.ctx, d, g, mk.cut_size, 0, 0, accumulate=False)
-        return g * 2, None, None
-
-
-class _CutoutsFunction(th.autograd.Function):
-    """MakeCutouts.forward as an autograd node (user-supplied cond_fns that follow the reference recipe, cgd.py:190-194)."""
-
-    @staticmethod
-    def forward(ctx, input, mk, geo, ncut):
-        ctx.mk, ctx.geo, ctx.ncut, ctx.in_shape = mk, geo, ncut, tuple(input.shape)
-        return mk._pool(input, geo, ncut)
-
-    @staticmethod
-    def backward(ctx, d_out):
-        mk = ctx.mk
-        B, _, H, W = ctx.in_shape
-        # cgd_cutouts_bwd returns d/dx of the kernel's own convention, out = (pool((x+1)/2) - mean) / std: feed it d_out * std and
-        # double the result to get the adjoint of the plain crop + adaptive average pool
-        std = th.tensor(CLIP_STD, device=d_out.device).view(1, 3, 1, 1)
-        d = (d_out.float() * std).contiguous()
-        g = th.empty(ctx.in_shape, device=d_out.device, dtype=th.float32)
-        mk.ctx.check(mk.ctx.lib.cgd_cutouts_bwd(mk.ctx.h, d.data_ptr(), ctx.geo.data_ptr(), g.data_ptr(), B, H, W, ctx.ncut, mk.cut_size,
-                                                0, 0, 0, mk.ctx.stream()))
-        return g * 2, None, None, None
 
 
 RESIZE_GRAY, RESIZE_FLIP = 1, 2  # flag bits of a resized cutout: grayscale before the resize, horizontal flip after it
@@ -485,9 +521,7 @@ class MakeCutoutsResized(th.nn.Module):
         if self.ctx is None:
             self.ctx = L.Context(input.device.index or 0)
         table = th.tensor(resize_table(recs, H, W), dtype=th.int32, device=input.device)
-        if input.requires_grad and th.is_grad_enabled():
-            return _ResizedCutoutsFunction.apply(input, self, table, len(recs))
-        return self._resize(input, table, len(recs))
+        return _cutouts(self, input, _CutLaunch(self.ctx.lib, recs, table, resized=True))
 
     def resized(self, input, records, cut_size=None):
         """crop -> (grayscale) -> Wy crop Wx^T -> (flip) -> cat: the torch restatement, with autograd."""
@@ -500,44 +534,6 @@ class MakeCutoutsResized(th.nn.Module):
             r = resize_matrix(h, cs, input.dtype, input.device) @ z @ resize_matrix(w, cs, input.dtype, input.device).t()
             outs.append(r.flip(-1) if fl & RESIZE_FLIP else r)
         return th.cat(outs)
-
-    def _resize(self, input, table, ncut):
-        B, _, H, W = input.shape
-        # the kernel resizes (x+1)/2 and applies the CLIP normalisation; undo the latter to return the raw resized crop
-        x_pm1 = (input.detach().float() * 2 - 1).contiguous()
-        out = th.empty((ncut * B, 3, self.cut_size, self.cut_size), device=input.device, dtype=th.float32)
-        self.ctx.check(self.ctx.lib.cgd_cutouts_resize_fwd(self.ctx.h, x_pm1.data_ptr(), table.data_ptr(), table.data_ptr() + 16 * ncut,
-                                                           out.data_ptr(), B, H, W, ncut, self.cut_size, 0, 0, self.ctx.stream()))
-        mean = th.tensor(CLIP_MEAN, device=input.device).view(1, 3, 1, 1)
-        std = th.tensor(CLIP_STD, device=input.device).view(1, 3, 1, 1)
-        return out * std + mean
-
-
-class _ResizedCutoutsFunction(th.autograd.Function):
-    """MakeCutoutsResized.forward on a GPU input as an autograd node; its backward is cgd_cutouts_resize_bwd."""
-
-    @staticmethod
-    def forward(ctx, input, mk, table, ncut):
-        ctx.mk, ctx.table, ctx.ncut, ctx.in_shape = mk, table, ncut, tuple(input.shape)
-        return mk._resize(input, table, ncut)
-
-    @staticmethod
-    def backward(ctx, d_out):
-        mk = ctx.mk
-        B, _, H, W = ctx.in_shape
-        # as in _CutoutsFunction: the kernel's convention is out = (resize((x+1)/2) - mean) / std
-        std = th.tensor(CLIP_STD, device=d_out.device).view(1, 3, 1, 1)
-        d = (d_out.float() * std).contiguous()
-        g = th.empty(ctx.in_shape, device=d_out.device, dtype=th.float32)
-        lib = mk.ctx.lib
-        scratch = th.empty(max(1, lib.cgd_cutouts_resize_scratch_floats(B, H, W, ctx.ncut)), device=d_out.device)
-        mk.ctx.check(lib.cgd_cutouts_resize_bwd(mk.ctx.h, d.data_ptr(), ctx.table.data_ptr(), ctx.table.data_ptr() + 16 * ctx.ncut,
-                                                g.data_ptr(), scratch.data_ptr(), B, H, W, ctx.ncut, mk.cut_size, 0, 0, 0, mk.ctx.stream()))
-        return g * 2, None, None, None
-
-
-CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
-CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
 def prompt_weight_matrix(weights, batch, device):
@@ -763,33 +759,14 @@ class ClipGuidance:
             acc = 1
         clip_part = self._b("clip_part", (len(self.towers) * N * self._clip_kinds(),), dev)
         self.clip_part = clip_part
-        if self.dirs_list is not None:
-            self._clip_leg_direction(x_in, geo, coords, wm, self._wmd[B], gclip, clip_part, acc)
-        elif resized:
-            self._clip_leg_resized(x_in, geo, cutn, wm, gclip, clip_part, acc)
+        if resized:
+            scratch = self._b("resize_scratch", (max(1, lib.cgd_cutouts_resize_scratch_floats(B, H, W, cutn)),), dev)  # one query per step
+            cuts = _CutLaunch(lib, coords, geo, True, scratch)
         elif self.make_cutouts.augs is not None:
-            self._clip_leg_with_augs(x_in, coords, wm, gclip, clip_part, acc)
-        for k, (tower, targets) in enumerate(zip(self.towers, self.targets_list)):
-            if resized or self.make_cutouts.augs is not None or self.dirs_list is not None:
-                break
-            cs, patch = tower.input_resolution, tower.patch
-            if patch:  # ViT towers: the cutout kernel writes the patch rows of the patch-embedding GEMM directly (layout 1)
-                gsz = cs // patch
-                clip_in = self._b(f"patches{k}", (N * gsz * gsz, 3 * patch * patch), dev)
-                layout = 1
-            else:      # ModifiedResNet towers: plain (N,3,cs,cs) images (layout 0)
-                clip_in = self._b(f"cut_images{k}", (N, 3, cs, cs), dev)
-                layout = 0
-            ctx.check(lib.cgd_cutouts_fwd(ctx.h, x_in.data_ptr(), geo.data_ptr(), clip_in.data_ptr(), B, H, W, cutn, cs, layout, patch, s))
-            emb = tower.encode_image(clip_in, layout=layout, n=N, out=self._b(f"emb{k}", (N, tower.out_dim), dev))
-            demb = self._b(f"demb{k}", (N, tower.out_dim), dev)
-            ctx.check(lib.cgd_spherical_loss(ctx.h, emb.data_ptr(), targets.data_ptr(), wm.data_ptr(), demb.data_ptr(),
-                                             clip_part[k * N:].data_ptr(), cutn, B, targets.shape[0], tower.out_dim, self.cgs, s))
-            dclip_in = tower.dgrad(demb, self._b(f"dclip_in{k}", tuple(clip_in.shape), dev))
-            ctx.check(lib.cgd_cutouts_bwd(ctx.h, dclip_in.data_ptr(), geo.data_ptr(), gclip.data_ptr(), B, H, W, cutn, cs, layout, patch, acc, s))
-            acc = 1
-            if k == 0:
-                self.emb = emb
+            cuts = _AugCuts(lib, coords, B, H, W, dev)
+        else:
+            cuts = _CutLaunch(lib, coords, geo)
+        self._clip_leg(x_in, cuts, wm, self._wmd.get(B), gclip, clip_part, acc)
         nblk = lib.cgd_guidance_part_blocks(B, H, W)
         # the saturation term is a mean over the WHOLE batch (cgd.py:214-218): a rank that holds B of the run's shard[1] samples scales
         # it so that its per-sample gradient equals the batched run's (the logged value is then this rank's share of the loss)
@@ -871,113 +848,108 @@ class ClipGuidance:
         self._buf["_direction_src"] = ((dev, B, H, W), src)
         return src
 
-    def _clip_leg_direction(self, x_in, geo, coords, wm, wmd, gclip, clip_part, accumulate):
-        """The CLIP leg with direction prompts, for the plain and the resized cutter.  Per tower, in tower order, on this step's uploaded boxes
-        (and flags): cutouts of the source image -> tower forward (into buffers of their own: the tower keeps its last input for dgrad, and
-        dgrad differentiates the LAST forward, so the source goes first) -> cutouts of x_in -> tower forward -> spherical loss (only with
-        target prompts) -> directional loss (accumulating onto the spherical gradient when that ran) -> tower dgrad -> the cutouts' adjoint
-        into gclip.  Partials: per tower the spherical rows (if any), then the directional rows.  With cached_cutouts the boxes do not
-        change, and the source embeddings of a cut count are computed once.  _clip_leg_direction_torch is the same leg with autograd."""
+    # -- the CLIP leg ------------------------------------------------------------------------------------
+    def _clip_in(self, name, k, tower, n, dev):
+        """(buffer, layout) of n cutouts for tower k: the cutout kernels write the patch rows of a ViT tower's patch-embedding GEMM directly
+        (layout 1), plain (n,3,cs,cs) images for a ModifiedResNet tower (layout 0)."""
+        cs, patch = tower.input_resolution, tower.patch
+        if patch:
+            gsz = cs // patch
+            return self._b(f"{name}patches{k}", (n * gsz * gsz, 3 * patch * patch), dev), 1
+        return self._b(f"{name}cut_images{k}", (n, 3, cs, cs), dev), 0
+
+    def _clip_leg(self, x_in, cuts, wm, wmd, gclip, clip_part, accumulate):
+        """d(CLIP loss)/dx_in into gclip for every cutter.  `cuts`: this step's _CutLaunch (plain or resized) or _AugCuts.  Per tower, in tower
+        order, on the same boxes at the tower's own cut size: cutouts of x_in -> tower forward -> spherical loss (mean over this step's
+        cuts, per-row partials into clip_part) -> tower dgrad -> the cutouts' adjoint into gclip (the first tower overwrites unless
+        `accumulate`).  With direction prompts the cutouts and the forward of the source image go first, into buffers of their own (the
+        tower keeps its last input for dgrad, and dgrad differentiates the LAST forward), the spherical launch is made only with target
+        prompts, and the directional loss follows it, accumulating onto the spherical gradient when that ran; partials: per tower the
+        spherical rows (if any), then the directional rows.  With cached_cutouts the boxes do not change, and the source embeddings of
+        a cut count are computed once.  _clip_leg_torch is the same leg with autograd."""
         ctx, lib = self.ctx, self.ctx.lib
         B, _, H, W = x_in.shape
         dev = x_in.device
         s = ctx.stream()
-        resized = isinstance(self.make_cutouts, MakeCutoutsResized)
-        cutn = len(coords)
+        cutn = len(cuts.coords)
         N = cutn * B
-        src = self._direction_source_on(dev, B, H, W)
-        Bs = src.shape[0]
-        kinds, has_t = self._clip_kinds(), int(self.targets_list[0].shape[0] > 0)
-        if resized:
-            flags_p = geo.data_ptr() + 16 * cutn
-            scratch = self._b("resize_scratch", (max(1, lib.cgd_cutouts_resize_scratch_floats(B, H, W, cutn)),), dev)
-
-        def cut_fwd(img, nb, out, cs, layout, patch):
-            if resized:
-                ctx.check(lib.cgd_cutouts_resize_fwd(ctx.h, img.data_ptr(), geo.data_ptr(), flags_p, out.data_ptr(), nb, H, W, cutn, cs, layout, patch, s))
-            else:
-                ctx.check(lib.cgd_cutouts_fwd(ctx.h, img.data_ptr(), geo.data_ptr(), out.data_ptr(), nb, H, W, cutn, cs, layout, patch, s))
-
-        boxes = [tuple(c) for c in coords]
-        hit = self._src_emb.get((cutn, B)) if self.cached_cutouts else None
-        src_embs = hit[1] if hit is not None and hit[0] == boxes else None
-        fresh = []
+        dirs_list = self.dirs_list
+        if dirs_list is not None:
+            src = self._direction_source_on(dev, B, H, W)
+            Bs = src.shape[0]
+            boxes = [tuple(c) for c in cuts.coords]
+            hit = self._src_emb.get((cutn, B)) if self.cached_cutouts else None
+            src_embs = hit[1] if hit is not None and hit[0] == boxes else None
+            fresh = []
+        kinds = self._clip_kinds()
         acc = accumulate
-        for k, (tower, targets, dirs) in enumerate(zip(self.towers, self.targets_list, self.dirs_list)):
+        for k, (tower, targets) in enumerate(zip(self.towers, self.targets_list)):
+            cut = cuts.per_tower()
             cs, patch = tower.input_resolution, tower.patch
-            layout = 1 if patch else 0
-            gsz = cs // patch if patch else 0
-            shape = (lambda n: (n * gsz * gsz, 3 * patch * patch)) if patch else (lambda n: (n, 3, cs, cs))
-            kind = "patches" if patch else "cut_images"
-            if src_embs is None:
-                src_in = self._b(f"src_{kind}{k}", shape(cutn * Bs), dev)
-                cut_fwd(src, Bs, src_in, cs, layout, patch)
+            if dirs_list is not None and src_embs is None:
+                src_in, layout = self._clip_in("src_", k, tower, cutn * Bs, dev)
+                cut.forward(ctx, src, src_in, cs, layout, patch)
                 name = f"src_emb{k}_{cutn}" if self.cached_cutouts else f"src_emb{k}"
-                semb = tower.encode_image(src_in, layout=layout, n=cutn * Bs, out=self._b(name, (cutn * Bs, tower.out_dim), dev))
-                fresh.append(semb)
-            else:
-                semb = src_embs[k]
-            clip_in = self._b(f"{kind}{k}", shape(N), dev)
-            cut_fwd(x_in, B, clip_in, cs, layout, patch)
+                fresh.append(tower.encode_image(src_in, layout=layout, n=cutn * Bs, out=self._b(name, (cutn * Bs, tower.out_dim), dev)))
+            clip_in, layout = self._clip_in("", k, tower, N, dev)
+            cut.forward(ctx, x_in, clip_in, cs, layout, patch)
             emb = tower.encode_image(clip_in, layout=layout, n=N, out=self._b(f"emb{k}", (N, tower.out_dim), dev))
             demb = self._b(f"demb{k}", (N, tower.out_dim), dev)
-            base = k * N * kinds
+            part = clip_part[k * N * kinds:]
+            has_t = int(dirs_list is None or targets.shape[0] > 0)
             if has_t:
-                ctx.check(lib.cgd_spherical_loss(ctx.h, emb.data_ptr(), targets.data_ptr(), wm.data_ptr(), demb.data_ptr(),
-                                                 clip_part[base:].data_ptr(), cutn, B, targets.shape[0], tower.out_dim, self.cgs, s))
-            ctx.check(lib.cgd_directional_loss(ctx.h, emb.data_ptr(), semb.data_ptr(), dirs.data_ptr(), wmd.data_ptr(), demb.data_ptr(),
-                                               clip_part[base + N * has_t:].data_ptr(), cutn, B, Bs, dirs.shape[0], tower.out_dim, self.cgs,
-                                               has_t, s))
+                ctx.check(lib.cgd_spherical_loss(ctx.h, emb.data_ptr(), targets.data_ptr(), wm.data_ptr(), demb.data_ptr(), part.data_ptr(),
+                                                 cutn, B, targets.shape[0], tower.out_dim, self.cgs, s))
+            if dirs_list is not None:
+                semb, dirs = (fresh if src_embs is None else src_embs)[k], dirs_list[k]
+                ctx.check(lib.cgd_directional_loss(ctx.h, emb.data_ptr(), semb.data_ptr(), dirs.data_ptr(), wmd.data_ptr(), demb.data_ptr(),
+                                                   part[N * has_t:].data_ptr(), cutn, B, Bs, dirs.shape[0], tower.out_dim, self.cgs, has_t, s))
             dclip_in = tower.dgrad(demb, self._b(f"dclip_in{k}", tuple(clip_in.shape), dev))
-            if resized:
-                ctx.check(lib.cgd_cutouts_resize_bwd(ctx.h, dclip_in.data_ptr(), geo.data_ptr(), flags_p, gclip.data_ptr(), scratch.data_ptr(),
-                                                     B, H, W, cutn, cs, layout, patch, acc, s))
-            else:
-                ctx.check(lib.cgd_cutouts_bwd(ctx.h, dclip_in.data_ptr(), geo.data_ptr(), gclip.data_ptr(), B, H, W, cutn, cs, layout, patch, acc, s))
+            cut.backward(ctx, dclip_in, gclip, cs, layout, patch, acc)
             acc = 1
             if k == 0:
                 self.emb = emb
-        if self.cached_cutouts and src_embs is None:
+        if dirs_list is not None and self.cached_cutouts and src_embs is None:
             self._src_emb[(cutn, B)] = (boxes, fresh)
 
-    def _clip_leg_direction_torch(self, x_in, geo, coords, wm, wmd, gclip, clip_part, accumulate):
-        """The torch restatement of _clip_leg_direction (the equivalence reference of the tests): crop / pool or resize / normalise in torch,
-        the CLIP tower as the autograd node over cgd_*_forward / _dgrad, both losses in torch ops.  The source forward runs first here too."""
+    def _clip_leg_torch(self, x_in, cuts, wm, wmd, gclip, clip_part, accumulate):
+        """The torch restatement of _clip_leg (the equivalence reference of the tests; swap it in with `guid._clip_leg = guid._clip_leg_torch`):
+        it follows the reference recipe (cgd.py:190-204) with torch autograd — the cutouts (cuts.torch_cuts) and the normalisation in torch
+        ops, the CLIP tower as the autograd node over cgd_*_forward / _dgrad, both losses in torch ops — and hands d(CLIP loss)/dx_in to
+        the native chain.  Same draws, in the same order, as the native leg; the source forward runs first here too.  clip_part gets
+        each tower's spherical total in the first of its spherical rows and its directional total in the first of its directional rows."""
         from .nets import EncodeImageFunction
         B, _, H, W = x_in.shape
         dev = x_in.device
-        mean = th.tensor(CLIP_MEAN, device=dev).view(1, 3, 1, 1)
-        std = th.tensor(CLIP_STD, device=dev).view(1, 3, 1, 1)
-        resized = isinstance(self.make_cutouts, MakeCutoutsResized)
-        n = len(coords)
+        mean, std = _clip_mean_std(dev)
+        n = len(cuts.coords)
         N = n * B
-        src = self._direction_source_on(dev, B, H, W)
-        kinds, has_t = self._clip_kinds(), int(self.targets_list[0].shape[0] > 0)
+        kinds = self._clip_kinds()
+        if self.dirs_list is not None:
+            src = self._direction_source_on(dev, B, H, W)
 
-        def cuts(img, cs):
-            img = img.add(1).div(2)
-            if resized:
-                out = self.make_cutouts.resized(img, coords, cs)
-            else:
-                out = th.cat([F.adaptive_avg_pool2d(img[:, :, oy:oy + size, ox:ox + size], cs) for ox, oy, size in coords])
-            return ((out - mean) / std).contiguous()
+        def clip_cuts(img, cs):
+            return ((cuts.torch_cuts(img.add(1).div(2), cs) - mean) / std).contiguous()
 
         clip_part.zero_()
         with th.enable_grad():
             xr = x_in.detach().requires_grad_()
             total = 0
-            for k, (tower, targets, dirs) in enumerate(zip(self.towers, self.targets_list, self.dirs_list)):
-                with th.no_grad():
-                    sn = F.normalize(tower.encode_image(cuts(src, tower.input_resolution)).clone().view(n, src.shape[0], -1), dim=-1)
-                emb = EncodeImageFunction.apply(cuts(xr, tower.input_resolution), tower).view(n, B, -1)
+            for k, (tower, targets) in enumerate(zip(self.towers, self.targets_list)):
+                has_t = int(self.dirs_list is None or targets.shape[0] > 0)
+                if self.dirs_list is not None:
+                    with th.no_grad():
+                        sn = F.normalize(tower.encode_image(clip_cuts(src, tower.input_resolution)).clone().view(n, src.shape[0], -1), dim=-1)
+                emb = EncodeImageFunction.apply(clip_cuts(xr, tower.input_resolution), tower).view(n, B, -1)
                 en = F.normalize(emb, dim=-1)
-                delta = en - sn
-                live = delta.norm(dim=-1, keepdim=True) > 1e-6
-                safe = th.where(live, delta, th.ones_like(delta))
-                cos = th.where(live, (safe / safe.norm(dim=-1, keepdim=True)) @ dirs.t(), th.zeros((), device=dev))  # (n, B, P_d)
-                l_dir = ((1 - cos) * wmd.view(1, B, -1)).sum(2).mean(0).sum() * self.cgs
-                total = total + l_dir
-                clip_part[k * N * kinds + N * has_t] = l_dir.detach()
+                if self.dirs_list is not None:
+                    delta = en - sn
+                    live = delta.norm(dim=-1, keepdim=True) > 1e-6
+                    safe = th.where(live, delta, th.ones_like(delta))
+                    cos = th.where(live, (safe / safe.norm(dim=-1, keepdim=True)) @ self.dirs_list[k].t(), th.zeros((), device=dev))  # (n, B, P_d)
+                    l_dir = ((1 - cos) * wmd.view(1, B, -1)).sum(2).mean(0).sum() * self.cgs
+                    total = total + l_dir
+                    clip_part[k * N * kinds + N * has_t] = l_dir.detach()
                 if has_t:
                     d = (en.unsqueeze(2) - targets.view(1, 1, -1, targets.shape[-1])).norm(dim=-1).div(2).arcsin().pow(2).mul(2)  # (n, B, P)
                     l_sph = (d * wm.view(1, B, -1)).sum(2).mean(0).sum() * self.cgs
@@ -990,128 +962,6 @@ class ClipGuidance:
             gclip.add_(g_in)
         else:
             gclip.copy_(g_in)
-
-    def _clip_leg_resized(self, x_in, table, cutn, wm, gclip, clip_part, accumulate):
-        """MakeCutoutsResized: per tower, in tower order, on the same boxes and flags (`table`: the uploaded resize_table) at the tower's
-        own cut size: resized cutouts (cgd_cutouts_resize_fwd, patch rows for ViT towers, images for ResNet towers) -> tower forward ->
-        spherical loss (mean over this step's cutn cuts, per-row partials into clip_part) -> tower dgrad -> the resize's gather-form
-        adjoint (cgd_cutouts_resize_bwd) into gclip.  _clip_leg_resized_torch is the same leg in torch ops with autograd."""
-        ctx, lib = self.ctx, self.ctx.lib
-        B, _, H, W = x_in.shape
-        dev = x_in.device
-        s = ctx.stream()
-        N = cutn * B
-        geo_p, flags_p = table.data_ptr(), table.data_ptr() + 16 * cutn
-        scratch = self._b("resize_scratch", (max(1, lib.cgd_cutouts_resize_scratch_floats(B, H, W, cutn)),), dev)
-        acc = accumulate
-        for k, (tower, targets) in enumerate(zip(self.towers, self.targets_list)):
-            cs, patch = tower.input_resolution, tower.patch
-            if patch:
-                gsz = cs // patch
-                clip_in = self._b(f"patches{k}", (N * gsz * gsz, 3 * patch * patch), dev)
-                layout = 1
-            else:
-                clip_in = self._b(f"cut_images{k}", (N, 3, cs, cs), dev)
-                layout = 0
-            ctx.check(lib.cgd_cutouts_resize_fwd(ctx.h, x_in.data_ptr(), geo_p, flags_p, clip_in.data_ptr(), B, H, W, cutn, cs, layout, patch, s))
-            emb = tower.encode_image(clip_in, layout=layout, n=N, out=self._b(f"emb{k}", (N, tower.out_dim), dev))
-            demb = self._b(f"demb{k}", (N, tower.out_dim), dev)
-            ctx.check(lib.cgd_spherical_loss(ctx.h, emb.data_ptr(), targets.data_ptr(), wm.data_ptr(), demb.data_ptr(),
-                                             clip_part[k * N:].data_ptr(), cutn, B, targets.shape[0], tower.out_dim, self.cgs, s))
-            dclip_in = tower.dgrad(demb, self._b(f"dclip_in{k}", tuple(clip_in.shape), dev))
-            ctx.check(lib.cgd_cutouts_resize_bwd(ctx.h, dclip_in.data_ptr(), geo_p, flags_p, gclip.data_ptr(), scratch.data_ptr(), B, H, W,
-                                                 cutn, cs, layout, patch, acc, s))
-            acc = 1
-            if k == 0:
-                self.emb = emb
-
-    def _clip_leg_resized_torch(self, x_in, records, wm, gclip, clip_part, accumulate):
-        """The torch restatement of _clip_leg_resized (the equivalence reference of the tests): crop / resize / normalise in torch
-        (MakeCutoutsResized.resized), the CLIP tower as the autograd node over cgd_*_forward / _dgrad."""
-        from .nets import EncodeImageFunction
-        B = x_in.shape[0]
-        mean = th.tensor(CLIP_MEAN, device=x_in.device).view(1, 3, 1, 1)
-        std = th.tensor(CLIP_STD, device=x_in.device).view(1, 3, 1, 1)
-        n = len(records)
-        with th.enable_grad():
-            xr = x_in.detach().requires_grad_()
-            total = 0
-            for tower, targets in zip(self.towers, self.targets_list):
-                cut = self.make_cutouts.resized(xr.add(1).div(2), records, tower.input_resolution)
-                emb = EncodeImageFunction.apply(((cut - mean) / std).contiguous(), tower).view(n, B, 1, -1)
-                en = F.normalize(emb, dim=-1)
-                d = (en - targets.view(1, 1, -1, targets.shape[-1])).norm(dim=-1).div(2).arcsin().pow(2).mul(2)  # (n, B, P)
-                total = total + (d * wm.view(1, B, -1)).sum(2).mean(0).sum() * self.cgs
-                if tower is self.towers[0]:
-                    self.emb = emb.detach().view(n * B, -1)
-            g_in, = th.autograd.grad(total, xr)
-        if accumulate:
-            gclip.add_(g_in)
-        else:
-            gclip.copy_(g_in)
-        clip_part.zero_()
-        clip_part[0] = total.detach()
-
-    def _clip_leg_with_augs(self, x_in, coords, wm, gclip, clip_part, accumulate):
-        """`use_augs=True`: the augmentations sit between the crop and the pool.  Per tower, in tower order, with fresh parameter
-        draws per tower: augmented cutouts (cgd_cutouts_aug_fwd, patch rows for ViT towers, images for ResNet towers) -> tower
-        forward -> spherical loss (per-row partials into clip_part) -> tower dgrad -> the augmented cutouts' gather-form adjoint
-        (cgd_cutouts_aug_bwd) into gclip.  _clip_leg_with_augs_torch is the same leg in torch ops with autograd."""
-        ctx, lib = self.ctx, self.ctx.lib
-        B, _, H, W = x_in.shape
-        dev = x_in.device
-        s = ctx.stream()
-        cutn = len(coords)
-        N = cutn * B
-        acc = accumulate
-        for k, (tower, targets) in enumerate(zip(self.towers, self.targets_list)):
-            aug = _AugLaunch(lib, coords, B, H, W, dev)
-            cs, patch = tower.input_resolution, tower.patch
-            if patch:
-                gsz = cs // patch
-                clip_in = self._b(f"patches{k}", (N * gsz * gsz, 3 * patch * patch), dev)
-                layout = 1
-            else:
-                clip_in = self._b(f"cut_images{k}", (N, 3, cs, cs), dev)
-                layout = 0
-            aug.forward(ctx, x_in, clip_in, cs, layout, patch)
-            emb = tower.encode_image(clip_in, layout=layout, n=N, out=self._b(f"emb{k}", (N, tower.out_dim), dev))
-            demb = self._b(f"demb{k}", (N, tower.out_dim), dev)
-            ctx.check(lib.cgd_spherical_loss(ctx.h, emb.data_ptr(), targets.data_ptr(), wm.data_ptr(), demb.data_ptr(),
-                                             clip_part[k * N:].data_ptr(), cutn, B, targets.shape[0], tower.out_dim, self.cgs, s))
-            dclip_in = tower.dgrad(demb, self._b(f"dclip_in{k}", tuple(clip_in.shape), dev))
-            aug.backward(ctx, dclip_in, gclip, cs, layout, patch, acc)
-            acc = 1
-            if k == 0:
-                self.emb = emb
-
-    def _clip_leg_with_augs_torch(self, x_in, coords, wm, gclip, clip_part, accumulate):
-        """The torch restatement of _clip_leg_with_augs (the equivalence reference of the tests): it follows the reference recipe
-        (cgd.py:190-204) with torch autograd — crop / augment / pool / normalise in torch, the CLIP tower as the autograd node over
-        cgd_*_forward / _dgrad — and hands d(CLIP loss)/d x_in to the native chain.  Same draws, in the same order, as the native leg."""
-        from .nets import EncodeImageFunction
-        B = x_in.shape[0]
-        mean = th.tensor(CLIP_MEAN, device=x_in.device).view(1, 3, 1, 1)
-        std = th.tensor(CLIP_STD, device=x_in.device).view(1, 3, 1, 1)
-        with th.enable_grad():
-            xr = x_in.detach().requires_grad_()
-            total = 0
-            for tower, targets in zip(self.towers, self.targets_list):
-                mk = MakeCutouts(tower.input_resolution, len(coords), self.make_cutouts.cut_pow, use_augs=True)
-                cut = mk.augmented(xr.add(1).div(2), coords)
-                emb = EncodeImageFunction.apply(((cut - mean) / std).contiguous(), tower).view(len(coords), B, 1, -1)
-                en = F.normalize(emb, dim=-1)
-                d = (en - targets.view(1, 1, -1, targets.shape[-1])).norm(dim=-1).div(2).arcsin().pow(2).mul(2)  # (cutn, B, P)
-                total = total + (d * wm.view(1, B, -1)).sum(2).mean(0).sum() * self.cgs
-                if tower is self.towers[0]:
-                    self.emb = emb.detach().view(len(coords) * B, -1)
-            g_in, = th.autograd.grad(total, xr)
-        if accumulate:
-            gclip.add_(g_in)
-        else:
-            gclip.copy_(g_in)
-        clip_part.zero_()
-        clip_part[0] = total.detach()
 
     def snapshot(self):
         """Asynchronous host copies of the last call's scalars: `log(snapshot)` later costs no wait on newer GPU work."""

@@ -322,13 +322,13 @@ class Scenario:
         if self.use_augs:
             dg.AUG_NOISE_STD = 0.0
             guid.make_cutouts = dg.MakeCutouts(self.res, self.cutn, use_augs=True, ctx=ctx)
-            plain_leg = guid._clip_leg_with_augs
+            plain_leg = guid._clip_leg
 
             def seeded_leg(*a, **k):
                 th.manual_seed(777 + guid.calls - 1)  # `calls` was incremented when the boxes of this call were taken
                 return plain_leg(*a, **k)
 
-            guid._clip_leg_with_augs = seeded_leg
+            guid._clip_leg = seeded_leg
         smp.tape = self.tape
         dmkw = {"y": th.zeros(B, dtype=th.long, device=DEV)} if self.kw.get("num_classes") else {}
         dloop = smp.ddim_sample_loop_progressive if self.ddim else smp.p_sample_loop_progressive

@@ -176,3 +176,69 @@ def test_perspective_draws_keep_the_vanishing_line_off_the_crop():
         m20, m21, m22 = d * hh - e * g, b * g - a * hh, a * e - b * d
         wz = [m20 * X + m21 * Y + m22 for X in (-1.5, w + 1.5) for Y in (-1.5, h + 1.5)]
         assert all(v > 0 for v in wz) or all(v < 0 for v in wz), (h, w, p.endpoints, wz)
+
+
+# ---- ClipGuidance with a recording library --------------------------------------------------------------------------------------
+@pytest.mark.parametrize("noise_std", [0.01, 0.0])
+def test_guidance_launch_order_with_use_augs_and_a_recording_library(monkeypatch, noise_std):
+    """The C-ABI calls of one guided step with use_augs cutouts on two towers: every tower draws its own parameters (six cutouts, in
+    tower order, right before its forward launch), the adjoint's scratch size is asked inside each tower's backward, the second tower
+    accumulates, and the noise and offset pointers are NULL exactly when the noise is off."""
+    import types
+    monkeypatch.setattr(dg, "AUG_NOISE_STD", noise_std)
+    calls = []
+    draw = dg.draw_aug_params
+
+    def recorded_draw(h, w):
+        p = draw(h, w)
+        calls.append(("draw", p.record()))
+        return p
+
+    monkeypatch.setattr(dg, "draw_aug_params", recorded_draw)
+
+    class FakeLib:
+        def __getattr__(self, name):
+            def fn(*args):
+                calls.append((name, args))
+                return {"cgd_guidance_part_blocks": 32, "cgd_cutouts_aug_scratch_floats": 7}.get(name, 0)
+            return fn
+
+    ctx = types.SimpleNamespace(lib=FakeLib(), h=1, check=lambda rc: None, stream=lambda: 0)
+
+    class Tower:
+        def __init__(self, name, res, patch, dim):
+            self.name, self.input_resolution, self.patch, self.out_dim = name, res, patch, dim
+
+        def encode_image(self, img, layout=0, n=None, out=None):
+            calls.append((f"{self.name}.encode_image", (layout, n, tuple(img.shape))))
+            return out
+
+        def dgrad(self, d_emb, d_img=None):
+            calls.append((f"{self.name}.dgrad", (tuple(d_emb.shape),)))
+            return d_img
+
+    unet = types.SimpleNamespace(dgrad=lambda seed, out: out)
+    diffusion = types.SimpleNamespace(num_timesteps=50)
+    vit, rn = Tower("vit", 32, 8, 16), Tower("rn", 64, 0, 24)
+    B, H, W = 2, 32, 48
+    guid = dg.ClipGuidance(ctx, unet, [vit, rn], diffusion, [th.randn(2, 16), th.randn(2, 24)], [1.0, -0.25], 6,
+                           make_cutouts=dg.MakeCutouts(32, 6, use_augs=True))
+    guid.current_timestep = 49
+    guid.coords_tape = [[(0, 0, 32), (4, 0, 20)] * 3]
+    x = th.zeros(B, 3, H, W)
+    th.manual_seed(3)
+    guid.native(x, x.clone(), x.clone(), coef=None)
+    names = [c[0] for c in calls]
+    leg = ["draw"] * 6 + ["cgd_cutouts_aug_fwd", "{}.encode_image", "cgd_spherical_loss", "{}.dgrad", "cgd_cutouts_aug_scratch_floats",
+                          "cgd_cutouts_aug_bwd"]
+    assert names == [n.format("vit") for n in leg] + [n.format("rn") for n in leg] + [
+        "cgd_guidance_part_blocks", "cgd_guidance_combine", "cgd_grad_finish", "cgd_scalars"]
+    by = {n: [c[1] for c in calls if c[0] == n] for n in set(names)}
+    fwd, bwd = by["cgd_cutouts_aug_fwd"], by["cgd_cutouts_aug_bwd"]  # (h, x, boxes, params, noise, offsets, out, B, H, W, n, cs, layout, patch, s)
+    assert fwd[0][7:] == (B, H, W, 6, 32, 1, 8, 0) and fwd[1][7:] == (B, H, W, 6, 64, 0, 0, 0)
+    for f in fwd:
+        assert (f[4] is None) == (f[5] is None) == (noise_std == 0.0)
+    assert [c[-2] for c in bwd] == [0, 1]
+    assert by["draw"][:6] != by["draw"][6:]  # a parameter table of its own per tower
+    assert by["vit.encode_image"] == [(1, 6 * B, (6 * B * 16, 3 * 64))] and by["rn.encode_image"] == [(0, 6 * B, (6 * B, 3, 64, 64))]
+    assert guid.make_cutouts.last_coords == guid.coords_tape[0] and guid.calls == 1 and guid.clip_part.numel() == 2 * 6 * B

@@ -1,5 +1,5 @@
 """Native `use_augs` cutouts (csrc/cutaug.hip) on the GPU: forward and adjoint against the torch restatement (same parameter and
-noise draws by seed), the adjoint identity, bit-reproducible backward, the single-tower ClipGuidance CLIP leg against _clip_leg_with_augs_torch,
+noise draws by seed), the adjoint identity, bit-reproducible backward, the single-tower ClipGuidance CLIP leg against _clip_leg_torch,
 and MakeCutouts(use_augs=True) as an autograd node.
 
 Criterion `nearest-ties`: |a - b| <= 1e-4 + 1e-3 |ref| except for at most 1e-4 of the elements.  GPU torch divides the grid by a
@@ -151,7 +151,7 @@ def _guidance(ctx, names, cutn):
 
 @pytest.mark.parametrize("names", [("ViT-B/32",), ("RN50",)])
 def test_clip_leg_matches_the_torch_leg(ctx, noise_std, names):
-    """ClipGuidance's use_augs CLIP leg, native against _clip_leg_with_augs_torch with the same seed and the noise on: d(CLIP loss)/dx_in
+    """ClipGuidance's use_augs CLIP leg, native against _clip_leg_torch with the same seed and the noise on: d(CLIP loss)/dx_in
     (accumulated onto a non-zero gclip), the CLIP loss and the tower's embeddings."""
     noise_std(0.01)
     cutn, B, H, W = 16, 1, 256, 256
@@ -166,8 +166,8 @@ def test_clip_leg_matches_the_torch_leg(ctx, noise_std, names):
         part = th.empty(len(names) * cutn * B, device=DEV)
         th.manual_seed(77)
         th.cuda.manual_seed(77)
-        fn = guid._clip_leg_with_augs if leg == "native" else guid._clip_leg_with_augs_torch
-        fn(x_in, coords, wm, gclip, part, 1)
+        fn = guid._clip_leg if leg == "native" else guid._clip_leg_torch
+        fn(x_in, dg._AugCuts(ctx.lib, coords, B, H, W, x_in.device), wm, None, gclip, part, 1)
         th.cuda.synchronize()
         res[leg] = (gclip - 0.5, float(part.double().sum()), guid.emb.clone())
     (g_n, l_n, e_n), (g_t, l_t, e_t) = res["native"], res["torch"]
@@ -206,7 +206,7 @@ def test_make_cutouts_use_augs_on_the_gpu(ctx, noise_std):
 def test_dual_tower_clip_leg_against_the_cpu_oracle(noise_std):
     """RN50 + ViT-B/32 (BASELINE config 5's dual-tower mode) with use_augs: the native leg's d(CLIP loss)/dx_in, CLIP loss and first-tower
     embeddings against the CPU oracle towers running the torch restatement (noise off, one seed, draws in tower order).  The CPU is the
-    judge here rather than _clip_leg_with_augs_torch on the GPU: GPU torch scales the sampling grid by a reciprocal, so a few nearest
+    judge here rather than _clip_leg_torch on the GPU: GPU torch scales the sampling grid by a reciprocal, so a few nearest
     picks per hundred thousand land on the neighbouring pixel, and through two random-weight towers that moves g well beyond rounding
     (reported below, not graded).  The kernels reproduce the CPU's picks exactly (tests/test_cutaug_host.py)."""
     import torch.nn.functional as F
@@ -237,12 +237,12 @@ def test_dual_tower_clip_leg_against_the_cpu_oracle(noise_std):
         gclip = th.zeros((B, 3, H, W), device=DEV)
         part = th.zeros(2 * cutn * B, device=DEV)
         th.manual_seed(77)
-        fn(x_in, coords, wm, gclip, part, 0)
+        fn(x_in, dg._AugCuts(ctx32.lib, coords, B, H, W, x_in.device), wm, None, gclip, part, 0)
         th.cuda.synchronize()
         return gclip.cpu(), float(part.double().sum()), guid.emb.cpu().clone()
 
-    g_n, l_n, e_n = device_leg(guid._clip_leg_with_augs)
-    g_t, l_t, _ = device_leg(guid._clip_leg_with_augs_torch)
+    g_n, l_n, e_n = device_leg(guid._clip_leg)
+    g_t, l_t, _ = device_leg(guid._clip_leg_torch)
     # the oracle: the reference recipe (cgd.py:190-204) on the CPU, towers in order, parameters from the same CPU seed
     mean = th.tensor(dg.CLIP_MEAN).view(1, 3, 1, 1)
     std = th.tensor(dg.CLIP_STD).view(1, 3, 1, 1)

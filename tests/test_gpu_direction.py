@@ -1,7 +1,7 @@
 """The directional CLIP loss on the GPU.  Op level: cgd_directional_loss (csrc/direction.hip) through the C ABI against the float64 reference
 (tests/direction_ref.py) at the literal |a - b| <= 1e-4 + 1e-3 |ref|; on the stressed value set each row's gradient is first multiplied by
 |e_r| n_r (it is homogeneous of degree -1 in both) and the tensor brought to unit peak.  Step level: ClipGuidance.native with direction prompts
-against the same step with the CLIP leg restated in torch ops and autograd (_clip_leg_direction_torch), and one short run of the drop-in generator."""
+against the same step with the CLIP leg restated in torch ops and autograd (_clip_leg_torch), and one short run of the drop-in generator."""
 import ctypes as C
 import functools
 import math
@@ -203,7 +203,7 @@ def _guided(st, leg="native", towers=1, with_target=True, cutter=None, tape=None
                                  direction_embeds=st["dirs"][:towers], direction_weights=th.tensor([0.4] if with_target else [1.0]),
                                  direction_source=st["source"], make_cutouts=cutter, **kw)
     if leg == "torch":
-        cond._clip_leg_direction = cond._clip_leg_direction_torch
+        cond._clip_leg = cond._clip_leg_torch
     cond.current_timestep = STEP_I
     cond.coords_tape = [tape or TAPE] * calls
     coef = tables.step_coef(STEP_I, STEP_I)

@@ -178,7 +178,7 @@ def _guidance(ctx, names, mk):
 
 @pytest.mark.parametrize("names", [("ViT-B/32",), ("RN50",)])
 def test_clip_leg_matches_the_torch_leg(ctx, names):
-    """ClipGuidance's resized CLIP leg, native against _clip_leg_resized_torch on the same records: d(CLIP loss)/dx_in (accumulated onto a
+    """ClipGuidance's resized CLIP leg, native against _clip_leg_torch on the same records: d(CLIP loss)/dx_in (accumulated onto a
     non-zero gclip), the CLIP loss and the tower's embeddings."""
     B, H, W = 1, 256, 256
     mk = dg.MakeCutoutsResized(224, overview=4, inner=4, ctx=ctx)
@@ -192,10 +192,8 @@ def test_clip_leg_matches_the_torch_leg(ctx, names):
     for leg in ("native", "torch"):
         gclip = th.full((B, 3, H, W), 0.5, device=DEV)
         part = th.empty(len(names) * cutn * B, device=DEV)
-        if leg == "native":
-            guid._clip_leg_resized(x_in, table_of(recs, H, W), cutn, wm, gclip, part, 1)
-        else:
-            guid._clip_leg_resized_torch(x_in, recs, wm, gclip, part, 1)
+        fn = guid._clip_leg if leg == "native" else guid._clip_leg_torch
+        fn(x_in, dg._CutLaunch(ctx.lib, recs, table_of(recs, H, W), resized=True), wm, None, gclip, part, 1)
         th.cuda.synchronize()
         res[leg] = (gclip - 0.5, float(part.double().sum()), guid.emb.clone())
     (g_n, l_n, e_n), (g_t, l_t, e_t) = res["native"], res["torch"]

@@ -463,6 +463,18 @@ int cgd_op_new_pass(cgd_ctx* ctx) {
 }
 int64_t cgd_op_gn_stats_offset(int B, int HW, int C) { return (int64_t)cgd_gn_stats_offset(B, HW, C); }
 int64_t cgd_op_gn_record_merges(cgd_ctx* ctx) { return ctx ? (int64_t)ctx->gn_record_merges : -3; }
+int cgd_op_gn_records(cgd_ctx* ctx, const float* y, int ldy, int64_t rows, int C, int kind, float* out, int64_t cap, int* pixels, void* stream) {
+  CGD_NEED_CTX(ctx);
+  if (!out || !pixels) return -3;
+  *pixels = 0;
+  ChanSrc cs;
+  if (!(cgd_chanstats_find(ctx, y, ldy, (long)rows, C, S(stream), &cs, kind) && cs.n0 == C)) return 0;
+  const int64_t n = rows / cs.c0 * C * 2;
+  if (n > cap) CGD_FAIL(ctx, "cgd_op_gn_records: out is too small");
+  CGD_HIP(ctx, hipMemcpyAsync(out, cs.p0, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
+  *pixels = cs.c0;
+  return 0;
+}
 int cgd_set_wino(cgd_ctx* ctx, int mode, int min_m) {
   CGD_NEED_CTX(ctx);
   // mode 5 (tests / micro-benchmarks): 8-row tiles with two 32-channel blocks per wavefront (8 x 16 pixels x 256 channels) wherever N is a multiple
@@ -486,6 +498,21 @@ int cgd_op_conv3x3(cgd_ctx* ctx, const float* x, int ldx, const float* w, const 
   p.Bpk = w_frag;
   p.A = x; p.lda = ldx; p.B = w; p.ldb = 9 * Cin; p.C = y; p.ldc = ldy; p.bias = bias; p.R = R; p.ldr = ldr;
   p.M = Bn * H * W; p.N = Cout; p.conv = 1; p.H = H; p.W = W; p.Cin = Cin; p.ups = ups; p.force_tile = force_tile; p.splitk = splitk;
+  return cgd_launch_gemm(ctx, p, S(stream));
+}
+int cgd_op_conv3x3_ex(cgd_ctx* ctx, const float* x, int ldx, const float* w, const float* w_frag, float* y, int ldy, const float* bias,
+                      const float* R, int ldr, const float* gn_ab, int Bn, int H, int W, int Cin, int Cout, int ups, int force_tile, int splitk,
+                      int defer, int stats, const float* gnb_x, int gnb_ldx, const float* gnb_scratch, void* stream) {
+  CGD_NEED_CTX(ctx);
+  GemmParams p;
+  p.Bpk = w_frag;
+  p.A = x; p.lda = ldx; p.B = w; p.ldb = 9 * Cin; p.C = y; p.ldc = ldy; p.bias = bias; p.R = R; p.ldr = ldr; p.gn_ab = gn_ab;
+  p.M = Bn * H * W; p.N = Cout; p.conv = 1; p.H = H; p.W = W; p.Cin = Cin; p.ups = ups; p.force_tile = force_tile; p.splitk = splitk;
+  p.defer = defer;
+  p.stats = stats;
+  if (gnb_x && gnb_scratch) {
+    p.gnb_x = gnb_x; p.gnb_ldx = gnb_ldx; p.gnb_coef = cgd_gn_coef(gnb_scratch, Bn, H * W, Cout); p.gnb_act = 1;
+  }
   return cgd_launch_gemm(ctx, p, S(stream));
 }
 int cgd_op_conv_in(cgd_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int Bn, int H, int W, int Cin, int Cout,

@@ -61,7 +61,8 @@ struct PendingReduce {  // a deferred reduction (GemmParams::defer) that has not
 };
 
 // Per-channel statistics of a conv OUTPUT, taken by the conv kernel's own epilogue (round 4: wconv_kernel): for every 8 x 16-pixel half tile and
-// channel the (mean, M2 = sum of squared deviations) pair of its 128 values, [B * HW / 128][N][2] floats.  The GroupNorm that reads the tensor next
+// channel the (mean, M2 = sum of squared deviations) pair of its 128 values, [B * HW / 128][N][2] floats (hconv2_kernel's unsplit tile: 4 x 16
+// pixels, 64 values per record: `cnt`).  The GroupNorm that reads the tensor next
 // merges these instead of sweeping the tensor (norm.hip gn_stats_final_ch_kernel): gn_stats_partial_kernel's pass over x disappears for conv-produced
 // tensors.  An entry belongs to the tensor it was taken from (pointer, row stride, rows, channels) and is only valid inside the network pass that
 // produced it (`serial`): a later pass that writes the same buffer with another kernel can never leave stale statistics behind.
@@ -74,11 +75,13 @@ struct ChanStatsEntry {
   hipStream_t stream = nullptr;
   unsigned long long serial = 0;
   int kind = 0;  // 0: forward statistics (mean, M2); 1: GroupNorm-backward sums (gcoef * sum du, gcoef * sum du (x - mean)) of a dgrad conv's output
+  int cnt = 128;  // pixels per record
 };
 struct ChanSrc {  // what the merging GroupNorm reads: channels [0, n0) from p0 (records of n0 channels), [n0, n0 + n1) from p1 (the two halves of a skip concat)
   const float* p0 = nullptr;
   const float* p1 = nullptr;
   int n0 = 0, n1 = 0;
+  int c0 = 128, c1 = 128;  // pixels per record of either source (the halves of a concat may come from different kernels)
 };
 
 struct FragEntry {  // fragment-order copy of a persistent weight (hgemm.hip)
@@ -98,7 +101,8 @@ struct cgd_ctx {
   int hconv_var = 0;  // halo conv tile: 0 = 8x16 pixels / 4 wavefronts / two workgroups per CU (default, +0.8 % on the step),
                       // bit 0 = 16x16 / 8 wavefronts everywhere, bit 1 = 16x16 below 16384 pixels, bit 2 = wavefront sub-tile
                       // 64 pixels x 64 channels instead of 128 x 32 (the kernel is power-limited: 128 x 32 moves half of the
-                      // fragment traffic from the vector-memory path to the LDS, +1.2..1.8 % per layer at the 1.36 kW cap)
+                      // fragment traffic from the vector-memory path to the LDS, +1.2..1.8 % per layer at the 1.36 kW cap), bit 3 = the
+                      // unsplit 4x16-pixel x 128-channel tile wherever it can run (0: only where cgd_hconv_tile_m picks it by itself)
   int hconv_small_m = 0, hconv_small_slots = 512, hconv_small_min_chunks = 2;  // optional separate split-K target for M <= hconv_small_m
   int hconv_slots = 0, hconv_min_chunks = 4;                 // split-K target of the halo conv: workgroup slots (0 = one per CU), chunks per slice
   int hconv_w8 = 0;    // 1: 8-pixel-wide maps (the UNet's 8x8 level) run on the halo kernel with half-filled tiles.  Supported and
@@ -288,15 +292,16 @@ struct GemmParams {
                        // 49-row GEMMs on the generic kernel (92 -> 25 us)
   const float* gn_ab = nullptr;  // conv on the halo kernel only: apply SiLU(x * a + b) to the input while staging it; {a, b} pairs
                                  // [B][Cin][2] of the GroupNorm(+FiLM) that precedes the conv (kernels.h cgd_gn_ab)
-  // conv on wconv_kernel only (a DGRAD conv whose output dz is the upstream gradient of a GroupNorm+SiLU): the epilogue also takes that GroupNorm's
+  // conv on wconv_kernel or hconv2_kernel's unsplit tile only (a DGRAD conv whose output dz is the upstream gradient of a GroupNorm+SiLU): the epilogue also takes that GroupNorm's
   // backward sums per (half tile, channel) from dz, the forward input x of the norm (gnb_x, row stride gnb_ldx: one extra read of the tile, like a
   // residual) and its folded coefficients (gnb_coef = cgd_gn_coef: {a, b, gcoef, mean} per (sample, channel)); gn_bwd_partial_kernel's sweep over x
   // and dz disappears (ChanStatsEntry kind 1)
   const float* gnb_x = nullptr;
   const float* gnb_coef = nullptr;
   int gnb_ldx = 0, gnb_act = 0;
-  int stats = 0;       // conv on wconv_kernel only: 1 = the epilogue also takes per-(half tile, channel) statistics of the output for the GroupNorm
-                       // that reads it next (ChanStatsEntry); ignored by the other kernels (their consumers sweep the tensor as before)
+  int stats = 0;       // conv on wconv_kernel or hconv2_kernel's unsplit tile only: 1 = the epilogue also takes per-(tile, channel) statistics of the
+                       // output for the GroupNorm that reads it next (ChanStatsEntry); ignored by the other kernels (their consumers sweep the
+                       // tensor as before)
   // GEMV kernel only (M <= 4 rows; round 6): how the A rows are formed while they are loaded into LDS — what the UNet's embedding head used to run
   // as separate one-workgroup launches in front of each of its three GEMVs.  0: A as is; 1: SiLU(A); 2: SiLU(A + a_table[a_idx[m]]) (the class
   // embedding row added first); 3: the sinusoidal timestep embedding [cos(t[m] f) | sin(t[m] f)], f = a_freqs[K / 2] (A is not read)
@@ -318,9 +323,9 @@ struct GemmParams {
                        // next kernel reading C is one that consumes a SplitSrc (cgd_take_pending); anything else flushes first
 };
 
-// conv-epilogue statistics (norm.hip): the buffer a producer writes its [M / 128][N][2] records to (registered for tensor C in the current pass;
+// conv-epilogue statistics (norm.hip): the buffer a producer writes its [M / cnt][N][2] records to (registered for tensor C in the current pass;
 // nullptr if the shape does not qualify or the allocation fails: the producer then simply takes none) / the sources covering tensor x for a consumer
-float* cgd_chanstats_register(cgd_ctx* ctx, const float* C, int ldc, int N, long M, hipStream_t s, int kind = 0);
+float* cgd_chanstats_register(cgd_ctx* ctx, const float* C, int ldc, int N, long M, hipStream_t s, int kind = 0, int cnt = 128);
 bool cgd_chanstats_find(cgd_ctx* ctx, const float* x, int ldx, long M, int Cn, hipStream_t s, ChanSrc* out, int kind = 0);
 void cgd_chanstats_clear(cgd_ctx* ctx);
 // a kernel that takes NO records is about to (re)write the tensor C: `rows` rows of `cols` floats at row stride `ld`: every record whose tensor
@@ -386,6 +391,7 @@ bool cgd_gemm_fuses_act(cgd_ctx* ctx, GemmParams p);
 bool cgd_gemm_fuses_gnb(cgd_ctx* ctx, GemmParams p);  // ... or a GroupNorm's backward (GemmParams::gnf_*)
 bool cgd_conv_takes_gnb(cgd_ctx* ctx, GemmParams p);  // a dgrad conv that will leave the backward records of the GroupNorm in its gnb_* fields
 bool cgd_wconv_takes_gnb(const cgd_ctx* ctx, const GemmParams& g);
+bool cgd_hconv_takes_gnb(const cgd_ctx* ctx, const GemmParams& g);  // (hconv2_kernel's unsplit tile)
 // would cgd_launch_gemm run this GEMM on the GEMV kernel (the only one that forms its A rows on the fly: GemmParams::a_mode)?
 bool cgd_gemm_is_gemv(cgd_ctx* ctx, GemmParams p);
 

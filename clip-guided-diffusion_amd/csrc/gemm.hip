@@ -581,7 +581,7 @@ int cgd_plan_gemm(cgd_ctx* ctx, GemmParams& p, int* tile_out, int* kernel_out) {
       slots = ctx->hconv_small_slots;
       min_ch = ctx->hconv_small_min_chunks;
     }
-    if (auto_split && tiles < slots) {
+    if (auto_split && tiles < slots && cgd_hconv_tile_m(ctx, p) != 64) {  // (the 64-pixel tile is the unsplit variant)
       long want = std::min<long>(cdiv(slots, tiles), nchunk / min_ch);
       while (want > 1 && (size_t)want * p.M * p.N * sizeof(float) > ctx->ws_bytes) --want;
       if (want >= 2) p.splitk = (int)want;
@@ -677,11 +677,13 @@ bool cgd_gemm_fuses_gnb(cgd_ctx* ctx, GemmParams p) {
   return ok;
 }
 
-// a dgrad conv that will run on wconv_kernel in one slice and take a GroupNorm's backward sums in its epilogue (GemmParams::gnb_*)
+// a dgrad conv that will run on wconv_kernel (or on hconv2_kernel's unsplit tile) in one slice and take a GroupNorm's backward sums in its epilogue
+// (GemmParams::gnb_*)
 bool cgd_conv_takes_gnb(cgd_ctx* ctx, GemmParams p) {
   int tile = 0, kernel = 0;
   const std::string keep = ctx->err;
-  const bool ok = p.conv && cgd_plan_gemm(ctx, p, &tile, &kernel) == 0 && tile == 515 && p.splitk == 1 && cgd_wconv_takes_gnb(ctx, p);
+  const bool ok = p.conv && cgd_plan_gemm(ctx, p, &tile, &kernel) == 0 && p.splitk == 1 &&
+                  ((tile == 515 && cgd_wconv_takes_gnb(ctx, p)) || (tile == 512 && cgd_hconv_takes_gnb(ctx, p)));
   ctx->err = keep;
   return ok;
 }
@@ -830,5 +832,36 @@ extern "C" int cgd_op_plan(int conv, int M, int N, int K, int H, int W, int Cin,
     wg = (long)cdiv(p.M, bm) * cdiv(p.N, bn);
   }
   out4[0] = kernel; out4[1] = tile; out4[2] = p.splitk; out4[3] = (int)(wg * p.splitk);
+  return 0;
+}
+
+// cgd_op_plan for a 3x3 conv with what the UNet's ResBlocks set besides the shape: the halo kernel's tile variant bits (cgd_set_hconv), a request for
+// forward GroupNorm records (stats) or for the backward sums of a norm (gnb).  out5 = {kernel, tile code, split-K slices, workgroups of the main
+// launch, pixels per workgroup tile of the halo conv kernel (0 on the other kernels)}.
+extern "C" int cgd_op_plan_conv(int Bn, int H, int W, int Cin, int Cout, int precision, int num_cu, int hconv_var, int stats, int gnb, int* out5) {
+  if (!out5) return -3;
+  cgd_ctx ctx;
+  ctx.precision = precision;
+  if (num_cu > 0) ctx.num_cu = num_cu;
+  ctx.hconv_var = hconv_var;
+  ctx.ws_bytes = (size_t)256 << 20;
+  GemmParams p;
+  float* const dummy = (float*)(uintptr_t)4096;
+  p.A = p.B = dummy;
+  p.C = dummy;
+  p.M = Bn * H * W; p.N = Cout; p.K = 9 * Cin; p.lda = Cin; p.ldb = p.K; p.ldc = Cout;
+  p.conv = 1; p.H = H; p.W = W; p.Cin = Cin; p.weight = 1;
+  p.Bpk = p.Bwk = dummy;
+  p.stats = stats;
+  if (gnb) {
+    p.gnb_x = p.gnb_coef = dummy; p.gnb_ldx = Cout; p.gnb_act = 1;
+  }
+  int tile = 0, kernel = 0;
+  const int rc = cgd_plan_gemm(&ctx, p, &tile, &kernel);
+  if (rc != 0) return rc;
+  const bool h = kernel == 1 && tile == 512;
+  const long wg = kernel != 1 ? 0 : tile == 516 ? cgd_kconv_tiles_m(&ctx, p) * (p.N >> 5)
+                                : tile == 515 ? cgd_wconv_tiles_m(&ctx, p) * cdiv(p.N, 128 * cgd_wconv_nc(&ctx, p)) : cgd_hconv_tiles_m(&ctx, p) * cdiv(p.N, 128);
+  out5[0] = kernel; out5[1] = tile; out5[2] = p.splitk; out5[3] = (int)(wg * p.splitk); out5[4] = h ? cgd_hconv_tile_m(&ctx, p) : 0;
   return 0;
 }

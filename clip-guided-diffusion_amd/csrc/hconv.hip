@@ -31,6 +31,14 @@ struct HConvParams {
   int M, N, H, W, Cin, ups, splitk;
   float alpha;
   const float* gn;  // GN variant: {a, b} pairs [B][Cin][2] of the GroupNorm(+FiLM) in front of this conv (GemmParams::gn_ab)
+  // the unsplit 4-row tile only (one workgroup holds every finished output element of its 64 pixels): GroupNorm records of the output, wconv_kernel's
+  // epilogue arithmetic on 64-pixel tiles (common.h ChanStatsEntry): stat = forward (mean, M2) per (tile, channel); bstat = the backward sums of the
+  // norm whose upstream gradient this dgrad conv's output is (bx = the norm's input, bcoef = its {a, b, gcoef, mean} table)
+  float* stat;
+  float* bstat;
+  const float* bx;
+  const float* bcoef;
+  int ldbx, bact;
   int nmajor;  // 1: channel-tile major order within an XCD's run of tiles (the <= 64x64-pixel levels, where the packed weights
                // are the larger operand: an XCD then owns a few output-channel panels and keeps their weights in its L2)
 };
@@ -57,9 +65,15 @@ struct HConvParams {
 //   * LDS patch layout: pixel pitch 80 B, patch-ROW pitch 1536 B (18 pixels = 1440 B, padded to a multiple of 256 B): a
 //     32-pixel MFMA block spans two tile rows, and with the unpadded row pitch lanes 12,13 / 28,29 (and 4,5 / 20,21) of each
 //     ds_read_b128 lane group hit the same banks (SQ_LDS_BANK_CONFLICT = 50 % of SQ_LDS_IDX_ACTIVE before the padding).
+//   * TH = 4, the unsplit tile of the 64x64 level (one sample, 512 output channels: 128 tiles of 8 x 16 pixels for 256 CUs, which the launcher fills
+//     by splitting K in two, so that no workgroup holds a finished output element): 4 x 16 pixels x 128 channels, ALL of K in one workgroup, 4
+//     wavefronts of 64 pixels x 32 channels (NI = 2: 6 MFMAs per k-step, a weight fragment used by 6 instead of 12), the 6 x 18 patch in 4 staging
+//     passes, a 9-slot fragment ring (8 k-steps ahead: the k-steps are half as long), 36,864 B of LDS, 160 / 172 VGPRs.  The workgroup's output
+//     elements are final, so its epilogue leaves the GroupNorm records wconv_kernel leaves on the larger maps (64 pixels each): the norms of the level
+//     merge records instead of sweeping the tensor to sum the slices (profiles/hconv_unsplit_64px_tile.txt).
 constexpr int PW2 = 18;     // patch width: 16 + 2
 constexpr int HRS = 768;    // LDS pitch of a patch row (bf16 elements)
-constexpr int NPASS2 = 6;   // staging passes (both tile heights)
+constexpr int NPASS2 = 6;   // staging passes (8- and 16-row tiles; 4 on the 4-row tile)
 
 //   * GN = true: the conv's input is SiLU(GroupNorm(x) [* (1 + scale) + shift]) of a tensor x whose statistics are already
 //     folded into per-(sample, channel) pairs {a, b}: the patch staging applies y = silu(x * a + b) to the values it has in
@@ -72,16 +86,18 @@ constexpr int NPASS2 = 6;   // staging passes (both tile heights)
 // cgd_buf_load16_if).
 
 template <int MODE, int TH, int NJ, bool GN>
-__global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict__ Ag, const uint4* __restrict__ Bg, float* Cg,
+__global__ __launch_bounds__(TH == 4 ? 256 : TH * 32) void hconv2_kernel(const float* __restrict__ Ag, const uint4* __restrict__ Bg, float* Cg,
                                                          const float* __restrict__ biasg, const float* Rg, float* __restrict__ wsg,
                                                          const float* __restrict__ gng, const HConvParams p) {
   constexpr int NPL = MODE == 1 ? 2 : 1;   // bf16 planes (hi, lo)
   constexpr int NP2 = (TH + 2) * PW2;      // patch rows: 324 / 180
   constexpr int PLANE = (TH + 2) * HRS;    // elements per plane
-  constexpr int NI = 4 / NJ;               // 32-pixel blocks per wavefront (NI x NJ = 4 MFMA blocks)
-  constexpr int NT = TH * 32;              // threads
+  constexpr int NI = TH == 4 ? 2 : 4 / NJ;  // 32-pixel blocks per wavefront (NI x NJ = 4 MFMA blocks; 2 on the 4-row tile)
+  constexpr int NT = TH == 4 ? 256 : TH * 32;  // threads
   constexpr int RPP = NT / 8;              // patch rows per staging pass
-  static_assert(NPASS2 * RPP >= NP2, "staging passes must cover the patch");
+  constexpr int NPASS = TH == 4 ? 4 : NPASS2;  // staging passes: 108 patch rows in 4 x 32 on the 4-row tile
+  static_assert(TH != 4 || NJ == 1, "the 4-row tile runs 64 pixels x 32 channels per wavefront");
+  static_assert(NPASS * RPP >= NP2, "staging passes must cover the patch");
   __shared__ __attribute__((aligned(16))) __bf16 lds[2 * NPL * PLANE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = NJ == 2 ? wave >> 1 : wave >> 2, wn = NJ == 2 ? wave & 1 : wave & 3;  // pixel group, channel group
@@ -104,9 +120,9 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
 
   // per-thread patch staging slots: RPP patch rows per pass, 8 float4 per row
   const int c4 = tid & 7;
-  int poff[NPASS2], soff[NPASS2];  // global offset, LDS offset
+  int poff[NPASS], soff[NPASS];  // global offset, LDS offset
 #pragma unroll
-  for (int j = 0; j < NPASS2; ++j) {
+  for (int j = 0; j < NPASS; ++j) {
     const int prow = (tid >> 3) + RPP * j;
     poff[j] = -2;  // beyond the patch (last pass only): such a thread stores zeros into the unused tail of LDS patch row 0, which
     soff[j] = PW2 * HPH + c4 * 4;  // keeps the store unconditional (a skipped store leaves the load pending at the loop back
@@ -123,9 +139,9 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
       poff[j] = inb ? (yy * Ws + xx) * p.lda + c4 * 4 : -1;  // -1: zero padding
     }
   }
-  int poffb[NPASS2];  // the same as byte offsets for the buffer loads: padding and beyond-the-patch slots are out of range
+  int poffb[NPASS];  // the same as byte offsets for the buffer loads: padding and beyond-the-patch slots are out of range
 #pragma unroll
-  for (int j = 0; j < NPASS2; ++j) poffb[j] = poff[j] >= 0 ? poff[j] * 4 : CGD_OOB;
+  for (int j = 0; j < NPASS; ++j) poffb[j] = poff[j] >= 0 ? poff[j] * 4 : CGD_OOB;
   // this lane's pixels (one per 32-pixel block of the wavefront's NI): patch position and output row
   int fro[NI];
   long mrow[NI];  // output row of this lane's pixel, or -1 for a tile column beyond the image (W not a multiple of 16)
@@ -167,7 +183,7 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
   // cgd_split_quad (mfma_stage.h) everywhere but in the largest instantiation: there the longer IR keeps the fully unrolled chunk loop from being formed
   // before the last scalar-replacement pass and the weight ring lands in scratch memory
   constexpr bool SPLITQ = !(GN && NJ == 2 && TH == 8);
-  cgd_f32x4 pr[NPASS2];
+  cgd_f32x4 pr[NPASS];
   cgd_f32x4 ga[GN ? 2 : 1];  // {a0, b0, a1, b1}, {a2, b2, a3, b3} of this thread's 4 channels of the chunk being staged
   const cgd_f32x4 z4 = cgd_f32x4{0.f, 0.f, 0.f, 0.f};
   const float* __restrict__ gnimg = GN ? gng + ((long)img * p.Cin + c4 * 4) * 2 : nullptr;
@@ -180,7 +196,7 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
       ga[0] = *(const cgd_f32x4*)(gnimg + cg_ * 64);                                                               \
       ga[1] = *(const cgd_f32x4*)(gnimg + cg_ * 64 + 4);                                                           \
     }                                                                                                              \
-    _Pragma("unroll") for (int j = 0; j < NPASS2; ++j)                                                             \
+    _Pragma("unroll") for (int j = 0; j < NPASS; ++j)                                                             \
         pr[j] = __builtin_bit_cast(cgd_f32x4, cgd_buf_load16_if(Aimg, 0x80000000u, (WANT), poffb[j], (CH) * 128)); \
   }
 #define PATCH_STORE2(DSTB, J0, J1)                                                                                                            \
@@ -241,14 +257,14 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
   // a k-step is compile-time and the ring runs across chunk boundaries without a drain.  The 4-wavefront tile has the
   // registers for 6 slots (5 k-steps ~ 2 us of slack: covers the patch loads queued in front of the B loads in the in-order
   // vmcnt counter); the 8-wavefront tile spills beyond 3.
-  constexpr int RING = (TH == 8 || NJ == 1) ? 6 : 3, DIST = RING - 1;
+  constexpr int RING = TH == 4 ? 9 : (TH == 8 || NJ == 1) ? 6 : 3, DIST = RING - 1;
   cgd_bf16x8 af[2][NI][NPL];     // [pipeline slot][pixel block][plane]
   uint4 bq[RING][NJ][NPL];   // [ring slot][channel block][plane]
   if (c0 < c1) {
     PATCH_LOAD2(c0, -1);
 #pragma unroll
     for (int q = 0; q < DIST; ++q) B_LOAD2(bq[q], c0, -1, q >> 1, q & 1);
-    PATCH_STORE2(lds, 0, NPASS2);
+    PATCH_STORE2(lds, 0, NPASS);
   }
   __syncthreads();
   for (int c = c0; c < c1; ++c) {
@@ -280,11 +296,15 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
       // ---- 12 MFMAs; the conversion of the next chunk's patch rides under k-steps 6..11 (unconditional: the last chunk
       //      rewrites the idle buffer with stale data, so there is no branch inside the scheduling region)
       MFMA12(af[q & 1], bq[q % RING]);
-      if (q >= 6 && q <= 11) PATCH_STORE2(nxt, q - 6, q - 5);
+      if (q >= 6 && q < 6 + NPASS) PATCH_STORE2(nxt, q - 6, q - 5);
 #pragma unroll
-      for (int r = 0; r < 12; ++r) {
+      for (int r = 0; r < (TH == 4 ? 6 : 12); ++r) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-        if constexpr (NJ == 2) {
+        if constexpr (TH == 4) {
+          if (r < 4) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);       // DS read (4 per k-step)
+          else __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);             // VMEM read (2)
+          __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);                  // VALU (twice per MFMA: half the MFMAs per patch pass)
+        } else if constexpr (NJ == 2) {
           if (r % 3 == 0) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read (4 per k-step)
           if (r % 3 == 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read (4)
         } else {
@@ -320,6 +340,97 @@ __global__ __launch_bounds__(TH * 32) void hconv2_kernel(const float* __restrict
                 cgd_f32x4{acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
         }
       }
+    return;
+  }
+  if constexpr (TH == 4) {
+    // The wavefront's 64 pixels x 32 channels are final values: lane (l31, hh) holds pixels l31 and 32 + l31, channels cb0 + 8 g + 4 hh .. + 3.
+    const int cb0 = nb0 * 32;
+    if (cb0 >= p.N) return;
+    cgd_f32x4 o[NI][4];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      cgd_f32x4 rv[4];
+      if (Rg && mrow[i] >= 0) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) rv[g] = *(const cgd_f32x4*)&Rg[mrow[i] * p.ldr + cb0 + 8 * g + 4 * hh];
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int col = cb0 + 8 * g + 4 * hh;
+        o[i][g] = cgd_f32x4{acc[i][0][4 * g], acc[i][0][4 * g + 1], acc[i][0][4 * g + 2], acc[i][0][4 * g + 3]} * p.alpha;
+        if (biasg) o[i][g] += cgd_f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]};
+        if (Rg && mrow[i] >= 0) o[i][g] += rv[g];
+        if (mrow[i] >= 0) *(cgd_f32x4*)&Cg[mrow[i] * p.ldc + col] = o[i][g];
+      }
+    }
+    // records (the launcher asks for them only where every tile pixel lies inside the image): sums over the 2 pixels of the lane, then over the 32
+    // lanes of its half-wavefront; lanes 0 and 32 write 16 channels each
+    if (p.stat) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        cgd_f32x4 kk, s1 = z4, s2 = z4;  // shift: the value of the tile's first pixel (wconv_kernel's choice)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) kk[e] = __shfl(o[0][g][e], lane & 32, 64);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+          const cgd_f32x4 d = o[i][g] - kk;
+          s1 += d;
+          s2 += d * d;
+        }
+#pragma unroll
+        for (int off = 1; off < 32; off <<= 1)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            s1[e] += __shfl_xor(s1[e], off, 64);
+            s2[e] += __shfl_xor(s2[e], off, 64);
+          }
+        if (l31 == 0) {
+          float* so = p.stat + ((long)mt * p.N + cb0 + 8 * g + 4 * hh) * 2;
+          const cgd_f32x4 mean = kk + s1 * (1.f / 64.f), m2 = s2 - s1 * s1 * (1.f / 64.f);
+          *(cgd_f32x4*)so = cgd_f32x4{mean[0], m2[0], mean[1], m2[1]};
+          *(cgd_f32x4*)(so + 4) = cgd_f32x4{mean[2], m2[2], mean[3], m2[3]};
+        }
+      }
+    }
+    if (p.bstat) {
+      // du = dz * SiLU'(x a + b); sums of du and du (x - mean) over the tile (norm.hip gn_bwd_partial_kernel's arithmetic, as in wconv_kernel)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int col = cb0 + 8 * g + 4 * hh;
+        cgd_f32x4 cfa, cfb, cfg_, cfm, q1 = z4, q2 = z4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const cgd_f32x4 c_ = *(const cgd_f32x4*)(p.bcoef + ((long)img * p.N + col + e) * 4);
+          cfa[e] = c_[0]; cfb[e] = c_[1]; cfg_[e] = c_[2]; cfm[e] = c_[3];
+        }
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+          const cgd_f32x4 xv = *(const cgd_f32x4*)&p.bx[mrow[i] * p.ldbx + col];
+          cgd_f32x4 d = o[i][g];
+          if (p.bact) {
+            const cgd_f32x4 uu = xv * cfa + cfb;
+            cgd_f32x4 sg;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) sg[e] = cgd_sigmoid_rcp(uu[e]);
+            d *= sg * (1.f + uu * (1.f - sg));
+          }
+          q1 += d;
+          q2 += d * (xv - cfm);
+        }
+#pragma unroll
+        for (int off = 1; off < 32; off <<= 1)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            q1[e] += __shfl_xor(q1[e], off, 64);
+            q2[e] += __shfl_xor(q2[e], off, 64);
+          }
+        if (l31 == 0) {
+          float* so = p.bstat + ((long)mt * p.N + col) * 2;
+          *(cgd_f32x4*)so = cgd_f32x4{cfg_[0] * q1[0], cfg_[0] * q2[0], cfg_[1] * q1[1], cfg_[1] * q2[1]};
+          *(cgd_f32x4*)(so + 4) = cgd_f32x4{cfg_[2] * q1[2], cfg_[2] * q2[2], cfg_[3] * q1[3], cfg_[3] * q2[3]};
+        }
+      }
+    }
     return;
   }
 #pragma unroll
@@ -399,11 +510,34 @@ bool cgd_hconv_supported(const cgd_ctx* ctx, const GemmParams& p) {
 
 // pixels per workgroup tile: the 8x16 tile (4 wavefronts, two workgroups per CU whose stalls are uncorrelated) unless
 // hconv_var bit 0 asks for 16x16 everywhere or bit 1 for 16x16 below 16384 pixels (ops_r1aj)
+// will a launch of this conv on the unsplit tile leave GroupNorm records: forward statistics of its output (GemmParams::stats) / the backward sums
+// of the norm named by its gnb_* fields?  Whole 4x16-pixel tiles only; the conditions of wconv_kernel's records otherwise (cgd_wconv_takes_gnb)
+static bool hconv_records_fwd(const cgd_ctx* ctx, const GemmParams& g) {
+  return g.stats && (ctx->gn_epi & 1) && g.H > 0 && g.W > 0 && !(g.W & 15) && cgd_gn_merges_records(g.H * g.W);
+}
+static bool hconv_records_bwd(const cgd_ctx* ctx, const GemmParams& g) {
+  return g.gnb_x && g.gnb_coef && (ctx->gn_epi & 2) && g.H > 0 && g.W > 0 && !(g.W & 15) && cgd_gn_merges_records(g.H * g.W) && !(g.gnb_ldx & 3) &&
+         !((uintptr_t)g.gnb_x & 15) && !g.stats && !g.R;
+}
+
 int cgd_hconv_tile_m(const cgd_ctx* ctx, const GemmParams& p) {
+  // The unsplit tile: 4x16 pixels x 128 channels, all of K in one workgroup, bf16x3 products.  Chosen where the 128-pixel
+  // tiling leaves CUs without a workgroup (so that K would be split and no workgroup would hold a finished output element), the 64-pixel tiling gives
+  // every CU one, and the launch is asked for GroupNorm records, which is what the finished elements are for: a launch nobody wants records from
+  // keeps its two slices (the conv itself is no faster unsplit, profiles/hconv_unsplit_64px_tile.txt).  hconv_var bit 3 forces it (tests, benchmarks).
+  if (ctx->precision == CGD_PREC_BF16X3 && !(p.N & 127) && p.splitk <= 1 && p.H > 0 && p.W > 0 && !(p.H & 3) && p.M % (p.H * p.W) == 0) {
+    if (ctx->hconv_var & 8) return 64;
+    if (ctx->hconv_var == 0 && !(p.W & 15) && (hconv_records_fwd(ctx, p) || hconv_records_bwd(ctx, p))) {
+      const long t64 = (long)(p.M / (p.H * p.W)) * (p.H / 4) * (p.W >> 4) * (p.N >> 7);
+      if (t64 / 2 < ctx->num_cu && t64 >= ctx->num_cu) return 64;
+    }
+  }
   if (ctx->hconv_var & 1) return HB_M;
   if ((ctx->hconv_var & 2) && p.M < 16384) return HB_M;
   return 128;
 }
+
+bool cgd_hconv_takes_gnb(const cgd_ctx* ctx, const GemmParams& g) { return g.splitk <= 1 && cgd_hconv_tile_m(ctx, g) == 64 && hconv_records_bwd(ctx, g); }
 
 // pixel tiles of a launch: images x tile rows x tile columns (the last column tile may be partial)
 long cgd_hconv_tiles_m(const cgd_ctx* ctx, const GemmParams& p) {
@@ -417,16 +551,21 @@ int cgd_launch_hconv(cgd_ctx* ctx, const GemmParams& g, hipStream_t s) {
   p.lda = g.lda; p.ldc = g.ldc; p.ldr = g.ldr;
   p.M = g.M; p.N = g.N; p.H = g.H; p.W = g.W; p.Cin = g.Cin; p.ups = g.ups; p.splitk = g.splitk; p.alpha = g.alpha;
   p.gn = g.gn_ab;
+  p.stat = p.bstat = nullptr; p.bx = g.gnb_x; p.bcoef = g.gnb_coef; p.ldbx = g.gnb_ldx; p.bact = g.gnb_act;
   // weights 9 * Cin * N against activations M * Cin (both x 4 B): weight-panel major when the weights are larger
   p.nmajor = (ctx->tile_order == 1 || (ctx->tile_order == 0 && 9L * g.N >= g.M)) ? 1 : 0;
   const int tm = cgd_hconv_tile_m(ctx, g);
+  if (tm == 64 && g.splitk <= 1) {  // records for the GroupNorm that reads the output next (64 pixels each)
+    if (hconv_records_fwd(ctx, g)) p.stat = cgd_chanstats_register(ctx, g.C, g.ldc, g.N, g.M, s, 0, 64);
+    if (hconv_records_bwd(ctx, g)) p.bstat = cgd_chanstats_register(ctx, g.C, g.ldc, g.N, g.M, s, 1, 64);
+  }
   dim3 grid((int)cgd_hconv_tiles_m(ctx, g) * cdiv(g.N, HB_N), 1, g.splitk > 1 ? g.splitk : 1);
 #define HC2_LAUNCH(M_, TH_, NJ_)                                                                                                   \
   {                                                                                                                                \
     if (p.gn)                                                                                                                      \
-      CGD_LAUNCH((hconv2_kernel<M_, TH_, NJ_, true>), grid, dim3(TH_ * 32), 0, s, p.A, p.Bp, p.C, p.bias, p.R, p.ws, p.gn, p);  \
+      CGD_LAUNCH((hconv2_kernel<M_, TH_, NJ_, true>), grid, dim3(TH_ == 4 ? 256 : TH_ * 32), 0, s, p.A, p.Bp, p.C, p.bias, p.R, p.ws, p.gn, p);  \
     else                                                                                                                           \
-      CGD_LAUNCH((hconv2_kernel<M_, TH_, NJ_, false>), grid, dim3(TH_ * 32), 0, s, p.A, p.Bp, p.C, p.bias, p.R, p.ws, p.gn, p); \
+      CGD_LAUNCH((hconv2_kernel<M_, TH_, NJ_, false>), grid, dim3(TH_ == 4 ? 256 : TH_ * 32), 0, s, p.A, p.Bp, p.C, p.bias, p.R, p.ws, p.gn, p); \
   }
 #define HC2_LAUNCH_T(M_, NJ_)  \
   {                            \
@@ -436,7 +575,9 @@ int cgd_launch_hconv(cgd_ctx* ctx, const GemmParams& g, hipStream_t s) {
       HC2_LAUNCH(M_, 16, NJ_)  \
   }
   const bool nj1 = (ctx->hconv_var & 4) == 0;  // wave -> sub-tile mapping (kernel header): 128 pixels x 32 channels unless bit 2
-  if (ctx->precision == CGD_PREC_BF16X3) {
+  if (tm == 64) {
+    HC2_LAUNCH(1, 4, 1)
+  } else if (ctx->precision == CGD_PREC_BF16X3) {
     if (nj1) HC2_LAUNCH_T(1, 1) else HC2_LAUNCH_T(1, 2)
   } else {
     if (nj1) HC2_LAUNCH_T(2, 1) else HC2_LAUNCH_T(2, 2)

@@ -251,10 +251,10 @@ __global__ __launch_bounds__(256) void gn_stats_final_kernel(const float* __rest
   gn_fold_group(b, g, lane, cpg, (float)mean, (float)(1.0 / sqrt(var + (double)eps)), stats, gamma, beta, film, ldfilm, coef);
 }
 
-// The same merge from the records a conv epilogue took (common.h ChanStatsEntry): (mean, M2) of every (128-pixel half tile, channel); equal
-// counts, so the group mean is the plain average of the ntile * cpg record means.  One block per (b, group); the records of a group are
-// cpg consecutive pairs per tile (64-768 bytes), read twice (L2-resident: a whole tensor's records are <= 2 MB).
-__global__ __launch_bounds__(256) void gn_stats_final_ch_kernel(const ChanSrc cs, int ntile, int cpg, int lg /*ceil log2 cpg*/, float eps,
+// The same merge from the records a conv epilogue took (common.h ChanStatsEntry): (mean, M2) of every (128- or 64-pixel tile, channel); the
+// group mean is the count-weighted average of the record means (the two sources of a concat may carry different counts).  One block per (b, group);
+// the records of a group are cpg consecutive pairs per tile (64-768 bytes), read twice (L2-resident: a whole tensor's records are <= 2 MB).
+__global__ __launch_bounds__(256) void gn_stats_final_ch_kernel(const ChanSrc cs, int HW, int cpg, int lg /*ceil log2 cpg*/, float eps,
                                                                 float* __restrict__ stats, const float* __restrict__ gamma,
                                                                 const float* __restrict__ beta, const float* __restrict__ film, int ldfilm,
                                                                 float* __restrict__ coef) {
@@ -265,6 +265,8 @@ __global__ __launch_bounds__(256) void gn_stats_final_ch_kernel(const ChanSrc cs
   const int c = g * cpg + ci;
   const bool on = ci < cpg;
   const bool first = c < cs.n0;
+  const double cnt = first ? cs.c0 : cs.c1;  // pixels per record (a power of two: the products below are exact)
+  const int ntile = HW / (first ? cs.c0 : cs.c1);
   const float* base = first ? cs.p0 + ((long)b * ntile * cs.n0 + c) * 2 : cs.p1 + ((long)b * ntile * cs.n1 + (c - cs.n0)) * 2;
   const long rstride = (first ? cs.n0 : cs.n1) * 2L;
   // the records come from other XCDs' epilogues, i.e. from beyond this L2 (~1-2 us per dependent access): 8 independent loads in flight per
@@ -281,9 +283,9 @@ __global__ __launch_bounds__(256) void gn_stats_final_ch_kernel(const ChanSrc cs
       }
 #pragma unroll
       for (int u = 0; u < U; ++u)
-        if (t0 + u * tstep < ntile) sum += (double)v[u];
+        if (t0 + u * tstep < ntile) sum += cnt * (double)v[u];
     }
-  const double items = (double)ntile * cpg;
+  const double items = (double)HW * cpg;
   const double mean = block_sum256(sum, red) / items;
   double m2 = 0.0;
   if (on)
@@ -298,11 +300,11 @@ __global__ __launch_bounds__(256) void gn_stats_final_ch_kernel(const ChanSrc cs
       for (int u = 0; u < U; ++u)
         if (t0 + u * tstep < ntile) {
           const double d = (double)v[u].x - mean;
-          m2 += (double)v[u].y + 128.0 * d * d;
+          m2 += (double)v[u].y + cnt * d * d;
         }
     }
   m2 = block_sum256(m2, red);
-  const double var = m2 / (items * 128.0);
+  const double var = m2 / items;
   gn_fold_group(b, g, lane, cpg, (float)mean, (float)(1.0 / sqrt(var + (double)eps)), stats, gamma, beta, film, ldfilm, coef);
 }
 
@@ -463,7 +465,7 @@ __global__ __launch_bounds__(256) void gn_bwd_coef_kernel(const float* __restric
   }
 }
 
-// The same from the records a dgrad conv's epilogue took (ChanStatsEntry kind 1): per (128-pixel half tile, channel) the pair
+// The same from the records a dgrad conv's epilogue took (ChanStatsEntry kind 1): per (128- or 64-pixel tile, channel: ntile of them) the pair
 // (gcoef * sum du, gcoef * sum du (x - mean)).  One block per (b, group); thread mapping and load batching of gn_stats_final_ch_kernel.
 __global__ __launch_bounds__(256) void gn_bwd_coef_ch_kernel(const float* __restrict__ rec, int ntile, int lg, const float* __restrict__ stats,
                                                              const float* __restrict__ coef, int C, int HW, float* __restrict__ bcoef) {
@@ -1227,7 +1229,7 @@ int cgd_launch_gn_fwd(cgd_ctx* ctx, const float* x, int ldx, float* y, int ldy, 
     ++ctx->gn_record_merges;
     int lg = 0;
     while ((1 << lg) < C / 32) ++lg;
-    CGD_LAUNCH(gn_stats_final_ch_kernel, dim3(32, B), dim3(256), 0, s, cs, HW / 128, C / 32, lg, eps, stats, gamma, beta, film, ldfilm, coef);
+    CGD_LAUNCH(gn_stats_final_ch_kernel, dim3(32, B), dim3(256), 0, s, cs, HW, C / 32, lg, eps, stats, gamma, beta, film, ldfilm, coef);
     if (y) {
       if (act)
         CGD_LAUNCH((gn_apply_kernel<1>), dim3(nchunk, B), dim3(256), 0, s, x, ldx, y, ldy, HW, C, chunk, coef);
@@ -1303,7 +1305,7 @@ int cgd_launch_gn_bwd(cgd_ctx* ctx, const float* x, int ldx, const float* dz, in
     ++ctx->gn_record_merges;
     int lg = 0;
     while ((1 << lg) < C / 32) ++lg;
-    CGD_LAUNCH(gn_bwd_coef_ch_kernel, dim3(32, B), dim3(256), 0, s, cs.p0, HW / 128, lg, stats, coef, C, HW, bcoef);
+    CGD_LAUNCH(gn_bwd_coef_ch_kernel, dim3(32, B), dim3(256), 0, s, cs.p0, HW / cs.c0, lg, stats, coef, C, HW, bcoef);
   } else {
     if (act) {
       CGD_LAUNCH((gn_bwd_partial_kernel<1>), dim3(nchunk, B), dim3(256), 0, s, x, ldx, dz, (float*)dz, lddz, HW, C, chunk, coef, part, src);
@@ -1342,7 +1344,7 @@ int cgd_launch_gn_bwd_skip_gemm(cgd_ctx* ctx, GemmParams sk, const float* x, int
   ++ctx->gn_record_merges;
   int lg = 0;
   while ((1 << lg) < C / 32) ++lg;
-  CGD_LAUNCH(gn_bwd_coef_ch_kernel, dim3(32, B), dim3(256), 0, s, cs.p0, HW / 128, lg, stats, coef, C, HW, bcoef);
+  CGD_LAUNCH(gn_bwd_coef_ch_kernel, dim3(32, B), dim3(256), 0, s, cs.p0, HW / cs.c0, lg, stats, coef, C, HW, bcoef);
   CGD_TRY(cgd_launch_gemm(ctx, sk, s));  // (kills the records of an earlier content of dx like every GEMM)
   CGD_TRY(cgd_prof_stamp(ctx, &pr, s));
   cgd_prof_push(ctx, &pr);
@@ -1406,9 +1408,9 @@ int cgd_launch_ln_bwd(cgd_ctx* ctx, const float* x, int ldx, const float* dy, in
 }
 
 // ---- conv-epilogue statistics registry (common.h ChanStatsEntry) -----------------------------------------------------------------
-float* cgd_chanstats_register(cgd_ctx* ctx, const float* C, int ldc, int N, long M, hipStream_t s, int kind) {
-  if ((M & 127) || (N & 3)) return nullptr;
-  const size_t need = (size_t)(M / 128) * N * 2;
+float* cgd_chanstats_register(cgd_ctx* ctx, const float* C, int ldc, int N, long M, hipStream_t s, int kind, int cnt) {
+  if ((cnt != 64 && cnt != 128) || (M % cnt) || (N & 3)) return nullptr;
+  const size_t need = (size_t)(M / cnt) * N * 2;
   ChanStatsEntry* e = nullptr;
   for (ChanStatsEntry& q : ctx->chanstats)
     if (q.C == C && q.kind == kind) e = &q;
@@ -1434,7 +1436,7 @@ float* cgd_chanstats_register(cgd_ctx* ctx, const float* C, int ldc, int N, long
     e->buf = (float*)p;
     e->cap = need;
   }
-  e->ldc = ldc; e->N = N; e->M = M; e->stream = s; e->serial = ctx->stats_serial; e->kind = kind;
+  e->ldc = ldc; e->N = N; e->M = M; e->stream = s; e->serial = ctx->stats_serial; e->kind = kind; e->cnt = cnt;
   return e->buf;
 }
 
@@ -1446,11 +1448,11 @@ bool cgd_chanstats_find(cgd_ctx* ctx, const float* x, int ldx, long M, int Cn, h
   };
   const ChanStatsEntry* a = hit(x);
   if (!a || a->N > Cn) return false;
-  out->p0 = a->buf; out->n0 = a->N; out->p1 = nullptr; out->n1 = 0;
+  out->p0 = a->buf; out->n0 = a->N; out->p1 = nullptr; out->n1 = 0; out->c0 = out->c1 = a->cnt;
   if (a->N == Cn) return true;
   const ChanStatsEntry* b = hit(x + a->N);  // the skip half of a concat
   if (!b || a->N + b->N != Cn) return false;
-  out->p1 = b->buf; out->n1 = b->N;
+  out->p1 = b->buf; out->n1 = b->N; out->c1 = b->cnt;
   return true;
 }
 

@@ -206,15 +206,18 @@ _SIGS = {
     "cgd_op_gemm_gn_bwd_accepts": (i32, [i32] * 12),
     "cgd_op_gemm_gn_bwd": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp]),
     "cgd_op_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(i32)]),
+    "cgd_op_plan_conv": (i32, [i32] * 10 + [C.POINTER(i32)]),
     "cgd_op_pack_conv3x3_frag": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "cgd_set_hconv": (i32, [vp, i32, i32]),
     "cgd_op_conv3x3": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "cgd_op_conv3x3_ex": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     "cgd_op_pack_conv3x3_wino": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "cgd_op_conv3x3_wino": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_set_wino": (i32, [vp, i32, i32]),
     "cgd_op_conv3x3_wino_ex": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     "cgd_op_new_pass": (i32, [vp]),
     "cgd_op_gn_record_merges": (i64, [vp]),
+    "cgd_op_gn_records": (i32, [vp, vp, i32, i64, i32, i32, vp, i64, C.POINTER(i32), vp]),
     "cgd_op_gn_stats_offset": (i64, [i32, i32, i32]),
     "cgd_op_wconv_schedule": (i32, [i32, i32, C.POINTER(i32)]),
     "cgd_op_mfma_peak": (i32, [vp, i32, C.POINTER(C.c_double), vp]),

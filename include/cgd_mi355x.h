@@ -541,12 +541,26 @@ int cgd_op_pack_conv3x3_frag(cgd_ctx* ctx, const float* w_torch, float* out /* C
  * weight) or a conv3x3 (conv = 1: M = B*H*W pixels, N = Cout) with the default knobs: out4 = {kernel: 0 igemm_kernel, 1 hconv2_kernel,
  * 2 hgemm_kernel; tile code; split-K slices; workgroups of the main launch}.  CPU tests of the dispatch policy use it. */
 int cgd_op_plan(int conv, int M, int N, int K, int H, int W, int Cin, int weight, int precision, int num_cu, int* out4);
+/* host-only, cgd_op_plan for a 3x3 conv [Bn][H][W][Cin] -> Cout with what the UNet's ResBlocks set besides the shape: hconv_var = the tile variant
+ * bits of cgd_set_hconv; stats = 1: the launch is asked for forward GroupNorm records of its output; gnb = 1: for the backward sums of a norm (a
+ * dgrad conv).  out5 = {kernel, tile code, split-K slices, workgroups, pixels per workgroup tile of hconv2_kernel (0 on the other kernels)}. */
+int cgd_op_plan_conv(int Bn, int H, int W, int Cin, int Cout, int precision, int num_cu, int hconv_var, int stats, int gnb, int* out5);
 /* tuning knob: mode & 15 = 0 off / 1 auto (M >= min_m); mode >> 4 = tile variant bits (0: 8x16 pixels, 1: 16x16, 2: 16x16 below 16384
- * pixels, 4: wavefront sub-tile 64 pixels x 64 channels instead of the default 128 x 32) */
+ * pixels, 4: wavefront sub-tile 64 pixels x 64 channels instead of the default 128 x 32, 8: the unsplit 4x16-pixel x 128-channel tile (all
+ * of K in one workgroup) wherever the context is bf16x3 and Cout a multiple of 128, not only where the launcher picks it by itself: tests and
+ * benchmarks; other problems keep their tile) */
 int cgd_set_hconv(cgd_ctx* ctx, int mode, int min_m);
 int cgd_op_conv3x3(cgd_ctx* ctx, const float* x_nhwc, int ldx, const float* w_packed, const float* w_frag, float* y_nhwc, int ldy,
                    const float* bias, const float* R, int ldr, int Bn, int H, int W, int Cin, int Cout, int upsample_input, int force_tile,
                    int splitk, void* stream);
+/* cgd_op_conv3x3 with the add-ons the UNet's ResBlocks switch on (test support, like cgd_op_conv3x3_wino_ex below).  gn_ab: per-(sample,
+ * channel) pairs {a, b} [Bn][Cin][2]; the conv then runs on SiLU(x * a + b), applied in the patch staging (halo conv kernels only: any other
+ * route is refused).  defer = 1: a launch that splits K leaves its slices to the cgd_op_gn_fwd / cgd_op_gn_bwd that reads y next.  stats,
+ * gnb_x, gnb_ldx, gnb_scratch: as in cgd_op_conv3x3_wino_ex. */
+int cgd_op_conv3x3_ex(cgd_ctx* ctx, const float* x_nhwc, int ldx, const float* w_packed, const float* w_frag, float* y_nhwc, int ldy,
+                      const float* bias, const float* R, int ldr, const float* gn_ab, int Bn, int H, int W, int Cin, int Cout,
+                      int upsample_input, int force_tile, int splitk, int defer, int stats, const float* gnb_x, int gnb_ldx,
+                      const float* gnb_scratch, void* stream);
 /* Winograd F(2,3)-along-W variant of the halo conv (wconv.hip; H a multiple of 8, W of 16; bf16x3 products, or — round 6 — exact fp32 products
  * in precision-0 contexts: wconv_kernel<..., F32> on v_mfma_f32_32x32x2_f32): w_wino = the torch weights transformed and packed by
  * cgd_op_pack_conv3x3_wino (Co*Ci*12 floats of storage) FOR THE CONTEXT'S CURRENT PRECISION MODE (fp32 values or bf16 hi / lo planes: pack and
@@ -573,6 +587,10 @@ int cgd_op_new_pass(cgd_ctx* ctx);
 /* number of GroupNorm launches since context creation that MERGED conv-epilogue records (forward statistics + backward sums) instead of
  * sweeping their input: lets a test assert which path a cgd_op_gn_fwd / cgd_op_gn_bwd call took */
 int64_t cgd_op_gn_record_merges(cgd_ctx* ctx);
+/* test support: copies the live records of the current pass for tensor y (`rows` rows of C floats at row stride ldy, written on `stream`), as ONE conv
+ * launch left them, to the device buffer out (cap floats): [rows / *pixels][C][2], kind 0 = (mean, M2) of the *pixels values of every (tile, channel),
+ * kind 1 = the backward sums (gcoef sum du, gcoef sum du (x - mean)); *pixels = 0 and nothing copied when the tensor has none */
+int cgd_op_gn_records(cgd_ctx* ctx, const float* y, int ldy, int64_t rows, int C, int kind, float* out, int64_t cap, int* pixels, void* stream);
 /* host-only: float offset of the per-(sample, group) statistics {mean, rstd} [B][32][2] inside a cgd_op_gn_fwd scratch buffer (tests compare
  * them with float64 group statistics) */
 int64_t cgd_op_gn_stats_offset(int B, int HW, int C);

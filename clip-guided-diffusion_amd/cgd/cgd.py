@@ -37,6 +37,9 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
     # "dpmN+thr=P[:CAP]" (an extension like "plmsN"): dynamic thresholding of the guided pred_xstart; refused on any other spacing, before
     # anything is loaded.  The tables are built from the spacing without the suffix
     timestep_respacing, threshold = script_util.split_threshold(timestep_respacing)
+    # "upsample=IMAGE" (an extension like "invert=IMAGE"): run the super-resolution checkpoint of image_size on IMAGE; refused before
+    # anything is loaded at other sizes, without class conditioning, or together with "invert="
+    upsample = script_util.check_init_upsample(init_image, image_size, class_cond)
     if init_image and script_util.split_init_invert(script_util.split_init_mask(init_image)[0])[1]:
         # refused before anything is loaded
         # the inverted latent is a start state of the deterministic loops only ('dpmsdeN' draws a noise per step; tested before 'dpm')
@@ -73,7 +76,10 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         tqdm.write("64x64 checkpoint: gradient-magnitude clamp switched on")
     Path(prefix_path).mkdir(parents=True, exist_ok=True)
     Path(checkpoints_dir).mkdir(parents=True, exist_ok=True)
-    diffusion_path = script_util.download_guided_diffusion(image_size=image_size, checkpoints_dir=checkpoints_dir, class_cond=class_cond)
+    if upsample:
+        diffusion_path = script_util.download_upsampler(image_size, checkpoints_dir)
+    else:
+        diffusion_path = script_util.download_guided_diffusion(image_size=image_size, checkpoints_dir=checkpoints_dir, class_cond=class_cond)
 
     # CLIP tower(s), prompt embeddings and weights.  "A+B" (e.g. "RN50+ViT-L/14", BASELINE config 5) sums the CLIP losses of
     # several towers: a build extension, the reference takes a single name.
@@ -137,8 +143,14 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         init_image, mask_image = script_util.split_init_mask(init_image)
         # "invert=IMAGE": start from the image's own DDIM-inverted latent instead of the image plus random noise
         init_image, invert = script_util.split_init_invert(init_image)
-        pil = Image.open(script_util.fetch(init_image)).convert("RGB").resize((image_size, image_size))
+        # "upsample=IMAGE": IMAGE at a quarter of the frame conditions the super-resolution model; at the full frame it stays the init image
+        init_image, _ = script_util.split_init_upsample(init_image)
+        source = Image.open(script_util.fetch(init_image)).convert("RGB")
+        pil = source.resize((image_size, image_size))
         init_tensor = th.from_numpy(np.array(pil)).float().div(255).permute(2, 0, 1).to(device).unsqueeze(0).mul(2).sub(1)
+        if upsample:
+            small = source.resize(((image_size + width_offset) // 4, (image_size + height_offset) // 4))
+            low_res_tensor = th.from_numpy(np.array(small)).float().div(255).permute(2, 0, 1).to(device).unsqueeze(0).mul(2).sub(1)
         if mask_image is not None:
             pil = Image.open(script_util.fetch(mask_image)).convert("L").resize((image_size, image_size))
             mask_tensor = th.from_numpy(np.array(pil)).float().div(255).to(device)[None, None]
@@ -153,9 +165,16 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
     if class_cond:
         model_kwargs["y"] = th.zeros([local_batch], device=device, dtype=th.long)
 
-    gd_model, diffusion = script_util.load_guided_diffusion(
-        checkpoint_path=diffusion_path, image_size=image_size, class_cond=class_cond, diffusion_steps=diffusion_steps,
-        timestep_respacing=timestep_respacing, use_fp16=True, device=device, noise_schedule=noise_schedule, dropout=dropout)
+    if upsample:
+        # one image for the whole batch (the handle broadcasts it); the sampler hands it to the model once per loop
+        model_kwargs["low_res"] = low_res_tensor
+        gd_model, diffusion = script_util.load_upsampler(
+            checkpoint_path=diffusion_path, large_size=image_size, diffusion_steps=diffusion_steps, timestep_respacing=timestep_respacing,
+            device=device, noise_schedule=noise_schedule, dropout=dropout)
+    else:
+        gd_model, diffusion = script_util.load_guided_diffusion(
+            checkpoint_path=diffusion_path, image_size=image_size, class_cond=class_cond, diffusion_steps=diffusion_steps,
+            timestep_respacing=timestep_respacing, use_fp16=True, device=device, noise_schedule=noise_schedule, dropout=dropout)
     # (a collective like the loads above: before the early return of a rank without samples)
     secondary = clip_util.load_secondary(gd_model.ctx, secondary_path, device) if secondary_path is not None else None
     classifier = None
@@ -280,7 +299,7 @@ _CLI_SPEC = f"""
 --prompts -txts str "" | text prompts with optional weights, pipe-separated: 'a cat:0.5|a dog:-0.5'; 'SOURCE CAPTION=>TARGET CAPTION[:weight]' is a direction prompt (needs --init_image): the change of the image's CLIP embedding relative to the init image is steered along the change from the source to the target caption (e.g. 'a photo of a cat=>a photo of a dog:1.5'); weights of all prompts are normalised together
 --image_prompts -imgs str "" | image prompts (paths or URLs) with optional weights, pipe-separated
 --image_size -size int 128 | resolution of the diffusion checkpoint: 64, 128, 256 or 512
---init_image -init str "" | start from this image (needs --skip_timesteps); IMAGE::MASK regenerates the white part of MASK and keeps the black part of IMAGE; invert=IMAGE (or invert=IMAGE::MASK, with -respace ddimN / plmsN / dpmN) starts from the DDIM-inverted latent of IMAGE; in every form IMAGE is also the source image of 'SOURCE=>TARGET' direction prompts
+--init_image -init str "" | start from this image (needs --skip_timesteps); IMAGE::MASK regenerates the white part of MASK and keeps the black part of IMAGE; invert=IMAGE (or invert=IMAGE::MASK, with -respace ddimN / plmsN / dpmN) starts from the DDIM-inverted latent of IMAGE; upsample=IMAGE (or upsample=IMAGE::MASK, with --image_size 256 or 512, not with --uncond or invert=) runs the 64->256 / 128->512 super-resolution checkpoint conditioned on IMAGE at a quarter of the frame, IMAGE at the full frame staying the init image; in every form IMAGE is also the source image of 'SOURCE=>TARGET' direction prompts
 --init_scale -is int 0 | weight of the LPIPS-VGG16 term that keeps the sample close to the init image
 --skip_timesteps -skip int 0 | how many of the (respaced) timesteps to skip at the noisy end
 --prefix -dir path outputs | directory for the PNG frames

@@ -30,6 +30,24 @@ DIFFUSION_LOOKUP = {
     },
 }
 
+
+def _upsampler(large, small, **delta):
+    url = _OPENAI + f"{small}_{large}_upsampler.pt"
+    flags = dict(_BASE, class_cond=True, large_size=large, small_size=small, num_channels=192, channel_mult=(1, 1, 2, 2, 4, 4))
+    flags.update(delta)
+    return {"url": url, "filename": url.rsplit("/", 1)[-1], "model_flags": flags}
+
+
+# guided-diffusion's super-resolution checkpoints (SuperResModel: a UNet with a 6-channel stem that reads x_t and the bilinearly upsampled
+# low-resolution image), keyed by large_size.  A table of its own: DIFFUSION_LOOKUP mirrors the reference's table, which has no upsamplers.
+# Written from memory of upstream's README flags and sr_create_model (channel_mult (1,1,2,2,4,4) at both sizes; the attention downsample
+# rates are large_size // resolution).  No checkpoint was at hand to confirm it: script_util.check_upsampler_state_dict compares every
+# shape of a loaded state dict with the manifest these flags give, and refuses a mismatch by name.
+UPSAMPLER_LOOKUP = {
+    256: _upsampler(256, 64, attention_resolutions="32,16,8", num_heads=4),
+    512: _upsampler(512, 128, attention_resolutions="32,16", num_head_channels=64),
+}
+
 # upstream guided_diffusion.script_util.model_and_diffusion_defaults()
 MODEL_AND_DIFFUSION_DEFAULTS = dict(
     image_size=64, num_channels=128, num_res_blocks=2, num_heads=4, num_heads_upsample=-1, num_head_channels=-1,

@@ -21,7 +21,7 @@ from cgd_amd import shard as _shard
 from cgd_amd import sampler as _sampler
 from cgd_amd import synthetic as _synthetic
 
-from .model_flags import DIFFUSION_LOOKUP, MODEL_AND_DIFFUSION_DEFAULTS
+from .model_flags import DIFFUSION_LOOKUP, MODEL_AND_DIFFUSION_DEFAULTS, UPSAMPLER_LOOKUP
 
 CACHE_PATH = os.path.expanduser("~/.cache/clip-guided-diffusion")
 TIMESTEP_RESPACINGS = tuple(p + n for p in ("", "ddim") for n in ("25", "50", "100", "250", "500", "1000"))
@@ -97,6 +97,44 @@ def split_init_invert(image_part):
     if not image:
         raise ValueError(f"init image {image_part!r}: 'invert=IMAGE' needs an image")
     return image, True
+
+
+UPSAMPLE_PREFIX = "upsample="
+
+
+def split_init_upsample(image_part):
+    """'upsample=IMAGE' -> (IMAGE, True); anything else -> (value, False).  Takes the image part split_init_mask returns, next to
+    split_init_invert: the request to run a super-resolution checkpoint on IMAGE rides on --init_image / init_image=, like the mask
+    ('upsample=IMAGE::MASK').  IMAGE at a quarter of the frame conditions the model; at the full frame it stays the ordinary init image."""
+    image_part = str(image_part)
+    if not image_part.startswith(UPSAMPLE_PREFIX):
+        return image_part, False
+    image = image_part[len(UPSAMPLE_PREFIX):]
+    if not image:
+        raise ValueError(f"init image {image_part!r}: 'upsample=IMAGE' needs an image")
+    return image, True
+
+
+def check_init_upsample(init_image, image_size, class_cond):
+    """Whether `init_image` asks for super-resolution ('upsample=IMAGE[::MASK]'), after refusing, before anything is loaded, what is not
+    built: other sizes than the two published upsamplers', the unconditional flag (both upsamplers are class-conditional), and
+    'invert=' together with 'upsample=' in either order (the inversion loop of the drop-in generator runs unconditioned)."""
+    if not init_image:
+        return False
+    part = split_init_mask(init_image)[0]
+    image, upsample = split_init_upsample(part)
+    inverted, invert = split_init_invert(part)
+    if (upsample and image.startswith(INVERT_PREFIX)) or (invert and inverted.startswith(UPSAMPLE_PREFIX)):
+        raise ValueError(f"init image {init_image!r}: 'invert=' and 'upsample=' cannot be combined (inversion under a low-resolution "
+                         "condition is not built)")
+    if not upsample:
+        return False
+    if image_size not in UPSAMPLER_LOOKUP:
+        raise ValueError(f"init image 'upsample=...' needs image_size {' or '.join(str(s) for s in sorted(UPSAMPLER_LOOKUP))} (the published "
+                         f"64->256 and 128->512 upsamplers), got {image_size}")
+    if not class_cond:
+        raise ValueError("init image 'upsample=...' does not work with --uncond: both upsamplers are class-conditional")
+    return True
 
 
 DIRECTION_SEP = "=>"
@@ -265,6 +303,82 @@ def unet_kwargs(cfg):
                 attention_resolutions=cfg["attention_resolutions"].replace(" ", ""), channel_mult=None,
                 num_classes=1000 if cfg["class_cond"] else None, num_heads=cfg["num_heads"], num_head_channels=cfg["num_head_channels"],
                 use_new_attention_order=cfg["use_new_attention_order"], out_channels=6 if cfg["learn_sigma"] else 3)
+
+
+def upsampler_config(large_size, diffusion_steps=None, timestep_respacing=None, use_fp16=True, noise_schedule="linear", dropout=0.0):
+    """model_config for the super-resolution checkpoint of `large_size` (UPSAMPLER_LOOKUP): upstream's defaults, the checkpoint's flags,
+    then the user-level overrides."""
+    cfg = dict(MODEL_AND_DIFFUSION_DEFAULTS)
+    cfg.update(UPSAMPLER_LOOKUP[large_size]["model_flags"])
+    cfg.update(diffusion_steps=diffusion_steps or cfg["diffusion_steps"], timestep_respacing=timestep_respacing, use_fp16=use_fp16,
+               noise_schedule=noise_schedule, dropout=dropout)
+    return cfg
+
+
+def upsampler_unet_kwargs(cfg):
+    """upstream's sr_create_model flags -> the device UNet's constructor arguments: the UNet of large_size with its own channel_mult and
+    a 6-channel stem (x_t and the upsampled low-resolution image)."""
+    return dict(image_size=cfg["large_size"], model_channels=cfg["num_channels"], num_res_blocks=cfg["num_res_blocks"],
+                attention_resolutions=cfg["attention_resolutions"].replace(" ", ""), channel_mult=tuple(cfg["channel_mult"]),
+                num_classes=1000 if cfg["class_cond"] else None, num_heads=cfg["num_heads"], num_head_channels=cfg["num_head_channels"],
+                use_new_attention_order=cfg["use_new_attention_order"], in_channels=6, out_channels=6 if cfg["learn_sigma"] else 3)
+
+
+def check_upsampler_state_dict(sd, specs, what="upsampler"):
+    """Every tensor of a loaded state dict against the manifest `specs` ([(name, numel)]: nets.manifest / UNet.param_specs) of the flag
+    table, which was written without a checkpoint at hand: a missing or unknown key, a wrong element count or a stem that is not
+    [ch0, 6, 3, 3] is a ValueError that names the tensor, before anything is uploaded."""
+    specs = dict(specs)
+    missing = [k for k in specs if k not in sd]
+    if missing:
+        raise ValueError(f"{what}: the checkpoint lacks {len(missing)} tensors the flag table expects, first {missing[0]!r}")
+    extra = [k for k in sd if k not in specs]
+    if extra:
+        raise ValueError(f"{what}: the checkpoint has {len(extra)} tensors the flag table does not expect, first {extra[0]!r}")
+    for name, numel in specs.items():
+        if sd[name].numel() != numel:
+            raise ValueError(f"{what}: {name} has shape {tuple(sd[name].shape)} ({sd[name].numel()} elements), the flag table expects {numel}")
+    stem = sd["input_blocks.0.0.weight"]
+    if stem.dim() != 4 or tuple(stem.shape[1:]) != (6, 3, 3):
+        raise ValueError(f"{what}: input_blocks.0.0.weight has shape {tuple(stem.shape)}, a super-resolution stem is [ch0, 6, 3, 3]")
+
+
+def download_upsampler(large_size: int, checkpoints_dir: str = CACHE_PATH) -> str:
+    """Path of the super-resolution checkpoint, found by name in `checkpoints_dir` (downloaded there when absent, as the base models are)."""
+    info = UPSAMPLER_LOOKUP[large_size]
+    target = Path(checkpoints_dir) / info["filename"]
+    if synthetic_weights_enabled():
+        return str(target)
+    return _shard.on_rank0(lambda: str(target) if target.exists() else _download(info["url"], info["filename"], checkpoints_dir, 3))
+
+
+@lru_cache(maxsize=1)
+def load_upsampler(checkpoint_path: str, large_size: int, diffusion_steps: int = None, timestep_respacing: str = None, device: str = "",
+                   noise_schedule: str = "linear", dropout: float = 0.0):
+    """-> (model, diffusion) like load_guided_diffusion, for the super-resolution checkpoint of `large_size`: the model is a 6-channel
+    nets.UNet, conditioned by model.set_low_res (the sampler does that from model_kwargs["low_res"])."""
+    if not (len(device) > 0):
+        raise ValueError("device must be set")
+    cfg = upsampler_config(large_size, diffusion_steps, timestep_respacing, True, noise_schedule, dropout)
+    ctx = get_context(device)
+    model = _nets.UNet(ctx, **upsampler_unet_kwargs(cfg))
+    dev = f"cuda:{ctx.device}"
+
+    def read():
+        sd = th.load(checkpoint_path, map_location="cpu")
+        check_upsampler_state_dict(sd, model.param_specs(), os.path.basename(checkpoint_path))
+        return sd
+
+    if os.path.isfile(checkpoint_path):
+        _shard.load_broadcast(model, read, dev)
+    elif synthetic_weights_enabled():
+        _shard.load_broadcast(model, lambda: _synthetic.synthetic_state_dict(model, seed=1234, device=dev), dev)
+    else:
+        raise FileNotFoundError(f"{checkpoint_path} not found (set CGD_SYNTHETIC_WEIGHTS=1 for seeded random weights)")
+    tables = _diffusion.create_gaussian_diffusion(steps=cfg["diffusion_steps"], noise_schedule=cfg["noise_schedule"],
+                                                  timestep_respacing=cfg["timestep_respacing"] or "",
+                                                  rescale_timesteps=cfg["rescale_timesteps"])
+    return model, _sampler.GuidedSampler(ctx, tables)
 
 
 @lru_cache(maxsize=1)

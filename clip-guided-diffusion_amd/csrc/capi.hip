@@ -520,6 +520,11 @@ int cgd_op_conv_in(cgd_ctx* ctx, const float* x, const float* w, const float* bi
   CGD_NEED_CTX(ctx);
   return cgd_launch_conv_in(ctx, x, w, bias, y, Bn, H, W, Cin, Cout, S(stream));
 }
+int cgd_op_sr_stem(cgd_ctx* ctx, const float* x, const float* low, int B_low, int h, int w, const float* wpacked, const float* bias, float* y,
+                   int ldy, int B, int H, int W, int Cout, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_sr_stem(ctx, x, low, B_low, h, w, wpacked, bias, y, ldy, B, H, W, Cout, S(stream));
+}
 int cgd_op_conv_thin_out(cgd_ctx* ctx, const float* x, int ldx, const float* w, const float* bias, float* y, int Bn, int H, int W,
                          int Cin, int Cout, void* stream) {
   CGD_NEED_CTX(ctx);

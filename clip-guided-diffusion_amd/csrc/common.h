@@ -400,3 +400,7 @@ int cgd_launch_conv_in(cgd_ctx* ctx, const float* x_nchw, const float* w /*[Cout
                        float* y_nhwc, int Bn, int H, int W, int Cin, int Cout, hipStream_t s, int ldy = 0 /*row stride, 0 = Cout*/);
 int cgd_launch_conv_thin_out(cgd_ctx* ctx, const float* x_nhwc, int ldx, const float* w /*[Cout][9*Cin]*/, const float* bias,
                              float* y_nchw, int Bn, int H, int W, int Cin, int Cout, hipStream_t s);
+// the conditioned stem of the super-resolution UNets (superres.hip): conv3x3(cat(x, bilinear(low -> H x W)), w, bias) in one launch
+int cgd_launch_sr_stem(cgd_ctx* ctx, const float* x_nchw, const float* low /*(B_low,3,lh,lw)*/, int B_low, int lh, int lw,
+                       const float* w /*[Cout][3][3][6] (co,ky,kx,ci)*/, const float* bias, float* y_nhwc, int ldy /*0 = Cout*/, int Bn, int H,
+                       int W, int Cout, hipStream_t s);

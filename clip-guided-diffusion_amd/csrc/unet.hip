@@ -122,9 +122,13 @@ struct UNet : NetBase {
   std::vector<int> cat_c1;      // channels of the h part
   std::vector<std::pair<int, int>> cat_hw;
   TV head_in;
+  // super-resolution handles (in_channels 6): the low-resolution image that conditions every forward (set_low_res), (low_B,3,low_h,low_w)
+  DevBuf low;
+  int low_B = 0, low_h = 0, low_w = 0;
 
   int build();
   int finalize(hipStream_t s);
+  int set_low_res(const float* img, int B_low, int h, int w, hipStream_t s);
   int embed(const float* t, const int64_t* y, int Bn, int slot, hipStream_t s, bool ahead = false);
   int forward(const float* x, const float* t, const int64_t* y, float* out, int B, int H, int W, hipStream_t s, int slot = -1);
   int dgrad(const float* gout, float* gx, hipStream_t s);
@@ -376,7 +380,8 @@ int UNet::build() {
   const int mc = cfg.model_channels;
   // configuration checks first (found by the host-sanitizer driver, tests/asan_host_driver.cpp: an empty channel_mult list used to
   // "build" a model without levels): everything the plan below divides by or indexes with
-  if (cfg.in_channels != 3 || (!encoder_only && cfg.out_channels != 6 && cfg.out_channels != 3)) CGD_FAIL(ctx, "unet: in_channels must be 3, out_channels 3 or 6");
+  if ((cfg.in_channels != 3 && (cfg.in_channels != 6 || encoder_only)) || (!encoder_only && cfg.out_channels != 6 && cfg.out_channels != 3))
+    CGD_FAIL(ctx, "unet: in_channels must be 3 (or 6: a super-resolution UNet), out_channels 3 or 6");
   if (cfg.n_mult < 1 || cfg.n_mult > 8) CGD_FAIL(ctx, "unet: bad channel_mult");
   if (cfg.n_att < 0 || cfg.n_att > 8) CGD_FAIL(ctx, "unet: at most 8 attention resolutions");
   if (mc <= 0 || mc % 32) CGD_FAIL(ctx, "unet: model_channels must be a positive multiple of 32 (GroupNorm32)");
@@ -640,12 +645,30 @@ int UNet::embed(const float* t, const int64_t* y, int Bn, int slot, hipStream_t 
   return 0;
 }
 
+// The low-resolution image of a super-resolution handle: copied, in stream order, into the handle's own buffer (grow-only, as every
+// other buffer), so that the caller's tensor need not outlive the call; it conditions every forward until it is replaced.
+int UNet::set_low_res(const float* img, int B_low, int h, int w, hipStream_t s) {
+  if (cfg.in_channels != 6) CGD_FAIL(ctx, "unet: set_low_res needs a super-resolution handle (in_channels 6); this one takes 3 channels");
+  if (!img) CGD_FAIL(ctx, "unet: set_low_res: the image is required");
+  if (B_low <= 0 || h <= 0 || w <= 0) CGD_FAIL(ctx, "unet: set_low_res: the image must be (B_low,3,h,w) with B_low, h, w >= 1");
+  const size_t n = (size_t)B_low * 3 * h * w;
+  CGD_TRY(ensure(low, n));
+  CGD_HIP(ctx, hipMemcpyAsync(low.p, img, n * sizeof(float), hipMemcpyDefault, s));
+  low_B = B_low; low_h = h; low_w = w;
+  return 0;
+}
+
 // slot < 0: the embedding head runs here, on `s`, into slot 0 (the plain model(x, t, y) call); slot 0 / 1: a preceding embed(t, y, B, slot) did it
 int UNet::forward(const float* x, const float* t, const int64_t* y, float* out, int Bn, int Hh, int Ww, hipStream_t s, int slot) {
   if (!finalized) CGD_FAIL(ctx, "unet: finalize() has not been called after the last set_param");
   const int levels = cfg.n_mult - 1;
   if ((Hh % (1 << levels)) || (Ww % (1 << levels))) CGD_FAIL(ctx, "unet: H and W must be divisible by 2^(levels-1)");
   if (slot > 1) CGD_FAIL(ctx, "unet: embedding slot must be 0 or 1");
+  if (cfg.in_channels == 6) {
+    if (!low_B) CGD_FAIL(ctx, "unet: a super-resolution handle needs its low-resolution image before forward(): call set_low_res first");
+    if (low_B != 1 && low_B != Bn)
+      CGD_FAIL(ctx, "unet: the low-resolution image has batch " + std::to_string(low_B) + ", forward() has " + std::to_string(Bn) + ": it must be 1 or equal");
+  }
   if (slot < 0) {
     CGD_TRY(embed(t, y, Bn, 0, s));
     slot = 0;
@@ -682,7 +705,10 @@ int UNet::forward(const float* x, const float* t, const int64_t* y, float* out, 
   const size_t klast = out_blocks.size() - 1;
   float* const h0p = cats[klast].p + cat_c1[klast];
   const int h0ld = cat_in[klast].ld;
-  CGD_TRY(cgd_launch_conv_in(ctx, x, stem_wf, P("input_blocks.0.0.bias"), h0p, B, H, W, cfg.in_channels, ch0, s, h0ld));
+  if (cfg.in_channels == 6)  // x (B,3,H,W) + the low-resolution image, upsampled while the stem stages its patch: no (B,6,H,W) tensor
+    CGD_TRY(cgd_launch_sr_stem(ctx, x, low.p, low_B, low_h, low_w, stem_wf, P("input_blocks.0.0.bias"), h0p, h0ld, B, H, W, ch0, s));
+  else
+    CGD_TRY(cgd_launch_conv_in(ctx, x, stem_wf, P("input_blocks.0.0.bias"), h0p, B, H, W, cfg.in_channels, ch0, s, h0ld));
   hs.clear(); hs_hw.clear();
   TV h{h0p, h0ld, ch0};
   int ch = H, cw = W;
@@ -738,8 +764,9 @@ int UNet::dgrad(const float* gout, float* gx, hipStream_t s) {
   for (int j = (int)mid.size() - 1; j >= 0; --j) CGD_TRY(mid[j]->bwd(*this, d, &d, s));
   for (int i = n - 1; i >= 1; --i)
     for (int j = (int)in_blocks[i].size() - 1; j >= 0; --j) CGD_TRY(in_blocks[i][j]->bwd(*this, d, &d, s));
-  // stem dgrad: NHWC (ch0) -> NCHW (in_channels)
-  CGD_TRY(cgd_launch_conv_thin_out(ctx, d.p, d.ld, stem_wd, nullptr, gx, B, H, W, ch0, cfg.in_channels, s));
+  // stem dgrad: NHWC (ch0) -> NCHW (3).  Only d/dx exists: on a super-resolution handle the dgrad weights [6][9 * ch0] start with the
+  // three rows of weight[:, 0:3], and the conditioning planes get no gradient
+  CGD_TRY(cgd_launch_conv_thin_out(ctx, d.p, d.ld, stem_wd, nullptr, gx, B, H, W, ch0, 3, s));
   return 0;
 }
 
@@ -918,6 +945,11 @@ int cgd_unet_forward_slot(cgd_unet* u, const float* x, int slot, float* out, int
 }
 int cgd_unet_dgrad(cgd_unet* u, const float* g_out, float* g_x, void* stream) {
   return net_pass(u, stream, [&](hipStream_t s) { return u->net.dgrad(g_out, g_x, s); });
+}
+int cgd_unet_set_low_res(cgd_unet* u, const float* low, int B_low, int h, int w, void* stream) {
+  if (!u) return -3;
+  DeviceScope dev_scope(u->net.ctx);
+  return u->net.set_low_res(low, B_low, h, w, (hipStream_t)stream);
 }
 }
 

@@ -1000,8 +1000,9 @@ class ClipGuidance:
         return out
 
     # -- reference plugin signature ----------------------------------------------------------------------
-    def __call__(self, x, t, out, y=None):
-        """cond_fn(x, t, out, y=None): `out['pred_xstart']` must come from the last `unet.forward(x, ...)`."""
+    def __call__(self, x, t, out, y=None, low_res=None):
+        """cond_fn(x, t, out, y=None): `out['pred_xstart']` must come from the last `unet.forward(x, ...)`.  `low_res` (super-resolution
+        sampling hands the whole model_kwargs to cond_fn, as upstream does) is accepted and ignored."""
         coef = self.diffusion.step_coef(int(t.flatten()[0].item()), self.fac_index())
         x = x.detach().contiguous().float()
         x0 = out["pred_xstart"].detach().contiguous().float()

@@ -110,6 +110,7 @@ _SIGS = {
     "cgd_unet_embed": (i32, [vp, vp, vp, i32, i32, vp]),
     "cgd_unet_forward_slot": (i32, [vp, vp, i32, vp, i32, i32, i32, vp]),
     "cgd_unet_dgrad": (i32, [vp, vp, vp, vp]),
+    "cgd_unet_set_low_res": (i32, [vp, vp, i32, i32, i32, vp]),
     "cgd_vit_create": (i32, [vp, C.POINTER(ViTConfig), C.POINTER(vp)]),
     "cgd_vit_destroy": (None, [vp]),
     "cgd_vit_num_params": (i32, [vp]),
@@ -223,6 +224,7 @@ _SIGS = {
     "cgd_op_mfma_peak": (i32, [vp, i32, C.POINTER(C.c_double), vp]),
     "cgd_op_conv_in": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "cgd_op_conv_thin_out": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "cgd_op_sr_stem": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "cgd_op_gn_scratch_floats": (i64, [i32, i32, i32]),
     "cgd_op_gn_fwd": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, i32, f32, vp, vp]),
     "cgd_op_gn_bwd": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, vp]),

@@ -117,6 +117,7 @@ class UNet(_Net):
                                num_head_channels, use_new_attention_order, in_channels, out_channels)
         self.cfg = cfg
         self.num_classes = num_classes
+        self.in_channels = in_channels
         self.out_channels = out_channels
         h = C.c_void_p()
         ctx.check(ctx.lib.cgd_unet_create(ctx.h, C.byref(cfg), C.byref(h)))
@@ -142,6 +143,18 @@ class UNet(_Net):
         cfg.use_new_attention_order = int(bool(use_new_attention_order))
         cfg.in_channels, cfg.out_channels = in_channels, out_channels
         return cfg
+
+    def set_low_res(self, low_res):
+        """Super-resolution handles (in_channels=6; guided-diffusion's SuperResModel): the low-resolution image, (1 or B,3,h,w) in [-1,1],
+        that conditions every later forward until it is replaced.  The forward upsamples it bilinearly to x's frame and feeds
+        cat([x, upsampled]) to the stem, in one launch; x stays (B,3,H,W) and dgrad returns (B,3,H,W).  The handle keeps its own copy."""
+        if not th.is_tensor(low_res) or low_res.dim() != 4 or low_res.shape[1] != 3 or 0 in low_res.shape:
+            raise ValueError(f"low_res must be (1 or B, 3, h, w), got {tuple(low_res.shape) if th.is_tensor(low_res) else type(low_res).__name__}")
+        low = low_res.detach().to(device=f"cuda:{self.ctx.device}", dtype=th.float32).contiguous()
+        n, _, h, w = low.shape
+        self.ctx.check(self.ctx.lib.cgd_unet_set_low_res(self.h, low.data_ptr(), n, h, w, self.ctx.stream()))
+        self._keep_low = low  # the copy is enqueued on the stream: the source outlives it here
+        return self
 
     def forward(self, x, timesteps, y=None, out=None):
         """x (B,3,H,W) fp32 NCHW on the GPU; timesteps (B,) (any dtype; converted to fp32); y (B,) int64."""

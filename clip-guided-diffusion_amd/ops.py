@@ -160,6 +160,28 @@ def conv_in(ctx, x_nchw, w_packed, bias, cout):
     return y
 
 
+def sr_stem(ctx, x_nchw, low, w_packed, bias=None, out=None):
+    """The conditioned stem of the super-resolution UNets in one launch: conv3x3(cat([x, bilinear(low -> H x W)], 1), w, bias).
+    x (B,3,H,W) and low (1 or B,3,h,w) NCHW, contiguous (offset views are fine); w_packed [Cout, 54] as pack_conv3x3 leaves the
+    [Cout,6,3,3] weight; `out` (B,H,W,Cout) NHWC may be a channel slice.  No (B,6,H,W) tensor is formed."""
+    if x_nchw.dim() != 4 or x_nchw.shape[1] != 3:
+        raise ValueError(f"x: expected (B,3,H,W), got {tuple(x_nchw.shape)}")
+    Bn, _, H, W = x_nchw.shape
+    if low.dim() != 4 or low.shape[1] != 3 or low.shape[0] not in (1, Bn) or 0 in low.shape:
+        raise ValueError(f"low: expected (1 or {Bn},3,h,w), got {tuple(low.shape)}")
+    if w_packed.dim() != 2 or w_packed.shape[1] != 54:
+        raise ValueError(f"w_packed: expected [Cout, 54], got {tuple(w_packed.shape)}")
+    cout = w_packed.shape[0]
+    px, pl, pw, pbias = _dense(x_nchw, "x"), _dense(low, "low"), _dense(w_packed, "w_packed"), _dense(bias, "bias")
+    if out is None:
+        out = th.empty((Bn, H, W, cout), device=x_nchw.device, dtype=th.float32)
+    elif tuple(out.shape) != (Bn, H, W, cout):
+        raise ValueError(f"out: expected {(Bn, H, W, cout)}, got {tuple(out.shape)}")
+    po, ldo = _rows(out, "out")
+    ctx.check(ctx.lib.cgd_op_sr_stem(ctx.h, px, pl, low.shape[0], low.shape[2], low.shape[3], pw, pbias, po, ldo, Bn, H, W, cout, _s()))
+    return out
+
+
 def conv_thin_out(ctx, x_nhwc, w_packed, bias, cout):
     """x (B,H,W,Cin) NHWC, may be a channel slice -> y (B,cout,H,W) NCHW"""
     Bn, H, W, Cin = x_nhwc.shape

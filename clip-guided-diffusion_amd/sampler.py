@@ -121,6 +121,19 @@ class GuidedSampler:
         idx, gb = self.shard
         return th.randn((gb,) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype)[idx].contiguous()
 
+    def _set_low_res(self, model, model_kwargs):
+        """Super-resolution sampling (upstream's super_res_sample puts the image into model_kwargs["low_res"]): once per loop, before the
+        first forward, the image goes to the model's handle, which conditions every forward of the loop on it.  Under sharding a
+        low_res of the global batch is cut to this rank's rows.  Without "low_res" nothing happens."""
+        low = model_kwargs.get("low_res") if model_kwargs else None
+        if low is None:
+            return
+        if not hasattr(model, "set_low_res"):
+            raise ValueError('model_kwargs["low_res"] needs a super-resolution model (nets.UNet(in_channels=6): set_low_res)')
+        if self.shard is not None and low.shape[0] == self.shard[1] and low.shape[0] != 1:
+            low = low[self.shard[0]]
+        model.set_low_res(low)
+
     # ---- one step -------------------------------------------------------------------------------------
     def _evaluate(self, model, x, i, cond_fn, model_kwargs, noise, bufs, ahead=None, draw_noise=True, draw_known=False):
         """One guided evaluation at (x, i): UNet forward -> p_mean_variance tail + blend -> (noise draw) -> cond_fn.  Returns the pieces
@@ -403,6 +416,7 @@ class GuidedSampler:
             img = float(self.tables.sqrt_alphas_cumprod[t0]) * init_image.to(device).float() + \
                 float(self.tables.sqrt_one_minus_alphas_cumprod[t0]) * img
         model_kwargs = dict(model_kwargs or {})
+        self._set_low_res(model, model_kwargs)
         it = indices
         if progress:
             from tqdm.auto import tqdm
@@ -579,6 +593,7 @@ class GuidedSampler:
         ctx, lib = self.ctx, self.ctx.lib
         init = image.to(device).float().contiguous()
         B, _, H, W = init.shape
+        self._set_low_res(model, model_kwargs)
         tt = th.tensor([float(self.tables.model_timestep(k)) for k in range(t0)], dtype=th.float32,
                        device=device).view(-1, 1).repeat(1, B).contiguous()
         y = model_kwargs.get("y")

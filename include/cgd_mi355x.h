@@ -71,7 +71,7 @@ typedef struct cgd_unet_config {
   int num_heads;
   int num_head_channels;   /* -1: use num_heads */
   int use_new_attention_order;
-  int in_channels;         /* 3 */
+  int in_channels;         /* 3, or 6: a super-resolution UNet, x (3) + the upsampled low-resolution image (3) */
   int out_channels;        /* 6 (learn_sigma) */
 } cgd_unet_config;
 
@@ -101,6 +101,12 @@ int cgd_unet_embed(cgd_unet* u, const float* timesteps, const int64_t* y, int B,
 int cgd_unet_forward_slot(cgd_unet* u, const float* x, int slot, float* out, int B, int H, int W, void* stream);
 /* d(sum(out * g_out))/dx of the LAST forward: replaces the UNet leg of th.autograd.grad(loss, x), cgd.py:228 */
 int cgd_unet_dgrad(cgd_unet* u, const float* g_out, float* g_x, void* stream);
+/* Super-resolution handles (in_channels 6; guided-diffusion's SuperResModel): the low-resolution image low (B_low,3,h,w) NCHW in [-1,1],
+ * B_low 1 or the batch of the later forwards, is copied (stream-ordered) into a buffer the handle owns and conditions every later
+ * cgd_unet_forward / cgd_unet_forward_slot until it is replaced: those take x (B,3,H,W) as on a 3-channel handle, upsample the image
+ * bilinearly to (H, W) and run the stem on cat([x, upsampled]) in one launch (cgd_op_sr_stem); they fail when no image is set or
+ * B_low is neither 1 nor B.  cgd_unet_dgrad still returns (B,3,H,W): only d/dx exists.  Refused on a 3-channel handle. */
+int cgd_unet_set_low_res(cgd_unet* u, const float* low, int B_low, int h, int w, void* stream);
 
 /* ---- CLIP image tower (VisionTransformer): replaces clip_model.encode_image, cgd/cgd.py:194 ---- */
 typedef struct cgd_vit_config {
@@ -606,6 +612,14 @@ int cgd_op_conv_in(cgd_ctx* ctx, const float* x_nchw, const float* w, const floa
                    int Cout, void* stream);
 int cgd_op_conv_thin_out(cgd_ctx* ctx, const float* x_nhwc, int ldx, const float* w, const float* bias, float* y_nchw, int Bn, int H,
                          int W, int Cin, int Cout, void* stream);
+/* The conditioned stem of the super-resolution UNets in one launch (csrc/superres.hip):
+ *   y = conv3x3(cat([x, bilinear(low -> H x W)], channels), w, bias)      (SuperResModel.forward + input_blocks.0.0)
+ * x (B,3,H,W) NCHW; low (B_low,3,h,w) NCHW with B_low 1 (shared by the batch) or B, any h, w >= 1; wpacked [Cout][3][3][6] as
+ * cgd_pack_conv3x3 leaves it; bias [Cout] or NULL; y NHWC rows of stride ldy (0 = Cout).  Cout a multiple of 4, at most 256.  The
+ * interpolation is F.interpolate(mode="bilinear", align_corners=False) with integer tap geometry; the zero padding is that of the
+ * concatenated tensor.  No (B,6,H,W) tensor is formed. */
+int cgd_op_sr_stem(cgd_ctx* ctx, const float* x, const float* low, int B_low, int h, int w, const float* wpacked, const float* bias, float* y,
+                   int ldy, int B, int H, int W, int Cout, void* stream);
 int64_t cgd_op_gn_scratch_floats(int B, int HW, int C);
 /* GroupNorm over 32 groups: C a multiple of 32 and <= 4096, forward row strides (ldx, ldy) multiples of 4.  Up to 1024 pixels per sample (the
  * default single-launch size)

@@ -53,6 +53,9 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
     # "SOURCE=>TARGET[:weight]" among the prompts (an extension like "plmsN"): a direction prompt, scored by the directional CLIP loss against
     # the init image; refused before anything is loaded when malformed or without an init image
     direction_pairs = script_util.direction_prompts(prompts, image_prompts, init_image, height_offset, width_offset)
+    # "style=FILE[:SCALE]" among the image prompts (likewise): the style image of the VGG Gram-matrix style loss, SCALE its weight; no CLIP
+    # prompt.  Refused before anything is loaded when malformed, given twice, or at a frame whose sides are no multiples of 16
+    image_prompts, style_spec = script_util.split_style_prompts(image_prompts, image_size + height_offset, image_size + width_offset)
     if use_augs and any(pair is not None for pair in direction_pairs):
         raise ValueError("'SOURCE=>TARGET' prompts do not work with use_augs: the random warp of every cut would have to be replayed on the init image")
 
@@ -113,11 +116,14 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
             embeds_per_tower[k].append(embed)
         weights.extend(batched)
     # (a run with direction prompts only has no target embeddings: ClipGuidance then makes no spherical launch)
-    target_embeds = [th.cat(e) for e in embeds_per_tower] if (embeds_per_tower[0] or not direction_columns) else None
+    # (... and a run with a style image and no prompt at all has neither: no cutouts, no CLIP pass)
+    style_only = style_spec is not None and not weights
+    target_embeds = [th.cat(e) for e in embeds_per_tower] if (embeds_per_tower[0] or not (direction_columns or style_only)) else None
     weight_t = th.tensor(weights, device=device)
-    if weight_t.sum().abs() < 1e-3:
-        raise RuntimeError("The weights must not sum to 0.")
-    weight_t = weight_t / weight_t.sum().abs()
+    if not style_only:
+        if weight_t.sum().abs() < 1e-3:
+            raise RuntimeError("The weights must not sum to 0.")
+        weight_t = weight_t / weight_t.sum().abs()
     direction_kw = {}
     if direction_columns:  # normalised together above; ClipGuidance builds the B x P matrix over the whole list and splits its columns
         target_columns = [c for c in range(len(weights)) if c not in direction_columns]
@@ -154,6 +160,14 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         if mask_image is not None:
             pil = Image.open(script_util.fetch(mask_image)).convert("L").resize((image_size, image_size))
             mask_tensor = th.from_numpy(np.array(pil)).float().div(255).to(device)[None, None]
+
+    style_tensor = None
+    if style_spec is not None:  # at the run's frame; every rank of a sharded run computes the style Gram matrices itself (no collective)
+        import numpy as np
+        from PIL import Image
+        pil = Image.open(script_util.fetch(style_spec[0])).convert("RGB").resize((image_size + width_offset, image_size + height_offset),
+                                                                                 Image.LANCZOS)
+        style_tensor = th.from_numpy(np.array(pil)).float().div(255).permute(2, 0, 1).to(device).unsqueeze(0).mul(2).sub(1)
 
     # Multi-GPU (cgd_amd.launch: one process per GPU, torch.distributed initialised): the batch is sharded by samples, one (or
     # a contiguous block) per rank; every rank draws the GLOBAL random tensors from the same seed and keeps its rows, so the
@@ -211,8 +225,11 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         clip_guidance_scale=clip_guidance_scale, tv_scale=tv_scale, range_scale=range_scale, sat_scale=sat_scale, use_magnitude=use_magnitude,
         reduce_clip=reduce_clip, progressive_cutout=progressive_cutout, cached_cutouts=cached_cutouts, make_cutouts=make_cutouts,
         # "initialized lazily as it can use a bit of VRAM" (reference cgd.py:146-148): only with an init image and a non-zero scale
-        lpips=script_util.load_lpips(gd_model.ctx, checkpoints_dir, device) if (init_tensor is not None and init_scale != 0) else None,
+        # ... or with a style image, whose term runs on the same trunk
+        lpips=script_util.load_lpips(gd_model.ctx, checkpoints_dir, device)
+        if ((init_tensor is not None and init_scale != 0) or style_tensor is not None) else None,
         init_tensor=init_tensor, init_scale=init_scale,
+        **({} if style_tensor is None else {"style_tensor": style_tensor, "style_scale": style_spec[1]}),
         secondary=secondary,
         **({"direction_source": init_tensor, **direction_kw} if direction_kw else {}),
         **({} if classifier is None else {"classifier": classifier, "classifier_scale": classifier_spec[2], "classifier_class": classifier_spec[1]}))
@@ -297,7 +314,7 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
 # for store_true switches.  Only names, aliases, types and defaults are contract (tests/golden/reference_host.json).
 _CLI_SPEC = f"""
 --prompts -txts str "" | text prompts with optional weights, pipe-separated: 'a cat:0.5|a dog:-0.5'; 'SOURCE CAPTION=>TARGET CAPTION[:weight]' is a direction prompt (needs --init_image): the change of the image's CLIP embedding relative to the init image is steered along the change from the source to the target caption (e.g. 'a photo of a cat=>a photo of a dog:1.5'); weights of all prompts are normalised together
---image_prompts -imgs str "" | image prompts (paths or URLs) with optional weights, pipe-separated
+--image_prompts -imgs str "" | image prompts (paths or URLs) with optional weights, pipe-separated; one entry may be 'style=FILE[:SCALE]': FILE is then no CLIP prompt but the style image of the VGG16 Gram-matrix style loss (texture and palette statistics of relu1_2 .. relu4_3, Gatys / Johnson), resized to the frame, SCALE the weight of that loss (default 1, positive; it does not enter the prompt weights); frame sides must be multiples of 16; works with or without prompts and with --init_image / --init_scale
 --image_size -size int 128 | resolution of the diffusion checkpoint: 64, 128, 256 or 512
 --init_image -init str "" | start from this image (needs --skip_timesteps); IMAGE::MASK regenerates the white part of MASK and keeps the black part of IMAGE; invert=IMAGE (or invert=IMAGE::MASK, with -respace ddimN / plmsN / dpmN) starts from the DDIM-inverted latent of IMAGE; upsample=IMAGE (or upsample=IMAGE::MASK, with --image_size 256 or 512, not with --uncond or invert=) runs the 64->256 / 128->512 super-resolution checkpoint conditioned on IMAGE at a quarter of the frame, IMAGE at the full frame staying the init image; in every form IMAGE is also the source image of 'SOURCE=>TARGET' direction prompts
 --init_scale -is int 0 | weight of the LPIPS-VGG16 term that keeps the sample close to the init image

@@ -153,11 +153,42 @@ def split_direction(text):
     return source, target
 
 
+STYLE_PREFIX = "style="
+
+
+def split_style_prompts(image_prompts, height=None, width=None):
+    """The entries of `image_prompts` without the 'style=FILE[:SCALE]' one, and (FILE, SCALE) of that one or None.  A style entry rides on
+    --image_prompts / image_prompts= but is no CLIP image prompt: FILE is the style image of the VGG Gram-matrix style loss and SCALE the
+    weight of that loss itself (default 1), so the entry stays out of the CLIP embeddings, the prompt weights, their normalisation and the
+    zero-sum check.  Refuses, before anything is loaded: an entry without a file, a SCALE that is no positive number, a second style entry,
+    and (when given) frame sides that are no multiples of 16 (the VGG trunk pools four times)."""
+    rest, style = [], None
+    for p in image_prompts:
+        if not str(p).startswith(STYLE_PREFIX):
+            rest.append(p)
+            continue
+        if style is not None:
+            raise ValueError(f"image prompt {p!r}: at most one 'style=FILE[:SCALE]' entry (one style image)")
+        try:
+            file, scale = parse_prompt(str(p)[len(STYLE_PREFIX):])
+        except ValueError:
+            raise ValueError(f"image prompt {p!r}: 'style=FILE[:SCALE]' takes a number as SCALE") from None
+        if not file:
+            raise ValueError(f"image prompt {p!r}: 'style=FILE[:SCALE]' needs a file")
+        if not scale > 0:
+            raise ValueError(f"image prompt {p!r}: the SCALE of 'style=FILE:SCALE' is the weight of the style loss and must be positive")
+        style = (file, scale)
+    if style is not None and height is not None and (height % 16 or width % 16):
+        raise ValueError(f"image prompt 'style=...' needs frame sides that are multiples of 16, got {height} x {width}")
+    return rest, style
+
+
 def direction_prompts(prompts, image_prompts=(), init_image=None, height_offset=0, width_offset=0):
     """Per entry of `prompts`: None, or the (source, target) captions of a direction prompt.  Refuses, before anything is loaded: a malformed
     entry, an image prompt with '=>', direction prompts without an init image (it is their source image) or with height / width offsets
     (the init image has the checkpoint's size), and weights that sum to zero over all prompts (the reference's rule, cgd.py:103-105)."""
     pairs = [split_direction(parse_prompt(p)[0]) for p in prompts]
+    image_prompts = [p for p in image_prompts if not str(p).startswith(STYLE_PREFIX)]  # (split_style_prompts: no CLIP prompt, no prompt weight)
     for p in image_prompts:
         if DIRECTION_SEP in parse_prompt(p)[0]:
             raise ValueError(f"image prompt {p!r}: only text prompts can be 'SOURCE=>TARGET' directions")

@@ -356,6 +356,10 @@ int cgd_op_gemm(cgd_ctx* ctx, const float* A, int lda, const float* B, int ldb, 
   }
   return cgd_launch_gemm(ctx, p, S(stream));
 }
+int cgd_op_gram(cgd_ctx* ctx, const float* A, int lda, int B, int N, int C, float scale, float* G_out, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_gram(ctx, A, lda, B, N, C, scale, G_out, nullptr, 0.f, 0.f, nullptr, 0, S(stream));
+}
 static GemmParams gemm_gn_bwd_params(const float* A, int lda, const float* Wt, int ldw, float* dx, int lddx, const float* x, int ldx, const float* dz,
                                      int lddz, const float* add, int ldadd, const float* coef, const float* bcoef, int Bn, int HW, int N, int K) {
   GemmParams p;

@@ -184,3 +184,13 @@ int cgd_attnpool_bwd(cgd_ctx* ctx, const AttnPoolShape& sh, const AttnPoolWeight
                      hipStream_t s);
 // g += d (n floats, n a multiple of 4, 16-byte aligned)
 int cgd_launch_accumulate(cgd_ctx* ctx, float* g, const float* d, long n, hipStream_t s);
+
+// ---- gram.hip: per-sample Gram matrices of tall-skinny activations (the VGG style loss) ---------------------------------------------
+// A [B * N][C] fp32 rows (row stride lda >= C, a multiple of 4; 16-byte aligned), C in {64, 128, 256, 512}, any N >= 1; exact fp32 products whatever the
+// context precision; the slab partials live in the context's split-K workspace.
+//   Gs == nullptr: out [B][C][C] = scale * A_b^T A_b
+//   else         : out [B][C][C] = gk * (scale * A_b^T A_b - Gs) and lpart[b * lstride + i] = lw * (partial sums of (scale * A_b^T A_b - Gs)^2),
+//                  i < cgd_gram_loss_parts(C)
+int cgd_gram_loss_parts(int C);
+int cgd_launch_gram(cgd_ctx* ctx, const float* A, int lda, int B, int N, int C, float scale, float* out, const float* Gs, float gk, float lw,
+                    float* lpart, long lstride, hipStream_t s);

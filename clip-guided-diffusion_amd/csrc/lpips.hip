@@ -12,11 +12,15 @@
 // Precision: the trunk always runs in the exact-fp32 MFMA mode.  Its gradient is discontinuous in the activations (ReLU
 // masks, pooling arg-max): with the bf16x3 products (1e-5 relative) enough masks flip against an fp32 reference to put a
 // 1-2 % error on the gradient (diag_r1ak), with fp32 products 3e-6.  The trunk is ~80 GFLOP per call at 256x256.
+// Style term (cgd_lpips_set_style / cgd_lpips_style_loss_grad): the VGG Gram-matrix style loss of a style image on the same taps,
+// sum_k lambda_k |G_k(x) - G_k(style)|_F^2 with G_k = A_k^T A_k / (C_k N_k) (gram.hip); its cotangents join the LPIPS head's in dtap, so one
+// trunk pass forward and one backward serve both terms.
 #include <algorithm>
 #include <memory>
 
 #include "../../include/cgd_mi355x.h"
 #include "net.h"
+#include "kernels.h"
 #include "mfma_stage.h"
 
 namespace {
@@ -202,6 +206,12 @@ struct Lpips : NetBase {
   DevBuf xs, dxs, n0[5], dtap[5], part;
   int B = 0, H = 0, W = 0;
   bool have_ref = false;
+  // VGG Gram-matrix style term (cgd_lpips_set_style): G_k(style) = A_k^T A_k / (C_k N_k) of the five taps of ONE style image, and the tap weights
+  // lambda_k (a tap with lambda_k = 0 is never touched).  dmat: D_k[b] = gk (G_k(x)[b] - G_k(style)), the B operand of the backward GEMM; spart: the
+  // loss partials of all active taps, [B][sum of cgd_gram_loss_parts]
+  DevBuf gs[5], dmat, spart;
+  float lam[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  bool have_style = false;
   // test support (cgd_lpips_debug_replay): when set, the trunk pass of the NEXT loss_grad call overwrites the post-ReLU activation of
   // conv l with replay[l] ([M][cout] rows on the device) right after computing it, so that the taps, the ReLU masks and the pooling
   // arg-max of the backward pass are taken from the caller's (the oracle's) activations
@@ -212,7 +222,11 @@ struct Lpips : NetBase {
   int finalize(hipStream_t s);
   int features(const float* x, int Bn, int Hh, int Ww, hipStream_t s);
   int set_reference(const float* ref, int Bn, int Hh, int Ww, hipStream_t s);
-  int loss_grad(const float* x, float gscale, float* loss, float* g, int accumulate, hipStream_t s);
+  int set_style(const float* style, int Hs, int Ws, const float* lambda, hipStream_t s);
+  // one trunk forward, the LPIPS head (loss != null) and / or the style head (style_loss != null), one trunk backward
+  int loss_grad(const float* x, int Bn, int Hh, int Ww, float gscale, float sscale, float* loss, float* style_loss, float* g, int accumulate,
+                hipStream_t s);
+  static int layer_of(int k) { return k == 0 ? 1 : 3 * k; }  // inverse of tap_of
   static int tap_of(int l) { return (l == 1) ? 0 : (l == 3) ? 1 : (l == 6) ? 2 : (l == 9) ? 3 : (l == 12) ? 4 : -1; }
   static bool pooled_in(int l) { return l == 2 || l == 4 || l == 7 || l == 10; }
 };
@@ -256,6 +270,7 @@ int Lpips::finalize(hipStream_t s) {
   CGD_HIP(ctx, hipStreamSynchronize(s));
   finalized = true;
   have_ref = false;
+  have_style = false;
   return 0;
 }
 
@@ -314,15 +329,54 @@ int Lpips::set_reference(const float* ref, int Bn, int Hh, int Ww, hipStream_t s
   return 0;
 }
 
-int Lpips::loss_grad(const float* x, float gscale, float* loss, float* g, int accumulate, hipStream_t s) {
-  if (!have_ref) CGD_FAIL(ctx, "lpips: no reference image set (cgd_lpips_set_reference)");
+// The Gram matrices of the style image's taps; the trunk runs on a batch of one at the style image's own size (a Gram matrix does not depend on
+// the frame), the reference's features (n0) and frame stay as they are.
+int Lpips::set_style(const float* style, int Hs, int Ws, const float* lambda, hipStream_t s) {
+  if (!style || !lambda) CGD_FAIL(ctx, "lpips: set_style needs an image and five tap weights");
+  bool any = false;
+  for (int k = 0; k < 5; ++k) {
+    if (!(lambda[k] >= 0.f)) CGD_FAIL(ctx, "lpips: style tap weights must be >= 0");
+    any = any || lambda[k] > 0.f;
+  }
+  if (!any) CGD_FAIL(ctx, "lpips: at least one style tap weight must be positive");
   ExactScope exact(ctx);
-  const int Bn = B, Hh = H, Ww = W;
+  const int Bk = B, Hk = H, Wk = W;
+  have_style = false;
+  const int frc = features(style, 1, Hs, Ws, s);
+  B = Bk; H = Hk; W = Wk;
+  CGD_TRY(frc);
+  for (int k = 0; k < 5; ++k) {
+    lam[k] = lambda[k];
+    if (lam[k] == 0.f) continue;
+    const VConv& c = cv[layer_of(k)];
+    const int n = (Hs >> k) * (Ws >> k);
+    CGD_TRY(ensure(gs[k], (size_t)c.cout * c.cout));
+    CGD_TRY(cgd_launch_gram(ctx, c.a.p, c.cout, 1, n, c.cout, 1.f / ((float)c.cout * (float)n), gs[k].p, nullptr, 0.f, 0.f, nullptr, 0, s));
+  }
+  have_style = true;
+  return 0;
+}
+
+int Lpips::loss_grad(const float* x, int Bn, int Hh, int Ww, float gscale, float sscale, float* loss, float* style_loss, float* g, int accumulate,
+                     hipStream_t s) {
+  if (loss && !have_ref) CGD_FAIL(ctx, "lpips: no reference image set (cgd_lpips_set_reference)");
+  if (style_loss && !have_style) CGD_FAIL(ctx, "lpips: no style image set (cgd_lpips_set_style)");
+  if (!loss && !style_loss) CGD_FAIL(ctx, "lpips: neither the LPIPS nor the style term is asked for");
+  if (loss && (Bn != B || Hh != H || Ww != W)) CGD_FAIL(ctx, "lpips: the input's shape differs from the reference image's");
+  if (Bn < 1 || Hh < 16 || Ww < 16) CGD_FAIL(ctx, "lpips: B, H and W must be given");
+  if (g == x) CGD_FAIL(ctx, "lpips: g may not alias x");
+  ExactScope exact(ctx);
+  const int Bk = B, Hk = H, Wk = W;  // (the reference's frame, when there is one)
+  struct Restore {
+    Lpips* n;
+    int b, h, w;
+    ~Restore() { n->B = b; n->H = h; n->W = w; }
+  } restore{this, Bk, Hk, Wk};
   in_loss_grad = true;
   const int frc = features(x, Bn, Hh, Ww, s);
   in_loss_grad = false;
   CGD_TRY(frc);
-  CGD_HIP(ctx, hipMemsetAsync(loss, 0, (size_t)B * sizeof(float), s));
+  if (loss) CGD_HIP(ctx, hipMemsetAsync(loss, 0, (size_t)B * sizeof(float), s));
   // taps: per-pixel loss and the gradient w.r.t. each tapped activation
   int hs[NCONV], ws_[NCONV];
   {
@@ -332,7 +386,7 @@ int Lpips::loss_grad(const float* x, float gscale, float* loss, float* g, int ac
       hs[l] = h; ws_[l] = w;
     }
   }
-  for (int l = 0; l < NCONV; ++l) {
+  for (int l = 0; l < NCONV && loss; ++l) {
     const int k = tap_of(l);
     if (k < 0) continue;
     const long hw = (long)hs[l] * ws_[l], M = (long)B * hw;
@@ -343,15 +397,49 @@ int Lpips::loss_grad(const float* x, float gscale, float* loss, float* g, int ac
                        gscale / (float)hw);
     CGD_LAUNCH(lp_loss_reduce_kernel, dim3(B), dim3(256), 0, s, part.p, hw / 4, 1.f / (float)hw, loss);
   }
+  // style head: per active tap the Gram contraction, its finish (D = gk (G - G_style) and the loss partials) and dtap (+)= A D as one batched GEMM
+  // (D is symmetric, so it serves as the GEMM's [n][k] operand as it is)
+  int ltop = loss ? NCONV - 1 : 0;  // the deepest layer that receives a cotangent: the backward pass starts there
+  if (style_loss) {
+    CGD_HIP(ctx, hipMemsetAsync(style_loss, 0, (size_t)B * sizeof(float), s));
+    long nper = 0;
+    int cmax = 0;
+    for (int k = 0; k < 5; ++k)
+      if (lam[k] > 0.f) {
+        nper += cgd_gram_loss_parts(cv[layer_of(k)].cout);
+        cmax = std::max(cmax, cv[layer_of(k)].cout);
+      }
+    CGD_TRY(ensure(spart, (size_t)B * nper));
+    CGD_TRY(ensure(dmat, (size_t)B * cmax * cmax));
+    long at = 0;
+    for (int k = 0; k < 5; ++k) {
+      if (lam[k] == 0.f) continue;
+      const int l = layer_of(k), Ck = cv[l].cout;
+      const long hw = (long)hs[l] * ws_[l];
+      const float inv = 1.f / ((float)Ck * (float)hw);
+      ltop = std::max(ltop, l);
+      CGD_TRY(ensure(dtap[k], (size_t)B * hw * Ck));
+      CGD_TRY(cgd_launch_gram(ctx, cv[l].a.p, Ck, B, (int)hw, Ck, inv, dmat.p, gs[k].p, 4.f * lam[k] * sscale * inv, lam[k], spart.p + at, nper, s));
+      at += cgd_gram_loss_parts(Ck);
+      GemmParams gp;
+      gp.A = cv[l].a.p; gp.lda = Ck; gp.B = dmat.p; gp.ldb = Ck; gp.C = dtap[k].p; gp.ldc = Ck;
+      gp.M = (int)hw; gp.N = Ck; gp.K = Ck;
+      gp.nbatch = B; gp.sA1 = hw * Ck; gp.sB1 = (long)Ck * Ck; gp.sC1 = hw * Ck;
+      if (loss) { gp.R = dtap[k].p; gp.ldr = Ck; gp.sR1 = hw * Ck; }  // the LPIPS head wrote its cotangent there first
+      CGD_TRY(cgd_launch_gemm(ctx, gp, s));
+    }
+    CGD_LAUNCH(lp_loss_reduce_kernel, dim3(B), dim3(256), 0, s, spart.p, nper, 1.f, style_loss);
+  }
   // backward through the trunk
   const float* dnext = nullptr;  // gradient w.r.t. the INPUT of conv l+1 (same resolution as its input)
-  for (int l = NCONV - 1; l >= 0; --l) {
+  for (int l = ltop; l >= 0; --l) {
     VConv& c = cv[l];
     const long M = (long)B * hs[l] * ws_[l];
-    const int k = tap_of(l);
+    int k = tap_of(l);
+    if (k >= 0 && !loss && lam[k] == 0.f) k = -1;  // a tap that neither term reads
     float* da = nullptr;
-    if (l == NCONV - 1) {
-      da = dtap[4].p;  // only the tap feeds the last activation
+    if (l == ltop) {
+      da = dtap[k].p;  // only the tap feeds the deepest activation that has a cotangent
     } else if (pooled_in(l + 1)) {
       // a_l -> max-pool -> conv l+1: route the pooled gradient back and add the tap gradient (every pooled layer is a tap)
       CGD_TRY(ensure(c.da, (size_t)M * c.cout));
@@ -416,6 +504,20 @@ int cgd_lpips_debug_replay(cgd_lpips* v, const float* const* acts) {
 int cgd_lpips_loss_grad(cgd_lpips* v, const float* x_nchw, float grad_scale, float* loss, float* g_nchw, int accumulate, void* stream) {
   if (!v) return -3;
   DeviceScope dev_scope(v->net.ctx);
-  return v->net.loss_grad(x_nchw, grad_scale, loss, g_nchw, accumulate, LS(stream));
+  if (!v->net.have_ref) CGD_FAIL(v->net.ctx, "lpips: no reference image set (cgd_lpips_set_reference)");
+  if (!loss) CGD_FAIL(v->net.ctx, "lpips: loss must not be null");
+  return v->net.loss_grad(x_nchw, v->net.B, v->net.H, v->net.W, grad_scale, 0.f, loss, nullptr, g_nchw, accumulate, LS(stream));
+}
+int cgd_lpips_set_style(cgd_lpips* v, const float* style_nchw, int Hs, int Ws, const float* lambda, void* stream) {
+  if (!v) return -3;
+  DeviceScope dev_scope(v->net.ctx);
+  return v->net.set_style(style_nchw, Hs, Ws, lambda, LS(stream));
+}
+int cgd_lpips_style_loss_grad(cgd_lpips* v, const float* x_nchw, int B, int H, int W, float lpips_grad_scale, float style_grad_scale,
+                              float* lpips_loss, float* style_loss, float* g_nchw, int accumulate, void* stream) {
+  if (!v) return -3;
+  DeviceScope dev_scope(v->net.ctx);
+  if (!style_loss) CGD_FAIL(v->net.ctx, "lpips: style_loss must not be null");
+  return v->net.loss_grad(x_nchw, B, H, W, lpips_grad_scale, style_grad_scale, lpips_loss, style_loss, g_nchw, accumulate, LS(stream));
 }
 }  // extern "C"

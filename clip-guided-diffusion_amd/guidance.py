@@ -571,7 +571,8 @@ class ClipGuidance:
                  clip_guidance_scale=1000.0, tv_scale=150.0, range_scale=50.0, sat_scale=0.0, use_magnitude=False,
                  reduce_clip=False, progressive_cutout=False, cached_cutouts=False, make_cutouts=None, lpips=None, init_tensor=None,
                  init_scale=0.0, secondary=None, classifier=None, classifier_scale=1.0, classifier_class=None, direction_embeds=None,
-                 direction_weights=None, direction_source=None, direction_columns=None):
+                 direction_weights=None, direction_source=None, direction_columns=None, style_tensor=None, style_scale=0.0,
+                 style_weights=(1, 1, 1, 1, 0)):
         # Multi-CLIP (BASELINE config 5, a build extension: the reference takes one clip_model_name): `clip_tower` / `target_embeds`
         # may be lists; the CLIP losses of the towers are summed (same cutout boxes, prompt weights and guidance scale).
         self.towers = list(clip_tower) if isinstance(clip_tower, (list, tuple)) else [clip_tower]
@@ -587,6 +588,19 @@ class ClipGuidance:
             if target_embeds is None:
                 target_embeds = [d.new_zeros((0, d.shape[-1])) for d in dirs]
                 weights = []
+        # VGG Gram-matrix style term (csrc/gram.hip, nets.LpipsVGG.set_style): `style_tensor` (1,3,Hs,Ws) in [-1,1] on the `lpips` handle's trunk,
+        # the loss gains style_scale * sum_b L_style(x_in_b).  With a style and no prompt of either kind the CLIP leg is not run at all
+        # (`target_embeds` None): the extension of the direction-only path
+        has_style = style_tensor is not None and style_scale != 0
+        if has_style and lpips is None:
+            raise ValueError("style_tensor needs the LPIPS-VGG16 handle (lpips=): the style term runs on its trunk")
+        if has_style and not (float(style_scale) > 0):
+            raise ValueError(f"style_scale must be positive, got {style_scale}")
+        if target_embeds is None and not has_dir:
+            if not has_style:
+                raise ValueError("no target embeddings: only a run with direction prompts or a style image goes without")
+            target_embeds = [style_tensor.new_zeros((0, t.out_dim)) for t in self.towers]
+            weights = []
         embeds = list(target_embeds) if isinstance(target_embeds, (list, tuple)) else [target_embeds]
         assert len(embeds) == len(self.towers), "one target-embedding tensor per CLIP tower"
         self.ctx, self.unet, self.clip, self.diffusion = ctx, unet, self.towers[0], diffusion
@@ -628,6 +642,12 @@ class ClipGuidance:
         if lpips is not None and init_tensor is not None and init_scale != 0:
             self.lpips, self.init_tensor = lpips, init_tensor.float()
         self._lpips_ref_batch = 0
+        self.style, self.style_scale, self.style_tensor, self.style_weights = None, float(style_scale), None, tuple(style_weights)
+        if has_style:
+            self.style, self.style_tensor = lpips, style_tensor.float()
+        self._style_set = False
+        self.style_loss = None
+        self.no_clip = self.dirs_list is None and self.targets_list[0].shape[0] == 0  # style (and init) terms only: no cutouts, no CLIP pass
         # secondary model (nets.SecondaryModel) or None: with one, pred / x_in of the guidance losses come from it and the gradient returns to x
         # through it; the UNet's backward pass is not run (its forward still gives the update's mean, variance and the yielded pred_xstart)
         self.secondary = secondary
@@ -736,7 +756,7 @@ class ClipGuidance:
         wm = self._wm.get(B)
         if wm is None and self.dirs_list is not None:
             wm = self._split_weight_matrix(B, dev)
-        if wm is None:
+        if wm is None and not self.no_clip:
             if self.shard is None:
                 wm = prompt_weight_matrix(self.weights.cpu(), B, dev)
             else:  # the B <-> P broadcast rule is decided on the GLOBAL batch (sample b <-> prompt b when B == P)
@@ -753,20 +773,37 @@ class ClipGuidance:
             if self._lpips_ref_batch != B:  # the reference broadcasts a (1,3,H,W) init image over the batch (cgd.py:221)
                 self.lpips.set_reference(self.init_tensor.to(dev).expand(B, -1, -1, -1).contiguous())
                 self._lpips_ref_batch = B
+        if self.style is not None:
+            if not self._style_set:  # once: the Gram matrices of the style image (every rank of a sharded run computes its own)
+                self.style.set_style(self.style_tensor.to(dev), self.style_weights)
+                self._style_set = True
+            # one trunk pass for the style term and, when there is an init image, the LPIPS term
+            with_lp = self.lpips is not None
+            self.style_loss, lp, _ = self.style.style_loss_grad(
+                x_in, style_scale=self.style_scale, lpips_scale=self.init_scale if with_lp else None, g=gclip, accumulate=False,
+                style_loss=self._b("style_loss", (B,), dev), lpips_loss=self._b("lpips_loss", (B,), dev) if with_lp else None)
+            if with_lp:
+                self.lpips_loss = lp
+            acc = 1
+        elif self.lpips is not None:
             # d(init_scale * sum_b lpips(x_in_b, init_b)) / dx_in goes into the same buffer as the CLIP gradient w.r.t. x_in
             self.lpips_loss, _ = self.lpips.loss_grad(x_in, grad_scale=self.init_scale, g=gclip, accumulate=False,
                                                       loss=self._b("lpips_loss", (B,), dev))
             acc = 1
         clip_part = self._b("clip_part", (len(self.towers) * N * self._clip_kinds(),), dev)
         self.clip_part = clip_part
-        if resized:
+        if self.no_clip:
+            clip_part.zero_()
+            cuts = None
+        elif resized:
             scratch = self._b("resize_scratch", (max(1, lib.cgd_cutouts_resize_scratch_floats(B, H, W, cutn)),), dev)  # one query per step
             cuts = _CutLaunch(lib, coords, geo, True, scratch)
         elif self.make_cutouts.augs is not None:
             cuts = _AugCuts(lib, coords, B, H, W, dev)
         else:
             cuts = _CutLaunch(lib, coords, geo)
-        self._clip_leg(x_in, cuts, wm, self._wmd.get(B), gclip, clip_part, acc)
+        if cuts is not None:
+            self._clip_leg(x_in, cuts, wm, self._wmd.get(B), gclip, clip_part, acc)
         nblk = lib.cgd_guidance_part_blocks(B, H, W)
         # the saturation term is a mean over the WHOLE batch (cgd.py:214-218): a rank that holds B of the run's shard[1] samples scales
         # it so that its per-sample gradient equals the batched run's (the logged value is then this rank's share of the loss)
@@ -967,6 +1004,8 @@ class ClipGuidance:
         """Asynchronous host copies of the last call's scalars: `log(snapshot)` later costs no wait on newer GPU work."""
         from .hostcopy import HostCopy
         snap = {"scalars": HostCopy(self.scalars.clone()), "lpips": HostCopy(self.lpips_loss.clone()) if self.lpips is not None else None}
+        if self.style is not None:
+            snap["style"] = HostCopy(self.style_loss.clone())
         if self.classifier is not None:
             snap["classifier"] = HostCopy(self.classifier_logp.clone())
         if self.dirs_list is not None:
@@ -990,6 +1029,10 @@ class ClipGuidance:
         if self.lpips is not None:
             out["Init VGG Loss"] = float(lpips_loss.sum().item()) * self.init_scale
             out["Total Loss"] += out["Init VGG Loss"]
+        if self.style is not None:
+            style_loss = snapshot["style"].get() if snapshot is not None else self.style_loss
+            out["Style Loss"] = float(style_loss.sum().item()) * self.style_scale
+            out["Total Loss"] += out["Style Loss"]
         if self.classifier is not None:
             logp = snapshot["classifier"].get() if snapshot is not None else self.classifier_logp
             out["Classifier Loss"] = -self.classifier_scale * float(logp.sum().item())

@@ -148,6 +148,9 @@ _SIGS = {
     "cgd_lpips_set_reference": (i32, [vp, vp, i32, i32, i32, vp]),
     "cgd_lpips_loss_grad": (i32, [vp, vp, f32, vp, vp, i32, vp]),
     "cgd_lpips_debug_replay": (i32, [vp, C.POINTER(vp)]),
+    "cgd_lpips_set_style": (i32, [vp, vp, i32, i32, C.POINTER(f32), vp]),
+    "cgd_lpips_style_loss_grad": (i32, [vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, i32, vp]),
+    "cgd_op_gram": (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp]),
     "cgd_secondary_manifest": (i32, [MANIFEST_CB, vp]),
     "cgd_secondary_create": (i32, [vp, C.POINTER(vp)]),
     "cgd_secondary_destroy": (None, [vp]),

@@ -408,6 +408,43 @@ class LpipsVGG(_Net):
         self._keep = x
         return loss, g
 
+    def set_style(self, img, weights=(1, 1, 1, 1, 0)):
+        """img (1,3,Hs,Ws) or (3,Hs,Ws) in [-1,1], the ONE style image; Hs, Ws multiples of 16, otherwise free.  weights: lambda_k of the five taps
+        (relu1_2, relu2_2, relu3_3, relu4_3, relu5_3) in L_style = sum_k lambda_k |G_k(x) - G_k(style)|_F^2, G_k = A_k^T A_k / (C_k N_k); a tap with weight 0
+        is skipped everywhere.  A reference set by `set_reference` stays intact."""
+        img = img.contiguous().float()
+        if img.dim() == 3:
+            img = img[None]
+        if img.dim() != 4 or img.shape[0] != 1 or img.shape[1] != 3:
+            raise ValueError(f"style image must be (1,3,H,W), got {tuple(img.shape)}")
+        weights = tuple(float(w) for w in weights)
+        if len(weights) != 5:
+            raise ValueError("style weights: one per tap, five in all")
+        lam = (C.c_float * 5)(*weights)
+        self.ctx.check(self.ctx.lib.cgd_lpips_set_style(self.h, img.data_ptr(), img.shape[2], img.shape[3], lam, self.ctx.stream()))
+        self._style = True
+        return self
+
+    def style_loss_grad(self, x, style_scale=1.0, lpips_scale=None, g=None, accumulate=False, style_loss=None, lpips_loss=None):
+        """One trunk pass for both terms.  Returns (style_loss (B,), lpips_loss (B,) or None, g (B,3,H,W)) with
+        g (+)= style_scale * d(sum style_loss)/dx [+ lpips_scale * d(sum lpips_loss)/dx].  lpips_scale=None: the style term alone (no reference needed)."""
+        x = x.contiguous().float()
+        assert getattr(self, "_style", False), "set_style first"
+        if lpips_scale is not None:
+            assert self._ref is not None and tuple(x.shape) == tuple(self._ref.shape), "set_reference first (same shape)"
+        B, _, H, W = x.shape
+        if g is None:
+            g = th.zeros_like(x) if accumulate else th.empty_like(x)
+        if style_loss is None:
+            style_loss = th.empty(B, device=x.device, dtype=th.float32)
+        if lpips_scale is not None and lpips_loss is None:
+            lpips_loss = th.empty(B, device=x.device, dtype=th.float32)
+        self.ctx.check(self.ctx.lib.cgd_lpips_style_loss_grad(
+            self.h, x.data_ptr(), B, H, W, float(lpips_scale or 0.0), float(style_scale), lpips_loss.data_ptr() if lpips_scale is not None else None,
+            style_loss.data_ptr(), g.data_ptr(), int(bool(accumulate)), self.ctx.stream()))
+        self._keep = x
+        return style_loss, (lpips_loss if lpips_scale is not None else None), g
+
 
 class SecondaryModel(_Net):
     """The secondary diffusion model (SecondaryDiffusionImageNet2 of Katherine Crowson's CLIP-guided diffusion notebooks, also shipped with

@@ -190,6 +190,17 @@ int cgd_lpips_loss_grad(cgd_lpips* v, const float* x_nchw, float grad_scale, flo
  * image the NEXT cgd_lpips_loss_grad call is given, [B*h_l*w_l][cout_l] NHWC rows) or NULL to switch it off: the trunk pass of that
  * call continues from these activations, so taps, ReLU masks and max-pool arg-max are the caller's (the oracle's). */
 int cgd_lpips_debug_replay(cgd_lpips* v, const float* const* acts);
+/* VGG Gram-matrix style term on the same trunk (Gatys et al.; Johnson et al.).  For tap k of sample b, A_k = the post-ReLU activation [N_k][C_k]
+ * (N_k = H_k W_k; C_k = 64, 128, 256, 512, 512):
+ *   G_k(x)[b] = A_k^T A_k / (C_k N_k),   L_style[b] = sum_k lambda_k |G_k(x)[b] - G_k(style)|_F^2.
+ * set_style: ONE style image (1,3,Hs,Ws) NCHW in [-1,1], Hs and Ws multiples of 16 but otherwise free (a Gram matrix does not depend on the frame);
+ * lambda[5] >= 0, a tap with lambda 0 is skipped everywhere.  A reference set by cgd_lpips_set_reference stays intact.
+ * style_loss_grad: one trunk forward, both heads, one trunk backward: x (B,3,H,W);  style_loss[b] = L_style[b];
+ * g (B,3,H,W) (+)= lpips_grad_scale * d(sum_b lpips_b)/dx + style_grad_scale * d(sum_b L_style[b])/dx.  lpips_loss [B] or NULL: NULL gives the style
+ * term alone and needs no reference; otherwise (B, H, W) must be the reference's.  g may not alias x.  cgd_lpips_debug_replay applies to this call too. */
+int cgd_lpips_set_style(cgd_lpips* v, const float* style_nchw, int Hs, int Ws, const float* lambda /* [5] */, void* stream);
+int cgd_lpips_style_loss_grad(cgd_lpips* v, const float* x_nchw, int B, int H, int W, float lpips_grad_scale, float style_grad_scale,
+                              float* lpips_loss /* [B] or NULL */, float* style_loss /* [B] */, float* g_nchw, int accumulate, void* stream);
 
 /* ---- Secondary diffusion model (SecondaryDiffusionImageNet2 of Katherine Crowson's CLIP-guided diffusion notebooks / Disco Diffusion): a
  *      small convolutional denoiser that predicts the clean image for the guidance losses, so that their gradient returns to x through ~50
@@ -528,6 +539,9 @@ int cgd_ddim_reverse_update(cgd_ctx* ctx, const float* x, const float* model_out
  * CGD_KGEMM policy knobs.  splitk: >= 1 slices (1 = automatic), -1 = one slice, never split automatically. */
 int cgd_op_gemm(cgd_ctx* ctx, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias, const float* R,
                 int ldr, int M, int N, int K, float alpha, int force_tile, int splitk, void* stream);
+/* G[b] = scale * A_b^T A_b for A [B * N][C] (row stride lda >= C, a multiple of 4; 16-byte aligned), C in {64, 128, 256, 512}, any N >= 1: the tall-skinny
+ * contraction of the style loss (csrc/gram.hip).  Exact fp32 products whatever the context precision; bit-identical from run to run. */
+int cgd_op_gram(cgd_ctx* ctx, const float* A, int lda, int B, int N, int C, float scale, float* G_out /* [B][C][C] */, void* stream);
 /* dx[M][N] = A[M][K] W[N][K]^T (+ add[M][N]) + the backward of a GroupNorm + SiLU over the same M = B * HW rows: dz silu'(x a + b) A1 - (x - mean) A2 - A3
  * per element, coef = [B][N][4] {a, b, unused, mean}, bcoef = [B][N][4] {A1, A2, A3, unused} (what cgd_op_gn_bwd computes internally).  One launch of
  * the weight GEMM kernel (W re-packed per call) whose epilogue applies the norm: a ResBlock's 1x1 skip dgrad and GN1's backward.  bf16x3 contexts only;

@@ -40,6 +40,9 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
     # "upsample=IMAGE" (an extension like "invert=IMAGE"): run the super-resolution checkpoint of image_size on IMAGE; refused before
     # anything is loaded at other sizes, without class conditioning, or together with "invert="
     upsample = script_util.check_init_upsample(init_image, image_size, class_cond)
+    # "ilvrN=IMAGE" / "ilvrN@U=IMAGE" (likewise): ILVR, sampling conditioned on IMAGE's low frequencies; refused before anything is loaded
+    # together with a mask, "invert=" or "upsample=", or when N does not divide both frame sides
+    ilvr_spec = script_util.check_init_ilvr(init_image, image_size, height_offset, width_offset)
     if init_image and script_util.split_init_invert(script_util.split_init_mask(init_image)[0])[1]:
         # refused before anything is loaded
         # the inverted latent is a start state of the deterministic loops only ('dpmsdeN' draws a noise per step; tested before 'dpm')
@@ -151,12 +154,17 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         init_image, invert = script_util.split_init_invert(init_image)
         # "upsample=IMAGE": IMAGE at a quarter of the frame conditions the super-resolution model; at the full frame it stays the init image
         init_image, _ = script_util.split_init_upsample(init_image)
+        # "ilvrN=IMAGE": IMAGE at the run's frame is the reference of ILVR; it also stays the ordinary init image
+        init_image, _ = script_util.split_init_ilvr(init_image)
         source = Image.open(script_util.fetch(init_image)).convert("RGB")
         pil = source.resize((image_size, image_size))
         init_tensor = th.from_numpy(np.array(pil)).float().div(255).permute(2, 0, 1).to(device).unsqueeze(0).mul(2).sub(1)
         if upsample:
             small = source.resize(((image_size + width_offset) // 4, (image_size + height_offset) // 4))
             low_res_tensor = th.from_numpy(np.array(small)).float().div(255).permute(2, 0, 1).to(device).unsqueeze(0).mul(2).sub(1)
+        if ilvr_spec is not None:  # at the run's frame, as the style image
+            pil = source.resize((image_size + width_offset, image_size + height_offset), Image.LANCZOS)
+            ilvr_tensor = th.from_numpy(np.array(pil)).float().div(255).permute(2, 0, 1).to(device).unsqueeze(0).mul(2).sub(1)
         if mask_image is not None:
             pil = Image.open(script_util.fetch(mask_image)).convert("L").resize((image_size, image_size))
             mask_tensor = th.from_numpy(np.array(pil)).float().div(255).to(device)[None, None]
@@ -246,6 +254,8 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         loop = functools.partial(diffusion.dpmpp_sample_loop_progressive, order=2, eta=0.0)
     else:
         loop = diffusion.ddim_sample_loop_progressive if timestep_respacing.startswith("ddim") else diffusion.p_sample_loop_progressive
+    if ilvr_spec is not None:
+        loop = functools.partial(loop, ilvr=(ilvr_tensor, ilvr_spec[0], script_util.ilvr_stop(ilvr_spec[1], diffusion.num_timesteps)))
     if threshold is not None:  # only with 'dpmN' / 'dpmsdeN' (split_threshold)
         loop = functools.partial(loop, threshold=threshold[0] if threshold[1] is None else threshold)
     try:
@@ -316,7 +326,7 @@ _CLI_SPEC = f"""
 --prompts -txts str "" | text prompts with optional weights, pipe-separated: 'a cat:0.5|a dog:-0.5'; 'SOURCE CAPTION=>TARGET CAPTION[:weight]' is a direction prompt (needs --init_image): the change of the image's CLIP embedding relative to the init image is steered along the change from the source to the target caption (e.g. 'a photo of a cat=>a photo of a dog:1.5'); weights of all prompts are normalised together
 --image_prompts -imgs str "" | image prompts (paths or URLs) with optional weights, pipe-separated; one entry may be 'style=FILE[:SCALE]': FILE is then no CLIP prompt but the style image of the VGG16 Gram-matrix style loss (texture and palette statistics of relu1_2 .. relu4_3, Gatys / Johnson), resized to the frame, SCALE the weight of that loss (default 1, positive; it does not enter the prompt weights); frame sides must be multiples of 16; works with or without prompts and with --init_image / --init_scale
 --image_size -size int 128 | resolution of the diffusion checkpoint: 64, 128, 256 or 512
---init_image -init str "" | start from this image (needs --skip_timesteps); IMAGE::MASK regenerates the white part of MASK and keeps the black part of IMAGE; invert=IMAGE (or invert=IMAGE::MASK, with -respace ddimN / plmsN / dpmN) starts from the DDIM-inverted latent of IMAGE; upsample=IMAGE (or upsample=IMAGE::MASK, with --image_size 256 or 512, not with --uncond or invert=) runs the 64->256 / 128->512 super-resolution checkpoint conditioned on IMAGE at a quarter of the frame, IMAGE at the full frame staying the init image; in every form IMAGE is also the source image of 'SOURCE=>TARGET' direction prompts
+--init_image -init str "" | start from this image (needs --skip_timesteps); IMAGE::MASK regenerates the white part of MASK and keeps the black part of IMAGE; invert=IMAGE (or invert=IMAGE::MASK, with -respace ddimN / plmsN / dpmN) starts from the DDIM-inverted latent of IMAGE; upsample=IMAGE (or upsample=IMAGE::MASK, with --image_size 256 or 512, not with --uncond or invert=) runs the 64->256 / 128->512 super-resolution checkpoint conditioned on IMAGE at a quarter of the frame, IMAGE at the full frame staying the init image; ilvrN=IMAGE or ilvrN@U=IMAGE (N a power of two in [2, 64] that divides both frame sides, U in (0, 1], default 1; not with ::MASK, invert= or upsample=) conditions sampling on the low frequencies of IMAGE (ILVR): after every step of the first fraction U of the run the band that survives a resize down by N and back up is replaced by that of IMAGE noised to the step's level, IMAGE staying the init image; in every form IMAGE is also the source image of 'SOURCE=>TARGET' direction prompts
 --init_scale -is int 0 | weight of the LPIPS-VGG16 term that keeps the sample close to the init image
 --skip_timesteps -skip int 0 | how many of the (respaced) timesteps to skip at the noisy end
 --prefix -dir path outputs | directory for the PNG frames

@@ -6,6 +6,7 @@ the guided sampler instead of guided_diffusion's (UNetModel, SpacedDiffusion).  
 network retry machinery are outside the hot-path scope (control plane) and kept minimal.
 """
 import io
+import math
 import os
 import time
 import re
@@ -135,6 +136,65 @@ def check_init_upsample(init_image, image_size, class_cond):
     if not class_cond:
         raise ValueError("init image 'upsample=...' does not work with --uncond: both upsamplers are class-conditional")
     return True
+
+
+ILVR_PREFIX = "ilvr"
+
+
+def split_init_ilvr(image_part):
+    """'ilvrN=IMAGE' -> (IMAGE, (N, 1.0)); 'ilvrN@U=IMAGE' -> (IMAGE, (N, U)); anything else -> (value, None).  Takes the image part
+    split_init_mask returns, next to split_init_invert: the request to condition sampling on IMAGE's low frequencies (ILVR,
+    GuidedSampler's ilvr=) rides on --init_image / init_image=.  N, the down-sampling factor, is a power of two in [2, 64]; U in (0, 1] is
+    the fraction of the run after which the refinement ends (ilvr_stop)."""
+    image_part = str(image_part)
+    m = re.match(r"ilvr([^=/]*)=(.*)$", image_part, flags=re.S)
+    if not m:
+        return image_part, None
+    spec, image = m.groups()
+    factor, sep, until = spec.partition("@")
+    try:
+        if not factor.isdigit() or (sep and not until):
+            raise ValueError(spec)
+        factor, until = int(factor), (float(until) if sep else 1.0)
+    except ValueError:
+        raise ValueError(f"init image {image_part!r}: 'ilvrN=IMAGE' or 'ilvrN@U=IMAGE' takes an integer N and a number U "
+                         "(e.g. ilvr8=a.png or ilvr8@0.8=a.png)") from None
+    if not 2 <= factor <= 64 or factor & (factor - 1):
+        raise ValueError(f"init image {image_part!r}: the factor N of 'ilvrN=IMAGE' must be a power of two in [2, 64]")
+    if not 0.0 < until <= 1.0:
+        raise ValueError(f"init image {image_part!r}: the U of 'ilvrN@U=IMAGE' must lie in (0, 1]")
+    if not image:
+        raise ValueError(f"init image {image_part!r}: 'ilvrN=IMAGE' needs an image")
+    return image, (factor, until)
+
+
+def ilvr_stop(until, num_timesteps):
+    """The step index below which ILVR no longer refines: ceil((1 - U) num_timesteps), the product rounded to nine places first so that
+    a U such as 0.7 does not land one index high"""
+    return int(math.ceil(round((1.0 - until) * num_timesteps, 9)))
+
+
+def check_init_ilvr(init_image, image_size, height_offset=0, width_offset=0):
+    """(N, U) when `init_image` asks for ILVR ('ilvrN[@U]=IMAGE'), else None, after refusing, before anything is loaded, what is not
+    built: a mask ('::MASK'), 'invert=' or 'upsample=' next to it in either order, and a factor that does not divide both frame sides."""
+    if not init_image:
+        return None
+    part, mask = split_init_mask(init_image)
+    image, spec = split_init_ilvr(part)
+    if spec is None:
+        for prefix in (INVERT_PREFIX, UPSAMPLE_PREFIX):
+            if part.startswith(prefix) and split_init_ilvr(part[len(prefix):])[1] is not None:
+                raise ValueError(f"init image {init_image!r}: 'ilvrN=' cannot be combined with '{prefix}'")
+        return None
+    if mask is not None:
+        raise ValueError(f"init image {init_image!r}: 'ilvrN=' cannot be combined with a mask ('::MASK'): both rewrite the state after every step")
+    for prefix in (INVERT_PREFIX, UPSAMPLE_PREFIX):
+        if image.startswith(prefix):
+            raise ValueError(f"init image {init_image!r}: 'ilvrN=' cannot be combined with '{prefix}'")
+    height, width = image_size + height_offset, image_size + width_offset
+    if height % spec[0] or width % spec[0]:
+        raise ValueError(f"init image {init_image!r}: the factor {spec[0]} does not divide the {height} x {width} frame")
+    return spec
 
 
 DIRECTION_SEP = "=>"

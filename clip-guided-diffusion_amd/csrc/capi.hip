@@ -322,6 +322,12 @@ int cgd_masked_merge(cgd_ctx* ctx, float* sample, float* x0, const float* init, 
   return cgd_launch_masked_merge(ctx, sample, x0, init, mask, n_known, n_re, x_re, B, H, W, init_batch, mask_batch, mask_channels, *k,
                                  S(stream));
 }
+long cgd_ilvr_scratch_floats(int B, int H, int W, int factor, int with_pred_xstart) { return cgd_ilvr_scratch(B, H, W, factor, with_pred_xstart); }
+int cgd_ilvr_refine(cgd_ctx* ctx, float* sample, float* x0, const float* ref, const float* noise, float* scratch, int B, int H, int W,
+                    int ref_batch, int factor, float sa, float sb, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_ilvr_refine(ctx, sample, x0, ref, noise, scratch, B, H, W, ref_batch, factor, sa, sb, S(stream));
+}
 
 int cgd_ddim_reverse_update(cgd_ctx* ctx, const float* x, const float* out6, const float* init, float* x_next, float* x0, float* noise_out,
                             int B, int H, int W, int init_batch, const cgd_reverse_coef* k, void* stream) {

@@ -143,6 +143,11 @@ struct cgd_mask_coef;
 int cgd_launch_masked_merge(cgd_ctx* ctx, float* sample, float* x0, const float* init, const float* mask, const float* n_known,
                             const float* n_re, float* x_re, int B, int H, int W, int init_batch, int mask_batch, int mask_channels,
                             const cgd_mask_coef& k, hipStream_t s);
+// ilvr.hip: the low-frequency refinement of ILVR after a sampler update (include/cgd_mi355x.h: cgd_ilvr_refine); sample and x0 (or null) are
+// refined in place; scratch: cgd_ilvr_scratch(B, H, W, factor, x0 != null) floats (0 for a shape or factor the launcher refuses)
+int cgd_launch_ilvr_refine(cgd_ctx* ctx, float* sample, float* x0, const float* ref, const float* noise, float* scratch, int B, int H, int W,
+                           int ref_batch, int factor, float sa, float sb, hipStream_t s);
+long cgd_ilvr_scratch(int B, int H, int W, int factor, int with_x0);
 // invert.hip: the update of one DDIM inversion step (include/cgd_mi355x.h: cgd_ddim_reverse_update); eps is read in place from the model's
 // 6-channel output, x0 and noise_out (with init) may be null
 struct cgd_reverse_coef;

@@ -205,6 +205,8 @@ _SIGS = {
     "cgd_dpmpp_threshold": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), i64, f32, f32, f32, vp, vp, vp]),
     "cgd_dpmpp_update_thr": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), C.POINTER(Dpmpp), vp]),
     "cgd_masked_merge": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(MaskCoef), vp]),
+    "cgd_ilvr_scratch_floats": (C.c_long, [i32, i32, i32, i32, i32]),
+    "cgd_ilvr_refine": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]),
     "cgd_ddim_reverse_update": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(ReverseCoef), vp]),
     "cgd_op_gemm": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
     "cgd_op_gemm_gn_bwd_accepts": (i32, [i32] * 12),

@@ -11,6 +11,9 @@ it with one cgd_multistep_update launch per evaluation; PLMS draws no per-step n
 Masked sampling (`mask=`, with an init image: 1 regenerates, 0 keeps) adds one cgd_masked_merge launch after every update, which puts the
 init image, noised to the level the update produced, back into the kept region; `resamples=r` repeats every step r times (RePaint with
 jump length 1).  Without a mask nothing of it runs.
+ILVR (`ilvr=(ref, factor[, stop])`; Choi et al., 2021) conditions sampling on the low frequencies of a reference image: where the masked
+merge sits, cgd_ilvr_refine (two launches, csrc/ilvr.hip) replaces the low-frequency band of the state by that of the reference noised to
+the level the update produced, at step indices >= stop.  Without `ilvr` nothing of it runs.
 DPM-Solver++(2M) (`dpmpp_sample_loop_progressive`, Lu et al., 2022; eta = 0 the ODE solver, eta > 0 the SDE solver) runs on the levels of
 'dpmN' (uniform in logSNR, diffusion.logsnr_timesteps): one guided evaluation per step and one cgd_dpmpp_update launch, which combines the
 evaluation's guided pred_xstart with the one of the step before; the two history buffers rotate by pointer.  With `threshold=` the guided
@@ -199,17 +202,21 @@ class GuidedSampler:
                 "fac_index": fac_index, "n_known": n_known}
 
     # ---- masked sampling ------------------------------------------------------------------------------
-    def _known_noise(self, masked, x):
+    def _known_noise(self, masked, x, i=None):
         """Before a step's evaluation -> (noise of the kept region for the next merge, whether _evaluate draws it instead): the loop's
         initial noise in the deterministic loops (the tensor that q_sampled the init image at the first index: the kept region follows one
         trajectory and nothing is drawn); in the stochastic loops the tape's next entry, or a fresh draw that _evaluate takes right after
-        the step's own noise.  (None, False) without a mask."""
+        the step's own noise.  (None, False) without a mask.  ILVR keeps its state in `masked` too: the reference's noise follows the
+        same rules (tape entry 'ilvr_noise'), and below its stop index, where nothing is refined, nothing is drawn."""
+        if masked is not None and "ilvr" in masked and i < masked["ilvr"][2]:
+            return None, False
         if masked is None or not masked["stochastic"]:
             return (masked["x_T"] if masked is not None else None), False
         if self.tape is None:
             return None, True
         masked["known"] += 1
-        return self.tape["known_noise"][masked["known"] - 1].to(x.device).float().contiguous(), False
+        key = "ilvr_noise" if "ilvr" in masked else "known_noise"
+        return self.tape[key][masked["known"] - 1].to(x.device).float().contiguous(), False
 
     def _renoise(self, masked, x):
         """The draw that takes a merged state back up one level (resamples > 1): the tape's next entry or a fresh one."""
@@ -235,9 +242,27 @@ class GuidedSampler:
         masked["_keep"] = (n_known, n_re)
         return x_re
 
+    def _refine(self, masked, i, sample, x0_out, n):
+        """cgd_ilvr_refine after the update of step index i >= stop: the low-frequency band of `sample` (the state at level i - 1) becomes
+        that of the reference noised to that level with `n`, the one of `x0_out` (or None) that of the reference; both in place."""
+        ctx = self.ctx
+        B, _, H, W = sample.shape
+        ref, factor, stop = masked["ilvr"]
+        if i < stop:
+            return
+        k = self.tables.mask_coef(i)
+        if k.sqrt_one_minus_ab_prev == 0.0:
+            n = None  # i == 0: the reference itself
+        ctx.check(ctx.lib.cgd_ilvr_refine(ctx.h, sample.data_ptr(), L.ptr(x0_out), ref.data_ptr(), L.ptr(n), masked["scratch"].data_ptr(),
+                                          B, H, W, ref.shape[0], factor, k.sqrt_ab_prev, k.sqrt_one_minus_ab_prev, ctx.stream()))
+        masked["_keep"] = (n,)
+
     def _masked_end(self, masked, ev, i, sample, x0_out, n_known, again=False):
         """After a step's update: the merge with the kept region's noise (`n_known`, or the one `ev` drew).  `again`: this step index runs
-        once more, the re-noised state is returned; otherwise (and without a mask, where nothing runs) None."""
+        once more, the re-noised state is returned; otherwise (and without a mask, where nothing runs) None.  Under ILVR the refinement
+        stands in the merge's place."""
+        if masked is not None and "ilvr" in masked:
+            return self._refine(masked, i, sample, x0_out, n_known if n_known is not None else ev["n_known"])
         if masked is not None:
             return self._merge(masked, i, sample, x0_out, n_known if n_known is not None else ev["n_known"],
                                self._renoise(masked, sample) if again else None)
@@ -263,13 +288,39 @@ class GuidedSampler:
         if not (lo >= 0.0 and hi <= 1.0):
             raise ValueError(f"mask values must lie in [0, 1] (1 regenerates, 0 keeps), got [{lo}, {hi}]")
 
+    def _check_ilvr(self, shape, ilvr, mask, resamples):
+        """None | (ref, factor) | (ref, factor, stop) -> None | (ref, factor, stop); refusals before anything runs"""
+        if ilvr is None:
+            return None
+        if mask is not None:
+            raise ValueError("ilvr and mask cannot be combined: both rewrite the state after every update")
+        if isinstance(resamples, int) and not isinstance(resamples, bool) and resamples > 1:
+            raise ValueError("ilvr cannot resample: resamples > 1 repeats the merge of masked sampling")
+        if not isinstance(ilvr, (tuple, list)) or len(ilvr) not in (2, 3):
+            raise ValueError("ilvr must be (ref, factor) or (ref, factor, stop)")
+        ref, factor = ilvr[0], ilvr[1]
+        stop = ilvr[2] if len(ilvr) == 3 else 0
+        B, H, W = shape[0], shape[2], shape[3]
+        if isinstance(factor, bool) or not isinstance(factor, int) or not 2 <= factor <= 64 or factor & (factor - 1):
+            raise ValueError(f"the ilvr factor must be a power of two in [2, 64], got {factor!r}")
+        if H % factor or W % factor:
+            raise ValueError(f"the ilvr factor {factor} does not divide the {H} x {W} frame")
+        if not th.is_tensor(ref) or ref.dim() != 4 or tuple(ref.shape[1:]) != (3, H, W):
+            raise ValueError(f"the ilvr reference must be (1 or {B}, 3, {H}, {W})")
+        gb = self.shard[1] if self.shard is not None else B
+        if ref.shape[0] not in (1, B, gb):
+            raise ValueError(f"the ilvr reference must be (1 or {B}, 3, {H}, {W}), got {tuple(ref.shape)}")
+        if isinstance(stop, bool) or not isinstance(stop, int) or not 0 <= stop <= self.num_timesteps:
+            raise ValueError(f"the ilvr stop index must be an int in [0, {self.num_timesteps}], got {stop!r}")
+        return ref, factor, stop
+
     def _step(self, model, x, i, cond_fn, model_kwargs, noise, mode, bufs, ahead=None, eta=0.0, masked=None, again=False):
         """One step of the p_sample (mode 0) or DDIM (mode 1) loop.  DDIM with eta > 0 runs its update through
         cgd_multistep_update (phase 3); eta == 0 keeps cgd_sample_update mode 1.  `masked`: the state of masked sampling, the update is
         followed by the merge; `again`: this step index runs once more, the merge also leaves the re-noised state in bufs['_x_re']."""
         ctx, lib = self.ctx, self.ctx.lib
         B, _, H, W = x.shape
-        n_known, draw_known = self._known_noise(masked, x)
+        n_known, draw_known = self._known_noise(masked, x, i)
         ev = self._evaluate(model, x, i, cond_fn, model_kwargs, noise, bufs, ahead, draw_known=draw_known)
         noise, g, coef = ev["noise"], ev["g"], ev["coef"]
         sample, x0_out = th.empty_like(x), th.empty_like(x)
@@ -300,7 +351,7 @@ class GuidedSampler:
         order, old = st["order"], st["old_eps"]
         eps_new = st["free"].pop() if st["free"] else th.empty_like(x)
         sample, x0_out = th.empty_like(x), th.empty_like(x)
-        n_known, _ = self._known_noise(masked, x)  # never stochastic: the loop's initial noise
+        n_known, _ = self._known_noise(masked, x, i)  # never stochastic: the loop's initial noise
         ev = self._evaluate(model, x, i, cond_fn, model_kwargs, None, bufs, draw_noise=False)
         g = ev["g"]
         if order > 1 and not old:
@@ -345,7 +396,7 @@ class GuidedSampler:
         predictions.  The buffer, the (B, 3) result and the selection's scratch live in `bufs`, allocated once per loop."""
         ctx, lib = self.ctx, self.ctx.lib
         B, _, H, W = x.shape
-        n_known, draw_known = self._known_noise(masked, x)
+        n_known, draw_known = self._known_noise(masked, x, i)
         ev = self._evaluate(model, x, i, cond_fn, model_kwargs, noise, bufs, ahead, draw_noise=bool(eta), draw_known=draw_known)
         noise, g, hist = ev["noise"], ev["g"], st["hist"]
         d = self.tables.dpmpp_coef(i, 2 if (st["order"] == 2 and hist is not None) else 1, eta)
@@ -386,10 +437,12 @@ class GuidedSampler:
             raise NotImplementedError("the reference passes cond_fn_with_grad=True (cgd.py:260)")
 
     def _loop(self, mode, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-              randomize_class, cond_fn_with_grad, eta=0.0, plms_order=None, mask=None, resamples=1, dpm_order=None, threshold=None):
+              randomize_class, cond_fn_with_grad, eta=0.0, plms_order=None, mask=None, resamples=1, dpm_order=None, threshold=None,
+              ilvr=None):
         """mode 0 p_sample, 1 DDIM (eta > 0: stochastic DDIM), 2 PLMS of order `plms_order` (no per-step noise), 3 DPM-Solver++(2M) of
         order `dpm_order` (eta > 0: the SDE solver, with a per-step noise; `threshold` (p, cap): dynamic thresholding).  `mask` (with `init_image`): masked sampling, every step
-        index > 0 `resamples` times."""
+        index > 0 `resamples` times.  `ilvr` (ref, factor, stop), checked by _check_ilvr: every update of a step index >= stop is followed by
+        the low-frequency refinement."""
         self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
         device = th.device(device or f"cuda:{self.ctx.device}")
         tape = self.tape
@@ -410,6 +463,15 @@ class GuidedSampler:
             # 'stochastic': the kept region gets a fresh noise per merge; otherwise it keeps the loop's initial noise, img as it is here
             masked = {"init": init_image.to(device).float().contiguous(), "mask": mask.to(device).float().contiguous(),
                       "x_T": img.contiguous(), "stochastic": mode == 0 or (mode in (1, 3) and bool(eta)), "known": 0, "re": 0}
+        if ilvr is not None:
+            # the masked merge's state with the reference in the init image's place; the scratch of the two launches lives as long as the loop
+            ref, factor, stop = ilvr
+            if self.shard is not None and ref.shape[0] == self.shard[1] and ref.shape[0] != 1:
+                ref = ref[self.shard[0]]  # a reference of the global batch: this rank's rows
+            B, _, H, W = img.shape
+            masked = {"ilvr": (ref.to(device).float().contiguous(), factor, stop), "x_T": img.contiguous(),
+                      "stochastic": mode == 0 or (mode in (1, 3) and bool(eta)), "known": 0,
+                      "scratch": th.empty(int(self.ctx.lib.cgd_ilvr_scratch_floats(B, H, W, factor, 1)), device=device, dtype=th.float32)}
         indices = list(range(self.num_timesteps - skip_timesteps))[::-1]
         if init_image is not None:
             t0 = indices[0]
@@ -484,53 +546,65 @@ class GuidedSampler:
 
     def p_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                   model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
-                                  randomize_class=False, cond_fn_with_grad=False, mask=None, resamples=1):
+                                  randomize_class=False, cond_fn_with_grad=False, mask=None, resamples=1, ilvr=None):
         """`mask` ((1 or B, 1 or 3, H, W) in [0, 1], with `init_image`): masked sampling, 1 regenerates and 0 keeps the init image;
-        `resamples`: how often every step index > 0 runs (RePaint with jump length 1)."""
+        `resamples`: how often every step index > 0 runs (RePaint with jump length 1).
+        `ilvr`: None, (ref, factor) or (ref, factor, stop): ILVR, after every update of a step index >= stop (default 0) the low-frequency
+        band of the state (the antialiased cubic resize down by `factor`, a power of two in [2, 64] that divides H and W, and back up)
+        is replaced by that of `ref` ((1 or B, 3, H, W) in [-1, 1]) noised to the level the update produced, with a fresh draw per
+        refinement.  Not together with `mask` or `resamples` > 1."""
+        ilvr = self._check_ilvr(shape, ilvr, mask, resamples)
         self._check_mask(shape, init_image, mask, resamples)
         return self._loop(0, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad, mask=mask, resamples=resamples)
+                          randomize_class, cond_fn_with_grad, mask=mask, resamples=resamples, ilvr=ilvr)
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None,
-                                     randomize_class=False, cond_fn_with_grad=False, mask=None, resamples=1):
+                                     randomize_class=False, cond_fn_with_grad=False, mask=None, resamples=1, ilvr=None):
         """eta == 0 (what the reference passes): cgd_sample_update mode 1.  eta > 0: ddim_sample_with_grad's sigma term with the
         per-step noise draw of this loop, through cgd_multistep_update.  `mask`, `resamples`: as in p_sample_loop_progressive; with
-        eta == 0 the kept region is noised with the loop's initial noise throughout and a masked run stays deterministic."""
+        eta == 0 the kept region is noised with the loop's initial noise throughout and a masked run stays deterministic.  `ilvr`: as in
+        p_sample_loop_progressive; with eta == 0 the reference is noised with the loop's initial noise and nothing is drawn."""
         eta = float(eta)
         if not eta >= 0.0:
             raise ValueError(f"eta must be >= 0, got {eta}")
+        ilvr = self._check_ilvr(shape, ilvr, mask, resamples)
         self._check_mask(shape, init_image, mask, resamples)
         return self._loop(1, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad, eta=eta, mask=mask, resamples=resamples)
+                          randomize_class, cond_fn_with_grad, eta=eta, mask=mask, resamples=resamples, ilvr=ilvr)
 
     def plms_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
-                                     randomize_class=False, cond_fn_with_grad=False, order=2, mask=None, resamples=1):
+                                     randomize_class=False, cond_fn_with_grad=False, order=2, mask=None, resamples=1, ilvr=None):
         """PLMS (pseudo linear multistep, Liu et al., ICLR 2022) as the guided_diffusion fork's `plms_sample_loop_progressive`:
         a first step of pseudo improved Euler (two guided evaluations, at t and at t-1) when order > 1, Adams-Bashforth of up to
         `order` eps terms afterwards.  No per-step noise.  A schedule of a single step with order > 1 would evaluate at t = -1 and is
         refused (the fork indexes its tables with -1 there).  `mask`: masked sampling as in p_sample_loop_progressive, the kept region
-        noised with the loop's initial noise; `resamples` > 1 is refused (the eps history would mix noise levels)."""
+        noised with the loop's initial noise; `resamples` > 1 is refused (the eps history would mix noise levels).  `ilvr`: as in
+        ddim_sample_loop_progressive with eta == 0; the start step's predictor is refined before its second evaluation, the eps history
+        stays as evaluated."""
         if isinstance(order, bool) or not isinstance(order, int) or not 1 <= order <= 4:
             raise ValueError(f"order is invalid (should be int from 1-4): {order!r}")
         self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
         if order > 1 and self.num_timesteps - skip_timesteps < 2:
             raise ValueError(f"PLMS of order {order} needs at least two timesteps: its first step also evaluates at t - 1")
+        ilvr = self._check_ilvr(shape, ilvr, mask, resamples)
         self._check_mask(shape, init_image, mask, resamples, plms=True)
         return self._loop(2, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad, plms_order=order, mask=mask)
+                          randomize_class, cond_fn_with_grad, plms_order=order, mask=mask, ilvr=ilvr)
 
     def dpmpp_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                       model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
-                                      randomize_class=False, cond_fn_with_grad=False, order=2, eta=0.0, mask=None, resamples=1, threshold=None):
+                                      randomize_class=False, cond_fn_with_grad=False, order=2, eta=0.0, mask=None, resamples=1, threshold=None,
+                                      ilvr=None):
         """DPM-Solver++(2M) (Lu et al., 2022: data prediction, multistep): one guided evaluation per step; the update extrapolates the guided
         pred_xstart with the one of the step before (`order` 2; the first step and step index 0 run at order 1; `order` 1 is DDIM with the
         same eta for eta in {0, 1}).  eta == 0: the deterministic solver, no per-step noise.  eta > 0: the SDE solver (eta = 1 is
         SDE-DPM-Solver++(2M)), one noise draw per evaluation before cond_fn, as in DDIM with eta.  Meant for tables spaced uniformly in
         logSNR (timestep_respacing 'dpmN'); on the integer-stride levels of 'ddimN' the second order gains nothing below about 50 steps
         (DESIGN.md).  `mask`: masked sampling as in ddim_sample_loop_progressive (eta == 0: the kept region is noised with the loop's
-        initial noise); `resamples` > 1 is refused: a resampled history would mix noise levels.
+        initial noise); `resamples` > 1 is refused: a resampled history would mix noise levels.  `ilvr`: as in
+        ddim_sample_loop_progressive (a fresh draw per refinement with eta > 0); the pred_xstart history stays as evaluated.
         `threshold`: None, p, or (p, cap): dynamic thresholding of the guided pred_xstart (Saharia et al., 2022).  Per sample, s = the
         p-quantile of |guided pred_xstart| (p in (0, 1]; torch.quantile's 'linear' rule, selected exactly on the device), raised to at least 1
         and lowered to at most `cap` (>= 1; none when not given); the prediction is clamped to [-s, s] and divided by s before the update, and
@@ -544,10 +618,11 @@ class GuidedSampler:
         if isinstance(resamples, int) and not isinstance(resamples, bool) and resamples > 1:
             raise ValueError("DPM-Solver++ cannot resample: its pred_xstart history would mix noise levels (use the DDIM loop, "
                              "ddim_sample_loop_progressive, for resamples > 1)")
+        ilvr = self._check_ilvr(shape, ilvr, mask, resamples)
         self._check_mask(shape, init_image, mask, resamples)
         threshold = self._check_threshold(threshold)
         return self._loop(3, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad, eta=float(eta), mask=mask, dpm_order=order, threshold=threshold)
+                          randomize_class, cond_fn_with_grad, eta=float(eta), mask=mask, dpm_order=order, threshold=threshold, ilvr=ilvr)
 
     @staticmethod
     def _check_threshold(threshold):

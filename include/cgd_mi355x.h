@@ -507,6 +507,25 @@ int cgd_masked_merge(cgd_ctx* ctx, float* sample, float* pred_xstart, const floa
                      const float* n_re, float* x_re, int B, int H, int W, int init_batch, int mask_batch, int mask_channels,
                      const cgd_mask_coef* k, void* stream);
 
+/* ---- ILVR (Choi et al., 2021): sampling conditioned on the low frequencies of a reference image; the refinement after a sampler update
+ *      at step index t, in two launches whatever B.  Per axis of extent n and factor N, D is the (n/N, n) antialiased cubic down-resize
+ *      and U the (n, n/N) cubic up-resize of cgd_cutouts_resize_weights (ResizeRight, pad_mode='constant': taps outside the extent read
+ *      zero, rows are not renormalised), P = U D and phi(z) = P_H z P_W^T per plane.  The update left `sample` (the state at level t-1)
+ *      and `pred_xstart`:
+ *        known        = sa ref + sb noise            (sa = sqrt(abar_{t-1}), sb = sqrt(1 - abar_{t-1}); two rounded products and a
+ *                                                     rounded sum, not fused)
+ *        sample      += phi(known - sample)
+ *        pred_xstart += phi(ref   - pred_xstart)
+ *      both in place; a correction that is exactly zero leaves the bits of its pixel alone.  Gather form, fixed summation order: the
+ *      same bits on every run.  sample, pred_xstart, noise: (B,3,H,W); ref: (ref_batch,3,H,W), ref_batch 1 or B; scratch:
+ *      cgd_ilvr_scratch_floats(B, H, W, factor, pred_xstart != NULL) floats (0 for a shape or factor that is refused).  pred_xstart
+ *      may be NULL; noise only when sb == 0 (t == 0; it is not read then).  Any 4-byte-aligned pointers are accepted.  Returns -2
+ *      (cgd_last_error), before any launch, for a missing sample, ref or scratch, a factor that is not a power of two in [2, 64] or
+ *      does not divide H and W, a ref_batch other than 1 or B, a missing noise with sb != 0, or a non-positive size. ---- */
+long cgd_ilvr_scratch_floats(int B, int H, int W, int factor, int with_pred_xstart);
+int cgd_ilvr_refine(cgd_ctx* ctx, float* sample, float* pred_xstart, const float* ref, const float* noise, float* scratch, int B, int H,
+                    int W, int ref_batch, int factor, float sa, float sb, void* stream);
+
 /* ---- DDIM inversion of an init image (guided_diffusion's ddim_reverse_sample, unguided, clip_denoised=False): the update of one inversion
  *      step, from level t up to level t+1 along the deterministic DDIM ODE, in one launch after the UNet forward:
  *        eps         = model_out6[:, 0:3]                 (read in place: plane b * 6 + c; the variance planes 3..5 are never touched)

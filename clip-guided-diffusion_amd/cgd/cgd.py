@@ -13,7 +13,7 @@ from pathlib import Path
 import torch as th
 from tqdm.auto import tqdm
 
-from cgd_amd import shard
+from cgd_amd import nets, shard
 from cgd_amd.guidance import ClipGuidance
 
 from . import clip_util, script_util
@@ -34,6 +34,11 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         print(f"device: {device}")
     if "cuda" not in device:
         raise ValueError(f"device {device!r}: this build runs the sampling step on an MI355X only (PyTorch-ROCm reports 'cuda')")
+    # "...+windows=STRIDE[:wrapx|:wrapy|:wrap][:feather]" (an extension like "plmsN", the last suffix): windowed sampling, the model runs on
+    # overlapping image_size windows of the image_size + offsets frame; a bad stride or frame, or a combination with "upsample=", "invert=" or
+    # "+classifier=", is refused before anything is loaded
+    timestep_respacing, windows_spec = script_util.split_windows(timestep_respacing, image_size, height_offset, width_offset, init_image,
+                                                                 clip_model_name)
     # "dpmN+thr=P[:CAP]" (an extension like "plmsN"): dynamic thresholding of the guided pred_xstart; refused on any other spacing, before
     # anything is loaded.  The tables are built from the spacing without the suffix
     timestep_respacing, threshold = script_util.split_threshold(timestep_respacing)
@@ -197,6 +202,8 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         gd_model, diffusion = script_util.load_guided_diffusion(
             checkpoint_path=diffusion_path, image_size=image_size, class_cond=class_cond, diffusion_steps=diffusion_steps,
             timestep_respacing=timestep_respacing, use_fp16=True, device=device, noise_schedule=noise_schedule, dropout=dropout)
+    if windows_spec is not None:  # ClipGuidance and the loop see the wrapper; the loader's cache keeps the bare handle
+        gd_model = nets.WindowedUNet(gd_model, stride=windows_spec[0], wrap=windows_spec[1], feather=windows_spec[2])
     # (a collective like the loads above: before the early return of a rank without samples)
     secondary = clip_util.load_secondary(gd_model.ctx, secondary_path, device) if secondary_path is not None else None
     classifier = None
@@ -339,7 +346,7 @@ _CLI_SPEC = f"""
 --seed -seed int 0 | RNG seed
 --save_frequency -freq int 1 | write a frame every N steps
 --diffusion_steps -steps int 1000 | length of the training schedule
---timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', 'plmsN' for PLMS (e.g. -respace plms50), or 'dpmN' / 'dpmsdeN' for DPM-Solver++(2M) / its SDE form on at most N logSNR-uniform levels (e.g. -respace dpm20); 'dpmN+thr=P' or 'dpmsdeN+thr=P:CAP' adds dynamic thresholding of the guided prediction: per sample it is clamped to its own P-quantile of absolute values s (at least 1, at most CAP) and divided by s (e.g. -respace dpm20+thr=0.995; CAP 1 is the static clip to [-1, 1])
+--timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', 'plmsN' for PLMS (e.g. -respace plms50), or 'dpmN' / 'dpmsdeN' for DPM-Solver++(2M) / its SDE form on at most N logSNR-uniform levels (e.g. -respace dpm20); 'dpmN+thr=P' or 'dpmsdeN+thr=P:CAP' adds dynamic thresholding of the guided prediction: per sample it is clamped to its own P-quantile of absolute values s (at least 1, at most CAP) and divided by s (e.g. -respace dpm20+thr=0.995; CAP 1 is the static clip to [-1, 1]); a last suffix '+windows=STRIDE[:wrapx|:wrapy|:wrap][:feather]' (e.g. -respace 250+windows=128:wrapx with --width_offset 256) samples a frame larger than the checkpoint in windows (MultiDiffusion): the model runs on overlapping --image_size windows STRIDE pixels apart (a positive multiple of 8, at most --image_size; frame sides multiples of 8) and their predictions are averaged, with sin^2 weights under :feather; :wrapx / :wrapy / :wrap let windows run over the right / bottom / both edges, so the result tiles seamlessly along that axis (STRIDE must divide its length); not with upsample=, invert= or +classifier=
 --num_cutouts -cutn int 16 | random cutouts shown to CLIP per step
 --cutout_power -cutpow float 1.0 | exponent of the cutout size distribution
 --clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, ARCH=FILE for an open_clip ViT checkpoint (ARCH: ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14, optional -quickgelu suffix), 'A+B' to sum two towers, 'A+secondary=FILE' to guide through the secondary model FILE, 'A+classifier=FILE:CLASS[:SCALE]' for classifier guidance toward ImageNet class CLASS with the noisy classifier FILE (weight SCALE, default 1; with a class-conditional model y is held at CLASS; needs zero height / width offsets), or 'A+cuts=OV:IN' (or 'cuts=OV:IN/OV2:IN2': the second pair once 40 percent of the run is done) for OV whole-frame and IN random cutouts per step through the antialiased cubic resize (--num_cutouts then only affects image prompts)

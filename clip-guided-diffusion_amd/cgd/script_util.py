@@ -85,6 +85,53 @@ def split_threshold(respacing):
     return spec, (p, cap)
 
 
+WINDOWS_SEP = "+windows="
+
+
+def split_windows(respacing, image_size=None, height_offset=0, width_offset=0, init_image=None, clip_model_name=""):
+    """'250+windows=STRIDE[:wrapx|:wrapy|:wrap][:feather]' -> (the spacing without the suffix, (STRIDE, wrap, feather)) with wrap in '', 'x',
+    'y', 'xy'; a value without '+windows=' -> (value, None).  Windowed sampling (nets.WindowedUNet: the model runs on overlapping windows of
+    image_size, STRIDE apart, whose predictions are averaged over the image_size + offsets frame; a wrapping axis tiles seamlessly) rides on
+    --timestep_respacing / timestep_respacing= as its last suffix: what is returned still carries a '+thr=' for split_threshold.  Refuses a
+    malformed suffix and, when `image_size` is given, before anything is loaded: a STRIDE that is no positive multiple of 8 or exceeds
+    image_size, frame sides that are no multiples of 8, wrap on an axis whose length STRIDE does not divide, and any combination with
+    'upsample=', 'invert=' (`init_image`) or '+classifier=' (`clip_model_name`)."""
+    respacing = str(respacing)
+    spec, sep, value = respacing.partition(WINDOWS_SEP)
+    if not sep:
+        return respacing, None
+    usage = f"timestep_respacing {respacing!r}: '+windows=' takes STRIDE[:wrapx|:wrapy|:wrap][:feather] (e.g. 250+windows=128:wrapx)"
+    parts = value.split(":")
+    if not spec or not parts[0].isdigit():
+        raise ValueError(usage)
+    stride, rest = int(parts[0]), parts[1:]
+    feather = bool(rest) and rest[-1] == "feather"
+    if feather:
+        rest = rest[:-1]
+    if len(rest) > 1 or (rest and rest[0] not in ("wrapx", "wrapy", "wrap")):
+        raise ValueError(usage)
+    wrap = {"wrapx": "x", "wrapy": "y", "wrap": "xy"}[rest[0]] if rest else ""
+    if stride <= 0 or stride % 8:
+        raise ValueError(f"timestep_respacing {respacing!r}: the STRIDE of '+windows=' must be a positive multiple of 8")
+    if image_size is not None:
+        if stride > image_size:
+            raise ValueError(f"timestep_respacing {respacing!r}: the STRIDE of '+windows=' exceeds the window, image_size {image_size}")
+        height, width = image_size + height_offset, image_size + width_offset
+        if height % 8 or width % 8 or height < image_size or width < image_size:
+            raise ValueError(f"timestep_respacing {respacing!r}: '+windows=' needs frame sides that are multiples of 8 and at least image_size "
+                             f"{image_size}, got {height} x {width}")
+        for axis, length in (("x", width), ("y", height)):
+            if axis in wrap and length % stride:
+                raise ValueError(f"timestep_respacing {respacing!r}: STRIDE {stride} does not divide the wrapping {axis} axis of length {length}")
+        part = split_init_mask(init_image)[0] if init_image else ""
+        for prefix in (UPSAMPLE_PREFIX, INVERT_PREFIX):
+            if part.startswith(prefix):
+                raise ValueError(f"timestep_respacing {respacing!r}: '+windows=' cannot be combined with init image '{prefix}...'")
+        if "+classifier=" in str(clip_model_name):
+            raise ValueError(f"timestep_respacing {respacing!r}: '+windows=' cannot be combined with '+classifier=' (the classifier is not windowed)")
+    return spec, (stride, wrap, feather)
+
+
 INVERT_PREFIX = "invert="
 
 

@@ -329,6 +329,17 @@ int cgd_ilvr_refine(cgd_ctx* ctx, float* sample, float* x0, const float* ref, co
   return cgd_launch_ilvr_refine(ctx, sample, x0, ref, noise, scratch, B, H, W, ref_batch, factor, sa, sb, S(stream));
 }
 
+int cgd_window_gather(cgd_ctx* ctx, const float* full, float* win, const int* oy, int ny, const int* ox, int nx, const float* ay, const float* ax,
+                      int B, int C, int H, int W, int S, int wrap, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_window_gather(ctx, full, win, oy, ny, ox, nx, ay, ax, B, C, H, W, S, wrap, S(stream));
+}
+int cgd_window_merge(cgd_ctx* ctx, const float* win, float* full, const int* oy, int ny, const int* ox, int nx, const float* ay, const float* ax,
+                     int B, int C, int H, int W, int S, int wrap, int accumulate, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_window_merge(ctx, win, full, oy, ny, ox, nx, ay, ax, B, C, H, W, S, wrap, accumulate, S(stream));
+}
+
 int cgd_ddim_reverse_update(cgd_ctx* ctx, const float* x, const float* out6, const float* init, float* x_next, float* x0, float* noise_out,
                             int B, int H, int W, int init_batch, const cgd_reverse_coef* k, void* stream) {
   CGD_NEED_CTX(ctx);

@@ -148,6 +148,12 @@ int cgd_launch_masked_merge(cgd_ctx* ctx, float* sample, float* x0, const float*
 int cgd_launch_ilvr_refine(cgd_ctx* ctx, float* sample, float* x0, const float* ref, const float* noise, float* scratch, int B, int H, int W,
                            int ref_batch, int factor, float sa, float sb, hipStream_t s);
 long cgd_ilvr_scratch(int B, int H, int W, int factor, int with_x0);
+// window.hip: the adjoint pair of windowed sampling (include/cgd_mi355x.h: cgd_window_gather / cgd_window_merge); oy [ny], ox [nx]: host arrays of
+// window origins; ay [ny][S], ax [nx][S]: device weight tables, both or neither (null = ones)
+int cgd_launch_window_gather(cgd_ctx* ctx, const float* full, float* win, const int* oy, int ny, const int* ox, int nx, const float* ay,
+                             const float* ax, int B, int C, int H, int W, int S, int wrap, hipStream_t s);
+int cgd_launch_window_merge(cgd_ctx* ctx, const float* win, float* full, const int* oy, int ny, const int* ox, int nx, const float* ay,
+                            const float* ax, int B, int C, int H, int W, int S, int wrap, int accumulate, hipStream_t s);
 // invert.hip: the update of one DDIM inversion step (include/cgd_mi355x.h: cgd_ddim_reverse_update); eps is read in place from the model's
 // 6-channel output, x0 and noise_out (with init) may be null
 struct cgd_reverse_coef;

@@ -207,6 +207,8 @@ _SIGS = {
     "cgd_masked_merge": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(MaskCoef), vp]),
     "cgd_ilvr_scratch_floats": (C.c_long, [i32, i32, i32, i32, i32]),
     "cgd_ilvr_refine": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]),
+    "cgd_window_gather": (i32, [vp, vp, vp, C.POINTER(i32), i32, C.POINTER(i32), i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "cgd_window_merge": (i32, [vp, vp, vp, C.POINTER(i32), i32, C.POINTER(i32), i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_ddim_reverse_update": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(ReverseCoef), vp]),
     "cgd_op_gemm": (i32, [vp, vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
     "cgd_op_gemm_gn_bwd_accepts": (i32, [i32] * 12),

@@ -221,6 +221,112 @@ class UNetFunction(th.autograd.Function):
         return ctx.unet.dgrad(g.contiguous()), None, None, None
 
 
+class WindowedUNet:
+    """Windowed sampling (MultiDiffusion, Bar-Tal et al., 2023) as a model wrapper: a frame larger than the checkpoint's trained size is cut
+    into overlapping windows of that size (windows.WindowPlan: `stride` apart, the last one flush with the edge; `wrap` in '', 'x', 'y',
+    'xy' lets them run over the right / bottom edge and continue at 0, which makes the frame tile along that axis).  `forward` gathers the
+    windows of `x` (cgd_window_gather), runs the wrapped net on all of them as one batch and averages the window outputs, all channels alike,
+    into one prediction for the frame (cgd_window_merge with the plan's weights: the plain average, or sin^2 weights with `feather`);
+    `dgrad` runs the adjoints in reverse, so it is the exact gradient of `forward`.  Same surface as `UNet` where the sampler and
+    ClipGuidance use it (ctx, forward, __call__, dgrad, num_classes, in_channels, out_channels; other attributes are the wrapped net's), but
+    no embed / forward_slot: the embedding head cannot run ahead of a windowed forward.  All windows go through one forward, because dgrad
+    differentiates the handle's last forward; a frame whose windows do not fit in memory raises the ordinary out-of-memory error."""
+
+    def __init__(self, unet, stride, wrap="", feather=False, window=None):
+        from . import windows
+        if getattr(unet, "in_channels", 3) != 3:
+            raise ValueError("windowed sampling wraps a 3-channel UNet: super-resolution on windows is not built")
+        size = int(unet.cfg.image_size)
+        if window is not None and int(window) != size:
+            raise ValueError(f"the window side is the wrapped net's image_size {size}, got {window!r}")
+        if wrap not in windows.WRAPS:
+            raise ValueError(f"wrap must be one of {sorted(windows.WRAPS)}, got {wrap!r}")
+        windows.window_origins(size, size, stride)  # refuses a stride that is no positive multiple of 8 or exceeds the window
+        self.unet, self.ctx = unet, unet.ctx
+        self.window, self.stride, self.wrap, self.feather = size, int(stride), wrap, bool(feather)
+        self.num_classes, self.in_channels, self.out_channels = unet.num_classes, unet.in_channels, unet.out_channels
+        self._plans = {}
+        self._last = None  # the plan and batch of the last forward: dgrad differentiates that one
+
+    def __getattr__(self, name):  # only what the wrapper does not define itself
+        if name in ("embed", "forward_slot", "unet"):
+            raise AttributeError(name)
+        return getattr(self.unet, name)
+
+    def set_low_res(self, low_res):
+        raise ValueError("windowed sampling does not take a low-resolution condition: super-resolution on windows is not built")
+
+    def plan(self, H, W):
+        """The window plan of an (H, W) frame, tables on the device; cached per shape."""
+        from . import windows
+        p = self._plans.get((H, W))
+        if p is None:
+            p = self._plans[(H, W)] = windows.WindowPlan(H, W, self.window, self.stride, self.wrap, self.feather).to(f"cuda:{self.ctx.device}")
+            p.c_oy, p.c_ox = (C.c_int * p.ny)(*p.oy), (C.c_int * p.nx)(*p.ox)
+            p.bufs = {}  # the window batches of this frame shape, by (role, B, channels)
+        return p
+
+    def _gather(self, p, full, win, weighted):
+        B, Cn = full.shape[:2]
+        self.ctx.check(self.ctx.lib.cgd_window_gather(self.ctx.h, full.data_ptr(), win.data_ptr(), p.c_oy, p.ny, p.c_ox, p.nx,
+                                                      p.ay.data_ptr() if weighted else None, p.ax.data_ptr() if weighted else None,
+                                                      B, Cn, p.H, p.W, p.S, p.wrap, self.ctx.stream()))
+
+    def _merge(self, p, win, full, weighted):
+        B, Cn = full.shape[:2]
+        self.ctx.check(self.ctx.lib.cgd_window_merge(self.ctx.h, win.data_ptr(), full.data_ptr(), p.c_oy, p.ny, p.c_ox, p.nx,
+                                                     p.ay.data_ptr() if weighted else None, p.ax.data_ptr() if weighted else None,
+                                                     B, Cn, p.H, p.W, p.S, p.wrap, 0, self.ctx.stream()))
+
+    def _buf(self, p, name, B, Cn, dev):
+        t = p.bufs.get((name, B, Cn))
+        if t is None or t.device != dev:
+            t = p.bufs[(name, B, Cn)] = th.empty((B * p.n, Cn, p.S, p.S), device=dev, dtype=th.float32)
+        return t
+
+    def forward(self, x, timesteps, y=None, out=None):
+        """x (B,3,H,W) fp32 NCHW on the GPU, H and W multiples of 8 and at least the window side; timesteps (B,), y (B,) as for UNet.forward:
+        every window of sample b runs at timesteps[b] and y[b]."""
+        B, _, H, W = x.shape
+        x = x.contiguous().float()
+        p = self.plan(H, W)
+        xw = self._buf(p, "x", B, 3, x.device)
+        self._gather(p, x, xw, False)
+        t = timesteps.to(device=x.device, dtype=th.float32).repeat_interleave(p.n)
+        if y is not None:
+            y = y.to(device=x.device, dtype=th.int64).repeat_interleave(p.n)
+        ow = self.unet.forward(xw, t, y, out=self._buf(p, "out", B, self.out_channels, x.device))
+        if out is None:
+            out = th.empty((B, self.out_channels, H, W), device=x.device, dtype=th.float32)
+        self._merge(p, ow, out, True)
+        self._last, self._keep = (p, B), x  # inputs must outlive the enqueued work
+        return out
+
+    def __call__(self, x, timesteps, y=None, out=None):
+        """model(x, timesteps, y): an autograd node (UNetFunction, over this wrapper's forward / dgrad) when `x` requires grad."""
+        if x.requires_grad and th.is_grad_enabled():
+            return UNetFunction.apply(x, self, timesteps, y)
+        return self.forward(x, timesteps, y, out)
+
+    def dgrad(self, g_out, g_x=None):
+        """d(sum(out*g_out))/dx for the last forward: the merge's adjoint (a weighted gather), the wrapped net's dgrad on all windows, the
+        gather's adjoint (an unweighted merge)."""
+        if self._last is None:
+            raise RuntimeError("WindowedUNet.dgrad: no forward to differentiate")
+        p, B = self._last
+        g_out = g_out.contiguous().float()
+        if tuple(g_out.shape) != (B, self.out_channels, p.H, p.W):
+            raise ValueError(f"g_out must have the last forward's output shape {(B, self.out_channels, p.H, p.W)}, got {tuple(g_out.shape)}")
+        gw = self._buf(p, "g_out", B, self.out_channels, g_out.device)
+        self._gather(p, g_out, gw, True)
+        gxw = self.unet.dgrad(gw, self._buf(p, "g_x", B, 3, g_out.device))
+        if g_x is None:
+            g_x = th.empty((B, 3, p.H, p.W), device=g_out.device, dtype=th.float32)
+        self._merge(p, gxw, g_x, False)
+        self._keep_g = g_out
+        return g_x
+
+
 class ClipImageTower(_Net):
     _prefix = "vit"
 

@@ -526,6 +526,26 @@ long cgd_ilvr_scratch_floats(int B, int H, int W, int factor, int with_pred_xsta
 int cgd_ilvr_refine(cgd_ctx* ctx, float* sample, float* pred_xstart, const float* ref, const float* noise, float* scratch, int B, int H,
                     int W, int ref_batch, int factor, float sa, float sb, void* stream);
 
+/* ---- windowed sampling (MultiDiffusion, Bar-Tal et al., 2023): the frame is cut into overlapping S x S windows of the model's trained size, the
+ *      model runs on all windows as one batch, and the window outputs are averaged into one prediction for the frame.  An adjoint pair, one
+ *      launch each whatever B, C and the window count:
+ *        gather  win[b,k,c,u,v]   = ay[ky][u] ax[kx][v] full[b,c,(oy[ky]+u) mod H,(ox[kx]+v) mod W]                 k = ky nx + kx
+ *        merge   full[b,c,y,x] (+)= sum_ky sum_kx ay[ky][u] ax[kx][v] win[b,k,c,u,v]      over the windows that cover (y,x):
+ *                                                                                        u = (y - oy[ky]) mod H < S, v = (x - ox[kx]) mod W < S
+ *      full: (B,C,H,W) fp32 NCHW; win: (B nW,C,S,S), nW = ny nx, row b nW + k.  oy [ny], ox [nx]: window origins per axis, HOST arrays (read
+ *      during the call, at most 16 per axis); the window grid is their outer product.  wrap: bit 0 lets windows run over the right edge and
+ *      continue at x = 0, bit 1 the same for the bottom edge.  ay [ny][S], ax [nx][S]: device tables of per-axis weights, both or neither;
+ *      NULL means ones, and the gather is then a copy that keeps every bit.  The merge is in gather form: one thread owns its output elements
+ *      and sums the covering windows in a fixed order (ky ascending outside, kx ascending inside), no atomics, the same bits on every run;
+ *      accumulate != 0 adds the sum to what `full` holds.  Any 4-byte-aligned pointers are accepted (16-byte accesses when full, win and the
+ *      tables are 16-byte aligned).  Both return -2 (cgd_last_error), before any launch, unless: S, H, W and every origin are multiples of 8;
+ *      S <= H and S <= W; 1 <= ny, nx <= 16; every origin lies in [0, extent), and o + S <= extent on an axis that does not wrap; every pixel
+ *      is covered by at least one window; H W and S S are below 2^31; the sizes are positive and full, win, oy, ox are given. ---- */
+int cgd_window_gather(cgd_ctx* ctx, const float* full, float* win, const int* oy, int ny, const int* ox, int nx, const float* ay, const float* ax,
+                      int B, int C, int H, int W, int S, int wrap, void* stream);
+int cgd_window_merge(cgd_ctx* ctx, const float* win, float* full, const int* oy, int ny, const int* ox, int nx, const float* ay, const float* ax,
+                     int B, int C, int H, int W, int S, int wrap, int accumulate, void* stream);
+
 /* ---- DDIM inversion of an init image (guided_diffusion's ddim_reverse_sample, unguided, clip_denoised=False): the update of one inversion
  *      step, from level t up to level t+1 along the deterministic DDIM ODE, in one launch after the UNet forward:
  *        eps         = model_out6[:, 0:3]                 (read in place: plane b * 6 + c; the variance planes 3..5 are never touched)

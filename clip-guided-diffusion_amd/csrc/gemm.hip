@@ -731,6 +731,9 @@ int cgd_launch_gemm(cgd_ctx* ctx, GemmParams p, hipStream_t s) {
   if ((p.act_out || p.act_in) && (p.act < 1 || p.act > 3)) CGD_FAIL(ctx, "cgd_launch_gemm: activation code must be 1 (SiLU), 2 (QuickGELU) or 3 (GELU)");
   if ((p.act_out || p.act_in) && !(use_g && p.splitk == 1 && ctx->hgemm_var != 0))
     CGD_FAIL(ctx, "cgd_launch_gemm: only hgemm2 in one slice fuses an activation into its epilogue (cgd_gemm_fuses_act)");
+  // hgemm2 takes A of M * lda < 2^29 floats (32-bit byte offsets); beyond that extent the weight GEMM runs hgemm_kernel, which has none of these epilogues
+  if ((p.act_out || p.act_in || p.skip_group) && (long)p.M * p.lda >= (1L << 29))
+    CGD_FAIL(ctx, "cgd_launch_gemm: activation / skip_group epilogues need M * lda < 2^29 floats, the extent limit of hgemm2 (cgd_gemm_fuses_act)");
   if (p.gnf_x && !(use_g && p.splitk == 1))
     CGD_FAIL(ctx, "cgd_launch_gemm: only hgemm2 in one slice applies a GroupNorm's backward in its epilogue (cgd_gemm_fuses_gnb)");
   if (p.splitk > 1) p.ws = ctx->ws;

@@ -935,6 +935,7 @@ void cgd_frag_cache_clear(cgd_ctx* ctx) {
 // while 128-row tiles would not give every CU a workgroup, 128 rows otherwise; 2 / 3 force hgemm2 with 128 / 64 rows
 int cgd_hgemm_tile_m(const cgd_ctx* ctx, const GemmParams& p) {
   if (p.gnf_x) return GM;  // the GroupNorm-backward epilogue exists for the 128-row tile only
+  if ((long)p.M * p.lda >= (1L << 29)) return GM;  // beyond hgemm2's extent (cgd_launch_hgemm, v2) hgemm_kernel runs, which maps workgroups to 128-row tiles
   if (ctx->hgemm_var == 3) return 64;
   if (ctx->hgemm_var == 1 && (long)cdiv(p.M, GM) * cdiv(p.N, GN) < ctx->num_cu) {
     // (round 5) 96-row tiles where 64-row tiles need more workgroups than the chip has CUs but 96-row tiles do not: the ViT's M = 800,
@@ -953,6 +954,9 @@ int cgd_hgemm_chunks(const GemmParams& p) { return p.K / GK; }
 // a forced launch used to fail with "does not support this problem" when a policy knob said no)
 bool cgd_kgemm_capable(const cgd_ctx* ctx, const GemmParams& p) {
   if ((uintptr_t)p.bias & 15) return false;  // the epilogue reads the bias 16 bytes at a time
+  // rows beyond M are not clamped: only the resource's extent (M * lda * 4 bytes) masks them, so the byte offset of the last row of the last
+  // 64-row tile must not wrap past 2^32 back into range (few rows on a huge stride: M = 5, lda near 2^29 / 5, row 11 would land on row 1)
+  if ((long)cdiv(p.M, 64) * 64 * p.lda >= (1L << 30)) return false;
   return p.weight && p.M > 4 && cgd_hgemm_supported(ctx, p) && !p.act_out && !p.act_in && !p.skip_group && !p.gnf_x && p.splitk <= 1 && (long)p.M * p.lda < (1L << 29);
 }
 bool cgd_kgemm_supported(const cgd_ctx* ctx, const GemmParams& p) {
@@ -1034,15 +1038,16 @@ int cgd_launch_hgemm(cgd_ctx* ctx, const GemmParams& g, hipStream_t s) {
   p.skip_group = g.skip_group;
   p.lep = ctx->hgemm_epi;
   p.nt_out = (long)g.M * g.N * 4 > (32L << 20) ? 1 : 0;  // an output beyond the 32 MB of L2
-  const int tm = cgd_hgemm_tile_m(ctx, g);
-  dim3 grid(cdiv(g.M, tm) * cdiv(g.N, GN), 1, g.splitk > 1 ? g.splitk : 1);
   const bool x3 = ctx->precision == CGD_PREC_BF16X3;
   // hgemm2 addresses A with 32-bit BYTE offsets (buffer loads)
   const bool v2 = ctx->hgemm_var != 0 && (long)g.M * g.lda < (1L << 29);
-  if (g.skip_group && (!v2 || g.splitk > 1 || g.R || g.act_out || g.act_in))
+  const int tm = cgd_hgemm_tile_m(ctx, g);  // GM whenever !v2
+  dim3 grid(cdiv(g.M, tm) * cdiv(g.N, GN), 1, g.splitk > 1 ? g.splitk : 1);
+  if (!v2 && (g.act_out || g.act_in || g.skip_group))
+    CGD_FAIL(ctx, "hgemm: activation / skip_group epilogues need hgemm2, i.e. M * lda < 2^29 floats (32-bit byte offsets into A)");
+  if (g.skip_group && (g.splitk > 1 || g.R || g.act_out || g.act_in))
     CGD_FAIL(ctx, "hgemm: skip_group needs hgemm2 in one slice without residual / activation operands");
   const bool gelu = (g.act_out || g.act_in) && g.act == 3;
-  if (gelu && !v2) CGD_FAIL(ctx, "hgemm: only hgemm2 fuses the GELU activation");
   if (g.gnf_x) {
     // (cgd_gemm_fuses_gnb is the callers' question; this is the kernel's own list)
     if (!v2 || !x3 || g.splitk > 1 || g.act_out || g.act_in || g.skip_group || !g.gnf_dz || !g.gnf_coef || !g.gnf_bcoef)

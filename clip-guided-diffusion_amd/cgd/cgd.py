@@ -13,7 +13,7 @@ from pathlib import Path
 import torch as th
 from tqdm.auto import tqdm
 
-from cgd_amd import nets, shard
+from cgd_amd import nets, regions, shard
 from cgd_amd.guidance import ClipGuidance
 
 from . import clip_util, script_util
@@ -58,11 +58,19 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
             raise ValueError(f"init image 'invert=...' needs height_offset = width_offset = 0, got {height_offset} and {width_offset}: the "
                              "inverted latent has the init image's size")
 
+    # "TEXT@@REGION[^POWER][:weight]" among the prompts and image prompts (an extension like "plmsN"): a region prompt, which acts on a cutout in
+    # proportion to the share of REGION (a mask file or a box "x0,y0,x1,y1") the cutout sees; malformed entries are refused before anything is
+    # loaded.  From here on `prompts` and `image_prompts` are the entries without their "@@..." parts
+    prompts, prompt_regions = script_util.split_region_prompts(prompts)
+    image_prompts, image_regions = script_util.split_region_prompts(image_prompts)
+    if use_augs and any(spec is not None for spec, _ in prompt_regions + image_regions):
+        raise ValueError("'TEXT@@REGION' prompts do not work with use_augs: the box is warped after the crop")
     # "SOURCE=>TARGET[:weight]" among the prompts (an extension like "plmsN"): a direction prompt, scored by the directional CLIP loss against
     # the init image; refused before anything is loaded when malformed or without an init image
     direction_pairs = script_util.direction_prompts(prompts, image_prompts, init_image, height_offset, width_offset)
     # "style=FILE[:SCALE]" among the image prompts (likewise): the style image of the VGG Gram-matrix style loss, SCALE its weight; no CLIP
     # prompt.  Refused before anything is loaded when malformed, given twice, or at a frame whose sides are no multiples of 16
+    image_regions = [r for p, r in zip(image_prompts, image_regions) if not str(p).startswith(script_util.STYLE_PREFIX)]
     image_prompts, style_spec = script_util.split_style_prompts(image_prompts, image_size + height_offset, image_size + width_offset)
     if use_augs and any(pair is not None for pair in direction_pairs):
         raise ValueError("'SOURCE=>TARGET' prompts do not work with use_augs: the random warp of every cut would have to be replayed on the init image")
@@ -101,6 +109,7 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         clip_size = clip_size or size
     clip_model = clip_models[0]
     embeds_per_tower, weights = [[] for _ in clip_names], []
+    region_specs = list(prompt_regions)  # (REGION or None, POWER) per entry of `weights`
     # direction prompts: per tower normalize(E(target caption)) - normalize(E(source caption)); their places in the weight list, which holds
     # targets and directions alike in the order given
     dirs_per_tower, direction_columns = [[] for _ in clip_names], []
@@ -117,12 +126,13 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         if pair is not None:
             direction_columns.append(len(weights))
         weights.append(w_k)
-    for image_prompt in image_prompts:
+    for image_prompt, region in zip(image_prompts, image_regions):
         img, weight = script_util.parse_prompt(image_prompt)
         for k, name in enumerate(clip_names):
             embed, batched = clip_util.encode_image_prompt(img, weight, image_size, num_cutouts=num_cutouts, clip_model_name=name, device=device)
             embeds_per_tower[k].append(embed)
         weights.extend(batched)
+        region_specs.extend([region] * len(batched))  # every embedding of the image gets its region
     # (a run with direction prompts only has no target embeddings: ClipGuidance then makes no spherical launch)
     # (... and a run with a style image and no prompt at all has neither: no cutouts, no CLIP pass)
     style_only = style_spec is not None and not weights
@@ -235,6 +245,8 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
                                              model_kwargs={"y": th.zeros([1], device=device, dtype=th.long)} if class_cond else {})
         invert_kw["noise"] = inv_noise.expand(local_batch, -1, -1, -1).contiguous()
 
+    # every rank of a sharded run builds the same plan; the frame is the sample's, offsets included
+    region_plan = regions.plan_from_specs(region_specs, image_size + height_offset, image_size + width_offset, device)
     cond_fn = ClipGuidance(
         gd_model.ctx, gd_model, [cm.tower for cm in clip_models], diffusion, target_embeds, weight_t, num_cutouts, cutout_power=cutout_power,
         clip_guidance_scale=clip_guidance_scale, tv_scale=tv_scale, range_scale=range_scale, sat_scale=sat_scale, use_magnitude=use_magnitude,
@@ -247,6 +259,7 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         **({} if style_tensor is None else {"style_tensor": style_tensor, "style_scale": style_spec[1]}),
         secondary=secondary,
         **({"direction_source": init_tensor, **direction_kw} if direction_kw else {}),
+        **({} if region_plan is None else {"regions": region_plan}),
         **({} if classifier is None else {"classifier": classifier, "classifier_scale": classifier_spec[2], "classifier_class": classifier_spec[1]}))
     if nranks > 1:
         cond_fn.shard = diffusion.shard = (mine, batch_size)
@@ -330,8 +343,8 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
 # The reference CLI, flag for flag (cgd.py:290-357): "long alias kind default | help".  kind: str / int / float / path, or "flag"
 # for store_true switches.  Only names, aliases, types and defaults are contract (tests/golden/reference_host.json).
 _CLI_SPEC = f"""
---prompts -txts str "" | text prompts with optional weights, pipe-separated: 'a cat:0.5|a dog:-0.5'; 'SOURCE CAPTION=>TARGET CAPTION[:weight]' is a direction prompt (needs --init_image): the change of the image's CLIP embedding relative to the init image is steered along the change from the source to the target caption (e.g. 'a photo of a cat=>a photo of a dog:1.5'); weights of all prompts are normalised together
---image_prompts -imgs str "" | image prompts (paths or URLs) with optional weights, pipe-separated; one entry may be 'style=FILE[:SCALE]': FILE is then no CLIP prompt but the style image of the VGG16 Gram-matrix style loss (texture and palette statistics of relu1_2 .. relu4_3, Gatys / Johnson), resized to the frame, SCALE the weight of that loss (default 1, positive; it does not enter the prompt weights); frame sides must be multiples of 16; works with or without prompts and with --init_image / --init_scale
+--prompts -txts str "" | text prompts with optional weights, pipe-separated: 'a cat:0.5|a dog:-0.5'; 'TEXT@@REGION[^POWER][:weight]' is a region prompt (direction prompts and --image_prompts entries take '@@REGION' too): REGION is a mask file (white inside, resized to the frame) or a box 'x0,y0,x1,y1' in fractions of the frame, and the prompt acts on every cutout in proportion to the share of REGION the cutout sees, raised to POWER (default 1), e.g. 'a castle on a hill@@0,0,0.5,1|a pine forest@@0.5,0,1,1'; not with use_augs; 'SOURCE CAPTION=>TARGET CAPTION[:weight]' is a direction prompt (needs --init_image): the change of the image's CLIP embedding relative to the init image is steered along the change from the source to the target caption (e.g. 'a photo of a cat=>a photo of a dog:1.5'); weights of all prompts are normalised together
+--image_prompts -imgs str "" | image prompts (paths or URLs) with optional weights, pipe-separated; 'FILE@@REGION[^POWER][:weight]' confines an image prompt to a region as on --prompts (every embedding of the image gets it); one entry may be 'style=FILE[:SCALE]' (no '@@' there): FILE is then no CLIP prompt but the style image of the VGG16 Gram-matrix style loss (texture and palette statistics of relu1_2 .. relu4_3, Gatys / Johnson), resized to the frame, SCALE the weight of that loss (default 1, positive; it does not enter the prompt weights); frame sides must be multiples of 16; works with or without prompts and with --init_image / --init_scale
 --image_size -size int 128 | resolution of the diffusion checkpoint: 64, 128, 256 or 512
 --init_image -init str "" | start from this image (needs --skip_timesteps); IMAGE::MASK regenerates the white part of MASK and keeps the black part of IMAGE; invert=IMAGE (or invert=IMAGE::MASK, with -respace ddimN / plmsN / dpmN) starts from the DDIM-inverted latent of IMAGE; upsample=IMAGE (or upsample=IMAGE::MASK, with --image_size 256 or 512, not with --uncond or invert=) runs the 64->256 / 128->512 super-resolution checkpoint conditioned on IMAGE at a quarter of the frame, IMAGE at the full frame staying the init image; ilvrN=IMAGE or ilvrN@U=IMAGE (N a power of two in [2, 64] that divides both frame sides, U in (0, 1], default 1; not with ::MASK, invert= or upsample=) conditions sampling on the low frequencies of IMAGE (ILVR): after every step of the first fraction U of the run the band that survives a resize down by N and back up is replaced by that of IMAGE noised to the step's level, IMAGE staying the init image; in every form IMAGE is also the source image of 'SOURCE=>TARGET' direction prompts
 --init_scale -is int 0 | weight of the LPIPS-VGG16 term that keeps the sample close to the init image

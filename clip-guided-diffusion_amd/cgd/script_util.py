@@ -261,6 +261,51 @@ def split_direction(text):
 
 
 STYLE_PREFIX = "style="
+REGION_SEP = "@@"
+
+
+def split_region(prompt):
+    """'TEXT@@REGION[^POWER][:weight]' -> ('TEXT[:weight]', REGION, POWER), split at the last '@@'; a prompt without '@@' -> (prompt, None, 1.0).
+    A region rides on an entry of --prompts (direction prompts included: 'SRC=>TGT@@REGION:1.5') or of --image_prompts: the prompt then acts
+    on a cutout in proportion to the share of REGION the cutout sees, raised to POWER (default 1).  REGION is a mask file (white inside) or
+    a box 'x0,y0,x1,y1' in fractions of the frame (cgd_amd.regions.parse_region).  Refuses, before anything is loaded: a missing TEXT or
+    REGION, a malformed box, a POWER or weight that is no number, a POWER that is not positive, and '@@' on a 'style=' entry."""
+    from cgd_amd.regions import parse_box
+    prompt = str(prompt)
+    text, sep, tail = prompt.rpartition(REGION_SEP)
+    if not sep:
+        return prompt, None, 1.0
+    if prompt.startswith(STYLE_PREFIX):
+        raise ValueError(f"image prompt {prompt!r}: a 'style=' entry is no CLIP prompt and takes no '@@REGION'")
+    is_url = tail.startswith(("http://", "https://"))
+    head, colon, weight = tail.rpartition(":")
+    if not colon or (is_url and head in ("http", "https")):
+        head, weight = tail, None
+    if weight is not None:
+        try:
+            float(weight)
+        except ValueError:
+            raise ValueError(f"prompt {prompt!r}: the weight behind 'TEXT@@REGION[^POWER]:' must be a number, got {weight!r}") from None
+    region, hat, power = head.partition("^")
+    if hat:
+        try:
+            power = float(power)
+        except ValueError:
+            raise ValueError(f"prompt {prompt!r}: the POWER of '@@REGION^POWER' must be a number, got {power!r}") from None
+        if not power > 0 or power == float("inf"):
+            raise ValueError(f"prompt {prompt!r}: the POWER of '@@REGION^POWER' must be positive and finite")
+    else:
+        power = 1.0
+    if not text.strip() or not region.strip():
+        raise ValueError(f"prompt {prompt!r}: 'TEXT@@REGION[^POWER][:weight]' needs a prompt and a region")
+    parse_box(region.strip())  # a list of numbers that is no box is refused here; a file is opened once the frame is known
+    return text + (":" + weight if weight is not None else ""), region.strip(), power
+
+
+def split_region_prompts(prompts):
+    """split_region over a list -> (the prompts without their '@@...' parts, [(REGION or None, POWER)] per prompt)."""
+    parts = [split_region(p) for p in prompts]
+    return [p[0] for p in parts], [(p[1], p[2]) for p in parts]
 
 
 def split_style_prompts(image_prompts, height=None, width=None):

@@ -252,6 +252,26 @@ int cgd_directional_loss(cgd_ctx* ctx, const float* emb, const float* src_emb, c
   CGD_NEED_CTX(ctx);
   return cgd_launch_directional_loss(ctx, emb, src_emb, dirs_n, weights, d_emb, loss_part, cutn, B, Bs, P, D, scale, accumulate, S(stream));
 }
+int cgd_spherical_loss_regions(cgd_ctx* ctx, const float* emb, const float* targets_n, const float* weights, float* d_emb, float* loss_part,
+                               int cutn, int B, int P, int D, float scale, const int32_t* sat, const int32_t* region_of,
+                               const int32_t* region_of_host, const float* power, const int32_t* geo, int R, int H, int W, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_spherical_loss_regions(ctx, emb, targets_n, weights, d_emb, loss_part, cutn, B, P, D, scale,
+                                           cgd_regions{sat, region_of, region_of_host, power, geo, R, H, W}, S(stream));
+}
+int cgd_directional_loss_regions(cgd_ctx* ctx, const float* emb, const float* src_emb, const float* dirs_n, const float* weights, float* d_emb,
+                                 float* loss_part, int cutn, int B, int Bs, int P, int D, float scale, int accumulate, const int32_t* sat,
+                                 const int32_t* region_of, const int32_t* region_of_host, const float* power, const int32_t* geo, int R, int H,
+                                 int W, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_directional_loss_regions(ctx, emb, src_emb, dirs_n, weights, d_emb, loss_part, cutn, B, Bs, P, D, scale, accumulate,
+                                             cgd_regions{sat, region_of, region_of_host, power, geo, R, H, W}, S(stream));
+}
+int cgd_op_region_coverage(cgd_ctx* ctx, const int32_t* sat, const int32_t* region_of, const int32_t* region_of_host, const float* power,
+                           const int32_t* geo, float* out, int cutn, int P, int R, int H, int W, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_region_coverage(ctx, cgd_regions{sat, region_of, region_of_host, power, geo, R, H, W}, out, cutn, P, S(stream));
+}
 int cgd_pmv_blend(cgd_ctx* ctx, const float* x, const float* out6, float* x0, float* mean, float* logvar, float* xin, int B, int H, int W,
                   const cgd_step_coef* k, void* stream) {
   CGD_NEED_CTX(ctx);

@@ -10,13 +10,19 @@
 // no LDS.  The source embedding gets no gradient.  All tensors fp32.
 #include "common.h"
 #include "guidance.h"
+#include "region_cov.h"
 
 namespace {
 
+// Instantiated without RG it is the plain loss, with the same arguments and machine code as before it was a template; with RG = RegionArgs
+// (cgd_directional_loss_regions) w_bp is scaled by the coverage of the row's cut (region_cov.h), and a row whose every column is skipped has
+// loss 0 and no gradient, like a row without a direction.
+template <class... RG>
 __global__ __launch_bounds__(64) void directional_loss_kernel(const float* __restrict__ emb, const float* __restrict__ src,
                                                               const float* __restrict__ dn /*unit rows*/, const float* __restrict__ wts,
                                                               float* __restrict__ demb, float* __restrict__ loss_part, int B, int Bs, int P,
-                                                              int D, float coef, int accumulate) {
+                                                              int D, float coef, int accumulate, RG... rg) {
+  constexpr bool REGIONS = sizeof...(RG) > 0;
   const int row = blockIdx.x, b = row % B, cut = row / B, lane = threadIdx.x;
   constexpr int MAXE = 32;  // D <= 2048
   const float* e = emb + (long)row * D;
@@ -47,12 +53,17 @@ __global__ __launch_bounds__(64) void directional_loss_kernel(const float* __res
   }
   for (int o = 32; o > 0; o >>= 1) n2 += __shfl_xor(n2, o, 64);
   const float n = sqrtf(n2);
-  const bool live = n > 1e-6f;
+  bool live = n > 1e-6f;
   const float invn = live ? 1.f / n : 0.f;
   float wsum = 0.f, wcos = 0.f;
+  bool any = false;
   for (int p = 0; p < P; ++p) {
-    const float w = wts[(long)b * P + p];
+    float w = wts[(long)b * P + p];
+    if constexpr (REGIONS) {
+      if (w != 0.f) w *= region_weight(rg..., cut, p);
+    }
     if (w == 0.f) continue;
+    any = true;
     const float* y = dn + (long)p * D;
     float dot = 0.f;
 #pragma unroll
@@ -66,7 +77,8 @@ __global__ __launch_bounds__(64) void directional_loss_kernel(const float* __res
     wsum += w;
     wcos += w * (dot * invn);  // cos_p = 0 on a row without a direction
   }
-  if (lane == 0) loss_part[row] = coef * (wsum - wcos);
+  if (lane == 0) loss_part[row] = REGIONS && !any ? 0.f : coef * (wsum - wcos);
+  if constexpr (REGIONS) live = live && any;
   float* out = demb + (long)row * D;
   if (!live) {  // no gradient: exact zeros, or the accumulated values as they are
     if (!accumulate) {
@@ -105,8 +117,22 @@ int cgd_launch_directional_loss(cgd_ctx* ctx, const float* emb, const float* src
   if (Bs != 1 && Bs != B) CGD_FAIL(ctx, "directional loss: the source batch must be 1 or B");
   if (cutn < 1 || B < 1 || P < 1 || D < 1) CGD_FAIL(ctx, "directional loss: cutn, B, P and D must be positive");
   if (!emb || !src_emb || !dirs_n || !weights || !demb || !loss_part) CGD_FAIL(ctx, "directional loss: null pointer");
-  CGD_LAUNCH(directional_loss_kernel, dim3(cutn * B), dim3(64), 0, s, emb, src_emb, dirs_n, weights, demb, loss_part, B, Bs, P, D,
+  CGD_LAUNCH(directional_loss_kernel<>, dim3(cutn * B), dim3(64), 0, s, emb, src_emb, dirs_n, weights, demb, loss_part, B, Bs, P, D,
              scale / (float)cutn, accumulate ? 1 : 0);
+  CGD_HIP(ctx, hipGetLastError());
+  return 0;
+}
+
+int cgd_launch_directional_loss_regions(cgd_ctx* ctx, const float* emb, const float* src_emb, const float* dirs_n, const float* weights,
+                                        float* demb, float* loss_part, int cutn, int B, int Bs, int P, int D, float scale, int accumulate,
+                                        const cgd_regions& rg, hipStream_t s) {
+  if (D > 2048) CGD_FAIL(ctx, "directional loss: embedding dim > 2048");
+  if (Bs != 1 && Bs != B) CGD_FAIL(ctx, "directional loss: the source batch must be 1 or B");
+  if (cutn < 1 || B < 1 || P < 1 || D < 1) CGD_FAIL(ctx, "directional loss: cutn, B, P and D must be positive");
+  if (!emb || !src_emb || !dirs_n || !weights || !demb || !loss_part) CGD_FAIL(ctx, "directional loss: null pointer");
+  CGD_TRY(cgd_check_regions(ctx, rg, P));
+  CGD_LAUNCH(directional_loss_kernel<RegionArgs>, dim3(cutn * B), dim3(64), 0, s, emb, src_emb, dirs_n, weights, demb, loss_part, B, Bs, P, D,
+             scale / (float)cutn, accumulate ? 1 : 0, RegionArgs{rg.sat, rg.region_of, rg.power, rg.geo, rg.H, rg.W});
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }

@@ -29,6 +29,24 @@ int cgd_launch_sample_update(cgd_ctx* ctx, const float* x, const float* x0, cons
 // direction.hip
 int cgd_launch_directional_loss(cgd_ctx* ctx, const float* emb, const float* src_emb, const float* dirs_n, const float* weights, float* demb,
                                 float* loss_part, int cutn, int B, int Bs, int P, int D, float scale, int accumulate, hipStream_t s);
+// region prompts (include/cgd_mi355x.h, cgd_spherical_loss_regions): what the `_regions` entries take on top of the plain ones.  All device
+// memory but region_of_host, the caller's host copy of region_of that cgd_check_regions reads
+struct cgd_regions {
+  const int* sat;
+  const int* region_of;
+  const int* region_of_host;
+  const float* power;
+  const int* geo;
+  int R, H, W;
+};
+// regions.hip: -2 (with the reason) for a null pointer, R < 1, a frame whose table does not fit int32 or a region_of entry outside [-1, R)
+int cgd_check_regions(cgd_ctx* ctx, const cgd_regions& rg, int P);
+int cgd_launch_region_coverage(cgd_ctx* ctx, const cgd_regions& rg, float* out, int cutn, int P, hipStream_t s);
+int cgd_launch_spherical_loss_regions(cgd_ctx* ctx, const float* emb, const float* targets_n, const float* weights, float* demb,
+                                      float* loss_part, int cutn, int B, int P, int D, float scale, const cgd_regions& rg, hipStream_t s);
+int cgd_launch_directional_loss_regions(cgd_ctx* ctx, const float* emb, const float* src_emb, const float* dirs_n, const float* weights,
+                                        float* demb, float* loss_part, int cutn, int B, int Bs, int P, int D, float scale, int accumulate,
+                                        const cgd_regions& rg, hipStream_t s);
 // plms.hip
 int cgd_launch_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eval, const float* x0, const float* g, const float* scalars,
                                 const float* noise, const float* const* eps_hist, float* eps_out, float* sample, float* x0_out, int B,

@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "guidance.h"
+#include "region_cov.h"
 
 namespace {
 
@@ -111,10 +112,14 @@ __global__ __launch_bounds__(256) void cutouts_bwd_kernel(const float* __restric
   }
 }
 
-// one wavefront per (cut, b) embedding row
+// one wavefront per (cut, b) embedding row.  Instantiated without RG it is the plain loss, with the same arguments and machine code as before it
+// was a template; with RG = RegionArgs (cgd_spherical_loss_regions) every prompt's weight is scaled by the coverage of the row's cut
+// (region_cov.h), and a row whose every column is skipped gets exact zeros.
+template <class... RG>
 __global__ __launch_bounds__(64) void spherical_loss_kernel(const float* __restrict__ emb, const float* __restrict__ tn /*normalised*/,
                                                             const float* __restrict__ wts, float* __restrict__ demb,
-                                                            float* __restrict__ loss_part, int B, int P, int D, float coef) {
+                                                            float* __restrict__ loss_part, int B, int P, int D, float coef, RG... rg) {
+  constexpr bool REGIONS = sizeof...(RG) > 0;
   const int row = blockIdx.x, b = row % B, lane = threadIdx.x;
   constexpr int MAXE = 32;  // D <= 2048
   const float* e = emb + (long)row * D;
@@ -133,9 +138,14 @@ __global__ __launch_bounds__(64) void spherical_loss_kernel(const float* __restr
 #pragma unroll
   for (int k = 0; k < MAXE; ++k) ev[k] *= inv;  // x_hat
   float loss = 0.f;
+  bool any = false;
   for (int p = 0; p < P; ++p) {
-    const float w = wts[(long)b * P + p];
+    float w = wts[(long)b * P + p];
+    if constexpr (REGIONS) {
+      if (w != 0.f) w *= region_weight(rg..., row / B, p);
+    }
     if (w == 0.f) continue;
+    any = true;
     const float* y = tn + (long)p * D;
     float dd = 0.f;
 #pragma unroll
@@ -166,9 +176,9 @@ __global__ __launch_bounds__(64) void spherical_loss_kernel(const float* __restr
 #pragma unroll
   for (int k = 0; k < MAXE; ++k) {
     const int c = lane + 64 * k;
-    if (c < D) demb[(long)row * D + c] = coef * (gv[k] - dot * ev[k]) * inv;
+    if (c < D) demb[(long)row * D + c] = REGIONS && !any ? 0.f : coef * (gv[k] - dot * ev[k]) * inv;
   }
-  if (lane == 0) loss_part[row] = coef * loss;
+  if (lane == 0) loss_part[row] = REGIONS && !any ? 0.f : coef * loss;
 }
 
 // p_mean_variance tail (+ blend).  out6 = UNet output (B,6,H,W).
@@ -376,7 +386,7 @@ int cgd_launch_cutouts_bwd(cgd_ctx* ctx, const float* dout, const int* coords, f
 int cgd_launch_spherical_loss(cgd_ctx* ctx, const float* emb, const float* targets_n, const float* weights, float* demb,
                               float* loss_part, int cutn, int B, int P, int D, float scale, hipStream_t s) {
   if (D > 2048) CGD_FAIL(ctx, "spherical loss: embedding dim > 2048");
-  CGD_LAUNCH(spherical_loss_kernel, dim3(cutn * B), dim3(64), 0, s, emb, targets_n, weights, demb, loss_part, B, P, D,
+  CGD_LAUNCH(spherical_loss_kernel<>, dim3(cutn * B), dim3(64), 0, s, emb, targets_n, weights, demb, loss_part, B, P, D,
                      scale / (float)cutn);
   CGD_HIP(ctx, hipGetLastError());
   return 0;
@@ -425,6 +435,18 @@ int cgd_launch_sample_update(cgd_ctx* ctx, const float* x, const float* x0, cons
   const long total = (long)B * 3 * H * W;
   CGD_LAUNCH(sample_update_kernel, dim3(grid_for(total)), dim3(256), 0, s, x, x0, mean, logvar, g, noise, scalars, sample,
                      x0_out, total, k, mode);
+  CGD_HIP(ctx, hipGetLastError());
+  return 0;
+}
+
+int cgd_launch_spherical_loss_regions(cgd_ctx* ctx, const float* emb, const float* targets_n, const float* weights, float* demb,
+                                      float* loss_part, int cutn, int B, int P, int D, float scale, const cgd_regions& rg, hipStream_t s) {
+  if (D > 2048) CGD_FAIL(ctx, "spherical loss: embedding dim > 2048");
+  if (cutn < 1 || B < 1 || P < 1 || D < 1) CGD_FAIL(ctx, "spherical loss: cutn, B, P and D must be positive");
+  if (!emb || !targets_n || !weights || !demb || !loss_part) CGD_FAIL(ctx, "spherical loss: null pointer");
+  CGD_TRY(cgd_check_regions(ctx, rg, P));
+  CGD_LAUNCH(spherical_loss_kernel<RegionArgs>, dim3(cutn * B), dim3(64), 0, s, emb, targets_n, weights, demb, loss_part, B, P, D,
+             scale / (float)cutn, RegionArgs{rg.sat, rg.region_of, rg.power, rg.geo, rg.H, rg.W});
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }

@@ -12,6 +12,7 @@ perspective / grayscale / additive noise) inside the cutaug HIP kernels, whose a
 are drawn like reference_augs draws them (draw_aug_params), the noise on the device generator in its randn_like order.
 `MakeCutoutsResized` is a second cutter: overview + inner cuts through an antialiased cubic resize (the cutresize HIP kernels).
 With `direction_embeds` the CLIP leg also scores the directional loss of prompt-pair edits against a source image (the direction HIP kernel).
+With `regions` (a regions.RegionPlan) every prompt weighs on a cutout by the share of its mask the cutout sees, inside the `_regions` loss entries.
 Every cutter reaches the kernels through one per-step launch object (_CutLaunch, _AugLaunch: forward, backward, and torch_cuts, the same
 cutouts in torch ops), so there is one CLIP leg (ClipGuidance._clip_leg) and one torch restatement of it (_clip_leg_torch) for all of them.
 """
@@ -572,7 +573,7 @@ class ClipGuidance:
                  reduce_clip=False, progressive_cutout=False, cached_cutouts=False, make_cutouts=None, lpips=None, init_tensor=None,
                  init_scale=0.0, secondary=None, classifier=None, classifier_scale=1.0, classifier_class=None, direction_embeds=None,
                  direction_weights=None, direction_source=None, direction_columns=None, style_tensor=None, style_scale=0.0,
-                 style_weights=(1, 1, 1, 1, 0)):
+                 style_weights=(1, 1, 1, 1, 0), regions=None):
         # Multi-CLIP (BASELINE config 5, a build extension: the reference takes one clip_model_name): `clip_tower` / `target_embeds`
         # may be lists; the CLIP losses of the towers are summed (same cutout boxes, prompt weights and guidance scale).
         self.towers = list(clip_tower) if isinstance(clip_tower, (list, tuple)) else [clip_tower]
@@ -627,6 +628,16 @@ class ClipGuidance:
                 raise ValueError("every tower needs the same number of target and of direction embeddings as there are weights")
             self.direction_columns = cols
             self.direction_source = direction_source.detach().float().contiguous()
+        # region prompts (regions.RegionPlan over the P_t + P_d prompts in the order of the weight list, or None): every prompt's weight on a
+        # cutout is scaled by the share of its mask the cutout sees, inside the `_regions` loss entries; split by column like the weights
+        self.regions = self._reg_t = self._reg_d = self._reg_cols = None
+        if regions is not None:
+            pt = self.weights.numel()
+            dcols = self.direction_columns or []
+            if regions.P != pt + len(dcols):
+                raise ValueError(f"the region plan covers {regions.P} prompts, the weights {pt + len(dcols)}")
+            self.regions = regions
+            self._reg_cols = ([c for c in range(regions.P) if c not in dcols], list(dcols))
         self.num_cutouts = num_cutouts
         self.cgs, self.tvs, self.rs, self.sats = float(clip_guidance_scale), float(tv_scale), float(range_scale), float(sat_scale)
         self.use_magnitude = bool(use_magnitude)
@@ -637,6 +648,9 @@ class ClipGuidance:
         if has_dir and self.make_cutouts.augs is not None:
             raise ValueError("direction prompts do not work with use_augs cutouts: the random warp of every cut would have to be replayed on "
                              "the source image")
+        if regions is not None and self.make_cutouts.augs is not None:
+            raise ValueError("region prompts do not work with use_augs cutouts: the box is warped after the crop, so its share of a mask is "
+                             "not the share the cutout shows")
         # init-image perceptual term (cgd.py:147-148,220-224): `lpips` is a nets.LpipsVGG, its reference = the init image
         self.lpips, self.init_scale, self.init_tensor = None, float(init_scale), None
         if lpips is not None and init_tensor is not None and init_scale != 0:
@@ -742,6 +756,12 @@ class ClipGuidance:
         resized = isinstance(self.make_cutouts, MakeCutoutsResized)
         if self.dirs_list is not None:
             self._direction_source_on(dev, B, H, W)  # refuses a source of another size before anything is drawn or launched
+        if self.regions is not None:
+            if (self.regions.H, self.regions.W) != (H, W):
+                raise ValueError(f"the region masks are {self.regions.H} x {self.regions.W}, the sample is {H} x {W}")
+            if self._reg_t is None or self._reg_t.sat is None or self._reg_t.sat.device != dev:  # one upload; both parts share the tables
+                self.regions.to(dev)
+                self._reg_t, self._reg_d = (self.regions.columns(c) for c in self._reg_cols)
         if self.coords_tape is not None:
             coords = self.coords_tape[self.calls]
         elif resized:  # (ox, oy, w, h, flags) records; this step's counts from the cutter's own schedule
@@ -903,7 +923,8 @@ class ClipGuidance:
         tower keeps its last input for dgrad, and dgrad differentiates the LAST forward), the spherical launch is made only with target
         prompts, and the directional loss follows it, accumulating onto the spherical gradient when that ran; partials: per tower the
         spherical rows (if any), then the directional rows.  With cached_cutouts the boxes do not change, and the source embeddings of
-        a cut count are computed once.  _clip_leg_torch is the same leg with autograd."""
+        a cut count are computed once.  With a region plan both losses go through their `_regions` entries, which read this step's boxes from
+        the cutter's uploaded table; without one the plain entries are called as ever.  _clip_leg_torch is the same leg with autograd."""
         ctx, lib = self.ctx, self.ctx.lib
         B, _, H, W = x_in.shape
         dev = x_in.device
@@ -934,13 +955,20 @@ class ClipGuidance:
             demb = self._b(f"demb{k}", (N, tower.out_dim), dev)
             part = clip_part[k * N * kinds:]
             has_t = int(dirs_list is None or targets.shape[0] > 0)
-            if has_t:
+            if has_t and self.regions is not None:
+                ctx.check(lib.cgd_spherical_loss_regions(ctx.h, emb.data_ptr(), targets.data_ptr(), wm.data_ptr(), demb.data_ptr(), part.data_ptr(),
+                                                         cutn, B, targets.shape[0], tower.out_dim, self.cgs, *self._reg_t.args(cuts.geo), s))
+            elif has_t:
                 ctx.check(lib.cgd_spherical_loss(ctx.h, emb.data_ptr(), targets.data_ptr(), wm.data_ptr(), demb.data_ptr(), part.data_ptr(),
                                                  cutn, B, targets.shape[0], tower.out_dim, self.cgs, s))
             if dirs_list is not None:
                 semb, dirs = (fresh if src_embs is None else src_embs)[k], dirs_list[k]
-                ctx.check(lib.cgd_directional_loss(ctx.h, emb.data_ptr(), semb.data_ptr(), dirs.data_ptr(), wmd.data_ptr(), demb.data_ptr(),
-                                                   part[N * has_t:].data_ptr(), cutn, B, Bs, dirs.shape[0], tower.out_dim, self.cgs, has_t, s))
+                dir_args = (ctx.h, emb.data_ptr(), semb.data_ptr(), dirs.data_ptr(), wmd.data_ptr(), demb.data_ptr(), part[N * has_t:].data_ptr(),
+                            cutn, B, Bs, dirs.shape[0], tower.out_dim, self.cgs, has_t)
+                if self.regions is not None:
+                    ctx.check(lib.cgd_directional_loss_regions(*dir_args, *self._reg_d.args(cuts.geo), s))
+                else:
+                    ctx.check(lib.cgd_directional_loss(*dir_args, s))
             dclip_in = tower.dgrad(demb, self._b(f"dclip_in{k}", tuple(clip_in.shape), dev))
             cut.backward(ctx, dclip_in, gclip, cs, layout, patch, acc)
             acc = 1
@@ -964,6 +992,15 @@ class ClipGuidance:
         kinds = self._clip_kinds()
         if self.dirs_list is not None:
             src = self._direction_source_on(dev, B, H, W)
+        wm3 = wm.view(1, B, -1) if wm is not None else None
+        wmd3 = wmd.view(1, B, -1) if wmd is not None else None
+        if self.regions is not None:  # w_eff[cut, b, p] = w[b, p] cov[cut, p] ** power[p], the coverage from the host restatement
+            from .regions import boxes_of
+            boxes = boxes_of(cuts.coords, H, W, cuts.resized)
+            if wm3 is not None and self._reg_t.P:
+                wm3 = wm3 * self._reg_t.coverage(boxes).to(dev, th.float32).view(n, 1, -1)
+            if wmd3 is not None and self._reg_d.P:
+                wmd3 = wmd3 * self._reg_d.coverage(boxes).to(dev, th.float32).view(n, 1, -1)
 
         def clip_cuts(img, cs):
             return ((cuts.torch_cuts(img.add(1).div(2), cs) - mean) / std).contiguous()
@@ -984,12 +1021,12 @@ class ClipGuidance:
                     live = delta.norm(dim=-1, keepdim=True) > 1e-6
                     safe = th.where(live, delta, th.ones_like(delta))
                     cos = th.where(live, (safe / safe.norm(dim=-1, keepdim=True)) @ self.dirs_list[k].t(), th.zeros((), device=dev))  # (n, B, P_d)
-                    l_dir = ((1 - cos) * wmd.view(1, B, -1)).sum(2).mean(0).sum() * self.cgs
+                    l_dir = ((1 - cos) * wmd3).sum(2).mean(0).sum() * self.cgs
                     total = total + l_dir
                     clip_part[k * N * kinds + N * has_t] = l_dir.detach()
                 if has_t:
                     d = (en.unsqueeze(2) - targets.view(1, 1, -1, targets.shape[-1])).norm(dim=-1).div(2).arcsin().pow(2).mul(2)  # (n, B, P)
-                    l_sph = (d * wm.view(1, B, -1)).sum(2).mean(0).sum() * self.cgs
+                    l_sph = (d * wm3).sum(2).mean(0).sum() * self.cgs
                     total = total + l_sph
                     clip_part[k * N * kinds] = l_sph.detach()
                 if k == 0:

@@ -190,6 +190,9 @@ _SIGS = {
     "cgd_cutouts_resize_weights": (i32, [i32, i32, vp, vp, C.POINTER(i32)]),
     "cgd_spherical_loss": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp]),
     "cgd_directional_loss": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "cgd_spherical_loss_regions": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "cgd_directional_loss_regions": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "cgd_op_region_coverage": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "cgd_pmv_blend": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), vp]),
     "cgd_guidance_part_blocks": (i32, [i32, i32, i32]),
     "cgd_guidance_combine": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), f32, f32, f32, vp]),

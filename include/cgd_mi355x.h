@@ -359,6 +359,36 @@ int cgd_spherical_loss(cgd_ctx* ctx, const float* emb, const float* targets_n, c
 int cgd_directional_loss(cgd_ctx* ctx, const float* emb, const float* src_emb, const float* dirs_n, const float* weights, float* d_emb,
                          float* loss_part, int cutn, int B, int Bs, int P, int D, float clip_guidance_scale, int accumulate, void* stream);
 
+/* ---- region prompts: both losses with every prompt weighted by its mask's share of the row's cutout.
+ *      A region is an 8-bit mask m of the frame's size H x W (the size of x; offsets and windows included), 255 inside and 0 outside.  Its
+ *      summed-area table S is (H+1, W+1) int32: row 0 and column 0 are zero, S[y][x] = sum of m over rows < y and columns < x.  sat holds the
+ *      R tables one after the other.  geo is the step's cutout table as the cutters upload it: only its first cutn rows (oy, ox, h, w) are read.
+ *      For the box of cut k and table r
+ *          cov[k, r] = (S[oy+h][ox+w] - S[oy][ox+w] - S[oy+h][ox] + S[oy][ox]) / (255 h w)
+ *      with the numerator in integer arithmetic (exact) and one float32 division; cov = 0 when h w == 0.  A corner outside the frame is clamped
+ *      to it (callers upload boxes inside the frame; the clamp only keeps the reads inside the table).  region_of (P) int32 names prompt p's
+ *      table, or -1 for "everywhere" (cov = 1); power (P) float32 > 0.  The effective weight of row cut * B + b is
+ *          w_eff[cut, b, p] = weights[b, p] * cov[cut, region_of[p]] ** power[p]
+ *      (the power is not evaluated when it is exactly 1), and everything else is as in the plain entries: c = clip_guidance_scale / cutn,
+ *      the layout of the partials, accumulate, and the n <= 1e-6 rule of the directional loss.
+ *      Skipping: a column with w_eff == 0 is skipped and its target / direction row is not read, exactly as a zero weight is in the plain
+ *      entries.  A row whose every column is skipped has loss 0 and gradient bits all zero; under accumulate = 1 it is left untouched.  There
+ *      is no renormalisation per cutout: a cut that sees no region contributes nothing.
+ *      One launch of one wavefront per embedding row, as the plain entries; the coverage is computed in the kernel, once per prompt.
+ *      region_of_host is the caller's host copy of region_of.  A null pointer, R < 1, a region_of_host entry outside [-1, R), D > 2048, a
+ *      count below 1, or a frame with 255 H W >= 2^31 (the table is int32) fail with -2 before any launch. ---- */
+int cgd_spherical_loss_regions(cgd_ctx* ctx, const float* emb, const float* targets_n, const float* weights, float* d_emb, float* loss_part,
+                               int cutn, int B, int P, int D, float clip_guidance_scale, const int32_t* sat, const int32_t* region_of,
+                               const int32_t* region_of_host, const float* power, const int32_t* geo, int R, int H, int W, void* stream);
+int cgd_directional_loss_regions(cgd_ctx* ctx, const float* emb, const float* src_emb, const float* dirs_n, const float* weights, float* d_emb,
+                                 float* loss_part, int cutn, int B, int Bs, int P, int D, float clip_guidance_scale, int accumulate,
+                                 const int32_t* sat, const int32_t* region_of, const int32_t* region_of_host, const float* power,
+                                 const int32_t* geo, int R, int H, int W, void* stream);
+/* test and benchmark support: out (cutn, P) = cov[k, region_of[p]] ** power[p] from the device function the two losses use (1 where
+ * region_of[p] is -1); the same -2 cases */
+int cgd_op_region_coverage(cgd_ctx* ctx, const int32_t* sat, const int32_t* region_of, const int32_t* region_of_host, const float* power,
+                           const int32_t* geo, float* out, int cutn, int P, int R, int H, int W, void* stream);
+
 /* per-timestep scalars of the (respaced) diffusion process, float64 tables evaluated on the host */
 typedef struct cgd_step_coef {
   float sqrt_recip;             /* sqrt(1/abar_t)                                  */

@@ -77,7 +77,11 @@ class _Net:
         return out
 
     def load_state_dict(self, sd, prefix=""):
-        """Upload every parameter (fp32) and pack the forward / dgrad weight layouts."""
+        """Upload every parameter (fp32) and pack the forward / dgrad weight layouts.  Safe on any stream: cgd_*_set_param and
+        cgd_*_finalize run on the null stream, which a created (non-blocking) stream does not order with, so the current stream of the
+        context's device is drained once before the first upload — the conversions to fp32 enqueued here, whatever produced a device
+        state dict on that stream, and a pass of this handle that is still in flight."""
+        staged = []
         for name, numel in self.param_specs():
             key = prefix + name
             if key not in sd:
@@ -85,6 +89,9 @@ class _Net:
             t = sd[key].detach().to(dtype=th.float32).contiguous()
             if t.numel() != numel:
                 raise ValueError(f"{key}: expected {numel} elements, got {t.numel()}")
+            staged.append((name, t, numel))
+        th.cuda.current_stream(self.ctx.device).synchronize()
+        for name, t, numel in staged:
             self.ctx.check(self._fn("set_param")(self.h, name.encode(), t.data_ptr(), numel))
         self.ctx.check(self._fn("finalize")(self.h))
         return self

@@ -83,7 +83,13 @@ int cgd_unet_manifest(const cgd_unet_config* cfg, cgd_manifest_cb cb, void* user
 int cgd_unet_create(cgd_ctx* ctx, const cgd_unet_config* cfg, cgd_unet** out);
 void cgd_unet_destroy(cgd_unet* u);
 /* parameter ingestion, names = upstream state-dict keys (model.load_state_dict at script_util.py:317);
- * `data` may be a host or device pointer */
+ * `data` may be a host or device pointer.
+ * Streams (this and every other cgd_*_set_param / cgd_*_finalize below): they take no stream, run on the NULL stream and are
+ * host-synchronous — the copy and the packing are complete on return.  The null stream is not ordered with streams created
+ * non-blocking (every PyTorch stream is), so a device `data` must be COMPLETE before set_param is called — synchronise the stream
+ * that produced it, a dtype conversion enqueued just before included — and no pass of the handle may be in flight on any stream
+ * between the first set_param and the return of finalize.  (nets._Net.load_state_dict drains the caller's current stream once
+ * before its first set_param.) */
 int cgd_unet_num_params(cgd_unet* u);
 int cgd_unet_param_info(cgd_unet* u, int index, char* name_buf, int buf_len, int64_t* numel);
 int cgd_unet_set_param(cgd_unet* u, const char* name, const float* data, int64_t numel);

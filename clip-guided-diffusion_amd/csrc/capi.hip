@@ -393,6 +393,26 @@ int cgd_op_gemm(cgd_ctx* ctx, const float* A, int lda, const float* B, int ldb, 
   }
   return cgd_launch_gemm(ctx, p, S(stream));
 }
+int cgd_op_gemm_ex(cgd_ctx* ctx, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias, const float* R,
+                   int ldr, int M, int N, int K, float alpha, int force_tile, int splitk, int weight, int defer, void* stream) {
+  CGD_NEED_CTX(ctx);
+  GemmParams p;  // what net.h lin() sets, with the tile and slice count of the caller
+  p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc; p.bias = bias; p.R = R; p.ldr = ldr;
+  p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.force_tile = force_tile; p.splitk = splitk;
+  p.weight = weight;
+  p.defer = defer;
+  return cgd_launch_gemm(ctx, p, S(stream));
+}
+int cgd_op_pending(cgd_ctx* ctx, int64_t out[5]) {
+  if (!ctx || !out) return -3;
+  const PendingReduce& q = ctx->pending;
+  out[0] = q.valid ? 1 : 0;
+  out[1] = q.valid ? q.src.n : 0;
+  out[2] = q.valid ? q.M : 0;
+  out[3] = q.valid ? q.src.N : 0;
+  out[4] = q.valid ? q.ldc : 0;
+  return 0;
+}
 int cgd_op_gram(cgd_ctx* ctx, const float* A, int lda, int B, int N, int C, float scale, float* G_out, void* stream) {
   CGD_NEED_CTX(ctx);
   return cgd_launch_gram(ctx, A, lda, B, N, C, scale, G_out, nullptr, 0.f, 0.f, nullptr, 0, S(stream));

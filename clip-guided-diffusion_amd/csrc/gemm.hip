@@ -435,6 +435,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
           }
         }
       }
+      // (the compiler contracts alpha * sum + bias into ONE fused multiply-add here and in the scalar tail below; the consumers that sum the slices
+      // themselves, norm.hip split_load4 / split_load1, spell that FMA out so that they produce the same bits: tests/defer_checks.py compares them)
       float4 o = make_float4(alpha * s.x, alpha * s.y, alpha * s.z, alpha * s.w);
       if (bias) {
         o.x += bv.x; o.y += bv.y; o.z += bv.z; o.w += bv.w;

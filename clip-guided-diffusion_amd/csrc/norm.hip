@@ -59,11 +59,11 @@ __device__ __forceinline__ float4 split_load4(const SplitSrc& s, long row, int c
       }
     }
   }
-  a.x *= s.alpha; a.y *= s.alpha; a.z *= s.alpha; a.w *= s.alpha;
-  if (s.bias) {
-    const float4 bv = *(const float4*)(s.bias + col);
-    a.x += bv.x; a.y += bv.y; a.z += bv.z; a.w += bv.w;
-  }
+  // alpha * sum + bias in ONE rounding, as splitk_reduce_kernel does it: with alpha != 1 a separate multiply and add differ from it in the last bit
+  float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (s.bias) bv = *(const float4*)(s.bias + col);
+  a.x = __builtin_fmaf(s.alpha, a.x, bv.x); a.y = __builtin_fmaf(s.alpha, a.y, bv.y);
+  a.z = __builtin_fmaf(s.alpha, a.z, bv.z); a.w = __builtin_fmaf(s.alpha, a.w, bv.w);
   if (s.R) {
     const float4 rv = *(const float4*)(s.R + row * s.ldr + col);
     a.x += rv.x; a.y += rv.y; a.z += rv.z; a.w += rv.w;
@@ -81,8 +81,7 @@ __device__ __forceinline__ float split_load1(const SplitSrc& s, long row, int co
     for (int u = 0; u < 8; ++u)
       if (k0 + u < s.n) a += v[u];
   }
-  a *= s.alpha;
-  if (s.bias) a += s.bias[col];
+  a = __builtin_fmaf(s.alpha, a, s.bias ? s.bias[col] : 0.f);  // one rounding, as in splitk_reduce_kernel
   if (s.R) a += s.R[row * s.ldr + col];
   return a;
 }
@@ -800,7 +799,7 @@ __global__ __launch_bounds__(GS_NT) void gn_small_fwd_kernel(const float* x, flo
   float* yg = y ? y + (long)b * HW * ldy + g * cpg + q * VEC : nullptr;
   const long row0 = (long)b * HW;
   const int col = g * cpg + q * VEC;
-  // shift for the sums, common to the workgroup (see gn_stats_partial_kernel: never through the aliasable residual): the median of three elements
+  // shift for the sums, common to the workgroup: the median of three elements
   // of the group on different pixels AND different channels ((pixel i, channel i) for i = 0, 1, 2, clamped to the group).  One element would do for
   // |mean| >> sigma, but var = ss / n - ms * ms cancels when that element is itself an outlier (1000 sigma: rstd off by 6e-3 on a 1024-pixel x
   // 64-channel group); the median of these three is no outlier when one element, one whole pixel or one whole channel is.  Wave-uniform loads.
@@ -809,11 +808,12 @@ __global__ __launch_bounds__(GS_NT) void gn_small_fwd_kernel(const float* x, flo
     const int c1 = min(1, cpg - 1), c2 = min(2, cpg - 1), p1 = min(1, HW - 1), p2 = min(2, HW - 1);
     float ka, kb, kc;
     if (src.n) {
-      SplitSrc s0 = src;
-      s0.R = nullptr;
-      ka = split_load1(s0, row0, g * cpg);
-      kb = split_load1(s0, row0 + p1, g * cpg + c1);
-      kc = split_load1(s0, row0 + p2, g * cpg + c2);
+      // WITH the residual: a mean that arrives through R (|mean| = 100 sigma: rstd off by 1.2e-3) must be shifted away like any other.  R may alias
+      // the output (skip-conv result accumulated in place); the three elements lie in this workgroup's own slab, which no other workgroup writes,
+      // and a barrier (`rsync`) puts every thread's read of them before the slab's first write
+      ka = split_load1(src, row0, g * cpg);
+      kb = split_load1(src, row0 + p1, g * cpg + c1);
+      kc = split_load1(src, row0 + p2, g * cpg + c2);
     } else {
       const float* xk = x + (long)b * HW * ldx + g * cpg;
       ka = xk[0];
@@ -822,19 +822,29 @@ __global__ __launch_bounds__(GS_NT) void gn_small_fwd_kernel(const float* x, flo
     }
     k0 = fmaxf(fminf(ka, kb), fminf(fmaxf(ka, kb), kc));
   }
+  // does the residual overlap the tensor this launch writes back?  (kernel arguments only: uniform)
+  const long nrow = (long)gridDim.y * HW;
+  const bool rsync = src.n && src.R && src.R < xw + nrow * ldx && xw < src.R + nrow * src.ldr;
   float s = 0.f, ss = 0.f;
   V vc[CACHE ? 8 : 1];
   if constexpr (CACHE) {
 #pragma unroll
     for (int it = 0; it < 8; ++it) {
       const int p = r + it * rows;
-      if (act_q && p < HW) {
-        if (src.n) {
-          vc[it] = split_load<VEC>(src, row0 + p, col);
-          *(V*)(xwg + (long)p * ldx) = vc[it];
-        } else {
-          vc[it] = *(const V*)(xg + (long)p * ldx);
-        }
+      if (act_q && p < HW) vc[it] = src.n ? split_load<VEC>(src, row0 + p, col) : *(const V*)(xg + (long)p * ldx);
+    }
+    if (src.n) {
+      // the write-back.  Only the stores that may hit one of the shift's three elements (pixels and channels 0 .. 2 of the slab: the first vector of
+      // the threads with r < 3 on the first columns; rows >= 8) wait for the barrier; everything else goes out as before
+      const bool late = rsync && r < 3 && q * VEC < 3;
+#pragma unroll
+      for (int it = 0; it < 8; ++it) {
+        const int p = r + it * rows;
+        if (act_q && p < HW && !(it == 0 && late)) *(V*)(xwg + (long)p * ldx) = vc[it];
+      }
+      if (rsync) {
+        __syncthreads();
+        if (late && act_q && r < HW) *(V*)(xwg + (long)r * ldx) = vc[0];
       }
     }
 #pragma unroll
@@ -848,27 +858,30 @@ __global__ __launch_bounds__(GS_NT) void gn_small_fwd_kernel(const float* x, flo
         }
       }
     }
-  } else if (act_q) {
-    for (int p0 = r; p0 < HW; p0 += rows * GS_U) {
-      V v[GS_U];
+  } else {
+    if (rsync) __syncthreads();
+    if (act_q) {
+      for (int p0 = r; p0 < HW; p0 += rows * GS_U) {
+        V v[GS_U];
 #pragma unroll
-      for (int u = 0; u < GS_U; ++u) {
-        const int p = p0 + u * rows, pc = p < HW ? p : r;
-        if (src.n) {
-          v[u] = split_load<VEC>(src, row0 + pc, col);
-          if (p < HW) *(V*)(xwg + (long)pc * ldx) = v[u];  // the apply loop below re-reads what this thread wrote
-        } else {
-          v[u] = *(const V*)(xg + (long)pc * ldx);
+        for (int u = 0; u < GS_U; ++u) {
+          const int p = p0 + u * rows, pc = p < HW ? p : r;
+          if (src.n) {
+            v[u] = split_load<VEC>(src, row0 + pc, col);
+            if (p < HW) *(V*)(xwg + (long)pc * ldx) = v[u];  // the apply loop below re-reads what this thread wrote
+          } else {
+            v[u] = *(const V*)(xg + (long)pc * ldx);
+          }
         }
-      }
 #pragma unroll
-      for (int u = 0; u < GS_U; ++u) {
-        if (p0 + u * rows < HW) {
+        for (int u = 0; u < GS_U; ++u) {
+          if (p0 + u * rows < HW) {
 #pragma unroll
-          for (int e = 0; e < VEC; ++e) {
-            const float d = vget<VEC>(v[u], e) - k0;
-            s += d;
-            ss += d * d;
+            for (int e = 0; e < VEC; ++e) {
+              const float d = vget<VEC>(v[u], e) - k0;
+              s += d;
+              ss += d * d;
+            }
           }
         }
       }

@@ -86,6 +86,30 @@ def gemm(ctx, A, B, bias=None, R=None, alpha=1.0, force_tile=0, splitk=1, out=No
     return out
 
 
+def gemm_ex(ctx, A, B, bias=None, R=None, alpha=1.0, force_tile=0, splitk=1, weight=False, defer=False, out=None):
+    """gemm() with the two switches of the networks' linears: `weight` (B is a persistent weight: its packed copy is cached by pointer) and
+    `defer` (a launch that splits K leaves its slices to the norm that reads `out` next; `pending(ctx)` shows them)."""
+    M, K = A.shape
+    N = B.shape[0]
+    pa, lda = _rows(A, "A")
+    pb, ldb = _rows(B, "B")
+    pbias = _dense(bias, "bias")
+    pr, ldr = _rows(R, "R")
+    if out is None:
+        out = th.empty((M, N), device=A.device, dtype=th.float32)
+    pc, ldc = _rows(out, "out")
+    ctx.check(ctx.lib.cgd_op_gemm_ex(ctx.h, pa, lda, pb, ldb, pc, ldc, pbias, pr, ldr, M, N, K, float(alpha), force_tile, splitk, int(bool(weight)),
+                                     int(bool(defer)), _s()))
+    return out
+
+
+def pending(ctx):
+    """The deferred split-K reduction the context still holds: {valid, slices, rows, cols, ldc} (host state only, all zero when none)."""
+    out = (C.c_int64 * 5)()
+    ctx.check(ctx.lib.cgd_op_pending(ctx.h, out))
+    return dict(zip(("valid", "slices", "rows", "cols", "ldc"), (int(v) for v in out)))
+
+
 def gemm_gn_bwd(ctx, A, W, x, dz, coef, bcoef, add=None, out=None):
     """dx[B,HW,N] = A[B,HW,K] @ W[N,K]^T (+add) + GroupNorm+SiLU backward of (x, dz) with the per-(sample, channel) tables coef [B,N,4] =
     {a, b, -, mean} and bcoef [B,N,4] = {A1, A2, A3, -}, in one launch.  A, W, x, dz, add and `out` may be row-strided views."""

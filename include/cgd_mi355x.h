@@ -614,6 +614,15 @@ int cgd_ddim_reverse_update(cgd_ctx* ctx, const float* x, const float* model_out
  * CGD_KGEMM policy knobs.  splitk: >= 1 slices (1 = automatic), -1 = one slice, never split automatically. */
 int cgd_op_gemm(cgd_ctx* ctx, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias, const float* R,
                 int ldr, int M, int N, int K, float alpha, int force_tile, int splitk, void* stream);
+/* cgd_op_gemm with the two switches the networks' linears set (test support, like cgd_op_conv3x3_ex).  weight = 1: B is a persistent weight, the
+ * weight GEMM kernel caches its fragment copy by B's pointer (B must then keep its content for the life of the context).  defer = 1: a launch that
+ * splits K leaves its slices in the context workspace; see cgd_op_conv3x3_ex for who sums them. */
+int cgd_op_gemm_ex(cgd_ctx* ctx, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias, const float* R,
+                   int ldr, int M, int N, int K, float alpha, int force_tile, int splitk, int weight, int defer, void* stream);
+/* host only, reads nothing on the device and changes nothing: the deferred split-K reduction the context still holds,
+ * out5 = {valid, slices, rows, columns, row stride of the output}; all zero when nothing is pending.  With out2[1] of cgd_launch_counts a test can
+ * tell whether a reader summed the slices itself (counter unchanged, nothing pending afterwards) or a reduce launch ran (counter + 1). */
+int cgd_op_pending(cgd_ctx* ctx, int64_t out5[5]);
 /* G[b] = scale * A_b^T A_b for A [B * N][C] (row stride lda >= C, a multiple of 4; 16-byte aligned), C in {64, 128, 256, 512}, any N >= 1: the tall-skinny
  * contraction of the style loss (csrc/gram.hip).  Exact fp32 products whatever the context precision; bit-identical from run to run. */
 int cgd_op_gram(cgd_ctx* ctx, const float* A, int lda, int B, int N, int C, float scale, float* G_out /* [B][C][C] */, void* stream);
@@ -650,8 +659,13 @@ int cgd_op_conv3x3(cgd_ctx* ctx, const float* x_nhwc, int ldx, const float* w_pa
                    int splitk, void* stream);
 /* cgd_op_conv3x3 with the add-ons the UNet's ResBlocks switch on (test support, like cgd_op_conv3x3_wino_ex below).  gn_ab: per-(sample,
  * channel) pairs {a, b} [Bn][Cin][2]; the conv then runs on SiLU(x * a + b), applied in the patch staging (halo conv kernels only: any other
- * route is refused).  defer = 1: a launch that splits K leaves its slices to the cgd_op_gn_fwd / cgd_op_gn_bwd that reads y next.  stats,
- * gnb_x, gnb_ldx, gnb_scratch: as in cgd_op_conv3x3_wino_ex. */
+ * route is refused).  defer = 1: a launch that splits K leaves its slices in the context workspace (unless CGD_DEFER=0).  The next entry of the
+ * context sums them: a cgd_op_gn_fwd (x) / cgd_op_gn_bwd (dz) / cgd_op_ln_fwd (x) / cgd_op_ln_bwd (dy) on exactly this tensor (pointer, rows,
+ * columns, row stride, stream) at load time, writing the finished tensor back as it goes (cgd_op_ln_bwd and the register-cached single-launch cgd_op_gn_bwd keep dy / dz in
+ * registers and do NOT write it back: that buffer then never holds the finished tensor; the LayerNorms
+ * only at C = 256 / 512 / 768 / 1024, the single-launch GroupNorms only with CGD_DEFER >= 2); a norm that does not match, and every GEMM / conv,
+ * pooling / upsampling, activation, attention and Gram entry, runs the reduce launch first, on the producer's stream.  stats, gnb_x, gnb_ldx, gnb_scratch: as in
+ * cgd_op_conv3x3_wino_ex. */
 int cgd_op_conv3x3_ex(cgd_ctx* ctx, const float* x_nhwc, int ldx, const float* w_packed, const float* w_frag, float* y_nhwc, int ldy,
                       const float* bias, const float* R, int ldr, const float* gn_ab, int Bn, int H, int W, int Cin, int Cout,
                       int upsample_input, int force_tile, int splitk, int defer, int stats, const float* gnb_x, int gnb_ldx,

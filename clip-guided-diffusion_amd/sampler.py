@@ -23,6 +23,7 @@ DDIM inversion (`ddim_reverse_sample_loop_progressive`, `ddim_invert`; guided_di
 upwards from an image: per step one UNet forward and one cgd_ddim_reverse_update launch.  `ddim_invert` returns the latent and the noise that
 q_samples the image to it, so every loop above starts from the latent when called with `noise=noise, init_image=image, skip_timesteps=s`.
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -32,6 +33,15 @@ import torch as th
 from . import lib as L
 from .guidance import ClipGuidance
 from .nets import UNetFunction  # noqa: F401  (re-exported: the autograd node of model(x, ts, y))
+
+
+def _timestep_table(tables, steps, B, device):
+    """model timesteps of step indices 0 .. steps - 1 on the device (one row per step, B columns): no per-step fill kernel"""
+    return th.tensor([float(tables.model_timestep(k)) for k in range(steps)], dtype=th.float32, device=device).view(-1, 1).repeat(1, B).contiguous()
+
+
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
 
 
 class EmbedAhead:
@@ -61,9 +71,8 @@ class EmbedAhead:
         self.fwd_seen = [False, False]
         self.n = 0  # the step whose forward comes next
         main = th.cuda.current_stream(dev)
-        # model timesteps of the whole schedule (one row per step, B columns), built on the main stream: the side stream waits for it once
-        self.tt = th.tensor([float(sampler.tables.model_timestep(k)) for k in range(sampler.num_timesteps)], dtype=th.float32,
-                            device=dev).view(-1, 1).repeat(1, B).contiguous()
+        # model timesteps of the whole schedule, built on the main stream: the side stream waits for it once
+        self.tt = _timestep_table(sampler.tables, sampler.num_timesteps, B, dev)
         ready = th.cuda.Event()
         ready.record(main)
         self.side.wait_event(ready)
@@ -94,6 +103,270 @@ class EmbedAhead:
         self.fwd_seen[slot] = True
         self.n += 1
         return o
+
+
+class _Run:
+    """State of one loop call: the model, cond_fn and model_kwargs, the work buffers of the evaluation (allocated once, for the loop's
+    shape), the model-timestep table, the optional EmbedAhead (the loop may drop it), the post-update rewrite (None, _Mask or _Ilvr), one
+    keep-alive slot for what the last update's launches read."""
+    Eval = collections.namedtuple("Eval", "x0 mean logvar g scal noise coef ts fac_index n_known")  # what `evaluate` hands to the update
+
+    def __init__(self, sampler, model, cond_fn, model_kwargs, img, rewrite=None):
+        self.sampler, self.model, self.cond_fn, self.model_kwargs, self.rewrite = sampler, model, cond_fn, model_kwargs, rewrite
+        self.native = isinstance(cond_fn, ClipGuidance)
+        (B, _, H, W), dev = img.shape, img.device
+        self.dims = (B, H, W)
+        self.x0, self.mean, self.logvar, self.xin = (th.empty((B, 3, H, W), device=dev, dtype=th.float32) for _ in range(4))
+        # the generic plugin path calls model(x, ts, y), which allocates its own output
+        self.out6 = th.empty((B, 6, H, W), device=dev, dtype=th.float32) if (cond_fn is None or self.native) else None
+        self.ts = _timestep_table(sampler.tables, sampler.num_timesteps, B, dev)
+        self.ahead = self.keep = None
+
+    def evaluate(self, x, i, noise, draw_noise=True, n_known=None):
+        """One guided evaluation at (x, i): UNet forward -> p_mean_variance tail + blend -> (noise draw) -> cond_fn.  Returns the pieces
+        the update kernels read; nothing of the update itself.  `n_known` is passed through, except True (a rewrite in a stochastic
+        loop): the noise of the kept region is drawn right after the step's own."""
+        smp, model, cond_fn, native = self.sampler, self.model, self.cond_fn, self.native
+        ctx, lib = smp.ctx, smp.ctx.lib
+        B, _, H, W = x.shape
+        fac_index = cond_fn.fac_index() if native else None
+        coef = smp.tables.step_coef(i, fac_index)
+        ts, y = self.ts[i], self.model_kwargs.get("y")
+        x0, mean, logvar, xin, scal = self.x0, self.mean, self.logvar, self.xin, None
+        if cond_fn is None or native:
+            if self.ahead is not None:
+                # the embedding head of this step ran ahead on the side stream (EmbedAhead): wait for it, run the rest of the model
+                out6 = self.ahead.forward(model, x, self.out6)
+            else:
+                out6 = model.forward(x, ts, y, out=self.out6)
+            ctx.check(lib.cgd_pmv_blend(ctx.h, x.data_ptr(), out6.data_ptr(), x0.data_ptr(), mean.data_ptr(), logvar.data_ptr(),
+                                        xin.data_ptr(), B, H, W, coef, ctx.stream()))
+            if noise is None and draw_noise:
+                noise = smp._draw_like(x)  # drawn before cond_fn, as in p_sample_with_grad
+            n_known = smp._draw_like(x) if n_known is True else n_known
+            if native:
+                cond_fn.step_ts = ts  # the model timesteps this forward received: a classifier term is evaluated at them
+            g = cond_fn.native(x, x0, xin, coef) if native else None
+            scal = cond_fn.scalars if (native and g is not None and cond_fn.use_magnitude) else None
+        else:
+            # generic plugin path: reference semantics via autograd over the C-ABI UNet node
+            with th.enable_grad():
+                xr = x.detach().requires_grad_()
+                out6 = model(xr, ts, y)  # autograd node over cgd_unet_forward / cgd_unet_dgrad (nets.UNetFunction)
+                eps, v = out6[:, :3], out6[:, 3:]
+                frac = (v + 1) / 2
+                lv = frac * coef.max_log + (1 - frac) * coef.min_log
+                p0 = coef.sqrt_recip * xr - coef.sqrt_recipm1 * eps
+                mu = coef.coef1 * p0 + coef.coef2 * xr
+                if noise is None and draw_noise:
+                    noise = smp._draw_like(x)
+                n_known = smp._draw_like(x) if n_known is True else n_known
+                t_idx = th.full((B,), i, device=x.device, dtype=th.long)
+                p = {"mean": mu, "variance": th.exp(lv), "log_variance": lv, "pred_xstart": p0}
+                g = cond_fn(xr, t_idx, p, **self.model_kwargs)
+            g = g.detach().float().contiguous()
+            x0.copy_(p0.detach()); mean.copy_(mu.detach()); logvar.copy_(lv.detach())
+        return self.Eval(x0, mean, logvar, g, scal, noise, coef, ts, fac_index, n_known)
+
+
+class _Rewrite:
+    """What `mask=` and `ilvr=` put after every update: a region of the new state (the mask's kept region, ILVR's low-frequency band) is
+    replaced by that of an image (the init image, the reference) noised to the level the update produced.  Two operations: `noise` before
+    the step's evaluation, `apply` after its update; subclasses launch."""
+    stop = 0  # step indices below it are left alone (ILVR's stop index)
+
+    def __init__(self, sampler, x_T, stochastic):
+        self.sampler, self.x_T, self.stochastic = sampler, x_T.contiguous(), stochastic
+        self.used, self.keep = 0, None  # tape entries taken; what the last launch read
+
+    def noise(self, x, i):
+        """-> the noise of the image for the next `apply`, or True for the evaluation to draw it: the loop's initial noise in the
+        deterministic loops (the tensor that q_sampled the init image at the first index: the region follows one trajectory and nothing is
+        drawn); in the stochastic loops the tape's next entry, or a fresh draw that the evaluation takes right after the step's own noise.
+        Below the stop index, where nothing is rewritten, nothing is drawn."""
+        if i < self.stop:
+            return None
+        if not self.stochastic:
+            return self.x_T
+        if self.sampler.tape is None:
+            return True
+        self.used += 1
+        return self.sampler.tape[self.tape_key][self.used - 1].to(x.device).float().contiguous()
+
+    def apply(self, i, sample, x0_out, n, again=False):
+        """After the update of step index i: `sample` (the state at level i - 1) and `x0_out` (or None) are rewritten in place, with the
+        image noised by `n`.  `again` (masks only): this step index runs once more, the re-noised state is returned; otherwise None."""
+        if i < self.stop:
+            return None
+        k = self.sampler.tables.mask_coef(i)
+        return self.launch(k, sample, x0_out, n if k.sqrt_one_minus_ab_prev != 0.0 else None, again)  # i == 0: the image itself, no noise
+
+
+class _Mask(_Rewrite):
+    """cgd_masked_merge: the init image goes back into the kept region (mask 0).  With `again` the same launch writes the merged sample
+    taken back up to level i (resamples > 1), with the tape's next 'renoise' entry or a fresh draw."""
+    tape_key = "known_noise"
+
+    def __init__(self, sampler, x_T, stochastic, init, mask):
+        super().__init__(sampler, x_T, stochastic)
+        self.init, self.mask = (t.to(x_T.device).float().contiguous() for t in (init, mask))
+        self.renoised = 0  # entries of the tape's 'renoise' taken
+
+    def launch(self, k, sample, x0_out, n_known, again):
+        smp, ctx = self.sampler, self.sampler.ctx
+        B, _, H, W = sample.shape
+        n_re = x_re = None
+        if again:
+            n_re = smp._draw_like(sample) if smp.tape is None else smp.tape["renoise"][self.renoised].to(sample.device).float().contiguous()
+            self.renoised += 1
+            x_re = th.empty_like(sample)
+        k.flags = (L.MASK_PRED_XSTART if x0_out is not None else 0) | (L.MASK_N_KNOWN if n_known is not None else 0) | \
+            (L.MASK_RENOISE if n_re is not None else 0)
+        init, mask = self.init, self.mask
+        ctx.check(ctx.lib.cgd_masked_merge(ctx.h, sample.data_ptr(), L.ptr(x0_out), init.data_ptr(), mask.data_ptr(), L.ptr(n_known),
+                                           L.ptr(n_re), L.ptr(x_re), B, H, W, init.shape[0], mask.shape[0], mask.shape[1], k, ctx.stream()))
+        self.keep = (n_known, n_re)
+        return x_re
+
+
+class _Ilvr(_Rewrite):
+    """cgd_ilvr_refine at step indices >= stop: the low-frequency band of the state becomes that of the reference noised to the state's
+    level, the one of pred_xstart that of the reference.  The scratch of the two launches lives as long as the loop."""
+    tape_key = "ilvr_noise"
+
+    def __init__(self, sampler, x_T, stochastic, ref, factor, stop):
+        super().__init__(sampler, x_T, stochastic)
+        if sampler.shard is not None and ref.shape[0] == sampler.shard[1] and ref.shape[0] != 1:
+            ref = ref[sampler.shard[0]]  # a reference of the global batch: this rank's rows
+        self.ref, self.factor, self.stop = ref.to(x_T.device).float().contiguous(), factor, stop
+        floats = sampler.ctx.lib.cgd_ilvr_scratch_floats(x_T.shape[0], x_T.shape[2], x_T.shape[3], factor, 1)
+        self.scratch = th.empty(int(floats), device=x_T.device, dtype=th.float32)
+
+    def launch(self, k, sample, x0_out, n, again):
+        ctx, ref = self.sampler.ctx, self.ref
+        B, _, H, W = sample.shape
+        ctx.check(ctx.lib.cgd_ilvr_refine(ctx.h, sample.data_ptr(), L.ptr(x0_out), ref.data_ptr(), L.ptr(n), self.scratch.data_ptr(),
+                                          B, H, W, ref.shape[0], self.factor, k.sqrt_ab_prev, k.sqrt_one_minus_ab_prev, ctx.stream()))
+        self.keep = (n,)
+
+
+class _Stepper:
+    """The update rule of one loop.  `step` is what the loop calls: rewrite noise -> guided evaluation -> `update` (the subclass's launches,
+    which returns what they read, to be kept alive) -> rewrite."""
+    draws_noise = False  # whether every evaluation takes a per-step noise: a fresh draw, or the replay tape's next entry
+    stochastic = False  # whether that noise enters the state, so that a rewrite noises its image afresh per step too
+    one_evaluation = True  # per step, which EmbedAhead's one-embedding-per-step choreography assumes
+
+    def step(self, run, x, i, noise, again=False):
+        """One step at (x, i) -> ({"sample", "pred_xstart"}, the re-noised state when the step index runs `again`, else None)"""
+        ev = run.evaluate(x, i, noise, self.draws_noise, run.rewrite.noise(x, i) if run.rewrite is not None else None)
+        sample, x0_out = th.empty_like(x), th.empty_like(x)
+        run.keep = self.update(run, x, i, ev, sample, x0_out)
+        x_re = run.rewrite.apply(i, sample, x0_out, ev.n_known, again) if run.rewrite is not None else None
+        return {"sample": sample, "pred_xstart": x0_out}, x_re
+
+
+class _Ancestral(_Stepper):
+    """p_sample, or DDIM with `eta`.  DDIM with eta > 0 runs its update through cgd_multistep_update (phase 3); eta == 0 keeps
+    cgd_sample_update mode 1, which takes a noise tensor (a draw, or the tape's entry) that its update does not use: the loop stays
+    deterministic and a rewrite follows the loop's initial noise."""
+    draws_noise = True
+
+    def __init__(self, ddim=False, eta=0.0):
+        self.mode, self.eta, self.stochastic = (1 if ddim else 0), eta, not ddim or bool(eta)  # mode: cgd_sample_update's
+
+    def update(self, run, x, i, ev, sample, x0_out):
+        tables, ctx = run.sampler.tables, run.sampler.ctx
+        if self.eta:
+            ab, abp = float(tables.alphas_cumprod[i]), float(tables.alphas_cumprod_prev[i])
+            sigma = self.eta * math.sqrt((1 - abp) / (1 - ab)) * math.sqrt(1 - ab / abp)
+            m = L.Multistep(3, 0, sigma, math.sqrt(max(0.0, 1 - abp - sigma * sigma)))
+            ctx.check(ctx.lib.cgd_multistep_update(ctx.h, x.data_ptr(), None, ev.x0.data_ptr(), L.ptr(ev.g), L.ptr(ev.scal), ev.noise.data_ptr(),
+                                                   None, None, sample.data_ptr(), x0_out.data_ptr(), *run.dims, ev.coef, None, m, ctx.stream()))
+        else:
+            ctx.check(ctx.lib.cgd_sample_update(ctx.h, x.data_ptr(), ev.x0.data_ptr(), ev.mean.data_ptr(), ev.logvar.data_ptr(), L.ptr(ev.g),
+                                                ev.noise.data_ptr(), L.ptr(ev.scal), sample.data_ptr(), x0_out.data_ptr(), *run.dims, ev.coef,
+                                                self.mode, ctx.stream()))
+        return ev.noise, ev.g, ev.ts
+
+
+class _Plms(_Stepper):
+    """PLMS (plms_sample of the guided_diffusion fork); draws no noise.  `old_eps`: history buffers (oldest first), `free`: spare buffers.
+    The history rotates by pointer: the buffer dropped from the front is the next step's eps_out.  Under a rewrite the start step's
+    predictor (level i - 1, the input of the second evaluation) is rewritten before that evaluation, and every step's result afterwards;
+    the eps history stays as evaluated."""
+    one_evaluation = False  # the start step evaluates twice
+
+    def __init__(self, order):
+        self.order, self.old_eps, self.free = order, [], []
+
+    def update(self, run, x, i, ev, sample, x0_out):
+        tables, ctx, lib = run.sampler.tables, run.sampler.ctx, run.sampler.ctx.lib
+        order, old, g, s = self.order, self.old_eps, ev.g, ctx.stream()
+        eps_new = self.free.pop() if self.free else th.empty_like(x)
+        if order > 1 and not old:
+            # start step, pseudo improved Euler: predictor at t, a second guided evaluation at (predictor, t-1), corrector
+            xp = th.empty_like(x)  # once per loop: the history is never empty again
+            ctx.check(lib.cgd_multistep_update(ctx.h, x.data_ptr(), None, ev.x0.data_ptr(), L.ptr(g), L.ptr(ev.scal), None, None,
+                                               eps_new.data_ptr(), xp.data_ptr(), x0_out.data_ptr(), *run.dims, ev.coef, None,
+                                               L.Multistep(1, 0, 0.0, 0.0), s))
+            old.append(eps_new)
+            if run.rewrite is not None:
+                run.rewrite.apply(i, xp, None, ev.n_known)
+            ev2 = run.evaluate(xp, i - 1, None, False)
+            hist = (C.c_void_p * 3)(eps_new.data_ptr(), None, None)
+            k_t = tables.step_coef(i, ev.fac_index)
+            ctx.check(lib.cgd_multistep_update(ctx.h, x.data_ptr(), xp.data_ptr(), ev2.x0.data_ptr(), L.ptr(ev2.g), L.ptr(ev2.scal), None,
+                                               hist, None, sample.data_ptr(), None, *run.dims, ev2.coef, k_t, L.Multistep(2, 0, 0.0, 0.0), s))
+            keep = (g, ev2.g, ev.ts, ev2.ts, xp)
+        else:
+            # Adams-Bashforth of min(order, history + 1) terms, the newest history entry first
+            prev = [old[-1 - j].data_ptr() if j < len(old) else None for j in range(3)]
+            ctx.check(lib.cgd_multistep_update(ctx.h, x.data_ptr(), None, ev.x0.data_ptr(), L.ptr(g), L.ptr(ev.scal), None,
+                                               (C.c_void_p * 3)(*prev), eps_new.data_ptr(), sample.data_ptr(), x0_out.data_ptr(), *run.dims,
+                                               ev.coef, None, L.Multistep(0, min(order, len(old) + 1), 0.0, 0.0), s))
+            old.append(eps_new)
+            keep = (g, ev.ts)
+        if len(old) >= order:
+            self.free.append(old.pop(0))
+        return keep
+
+
+class _Dpmpp(_Stepper):
+    """DPM-Solver++(2M).  `hist`: the guided pred_xstart of the step before (None on the first step, which therefore runs at order 1),
+    `free`: the spare buffer.  The history rotates by pointer: the entry the launch has read is the buffer the next launch writes.  Step
+    index 0 runs at order 1 (diffusion.dpmpp_coef) and nothing reads the entry of step index 1 or 0, so those are not written.  Under a
+    rewrite the history stays as evaluated.
+    `threshold` (p, cap): cgd_dpmpp_threshold writes the guided pred_xstart to a buffer and selects the sample's scale s on the device,
+    cgd_dpmpp_update_thr clamps, rescales and updates.  The buffer, the (B, 3) result and the selection's scratch (`thr`) are allocated once."""
+
+    def __init__(self, order, eta, threshold):
+        self.order, self.eta, self.threshold, self.hist, self.free, self.thr = order, eta, threshold, None, [], None
+        self.draws_noise = self.stochastic = bool(eta)  # eta > 0: the SDE solver
+
+    def update(self, run, x, i, ev, sample, x0_out):
+        tables, ctx, lib = run.sampler.tables, run.sampler.ctx, run.sampler.ctx.lib
+        (B, H, W), noise, g, hist = run.dims, ev.noise, ev.g, self.hist
+        d = tables.dpmpp_coef(i, 2 if (self.order == 2 and hist is not None) else 1, self.eta)
+        x0c = (self.free.pop() if self.free else th.empty_like(x)) if (self.order == 2 and i > 1) else None
+        tail = (L.ptr(noise), L.ptr(hist) if d.c_r else None, L.ptr(x0c), sample.data_ptr(), x0_out.data_ptr(), B, H, W, ev.coef, d, ctx.stream())
+        if self.threshold is not None:
+            p, cap = self.threshold
+            if self.thr is None:
+                n = 3 * H * W
+                # cap == 1: every scale is 1 (the static clip), nothing is selected and no scratch is needed
+                scratch = th.empty(int(lib.cgd_abs_quantile_scratch_bytes(B, n)), dtype=th.uint8, device=x.device) if cap > 1.0 else None
+                self.thr = (th.empty_like(x), th.empty((B, 3), dtype=th.float32, device=x.device), scratch, tables.threshold_rank(p, n))
+            raw, thr3, scratch, (rank, frac) = self.thr
+            ctx.check(lib.cgd_dpmpp_threshold(ctx.h, x.data_ptr(), ev.x0.data_ptr(), L.ptr(g), L.ptr(ev.scal), raw.data_ptr(), B, H, W,
+                                              ev.coef, rank, frac, 1.0, cap, thr3.data_ptr(), L.ptr(scratch), ctx.stream()))
+            ctx.check(lib.cgd_dpmpp_update_thr(ctx.h, x.data_ptr(), ev.x0.data_ptr(), raw.data_ptr(), thr3.data_ptr(), *tail))
+        else:
+            ctx.check(lib.cgd_dpmpp_update(ctx.h, x.data_ptr(), ev.x0.data_ptr(), L.ptr(g), L.ptr(ev.scal), *tail))
+        if hist is not None:
+            self.free.append(hist)
+        self.hist = x0c
+        return noise, g, ev.ts
 
 
 class GuidedSampler:
@@ -137,139 +410,9 @@ class GuidedSampler:
             low = low[self.shard[0]]
         model.set_low_res(low)
 
-    # ---- one step -------------------------------------------------------------------------------------
-    def _evaluate(self, model, x, i, cond_fn, model_kwargs, noise, bufs, ahead=None, draw_noise=True, draw_known=False):
-        """One guided evaluation at (x, i): UNet forward -> p_mean_variance tail + blend -> (noise draw) -> cond_fn.  Returns the pieces
-        the update kernels read; nothing of the update itself.  `draw_known`: masked sampling in a stochastic loop, the noise of the
-        kept region is drawn right after the step's own."""
-        ctx, lib = self.ctx, self.ctx.lib
-        B, _, H, W = x.shape
-        dev = x.device
-        s = ctx.stream()
-        native = isinstance(cond_fn, ClipGuidance)
-        fac_index = cond_fn.fac_index() if native else None
-        coef = self.tables.step_coef(i, fac_index)
-        # model timesteps of the whole schedule live on the device (one row per step, B columns): no per-step fill kernel
-        tt = bufs.get("_ts")
-        if tt is None or tt.shape[1] != B or tt.device != dev:
-            tt = bufs["_ts"] = th.tensor([float(self.tables.model_timestep(k)) for k in range(self.num_timesteps)], dtype=th.float32,
-                                         device=dev).view(-1, 1).repeat(1, B).contiguous()
-        ts = tt[i]
-        y = model_kwargs.get("y") if model_kwargs else None
-
-        def buf(name, shape):
-            t = bufs.get(name)
-            if t is None or tuple(t.shape) != tuple(shape):
-                t = bufs[name] = th.empty(shape, device=dev, dtype=th.float32)
-            return t
-
-        x0, mean, logvar, xin = (buf(n, (B, 3, H, W)) for n in ("x0", "mean", "logvar", "xin"))
-        scal = None
-        if cond_fn is None or native:
-            if ahead is not None:
-                # the embedding head of this step ran ahead on the side stream (EmbedAhead): wait for it, run the rest of the model
-                out6 = ahead.forward(model, x, buf("out6", (B, 6, H, W)))
-            else:
-                out6 = model.forward(x, ts, y, out=buf("out6", (B, 6, H, W)))
-            ctx.check(lib.cgd_pmv_blend(ctx.h, x.data_ptr(), out6.data_ptr(), x0.data_ptr(), mean.data_ptr(), logvar.data_ptr(),
-                                        xin.data_ptr(), B, H, W, coef, s))
-            if noise is None and draw_noise:
-                noise = self._draw_like(x)  # drawn before cond_fn, as in p_sample_with_grad
-            n_known = self._draw_like(x) if draw_known else None
-            if native:
-                cond_fn.step_ts = ts  # the model timesteps this forward received: a classifier term is evaluated at them
-            g = cond_fn.native(x, x0, xin, coef) if native else None
-            scal = cond_fn.scalars if (native and g is not None and cond_fn.use_magnitude) else None
-        else:
-            # generic plugin path: reference semantics via autograd over the C-ABI UNet node
-            with th.enable_grad():
-                xr = x.detach().requires_grad_()
-                out6 = model(xr, ts, y)  # autograd node over cgd_unet_forward / cgd_unet_dgrad (nets.UNetFunction)
-                eps, v = out6[:, :3], out6[:, 3:]
-                frac = (v + 1) / 2
-                lv = frac * coef.max_log + (1 - frac) * coef.min_log
-                p0 = coef.sqrt_recip * xr - coef.sqrt_recipm1 * eps
-                mu = coef.coef1 * p0 + coef.coef2 * xr
-                if noise is None and draw_noise:
-                    noise = self._draw_like(x)
-                n_known = self._draw_like(x) if draw_known else None
-                t_idx = th.full((B,), i, device=dev, dtype=th.long)
-                p = {"mean": mu, "variance": th.exp(lv), "log_variance": lv, "pred_xstart": p0}
-                g = cond_fn(xr, t_idx, p, **(model_kwargs or {}))
-            g = g.detach().float().contiguous()
-            x0.copy_(p0.detach()); mean.copy_(mu.detach()); logvar.copy_(lv.detach())
-        return {"x0": x0, "mean": mean, "logvar": logvar, "g": g, "scal": scal, "noise": noise, "coef": coef, "ts": ts,
-                "fac_index": fac_index, "n_known": n_known}
-
-    # ---- masked sampling ------------------------------------------------------------------------------
-    def _known_noise(self, masked, x, i=None):
-        """Before a step's evaluation -> (noise of the kept region for the next merge, whether _evaluate draws it instead): the loop's
-        initial noise in the deterministic loops (the tensor that q_sampled the init image at the first index: the kept region follows one
-        trajectory and nothing is drawn); in the stochastic loops the tape's next entry, or a fresh draw that _evaluate takes right after
-        the step's own noise.  (None, False) without a mask.  ILVR keeps its state in `masked` too: the reference's noise follows the
-        same rules (tape entry 'ilvr_noise'), and below its stop index, where nothing is refined, nothing is drawn."""
-        if masked is not None and "ilvr" in masked and i < masked["ilvr"][2]:
-            return None, False
-        if masked is None or not masked["stochastic"]:
-            return (masked["x_T"] if masked is not None else None), False
-        if self.tape is None:
-            return None, True
-        masked["known"] += 1
-        key = "ilvr_noise" if "ilvr" in masked else "known_noise"
-        return self.tape[key][masked["known"] - 1].to(x.device).float().contiguous(), False
-
-    def _renoise(self, masked, x):
-        """The draw that takes a merged state back up one level (resamples > 1): the tape's next entry or a fresh one."""
-        if self.tape is None:
-            return self._draw_like(x)
-        masked["re"] += 1
-        return self.tape["renoise"][masked["re"] - 1].to(x.device).float().contiguous()
-
-    def _merge(self, masked, i, sample, x0_out, n_known, n_re=None):
-        """cgd_masked_merge after the update of step index i: `sample` (the state at level i - 1) and `x0_out` (or None) are merged in
-        place.  With `n_re` the same launch writes the merged sample taken back up to level i, which is returned."""
-        ctx = self.ctx
-        B, _, H, W = sample.shape
-        k = self.tables.mask_coef(i)
-        if k.sqrt_one_minus_ab_prev == 0.0:
-            n_known = None  # i == 0: the known region is the init image itself
-        x_re = th.empty_like(sample) if n_re is not None else None
-        k.flags = (L.MASK_PRED_XSTART if x0_out is not None else 0) | (L.MASK_N_KNOWN if n_known is not None else 0) | \
-            (L.MASK_RENOISE if n_re is not None else 0)
-        init, mask = masked["init"], masked["mask"]
-        ctx.check(ctx.lib.cgd_masked_merge(ctx.h, sample.data_ptr(), L.ptr(x0_out), init.data_ptr(), mask.data_ptr(), L.ptr(n_known),
-                                           L.ptr(n_re), L.ptr(x_re), B, H, W, init.shape[0], mask.shape[0], mask.shape[1], k, ctx.stream()))
-        masked["_keep"] = (n_known, n_re)
-        return x_re
-
-    def _refine(self, masked, i, sample, x0_out, n):
-        """cgd_ilvr_refine after the update of step index i >= stop: the low-frequency band of `sample` (the state at level i - 1) becomes
-        that of the reference noised to that level with `n`, the one of `x0_out` (or None) that of the reference; both in place."""
-        ctx = self.ctx
-        B, _, H, W = sample.shape
-        ref, factor, stop = masked["ilvr"]
-        if i < stop:
-            return
-        k = self.tables.mask_coef(i)
-        if k.sqrt_one_minus_ab_prev == 0.0:
-            n = None  # i == 0: the reference itself
-        ctx.check(ctx.lib.cgd_ilvr_refine(ctx.h, sample.data_ptr(), L.ptr(x0_out), ref.data_ptr(), L.ptr(n), masked["scratch"].data_ptr(),
-                                          B, H, W, ref.shape[0], factor, k.sqrt_ab_prev, k.sqrt_one_minus_ab_prev, ctx.stream()))
-        masked["_keep"] = (n,)
-
-    def _masked_end(self, masked, ev, i, sample, x0_out, n_known, again=False):
-        """After a step's update: the merge with the kept region's noise (`n_known`, or the one `ev` drew).  `again`: this step index runs
-        once more, the re-noised state is returned; otherwise (and without a mask, where nothing runs) None.  Under ILVR the refinement
-        stands in the merge's place."""
-        if masked is not None and "ilvr" in masked:
-            return self._refine(masked, i, sample, x0_out, n_known if n_known is not None else ev["n_known"])
-        if masked is not None:
-            return self._merge(masked, i, sample, x0_out, n_known if n_known is not None else ev["n_known"],
-                               self._renoise(masked, sample) if again else None)
-
     @staticmethod
     def _check_mask(shape, init_image, mask, resamples, plms=False):
-        if isinstance(resamples, bool) or not isinstance(resamples, int) or resamples < 1:
+        if not _is_int(resamples) or resamples < 1:
             raise ValueError(f"resamples must be an int >= 1, got {resamples!r}")
         if resamples > 1 and plms:
             raise ValueError("PLMS cannot resample: its eps history would mix noise levels (use the p_sample or DDIM loop)")
@@ -294,14 +437,14 @@ class GuidedSampler:
             return None
         if mask is not None:
             raise ValueError("ilvr and mask cannot be combined: both rewrite the state after every update")
-        if isinstance(resamples, int) and not isinstance(resamples, bool) and resamples > 1:
+        if _is_int(resamples) and resamples > 1:
             raise ValueError("ilvr cannot resample: resamples > 1 repeats the merge of masked sampling")
         if not isinstance(ilvr, (tuple, list)) or len(ilvr) not in (2, 3):
             raise ValueError("ilvr must be (ref, factor) or (ref, factor, stop)")
         ref, factor = ilvr[0], ilvr[1]
         stop = ilvr[2] if len(ilvr) == 3 else 0
         B, H, W = shape[0], shape[2], shape[3]
-        if isinstance(factor, bool) or not isinstance(factor, int) or not 2 <= factor <= 64 or factor & (factor - 1):
+        if not _is_int(factor) or not 2 <= factor <= 64 or factor & (factor - 1):
             raise ValueError(f"the ilvr factor must be a power of two in [2, 64], got {factor!r}")
         if H % factor or W % factor:
             raise ValueError(f"the ilvr factor {factor} does not divide the {H} x {W} frame")
@@ -310,123 +453,9 @@ class GuidedSampler:
         gb = self.shard[1] if self.shard is not None else B
         if ref.shape[0] not in (1, B, gb):
             raise ValueError(f"the ilvr reference must be (1 or {B}, 3, {H}, {W}), got {tuple(ref.shape)}")
-        if isinstance(stop, bool) or not isinstance(stop, int) or not 0 <= stop <= self.num_timesteps:
+        if not _is_int(stop) or not 0 <= stop <= self.num_timesteps:
             raise ValueError(f"the ilvr stop index must be an int in [0, {self.num_timesteps}], got {stop!r}")
         return ref, factor, stop
-
-    def _step(self, model, x, i, cond_fn, model_kwargs, noise, mode, bufs, ahead=None, eta=0.0, masked=None, again=False):
-        """One step of the p_sample (mode 0) or DDIM (mode 1) loop.  DDIM with eta > 0 runs its update through
-        cgd_multistep_update (phase 3); eta == 0 keeps cgd_sample_update mode 1.  `masked`: the state of masked sampling, the update is
-        followed by the merge; `again`: this step index runs once more, the merge also leaves the re-noised state in bufs['_x_re']."""
-        ctx, lib = self.ctx, self.ctx.lib
-        B, _, H, W = x.shape
-        n_known, draw_known = self._known_noise(masked, x, i)
-        ev = self._evaluate(model, x, i, cond_fn, model_kwargs, noise, bufs, ahead, draw_known=draw_known)
-        noise, g, coef = ev["noise"], ev["g"], ev["coef"]
-        sample, x0_out = th.empty_like(x), th.empty_like(x)
-        if eta:
-            ab, abp = float(self.tables.alphas_cumprod[i]), float(self.tables.alphas_cumprod_prev[i])
-            sigma = eta * math.sqrt((1 - abp) / (1 - ab)) * math.sqrt(1 - ab / abp)
-            m = L.Multistep(3, 0, sigma, math.sqrt(max(0.0, 1 - abp - sigma * sigma)))
-            ctx.check(lib.cgd_multistep_update(ctx.h, x.data_ptr(), None, ev["x0"].data_ptr(), L.ptr(g), L.ptr(ev["scal"]),
-                                               noise.data_ptr(), None, None, sample.data_ptr(), x0_out.data_ptr(), B, H, W, coef, None,
-                                               m, ctx.stream()))
-        else:
-            ctx.check(lib.cgd_sample_update(ctx.h, x.data_ptr(), ev["x0"].data_ptr(), ev["mean"].data_ptr(), ev["logvar"].data_ptr(),
-                                            L.ptr(g), noise.data_ptr(), L.ptr(ev["scal"]), sample.data_ptr(), x0_out.data_ptr(), B, H,
-                                            W, coef, mode, ctx.stream()))
-        bufs["_keep"] = (noise, g, ev["ts"])
-        if masked is not None:
-            bufs["_x_re"] = self._masked_end(masked, ev, i, sample, x0_out, n_known, again)
-        return {"sample": sample, "pred_xstart": x0_out}
-
-    def _plms_step(self, model, x, i, cond_fn, model_kwargs, bufs, st, masked=None):
-        """One PLMS step (plms_sample of the guided_diffusion fork).  `st`: {'order', 'old_eps': history buffers (oldest first),
-        'free': spare buffers}.  The history rotates by pointer: the buffer dropped from the front is the next step's eps_out.
-        `masked`: the start step's predictor (level i - 1, the input of the second evaluation) is merged before that evaluation, and
-        every step's result afterwards; the eps history stays as evaluated."""
-        ctx, lib = self.ctx, self.ctx.lib
-        B, _, H, W = x.shape
-        s = ctx.stream()
-        order, old = st["order"], st["old_eps"]
-        eps_new = st["free"].pop() if st["free"] else th.empty_like(x)
-        sample, x0_out = th.empty_like(x), th.empty_like(x)
-        n_known, _ = self._known_noise(masked, x, i)  # never stochastic: the loop's initial noise
-        ev = self._evaluate(model, x, i, cond_fn, model_kwargs, None, bufs, draw_noise=False)
-        g = ev["g"]
-        if order > 1 and not old:
-            # start step, pseudo improved Euler: predictor at t, a second guided evaluation at (predictor, t-1), corrector
-            xp = bufs.get("_plms_xp")
-            if xp is None or xp.shape != x.shape or xp.device != x.device:
-                xp = bufs["_plms_xp"] = th.empty_like(x)
-            ctx.check(lib.cgd_multistep_update(ctx.h, x.data_ptr(), None, ev["x0"].data_ptr(), L.ptr(g), L.ptr(ev["scal"]), None, None,
-                                               eps_new.data_ptr(), xp.data_ptr(), x0_out.data_ptr(), B, H, W, ev["coef"], None,
-                                               L.Multistep(1, 0, 0.0, 0.0), s))
-            old.append(eps_new)
-            self._masked_end(masked, ev, i, xp, None, n_known)
-            ev2 = self._evaluate(model, xp, i - 1, cond_fn, model_kwargs, None, bufs, draw_noise=False)
-            hist = (C.c_void_p * 3)(eps_new.data_ptr(), None, None)
-            k_t = self.tables.step_coef(i, ev["fac_index"])
-            ctx.check(lib.cgd_multistep_update(ctx.h, x.data_ptr(), xp.data_ptr(), ev2["x0"].data_ptr(), L.ptr(ev2["g"]),
-                                               L.ptr(ev2["scal"]), None, hist, None, sample.data_ptr(), None, B, H, W, ev2["coef"], k_t,
-                                               L.Multistep(2, 0, 0.0, 0.0), s))
-            keep = (g, ev2["g"], ev["ts"], ev2["ts"], xp)
-        else:
-            # Adams-Bashforth of min(order, history + 1) terms, the newest history entry first
-            k = min(order, len(old) + 1)
-            prev = [old[-1 - j].data_ptr() if j < len(old) else None for j in range(3)]
-            ctx.check(lib.cgd_multistep_update(ctx.h, x.data_ptr(), None, ev["x0"].data_ptr(), L.ptr(g), L.ptr(ev["scal"]), None,
-                                               (C.c_void_p * 3)(*prev), eps_new.data_ptr(), sample.data_ptr(), x0_out.data_ptr(), B, H, W,
-                                               ev["coef"], None, L.Multistep(0, k, 0.0, 0.0), s))
-            old.append(eps_new)
-            keep = (g, ev["ts"])
-        if len(old) >= order:
-            st["free"].append(old.pop(0))
-        bufs["_keep"] = keep
-        self._masked_end(masked, ev, i, sample, x0_out, n_known)
-        return {"sample": sample, "pred_xstart": x0_out}
-
-    def _dpmpp_step(self, model, x, i, cond_fn, model_kwargs, noise, bufs, st, ahead=None, eta=0.0, masked=None, threshold=None):
-        """One DPM-Solver++(2M) step.  `st`: {'order', 'hist': the guided pred_xstart of the step before (None on the first step, which
-        therefore runs at order 1), 'free': the spare buffer}.  The history rotates by pointer: the entry the launch has read is the
-        buffer the next launch writes.  Step index 0 runs at order 1 (diffusion.dpmpp_coef) and nothing reads the entry of step
-        index 1 or 0, so those are not written.  `masked`: the result is merged after the update; the history stays as evaluated.
-        `threshold` (p, cap): dynamic thresholding of the guided pred_xstart (csrc/threshold.hip): cgd_dpmpp_threshold writes it to a buffer and
-        selects the sample's scale s on the device, cgd_dpmpp_update_thr clamps, rescales and updates; the history then holds the thresholded
-        predictions.  The buffer, the (B, 3) result and the selection's scratch live in `bufs`, allocated once per loop."""
-        ctx, lib = self.ctx, self.ctx.lib
-        B, _, H, W = x.shape
-        n_known, draw_known = self._known_noise(masked, x, i)
-        ev = self._evaluate(model, x, i, cond_fn, model_kwargs, noise, bufs, ahead, draw_noise=bool(eta), draw_known=draw_known)
-        noise, g, hist = ev["noise"], ev["g"], st["hist"]
-        d = self.tables.dpmpp_coef(i, 2 if (st["order"] == 2 and hist is not None) else 1, eta)
-        x0c = None
-        if st["order"] == 2 and i > 1:
-            x0c = st["free"].pop() if st["free"] else th.empty_like(x)
-        sample, x0_out = th.empty_like(x), th.empty_like(x)
-        if threshold is not None:
-            p, cap = threshold
-            if "_thr" not in bufs:
-                n = 3 * H * W
-                # cap == 1: every scale is 1 (the static clip), nothing is selected and no scratch is needed
-                scratch = th.empty(int(lib.cgd_abs_quantile_scratch_bytes(B, n)), dtype=th.uint8, device=x.device) if cap > 1.0 else None
-                bufs["_thr"] = (th.empty_like(x), th.empty((B, 3), dtype=th.float32, device=x.device), scratch, self.tables.threshold_rank(p, n))
-            raw, thr3, scratch, (rank, frac) = bufs["_thr"]
-            ctx.check(lib.cgd_dpmpp_threshold(ctx.h, x.data_ptr(), ev["x0"].data_ptr(), L.ptr(g), L.ptr(ev["scal"]), raw.data_ptr(), B, H, W,
-                                              ev["coef"], rank, frac, 1.0, cap, thr3.data_ptr(), L.ptr(scratch), ctx.stream()))
-            ctx.check(lib.cgd_dpmpp_update_thr(ctx.h, x.data_ptr(), ev["x0"].data_ptr(), raw.data_ptr(), thr3.data_ptr(), L.ptr(noise),
-                                               L.ptr(hist) if d.c_r else None, L.ptr(x0c), sample.data_ptr(), x0_out.data_ptr(), B, H, W,
-                                               ev["coef"], d, ctx.stream()))
-        else:
-            ctx.check(lib.cgd_dpmpp_update(ctx.h, x.data_ptr(), ev["x0"].data_ptr(), L.ptr(g), L.ptr(ev["scal"]), L.ptr(noise),
-                                           L.ptr(hist) if d.c_r else None, L.ptr(x0c), sample.data_ptr(), x0_out.data_ptr(), B, H, W,
-                                           ev["coef"], d, ctx.stream()))
-        if hist is not None:
-            st["free"].append(hist)
-        st["hist"] = x0c
-        bufs["_keep"] = (noise, g, ev["ts"])
-        self._masked_end(masked, ev, i, sample, x0_out, n_known)
-        return {"sample": sample, "pred_xstart": x0_out}
 
     # ---- loops ------------------------------------------------------------------------------------------
     @staticmethod
@@ -436,14 +465,10 @@ class GuidedSampler:
         if cond_fn is not None and not cond_fn_with_grad:
             raise NotImplementedError("the reference passes cond_fn_with_grad=True (cgd.py:260)")
 
-    def _loop(self, mode, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-              randomize_class, cond_fn_with_grad, eta=0.0, plms_order=None, mask=None, resamples=1, dpm_order=None, threshold=None,
-              ilvr=None):
-        """mode 0 p_sample, 1 DDIM (eta > 0: stochastic DDIM), 2 PLMS of order `plms_order` (no per-step noise), 3 DPM-Solver++(2M) of
-        order `dpm_order` (eta > 0: the SDE solver, with a per-step noise; `threshold` (p, cap): dynamic thresholding).  `mask` (with `init_image`): masked sampling, every step
-        index > 0 `resamples` times.  `ilvr` (ref, factor, stop), checked by _check_ilvr: every update of a step index >= stop is followed by
-        the low-frequency refinement."""
-        self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
+    def _loop(self, stepper, model, shape, *, noise, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image, randomize_class,
+              mask=None, resamples=1, ilvr=None):
+        """The loop of every sampler; `stepper` is its update rule (_Ancestral, _Plms, _Dpmpp).  The arguments arrive checked by the public
+        loops, `ilvr` as the (ref, factor, stop) of _check_ilvr."""
         device = th.device(device or f"cuda:{self.ctx.device}")
         tape = self.tape
         if noise is not None:
@@ -458,88 +483,57 @@ class GuidedSampler:
             img = th.randn(*shape, device=device)
         if skip_timesteps and init_image is None:
             init_image = th.zeros_like(img)
-        masked = None
-        if mask is not None:
-            # 'stochastic': the kept region gets a fresh noise per merge; otherwise it keeps the loop's initial noise, img as it is here
-            masked = {"init": init_image.to(device).float().contiguous(), "mask": mask.to(device).float().contiguous(),
-                      "x_T": img.contiguous(), "stochastic": mode == 0 or (mode in (1, 3) and bool(eta)), "known": 0, "re": 0}
+        # a rewrite's x_T is img as it is here: in a loop that is not stochastic its image keeps the loop's initial noise
+        rewrite = _Mask(self, img, stepper.stochastic, init_image, mask) if mask is not None else None
         if ilvr is not None:
-            # the masked merge's state with the reference in the init image's place; the scratch of the two launches lives as long as the loop
-            ref, factor, stop = ilvr
-            if self.shard is not None and ref.shape[0] == self.shard[1] and ref.shape[0] != 1:
-                ref = ref[self.shard[0]]  # a reference of the global batch: this rank's rows
-            B, _, H, W = img.shape
-            masked = {"ilvr": (ref.to(device).float().contiguous(), factor, stop), "x_T": img.contiguous(),
-                      "stochastic": mode == 0 or (mode in (1, 3) and bool(eta)), "known": 0,
-                      "scratch": th.empty(int(self.ctx.lib.cgd_ilvr_scratch_floats(B, H, W, factor, 1)), device=device, dtype=th.float32)}
+            rewrite = _Ilvr(self, img, stepper.stochastic, *ilvr)
         indices = list(range(self.num_timesteps - skip_timesteps))[::-1]
         if init_image is not None:
-            t0 = indices[0]
-            img = float(self.tables.sqrt_alphas_cumprod[t0]) * init_image.to(device).float() + \
-                float(self.tables.sqrt_one_minus_alphas_cumprod[t0]) * img
+            img = float(self.tables.sqrt_alphas_cumprod[indices[0]]) * init_image.to(device).float() + \
+                float(self.tables.sqrt_one_minus_alphas_cumprod[indices[0]]) * img
         model_kwargs = dict(model_kwargs or {})
         self._set_low_res(model, model_kwargs)
         it = indices
         if progress:
             from tqdm.auto import tqdm
             it = tqdm(indices)
-        bufs = {}
         img = img.contiguous()
+        run = _Run(self, model, cond_fn, model_kwargs, img, rewrite)
 
-        def draw_y():
-            """this step's class labels under `randomize_class` — same draws, in the same order of the generator, as the reference loop"""
+        def draw_y(n):
+            """step n's class labels under `randomize_class` — same draws, in the same order of the generator, as the reference loop"""
             if tape is not None:
-                return tape["y"][draw_y.n].to(device)
+                return tape["y"][n].to(device)
             if self.shard is not None:
                 return th.randint(0, model.num_classes, (self.shard[1],), device=device)[self.shard[0]]
             return th.randint(0, model.num_classes, model_kwargs["y"].shape, device=device)
 
-        draw_y.n = 0
         rand_y = bool(randomize_class and "y" in model_kwargs)
-        # PLMS: its start step evaluates the model twice, EmbedAhead's one-embedding-per-step choreography does not apply (off);
-        # neither does it to the repeated evaluations of resamples > 1
-        ahead = EmbedAhead.create(self, model, cond_fn, img, indices) if (mode != 2 and resamples == 1) else None
-        # The step of this loop, chosen once.  `st`: the multistep history of PLMS / DPM-Solver++.  `tape_noise`: whether an evaluation
-        # consumes the replay tape's next step noise (where a step noise is drawn at all).  `ahead` is read at call time: the loop may drop it.
-        tape_noise = mode in (0, 1) or (mode == 3 and bool(eta))
-        if mode == 2:
-            st = {"order": plms_order, "old_eps": [], "free": []}
-            def step(x, i, noise, again):  # noqa: E306
-                return self._plms_step(model, x, i, cond_fn, model_kwargs, bufs, st, masked=masked)
-        elif mode == 3:
-            st = {"order": dpm_order, "hist": None, "free": []}
-            def step(x, i, noise, again):  # noqa: E306
-                return self._dpmpp_step(model, x, i, cond_fn, model_kwargs, noise, bufs, st, ahead=ahead, eta=eta, masked=masked,
-                                        threshold=threshold)
-        else:
-            def step(x, i, noise, again):
-                return self._step(model, x, i, cond_fn, model_kwargs, noise, mode, bufs, ahead=ahead, eta=eta, masked=masked, again=again)
+        # EmbedAhead's one-embedding-per-step choreography applies neither to PLMS, whose start step evaluates the model twice, nor to
+        # the repeated evaluations of resamples > 1
+        ahead = run.ahead = EmbedAhead.create(self, model, cond_fn, img, indices) if (stepper.one_evaluation and resamples == 1) else None
         evals = 0  # evaluations so far: the tape's step noise is consumed per evaluation
         for n, i in enumerate(it):
             if rand_y and (ahead is None or n == 0):
-                draw_y.n = n
-                model_kwargs["y"] = draw_y()
+                model_kwargs["y"] = draw_y(n)
             if ahead is not None and n == 0:
                 ahead.launch(model, 0, model_kwargs.get("y"))
             # masked sampling with resamples = r: step index i > 0 runs r times; after each of the first r - 1 merges the state goes back
-            # up one level (bufs['_x_re'], written by the merge's launch) and the step runs again.  One yield per step index.
-            repeats = resamples if (masked is not None and i > 0) else 1
+            # up one level (written by the merge's launch, returned by the step) and the step runs again.  One yield per step index.
+            repeats = resamples if (rewrite is not None and i > 0) else 1
             for r in range(repeats):
-                step_noise = tape["noise"][evals].to(device).float().contiguous() if (tape is not None and tape_noise) else None
+                step_noise = tape["noise"][evals].to(device).float().contiguous() if (tape is not None and stepper.draws_noise) else None
                 evals += 1
                 with th.no_grad():
-                    out = step(img, i, step_noise, r + 1 < repeats)
-                if r + 1 < repeats:
-                    img = bufs.pop("_x_re")
+                    out, img = stepper.step(run, img, i, step_noise, r + 1 < repeats)  # img: the re-noised state while the index repeats
             if ahead is not None and tape is not None and rand_y and n + 1 >= len(tape["y"]):
-                ahead = None  # a replay tape shorter than the schedule (tests that run a few steps): the remaining steps run in line
+                ahead = run.ahead = None  # a replay tape shorter than the schedule (tests that run a few steps): the remaining steps run in line
             if ahead is not None and n + 1 < len(indices):
                 # step n is enqueued: now (host order = the reference's order of random draws: after this step's noise) draw the next step's
                 # labels and run its embedding head on the side stream, where it overlaps this step's kernels
                 with ahead.side_stream():
                     if rand_y:
-                        draw_y.n = n + 1
-                        model_kwargs["y"] = draw_y()
+                        model_kwargs["y"] = draw_y(n + 1)
                     ahead.launch(model, n + 1, model_kwargs.get("y"))
             yield out
             img = out["sample"]
@@ -555,8 +549,10 @@ class GuidedSampler:
         refinement.  Not together with `mask` or `resamples` > 1."""
         ilvr = self._check_ilvr(shape, ilvr, mask, resamples)
         self._check_mask(shape, init_image, mask, resamples)
-        return self._loop(0, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad, mask=mask, resamples=resamples, ilvr=ilvr)
+        self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
+        return self._loop(_Ancestral(), model, shape, noise=noise, cond_fn=cond_fn, model_kwargs=model_kwargs, device=device, progress=progress,
+                          skip_timesteps=skip_timesteps, init_image=init_image, randomize_class=randomize_class, mask=mask, resamples=resamples,
+                          ilvr=ilvr)
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, eta=0.0, skip_timesteps=0, init_image=None,
@@ -570,8 +566,10 @@ class GuidedSampler:
             raise ValueError(f"eta must be >= 0, got {eta}")
         ilvr = self._check_ilvr(shape, ilvr, mask, resamples)
         self._check_mask(shape, init_image, mask, resamples)
-        return self._loop(1, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad, eta=eta, mask=mask, resamples=resamples, ilvr=ilvr)
+        self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
+        return self._loop(_Ancestral(True, eta), model, shape, noise=noise, cond_fn=cond_fn, model_kwargs=model_kwargs, device=device,
+                          progress=progress, skip_timesteps=skip_timesteps, init_image=init_image, randomize_class=randomize_class, mask=mask,
+                          resamples=resamples, ilvr=ilvr)
 
     def plms_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                      model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
@@ -583,15 +581,15 @@ class GuidedSampler:
         noised with the loop's initial noise; `resamples` > 1 is refused (the eps history would mix noise levels).  `ilvr`: as in
         ddim_sample_loop_progressive with eta == 0; the start step's predictor is refined before its second evaluation, the eps history
         stays as evaluated."""
-        if isinstance(order, bool) or not isinstance(order, int) or not 1 <= order <= 4:
+        if not _is_int(order) or not 1 <= order <= 4:
             raise ValueError(f"order is invalid (should be int from 1-4): {order!r}")
         self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
         if order > 1 and self.num_timesteps - skip_timesteps < 2:
             raise ValueError(f"PLMS of order {order} needs at least two timesteps: its first step also evaluates at t - 1")
         ilvr = self._check_ilvr(shape, ilvr, mask, resamples)
         self._check_mask(shape, init_image, mask, resamples, plms=True)
-        return self._loop(2, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad, plms_order=order, mask=mask, ilvr=ilvr)
+        return self._loop(_Plms(order), model, shape, noise=noise, cond_fn=cond_fn, model_kwargs=model_kwargs, device=device, progress=progress,
+                          skip_timesteps=skip_timesteps, init_image=init_image, randomize_class=randomize_class, mask=mask, ilvr=ilvr)
 
     def dpmpp_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                                       model_kwargs=None, device=None, progress=False, skip_timesteps=0, init_image=None,
@@ -610,19 +608,19 @@ class GuidedSampler:
         and lowered to at most `cap` (>= 1; none when not given); the prediction is clamped to [-s, s] and divided by s before the update, and
         the history holds the thresholded predictions.  cap = 1 is the static clip of the guided prediction to [-1, 1].  With order 1 this
         is thresholded DDIM.  The yielded pred_xstart stays the unguided prediction."""
-        if isinstance(order, bool) or not isinstance(order, int) or order not in (1, 2):
+        if not _is_int(order) or order not in (1, 2):
             raise ValueError(f"order is invalid (should be 1 or 2): {order!r}")
         if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not eta >= 0.0:
             raise ValueError(f"eta must be a number >= 0, got {eta!r}")
         self._check_guards(clip_denoised, cond_fn, cond_fn_with_grad)
-        if isinstance(resamples, int) and not isinstance(resamples, bool) and resamples > 1:
+        if _is_int(resamples) and resamples > 1:
             raise ValueError("DPM-Solver++ cannot resample: its pred_xstart history would mix noise levels (use the DDIM loop, "
                              "ddim_sample_loop_progressive, for resamples > 1)")
         ilvr = self._check_ilvr(shape, ilvr, mask, resamples)
         self._check_mask(shape, init_image, mask, resamples)
-        threshold = self._check_threshold(threshold)
-        return self._loop(3, model, shape, noise, clip_denoised, cond_fn, model_kwargs, device, progress, skip_timesteps, init_image,
-                          randomize_class, cond_fn_with_grad, eta=float(eta), mask=mask, dpm_order=order, threshold=threshold, ilvr=ilvr)
+        return self._loop(_Dpmpp(order, float(eta), self._check_threshold(threshold)), model, shape, noise=noise, cond_fn=cond_fn,
+                          model_kwargs=model_kwargs, device=device, progress=progress, skip_timesteps=skip_timesteps, init_image=init_image,
+                          randomize_class=randomize_class, mask=mask, ilvr=ilvr)
 
     @staticmethod
     def _check_threshold(threshold):
@@ -654,7 +652,7 @@ class GuidedSampler:
         if clip_denoised:
             raise NotImplementedError("DDIM inversion runs with clip_denoised=False: clamping pred_xstart breaks the ODE the sampling loops "
                                       "run back down (the reference samples with clip_denoised=False, cgd.py:253)")
-        if isinstance(skip_timesteps, bool) or not isinstance(skip_timesteps, int) or skip_timesteps < 0:
+        if not _is_int(skip_timesteps) or skip_timesteps < 0:
             raise ValueError(f"skip_timesteps must be an int >= 0, got {skip_timesteps!r}")
         t0 = self.num_timesteps - 1 - skip_timesteps
         if t0 < 1:
@@ -669,8 +667,7 @@ class GuidedSampler:
         init = image.to(device).float().contiguous()
         B, _, H, W = init.shape
         self._set_low_res(model, model_kwargs)
-        tt = th.tensor([float(self.tables.model_timestep(k)) for k in range(t0)], dtype=th.float32,
-                       device=device).view(-1, 1).repeat(1, B).contiguous()
+        tt = _timestep_table(self.tables, t0, B, device)
         y = model_kwargs.get("y")
         out6 = th.empty((B, 6, H, W), device=device, dtype=th.float32)
         it = range(t0)

@@ -149,11 +149,11 @@ def test_sampler_sharded_draws_are_rows_of_the_global_draws(monkeypatch):
         smp.shard = shard
         seen = []
 
-        def fake_step(model, x, i, cond_fn, model_kwargs, noise, mode, bufs, **kw):
-            seen.append((x.clone(), smp._draw_like(x), model_kwargs["y"].clone()))
-            return {"sample": x * 0.5, "pred_xstart": x}
+        def fake_step(stepper, run, x, i, noise, again):
+            seen.append((x.clone(), smp._draw_like(x), run.model_kwargs["y"].clone()))
+            return {"sample": x * 0.5, "pred_xstart": x}, None
 
-        smp._step = fake_step
+        monkeypatch.setattr(sampler._Ancestral, "step", fake_step)
         th.manual_seed(11)
         model = types.SimpleNamespace(num_classes=1000)
         gen = smp.p_sample_loop_progressive(model, (nb, 3, 4, 4), clip_denoised=False, cond_fn=None, model_kwargs={"y": th.zeros(nb, dtype=th.long)},

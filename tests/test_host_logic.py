@@ -385,15 +385,15 @@ def test_device_sampler_loop_prologue_matches_the_oracle(monkeypatch, skip, with
     init = th.rand(shape, generator=th.Generator().manual_seed(1)) * 2 - 1 if with_init else None
     seen_dev, seen_ora = [], []
 
-    def dev_step(model_, x, i, cond_fn, model_kwargs, noise, mode, bufs, ahead=None, **kw):
-        seen_dev.append((i, x.clone(), model_kwargs["y"].clone()))
-        return {"sample": x * 0.5 + i, "pred_xstart": x}
+    def dev_step(stepper, run, x, i, noise, again):
+        seen_dev.append((i, x.clone(), run.model_kwargs["y"].clone()))
+        return {"sample": x * 0.5 + i, "pred_xstart": x}, None
 
     def ora_step(model_, x, t, clip_denoised=True, cond_fn=None, model_kwargs=None, noise=None):
         seen_ora.append((int(t[0]), x.clone(), model_kwargs["y"].clone()))
         return {"sample": x * 0.5 + int(t[0]), "pred_xstart": x}
 
-    monkeypatch.setattr(smp, "_step", dev_step)
+    monkeypatch.setattr(sampler._Ancestral, "step", dev_step)
     monkeypatch.setattr(o_diff, "p_sample_with_grad", ora_step)
     kw = dict(clip_denoised=False, cond_fn=None, model_kwargs={"y": th.zeros(2, dtype=th.long)}, device="cpu", skip_timesteps=skip,
               init_image=init, randomize_class=True, cond_fn_with_grad=True)
@@ -491,8 +491,8 @@ def test_guidance_call_sequence_with_a_recording_library(monkeypatch):
 
 def test_native_step_orders_noise_draw_before_guidance(monkeypatch):
     """p_sample_with_grad draws `noise = randn_like(x)` BEFORE it calls cond_fn, so the step noise precedes the
-    cutout-coordinate draws in the global RNG stream; `GuidedSampler._step` (native ClipGuidance path) must keep that order and issue
-    model.forward -> cgd_pmv_blend -> guidance -> cgd_sample_update.  Recording fakes, CPU tensors."""
+    cutout-coordinate draws in the global RNG stream; the p_sample step (`sampler._Ancestral.step`, native ClipGuidance path) must keep
+    that order and issue model.forward -> cgd_pmv_blend -> guidance -> cgd_sample_update.  Recording fakes, CPU tensors."""
     import types
     from cgd_amd import sampler
     monkeypatch.setattr(sampler.L, "stream_ptr", lambda: 0)
@@ -520,15 +520,16 @@ def test_native_step_orders_noise_draw_before_guidance(monkeypatch):
     model = types.SimpleNamespace(forward=lambda x, ts, y, out=None: calls.append("model.forward") or out)
     x = th.zeros(1, 3, 8, 8)
     th.manual_seed(5)
-    out = smp._step(model, x, 9, guid, {"y": th.zeros(1, dtype=th.long)}, None, 0, bufs := {})
+    run = sampler._Run(smp, model, guid, {"y": th.zeros(1, dtype=th.long)}, x)
+    out, _ = sampler._Ancestral().step(run, x, 9, None)
     th.manual_seed(5)
     expect_noise, expect_draw = th.randn_like(x), th.rand(1)
-    assert th.equal(bufs["_keep"][0], expect_noise) and th.equal(draws[0], expect_draw)
+    assert th.equal(run.keep[0], expect_noise) and th.equal(draws[0], expect_draw)
     assert calls == ["model.forward", "cgd_pmv_blend", "guidance.native", "cgd_sample_update"]
     assert set(out) == {"sample", "pred_xstart"} and out["sample"].shape == x.shape
     # a replayed tape supplies the noise: nothing is drawn for it
     th.manual_seed(5)
-    smp._step(model, x, 8, guid, {"y": th.zeros(1, dtype=th.long)}, th.full_like(x, 0.25), 0, bufs)
+    sampler._Ancestral().step(run, x, 8, th.full_like(x, 0.25))
     assert th.equal(draws[1], th.manual_seed(5) and th.rand(1))
 
 

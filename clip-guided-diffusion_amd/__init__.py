@@ -4,4 +4,4 @@
 The directory name carries a hyphen (`clip-guided-diffusion_amd`); import it as `cgd_amd` through the
 repo-root shim `cgd_amd.py`.
 """
-__all__ = ["lib", "ops", "nets", "diffusion", "guidance", "sampler", "windows"]
+__all__ = ["lib", "ops", "nets", "diffusion", "guidance", "sampler", "windows", "animate"]

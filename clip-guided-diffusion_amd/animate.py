@@ -1,0 +1,289 @@
+"""Keyframed 2D animation in the manner of Disco Diffusion's 2D mode and Deforum: frame k is sampled from frame k - 1 after zooming,
+rotating and shifting it and noising it part of the way up the schedule; an LPIPS term holds it to the warped frame, and the text prompts may
+change at keyframes.
+
+    python -m cgd_amd.animate --frames 120 --zoom "0:(1.02)" --angle "0:(0),60:(2)" --translation_x 0 --translation_y "0:(0),120:(-40)" \\
+        --border wrap --interp bicubic --frames_skip 0.6 --frames_scale 1500 --color_match 1 [--fixed_seed] \\
+        [--prompts_at "40=a city at night|a skyline:0.5"]... -- <cgd command-line flags>
+
+or, from Python, `animate(frames, zoom=..., **clip_guided_diffusion_kwargs)`, a generator of `(frame_idx, batch_idx, png_path)`.
+
+Networks, cutout maker, tables and guidance are built once (cgd.cgd.prepare_run) and every frame runs the sampler loop on them.  Between two
+frames the state stays fp32 on the GPU: the final `sample` of frame k - 1 goes through cgd_frame_warp (one launch, csrc/warp.hip) and, with
+`color_match`, through cgd_color_match against frame 0's channel statistics; nothing passes through a file or through 8 bits.
+
+Conventions (motion_matrix).  The forward map of a frame is p' = t + c + z R(theta) (p - c) with
+  c = ((W - 1) / 2, (H - 1) / 2), the geometric centre of the pixel grid (pixel centres sit on integers).  Disco Diffusion and OpenCV recipes
+      use (W // 2, H // 2), which on even sizes lies half a pixel to the lower right: a pure zoom or rotation there drifts by up to half a
+      pixel per frame toward the upper left, and a 180 degree turn is no permutation of the pixels.  Here it is;
+  R(theta) = [[cos, sin], [-sin, cos]], OpenCV's getRotationMatrix2D convention: a positive angle (degrees) turns the picture
+      counter-clockwise on the screen (y points down);
+  t = (translation_x, translation_y): positive values move the content right and down;
+  z = zoom: above 1 magnifies.
+The kernel takes the inverse map, which is what motion_matrix returns.
+"""
+import argparse
+import math
+import re
+import sys
+
+BORDERS = ("wrap", "reflect", "replicate")
+INTERPS = ("bilinear", "bicubic")
+
+_KEY = re.compile(r"^\s*([^:\s]+)\s*:\s*\(\s*([^()\s]+)\s*\)\s*$")
+
+
+def _number(text, what):
+    try:
+        value = float(text)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: {text!r} is not a number") from None
+    if not math.isfinite(value):
+        raise ValueError(f"{what}: {text!r} is not finite")
+    return value
+
+
+def keyframes(spec, frames):
+    """Disco's keyframe syntax '0:(1.0), 30:(1.04), 90:(1.0)' (or a bare number) -> one float per frame: linear between keys, the first
+    value before the first key, the last value after the last key.  ValueError on malformed text, a repeated key, or a key frame that is
+    negative or no integer."""
+    frames = int(frames)
+    if frames < 1:
+        raise ValueError(f"frames must be at least 1, got {frames}")
+    if isinstance(spec, bool):
+        raise ValueError(f"keyframes: {spec!r} is not a number")
+    if isinstance(spec, (int, float)):
+        return [_number(spec, "keyframes")] * frames
+    text = str(spec).strip()
+    if not text:
+        raise ValueError("keyframes: empty")
+    if ":" not in text and "(" not in text and "," not in text:
+        return [_number(text, "keyframes")] * frames
+    keys = {}
+    for item in text.split(","):
+        m = _KEY.match(item)
+        if m is None:
+            raise ValueError(f"keyframes {spec!r}: {item.strip()!r} is not 'FRAME:(VALUE)'")
+        if not re.fullmatch(r"\+?\d+", m.group(1)):
+            raise ValueError(f"keyframes {spec!r}: the frame {m.group(1)!r} must be a non-negative integer")
+        frame = int(m.group(1))
+        if frame in keys:
+            raise ValueError(f"keyframes {spec!r}: frame {frame} is given twice")
+        keys[frame] = _number(m.group(2), f"keyframes {spec!r}")
+    at = sorted(keys)
+    out = []
+    for k in range(frames):
+        if k <= at[0]:
+            out.append(keys[at[0]])
+        elif k >= at[-1]:
+            out.append(keys[at[-1]])
+        else:
+            hi = next(i for i, f in enumerate(at) if f >= k)
+            f0, f1 = at[hi - 1], at[hi]
+            u = (k - f0) / (f1 - f0)
+            out.append(keys[f1] if k == f1 else keys[f0] + (keys[f1] - keys[f0]) * u)
+    return out
+
+
+def motion_matrix(zoom, angle_deg, tx, ty, H, W):
+    """The six float64 entries (m0 .. m5) of the INVERSE map of p' = t + c + zoom R(angle) (p - c) (module docstring): destination pixel
+    (x, y) reads the source at (m0 x + m1 y + m2, m3 x + m4 y + m5)."""
+    zoom, angle_deg, tx, ty = (_number(v, n) for v, n in ((zoom, "zoom"), (angle_deg, "angle"), (tx, "translation_x"), (ty, "translation_y")))
+    if not zoom > 0:
+        raise ValueError(f"zoom must be positive, got {zoom}")
+    if H < 1 or W < 1:
+        raise ValueError(f"the frame must be at least 1 x 1, got {H} x {W}")
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+    a = math.radians(angle_deg)
+    cos, sin = math.cos(a), math.sin(a)
+    # p = c + R^T (p' - t - c) / zoom,  R^T = [[cos, -sin], [sin, cos]]
+    ux, uy = tx + cx, ty + cy
+    return (cos / zoom, -sin / zoom, cx - (cos * ux - sin * uy) / zoom,
+            sin / zoom, cos / zoom, cy - (sin * ux + cos * uy) / zoom)
+
+
+def forward_matrix(zoom, angle_deg, tx, ty, H, W):
+    """The forward map itself, in the same row layout (for tests and for drawing motion paths)."""
+    cx, cy = (W - 1) / 2.0, (H - 1) / 2.0
+    a = math.radians(angle_deg)
+    cos, sin = math.cos(a) * zoom, math.sin(a) * zoom
+    return (cos, sin, tx + cx - (cos * cx + sin * cy), -sin, cos, ty + cy - (-sin * cx + cos * cy))
+
+
+def parse_prompts_at(values):
+    """CLI '--prompts_at "40=a city at night|a skyline:0.5"' entries -> {40: ['a city at night', 'a skyline:0.5']}."""
+    out = {}
+    for value in values or []:
+        frame, sep, text = str(value).partition("=")
+        if not sep or not re.fullmatch(r"\s*\d+\s*", frame) or not text.strip():
+            raise ValueError(f"prompts_at {value!r}: expected 'FRAME=prompt|prompt...'")
+        if int(frame) in out:
+            raise ValueError(f"prompts_at: frame {int(frame)} is given twice")
+        out[int(frame)] = text.split("|")
+    return out
+
+
+def _check(frames, border, interp, frames_skip, frames_scale, color_match, prompts_at, kw):
+    """Every refusal of animate that needs nothing loaded -> (frames, prompts_at as {int: [str]})."""
+    from cgd import script_util
+    from cgd_amd import diffusion as dd
+    from cgd_amd import shard
+    if isinstance(frames, bool) or int(frames) != frames or frames < 1:
+        raise ValueError(f"frames must be an integer of at least 1, got {frames!r}")
+    frames = int(frames)
+    if border not in BORDERS or interp not in INTERPS:
+        raise ValueError(f"border must be one of {BORDERS} and interp one of {INTERPS}, got {border!r} and {interp!r}")
+    if not (0 <= frames_skip < 1):
+        raise ValueError(f"frames_skip must lie in [0, 1), got {frames_skip!r}")
+    if not (frames_scale >= 0):
+        raise ValueError(f"frames_scale must not be negative, got {frames_scale!r}")
+    if not (0 <= color_match <= 1):
+        raise ValueError(f"color_match must lie in [0, 1], got {color_match!r}")
+    if kw.get("use_augs"):
+        raise ValueError("animate does not work with use_augs")
+    if shard.world()[1] > 1:
+        raise ValueError("animate runs in one process: frames are sequential, a sharded run would leave the other GPUs idle")
+    init = kw.get("init_image")
+    if init:
+        image, mask = script_util.split_init_mask(init)
+        if mask is not None:
+            raise ValueError(f"init image {init!r}: animate takes a plain init image for frame 0, not '::MASK'")
+        for what, split in (("invert=", script_util.split_init_invert), ("upsample=", script_util.split_init_upsample),
+                            ("ilvrN=", script_util.split_init_ilvr)):
+            if split(image)[1]:
+                raise ValueError(f"init image {init!r}: animate takes a plain init image for frame 0, not '{what}'")
+    plan = {}
+    for frame, texts in (prompts_at or {}).items():
+        if isinstance(frame, bool) or int(frame) != frame or frame < 0:
+            raise ValueError(f"prompts_at: the frame {frame!r} must be a non-negative integer")
+        texts = [texts] if isinstance(texts, str) else list(texts)
+        if not texts:
+            raise ValueError(f"prompts_at[{frame}]: at least one prompt")
+        plan[int(frame)] = texts
+    every = list(kw.get("prompts") or []) + [t for texts in plan.values() for t in texts]
+    if any(script_util.split_direction(script_util.parse_prompt(p)[0]) is not None for p in every):
+        raise ValueError("animate does not take 'SOURCE=>TARGET' prompts: the source image would change every frame")
+    if plan:
+        if any(script_util.REGION_SEP in str(p) for p in every + list(kw.get("image_prompts") or [])):
+            raise ValueError("prompts_at does not work with 'TEXT@@REGION' prompts: the region plan is built once, over the first prompt list")
+        for frame, texts in plan.items():
+            if abs(sum(script_util.parse_prompt(t)[1] for t in texts) + 0.0) < 1e-3 and not kw.get("image_prompts"):
+                raise ValueError(f"prompts_at[{frame}]: the weights must not sum to 0")
+    # how many steps the run has, from the tables alone (the suffixes of the spacing are the generator's to judge)
+    spacing = script_util.split_threshold(script_util.split_windows(kw.get("timestep_respacing", "1000"))[0])[0]
+    steps = dd.create_gaussian_diffusion(kw.get("diffusion_steps", 1000), kw.get("noise_schedule", "linear"), spacing).num_timesteps
+    if frames > 1 and round(frames_skip * steps) >= steps:
+        raise ValueError(f"frames_skip {frames_skip} leaves no step of the {steps} for the frames after the first")
+    return frames, plan
+
+
+def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, border="wrap", interp="bicubic", frames_skip=0.6,
+            frames_scale=1500, color_match=0.0, fixed_seed=False, prompts_at=None, **cgd_kwargs):
+    """Generator of `(frame_idx, batch_idx, png_path)`: `frames` frames, each the last image of one sampling run, written to
+    prefix_path/<prompts>/<batch_idx:02>/<frame_idx:04>.png.
+
+    Frame 0 is an ordinary run of `cgd_kwargs` (cgd.cgd.clip_guided_diffusion's keywords; its own init_image / skip_timesteps / init_scale
+    apply).  Frame k > 0 starts from the final `sample` of frame k - 1 of each of the batch's samples (B independent chains, one motion):
+    warped by frame k's motion (`zoom`, `angle` in degrees, `translation_x`, `translation_y`: numbers or keyframe strings, see keyframes and
+    motion_matrix; `border` wrap / reflect / replicate, `interp` bilinear / bicubic) and clamped to [-1, 1], moved toward frame 0's channel
+    statistics by `color_match` in [0, 1], then used as the init image with skip_timesteps = round(frames_skip * num_timesteps) and the LPIPS
+    weight `frames_scale` (0: no LPIPS term, and the LPIPS network is not loaded).  th.manual_seed(seed + k) precedes frame k (`fixed_seed`:
+    seed itself).  `prompts_at` = {frame: [prompt strings]} replaces the text prompts from that frame on (image prompts stay; the weights are
+    normalised together as at the start); a text is encoded when first needed and kept.
+
+    Refused before anything is loaded (ValueError): an init_image with '::MASK', 'invert=', 'upsample=' or 'ilvrN=', 'SOURCE=>TARGET'
+    prompts, use_augs, a world size above 1, frames < 1, frames_skip outside [0, 1) or so high that no step is left, and prompts_at together
+    with region prompts.  Everything else in `cgd_kwargs` passes through: samplers, '+thr=', '+windows=', 'cuts=', regions, style,
+    secondary, classifier."""
+    import torch as th
+
+    from cgd import cgd as entry
+    from cgd import clip_util, script_util
+    from cgd_amd import ops
+    frames, plan = _check(frames, border, interp, frames_skip, frames_scale, color_match, prompts_at, cgd_kwargs)
+    tracks = [keyframes(spec, frames) for spec in (zoom, angle, translation_x, translation_y)]
+    if any(not z > 0 for z in tracks[0]):
+        raise ValueError("zoom must stay positive on every frame")
+    seed = cgd_kwargs.get("seed", 0)
+    run = entry.prepare_run(**cgd_kwargs, lpips_for_later=frames > 1 and frames_scale != 0)
+    if run is None:
+        return
+    cond_fn, ctx = run.cond_fn, run.model.ctx
+    _, _, H, W = run.shape
+    skip = int(round(frames_skip * run.diffusion.num_timesteps))
+    if frames > 1 and skip >= run.diffusion.num_timesteps:
+        raise ValueError(f"frames_skip {frames_skip} leaves no step of the {run.diffusion.num_timesteps} for the frames after the first")
+
+    def retarget(texts):
+        embeds, weights = [[] for _ in run.clip_names], []
+        for prompt in texts:
+            text, weight = script_util.parse_prompt(prompt)
+            for k, name in enumerate(run.clip_names):
+                if (text, name) not in run.text_cache:
+                    run.text_cache[(text, name)] = clip_util.encode_text_prompt(text, weight, name, run.device)[0]
+                embeds[k].append(run.text_cache[(text, name)])
+            weights.append(float(weight))
+        weights += [float(w) for w in run.image_weights]
+        w = th.tensor(weights)
+        if w.sum().abs() < 1e-3:
+            raise RuntimeError("The weights must not sum to 0.")
+        cond_fn.set_targets([th.cat(e + list(img)) for e, img in zip(embeds, run.image_embeds)], w / w.sum().abs())
+
+    previous = stats0 = None
+    for k in range(frames):
+        if k in plan:
+            retarget(plan[k])
+        init = None
+        if k > 0:
+            th.manual_seed(seed if fixed_seed else seed + k)
+            matrix = motion_matrix(tracks[0][k], tracks[1][k], tracks[2][k], tracks[3][k], H, W)
+            init = ops.frame_warp(ctx, previous, matrix, interp=interp, border=border, clamp=True)
+            if color_match > 0:
+                ops.color_match(ctx, init, stats0, amount=color_match, clamp=True)
+            cond_fn.set_init(init if frames_scale != 0 else None, frames_scale)
+        last = None
+        for last in (run.samples() if k == 0 else run.samples(init_image=init, skip_timesteps=skip)):
+            cond_fn.current_timestep -= 1
+        if last is None:
+            raise RuntimeError(f"frame {k}: the sampler loop made no step")
+        staged = script_util.stage_images(last["pred_xstart"])
+        previous = last["sample"].detach().clone()  # the loop's buffers are reused by the next frame
+        if k == 0 and color_match > 0 and frames > 1:
+            stats0 = ops.channel_stats(ctx, previous)
+        for batch_idx, path in run.write(staged.get().numpy(), k):
+            yield k, batch_idx, path
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--frames", type=int, required=True, help="number of frames")
+    for name, default, what in (("zoom", "1.0", "magnification per frame (above 1 zooms in)"),
+                                ("angle", "0", "degrees per frame, positive turns the picture counter-clockwise"),
+                                ("translation_x", "0", "pixels per frame, positive moves the content right"),
+                                ("translation_y", "0", "pixels per frame, positive moves the content down")):
+        p.add_argument(f"--{name}", default=default, help=f"{what}: a number or keyframes 'FRAME:(VALUE), ...'")
+    p.add_argument("--border", default="wrap", choices=BORDERS, help="what the warp reads outside the frame")
+    p.add_argument("--interp", default="bicubic", choices=INTERPS, help="interpolation of the warp")
+    p.add_argument("--frames_skip", type=float, default=0.6, help="fraction of the schedule the frames after the first skip")
+    p.add_argument("--frames_scale", type=float, default=1500, help="LPIPS weight toward the warped previous frame (0: no LPIPS)")
+    p.add_argument("--color_match", type=float, default=0.0, help="how far every frame's channel mean / std are moved to frame 0's, in [0, 1]")
+    p.add_argument("--fixed_seed", action="store_true", help="the same seed for every frame instead of seed + frame")
+    p.add_argument("--prompts_at", action="append", default=[], help="'FRAME=prompt|prompt...': the text prompts from FRAME on (repeatable)")
+    return p
+
+
+def main(argv=None):
+    from cgd import cgd as entry
+    argv = list(sys.argv[1:] if argv is None else argv)
+    own, rest = (argv[:argv.index("--")], argv[argv.index("--") + 1:]) if "--" in argv else (argv, [])
+    a = build_parser().parse_args(own)
+    kwargs = entry.kwargs_from_args(entry.build_parser().parse_args(rest))
+    kwargs.pop("save_frequency", None)  # one PNG per frame
+    for item in animate(a.frames, zoom=a.zoom, angle=a.angle, translation_x=a.translation_x, translation_y=a.translation_y, border=a.border,
+                        interp=a.interp, frames_skip=a.frames_skip, frames_scale=a.frames_scale, color_match=a.color_match,
+                        fixed_seed=a.fixed_seed, prompts_at=parse_prompts_at(a.prompts_at), **kwargs):
+        print("\t".join(str(v) for v in item))
+
+
+if __name__ == "__main__":
+    main()

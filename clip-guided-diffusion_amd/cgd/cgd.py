@@ -19,6 +19,89 @@ from cgd_amd.guidance import ClipGuidance
 from . import clip_util, script_util
 
 
+class GuidedRun:
+    """What `clip_guided_diffusion` builds between its argument checks and its sampling loop (prepare_run): the model, the diffusion, the
+    cond_fn, the sampler loop and its arguments, and the output helpers.  The generator runs `frames()` once; cgd_amd.animate builds one and
+    runs `samples()` once per animation frame on the same networks and guidance."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def samples(self, init_image=None, skip_timesteps=None, **loop_kw):
+        """The sampler loop's iterator over one run, the cond_fn's closure counter set as the reference sets it (cgd.py:265); the caller
+        lowers `cond_fn.current_timestep` by one per yielded step.  `init_image` / `skip_timesteps`: instead of the run's own (None)."""
+        samples = self.loop(self.model, self.shape, clip_denoised=False, model_kwargs=self.model_kwargs, cond_fn=self.cond_fn,
+                            progress=self.progress, skip_timesteps=self.skip_timesteps if skip_timesteps is None else skip_timesteps,
+                            init_image=self.init_tensor if init_image is None else init_image, randomize_class=self.randomize_class,
+                            cond_fn_with_grad=True, **{**self.loop_kw, **loop_kw})
+        self.cond_fn.current_timestep = self.diffusion.num_timesteps - 1
+        return samples
+
+    def write(self, arr, name_idx):
+        """(local batch, H, W, 3) uint8 -> one PNG per sample, '<prefix>/<prompts>/<batch_idx:02>/<name_idx:04>.png'; yields
+        (batch_idx, path), batch_idx the index in the GLOBAL batch."""
+        for local_idx, batch_idx in enumerate(self.mine):
+            yield batch_idx, script_util.write_image(arr[local_idx], self.prefix_path, self.prompts, name_idx, batch_idx)
+
+    def frames(self):
+        """The run: generator of `(batch_idx, png_path)`."""
+        cond_fn, wandb_run, progress, save_frequency = self.cond_fn, self.wandb_run, self.progress, self.save_frequency
+        try:
+            samples = self.samples()
+
+            # Output path (reference cgd.py:180-186,234-238,265-270), software-pipelined by one timestep: the GPU work of timestep
+            # k+1 is enqueued BEFORE the host looks at timestep k (loss scalars, uint8 frames), and those reads travel on a side
+            # stream (cgd_amd/hostcopy.py).  With the CLI default --save_frequency 1 the two PNG encodes per sample then overlap the
+            # next step on the GPU instead of idling it.  Yield order and file naming are unchanged.
+            def enqueue_steps():
+                for step, sample in enumerate(samples):
+                    cond_fn.current_timestep -= 1
+                    # a gated --reduce-clip step logs nothing (the reference's cond_fn returns before its logging, cgd.py:155-160)
+                    want_log = (progress or wandb_run is not None) and cond_fn.last_ran
+                    save = step % save_frequency == 0 or cond_fn.current_timestep == -1
+                    yield (step, cond_fn.snapshot() if want_log else None, script_util.stage_images(sample["pred_xstart"]) if save else None)
+
+            def finish(item):
+                step, snapshot, frames = item
+                if snapshot is not None:
+                    log = cond_fn.log(snapshot)
+                    if progress:
+                        tqdm.write("\t".join(f"{k}: {v:.3f}" for k, v in log.items() if "loss" in k.lower()))
+                    if wandb_run is not None:
+                        wandb_run.log(log)
+                if frames is not None:
+                    yield from self.write(frames.get().numpy(), step)
+
+            previous = None
+            pending = enqueue_steps()
+            while True:
+                try:
+                    item = next(pending)
+                except StopIteration:
+                    break
+                except (RuntimeError, KeyboardInterrupt):
+                    # enqueuing timestep k+1 failed (OOM, ^C): timestep k is complete, so its frames are still written and yielded
+                    # first, as the unpipelined reference would have done before starting k+1
+                    if previous is not None:
+                        item, previous = previous, None
+                        yield from finish(item)
+                    raise
+                if previous is not None:
+                    yield from finish(previous)
+                previous = item
+            if previous is not None:
+                yield from finish(previous)
+        except (RuntimeError, KeyboardInterrupt) as runtime_ex:
+            if "out of memory" in str(runtime_ex).lower():
+                # the reference's hint, kept word for word (cgd.py:274-283)
+                print("\n".join((
+                    "CUDA OOM error occurred.", "Try lowering --image_size/-size, --batch_size/-bs, --num_cutouts/-cutn",
+                    f"--clip_model/-clip (currently {self.clip_model_name}) can have a large impact on VRAM usage.",
+                    "'RN50' will use the least VRAM. 'ViT-B/32' the second least and is good for its memory/runtime constraints.")))
+            else:
+                raise runtime_ex
+
+
 def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prompts=[], clip_guidance_scale=1000, tv_scale=150,
                           range_scale=50, sat_scale=0, init_scale=0, batch_size=1, init_image=None, class_cond=True,
                           cutout_power=1.0, timestep_respacing="1000", seed=0, diffusion_steps=1000, skip_timesteps=0,
@@ -27,6 +110,21 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
                           wandb_project=None, wandb_entity=None, use_augs=False, use_magnitude=False, height_offset=0,
                           width_offset=0, progress=True, reduce_clip=False, progressive_cutout=False, cached_cutouts=False):
     """Generator of `(batch_idx, png_path)`; keyword names and defaults are the reference's (cgd.py:19-55)."""
+    run = prepare_run(**locals())
+    if run is not None:  # (None: a rank of a sharded run that has no sample)
+        yield from run.frames()
+
+
+def prepare_run(image_size=128, num_cutouts=16, prompts=[], image_prompts=[], clip_guidance_scale=1000, tv_scale=150,
+                range_scale=50, sat_scale=0, init_scale=0, batch_size=1, init_image=None, class_cond=True,
+                cutout_power=1.0, timestep_respacing="1000", seed=0, diffusion_steps=1000, skip_timesteps=0,
+                checkpoints_dir=script_util.CACHE_PATH, clip_model_name="ViT-B/32", randomize_class=True,
+                prefix_path=Path("./outputs"), save_frequency=25, noise_schedule="linear", dropout=0.0, device="",
+                wandb_project=None, wandb_entity=None, use_augs=False, use_magnitude=False, height_offset=0,
+                width_offset=0, progress=True, reduce_clip=False, progressive_cutout=False, cached_cutouts=False, lpips_for_later=False):
+    """`clip_guided_diffusion`'s arguments -> its GuidedRun (None on a rank of a sharded run that has no sample): every argument check, then
+    every load, then the guidance and the sampler loop; nothing is sampled.  `lpips_for_later`: load the LPIPS-VGG16 handle although this
+    run's own arguments need none (ClipGuidance.set_init may then switch the init-image term on)."""
     if len(device) == 0:
         device = "cuda" if th.cuda.is_available() else "cpu"
         print(f"device: {device} (picked automatically; --device/-dev overrides)")
@@ -113,6 +211,7 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
     # direction prompts: per tower normalize(E(target caption)) - normalize(E(source caption)); their places in the weight list, which holds
     # targets and directions alike in the order given
     dirs_per_tower, direction_columns = [[] for _ in clip_names], []
+    text_cache = {}  # (text, tower name) -> embedding, for GuidedRun
     for prompt, pair in zip(prompts, direction_pairs):
         text, weight = script_util.parse_prompt(prompt)
         for k, name in enumerate(clip_names):
@@ -122,10 +221,12 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
                 dirs_per_tower[k].append(th.nn.functional.normalize(e_tgt.float(), dim=-1) - th.nn.functional.normalize(e_src.float(), dim=-1))
                 continue
             embed, w_k = clip_util.encode_text_prompt(text, weight, name, device)
+            text_cache[(text, name)] = embed
             embeds_per_tower[k].append(embed)
         if pair is not None:
             direction_columns.append(len(weights))
         weights.append(w_k)
+    text_embeds, text_weights = len(embeds_per_tower[0]), len(weights)  # what comes behind belongs to the image prompts
     for image_prompt, region in zip(image_prompts, image_regions):
         img, weight = script_util.parse_prompt(image_prompt)
         for k, name in enumerate(clip_names):
@@ -254,7 +355,7 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         # "initialized lazily as it can use a bit of VRAM" (reference cgd.py:146-148): only with an init image and a non-zero scale
         # ... or with a style image, whose term runs on the same trunk
         lpips=script_util.load_lpips(gd_model.ctx, checkpoints_dir, device)
-        if ((init_tensor is not None and init_scale != 0) or style_tensor is not None) else None,
+        if ((init_tensor is not None and init_scale != 0) or style_tensor is not None or lpips_for_later) else None,
         init_tensor=init_tensor, init_scale=init_scale,
         **({} if style_tensor is None else {"style_tensor": style_tensor, "style_scale": style_spec[1]}),
         secondary=secondary,
@@ -278,66 +379,15 @@ def clip_guided_diffusion(image_size=128, num_cutouts=16, prompts=[], image_prom
         loop = functools.partial(loop, ilvr=(ilvr_tensor, ilvr_spec[0], script_util.ilvr_stop(ilvr_spec[1], diffusion.num_timesteps)))
     if threshold is not None:  # only with 'dpmN' / 'dpmsdeN' (split_threshold)
         loop = functools.partial(loop, threshold=threshold[0] if threshold[1] is None else threshold)
-    try:
-        samples = loop(gd_model, (local_batch, 3, image_size + height_offset, image_size + width_offset), clip_denoised=False,
-                       model_kwargs=model_kwargs, cond_fn=cond_fn, progress=progress, skip_timesteps=skip_timesteps, init_image=init_tensor,
-                       randomize_class=randomize_class, cond_fn_with_grad=True, **({} if mask_tensor is None else {"mask": mask_tensor}),
-                       **invert_kw)
-        cond_fn.current_timestep = diffusion.num_timesteps - 1
-
-        # Output path (reference cgd.py:180-186,234-238,265-270), software-pipelined by one timestep: the GPU work of timestep
-        # k+1 is enqueued BEFORE the host looks at timestep k (loss scalars, uint8 frames), and those reads travel on a side
-        # stream (cgd_amd/hostcopy.py).  With the CLI default --save_frequency 1 the two PNG encodes per sample then overlap the
-        # next step on the GPU instead of idling it.  Yield order and file naming are unchanged.
-        def enqueue_steps():
-            for step, sample in enumerate(samples):
-                cond_fn.current_timestep -= 1
-                # a gated --reduce-clip step logs nothing (the reference's cond_fn returns before its logging, cgd.py:155-160)
-                want_log = (progress or wandb_run is not None) and cond_fn.last_ran
-                save = step % save_frequency == 0 or cond_fn.current_timestep == -1
-                yield (step, cond_fn.snapshot() if want_log else None, script_util.stage_images(sample["pred_xstart"]) if save else None)
-
-        def finish(item):
-            step, snapshot, frames = item
-            if snapshot is not None:
-                log = cond_fn.log(snapshot)
-                if progress:
-                    tqdm.write("\t".join(f"{k}: {v:.3f}" for k, v in log.items() if "loss" in k.lower()))
-                if wandb_run is not None:
-                    wandb_run.log(log)
-            if frames is not None:
-                arr = frames.get().numpy()
-                for local_idx, batch_idx in enumerate(mine):  # batch_idx: index in the GLOBAL batch (output directory <idx:02>)
-                    yield batch_idx, script_util.write_image(arr[local_idx], prefix_path, prompts, step, batch_idx)
-
-        previous = None
-        pending = enqueue_steps()
-        while True:
-            try:
-                item = next(pending)
-            except StopIteration:
-                break
-            except (RuntimeError, KeyboardInterrupt):
-                # enqueuing timestep k+1 failed (OOM, ^C): timestep k is complete, so its frames are still written and yielded
-                # first, as the unpipelined reference would have done before starting k+1
-                if previous is not None:
-                    item, previous = previous, None
-                    yield from finish(item)
-                raise
-            if previous is not None:
-                yield from finish(previous)
-            previous = item
-        if previous is not None:
-            yield from finish(previous)
-    except (RuntimeError, KeyboardInterrupt) as runtime_ex:
-        if "out of memory" in str(runtime_ex).lower():
-            # the reference's hint, kept word for word (cgd.py:274-283)
-            print("\n".join((
-                "CUDA OOM error occurred.", "Try lowering --image_size/-size, --batch_size/-bs, --num_cutouts/-cutn",
-                f"--clip_model/-clip (currently {clip_model_name}) can have a large impact on VRAM usage.",
-                "'RN50' will use the least VRAM. 'ViT-B/32' the second least and is good for its memory/runtime constraints.")))
-        else:
-            raise runtime_ex
+    return GuidedRun(
+        model=gd_model, diffusion=diffusion, cond_fn=cond_fn, loop=loop, model_kwargs=model_kwargs,
+        shape=(local_batch, 3, image_size + height_offset, image_size + width_offset), init_tensor=init_tensor, skip_timesteps=skip_timesteps,
+        randomize_class=randomize_class, loop_kw={**({} if mask_tensor is None else {"mask": mask_tensor}), **invert_kw}, progress=progress,
+        save_frequency=save_frequency, wandb_run=wandb_run, mine=mine, prefix_path=prefix_path, prompts=prompts, clip_model_name=clip_model_name,
+        # what a caller that changes the text prompts between runs needs (cgd_amd.animate): the towers' names, the device, every text
+        # embedding made so far by (text, tower name), and the image prompts' embeddings per tower with their weights
+        clip_names=clip_names, device=device, text_cache=text_cache,
+        image_embeds=[e[text_embeds:] for e in embeds_per_tower], image_weights=weights[text_weights:])
 
 
 # The reference CLI, flag for flag (cgd.py:290-357): "long alias kind default | help".  kind: str / int / float / path, or "flag"

@@ -349,6 +349,21 @@ int cgd_ilvr_refine(cgd_ctx* ctx, float* sample, float* x0, const float* ref, co
   return cgd_launch_ilvr_refine(ctx, sample, x0, ref, noise, scratch, B, H, W, ref_batch, factor, sa, sb, S(stream));
 }
 
+// (the launchers of warp.hip judge the arguments first and ask for the context afterwards; DeviceScope takes a null context)
+int cgd_frame_warp(cgd_ctx* ctx, const float* src, float* dst, int B, int C, int H, int W, const cgd_warp* w, void* stream) {
+  DeviceScope dev_scope__(ctx);
+  return cgd_launch_frame_warp(ctx, src, dst, B, C, H, W, w, S(stream));
+}
+int cgd_channel_stats(cgd_ctx* ctx, const float* x, float* stats, int B, int C, int H, int W, void* stream) {
+  DeviceScope dev_scope__(ctx);
+  return cgd_launch_channel_stats(ctx, x, stats, B, C, H, W, S(stream));
+}
+int cgd_color_match(cgd_ctx* ctx, float* x, const float* stats_x, const float* stats_ref, int ref_batch, float amount, int clamp, int B, int C,
+                    int H, int W, void* stream) {
+  DeviceScope dev_scope__(ctx);
+  return cgd_launch_color_match(ctx, x, stats_x, stats_ref, ref_batch, amount, clamp, B, C, H, W, S(stream));
+}
+
 int cgd_window_gather(cgd_ctx* ctx, const float* full, float* win, const int* oy, int ny, const int* ox, int nx, const float* ay, const float* ax,
                       int B, int C, int H, int W, int S, int wrap, void* stream) {
   CGD_NEED_CTX(ctx);

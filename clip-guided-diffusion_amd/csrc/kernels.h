@@ -148,6 +148,13 @@ int cgd_launch_masked_merge(cgd_ctx* ctx, float* sample, float* x0, const float*
 int cgd_launch_ilvr_refine(cgd_ctx* ctx, float* sample, float* x0, const float* ref, const float* noise, float* scratch, int B, int H, int W,
                            int ref_batch, int factor, float sa, float sb, hipStream_t s);
 long cgd_ilvr_scratch(int B, int H, int W, int factor, int with_x0);
+// warp.hip: what 2D animation runs between two frames (include/cgd_mi355x.h: cgd_frame_warp, cgd_channel_stats, cgd_color_match).  The
+// arguments are judged before the context is needed: a refused call returns -2 even with a null context, an accepted one -3 without one
+struct cgd_warp;
+int cgd_launch_frame_warp(cgd_ctx* ctx, const float* src, float* dst, int B, int C, int H, int W, const cgd_warp* w, hipStream_t s);
+int cgd_launch_channel_stats(cgd_ctx* ctx, const float* x, float* stats, int B, int C, int H, int W, hipStream_t s);
+int cgd_launch_color_match(cgd_ctx* ctx, float* x, const float* stats_x, const float* stats_ref, int ref_batch, float amount, int clamp, int B,
+                           int C, int H, int W, hipStream_t s);
 // window.hip: the adjoint pair of windowed sampling (include/cgd_mi355x.h: cgd_window_gather / cgd_window_merge); oy [ny], ox [nx]: host arrays of
 // window origins; ay [ny][S], ax [nx][S]: device weight tables, both or neither (null = ones)
 int cgd_launch_window_gather(cgd_ctx* ctx, const float* full, float* win, const int* oy, int ny, const int* ox, int nx, const float* ay,

@@ -686,6 +686,42 @@ class ClipGuidance:
         self._wm = {}
         self._wmd = {}           # the direction columns of the weight matrix, per batch size
         self._buf = {}
+        self._lpips_net = lpips  # the handle as given: set_init can switch the init-image term on later
+
+    # -- between runs on the same guidance (cgd_amd.animate; nothing on the existing paths calls these) --------------------------
+    def set_init(self, init_tensor, init_scale, lpips=None):
+        """Replace the image the LPIPS term holds the sample to, (1 or B, 3, H, W) in [-1, 1], and its weight; the next call hands the new
+        image to the LPIPS handle (set_reference).  None or a zero scale switches the term off.  `lpips`: a nets.LpipsVGG for a guidance
+        that was built without one."""
+        self.init_scale = float(init_scale)
+        if lpips is not None:
+            self._lpips_net = lpips
+        if init_tensor is None or init_scale == 0:
+            self.lpips = self.init_tensor = None
+        else:
+            if self._lpips_net is None:
+                raise ValueError("set_init needs the LPIPS-VGG16 handle the guidance was built with (lpips=)")
+            if init_tensor.dim() != 4 or init_tensor.shape[1] != 3:
+                raise ValueError(f"init_tensor must be (1 or B, 3, H, W), got {tuple(init_tensor.shape)}")
+            self.lpips, self.init_tensor = self._lpips_net, init_tensor.detach().float()
+        self._lpips_ref_batch = 0
+
+    def set_targets(self, embeds, weights):
+        """Replace the target embeddings (one (P, D) tensor per tower, or one tensor) and their P weights (as the constructor takes them);
+        the B x P weight matrices are rebuilt at the next call.  Not with direction prompts or regions: their columns index the old list."""
+        if self.dirs_list is not None or self.regions is not None:
+            raise ValueError("set_targets does not work with direction prompts or region prompts: their columns index the first prompt list")
+        embeds = list(embeds) if isinstance(embeds, (list, tuple)) else [embeds]
+        if len(embeds) != len(self.towers):
+            raise ValueError("one target-embedding tensor per CLIP tower")
+        w = th.as_tensor(weights, dtype=th.float32).flatten()
+        if any(e.dim() != 2 or e.shape[0] != w.numel() for e in embeds) or w.numel() == 0:
+            raise ValueError(f"every tower needs as many target embeddings as there are weights ({w.numel()}), and at least one")
+        self.targets_list = [F.normalize(e.float(), dim=-1).contiguous() for e in embeds]
+        self.targets_n = self.targets_list[0]
+        self.weights = w.to(self.targets_n.device)
+        self.no_clip = False
+        self._wm, self._wmd = {}, {}
 
     # -- helpers ------------------------------------------------------------------------------------
     def _b(self, name, shape, device, dtype=th.float32):

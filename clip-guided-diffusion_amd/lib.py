@@ -78,6 +78,15 @@ class Dpmpp(C.Structure):
     _fields_ = [("c_x", f32), ("c_d", f32), ("c_r", f32), ("c_n", f32)]
 
 
+class Warp(C.Structure):
+    """cgd_warp: the inverse affine map of cgd_frame_warp (source position of destination pixel (x, y): m0 x + m1 y + m2, m3 x + m4 y + m5),
+    interp 0 bilinear / 1 bicubic, border 0 wrap / 1 reflect / 2 replicate, clamp 1 = clamp the result to [-1, 1]"""
+    _fields_ = [("m", C.c_double * 6), ("interp", i32), ("border", i32), ("clamp", i32)]
+
+
+WARP_INTERP = {"bilinear": 0, "bicubic": 1}
+WARP_BORDER = {"wrap": 0, "reflect": 1, "replicate": 2}
+
 MANIFEST_CB = C.CFUNCTYPE(None, C.c_char_p, i64, vp)
 
 # name -> (restype, argtypes).  Pointers to device memory are passed as integers (tensor.data_ptr()).
@@ -210,6 +219,9 @@ _SIGS = {
     "cgd_masked_merge": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(MaskCoef), vp]),
     "cgd_ilvr_scratch_floats": (C.c_long, [i32, i32, i32, i32, i32]),
     "cgd_ilvr_refine": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]),
+    "cgd_frame_warp": (i32, [vp, vp, vp, i32, i32, i32, i32, C.POINTER(Warp), vp]),
+    "cgd_channel_stats": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
+    "cgd_color_match": (i32, [vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, i32, vp]),
     "cgd_window_gather": (i32, [vp, vp, vp, C.POINTER(i32), i32, C.POINTER(i32), i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_window_merge": (i32, [vp, vp, vp, C.POINTER(i32), i32, C.POINTER(i32), i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_ddim_reverse_update": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(ReverseCoef), vp]),

@@ -289,6 +289,61 @@ def act(ctx, x, kind, dy=None):
     return out
 
 
+def _nchw(t, name):
+    ptr = _dense(t, name)
+    if t.dim() != 4:
+        raise ValueError(f"{name}: expected (B, C, H, W), got shape {tuple(t.shape)}")
+    return ptr
+
+
+def frame_warp(ctx, src, matrix, interp="bicubic", border="wrap", clamp=False, out=None):
+    """Affine resampling of src (B,C,H,W) in one launch (cgd_frame_warp): `matrix` holds the six entries of the INVERSE map, destination
+    pixel (x, y) reads the source at (m0 x + m1 y + m2, m3 x + m4 y + m5); interp 'bilinear' / 'bicubic' (a = -0.75), border 'wrap' /
+    'reflect' / 'replicate', clamp: to [-1, 1] after interpolation.  `out` must not alias `src`."""
+    ps = _nchw(src, "src")
+    if interp not in L.WARP_INTERP or border not in L.WARP_BORDER:
+        raise ValueError(f"interp must be one of {sorted(L.WARP_INTERP)} and border one of {sorted(L.WARP_BORDER)}, got {interp!r} and {border!r}")
+    m = [float(v) for v in matrix]
+    if len(m) != 6:
+        raise ValueError(f"matrix: expected 6 entries, got {len(m)}")
+    if out is None:
+        out = th.empty_like(src)
+    po = _nchw(out, "out")
+    if tuple(out.shape) != tuple(src.shape):
+        raise ValueError(f"out: shape {tuple(out.shape)}, src has {tuple(src.shape)}")
+    B, Cn, H, W = src.shape
+    w = L.Warp((C.c_double * 6)(*m), L.WARP_INTERP[interp], L.WARP_BORDER[border], int(bool(clamp)))
+    ctx.check(ctx.lib.cgd_frame_warp(ctx.h, ps, po, B, Cn, H, W, C.byref(w), _s()))
+    return out
+
+
+def channel_stats(ctx, x, out=None):
+    """(B,C,2): mean and population standard deviation of every plane of x (B,C,H,W), sums in fp64 (cgd_channel_stats)."""
+    px = _nchw(x, "x")
+    B, Cn, H, W = x.shape
+    if out is None:
+        out = th.empty((B, Cn, 2), device=x.device, dtype=th.float32)
+    po = _dense(out, "out")
+    if tuple(out.shape) != (B, Cn, 2):
+        raise ValueError(f"out: expected shape {(B, Cn, 2)}, got {tuple(out.shape)}")
+    ctx.check(ctx.lib.cgd_channel_stats(ctx.h, px, po, B, Cn, H, W, _s()))
+    return out
+
+
+def color_match(ctx, x, stats_ref, amount=1.0, clamp=False, stats_x=None):
+    """In place: every plane of x (B,C,H,W) is moved toward the mean and standard deviation `stats_ref` (1 or B, C, 2) by `amount` in
+    [0, 1] (cgd_color_match); `stats_x`: channel_stats(x) (taken here when None).  Returns x."""
+    px = _nchw(x, "x")
+    B, Cn, H, W = x.shape
+    if stats_x is None:
+        stats_x = channel_stats(ctx, x)
+    psx, psr = _dense(stats_x, "stats_x"), _dense(stats_ref, "stats_ref")
+    if tuple(stats_x.shape) != (B, Cn, 2) or stats_ref.dim() != 3 or tuple(stats_ref.shape[1:]) != (Cn, 2):
+        raise ValueError(f"stats_x must be {(B, Cn, 2)} and stats_ref (1 or {B}, {Cn}, 2), got {tuple(stats_x.shape)} and {tuple(stats_ref.shape)}")
+    ctx.check(ctx.lib.cgd_color_match(ctx.h, px, psx, psr, int(stats_ref.shape[0]), float(amount), int(bool(clamp)), B, Cn, H, W, _s()))
+    return x
+
+
 class Attention:
     """QKV attention on token-major qkv (nb*T, 3C); keeps the buffers the backward needs."""
 

@@ -562,6 +562,38 @@ long cgd_ilvr_scratch_floats(int B, int H, int W, int factor, int with_pred_xsta
 int cgd_ilvr_refine(cgd_ctx* ctx, float* sample, float* pred_xstart, const float* ref, const float* noise, float* scratch, int B, int H,
                     int W, int ref_batch, int factor, float sa, float sb, void* stream);
 
+/* ---- 2D animation (Disco Diffusion's 2D mode, Deforum): frame k starts from frame k - 1, zoomed, rotated and shifted.  What runs once per
+ *      frame, each in one launch; NCHW fp32, any C.
+ *      cgd_frame_warp: affine resampling.  For destination pixel (x, y) the source position is
+ *        sx = m0 x + m1 y + m2,  sy = m3 x + m4 y + m5        (the INVERSE map, built by the host; pixel centres sit on integers)
+ *      computed, floored and split into integer and fractional parts in fp64; the fractions then become fp32, weights and sums are fp32.
+ *      interp 0: bilinear, taps floor, floor + 1.  interp 1: bicubic, Keys kernel with a = -0.75 (OpenCV's INTER_CUBIC, torch's bicubic; not
+ *      the a = -0.5 of the cutout resize), taps floor - 1 .. floor + 2.  Separable: the x taps of a row are summed in ascending order, then
+ *      the row results in ascending y.  border, applied to every tap index on its own: 0 wrap (i mod n, also for negative i), 1 reflect
+ *      without repeating the edge (period 2 (n - 1): OpenCV's REFLECT_101, torch's reflection with align_corners=True; a side of length 1
+ *      gives index 0), 2 replicate (clamp).  clamp 1: the result is clamped to [-1, 1] after interpolation (bicubic overshoots).  At a
+ *      fraction of 0 the weights are exactly 1 and 0: the identity and integer shifts copy bits.
+ *      cgd_channel_stats: stats (B,C,2) = (mean, population standard deviation) of every plane; the sums of x and x^2 are fp64, in a fixed
+ *      order, one workgroup per plane.
+ *      cgd_color_match, in place: x <- x + amount ((mu_ref + (x - mu_x) r) - x), r = sigma_ref / sigma_x and r = 1 where sigma_x < 1e-6 (a
+ *      flat plane stays flat); stats_x (B,C,2) and stats_ref (ref_batch,C,2) as cgd_channel_stats writes them, ref_batch 1 or B, amount in
+ *      [0, 1] (0 leaves the bits alone), clamp 1 = clamp the result to [-1, 1].
+ *      Gather form, no atomics, no scratch buffer: the same bits on every run.  Plane offsets are 64-bit.  Any 4-byte-aligned pointers
+ *      are accepted.  dst must not alias src.  Each returns -2 (cgd_last_error), before any launch, for a null pointer, src == dst, a
+ *      non-positive size, H W >= 2^31, an unknown interp or border, a non-finite matrix entry, a matrix that maps a frame corner beyond
+ *      +-2^30 (the integer tap indices then cannot overflow), a ref_batch other than 1 or B, or an amount outside [0, 1].  The arguments
+ *      are judged before the context is looked at: a refused call returns -2 with a NULL context too, an accepted one -3. ---- */
+typedef struct cgd_warp {
+  double m[6];
+  int interp; /* 0 bilinear, 1 bicubic */
+  int border; /* 0 wrap, 1 reflect, 2 replicate */
+  int clamp;  /* 1: clamp the result to [-1, 1] */
+} cgd_warp;
+int cgd_frame_warp(cgd_ctx* ctx, const float* src, float* dst, int B, int C, int H, int W, const cgd_warp* warp, void* stream);
+int cgd_channel_stats(cgd_ctx* ctx, const float* x, float* stats, int B, int C, int H, int W, void* stream);
+int cgd_color_match(cgd_ctx* ctx, float* x, const float* stats_x, const float* stats_ref, int ref_batch, float amount, int clamp, int B, int C,
+                    int H, int W, void* stream);
+
 /* ---- windowed sampling (MultiDiffusion, Bar-Tal et al., 2023): the frame is cut into overlapping S x S windows of the model's trained size, the
  *      model runs on all windows as one batch, and the window outputs are averaged into one prediction for the frame.  An adjoint pair, one
  *      launch each whatever B, C and the window count:

@@ -218,6 +218,7 @@ inline int elem_grid(long n) { return grid_for(n, 4096); }
 int cgd_launch_pool2x2(cgd_ctx* ctx, const float* in, int ldi, float* out, int ldo, const float* add, int ldadd, int B, int Ho,
                        int Wo, int C, float scale, hipStream_t s) {
   CGD_TRY(cgd_sync_pending(ctx, s));  // reads activations: a deferred split-K reduction must have landed
+  if (B <= 0 || Ho <= 0 || Wo <= 0 || C <= 0) CGD_FAIL(ctx, "pool2x2: B, Ho, Wo and C must be positive");
   if ((C & 3) || (ldi & 3) || (ldo & 3)) CGD_FAIL(ctx, "pool2x2: C and strides must be multiples of 4");
   if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)add) & 15) CGD_FAIL(ctx, "pool2x2: in / out / add must be 16-byte aligned");
   cgd_chanstats_invalidate(ctx, out, (long)B * Ho * Wo, ldo, C);
@@ -230,6 +231,8 @@ int cgd_launch_pool2x2(cgd_ctx* ctx, const float* in, int ldi, float* out, int l
 int cgd_launch_upsample2x(cgd_ctx* ctx, const float* in, int ldi, float* out, int ldo, const float* add, int ldadd, int B, int Ho,
                           int Wo, int C, float scale, hipStream_t s) {
   CGD_TRY(cgd_sync_pending(ctx, s));  // reads activations: a deferred split-K reduction must have landed
+  // the output is twice the input along H and W: an odd Ho / Wo has no input map (the kernel would index (Ho >> 1) x (Wo >> 1) pixels)
+  if (B <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || ((Ho | Wo) & 1)) CGD_FAIL(ctx, "upsample2x: B and C must be positive, Ho and Wo positive and even");
   if ((C & 3) || (ldi & 3) || (ldo & 3)) CGD_FAIL(ctx, "upsample2x: C and strides must be multiples of 4");
   if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)add) & 15) CGD_FAIL(ctx, "upsample2x: in / out / add must be 16-byte aligned");
   cgd_chanstats_invalidate(ctx, out, (long)B * Ho * Wo, ldo, C);

@@ -729,8 +729,14 @@ __global__ __launch_bounds__(256 * KG) void hgemm2_kernel(const float* __restric
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       const int col = cb0 + 8 * g + 4 * hh;
-      cgd_f32x4 o = cgd_f32x4{acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]} * p.alpha;
-      if (biasg) o += cgd_f32x4{biasg[col], biasg[col + 1], biasg[col + 2], biasg[col + 3]};
+      const cgd_f32x4 av = cgd_f32x4{acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]};
+      cgd_f32x4 o = av * p.alpha;
+      if (biasg) {
+        // alpha * acc + bias in ONE rounding, as the LDS epilogue above (the compiler contracts its multiply and add) and splitk_reduce_kernel do it:
+        // written as a multiply and an add this path kept both roundings and differed from them in the last bit whenever alpha != 1 met a bias
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = __builtin_fmaf(av[e], p.alpha, biasg[col + e]);
+      }
       if (Rg) o += rv[g];
       if (p.act_in) {  // backward through the activation: multiply by act'(u), same arithmetic as elem.hip dact_f
         cgd_f32x4 d;

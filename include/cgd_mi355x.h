@@ -769,7 +769,8 @@ int cgd_op_ln_fwd(cgd_ctx* ctx, const float* x, float* y, int rows, int C, const
                   float* stats, void* stream);
 int cgd_op_ln_bwd(cgd_ctx* ctx, const float* x, const float* dy, float* dx, int rows, int C, const float* gamma, const float* stats,
                   void* stream);
-/* pool2x2 / upsample2x: C a multiple of 4 and in / out 16-byte aligned, or the call fails before anything is launched */
+/* pool2x2 / upsample2x: (Ho, Wo) = the OUTPUT map, the input is (2 Ho, 2 Wo) / (Ho / 2, Wo / 2).  B, Ho, Wo, C positive, C a multiple of 4, in / out
+ * 16-byte aligned and, for upsample2x, Ho and Wo even, or the call fails before anything is launched */
 int cgd_op_pool2x2(cgd_ctx* ctx, const float* in, float* out, int B, int Ho, int Wo, int C, float scale, void* stream);
 int cgd_op_upsample2x(cgd_ctx* ctx, const float* in, float* out, int B, int Ho, int Wo, int C, float scale, void* stream);
 /* act: 1 SiLU, 2 QuickGELU, 3 exact (erf) GELU; any other code fails (-2).  dy null: out = act(x); else out = dy * act'(x) */

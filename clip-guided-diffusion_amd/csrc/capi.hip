@@ -649,6 +649,13 @@ int64_t cgd_op_attn_buf_floats(int nb, int heads, int T, int d, int which) {
     default: return (int64_t)nb * heads * T * Tp;
   }
 }
+// test support: what NetBase::attn_fwd / attn_bwd would `ensure` for this call on this context (the kernel family's own size, 0 for a buffer the
+// family does not touch); -1 without a context or for a non-positive shape
+int64_t cgd_op_attn_buf_floats_ctx(cgd_ctx* ctx, int nb, int heads, int T, int d, int legacy, int causal, int which) {
+  if (!ctx || nb <= 0 || heads <= 0 || T <= 0 || d <= 0 || which < 0 || which > 4) return -1;
+  AttnShape sh{nb, heads, T, d, heads * d, legacy, causal};
+  return (int64_t)cgd_attn_buf_floats(ctx, sh, 3 * heads * d, heads * d, which);
+}
 int cgd_op_attn_fwd(cgd_ctx* ctx, const float* qkv, float* out, int nb, int heads, int T, int d, int legacy, float* bufs[5],
                     void* stream) {
   CGD_NEED_CTX(ctx);

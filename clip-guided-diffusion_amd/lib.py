@@ -258,6 +258,7 @@ _SIGS = {
     "cgd_op_upsample2x": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, vp]),
     "cgd_op_act": (i32, [vp, vp, vp, vp, i64, i32, vp]),
     "cgd_op_attn_buf_floats": (i64, [i32, i32, i32, i32, i32]),
+    "cgd_op_attn_buf_floats_ctx": (i64, [vp, i32, i32, i32, i32, i32, i32, i32]),
     "cgd_op_attn_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(vp), vp]),
     "cgd_op_attn_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(vp), vp]),
     "cgd_op_attn_fwd_causal": (i32, [vp, vp, vp, i32, i32, i32, i32, C.POINTER(vp), vp]),

@@ -777,6 +777,12 @@ int cgd_op_upsample2x(cgd_ctx* ctx, const float* in, float* out, int B, int Ho, 
 int cgd_op_act(cgd_ctx* ctx, const float* x, const float* dy, float* out, int64_t n, int act, void* stream);
 /* upper bound over all kernel families (the GEMM path's T x T probabilities); the networks size their own scratch per family (flash: row statistics) */
 int64_t cgd_op_attn_buf_floats(int nb, int heads, int T, int d, int which);
+/* test support (like cgd_op_gemm_ex / cgd_op_pending), host only: the floats of buffer `which` that the networks allocate for this call on THIS
+ * context, i.e. the size of the kernel family the context would run it on now (row strides 3 heads d and heads d): flash keeps a copy of O in
+ * bufs[0] and LSE | D, 2 nb heads 32 ceil(T / 32) floats, in bufs[1]; attn_s64_* only P; attn_mid_* no Pt / dAt; 0 = the family does not touch the
+ * buffer (the forward of every family leaves bufs[2..4] alone: the networks hand it NULL there).  -1 for a NULL context or a non-positive shape.
+ * The buffers carry state from a forward to its backward only. */
+int64_t cgd_op_attn_buf_floats_ctx(cgd_ctx* ctx, int nb, int heads, int T, int d, int legacy, int causal, int which);
 int cgd_op_attn_fwd(cgd_ctx* ctx, const float* qkv, float* out, int nb, int heads, int T, int d, int legacy, float* bufs[5],
                     void* stream);
 int cgd_op_attn_bwd(cgd_ctx* ctx, const float* qkv, const float* dout, float* dqkv, int nb, int heads, int T, int d, int legacy,

@@ -175,10 +175,14 @@ def prepare_run(image_size=128, num_cutouts=16, prompts=[], image_prompts=[], cl
 
     # "A+cuts=OV:IN" (an extension like "plmsN"): overview + inner cutouts through the antialiased cubic resize instead of pooled crops
     # "A+classifier=FILE:CLASS[:SCALE]" (likewise): classifier guidance with guided-diffusion's noisy ImageNet classifier
-    without_classifier, classifier_spec = clip_util.split_classifier(clip_model_name, height_offset, width_offset)  # refuses before any load
+    # "A+aesthetic=FILE:SCALE" (likewise): an aesthetic predictor on the embeddings of the tower entry before it; taken out of the list first
+    without_aesthetic, aesthetic_specs = clip_util.split_aesthetic(clip_model_name)  # refuses before any load
+    without_classifier, classifier_spec = clip_util.split_classifier(without_aesthetic, height_offset, width_offset)  # refuses before any load
     towers_and_secondary, cuts = clip_util.split_cuts(without_classifier, progressive_cutout, use_augs)  # refuses before any load
     # "A+secondary=FILE" (likewise): the guidance gradient returns through the secondary model instead of through the UNet
     clip_names, secondary_path = clip_util.split_secondary(towers_and_secondary, image_size, height_offset, width_offset)  # refuses before any load
+    if any(spec is not None for spec in aesthetic_specs) and len(aesthetic_specs) != len(clip_names):
+        raise ValueError(f"{clip_model_name}: an empty entry in the list; 'aesthetic=' entries cannot be bound to its {len(clip_names)} towers")
 
     wandb_run = None
     if wandb_project is not None:
@@ -236,7 +240,8 @@ def prepare_run(image_size=128, num_cutouts=16, prompts=[], image_prompts=[], cl
         region_specs.extend([region] * len(batched))  # every embedding of the image gets its region
     # (a run with direction prompts only has no target embeddings: ClipGuidance then makes no spherical launch)
     # (... and a run with a style image and no prompt at all has neither: no cutouts, no CLIP pass)
-    style_only = style_spec is not None and not weights
+    # (... and so has a run with an aesthetic head and no prompt: the CLIP pass then runs for the head alone)
+    style_only = (style_spec is not None or any(spec is not None for spec in aesthetic_specs)) and not weights
     target_embeds = [th.cat(e) for e in embeds_per_tower] if (embeds_per_tower[0] or not (direction_columns or style_only)) else None
     weight_t = th.tensor(weights, device=device)
     if not style_only:
@@ -317,6 +322,11 @@ def prepare_run(image_size=128, num_cutouts=16, prompts=[], image_prompts=[], cl
         gd_model = nets.WindowedUNet(gd_model, stride=windows_spec[0], wrap=windows_spec[1], feather=windows_spec[2])
     # (a collective like the loads above: before the early return of a rank without samples)
     secondary = clip_util.load_secondary(gd_model.ctx, secondary_path, device) if secondary_path is not None else None
+    aesthetic_kw = {}
+    if any(spec is not None for spec in aesthetic_specs):  # (collectives too: one small broadcast per head)
+        heads = [None if spec is None else clip_util.load_aesthetic(gd_model.ctx, spec[0], device, cm.tower.out_dim, name)
+                 for spec, cm, name in zip(aesthetic_specs, clip_models, clip_names)]
+        aesthetic_kw = dict(aesthetic_heads=heads, aesthetic_scale=[0.0 if spec is None else spec[1] for spec in aesthetic_specs])
     classifier = None
     if classifier_spec is not None:  # (a collective too)
         classifier = clip_util.load_classifier(gd_model.ctx, classifier_spec[0], device, image_size)
@@ -361,6 +371,7 @@ def prepare_run(image_size=128, num_cutouts=16, prompts=[], image_prompts=[], cl
         secondary=secondary,
         **({"direction_source": init_tensor, **direction_kw} if direction_kw else {}),
         **({} if region_plan is None else {"regions": region_plan}),
+        **aesthetic_kw,
         **({} if classifier is None else {"classifier": classifier, "classifier_scale": classifier_spec[2], "classifier_class": classifier_spec[1]}))
     if nranks > 1:
         cond_fn.shard = diffusion.shard = (mine, batch_size)
@@ -412,7 +423,7 @@ _CLI_SPEC = f"""
 --timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', 'plmsN' for PLMS (e.g. -respace plms50), or 'dpmN' / 'dpmsdeN' for DPM-Solver++(2M) / its SDE form on at most N logSNR-uniform levels (e.g. -respace dpm20); 'dpmN+thr=P' or 'dpmsdeN+thr=P:CAP' adds dynamic thresholding of the guided prediction: per sample it is clamped to its own P-quantile of absolute values s (at least 1, at most CAP) and divided by s (e.g. -respace dpm20+thr=0.995; CAP 1 is the static clip to [-1, 1]); a last suffix '+windows=STRIDE[:wrapx|:wrapy|:wrap][:feather]' (e.g. -respace 250+windows=128:wrapx with --width_offset 256) samples a frame larger than the checkpoint in windows (MultiDiffusion): the model runs on overlapping --image_size windows STRIDE pixels apart (a positive multiple of 8, at most --image_size; frame sides multiples of 8) and their predictions are averaged, with sin^2 weights under :feather; :wrapx / :wrapy / :wrap let windows run over the right / bottom / both edges, so the result tiles seamlessly along that axis (STRIDE must divide its length); not with upsample=, invert= or +classifier=
 --num_cutouts -cutn int 16 | random cutouts shown to CLIP per step
 --cutout_power -cutpow float 1.0 | exponent of the cutout size distribution
---clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, ARCH=FILE for an open_clip ViT checkpoint (ARCH: ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14, optional -quickgelu suffix), 'A+B' to sum two towers, 'A+secondary=FILE' to guide through the secondary model FILE, 'A+classifier=FILE:CLASS[:SCALE]' for classifier guidance toward ImageNet class CLASS with the noisy classifier FILE (weight SCALE, default 1; with a class-conditional model y is held at CLASS; needs zero height / width offsets), or 'A+cuts=OV:IN' (or 'cuts=OV:IN/OV2:IN2': the second pair once 40 percent of the run is done) for OV whole-frame and IN random cutouts per step through the antialiased cubic resize (--num_cutouts then only affects image prompts)
+--clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, ARCH=FILE for an open_clip ViT checkpoint (ARCH: ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14, optional -quickgelu suffix), 'A+B' to sum two towers, 'A+secondary=FILE' to guide through the secondary model FILE, 'A+classifier=FILE:CLASS[:SCALE]' for classifier guidance toward ImageNet class CLASS with the noisy classifier FILE (weight SCALE, default 1; with a class-conditional model y is held at CLASS; needs zero height / width offsets), 'A+aesthetic=FILE:SCALE' to add the LAION aesthetic predictor FILE (the linear sa_0_4_vit_*_linear.pth heads or the five-layer improved-aesthetic-predictor ones, whose embedding width must be tower A's) on the embeddings of the tower entry before it: the loss gains -SCALE times the mean predicted score of the cutouts, a negative SCALE steers away, each tower takes at most one (the list is split on '+': a checkpoint whose own name contains '+', as sac+logos+ava1-l14-linearMSE.pth does, has to be renamed or symlinked), or 'A+cuts=OV:IN' (or 'cuts=OV:IN/OV2:IN2': the second pair once 40 percent of the run is done) for OV whole-frame and IN random cutouts per step through the antialiased cubic resize (--num_cutouts then only affects image prompts)
 --uncond -uncond flag | use the unconditional 256 / 512 checkpoints
 --noise_schedule -sched str linear | 'linear' or 'cosine'
 --dropout -drop float 0.0 | dropout of the diffusion model (inference: keep 0)

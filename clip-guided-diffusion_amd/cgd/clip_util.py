@@ -213,6 +213,89 @@ def load_secondary(ctx, path, device):
     return net
 
 
+_NO_TOWER_ENTRIES = ("secondary=", "cuts=", "classifier=", "aesthetic=")
+AESTHETIC_PLUS_HINT = ("the list is split on '+', so a checkpoint whose own name contains '+' (sac+logos+ava1-l14-linearMSE.pth) has to be "
+                       "renamed or symlinked first")
+
+
+def _known_tower_entry(entry):
+    """Can load_clip make something of this piece of the list: a tower name, an open_clip 'ARCH' or 'ARCH=FILE', or a checkpoint file?"""
+    return (entry in CLIP_MODEL_URLS or entry in _nets.VIT_CONFIGS or entry in _nets.RN_CONFIGS
+            or _nets.openclip_arch(entry.partition("=")[0].strip()) is not None or os.path.isfile(entry))
+
+
+def split_aesthetic(clip_model_name):
+    """The '+'-separated `--clip_model` list -> (the list without its `aesthetic=` entries, one (FILE, SCALE) or None per tower entry of that
+    list, in order).  An `aesthetic=FILE:SCALE` entry puts an aesthetic predictor (`cgd_amd.nets.AestheticHead`: the guidance loss gains
+    -SCALE * sum_b mean_cut score) on the tower entry BEFORE it, `secondary=` / `cuts=` / `classifier=` entries in between not counting:
+    'ViT-L/14+aesthetic=sa_0_4_vit_l_14_linear.pth:500+ViT-B/32' scores ViT-L/14's embeddings only.  It is a value like 'secondary=FILE' and
+    counts as no tower.  FILE may contain colons of its own: it is split from SCALE at the last ':'; a negative SCALE steers away.  FILE is not
+    read under CGD_SYNTHETIC_WEIGHTS=1.  Refused here, before anything is loaded (FILE is never opened): no tower before the entry, an empty
+    FILE, a SCALE that is missing, not a finite float or zero, and two heads on one tower.  A list without the entry passes through unchanged
+    (the very string).  The list is split on '+': a checkpoint whose own name contains '+' has to be renamed or symlinked, and the errors
+    about a missing SCALE and about an unknown piece behind an `aesthetic=` entry say so."""
+    entries = [n.strip() for n in clip_model_name.split("+")]
+    if not any(e.partition("=")[1] and e.partition("=")[0].strip() == "aesthetic" for e in entries):
+        return clip_model_name, [None] * sum(1 for e in entries if e and not e.startswith(_NO_TOWER_ENTRIES))
+    names, heads, seen = [], [], False
+    for entry in entries:
+        head, sep, value = entry.partition("=")
+        if not (sep and head.strip() == "aesthetic"):
+            names.append(entry)
+            if entry and not entry.startswith(_NO_TOWER_ENTRIES):
+                if seen and not _known_tower_entry(entry):
+                    raise ValueError(f"{clip_model_name}: '{entry}' behind an 'aesthetic=' entry is no CLIP tower, checkpoint file or known entry; "
+                                     f"{AESTHETIC_PLUS_HINT}")
+                heads.append(None)
+            continue
+        seen = True
+        usage = f"{entry}: expected 'aesthetic=FILE:SCALE' (SCALE a finite non-zero number); {AESTHETIC_PLUS_HINT}"
+        if not heads:
+            raise ValueError(f"{clip_model_name}: 'aesthetic=' needs a CLIP tower before it, e.g. 'ViT-L/14+aesthetic=FILE:500'")
+        path, colon, scale_text = value.strip().rpartition(":")
+        path, scale_text = path.strip(), scale_text.strip()
+        if not colon:
+            raise ValueError(usage if value.strip() else f"{entry}: 'aesthetic=FILE:SCALE' needs a checkpoint path after '='")
+        if not path:
+            raise ValueError(f"{entry}: 'aesthetic=FILE:SCALE' needs a checkpoint path after '='")
+        try:
+            scale = float(scale_text)
+        except ValueError:
+            raise ValueError(usage) from None
+        if scale != scale or scale in (float("inf"), float("-inf")) or scale == 0:
+            raise ValueError(f"{entry}: SCALE must be a finite non-zero number, got {scale_text}")
+        if heads[-1] is not None:
+            raise ValueError(f"{clip_model_name}: two 'aesthetic=' entries on one tower ('{heads[-1][0]}' and '{path}'); each binds to the tower "
+                             "entry before it")
+        heads[-1] = (path, scale)
+    return "+".join(names), heads
+
+
+def load_aesthetic(ctx, path, device, dim, what="the tower"):
+    """The device aesthetic head (`aesthetic=FILE:SCALE`) for a tower of embedding width `dim`: FILE is a published linear or five-layer
+    predictor (nets.collapse_aesthetic_state_dict), read and collapsed on rank 0 and broadcast as one (dim + 1,) vector; a head of another
+    width is refused naming both.  With CGD_SYNTHETIC_WEIGHTS=1 a seeded head, FILE is not read."""
+    dev = f"cuda:{ctx.device}"
+    head = _nets.AestheticHead(dim, dev)
+    if script_util.synthetic_weights_enabled():
+        _shard.load_broadcast(head, lambda: _synthetic.aesthetic_head(dim), dev)
+        return head
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path} not found (set CGD_SYNTHETIC_WEIGHTS=1 for seeded random weights)")
+    held = {}
+
+    def probe():  # rank 0 only: the other ranks receive the width, never the file
+        held["vec"] = _nets.collapse_aesthetic_state_dict(th.load(path, map_location="cpu"))
+        return held["vec"].numel() - 1
+
+    got = _shard.on_rank0(probe)
+    if got != dim:
+        raise ValueError(f"{path} is an aesthetic head for {got}-wide embeddings, {what} gives {dim}")
+    _shard.load_broadcast(head, lambda: {"head": held["vec"]}, dev)
+    held.clear()
+    return head
+
+
 def split_classifier(clip_model_name, height_offset=0, width_offset=0):
     """The '+'-separated `--clip_model` list -> (the list without its `classifier=` entry, None or (FILE, CLASS, SCALE)).  A
     `classifier=FILE:CLASS[:SCALE]` entry switches classifier guidance on (`cgd_amd.nets.NoisyClassifier`: the guidance loss gains

@@ -272,6 +272,11 @@ int cgd_op_region_coverage(cgd_ctx* ctx, const int32_t* sat, const int32_t* regi
   CGD_NEED_CTX(ctx);
   return cgd_launch_region_coverage(ctx, cgd_regions{sat, region_of, region_of_host, power, geo, R, H, W}, out, cutn, P, S(stream));
 }
+int cgd_aesthetic_loss(cgd_ctx* ctx, const float* emb, const float* head, float* d_emb, float* loss_part, float* score, int cutn, int B,
+                       int D, float scale, int accumulate, void* stream) {
+  DeviceScope dev_scope__(ctx);  // (the launcher judges the arguments before it needs the context)
+  return cgd_launch_aesthetic_loss(ctx, emb, head, d_emb, loss_part, score, cutn, B, D, scale, accumulate, S(stream));
+}
 int cgd_pmv_blend(cgd_ctx* ctx, const float* x, const float* out6, float* x0, float* mean, float* logvar, float* xin, int B, int H, int W,
                   const cgd_step_coef* k, void* stream) {
   CGD_NEED_CTX(ctx);

@@ -47,6 +47,9 @@ int cgd_launch_spherical_loss_regions(cgd_ctx* ctx, const float* emb, const floa
 int cgd_launch_directional_loss_regions(cgd_ctx* ctx, const float* emb, const float* src_emb, const float* dirs_n, const float* weights,
                                         float* demb, float* loss_part, int cutn, int B, int Bs, int P, int D, float scale, int accumulate,
                                         const cgd_regions& rg, hipStream_t s);
+// aesthetic.hip
+int cgd_launch_aesthetic_loss(cgd_ctx* ctx, const float* emb, const float* head, float* demb, float* loss_part, float* score, int cutn, int B,
+                              int D, float scale, int accumulate, hipStream_t s);
 // plms.hip
 int cgd_launch_multistep_update(cgd_ctx* ctx, const float* x, const float* x_eval, const float* x0, const float* g, const float* scalars,
                                 const float* noise, const float* const* eps_hist, float* eps_out, float* sample, float* x0_out, int B,

@@ -12,6 +12,7 @@ perspective / grayscale / additive noise) inside the cutaug HIP kernels, whose a
 are drawn like reference_augs draws them (draw_aug_params), the noise on the device generator in its randn_like order.
 `MakeCutoutsResized` is a second cutter: overview + inner cuts through an antialiased cubic resize (the cutresize HIP kernels).
 With `direction_embeds` the CLIP leg also scores the directional loss of prompt-pair edits against a source image (the direction HIP kernel).
+With `aesthetic_heads` it also scores the LAION aesthetic predictors on the cutouts' embeddings (the aesthetic HIP kernel).
 With `regions` (a regions.RegionPlan) every prompt weighs on a cutout by the share of its mask the cutout sees, inside the `_regions` loss entries.
 Every cutter reaches the kernels through one per-step launch object (_CutLaunch, _AugLaunch: forward, backward, and torch_cuts, the same
 cutouts in torch ops), so there is one CLIP leg (ClipGuidance._clip_leg) and one torch restatement of it (_clip_leg_torch) for all of them.
@@ -573,7 +574,7 @@ class ClipGuidance:
                  reduce_clip=False, progressive_cutout=False, cached_cutouts=False, make_cutouts=None, lpips=None, init_tensor=None,
                  init_scale=0.0, secondary=None, classifier=None, classifier_scale=1.0, classifier_class=None, direction_embeds=None,
                  direction_weights=None, direction_source=None, direction_columns=None, style_tensor=None, style_scale=0.0,
-                 style_weights=(1, 1, 1, 1, 0), regions=None):
+                 style_weights=(1, 1, 1, 1, 0), regions=None, aesthetic_heads=None, aesthetic_scale=0.0):
         # Multi-CLIP (BASELINE config 5, a build extension: the reference takes one clip_model_name): `clip_tower` / `target_embeds`
         # may be lists; the CLIP losses of the towers are summed (same cutout boxes, prompt weights and guidance scale).
         self.towers = list(clip_tower) if isinstance(clip_tower, (list, tuple)) else [clip_tower]
@@ -582,6 +583,12 @@ class ClipGuidance:
         # (1 or B, 3, H, W) in [-1, 1].  The B x P weight matrix is built over the P_t + P_d prompts together, the directions in the columns
         # `direction_columns` of that list (default: behind the targets) and `weights` in the others in order, and then split into the
         # two groups.  `target_embeds` may be None (or empty tensors) when there are only directions: the spherical launch is then not made
+        # aesthetic-predictor guidance (csrc/aesthetic.hip), off without `aesthetic_heads`: one nets.AestheticHead
+        # or None per tower, or a single head for a single tower, and `aesthetic_scale`, a float or one per tower; the loss gains
+        # -aesthetic_scale_k * sum_b mean_cut (a_k . normalize(e) + beta_k) for every tower k with a head.  A scale of 0 means no head.  The head
+        # is no prompt: it has no column in the weight matrix and takes no region weight.  `target_embeds` may be None with a head present
+        self.aes_list = self._aesthetic_heads(aesthetic_heads, aesthetic_scale)
+        self.aes_score = None
         has_dir = direction_embeds is not None
         if has_dir:
             dirs = list(direction_embeds) if isinstance(direction_embeds, (list, tuple)) else [direction_embeds]
@@ -598,9 +605,10 @@ class ClipGuidance:
         if has_style and not (float(style_scale) > 0):
             raise ValueError(f"style_scale must be positive, got {style_scale}")
         if target_embeds is None and not has_dir:
-            if not has_style:
-                raise ValueError("no target embeddings: only a run with direction prompts or a style image goes without")
-            target_embeds = [style_tensor.new_zeros((0, t.out_dim)) for t in self.towers]
+            if not has_style and self.aes_list is None:
+                raise ValueError("no target embeddings: only a run with direction prompts, a style image or an aesthetic head goes without")
+            like = style_tensor if self.aes_list is None else next(a[0] for a in self.aes_list if a is not None)
+            target_embeds = [like.new_zeros((0, t.out_dim)) for t in self.towers]
             weights = []
         embeds = list(target_embeds) if isinstance(target_embeds, (list, tuple)) else [target_embeds]
         assert len(embeds) == len(self.towers), "one target-embedding tensor per CLIP tower"
@@ -661,7 +669,8 @@ class ClipGuidance:
             self.style, self.style_tensor = lpips, style_tensor.float()
         self._style_set = False
         self.style_loss = None
-        self.no_clip = self.dirs_list is None and self.targets_list[0].shape[0] == 0  # style (and init) terms only: no cutouts, no CLIP pass
+        # style (and init) terms only: no cutouts, no CLIP pass
+        self.no_clip = self.dirs_list is None and self.aes_list is None and self.targets_list[0].shape[0] == 0
         # secondary model (nets.SecondaryModel) or None: with one, pred / x_in of the guidance losses come from it and the gradient returns to x
         # through it; the UNet's backward pass is not run (its forward still gives the update's mean, variance and the yielded pred_xstart)
         self.secondary = secondary
@@ -724,6 +733,33 @@ class ClipGuidance:
         self._wm, self._wmd = {}, {}
 
     # -- helpers ------------------------------------------------------------------------------------
+    def _aesthetic_heads(self, heads, scales):
+        """The constructor's `aesthetic_heads` / `aesthetic_scale` -> None (no head anywhere: every path is then as without the keywords), or
+        per tower None or (the (D + 1,) fp32 vector, the scale).  Refuses a list of another length than the towers and a head of another
+        width than its tower's embeddings, naming both."""
+        if heads is None:
+            return None
+        heads = list(heads) if isinstance(heads, (list, tuple)) else [heads]
+        if len(heads) != len(self.towers):
+            raise ValueError(f"{len(heads)} aesthetic heads for {len(self.towers)} CLIP towers: give one head or None per tower")
+        scales = [float(v) for v in scales] if isinstance(scales, (list, tuple)) else [float(scales)] * len(heads)
+        if len(scales) != len(heads):
+            raise ValueError(f"{len(scales)} aesthetic scales for {len(heads)} heads: give one float, or one per tower")
+        out = []
+        for k, (head, scale, tower) in enumerate(zip(heads, scales, self.towers)):
+            if head is None or scale == 0:
+                out.append(None)
+                continue
+            if not math.isfinite(scale):
+                raise ValueError(f"aesthetic_scale of tower {k} must be finite, got {scale}")
+            vec, dim = head.vec, int(head.dim)
+            if vec is None or vec.numel() != dim + 1:
+                raise ValueError(f"aesthetic head of tower {k}: expected a loaded (dim + 1,) vector")
+            if dim != tower.out_dim:
+                raise ValueError(f"the aesthetic head of tower {k} is for {dim}-wide embeddings, the tower gives {tower.out_dim}")
+            out.append((vec.detach().float().flatten().contiguous(), scale))
+        return out if any(a is not None for a in out) else None
+
     def _b(self, name, shape, device, dtype=th.float32):
         t = self._buf.get(name)
         if t is None or tuple(t.shape) != tuple(shape) or t.device != device:
@@ -812,7 +848,7 @@ class ClipGuidance:
         wm = self._wm.get(B)
         if wm is None and self.dirs_list is not None:
             wm = self._split_weight_matrix(B, dev)
-        if wm is None and not self.no_clip:
+        if wm is None and not self.no_clip and self.weights.numel() > 0:  # (no prompt at all: the CLIP leg runs for the aesthetic heads alone)
             if self.shard is None:
                 wm = prompt_weight_matrix(self.weights.cpu(), B, dev)
             else:  # the B <-> P broadcast rule is decided on the GLOBAL batch (sample b <-> prompt b when B == P)
@@ -905,8 +941,13 @@ class ClipGuidance:
 
     # -- directional loss ------------------------------------------------------------------------------
     def _clip_kinds(self):
-        """Partial-loss rows per (tower, cut, sample): 2 when target prompts and direction prompts are both present, else 1."""
-        return 2 if self.dirs_list is not None and self.targets_list[0].shape[0] > 0 else 1
+        """Partial-loss rows per (tower, cut, sample): one for each kind of CLIP term that is present, in the order spherical (target prompts),
+        directional (direction prompts), aesthetic (a head on any tower); 1 without directions and heads, as ever."""
+        return self._has_targets() + int(self.dirs_list is not None) + int(self.aes_list is not None)
+
+    def _has_targets(self):
+        """1 when the spherical launch is made: with target prompts, and (as ever) in a leg that has neither directions nor heads."""
+        return int(self.targets_list[0].shape[0] > 0 or (self.dirs_list is None and self.aes_list is None))
 
     def _split_weight_matrix(self, B, dev):
         """The B x P matrix of prompt_weight_matrix over targets and directions together (the B <-> P pairing rule sees the whole list,
@@ -923,6 +964,14 @@ class ClipGuidance:
             m = prompt_weight_matrix(full, self.shard[1], dev)[self.shard[0]]
         self._wm[B], self._wmd[B] = m[:, tcols].contiguous(), m[:, cols].contiguous()
         return self._wm[B]
+
+    def _aes_head_on(self, k, dev):
+        """Tower k's (D + 1,) head vector on the device (moved there once)."""
+        vec, scale = self.aes_list[k]
+        if vec.device != dev:
+            vec = vec.to(dev)
+            self.aes_list[k] = (vec, scale)
+        return vec
 
     def _direction_source_on(self, dev, B, H, W):
         """The source image on the device, (1 or B, 3, H, W): a (1, ...) source is shared by all samples, one with the run's global batch
@@ -960,7 +1009,9 @@ class ClipGuidance:
         prompts, and the directional loss follows it, accumulating onto the spherical gradient when that ran; partials: per tower the
         spherical rows (if any), then the directional rows.  With cached_cutouts the boxes do not change, and the source embeddings of
         a cut count are computed once.  With a region plan both losses go through their `_regions` entries, which read this step's boxes from
-        the cutter's uploaded table; without one the plain entries are called as ever.  _clip_leg_torch is the same leg with autograd."""
+        the cutter's uploaded table; without one the plain entries are called as ever.  With aesthetic heads the aesthetic launch of a tower
+        that has one comes last, accumulating iff one of the other two ran; its partials are the last rows of every tower (zeros for a tower
+        without a head), and a head sees no region weight.  _clip_leg_torch is the same leg with autograd."""
         ctx, lib = self.ctx, self.ctx.lib
         B, _, H, W = x_in.shape
         dev = x_in.device
@@ -975,9 +1026,16 @@ class ClipGuidance:
             hit = self._src_emb.get((cutn, B)) if self.cached_cutouts else None
             src_embs = hit[1] if hit is not None and hit[0] == boxes else None
             fresh = []
-        kinds = self._clip_kinds()
+        kinds, has_t = self._clip_kinds(), self._has_targets()
+        aes_list = self.aes_list
+        if aes_list is not None:  # one row of predicted scores per head, for the log
+            self.aes_score = self._b("aes_score", (sum(a is not None for a in aes_list), N), dev)
+            heads_done = 0
         acc = accumulate
         for k, (tower, targets) in enumerate(zip(self.towers, self.targets_list)):
+            if aes_list is not None and aes_list[k] is None and not has_t and dirs_list is None:
+                clip_part[k * N * kinds:(k + 1) * N * kinds].zero_()  # heads only, and none on this tower: it has no term and is not run
+                continue
             cut = cuts.per_tower()
             cs, patch = tower.input_resolution, tower.patch
             if dirs_list is not None and src_embs is None:
@@ -990,7 +1048,6 @@ class ClipGuidance:
             emb = tower.encode_image(clip_in, layout=layout, n=N, out=self._b(f"emb{k}", (N, tower.out_dim), dev))
             demb = self._b(f"demb{k}", (N, tower.out_dim), dev)
             part = clip_part[k * N * kinds:]
-            has_t = int(dirs_list is None or targets.shape[0] > 0)
             if has_t and self.regions is not None:
                 ctx.check(lib.cgd_spherical_loss_regions(ctx.h, emb.data_ptr(), targets.data_ptr(), wm.data_ptr(), demb.data_ptr(), part.data_ptr(),
                                                          cutn, B, targets.shape[0], tower.out_dim, self.cgs, *self._reg_t.args(cuts.geo), s))
@@ -1005,6 +1062,16 @@ class ClipGuidance:
                     ctx.check(lib.cgd_directional_loss_regions(*dir_args, *self._reg_d.args(cuts.geo), s))
                 else:
                     ctx.check(lib.cgd_directional_loss(*dir_args, s))
+            if aes_list is not None:
+                rows = part[N * (kinds - 1):N * kinds]
+                if aes_list[k] is None:  # a tower without a head: zeros in its aesthetic rows
+                    rows.zero_()
+                else:
+                    head = self._aes_head_on(k, dev)
+                    ctx.check(lib.cgd_aesthetic_loss(ctx.h, emb.data_ptr(), head.data_ptr(), demb.data_ptr(), rows.data_ptr(),
+                                                     self.aes_score[heads_done].data_ptr(), cutn, B, tower.out_dim, aes_list[k][1],
+                                                     int(bool(has_t or dirs_list is not None)), s))
+                    heads_done += 1
             dclip_in = tower.dgrad(demb, self._b(f"dclip_in{k}", tuple(clip_in.shape), dev))
             cut.backward(ctx, dclip_in, gclip, cs, layout, patch, acc)
             acc = 1
@@ -1018,14 +1085,19 @@ class ClipGuidance:
         it follows the reference recipe (cgd.py:190-204) with torch autograd — the cutouts (cuts.torch_cuts) and the normalisation in torch
         ops, the CLIP tower as the autograd node over cgd_*_forward / _dgrad, both losses in torch ops — and hands d(CLIP loss)/dx_in to
         the native chain.  Same draws, in the same order, as the native leg; the source forward runs first here too.  clip_part gets
-        each tower's spherical total in the first of its spherical rows and its directional total in the first of its directional rows."""
+        each tower's spherical total in the first of its spherical rows, its directional total in the first of its directional rows and its
+        aesthetic total in the first of its aesthetic rows; the heads' scores go to aes_score as in the native leg."""
         from .nets import EncodeImageFunction
         B, _, H, W = x_in.shape
         dev = x_in.device
         mean, std = _clip_mean_std(dev)
         n = len(cuts.coords)
         N = n * B
-        kinds = self._clip_kinds()
+        kinds, has_t = self._clip_kinds(), self._has_targets()
+        aes_list = self.aes_list
+        if aes_list is not None:
+            self.aes_score = self._b("aes_score", (sum(a is not None for a in aes_list), N), dev)
+            heads_done = 0
         if self.dirs_list is not None:
             src = self._direction_source_on(dev, B, H, W)
         wm3 = wm.view(1, B, -1) if wm is not None else None
@@ -1046,7 +1118,8 @@ class ClipGuidance:
             xr = x_in.detach().requires_grad_()
             total = 0
             for k, (tower, targets) in enumerate(zip(self.towers, self.targets_list)):
-                has_t = int(self.dirs_list is None or targets.shape[0] > 0)
+                if aes_list is not None and aes_list[k] is None and not has_t and self.dirs_list is None:
+                    continue  # heads only, and none on this tower
                 if self.dirs_list is not None:
                     with th.no_grad():
                         sn = F.normalize(tower.encode_image(clip_cuts(src, tower.input_resolution)).clone().view(n, src.shape[0], -1), dim=-1)
@@ -1065,6 +1138,14 @@ class ClipGuidance:
                     l_sph = (d * wm3).sum(2).mean(0).sum() * self.cgs
                     total = total + l_sph
                     clip_part[k * N * kinds] = l_sph.detach()
+                if aes_list is not None and aes_list[k] is not None:
+                    head = self._aes_head_on(k, dev)
+                    score = en @ head[:-1] + head[-1]  # (n, B)
+                    l_aes = score.mean(0).sum() * -aes_list[k][1]
+                    total = total + l_aes
+                    clip_part[k * N * kinds + N * (kinds - 1)] = l_aes.detach()
+                    self.aes_score[heads_done] = score.detach().reshape(N)
+                    heads_done += 1
                 if k == 0:
                     self.emb = emb.detach().view(N, -1)
             g_in, = th.autograd.grad(total, xr)
@@ -1083,10 +1164,17 @@ class ClipGuidance:
             snap["classifier"] = HostCopy(self.classifier_logp.clone())
         if self.dirs_list is not None:
             snap["direction"] = HostCopy(self.clip_part.clone())
+        if self.aes_list is not None:
+            snap["aesthetic"] = snap["direction"] if "direction" in snap else HostCopy(self.clip_part.clone())  # one copy of the partials
+            snap["aesthetic_score"] = HostCopy(self.aes_score.clone())
         return snap
 
     def _direction_share(self, clip_part):
         """The directional rows of the per-tower partials (towers, kinds, N): their sum is the directional share of 'CLIP Loss'."""
+        return float(clip_part.double().view(len(self.towers), self._clip_kinds(), -1)[:, self._has_targets()].sum().item())
+
+    def _aesthetic_share(self, clip_part):
+        """The aesthetic rows of the per-tower partials, the last kind: their sum is the aesthetic share of 'CLIP Loss'."""
         return float(clip_part.double().view(len(self.towers), self._clip_kinds(), -1)[:, -1].sum().item())
 
     def log(self, snapshot=None):
@@ -1096,6 +1184,9 @@ class ClipGuidance:
         out = {"CLIP Loss": v[0], "Range Loss": v[2], "TV Loss": v[1]}
         if self.dirs_list is not None:  # already part of 'CLIP Loss' and 'Total Loss' (cgd_scalars sums every partial row)
             out["Direction Loss"] = self._direction_share(snapshot["direction"].get() if snapshot is not None else self.clip_part)
+        if self.aes_list is not None:  # likewise part of 'CLIP Loss'; the score is the mean over cuts, samples and heads
+            out["Aesthetic Loss"] = self._aesthetic_share(snapshot["aesthetic"].get() if snapshot is not None else self.clip_part)
+            out["Aesthetic Score"] = float((snapshot["aesthetic_score"].get() if snapshot is not None else self.aes_score).double().mean().item())
         if self.sats != 0:
             out["Saturation Loss"] = v[3]
         out["Total Loss"] = v[4]

@@ -202,6 +202,7 @@ _SIGS = {
     "cgd_spherical_loss_regions": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "cgd_directional_loss_regions": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "cgd_op_region_coverage": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "cgd_aesthetic_loss": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp]),
     "cgd_pmv_blend": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), vp]),
     "cgd_guidance_part_blocks": (i32, [i32, i32, i32]),
     "cgd_guidance_combine": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(StepCoef), f32, f32, f32, vp]),

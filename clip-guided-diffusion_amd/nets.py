@@ -621,6 +621,79 @@ class SecondaryModel(_Net):
         self.ctx.check(self.ctx.lib.cgd_secondary_debug_replay(self.h, arr))
 
 
+def collapse_aesthetic_state_dict(sd):
+    """A published aesthetic-predictor checkpoint -> the (D + 1,) float64 host vector (a, beta) with score = a . normalize(e) + beta.  Two
+    formats, written from memory of the upstream repositories and therefore cross-checked shape by shape here:
+      LAION-AI/aesthetic-predictor (sa_0_4_vit_b_32_linear.pth, ..._b_16_..., ..._l_14_...): the state dict of nn.Linear(D, 1), `weight` (1, D)
+        and `bias` (1,);
+      improved-aesthetic-predictor (sac+logos+ava1-l14-linearMSE.pth and siblings): `layers.{0,2,4,6,7}.weight` / `.bias` of the chain
+        768 -> 1024 -> 128 -> 64 -> 16 -> 1 with only dropout in between, which is the identity at inference: no active non-linearity.
+    The rule is the general one, not the key list: the 2-D `*.weight` tensors in key order must chain (each one's input width is the one
+    before's output width) from some D down to 1, every one with a `*.bias` of its output width (or none); the chain is collapsed in float64,
+    a = W_n ... W_1 and beta chained likewise.  A {'state_dict': ...} wrapper and `module.` prefixes are removed.  ValueError names what does
+    not fit; any tensor that is neither such a weight nor its bias is refused too (a layer this rule would drop silently)."""
+    if isinstance(sd, dict) and isinstance(sd.get("state_dict"), dict):
+        sd = sd["state_dict"]
+    if not isinstance(sd, dict):
+        raise ValueError(f"aesthetic head: expected a state dict, got {type(sd).__name__}")
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items() if isinstance(v, th.Tensor)}
+    names = [k for k in sd if (k == "weight" or k.endswith(".weight")) and sd[k].dim() == 2]
+    if not names:
+        raise ValueError(f"aesthetic head: no 2-D '*.weight' tensor among {sorted(sd)[:8]}")
+    used = set(names)
+    a, beta = None, None
+    for k in names:
+        w = sd[k].detach().double().cpu()
+        bias_key = k[:-len("weight")] + "bias"
+        b = sd.get(bias_key)
+        if b is not None:
+            used.add(bias_key)
+            b = b.detach().double().cpu().flatten()
+            if b.numel() != w.shape[0]:
+                raise ValueError(f"aesthetic head: '{bias_key}' has {b.numel()} elements, '{k}' has {w.shape[0]} outputs")
+        else:
+            b = th.zeros(w.shape[0], dtype=th.float64)
+        if a is None:
+            a, beta = w, b
+        else:
+            if w.shape[1] != a.shape[0]:
+                raise ValueError(f"aesthetic head: broken chain, '{k}' takes {w.shape[1]} inputs but the layer before it gives {a.shape[0]}")
+            a, beta = w @ a, w @ beta + b
+    if a.shape[0] != 1:
+        raise ValueError(f"aesthetic head: the chain ends in {a.shape[0]} outputs, not in 1 score")
+    extra = sorted(set(sd) - used)
+    if extra:
+        raise ValueError(f"aesthetic head: tensors that are no linear layer of the chain: {extra[:8]}")
+    return th.cat([a.flatten(), beta.flatten()])
+
+
+class AestheticHead:
+    """An aesthetic predictor on a tower's image embeddings as the guidance uses it (csrc/aesthetic.hip): `vec`, one (dim + 1,) fp32 device
+    tensor holding a (dim) and then beta, score = a . normalize(e) + beta.  Built from a checkpoint's state dict (`from_state_dict`, the two
+    formats of collapse_aesthetic_state_dict) or loaded like a network handle (param_specs / load_state_dict with the one entry 'head':
+    shard.load_broadcast then reads on rank 0 and broadcasts)."""
+
+    def __init__(self, dim, device="cuda"):
+        self.dim, self.device, self.vec = int(dim), device, None
+        if self.dim < 1:
+            raise ValueError(f"aesthetic head: dim must be positive, got {dim}")
+
+    def param_specs(self):
+        return [("head", self.dim + 1)]
+
+    def load_state_dict(self, sd, prefix=""):
+        v = sd[prefix + "head"].flatten()
+        if v.numel() != self.dim + 1:
+            raise ValueError(f"aesthetic head: {v.numel()} values for dim {self.dim} (expected dim + 1)")
+        self.vec = v.to(device=self.device, dtype=th.float32).contiguous()
+        return self
+
+    @classmethod
+    def from_state_dict(cls, sd, device="cuda"):
+        v = collapse_aesthetic_state_dict(sd)
+        return cls(v.numel() - 1, device).load_state_dict({"head": v})
+
+
 CLASSIFIER_CONFIGS = {
     # guided-diffusion's create_classifier defaults by image size (64x64_classifier.pt ... 512x512_classifier.pt): width 128, depth 2 (4 at
     # 64x64), attention at resolutions 32,16,8, 64-channel heads, the UNet's channel_mult by size, 1000 classes.  Written from the published

@@ -150,3 +150,10 @@ def classifier_state_dict(cfg, seed=8642, device="cpu"):
             t = (th.rand(numel, generator=g) * 2 - 1) * (3.0 / _fan_in(name, numel, specs)) ** 0.5
         sd[name] = t.to(device)
     return sd
+
+
+def aesthetic_head(dim, seed=1357, device="cpu"):
+    """Seeded stand-in for an aesthetic predictor on `dim`-wide embeddings (`nets.AestheticHead`) under its one state-dict name: a ~ N(0, 1)
+    per element, so that a . normalize(e) is of order 1 like the spread of a trained head's scores, and beta = 5, the middle of their 1-10 scale."""
+    g = th.Generator().manual_seed(seed + int(dim))
+    return {"head": th.cat([th.randn(int(dim), generator=g), th.tensor([5.0])]).to(device)}

@@ -395,6 +395,19 @@ int cgd_directional_loss_regions(cgd_ctx* ctx, const float* emb, const float* sr
 int cgd_op_region_coverage(cgd_ctx* ctx, const int32_t* sat, const int32_t* region_of, const int32_t* region_of_host, const float* power,
                            const int32_t* geo, float* out, int cutn, int P, int R, int H, int W, void* stream);
 
+/* ---- aesthetic-predictor guidance (the LAION aesthetic predictors on the CLIP image embedding), with its gradient.  emb (cutn*B, D)
+ *      row = cut*B+b; head (D + 1): the predictor collapsed to one vector a (D) followed by its bias beta.  With e^ = e / max(|e|, 1e-12),
+ *      s = a . e^ + beta (the predicted score of the cutout) and c = scale / cutn:
+ *          loss_part[cut*B+b] = -c s        score[cut*B+b] = s  (score may be NULL: it is then not written)
+ *      and d_emb (cutn*B, D) is set to (accumulate 0: every element is written) or increased by (accumulate 1: the spherical or directional
+ *      launch of the same step wrote it; one float addition per element) d loss_part / d emb = -c (a - (a . e^) e^) / max(|e|, 1e-12).
+ *      A row of exact zeros has s = beta and no gradient: zero bits under accumulate 0, left untouched under accumulate 1.  scale may be
+ *      negative (steers away from what the predictor rates highly).  One wavefront per row, reductions in a fixed order: repeated calls are
+ *      bit-identical.  D > 2048, a count below 1, or a null emb, head, d_emb or loss_part fail with -2 before any launch
+ *      (and before the context is needed: without one a well-formed call returns -3). ---- */
+int cgd_aesthetic_loss(cgd_ctx* ctx, const float* emb, const float* head, float* d_emb, float* loss_part, float* score, int cutn, int B,
+                       int D, float scale, int accumulate, void* stream);
+
 /* per-timestep scalars of the (respaced) diffusion process, float64 tables evaluated on the host */
 typedef struct cgd_step_coef {
   float sqrt_recip;             /* sqrt(1/abar_t)                                  */

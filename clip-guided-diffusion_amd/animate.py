@@ -170,7 +170,8 @@ def _check(frames, border, interp, frames_skip, frames_scale, color_match, promp
             if abs(sum(script_util.parse_prompt(t)[1] for t in texts) + 0.0) < 1e-3 and not kw.get("image_prompts"):
                 raise ValueError(f"prompts_at[{frame}]: the weights must not sum to 0")
     # how many steps the run has, from the tables alone (the suffixes of the spacing are the generator's to judge)
-    spacing = script_util.split_threshold(script_util.split_windows(kw.get("timestep_respacing", "1000"))[0])[0]
+    spacing = script_util.split_model(kw.get("timestep_respacing", "1000"))[0]  # '+model=' is the last suffix and comes off first
+    spacing = script_util.split_threshold(script_util.split_windows(spacing)[0])[0]
     steps = dd.create_gaussian_diffusion(kw.get("diffusion_steps", 1000), kw.get("noise_schedule", "linear"), spacing).num_timesteps
     if frames > 1 and round(frames_skip * steps) >= steps:
         raise ValueError(f"frames_skip {frames_skip} leaves no step of the {steps} for the frames after the first")
@@ -193,7 +194,7 @@ def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, b
 
     Refused before anything is loaded (ValueError): an init_image with '::MASK', 'invert=', 'upsample=' or 'ilvrN=', 'SOURCE=>TARGET'
     prompts, use_augs, a world size above 1, frames < 1, frames_skip outside [0, 1) or so high that no step is left, and prompts_at together
-    with region prompts.  Everything else in `cgd_kwargs` passes through: samplers, '+thr=', '+windows=', 'cuts=', regions, style,
+    with region prompts.  Everything else in `cgd_kwargs` passes through: samplers, '+thr=', '+windows=', '+model=', 'cuts=', regions, style,
     secondary, classifier."""
     import torch as th
 

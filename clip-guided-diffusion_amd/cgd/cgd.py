@@ -132,7 +132,13 @@ def prepare_run(image_size=128, num_cutouts=16, prompts=[], image_prompts=[], cl
         print(f"device: {device}")
     if "cuda" not in device:
         raise ValueError(f"device {device!r}: this build runs the sampling step on an MI355X only (PyTorch-ROCm reports 'cuda')")
-    # "...+windows=STRIDE[:wrapx|:wrapy|:wrap][:feather]" (an extension like "plmsN", the last suffix): windowed sampling, the model runs on
+    # "...+model=FILE[:heads=N | :head_channels=N][:new_order]" (an extension like "plmsN", the last suffix of all): a community checkpoint of the
+    # classic UNet architecture instead of the published one of image_size; malformed text, a file that is neither known nor given a head count,
+    # a class conditioning that disagrees with a known file and "upsample=" next to it are refused before anything is loaded
+    timestep_respacing, model_spec = script_util.split_model(timestep_respacing)
+    if model_spec is not None:
+        script_util.check_model(model_spec, image_size, class_cond, init_image)
+    # "...+windows=STRIDE[:wrapx|:wrapy|:wrap][:feather]" (likewise, the last suffix among what remains): windowed sampling, the model runs on
     # overlapping image_size windows of the image_size + offsets frame; a bad stride or frame, or a combination with "upsample=", "invert=" or
     # "+classifier=", is refused before anything is loaded
     timestep_respacing, windows_spec = script_util.split_windows(timestep_respacing, image_size, height_offset, width_offset, init_image,
@@ -199,6 +205,8 @@ def prepare_run(image_size=128, num_cutouts=16, prompts=[], image_prompts=[], cl
     Path(checkpoints_dir).mkdir(parents=True, exist_ok=True)
     if upsample:
         diffusion_path = script_util.download_upsampler(image_size, checkpoints_dir)
+    elif model_spec is not None:
+        diffusion_path = None  # a local file (as given or under checkpoints_dir): nothing to download
     else:
         diffusion_path = script_util.download_guided_diffusion(image_size=image_size, checkpoints_dir=checkpoints_dir, class_cond=class_cond)
 
@@ -314,6 +322,10 @@ def prepare_run(image_size=128, num_cutouts=16, prompts=[], image_prompts=[], cl
         gd_model, diffusion = script_util.load_upsampler(
             checkpoint_path=diffusion_path, large_size=image_size, diffusion_steps=diffusion_steps, timestep_respacing=timestep_respacing,
             device=device, noise_schedule=noise_schedule, dropout=dropout)
+    elif model_spec is not None:
+        gd_model, diffusion = script_util.load_community_model(
+            model_spec, image_size=image_size, class_cond=class_cond, diffusion_steps=diffusion_steps, timestep_respacing=timestep_respacing,
+            device=device, noise_schedule=noise_schedule, checkpoints_dir=str(checkpoints_dir))
     else:
         gd_model, diffusion = script_util.load_guided_diffusion(
             checkpoint_path=diffusion_path, image_size=image_size, class_cond=class_cond, diffusion_steps=diffusion_steps,
@@ -420,7 +432,7 @@ _CLI_SPEC = f"""
 --seed -seed int 0 | RNG seed
 --save_frequency -freq int 1 | write a frame every N steps
 --diffusion_steps -steps int 1000 | length of the training schedule
---timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', 'plmsN' for PLMS (e.g. -respace plms50), or 'dpmN' / 'dpmsdeN' for DPM-Solver++(2M) / its SDE form on at most N logSNR-uniform levels (e.g. -respace dpm20); 'dpmN+thr=P' or 'dpmsdeN+thr=P:CAP' adds dynamic thresholding of the guided prediction: per sample it is clamped to its own P-quantile of absolute values s (at least 1, at most CAP) and divided by s (e.g. -respace dpm20+thr=0.995; CAP 1 is the static clip to [-1, 1]); a last suffix '+windows=STRIDE[:wrapx|:wrapy|:wrap][:feather]' (e.g. -respace 250+windows=128:wrapx with --width_offset 256) samples a frame larger than the checkpoint in windows (MultiDiffusion): the model runs on overlapping --image_size windows STRIDE pixels apart (a positive multiple of 8, at most --image_size; frame sides multiples of 8) and their predictions are averaged, with sin^2 weights under :feather; :wrapx / :wrapy / :wrap let windows run over the right / bottom / both edges, so the result tiles seamlessly along that axis (STRIDE must divide its length); not with upsample=, invert= or +classifier=
+--timestep_respacing -respace str 1000 | number of sampling steps ('250'), 'ddimN', 'plmsN' for PLMS (e.g. -respace plms50), or 'dpmN' / 'dpmsdeN' for DPM-Solver++(2M) / its SDE form on at most N logSNR-uniform levels (e.g. -respace dpm20); 'dpmN+thr=P' or 'dpmsdeN+thr=P:CAP' adds dynamic thresholding of the guided prediction: per sample it is clamped to its own P-quantile of absolute values s (at least 1, at most CAP) and divided by s (e.g. -respace dpm20+thr=0.995; CAP 1 is the static clip to [-1, 1]); a last suffix '+windows=STRIDE[:wrapx|:wrapy|:wrap][:feather]' (e.g. -respace 250+windows=128:wrapx with --width_offset 256) samples a frame larger than the checkpoint in windows (MultiDiffusion): the model runs on overlapping --image_size windows STRIDE pixels apart (a positive multiple of 8, at most --image_size; frame sides multiples of 8) and their predictions are averaged, with sin^2 weights under :feather; :wrapx / :wrapy / :wrap let windows run over the right / bottom / both edges, so the result tiles seamlessly along that axis (STRIDE must divide its length); not with upsample=, invert= or +classifier=; behind everything else, '+model=FILE[:heads=N|:head_channels=N][:new_order]' (e.g. -respace ddim100+model=pixel_art_diffusion_hard_256.pt with --uncond) samples with a community checkpoint of the classic UNet architecture, FILE as given or under --checkpoints_dir: the architecture is read from the file's tensor shapes, the head count from the table of known files or from heads= / head_channels=; not with upsample=
 --num_cutouts -cutn int 16 | random cutouts shown to CLIP per step
 --cutout_power -cutpow float 1.0 | exponent of the cutout size distribution
 --clip_model -clip str ViT-B/32 | one of {clip_util.CLIP_MODEL_NAMES}, a checkpoint file, ARCH=FILE for an open_clip ViT checkpoint (ARCH: ViT-B-32, ViT-B-16, ViT-L-14, ViT-H-14, optional -quickgelu suffix), 'A+B' to sum two towers, 'A+secondary=FILE' to guide through the secondary model FILE, 'A+classifier=FILE:CLASS[:SCALE]' for classifier guidance toward ImageNet class CLASS with the noisy classifier FILE (weight SCALE, default 1; with a class-conditional model y is held at CLASS; needs zero height / width offsets), 'A+aesthetic=FILE:SCALE' to add the LAION aesthetic predictor FILE (the linear sa_0_4_vit_*_linear.pth heads or the five-layer improved-aesthetic-predictor ones, whose embedding width must be tower A's) on the embeddings of the tower entry before it: the loss gains -SCALE times the mean predicted score of the cutouts, a negative SCALE steers away, each tower takes at most one (the list is split on '+': a checkpoint whose own name contains '+', as sac+logos+ava1-l14-linearMSE.pth does, has to be renamed or symlinked), or 'A+cuts=OV:IN' (or 'cuts=OV:IN/OV2:IN2': the second pair once 40 percent of the run is done) for OV whole-frame and IN random cutouts per step through the antialiased cubic resize (--num_cutouts then only affects image prompts)

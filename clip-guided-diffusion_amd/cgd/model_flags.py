@@ -48,6 +48,27 @@ UPSAMPLER_LOOKUP = {
     512: _upsampler(512, 128, attention_resolutions="32,16", num_head_channels=64),
 }
 
+def _community(filename, **delta):
+    # the classic architecture: conv down / upsampling (resblock_updown False) and, for most fine-tunes, additive timestep embeddings
+    flags = dict(_BASE, class_cond=False, image_size=256, num_channels=128, num_res_blocks=2, attention_resolutions="16", num_heads=1,
+                 num_head_channels=-1, resblock_updown=False, use_scale_shift_norm=False, use_new_attention_order=False)
+    flags.update(delta)
+    return {"filename": filename, "model_flags": flags}
+
+
+# Community fine-tunes trained from improved-diffusion / guided-diffusion DEFAULTS, selected with '+model=FILE' on --timestep_respacing
+# (script_util.split_model), keyed by file basename.  A hit supplies what no tensor shape shows: the head count.  Written from memory of the
+# flags Disco Diffusion sets for these files; no checkpoint was at hand to confirm them, so only entries that can be stated with confidence
+# are listed, and script_util.load_community_model compares every shape of a loaded state dict with the manifest these flags give and
+# refuses a mismatch by name (as for UPSAMPLER_LOOKUP).  Other files load with '+model=FILE:heads=N' or ':head_channels=N'.
+COMMUNITY_LOOKUP = {
+    name: _community(name) for name in (
+        "256x256_openai_comics_faces_by_alex_spirin_084000.pt",
+        "pixel_art_diffusion_hard_256.pt",
+        "pixel_art_diffusion_soft_256.pt",
+    )
+}
+
 # upstream guided_diffusion.script_util.model_and_diffusion_defaults()
 MODEL_AND_DIFFUSION_DEFAULTS = dict(
     image_size=64, num_channels=128, num_res_blocks=2, num_heads=4, num_heads_upsample=-1, num_head_channels=-1,

@@ -592,6 +592,271 @@ def load_guided_diffusion(checkpoint_path: str, image_size: int, class_cond: boo
     return model, _sampler.GuidedSampler(ctx, tables)
 
 
+MODEL_SEP = "+model="
+
+
+def split_model(respacing):
+    """'ddim100+model=FILE[:heads=N | :head_channels=N][:new_order]' -> (the spacing without the suffix, (FILE, heads, head_channels,
+    new_order)) with None for an option not given; a value without '+model=' -> (value, None).  A community checkpoint of the classic UNet
+    architecture (COMMUNITY_LOOKUP, unet_flags_from_state_dict) rides on --timestep_respacing / timestep_respacing= as its LAST suffix, split
+    off before split_windows; what is returned still carries '+windows=' / '+thr='.  The head count and the attention order change the output
+    and show in no tensor shape: they come from the table (by FILE's basename) or from these options.  Malformed text is refused here, before
+    anything is loaded."""
+    respacing = str(respacing)
+    spec, sep, value = respacing.partition(MODEL_SEP)
+    if not sep:
+        return respacing, None
+    usage = (f"timestep_respacing {respacing!r}: '+model=' takes FILE[:heads=N | :head_channels=N][:new_order] "
+             "(e.g. ddim100+model=pixel_art_diffusion_hard_256.pt or 250+model=mine.pt:heads=4)")
+    if not spec:
+        raise ValueError(usage)
+    if "+" in value and any(s in value for s in (MODEL_SEP, WINDOWS_SEP, THRESHOLD_SEP)):
+        raise ValueError(f"timestep_respacing {respacing!r}: '+model=' is the last suffix ('+thr=' and '+windows=' come before it)")
+    parts = value.split(":")
+    file, heads, head_channels, new_order = parts[0], None, None, False
+    if not file:
+        raise ValueError(usage)
+    for opt in parts[1:]:
+        key, eq, num = opt.partition("=")
+        if opt == "new_order" and not new_order:
+            new_order = True
+        elif key in ("heads", "head_channels") and eq and num.isdigit() and int(num) > 0 and heads is None and head_channels is None:
+            heads, head_channels = (int(num), None) if key == "heads" else (None, int(num))
+        else:
+            raise ValueError(usage)
+    return spec, (file, heads, head_channels, new_order)
+
+
+def unwrap_state_dict(sd, what="checkpoint"):
+    """What th.load gave -> the flat {name: tensor} state dict: a {'state_dict': {...}} or {'model': {...}} wrapper (training scripts save
+    those) is opened; anything that is then no mapping of names to tensors is refused by the name of the first offending entry."""
+    for key in ("state_dict", "model"):
+        if isinstance(sd, dict) and key in sd and isinstance(sd[key], dict) and not th.is_tensor(sd[key]):
+            sd = sd[key]
+    if not isinstance(sd, dict) or not sd:
+        raise ValueError(f"{what}: th.load gave a {type(sd).__name__}, not a state dict")
+    for name, v in sd.items():
+        if not th.is_tensor(v):
+            raise ValueError(f"{what}: entry {name!r} is a {type(v).__name__}, not a tensor: no plain state dict")
+    return sd
+
+
+def _shape(sd, name, dims=None):
+    if name not in sd:
+        raise ValueError(f"{name}: the checkpoint has no such tensor; it is no guided-diffusion / improved-diffusion UNet this build supports")
+    shape = tuple(sd[name].shape)
+    if dims is not None and len(shape) != dims:
+        raise ValueError(f"{name}: expected {dims} dimensions, got shape {shape}")
+    return shape
+
+
+def unet_flags_from_state_dict(sd, image_size):
+    """The create_model flags a UNet state dict reveals, from its tensor SHAPES alone: num_channels (from time_embed.0.weight: the 512 model's
+    stem is half as wide), channel_mult and num_res_blocks (from the widths and the grouping of the output blocks), attention_resolutions
+    (which input blocks hold a '.norm.weight'), resblock_updown (no '.op.weight'), use_scale_shift_norm (rows of emb_layers.1.weight against
+    the block's width), class_cond (label_emb.weight), learn_sigma (rows of out.2.weight) and in_channels.  The head count, the attention
+    order and the noise schedule show in no shape.  Raises ValueError naming the tensor for anything that fits no supported architecture:
+    learn_sigma=False (a 3-row out.2) among them, which the sampler's variance blend does not cover."""
+    ted, mc = _shape(sd, "time_embed.0.weight", 2)
+    if mc <= 0 or ted != 4 * mc or mc % 32:
+        raise ValueError(f"time_embed.0.weight: shape {(ted, mc)} is no [4 * num_channels, num_channels] with num_channels a multiple of 32")
+    stem = _shape(sd, "input_blocks.0.0.weight", 4)
+    if stem[1] not in (3, 6) or stem[2:] != (3, 3):
+        raise ValueError(f"input_blocks.0.0.weight: shape {stem} is no 3x3 stem over 3 (or, super-resolution, 6) channels")
+    head = _shape(sd, "out.2.weight", 4)
+    if head[0] == 3:
+        raise ValueError("out.2.weight: 3 output channels, a learn_sigma=False model; only learn_sigma=True checkpoints (6 channels) are supported")
+    if head[0] != 6 or head[1] != stem[0]:
+        raise ValueError(f"out.2.weight: shape {head} is no [6, {stem[0]}, 3, 3] head")
+    # levels from the output blocks: the last block of every level but the final one ends in the upsampler, a second ResBlock
+    # (resblock_updown) or a '.conv' (the classic Upsample)
+    widths, per_level, count, k = [], [], 0, 0
+    while f"output_blocks.{k}.0.in_layers.2.weight" in sd:
+        pre = f"output_blocks.{k}"
+        width = _shape(sd, f"{pre}.0.in_layers.2.weight", 4)[0]
+        count += 1
+        ends = any(f"{pre}.{j}.conv.weight" in sd or f"{pre}.{j}.in_layers.2.weight" in sd for j in (1, 2))
+        if ends:
+            widths.append(width)
+            per_level.append(count)
+            count = 0
+        k += 1
+    if k == 0:
+        raise ValueError("output_blocks.0.0.in_layers.2.weight: the checkpoint has no such tensor; it is no UNet this build supports")
+    widths.append(_shape(sd, f"output_blocks.{k - 1}.0.in_layers.2.weight", 4)[0])
+    per_level.append(count)
+    if len(set(per_level)) != 1 or per_level[0] < 2:
+        raise ValueError(f"output_blocks.{k - 1}.0.in_layers.2.weight: the output blocks group into levels of {per_level} blocks, not into equal "
+                         "levels of num_res_blocks + 1")
+    num_res_blocks, widths = per_level[0] - 1, widths[::-1]
+    mult = []
+    for level, w in enumerate(widths):
+        m = w / mc
+        if w % 32 or m <= 0:
+            raise ValueError(f"output_blocks: level {level} is {w} channels wide, no multiple of 32")
+        mult.append(int(m) if m == int(m) else m)
+    if widths[0] != stem[0]:
+        raise ValueError(f"input_blocks.0.0.weight: the stem is {stem[0]} channels wide, the last output level {widths[0]}")
+    # the input side must be the mirror of that plan
+    classic = any(name.endswith(".0.op.weight") for name in sd)
+    att_ds, idx = [], 1
+    for level, w in enumerate(widths):
+        flags_here = set()
+        for _ in range(num_res_blocks):
+            got = _shape(sd, f"input_blocks.{idx}.0.in_layers.2.weight", 4)[0]
+            if got != w:
+                raise ValueError(f"input_blocks.{idx}.0.in_layers.2.weight: {got} output channels, the mirrored output level has {w}")
+            flags_here.add(f"input_blocks.{idx}.1.norm.weight" in sd)
+            idx += 1
+        if len(flags_here) != 1:
+            raise ValueError(f"input_blocks.{idx - 1}.1.norm.weight: only some of the blocks of level {level} carry attention")
+        if flags_here.pop():
+            att_ds.append(1 << level)
+        if level != len(widths) - 1:
+            name = f"input_blocks.{idx}.0.op.weight" if classic else f"input_blocks.{idx}.0.in_layers.2.weight"
+            if _shape(sd, name, 4) != (w, w, 3, 3):
+                raise ValueError(f"{name}: shape {tuple(sd[name].shape)} is no [{w}, {w}, 3, 3] downsampler")
+            idx += 1
+    if f"input_blocks.{idx}.0.in_layers.2.weight" in sd or f"input_blocks.{idx}.0.op.weight" in sd:
+        raise ValueError(f"input_blocks.{idx}: more input blocks than the output blocks mirror")
+    if image_size % (1 << (len(widths) - 1)):
+        raise ValueError(f"output_blocks: {len(widths)} levels do not divide image_size {image_size}")
+    rows = _shape(sd, "input_blocks.1.0.emb_layers.1.weight", 2)[0]
+    if rows not in (widths[0], 2 * widths[0]):
+        raise ValueError(f"input_blocks.1.0.emb_layers.1.weight: {rows} rows for a block of {widths[0]} channels: neither an additive embedding "
+                         "nor scale and shift")
+    num_classes = 0
+    if "label_emb.weight" in sd:
+        num_classes, width = _shape(sd, "label_emb.weight", 2)
+        if width != ted or num_classes < 1:
+            raise ValueError(f"label_emb.weight: shape {(num_classes, width)} is no [num_classes, {ted}] class embedding")
+    # attention_resolutions "" = no attention level on the way down (the middle block always attends): nets.UNet.make_config takes it
+    return dict(image_size=image_size, num_channels=mc, num_res_blocks=num_res_blocks, channel_mult=tuple(mult),
+                attention_resolutions=",".join(str(image_size // ds) for ds in att_ds), resblock_updown=not classic,
+                use_scale_shift_norm=rows == 2 * widths[0], class_cond=num_classes > 0, num_classes=num_classes, learn_sigma=True,
+                in_channels=stem[1])
+
+
+SNIFFED_FLAGS = ("num_channels", "num_res_blocks", "attention_resolutions", "resblock_updown", "use_scale_shift_norm", "class_cond", "learn_sigma")
+
+
+def community_flags(model_spec, image_size, class_cond, noise_schedule="linear", sd=None):
+    """The flags of a '+model=' run: the table entry of FILE's basename (COMMUNITY_LOOKUP) or, with `sd`, what the state dict's shapes show,
+    plus the head count and attention order of the options.  Refuses: neither a table hit nor 'heads=' / 'head_channels=' (the head count
+    changes the output and no shape shows it); a table entry of another image_size; a class conditioning that disagrees with the checkpoint;
+    a state dict that contradicts its table entry (by flag); a super-resolution checkpoint."""
+    from .model_flags import COMMUNITY_LOOKUP
+    file, heads, head_channels, new_order = model_spec
+    hit = COMMUNITY_LOOKUP.get(os.path.basename(file))
+    if hit is None and heads is None and head_channels is None:
+        raise ValueError(f"'+model={file}': not among the known checkpoints ({', '.join(sorted(COMMUNITY_LOOKUP))}); give the head count with "
+                         "':heads=N' or ':head_channels=N' (it changes the output and no tensor shape shows it)")
+    if hit is None and sd is None:
+        raise ValueError(f"'+model={file}': with CGD_SYNTHETIC_WEIGHTS=1 the file is not read, so only the known checkpoints work "
+                         f"({', '.join(sorted(COMMUNITY_LOOKUP))})")
+    flags = dict(MODEL_AND_DIFFUSION_DEFAULTS)
+    if hit is not None:
+        flags.update(hit["model_flags"])
+        if flags["image_size"] != image_size:
+            raise ValueError(f"'+model={file}' is a {flags['image_size']} x {flags['image_size']} checkpoint, image_size is {image_size}")
+    if sd is not None:
+        seen = unet_flags_from_state_dict(sd, image_size)
+        if seen["in_channels"] != 3:
+            raise ValueError(f"'+model={file}': input_blocks.0.0.weight takes 6 channels, a super-resolution checkpoint; use init image 'upsample=...'")
+        if hit is not None:
+            for key in SNIFFED_FLAGS:
+                if str(flags[key]).replace(" ", "") != str(seen[key]):
+                    raise ValueError(f"'+model={file}': the checkpoint's shapes give {key}={seen[key]!r}, the table says {flags[key]!r}")
+            default = _nets.DEFAULT_CHANNEL_MULT.get(image_size)
+            if tuple(flags.get("channel_mult") or default or ()) != tuple(seen["channel_mult"]):
+                raise ValueError(f"'+model={file}': the checkpoint's shapes give channel_mult={seen['channel_mult']!r}, the table says "
+                                 f"{tuple(flags.get('channel_mult') or default or ())!r}")
+        flags.update(seen)
+    elif not flags.get("channel_mult"):
+        flags["channel_mult"] = _nets.DEFAULT_CHANNEL_MULT[image_size]
+    if bool(flags["class_cond"]) != bool(class_cond):
+        raise ValueError(f"'+model={file}' is {'class-conditional' if flags['class_cond'] else 'unconditional'}: run it "
+                         f"{'without' if flags['class_cond'] else 'with'} --uncond")
+    if heads is not None:
+        flags.update(num_heads=heads, num_head_channels=-1)
+    if head_channels is not None:
+        flags.update(num_head_channels=head_channels)
+    if new_order:
+        flags["use_new_attention_order"] = True
+    flags["noise_schedule"] = noise_schedule
+    return flags
+
+
+def community_unet_kwargs(flags):
+    """community_flags -> the device UNet's constructor arguments"""
+    return dict(image_size=flags["image_size"], model_channels=flags["num_channels"], num_res_blocks=flags["num_res_blocks"],
+                attention_resolutions=str(flags["attention_resolutions"]).replace(" ", ""), channel_mult=tuple(flags["channel_mult"]),
+                num_classes=(flags.get("num_classes") or 1000) if flags["class_cond"] else None, num_heads=flags["num_heads"],
+                num_head_channels=flags["num_head_channels"],
+                use_new_attention_order=flags["use_new_attention_order"], out_channels=6, resblock_updown=flags["resblock_updown"],
+                use_scale_shift_norm=flags["use_scale_shift_norm"])
+
+
+def check_model(model_spec, image_size, class_cond, init_image=None):
+    """What a '+model=' run refuses before anything is loaded: a file that is neither known nor given a head count (community_flags, for a
+    known file also its size and class conditioning), and init image 'upsample=' (that run loads the super-resolution checkpoint instead)."""
+    from .model_flags import COMMUNITY_LOOKUP
+    file = model_spec[0]
+    if init_image and split_init_mask(init_image)[0].startswith(UPSAMPLE_PREFIX):
+        raise ValueError(f"'+model={file}' cannot be combined with init image 'upsample=...': that run samples with the super-resolution checkpoint")
+    if os.path.basename(file) in COMMUNITY_LOOKUP:
+        community_flags(model_spec, image_size, class_cond)
+    elif model_spec[1] is None and model_spec[2] is None or synthetic_weights_enabled():
+        community_flags(model_spec, image_size, class_cond)  # raises
+
+
+def check_state_dict(sd, specs, what):
+    """Every tensor of a loaded state dict against the manifest `specs` ([(name, numel)]) of the flags it is loaded under: a missing or
+    unknown key or a wrong element count is a ValueError that names the tensor, before anything is uploaded."""
+    specs = dict(specs)
+    missing = [k for k in specs if k not in sd]
+    if missing:
+        raise ValueError(f"{what}: the checkpoint lacks {len(missing)} tensors its flags expect, first {missing[0]!r}")
+    extra = [k for k in sd if k not in specs]
+    if extra:
+        raise ValueError(f"{what}: the checkpoint has {len(extra)} tensors its flags do not expect, first {extra[0]!r}")
+    for name, numel in specs.items():
+        if sd[name].numel() != numel:
+            raise ValueError(f"{what}: {name} has shape {tuple(sd[name].shape)} ({sd[name].numel()} elements), its flags expect {numel}")
+
+
+@lru_cache(maxsize=1)
+def load_community_model(model_spec, image_size: int, class_cond: bool, diffusion_steps: int = None, timestep_respacing: str = None,
+                         device: str = "", noise_schedule: str = "linear", checkpoints_dir: str = CACHE_PATH):
+    """-> (model, diffusion) like load_guided_diffusion, for the checkpoint a '+model=FILE...' suffix names (split_model's tuple): FILE as
+    given or, when that is no file, under `checkpoints_dir`.  With CGD_SYNTHETIC_WEIGHTS=1 the file is not read: table names only, seeded
+    weights drawn from param_specs."""
+    if not (len(device) > 0):
+        raise ValueError("device must be set")
+    if noise_schedule not in ("linear", "cosine"):
+        raise ValueError("linear_or_cosine must be set")
+    file = model_spec[0]
+    path = file if os.path.isfile(file) else os.path.join(checkpoints_dir, file)
+    ctx = get_context(device)
+    dev = f"cuda:{ctx.device}"
+    if synthetic_weights_enabled():
+        flags = community_flags(model_spec, image_size, class_cond, noise_schedule)
+        model = _nets.UNet(ctx, **community_unet_kwargs(flags))
+        _shard.load_broadcast(model, lambda: _synthetic.synthetic_state_dict(model, seed=1234, device=dev), dev)
+    elif os.path.isfile(path):
+        # every rank reads it: the flags come from its shapes.  (fp16 tensors are fine: the upload converts every tensor to fp32)
+        sd = unwrap_state_dict(th.load(path, map_location="cpu"), os.path.basename(path))
+        flags = community_flags(model_spec, image_size, class_cond, noise_schedule, sd=sd)
+        model = _nets.UNet(ctx, **community_unet_kwargs(flags))
+        check_state_dict(sd, model.param_specs(), os.path.basename(path))
+        _shard.load_broadcast(model, lambda: sd, dev)
+    else:
+        raise FileNotFoundError(f"{path} not found (for a known checkpoint, CGD_SYNTHETIC_WEIGHTS=1 gives seeded random weights)")
+    tables = _diffusion.create_gaussian_diffusion(steps=diffusion_steps or flags["diffusion_steps"], noise_schedule=flags["noise_schedule"],
+                                                  timestep_respacing=timestep_respacing or "", rescale_timesteps=flags["rescale_timesteps"])
+    return model, _sampler.GuidedSampler(ctx, tables)
+
+
 def load_lpips(ctx, checkpoints_dir: str = CACHE_PATH, device="cuda"):
     """Device LPIPS-VGG16 (reference: `lpips.LPIPS(net='vgg')`, cgd.py:147-148).  Weights: `<checkpoints_dir>/lpips_vgg16.pt`, a
     state dict with the package's keys (torchvision VGG16 trunk as `net.slice{k}.{idx}.weight|bias`, heads `lin{k}.model.1.weight`);

@@ -4,6 +4,7 @@
 #include "guidance.h"
 #include "kernels.h"
 #include "mfma_stage.h"
+#include "net.h"
 
 #define S(stream) ((hipStream_t)(stream))
 
@@ -595,6 +596,55 @@ int cgd_op_conv3x3_ex(cgd_ctx* ctx, const float* x, int ldx, const float* w, con
     p.gnb_x = gnb_x; p.gnb_ldx = gnb_ldx; p.gnb_coef = cgd_gn_coef(gnb_scratch, Bn, H * W, Cout); p.gnb_act = 1;
   }
   return cgd_launch_gemm(ctx, p, S(stream));
+}
+// ---- the stride-2 3x3 conv (sconv.hip).  The op entries take the torch weight and pack it per call into the context's scratch copy of a
+// non-persistent operand (stream-ordered reuse, as the forced weight GEMM does); the UNet packs once at finalize.
+static int sconv_pack_tmp(cgd_ctx* ctx, const float* w, int Co, int Ci, int dgrad, float** out, hipStream_t s) {
+  const size_t need = (size_t)Co * Ci * 9 * sizeof(float);
+  if (need > ctx->frag_tmp_bytes) {
+    if (ctx->frag_tmp) {
+      CGD_HIP(ctx, hipStreamSynchronize(s));
+      CGD_HIP(ctx, hipFree(ctx->frag_tmp));
+    }
+    ctx->frag_tmp = nullptr;
+    ctx->frag_tmp_bytes = 0;
+    CGD_HIP(ctx, hipMalloc(&ctx->frag_tmp, need));
+    ctx->frag_tmp_bytes = need;
+  }
+  *out = (float*)ctx->frag_tmp;
+  return cgd_pack_conv3x3(ctx, w, dgrad ? nullptr : *out, dgrad ? *out : nullptr, Co, Ci, s);
+}
+int cgd_op_conv3x3_s2_accepts(int dgrad, int ld_in, int ld_out, int ldadd, int Bn, int H, int W, int Cin, int Cout) {
+  return cgd_sconv_refusal(dgrad, ld_in, ld_out, ldadd, Bn, H, W, Cin, Cout) ? 0 : 1;
+}
+int cgd_op_conv3x3_s2(cgd_ctx* ctx, const float* x, int ldx, const float* w_torch, const float* bias, float* y, int ldy, int Bn, int H, int W,
+                      int Cin, int Cout, void* stream) {
+  CGD_NEED_CTX(ctx);
+  if (const char* why = cgd_sconv_refusal(0, ldx, ldy, 0, Bn, H, W, Cin, Cout)) CGD_FAIL(ctx, why);
+  if (!w_torch) CGD_FAIL(ctx, "cgd_op_conv3x3_s2: the weight is required");
+  float* wf = nullptr;
+  CGD_TRY(sconv_pack_tmp(ctx, w_torch, Cout, Cin, 0, &wf, S(stream)));
+  return cgd_launch_sconv_fwd(ctx, x, ldx, wf, bias, y, ldy, Bn, H, W, Cin, Cout, S(stream));
+}
+int cgd_op_conv3x3_s2_dgrad(cgd_ctx* ctx, const float* dy, int lddy, const float* w_torch, float* dx, int lddx, const float* add, int ldadd,
+                            int Bn, int H, int W, int Cin, int Cout, void* stream) {
+  CGD_NEED_CTX(ctx);
+  if (const char* why = cgd_sconv_refusal(1, lddy, lddx, add ? ldadd : 0, Bn, H, W, Cin, Cout)) CGD_FAIL(ctx, why);
+  if (!w_torch) CGD_FAIL(ctx, "cgd_op_conv3x3_s2_dgrad: the weight is required");
+  float* wd = nullptr;
+  CGD_TRY(sconv_pack_tmp(ctx, w_torch, Cout, Cin, 1, &wd, S(stream)));
+  return cgd_launch_sconv_dgrad(ctx, dy, lddy, wd, dx, lddx, add, ldadd, Bn, H, W, Cin, Cout, S(stream));
+}
+// the same on weights packed once by the caller (what the UNet's Downsample runs per step): w_fwd [Cout][9 Cin], w_dgrad [Cin][9 Cout]
+int cgd_op_conv3x3_s2_packed(cgd_ctx* ctx, const float* x, int ldx, const float* w_fwd, const float* bias, float* y, int ldy, int Bn, int H, int W,
+                             int Cin, int Cout, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_sconv_fwd(ctx, x, ldx, w_fwd, bias, y, ldy, Bn, H, W, Cin, Cout, S(stream));
+}
+int cgd_op_conv3x3_s2_dgrad_packed(cgd_ctx* ctx, const float* dy, int lddy, const float* w_dgrad, float* dx, int lddx, const float* add, int ldadd,
+                                   int Bn, int H, int W, int Cin, int Cout, void* stream) {
+  CGD_NEED_CTX(ctx);
+  return cgd_launch_sconv_dgrad(ctx, dy, lddy, w_dgrad, dx, lddx, add, ldadd, Bn, H, W, Cin, Cout, S(stream));
 }
 int cgd_op_conv_in(cgd_ctx* ctx, const float* x, const float* w, const float* bias, float* y, int Bn, int H, int W, int Cin, int Cout,
                    void* stream) {

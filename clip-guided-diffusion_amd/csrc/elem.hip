@@ -347,3 +347,31 @@ int cgd_launch_fill(cgd_ctx* ctx, float* p, long n, float v, hipStream_t s) {
   CGD_HIP(ctx, hipGetLastError());
   return 0;
 }
+
+// ---- the additive timestep embedding of a classic ResBlock (use_scale_shift_norm = False) ----------------------------------------------
+namespace {
+// h[r][:] += e[r / HW][:]: a per-(sample, channel) vector added to every pixel, in place
+__global__ __launch_bounds__(256) void add_chan_kernel(float* __restrict__ h, int ldh, const float* __restrict__ e, int lde, long rows, int HW, int C) {
+  const int cq = C >> 2;
+  const long total = rows * cq;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int q = (int)(i % cq);
+    const long r = i / cq;
+    const float4 v = *(const float4*)(e + (r / HW) * lde + q * 4);
+    float4 o = *(const float4*)(h + r * ldh + q * 4);
+    o.x += v.x; o.y += v.y; o.z += v.z; o.w += v.w;
+    *(float4*)(h + r * ldh + q * 4) = o;
+  }
+}
+}  // namespace
+
+int cgd_launch_add_chan(cgd_ctx* ctx, float* h, int ldh, const float* e, int lde, int B, int HW, int C, hipStream_t s) {
+  CGD_TRY(cgd_sync_pending(ctx, s));  // reads an activation: a deferred split-K reduction must have landed
+  if (B <= 0 || HW <= 0 || C <= 0 || (C & 3) || (ldh & 3) || (lde & 3)) CGD_FAIL(ctx, "add_chan: B, HW and C must be positive, C and the strides multiples of 4");
+  if (((uintptr_t)h | (uintptr_t)e) & 15) CGD_FAIL(ctx, "add_chan: h and e must be 16-byte aligned");
+  const long rows = (long)B * HW;
+  cgd_chanstats_invalidate(ctx, h, rows, ldh, C);  // statistics taken of h before the addition are not those of the sum
+  CGD_LAUNCH(add_chan_kernel, dim3(elem_grid(rows * (C / 4))), dim3(256), 0, s, h, ldh, e, lde, rows, HW, C);
+  CGD_HIP(ctx, hipGetLastError());
+  return 0;
+}

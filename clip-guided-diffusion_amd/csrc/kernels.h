@@ -66,6 +66,20 @@ int cgd_launch_vit_tokens(cgd_ctx* ctx, const float* patch, const float* cls, co
 int cgd_launch_patchify(cgd_ctx* ctx, const float* img, float* cols, int N, int res, int P, hipStream_t s);
 int cgd_launch_unpatchify(cgd_ctx* ctx, const float* cols, float* img, int N, int res, int P, hipStream_t s);
 int cgd_launch_fill(cgd_ctx* ctx, float* p, long n, float v, hipStream_t s);
+// h[b * HW + i][c] += e[b * lde + c]: a per-(sample, channel) vector added to every pixel, in place (the additive timestep embedding of a
+// classic ResBlock); C, ldh and lde multiples of 4, h and e 16-byte aligned
+int cgd_launch_add_chan(cgd_ctx* ctx, float* h, int ldh, const float* e, int lde, int B, int HW, int C, hipStream_t s);
+
+// ---- sconv.hip: 3x3 convolution of stride 2, padding 1 (the classic UNet's Downsample) and its backward to the input ---------------------
+// nullptr when the launchers below run the problem, else the reason they refuse it (host only).  ld_in: row stride of the gathered operand (x, or
+// dy when dgrad), ld_out: of the written one (y / dx), ldadd: of the backward's add operand (0 = none); B, H, W: the input's
+const char* cgd_sconv_refusal(int dgrad, int ld_in, int ld_out, int ldadd, int B, int H, int W, int Cin, int Cout);
+// wf / wd: the two copies cgd_pack_conv3x3 leaves (net.h)
+int cgd_launch_sconv_fwd(cgd_ctx* ctx, const float* x, int ldx, const float* wf, const float* bias, float* y, int ldy, int B, int H, int W, int Cin,
+                         int Cout, hipStream_t s);
+// dx (B, H, W, Cin) = conv^T dy (+ add): one launch, the pixel parity taken from the workgroup index; deterministic
+int cgd_launch_sconv_dgrad(cgd_ctx* ctx, const float* dy, int lddy, const float* wd, float* dx, int lddx, const float* add, int ldadd, int B, int H,
+                           int W, int Cin, int Cout, hipStream_t s);
 
 // ---- attn.hip ---------------------------------------------------------------------------------------------
 // in-place row softmax over the first T columns of [rows][ld]; columns [T, ld) are set to 0

@@ -62,6 +62,7 @@ struct ResBlock : Module {
   std::string pre;
   int cin = 0, cout = 0;
   bool up = false, down = false, skip_conv = false;
+  bool additive = false;  // use_scale_shift_norm = False: h = conv1(...) + e[b, :], GN2 without FiLM (emb_layers.1 has cout rows)
   long emb_off = 0;
   // params / packed
   float *g1 = 0, *b1 = 0, *cw1f = 0, *cw1d = 0, *cb1 = 0, *g2 = 0, *b2 = 0, *cw2f = 0, *cw2d = 0, *cb2 = 0, *skw = 0, *skwT = 0,
@@ -76,6 +77,28 @@ struct ResBlock : Module {
   TV add_skip;  // backward: gradient of the skip connection that consumed this block's INPUT (the split half of a later concat)
   DevBuf h1, h1p, xr, h2, h3, out, s1, s2;
   DevBuf d3, d2, d1, d1f, dx;
+  int fwd(UNet& u, TV x, int B, int& H, int& W, TV* out, hipStream_t s) override;
+  int bwd(UNet& u, TV dout, TV* din, hipStream_t s) override;
+};
+
+// The resampling modules of the classic architecture (cgd_unet_config::classic_resample; upstream Downsample / Upsample with use_conv = True).  They
+// take no embedding and hold one conv, ch -> ch; `add_skip` is the gradient of the skip connection that read the module's INPUT, as in ResBlock.
+struct Downsample : Module {  // the 3x3 conv of stride 2 (sconv.hip)
+  std::string pre;            // "...0.op"
+  int C = 0;
+  float *wf = 0, *wd = 0, *cb = 0;
+  int B = 0, H = 0, W = 0;
+  TV add_skip;
+  DevBuf out, dx;
+  int fwd(UNet& u, TV x, int B, int& H, int& W, TV* out, hipStream_t s) override;
+  int bwd(UNet& u, TV dout, TV* din, hipStream_t s) override;
+};
+struct Upsample : Module {  // nearest 2x folded into the gather of a 3x3 conv (GemmParams::ups): no full-resolution temporary in the forward
+  std::string pre;          // "...J.conv"
+  int C = 0;
+  float *wf = 0, *wd = 0, *wfp = 0, *wdp = 0, *cb = 0;
+  int B = 0, H = 0, W = 0;  // the input's
+  DevBuf out, d1, dx;
   int fwd(UNet& u, TV x, int B, int& H, int& W, TV* out, hipStream_t s) override;
   int bwd(UNet& u, TV dout, TV* din, hipStream_t s) override;
 };
@@ -104,6 +127,8 @@ struct UNet : NetBase {
   std::vector<int> in_chans;  // channels of every hs entry
   std::vector<int> in_ds;     // downsampling factor of every hs entry
   std::vector<ResBlock*> resblocks;
+  std::vector<Downsample*> downs;
+  std::vector<Upsample*> ups;
   // packed stem / head weights
   float *stem_wf = 0, *stem_wd = 0, *head_wf = 0, *head_wd = 0;
   float *emb_w_all = 0, *emb_b_all = 0, *freqs = 0;
@@ -181,6 +206,9 @@ int ResBlock::fwd(UNet& u, TV xin, int Bn, int& Hh, int& Ww, TV* o, hipStream_t 
   c1.M = (int)npo; c1.N = cout; c1.conv = 1; c1.H = Ho; c1.W = Wo; c1.Cin = cin; c1.ups = up ? 1 : 0;
   c1.defer = 1;  // a split-K launch leaves its slices for the GroupNorm right below (SplitSrc)
   c1.stats = 1;  // ... and a wconv_kernel launch takes the statistics that GroupNorm needs in its epilogue (ChanStatsEntry)
+  // an additive block normalises conv1's output PLUS the embedding: slices summed by the norm and epilogue records would be those of the tensor before
+  // the addition, so both are off and one small kernel adds e[b, :] in between
+  if (additive) c1.defer = c1.stats = 0;
   // in_layers: GN -> SiLU.  When conv1 runs on the halo kernel (and nothing else reads the normalised tensor: `down` blocks
   // pool it first) the kernel applies SiLU(GN(x)) while it stages its input: only the statistics pass runs here and h1 is
   // never materialised.
@@ -211,6 +239,8 @@ int ResBlock::fwd(UNet& u, TV xin, int Bn, int& Hh, int& Ww, TV* o, hipStream_t 
     skip_ld = cin;
   }
   CGD_TRY(cgd_launch_gemm(ctx, c1, s));
+  if (additive) CGD_TRY(cgd_launch_add_chan(ctx, h2.p, cout, u.emb_cur + emb_off, (int)u.emb_total, B, Ho * Wo, cout, s));
+  const float* const film = additive ? nullptr : u.emb_cur + emb_off;
   // out_layers: GN * (1+scale) + shift -> SiLU -> conv2 (+ skip); same on-the-fly application when conv2 runs on the halo kernel
   GemmParams c2;
   c2.A = h2.p; c2.lda = cout; c2.B = cw2f; c2.Bpk = cw2fp; c2.Bwk = wino_ready ? cw2wp : nullptr; c2.bwk_prec = wino_prec; c2.ldb = 9 * cout; c2.C = outp; c2.ldc = ldo; c2.bias = cb2;
@@ -219,12 +249,12 @@ int ResBlock::fwd(UNet& u, TV xin, int Bn, int& Hh, int& Ww, TV* o, hipStream_t 
   c2.stats = 1;  // (both halves of a skip concat carry their own records: the GroupNorm of the concat merges the two sources)
   const bool fuse2 = cgd_conv_uses_hconv(ctx, c2);
   if (fuse2) {
-    CGD_TRY(cgd_launch_gn_fwd(ctx, h2.p, cout, nullptr, 0, B, Ho * Wo, cout, g2, b2, u.emb_cur + emb_off, (int)u.emb_total, 1, 1e-5f,
+    CGD_TRY(cgd_launch_gn_fwd(ctx, h2.p, cout, nullptr, 0, B, Ho * Wo, cout, g2, b2, film, (int)u.emb_total, 1, 1e-5f,
                               s2.p, s));
     c2.gn_ab = cgd_gn_ab(s2.p, B, Ho * Wo, cout);
   } else {
     CGD_TRY(u.ensure(h3, npo * cout));
-    CGD_TRY(cgd_launch_gn_fwd(ctx, h2.p, cout, h3.p, cout, B, Ho * Wo, cout, g2, b2, u.emb_cur + emb_off, (int)u.emb_total, 1, 1e-5f,
+    CGD_TRY(cgd_launch_gn_fwd(ctx, h2.p, cout, h3.p, cout, B, Ho * Wo, cout, g2, b2, film, (int)u.emb_total, 1, 1e-5f,
                               s2.p, s));
     c2.A = h3.p;
   }
@@ -325,6 +355,59 @@ int ResBlock::bwd(UNet& u, TV dout, TV* din, hipStream_t s) {
   return 0;
 }
 
+int Downsample::fwd(UNet& u, TV xin, int Bn, int& Hh, int& Ww, TV* o, hipStream_t s) {
+  B = Bn; H = Hh; W = Ww;
+  const int Ho = H / 2, Wo = W / 2;
+  if (!dst.p) CGD_TRY(u.ensure(out, (size_t)B * Ho * Wo * C));
+  float* const outp = dst.p ? dst.p : out.p;
+  const int ldo = dst.p ? dst.ld : C;
+  CGD_TRY(cgd_launch_sconv_fwd(u.ctx, xin.p, xin.ld, wf, cb, outp, ldo, B, H, W, C, C, s));
+  Hh = Ho; Ww = Wo;
+  *o = TV{outp, ldo, C};
+  return 0;
+}
+
+int Downsample::bwd(UNet& u, TV dout, TV* din, hipStream_t s) {
+  CGD_TRY(u.ensure(dx, (size_t)B * H * W * C));
+  // + the gradient of the skip connection that read this module's input, in the kernel's epilogue
+  CGD_TRY(cgd_launch_sconv_dgrad(u.ctx, dout.p, dout.ld, wd, dx.p, C, add_skip.p, add_skip.ld, B, H, W, C, C, s));
+  *din = TV{dx.p, C, C};
+  return 0;
+}
+
+int Upsample::fwd(UNet& u, TV xin, int Bn, int& Hh, int& Ww, TV* o, hipStream_t s) {
+  B = Bn; H = Hh; W = Ww;
+  const int Ho = 2 * H, Wo = 2 * W;
+  const long npo = (long)B * Ho * Wo;
+  if (!dst.p) CGD_TRY(u.ensure(out, (size_t)npo * C));
+  float* const outp = dst.p ? dst.p : out.p;
+  const int ldo = dst.p ? dst.ld : C;
+  GemmParams c;
+  c.A = xin.p; c.lda = xin.ld; c.B = wf; c.Bpk = wfp; c.ldb = 9 * C; c.C = outp; c.ldc = ldo; c.bias = cb;
+  c.M = (int)npo; c.N = C; c.conv = 1; c.H = Ho; c.W = Wo; c.Cin = C; c.ups = 1;
+  c.defer = 1;  // as a ResBlock's conv2: the next module starts with a GroupNorm of this tensor (the h half of a skip concat)
+  c.stats = 1;
+  CGD_TRY(cgd_launch_gemm(u.ctx, c, s));
+  Hh = Ho; Ww = Wo;
+  *o = TV{outp, ldo, C};
+  return 0;
+}
+
+int Upsample::bwd(UNet& u, TV dout, TV* din, hipStream_t s) {
+  const int Ho = 2 * H, Wo = 2 * W;
+  const long npo = (long)B * Ho * Wo;
+  CGD_TRY(u.ensure(d1, (size_t)npo * C));
+  CGD_TRY(u.ensure(dx, (size_t)B * H * W * C));
+  // the conv's dgrad at the high resolution, then the adjoint of the nearest 2x: the 2 x 2 sum
+  GemmParams c;
+  c.A = dout.p; c.lda = dout.ld; c.B = wd; c.Bpk = wdp; c.ldb = 9 * C; c.C = d1.p; c.ldc = C;
+  c.M = (int)npo; c.N = C; c.conv = 1; c.H = Ho; c.W = Wo; c.Cin = C;
+  CGD_TRY(cgd_launch_gemm(u.ctx, c, s));
+  CGD_TRY(cgd_launch_pool2x2(u.ctx, d1.p, C, dx.p, C, nullptr, 0, B, H, W, C, 1.f, s));
+  *din = TV{dx.p, C, C};
+  return 0;
+}
+
 int AttnBlock::fwd(UNet& u, TV xin, int Bn, int& H, int& W, TV* o, hipStream_t s) {
   cgd_ctx* ctx = u.ctx;
   B = Bn; T = H * W;
@@ -386,6 +469,7 @@ int UNet::build() {
   if (cfg.n_att < 0 || cfg.n_att > 8) CGD_FAIL(ctx, "unet: at most 8 attention resolutions");
   if (mc <= 0 || mc % 32) CGD_FAIL(ctx, "unet: model_channels must be a positive multiple of 32 (GroupNorm32)");
   if (cfg.num_res_blocks < 1) CGD_FAIL(ctx, "unet: num_res_blocks must be >= 1");
+  if ((cfg.classic_resample | cfg.additive_emb) & ~1) CGD_FAIL(ctx, "unet: classic_resample and additive_emb must be 0 or 1");
   if (cfg.image_size <= 0 || cfg.image_size % (1 << (cfg.n_mult - 1))) CGD_FAIL(ctx, "unet: image_size must be divisible by 2^(levels-1)");
   if (cfg.num_classes < 0) CGD_FAIL(ctx, "unet: num_classes must be >= 0");
   if (cfg.num_head_channels == -1 ? cfg.num_heads <= 0 : cfg.num_head_channels <= 0) CGD_FAIL(ctx, "unet: num_heads / num_head_channels");
@@ -413,12 +497,14 @@ int UNet::build() {
   auto make_rb = [&](const std::string& pre, int cin, int cout, bool up, bool down) {
     auto rb = std::make_unique<ResBlock>();
     rb->pre = pre; rb->cin = cin; rb->cout = cout; rb->up = up; rb->down = down; rb->skip_conv = cin != cout;
+    rb->additive = cfg.additive_emb != 0;
+    const int emb_rows = rb->additive ? cout : 2 * cout;  // FiLM: (scale | shift)
     add_param(pre + ".in_layers.0.weight", cin);
     add_param(pre + ".in_layers.0.bias", cin);
     add_param(pre + ".in_layers.2.weight", (int64_t)cout * cin * 9);
     add_param(pre + ".in_layers.2.bias", cout);
-    add_param(pre + ".emb_layers.1.weight", (int64_t)2 * cout * ted);
-    add_param(pre + ".emb_layers.1.bias", 2 * cout);
+    add_param(pre + ".emb_layers.1.weight", (int64_t)emb_rows * ted);
+    add_param(pre + ".emb_layers.1.bias", emb_rows);
     add_param(pre + ".out_layers.0.weight", cout);
     add_param(pre + ".out_layers.0.bias", cout);
     add_param(pre + ".out_layers.3.weight", (int64_t)cout * cout * 9);
@@ -428,9 +514,26 @@ int UNet::build() {
       add_param(pre + ".skip_connection.bias", cout);
     }
     rb->emb_off = emb_total;
-    emb_total += 2 * cout;
+    emb_total += emb_rows;
     resblocks.push_back(rb.get());
     return rb;
+  };
+  // classic_resample: the modules that stand where the resampling ResBlocks stand otherwise
+  auto make_down = [&](const std::string& pre, int C) {
+    auto m = std::make_unique<Downsample>();
+    m->pre = pre + ".op"; m->C = C;
+    add_param(m->pre + ".weight", (int64_t)C * C * 9);
+    add_param(m->pre + ".bias", C);
+    downs.push_back(m.get());
+    return m;
+  };
+  auto make_up = [&](const std::string& pre, int C) {
+    auto m = std::make_unique<Upsample>();
+    m->pre = pre + ".conv"; m->C = C;
+    add_param(m->pre + ".weight", (int64_t)C * C * 9);
+    add_param(m->pre + ".bias", C);
+    ups.push_back(m.get());
+    return m;
   };
   auto make_att = [&](const std::string& pre, int C) {
     auto ab = std::make_unique<AttnBlock>();
@@ -469,7 +572,10 @@ int UNet::build() {
     }
     if (level != cfg.n_mult - 1) {
       std::vector<std::unique_ptr<Module>> blk;
-      blk.push_back(make_rb("input_blocks." + std::to_string(idx) + ".0", ch, ch, false, true));
+      if (cfg.classic_resample)
+        blk.push_back(make_down("input_blocks." + std::to_string(idx) + ".0", ch));
+      else
+        blk.push_back(make_rb("input_blocks." + std::to_string(idx) + ".0", ch, ch, false, true));
       in_blocks.push_back(std::move(blk));
       in_chans.push_back(ch);
       ++idx;
@@ -498,7 +604,10 @@ int UNet::build() {
       ch = co;
       if (is_att(ds)) blk.push_back(make_att(pre + "." + std::to_string(sub++), ch));
       if (level && i == cfg.num_res_blocks) {
-        blk.push_back(make_rb(pre + "." + std::to_string(sub++), ch, ch, true, false));
+        if (cfg.classic_resample)
+          blk.push_back(make_up(pre + "." + std::to_string(sub++), ch));
+        else
+          blk.push_back(make_rb(pre + "." + std::to_string(sub++), ch, ch, true, false));
         ds /= 2;
       }
       out_blocks.push_back(std::move(blk));
@@ -549,10 +658,31 @@ int UNet::finalize(hipStream_t s) {
       rb->skb = P(p + ".skip_connection.bias");
       CGD_TRY(transpose_weight(rb->skw, &rb->skwT, rb->cout, rb->cin, s));
     }
-    CGD_HIP(ctx, hipMemcpyAsync(emb_w_all + rb->emb_off * ted, P(p + ".emb_layers.1.weight"), (size_t)2 * rb->cout * ted * sizeof(float),
+    const size_t emb_rows = rb->additive ? rb->cout : 2 * rb->cout;
+    CGD_HIP(ctx, hipMemcpyAsync(emb_w_all + rb->emb_off * ted, P(p + ".emb_layers.1.weight"), emb_rows * ted * sizeof(float),
                                 hipMemcpyDeviceToDevice, s));
-    CGD_HIP(ctx, hipMemcpyAsync(emb_b_all + rb->emb_off, P(p + ".emb_layers.1.bias"), (size_t)2 * rb->cout * sizeof(float),
+    CGD_HIP(ctx, hipMemcpyAsync(emb_b_all + rb->emb_off, P(p + ".emb_layers.1.bias"), emb_rows * sizeof(float),
                                 hipMemcpyDeviceToDevice, s));
+  }
+  for (Downsample* m : downs) {
+    m->cb = P(m->pre + ".bias");
+    if (!m->wf) {
+      CGD_TRY(alloc(&m->wf, (size_t)m->C * m->C * 9));
+      CGD_TRY(alloc(&m->wd, (size_t)m->C * m->C * 9));
+    }
+    CGD_TRY(cgd_pack_conv3x3(ctx, P(m->pre + ".weight"), m->wf, m->wd, m->C, m->C, s));
+  }
+  for (Upsample* m : ups) {
+    m->cb = P(m->pre + ".bias");
+    if (!m->wf) {
+      CGD_TRY(alloc(&m->wf, (size_t)m->C * m->C * 9));
+      CGD_TRY(alloc(&m->wd, (size_t)m->C * m->C * 9));
+      CGD_TRY(alloc(&m->wfp, (size_t)m->C * m->C * 9));
+      CGD_TRY(alloc(&m->wdp, (size_t)m->C * m->C * 9));
+    }
+    CGD_TRY(cgd_pack_conv3x3_frag(ctx, P(m->pre + ".weight"), m->wfp, m->C, m->C, 0, s));
+    CGD_TRY(cgd_pack_conv3x3_frag(ctx, P(m->pre + ".weight"), m->wdp, m->C, m->C, 1, s));
+    CGD_TRY(cgd_pack_conv3x3(ctx, P(m->pre + ".weight"), m->wf, m->wd, m->C, m->C, s));
   }
   auto fin_att = [&](Module* m) -> int {
     AttnBlock* ab = dynamic_cast<AttnBlock*>(m);
@@ -757,10 +887,15 @@ int UNet::dgrad(const float* gout, float* gx, hipStream_t s) {
   // hs[i] (the output of input block i, or of the stem for i = 0) was also consumed by output block k = n-1-i: its gradient is the
   // sum of what the next module hands back and the skip half dskip[n-1-i].  The module that produces the former is always a
   // ResBlock (input block i+1's first module, or middle_block.0 for the last one), whose final GroupNorm-backward pass adds the
-  // skip half on the fly (`add_skip`): no separate add kernel.
+  // skip half on the fly (`add_skip`): no separate add kernel.  (A classic Downsample in that place adds it in its dgrad's epilogue.)
   const int n = (int)in_blocks.size();
   static_cast<ResBlock*>(mid[0].get())->add_skip = dskip[0];
-  for (int i = 1; i < n; ++i) static_cast<ResBlock*>(in_blocks[i][0].get())->add_skip = dskip[n - i];
+  for (int i = 1; i < n; ++i) {
+    if (Downsample* dn = dynamic_cast<Downsample*>(in_blocks[i][0].get()))
+      dn->add_skip = dskip[n - i];
+    else
+      static_cast<ResBlock*>(in_blocks[i][0].get())->add_skip = dskip[n - i];
+  }
   for (int j = (int)mid.size() - 1; j >= 0; --j) CGD_TRY(mid[j]->bwd(*this, d, &d, s));
   for (int i = n - 1; i >= 1; --i)
     for (int j = (int)in_blocks[i].size() - 1; j >= 0; --j) CGD_TRY(in_blocks[i][j]->bwd(*this, d, &d, s));
@@ -802,6 +937,7 @@ int Classifier::build() {
   }
   u.n_att = cfg.n_att; u.num_classes = 0; u.num_heads = 1; u.num_head_channels = cfg.num_head_channels; u.use_new_attention_order = 0;
   u.in_channels = 3; u.out_channels = cfg.out_channels;
+  u.classic_resample = 0; u.additive_emb = 0;  // the published classifiers: resblock_updown, use_scale_shift_norm
   encoder_only = true;
   CGD_TRY(UNet::build());
   // the middle_block and the pool always attend: their width must be a whole number of heads

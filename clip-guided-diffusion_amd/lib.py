@@ -24,6 +24,8 @@ class UNetConfig(C.Structure):
         ("channel_mult", f32 * 8), ("n_att", i32), ("attention_ds", i32 * 8), ("num_classes", i32),
         ("num_heads", i32), ("num_head_channels", i32), ("use_new_attention_order", i32),
         ("in_channels", i32), ("out_channels", i32),
+        # the classic architecture (0 / 0: the published guided-diffusion checkpoints, and what UNetConfig() gets)
+        ("classic_resample", i32), ("additive_emb", i32),
     ]
 
 
@@ -235,6 +237,11 @@ _SIGS = {
     "cgd_op_plan_conv": (i32, [i32] * 10 + [C.POINTER(i32)]),
     "cgd_op_pack_conv3x3_frag": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "cgd_set_hconv": (i32, [vp, i32, i32]),
+    "cgd_op_conv3x3_s2": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "cgd_op_conv3x3_s2_dgrad": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "cgd_op_conv3x3_s2_accepts": (i32, [i32] * 9),
+    "cgd_op_conv3x3_s2_packed": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "cgd_op_conv3x3_s2_dgrad_packed": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_op_conv3x3": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_op_conv3x3_ex": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, vp, vp]),
     "cgd_op_pack_conv3x3_wino": (i32, [vp, vp, vp, i32, i32, i32, vp]),

@@ -118,10 +118,10 @@ class UNet(_Net):
 
     def __init__(self, ctx, image_size, model_channels, num_res_blocks, attention_resolutions="32,16,8", channel_mult=None,
                  num_classes=None, num_heads=4, num_head_channels=-1, use_new_attention_order=False, in_channels=3,
-                 out_channels=6):
+                 out_channels=6, resblock_updown=True, use_scale_shift_norm=True):
         self.ctx = ctx
         cfg = self.make_config(image_size, model_channels, num_res_blocks, attention_resolutions, channel_mult, num_classes, num_heads,
-                               num_head_channels, use_new_attention_order, in_channels, out_channels)
+                               num_head_channels, use_new_attention_order, in_channels, out_channels, resblock_updown, use_scale_shift_norm)
         self.cfg = cfg
         self.num_classes = num_classes
         self.in_channels = in_channels
@@ -132,11 +132,14 @@ class UNet(_Net):
 
     @staticmethod
     def make_config(image_size, model_channels, num_res_blocks, attention_resolutions="32,16,8", channel_mult=None, num_classes=None,
-                    num_heads=4, num_head_channels=-1, use_new_attention_order=False, in_channels=3, out_channels=6):
-        """guided_diffusion's create_model arguments -> the C struct (host-only: also feeds cgd_unet_manifest in the CPU tests)."""
+                    num_heads=4, num_head_channels=-1, use_new_attention_order=False, in_channels=3, out_channels=6, resblock_updown=True,
+                    use_scale_shift_norm=True):
+        """guided_diffusion's create_model arguments -> the C struct (host-only: also feeds cgd_unet_manifest in the CPU tests).
+        resblock_updown=False: Downsample / Upsample are convs (conv_resample=True); use_scale_shift_norm=False: the timestep embedding is
+        added to conv1's output instead of modulating the second norm.  The defaults are the published guided-diffusion checkpoints'."""
         if channel_mult is None:
             channel_mult = DEFAULT_CHANNEL_MULT[image_size]
-        att = [image_size // int(r) for r in str(attention_resolutions).split(",")]
+        att = [image_size // int(r) for r in str(attention_resolutions).split(",") if r.strip()]  # "": attention in the middle block only
         cfg = L.UNetConfig()
         cfg.image_size, cfg.model_channels, cfg.num_res_blocks = image_size, model_channels, num_res_blocks
         cfg.n_mult = len(channel_mult)
@@ -149,6 +152,8 @@ class UNet(_Net):
         cfg.num_heads, cfg.num_head_channels = num_heads, num_head_channels
         cfg.use_new_attention_order = int(bool(use_new_attention_order))
         cfg.in_channels, cfg.out_channels = in_channels, out_channels
+        cfg.classic_resample = int(not resblock_updown)
+        cfg.additive_emb = int(not use_scale_shift_norm)
         return cfg
 
     def set_low_res(self, low_res):

@@ -152,6 +152,37 @@ def conv3x3(ctx, x_nhwc, w_packed, bias=None, R=None, upsample_input=False, forc
     return y
 
 
+def conv3x3_s2(ctx, x_nhwc, w, bias=None, out=None, packed=False):
+    """conv2d(stride=2, padding=1) of x (B,H,W,Cin) NHWC with the torch weight w [Cout][Cin][3][3] -> (B,H/2,W/2,Cout); x and `out` may be
+    channel slices.  packed: w is pack_conv3x3(w)[0], [Cout][9 Cin], packed once by the caller (no per-call pack launch)."""
+    Bn, H, W, Cin = x_nhwc.shape
+    Cout = w.shape[0]
+    px, ldx = _rows(x_nhwc, "x")
+    pw, pbias = _dense(w, "w"), _dense(bias, "bias")
+    if out is None:
+        out = th.empty((Bn, H // 2, W // 2, Cout), device=x_nhwc.device, dtype=th.float32)
+    py, ldy = _rows(out, "out")
+    fn = ctx.lib.cgd_op_conv3x3_s2_packed if packed else ctx.lib.cgd_op_conv3x3_s2
+    ctx.check(fn(ctx.h, px, ldx, pw, pbias, py, ldy, Bn, H, W, Cin, Cout, _s()))
+    return out
+
+
+def conv3x3_s2_dgrad(ctx, dy_nhwc, w, add=None, out=None, packed=False):
+    """The input gradient of conv3x3_s2: dy (B,Ho,Wo,Cout) -> dx (B,2Ho,2Wo,Cin) (+ add, dx's shape); dy, add and `out` may be channel slices.
+    packed: w is pack_conv3x3(w)[1], [Cin][9 Cout], packed once by the caller."""
+    Bn, Ho, Wo, Cout = dy_nhwc.shape
+    Cin = w.shape[0] if packed else w.shape[1]
+    pdy, lddy = _rows(dy_nhwc, "dy")
+    pw = _dense(w, "w")
+    padd, ldadd = _rows(add, "add")
+    if out is None:
+        out = th.empty((Bn, 2 * Ho, 2 * Wo, Cin), device=dy_nhwc.device, dtype=th.float32)
+    pdx, lddx = _rows(out, "out")
+    fn = ctx.lib.cgd_op_conv3x3_s2_dgrad_packed if packed else ctx.lib.cgd_op_conv3x3_s2_dgrad
+    ctx.check(fn(ctx.h, pdy, lddy, pw, pdx, lddx, padd, ldadd, Bn, 2 * Ho, 2 * Wo, Cin, Cout, _s()))
+    return out
+
+
 def pack_conv3x3_wino(ctx, w, dgrad=False):
     """torch conv weight [Co][Ci][3][3] (on the GPU) -> Winograd F(2,3)-transformed bf16 hi/lo fragments for wconv.hip."""
     co, ci = w.shape[:2]

@@ -73,6 +73,11 @@ typedef struct cgd_unet_config {
   int use_new_attention_order;
   int in_channels;         /* 3, or 6: a super-resolution UNet, x (3) + the upsampled low-resolution image (3) */
   int out_channels;        /* 6 (learn_sigma) */
+  /* The classic architecture of improved-diffusion / guided-diffusion's defaults.  0 for both is the architecture of the published
+   * guided-diffusion checkpoints, and what a zero-initialised struct gets. */
+  int classic_resample;    /* 1: resblock_updown = False, conv_resample = True: Downsample is a 3x3 conv of stride 2 (input_blocks.K.0.op),
+                              Upsample nearest 2x + a 3x3 conv (output_blocks.K.J.conv) */
+  int additive_emb;        /* 1: use_scale_shift_norm = False: the timestep embedding is added to conv1's output (emb_layers.1 has cout rows) */
 } cgd_unet_config;
 
 /* host-only (no GPU, no context): the parameter manifest of a configuration — cb(name, numel, user) per parameter in upload order,
@@ -737,6 +742,28 @@ int cgd_set_wino(cgd_ctx* ctx, int mode, int min_m);
 int cgd_op_conv3x3_wino_ex(cgd_ctx* ctx, const float* x_nhwc, int ldx, const float* w_wino, float* y_nhwc, int ldy, const float* bias,
                            const float* R, int ldr, const float* gn_ab, int Bn, int H, int W, int Cin, int Cout, int upsample_input,
                            int stats, const float* gnb_x, int gnb_ldx, const float* gnb_scratch, void* stream);
+/* 3x3 convolution of stride 2, padding 1 (csrc/sconv.hip: the classic UNet's Downsample) and its backward to the input, as implicit GEMMs on MFMA
+ * in the context's precision mode.  NHWC fp32 rows with a row stride; w_torch [Cout][Cin][3][3] as uploaded, packed per call (test and benchmark
+ * entries: the UNet packs once at finalize).
+ *   cgd_op_conv3x3_s2:       y (B, H/2, W/2, Cout) = conv(x (B, H, W, Cin)) + bias (bias may be NULL)
+ *   cgd_op_conv3x3_s2_dgrad: dx (B, H, W, Cin) = conv^T(dy (B, H/2, W/2, Cout)) (+ add, same shape as dx, may be NULL); B, H, W are the INPUT's.
+ *                            A gather per input-pixel parity (1, 2, 2 and 4 taps), one launch, no atomics: bit-identical from run to run.
+ * Refused (-2, cgd_last_error): odd H or W, Cin or Cout not a positive multiple of 32, a row stride below its channel count or not a multiple of 4,
+ * an operand of 2^31 bytes or more (32-bit byte offsets), a pointer that is not 16-byte aligned.
+ * cgd_op_conv3x3_s2_accepts: host-only (no GPU, no context), 1 if the entries run a problem of these strides and shape, 0 if they refuse it (the
+ * same predicate, pointers aside).  dgrad = 0: ld_in = ldx, ld_out = ldy; dgrad = 1: ld_in = lddy, ld_out = lddx; ldadd = 0: no add operand. */
+int cgd_op_conv3x3_s2(cgd_ctx* ctx, const float* x_nhwc, int ldx, const float* w_torch, const float* bias, float* y_nhwc, int ldy, int B, int H,
+                      int W, int Cin, int Cout, void* stream);
+int cgd_op_conv3x3_s2_dgrad(cgd_ctx* ctx, const float* dy_nhwc, int lddy, const float* w_torch, float* dx_nhwc, int lddx, const float* add,
+                            int ldadd, int B, int H, int W, int Cin, int Cout, void* stream);
+int cgd_op_conv3x3_s2_accepts(int dgrad, int ld_in, int ld_out, int ldadd, int B, int H, int W, int Cin, int Cout);
+/* The same two on weights the caller packed once (what the UNet's Downsample runs per step; benchmarks time these, so that no per-call weight
+ * pack is inside the figure): w_fwd [Cout][9 Cin] with column (ky * 3 + kx) * Cin + ci, w_dgrad [Cin][9 Cout] with column
+ * ((2 - ky) * 3 + (2 - kx)) * Cout + co = w[co][ci][ky][kx] (ops.pack_conv3x3 gives both). */
+int cgd_op_conv3x3_s2_packed(cgd_ctx* ctx, const float* x_nhwc, int ldx, const float* w_fwd, const float* bias, float* y_nhwc, int ldy, int B,
+                             int H, int W, int Cin, int Cout, void* stream);
+int cgd_op_conv3x3_s2_dgrad_packed(cgd_ctx* ctx, const float* dy_nhwc, int lddy, const float* w_dgrad, float* dx_nhwc, int lddx,
+                                   const float* add, int ldadd, int B, int H, int W, int Cin, int Cout, void* stream);
 int cgd_op_new_pass(cgd_ctx* ctx);
 /* number of GroupNorm launches since context creation that MERGED conv-epilogue records (forward statistics + backward sums) instead of
  * sweeping their input: lets a test assert which path a cgd_op_gn_fwd / cgd_op_gn_bwd call took */

@@ -5,6 +5,8 @@ change at keyframes.
     python -m cgd_amd.animate --frames 120 --zoom "0:(1.02)" --angle "0:(0),60:(2)" --translation_x 0 --translation_y "0:(0),120:(-40)" \\
         --border wrap --interp bicubic --frames_skip 0.6 --frames_scale 1500 --color_match 1 [--fixed_seed] \\
         [--prompts_at "40=a city at night|a skyline:0.5"]... -- <cgd command-line flags>
+    python -m cgd_amd.animate --frames 120 --mode 3d --translation_z "0:(4)" --rotation_3d_y "0:(0),60:(0.5)" --translation_x 2 --fov 40 \\
+        [--depth_fn MODULE:FUNCTION --depth_iters 2] ... -- <cgd command-line flags>
 
 or, from Python, `animate(frames, zoom=..., **clip_guided_diffusion_kwargs)`, a generator of `(frame_idx, batch_idx, png_path)`.
 
@@ -21,14 +23,35 @@ Conventions (motion_matrix).  The forward map of a frame is p' = t + c + z R(the
   t = (translation_x, translation_y): positive values move the content right and down;
   z = zoom: above 1 magnifies.
 The kernel takes the inverse map, which is what motion_matrix returns.
+
+3D mode (`--mode 3d`, Disco's and Deforum's 3D animation): the previous frame is seen by a pinhole camera that has moved, with a depth for
+every pixel, so that near things move faster than far ones (cgd_frame_warp3d, csrc/warp3d.hip).  Conventions (camera, project, unproject):
+  axes x right, y down, z into the screen; c as above; focal length f = (H / 2) / tan(fov / 2) pixels, fov the vertical field of view in
+      degrees (default 40); a source position q of depth z is the point X = z ((qx - cx) / f, (qy - cy) / f, 1);
+  between two frames X' = R X + T, seen at c + f (X'x, X'y) / X'z, with T = (translation_x, translation_y, -translation_z) / 200 (the 1 / 200
+      is Deforum's translation scale as remembered, not checked against its source) and R = Rx(rotation_3d_x) Ry(rotation_3d_y)
+      Rz(rotation_3d_z), degrees, Rx(a) = [[1,0,0],[0,cos,sin],[0,-sin,cos]], Ry(b) = [[cos,0,-sin],[0,1,0],[sin,0,cos]],
+      Rz(c) = [[cos,sin,0],[-sin,cos,0],[0,0,1]];
+  on the screen: translation_x > 0 moves the content right by f tx / 200 / z pixels (parallax), translation_y > 0 down, translation_z > 0
+      flies forward (at flat depth z0 a magnification of z0 / (z0 - tz / 200)), rotation_3d_z > 0 turns the picture counter-clockwise like
+      `angle`, rotation_3d_y > 0 turns the camera right (content moves left), rotation_3d_x > 0 tilts it up (content moves down).  These
+      signs are this project's own; they have not been compared with Deforum's.
+Depth is flat (Deforum's use_depth_warping=False) or the caller's: a tensor, or a callable of the previous frame.  No depth network is
+included.
 """
 import argparse
+import collections
+import importlib
 import math
 import re
 import sys
 
 BORDERS = ("wrap", "reflect", "replicate")
 INTERPS = ("bilinear", "bicubic")
+MODES = ("2d", "3d")
+TRANSLATION_SCALE = 200.0
+
+Camera = collections.namedtuple("Camera", "R T f cx cy z0 near")
 
 _KEY = re.compile(r"^\s*([^:\s]+)\s*:\s*\(\s*([^()\s]+)\s*\)\s*$")
 
@@ -110,6 +133,49 @@ def forward_matrix(zoom, angle_deg, tx, ty, H, W):
     return (cos, sin, tx + cx - (cos * cx + sin * cy), -sin, cos, ty + cy - (-sin * cx + cos * cy))
 
 
+def camera(tx, ty, tz, rx, ry, rz, fov, H, W, z0=1.0, near=0.05):
+    """The Camera (R as 9 row-major float64 entries, T, f, cx, cy, z0, near) of one frame's 3D motion (module docstring): translations in
+    Deforum units (1 / 200 of a depth unit), rotations and the vertical field of view `fov` in degrees.  ValueError on a non-finite value, a
+    fov outside (0, 180), or a z0 or near that is not positive."""
+    tx, ty, tz, rx, ry, rz, fov, z0, near = (_number(v, n) for v, n in (
+        (tx, "translation_x"), (ty, "translation_y"), (tz, "translation_z"), (rx, "rotation_3d_x"), (ry, "rotation_3d_y"),
+        (rz, "rotation_3d_z"), (fov, "fov"), (z0, "z0"), (near, "near")))
+    if not 0 < fov < 180:
+        raise ValueError(f"fov must lie in (0, 180) degrees, got {fov}")
+    if not z0 > 0 or not near > 0:
+        raise ValueError(f"z0 and near must be positive, got {z0} and {near}")
+    if H < 1 or W < 1:
+        raise ValueError(f"the frame must be at least 1 x 1, got {H} x {W}")
+    (ca, sa), (cb, sb), (cc, sc) = ((math.cos(math.radians(v)), math.sin(math.radians(v))) for v in (rx, ry, rz))
+    # Rx(a) Ry(b) Rz(c), written out
+    R = (cb * cc, cb * sc, -sb,
+         sa * sb * cc - ca * sc, sa * sb * sc + ca * cc, sa * cb,
+         ca * sb * cc + sa * sc, ca * sb * sc - sa * cc, ca * cb)
+    R = tuple(v + 0.0 for v in R)  # no negative zeros: an identity camera is the identity matrix to the bit
+    T = (tx / TRANSLATION_SCALE, ty / TRANSLATION_SCALE, -tz / TRANSLATION_SCALE + 0.0)
+    return Camera(R, T, (H / 2.0) / math.tan(math.radians(fov) / 2.0), (W - 1) / 2.0, (H - 1) / 2.0, z0, near)
+
+
+def project(cam, q, z):
+    """Forward map: where the source position q = (x, y) of depth z is seen after the camera's motion."""
+    X = (z * (q[0] - cam.cx) / cam.f, z * (q[1] - cam.cy) / cam.f, z)
+    R, T = cam.R, cam.T
+    Y = [R[3 * i] * X[0] + R[3 * i + 1] * X[1] + R[3 * i + 2] * X[2] + T[i] for i in range(3)]
+    return cam.cx + cam.f * Y[0] / Y[2], cam.cy + cam.f * Y[1] / Y[2]
+
+
+def unproject(cam, p, z):
+    """Backward map G(p, z): the source position that a source point of depth z must have to be seen at p = (x, y); what the kernel
+    evaluates (a_z is kept at or above 1e-6 and lambda at or above near, which the exact inverse never needs inside the view)."""
+    r = ((p[0] - cam.cx) / cam.f, (p[1] - cam.cy) / cam.f, 1.0)
+    R, T = cam.R, cam.T
+    a = [R[i] * r[0] + R[3 + i] * r[1] + R[6 + i] * r[2] for i in range(3)]
+    b = [R[i] * T[0] + R[3 + i] * T[1] + R[6 + i] * T[2] for i in range(3)]
+    a[2] = max(a[2], 1e-6)
+    lam = max((z + b[2]) / a[2], cam.near)
+    return cam.cx + cam.f * (lam * a[0] - b[0]) / z, cam.cy + cam.f * (lam * a[1] - b[1]) / z
+
+
 def parse_prompts_at(values):
     """CLI '--prompts_at "40=a city at night|a skyline:0.5"' entries -> {40: ['a city at night', 'a skyline:0.5']}."""
     out = {}
@@ -178,8 +244,53 @@ def _check(frames, border, interp, frames_skip, frames_scale, color_match, promp
     return frames, plan
 
 
+def _check_mode(mode, frames, zoom, angle, motion3d, fov, depth, depth_iters, near):
+    """The refusals of the mode arguments, before anything is loaded -> the five 3D tracks (translation_z, rotation_3d_x / y / z, fov)."""
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+    names = ("translation_z", "rotation_3d_x", "rotation_3d_y", "rotation_3d_z")
+    tracks = [keyframes(spec, frames) for spec in motion3d] + [keyframes(fov, frames)]
+    if isinstance(depth_iters, bool) or not isinstance(depth_iters, int) or not 1 <= depth_iters <= 4:
+        raise ValueError(f"depth_iters must be an integer in 1..4, got {depth_iters!r}")
+    near = _number(near, "near")
+    if not near > 0:
+        raise ValueError(f"near must be positive, got {near}")
+    if any(not 0 < v < 180 for v in tracks[4]):
+        raise ValueError("fov must stay inside (0, 180) degrees on every frame")
+    if mode == "2d":
+        given = [n for n, t in zip(names, tracks) if any(v != 0 for v in t)]
+        given += ["fov"] * any(v != 40 for v in tracks[4]) + ["depth"] * (depth is not None) + ["depth_iters"] * (depth_iters != 1)
+        given += ["near"] * (near != 0.05)
+        if given:
+            raise ValueError(f"{', '.join(given)}: only with mode='3d'")
+        return tracks
+    if any(v != 1 for v in keyframes(zoom, frames)) or any(v != 0 for v in keyframes(angle, frames)):
+        raise ValueError("mode='3d' takes no zoom or angle: fly with translation_z and turn with rotation_3d_z")
+    if depth is not None and not callable(depth):
+        import torch as th
+        if not isinstance(depth, th.Tensor) or depth.dim() not in (2, 4):
+            raise ValueError("depth must be None, a callable, or a tensor (1 or B, 1, H, W) or (H, W)")
+    return tracks
+
+
+def _depth_map(depth, k, B, H, W, device=None):
+    """A depth tensor as cgd_frame_warp3d takes it: (1 or B, 1, H, W) fp32, on `device` if given; ValueError naming frame k otherwise."""
+    import torch as th
+    if not isinstance(depth, th.Tensor):
+        raise ValueError(f"frame {k}: the depth must be a tensor, got {type(depth).__name__}")
+    if depth.dim() == 2:
+        depth = depth[None, None]
+    if depth.dim() != 4 or tuple(depth.shape[1:]) != (1, H, W) or depth.shape[0] not in (1, B):
+        raise ValueError(f"frame {k}: the depth must have shape (1 or {B}, 1, {H}, {W}) or ({H}, {W}), got {tuple(depth.shape)}")
+    depth = depth.detach().to(device=depth.device if device is None else device, dtype=th.float32).contiguous()
+    if not bool((th.isfinite(depth) & (depth > 0)).all()):
+        raise ValueError(f"frame {k}: the depth must be finite and positive everywhere")
+    return depth
+
+
 def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, border="wrap", interp="bicubic", frames_skip=0.6,
-            frames_scale=1500, color_match=0.0, fixed_seed=False, prompts_at=None, **cgd_kwargs):
+            frames_scale=1500, color_match=0.0, fixed_seed=False, prompts_at=None, mode="2d", translation_z=0.0, rotation_3d_x=0.0,
+            rotation_3d_y=0.0, rotation_3d_z=0.0, fov=40.0, depth=None, depth_iters=1, near=0.05, **cgd_kwargs):
     """Generator of `(frame_idx, batch_idx, png_path)`: `frames` frames, each the last image of one sampling run, written to
     prefix_path/<prompts>/<batch_idx:02>/<frame_idx:04>.png.
 
@@ -192,7 +303,16 @@ def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, b
     seed itself).  `prompts_at` = {frame: [prompt strings]} replaces the text prompts from that frame on (image prompts stay; the weights are
     normalised together as at the start); a text is encoded when first needed and kept.
 
-    Refused before anything is loaded (ValueError): an init_image with '::MASK', 'invert=', 'upsample=' or 'ilvrN=', 'SOURCE=>TARGET'
+    `mode="3d"` replaces the affine warp by the camera's (module docstring; ops.frame_warp3d): `translation_x`, `translation_y`,
+    `translation_z`, `rotation_3d_x`, `rotation_3d_y`, `rotation_3d_z` and `fov` are numbers or keyframe strings, `near` the near plane;
+    everything else of the frame step is the same.  `depth`: None (flat, depth 1.0 everywhere: no parallax), a tensor (1 or B, 1, H, W) or
+    (H, W) used for every frame, or a callable that is called once per frame k > 0 with the previous frame's pred_xstart as (B, 3, H, W) in
+    [0, 1] on the GPU and returns such a tensor; the units are those in which the flat depth is 1.0.  `depth_iters` in 1..4: fixed-point steps
+    that look the depth up at the source pixel (1: the destination pixel's own depth).  A depth of the wrong shape, or one that is not finite
+    and positive everywhere, raises ValueError naming the frame.
+
+    Refused before anything is loaded (ValueError): an unknown `mode`, `zoom` / `angle` in 3D mode, a 3D-only argument in 2D mode,
+    `depth_iters` outside 1..4, a `fov` that leaves (0, 180), an init_image with '::MASK', 'invert=', 'upsample=' or 'ilvrN=', 'SOURCE=>TARGET'
     prompts, use_augs, a world size above 1, frames < 1, frames_skip outside [0, 1) or so high that no step is left, and prompts_at together
     with region prompts.  Everything else in `cgd_kwargs` passes through: samplers, '+thr=', '+windows=', '+model=', 'cuts=', regions, style,
     secondary, classifier."""
@@ -205,6 +325,7 @@ def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, b
     tracks = [keyframes(spec, frames) for spec in (zoom, angle, translation_x, translation_y)]
     if any(not z > 0 for z in tracks[0]):
         raise ValueError("zoom must stay positive on every frame")
+    tracks3d = _check_mode(mode, frames, zoom, angle, (translation_z, rotation_3d_x, rotation_3d_y, rotation_3d_z), fov, depth, depth_iters, near)
     seed = cgd_kwargs.get("seed", 0)
     run = entry.prepare_run(**cgd_kwargs, lpips_for_later=frames > 1 and frames_scale != 0)
     if run is None:
@@ -230,15 +351,26 @@ def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, b
             raise RuntimeError("The weights must not sum to 0.")
         cond_fn.set_targets([th.cat(e + list(img)) for e, img in zip(embeds, run.image_embeds)], w / w.sum().abs())
 
-    previous = stats0 = None
+    B = run.shape[0]
+    if mode == "3d" and depth is not None and not callable(depth):
+        depth = _depth_map(depth, 0, B, H, W)  # judged now that the frame size is known; it joins the state's device at its first use
+    previous = previous_x0 = stats0 = None
     for k in range(frames):
         if k in plan:
             retarget(plan[k])
         init = None
         if k > 0:
             th.manual_seed(seed if fixed_seed else seed + k)
-            matrix = motion_matrix(tracks[0][k], tracks[1][k], tracks[2][k], tracks[3][k], H, W)
-            init = ops.frame_warp(ctx, previous, matrix, interp=interp, border=border, clamp=True)
+            if mode == "3d":
+                cam = camera(tracks[2][k], tracks[3][k], *(t[k] for t in tracks3d), H, W, near=near)
+                if callable(depth):
+                    dmap = _depth_map(depth((previous_x0.clamp(-1, 1) + 1) / 2), k, B, H, W, previous.device)
+                else:
+                    dmap = depth = None if depth is None else depth.to(previous.device)
+                init = ops.frame_warp3d(ctx, previous, cam, depth=dmap, interp=interp, border=border, clamp=True, iters=depth_iters)
+            else:
+                matrix = motion_matrix(tracks[0][k], tracks[1][k], tracks[2][k], tracks[3][k], H, W)
+                init = ops.frame_warp(ctx, previous, matrix, interp=interp, border=border, clamp=True)
             if color_match > 0:
                 ops.color_match(ctx, init, stats0, amount=color_match, clamp=True)
             cond_fn.set_init(init if frames_scale != 0 else None, frames_scale)
@@ -249,6 +381,8 @@ def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, b
             raise RuntimeError(f"frame {k}: the sampler loop made no step")
         staged = script_util.stage_images(last["pred_xstart"])
         previous = last["sample"].detach().clone()  # the loop's buffers are reused by the next frame
+        if callable(depth) and k + 1 < frames:
+            previous_x0 = last["pred_xstart"].detach().clone()
         if k == 0 and color_match > 0 and frames > 1:
             stats0 = ops.channel_stats(ctx, previous)
         for batch_idx, path in run.write(staged.get().numpy(), k):
@@ -263,6 +397,17 @@ def build_parser():
                                 ("translation_x", "0", "pixels per frame, positive moves the content right"),
                                 ("translation_y", "0", "pixels per frame, positive moves the content down")):
         p.add_argument(f"--{name}", default=default, help=f"{what}: a number or keyframes 'FRAME:(VALUE), ...'")
+    p.add_argument("--mode", default="2d", choices=MODES, help="2d: affine warp (zoom, angle, translation_x / y); 3d: a moving pinhole camera")
+    for name, default, what in (("translation_z", "0", "3d: 1 / 200 depth units per frame, positive flies forward"),
+                                ("rotation_3d_x", "0", "3d: degrees per frame, positive tilts the camera up (the content moves down)"),
+                                ("rotation_3d_y", "0", "3d: degrees per frame, positive turns the camera right (the content moves left)"),
+                                ("rotation_3d_z", "0", "3d: degrees per frame, positive turns the picture counter-clockwise"),
+                                ("fov", "40", "3d: vertical field of view in degrees, inside (0, 180)")):
+        p.add_argument(f"--{name}", default=default, help=f"{what}: a number or keyframes 'FRAME:(VALUE), ...'")
+    p.add_argument("--depth_fn", default=None, help="3d: MODULE:FUNCTION, called with the previous frame (B,3,H,W) in [0,1], returns its depth "
+                                                    "(1 or B,1,H,W), 1.0 = the flat default; without it the depth is flat")
+    p.add_argument("--depth_iters", type=int, default=1, help="3d: fixed-point steps of the depth lookup, 1..4")
+    p.add_argument("--near", type=float, default=0.05, help="3d: the near plane, in depth units")
     p.add_argument("--border", default="wrap", choices=BORDERS, help="what the warp reads outside the frame")
     p.add_argument("--interp", default="bicubic", choices=INTERPS, help="interpolation of the warp")
     p.add_argument("--frames_skip", type=float, default=0.6, help="fraction of the schedule the frames after the first skip")
@@ -271,6 +416,19 @@ def build_parser():
     p.add_argument("--fixed_seed", action="store_true", help="the same seed for every frame instead of seed + frame")
     p.add_argument("--prompts_at", action="append", default=[], help="'FRAME=prompt|prompt...': the text prompts from FRAME on (repeatable)")
     return p
+
+
+def load_depth_fn(spec):
+    """'MODULE:FUNCTION' -> the callable (importlib); ValueError when the text has another form or the attribute is not callable."""
+    if spec is None:
+        return None
+    module, sep, name = str(spec).partition(":")
+    if not sep or not module.strip() or not name.strip():
+        raise ValueError(f"depth_fn {spec!r}: expected 'MODULE:FUNCTION'")
+    fn = getattr(importlib.import_module(module.strip()), name.strip(), None)
+    if not callable(fn):
+        raise ValueError(f"depth_fn {spec!r}: {name.strip()!r} of {module.strip()!r} is not callable")
+    return fn
 
 
 def main(argv=None):
@@ -282,7 +440,9 @@ def main(argv=None):
     kwargs.pop("save_frequency", None)  # one PNG per frame
     for item in animate(a.frames, zoom=a.zoom, angle=a.angle, translation_x=a.translation_x, translation_y=a.translation_y, border=a.border,
                         interp=a.interp, frames_skip=a.frames_skip, frames_scale=a.frames_scale, color_match=a.color_match,
-                        fixed_seed=a.fixed_seed, prompts_at=parse_prompts_at(a.prompts_at), **kwargs):
+                        fixed_seed=a.fixed_seed, prompts_at=parse_prompts_at(a.prompts_at), mode=a.mode, translation_z=a.translation_z,
+                        rotation_3d_x=a.rotation_3d_x, rotation_3d_y=a.rotation_3d_y, rotation_3d_z=a.rotation_3d_z, fov=a.fov,
+                        depth=load_depth_fn(a.depth_fn), depth_iters=a.depth_iters, near=a.near, **kwargs):
         print("\t".join(str(v) for v in item))
 
 

@@ -360,6 +360,11 @@ int cgd_frame_warp(cgd_ctx* ctx, const float* src, float* dst, int B, int C, int
   DeviceScope dev_scope__(ctx);
   return cgd_launch_frame_warp(ctx, src, dst, B, C, H, W, w, S(stream));
 }
+int cgd_frame_warp3d(cgd_ctx* ctx, const float* src, float* dst, const float* depth, int depth_batch, int B, int C, int H, int W,
+                     const cgd_camera* cam, void* stream) {
+  DeviceScope dev_scope__(ctx);
+  return cgd_launch_frame_warp3d(ctx, src, dst, depth, depth_batch, B, C, H, W, cam, S(stream));
+}
 int cgd_channel_stats(cgd_ctx* ctx, const float* x, float* stats, int B, int C, int H, int W, void* stream) {
   DeviceScope dev_scope__(ctx);
   return cgd_launch_channel_stats(ctx, x, stats, B, C, H, W, S(stream));

@@ -169,6 +169,11 @@ int cgd_launch_frame_warp(cgd_ctx* ctx, const float* src, float* dst, int B, int
 int cgd_launch_channel_stats(cgd_ctx* ctx, const float* x, float* stats, int B, int C, int H, int W, hipStream_t s);
 int cgd_launch_color_match(cgd_ctx* ctx, float* x, const float* stats_x, const float* stats_ref, int ref_batch, float amount, int clamp, int B,
                            int C, int H, int W, hipStream_t s);
+// warp3d.hip: the perspective warp of 3D animation (cgd_frame_warp3d); judged like the launchers of warp.hip, -2 before -3.  An identity
+// camera goes to cgd_launch_frame_warp with the identity matrix
+struct cgd_camera;
+int cgd_launch_frame_warp3d(cgd_ctx* ctx, const float* src, float* dst, const float* depth, int depth_batch, int B, int C, int H, int W,
+                            const cgd_camera* cam, hipStream_t s);
 // window.hip: the adjoint pair of windowed sampling (include/cgd_mi355x.h: cgd_window_gather / cgd_window_merge); oy [ny], ox [nx]: host arrays of
 // window origins; ay [ny][S], ax [nx][S]: device weight tables, both or neither (null = ones)
 int cgd_launch_window_gather(cgd_ctx* ctx, const float* full, float* win, const int* oy, int ny, const int* ox, int nx, const float* ay,

@@ -86,6 +86,13 @@ class Warp(C.Structure):
     _fields_ = [("m", C.c_double * 6), ("interp", i32), ("border", i32), ("clamp", i32)]
 
 
+class Camera(C.Structure):
+    """cgd_camera: the pinhole camera of cgd_frame_warp3d.  X' = R X + T between two frames (R row-major), focal length f in pixels, principal
+    point (cx, cy), flat depth z0, near plane, `iters` fixed-point steps of the depth lookup; interp / border / clamp as in cgd_warp"""
+    _fields_ = [("R", C.c_double * 9), ("T", C.c_double * 3), ("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("z0", C.c_double),
+                ("near", C.c_double), ("iters", i32), ("interp", i32), ("border", i32), ("clamp", i32)]
+
+
 WARP_INTERP = {"bilinear": 0, "bicubic": 1}
 WARP_BORDER = {"wrap": 0, "reflect": 1, "replicate": 2}
 
@@ -223,6 +230,7 @@ _SIGS = {
     "cgd_ilvr_scratch_floats": (C.c_long, [i32, i32, i32, i32, i32]),
     "cgd_ilvr_refine": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]),
     "cgd_frame_warp": (i32, [vp, vp, vp, i32, i32, i32, i32, C.POINTER(Warp), vp]),
+    "cgd_frame_warp3d": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(Camera), vp]),
     "cgd_channel_stats": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "cgd_color_match": (i32, [vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, i32, vp]),
     "cgd_window_gather": (i32, [vp, vp, vp, C.POINTER(i32), i32, C.POINTER(i32), i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),

@@ -348,6 +348,38 @@ def frame_warp(ctx, src, matrix, interp="bicubic", border="wrap", clamp=False, o
     return out
 
 
+def frame_warp3d(ctx, src, camera, depth=None, interp="bicubic", border="wrap", clamp=False, iters=1, out=None):
+    """Perspective resampling of src (B,C,H,W) in one launch (cgd_frame_warp3d): `camera` is what animate.camera returns (R, T, f, cx, cy, z0,
+    near: the motion X' = R X + T of a pinhole camera between two frames); `depth` None (flat, at camera.z0) or (1 or B, 1, H, W) in the units
+    of z0, resolved at the source pixel by `iters` in 1..4 fixed-point steps; interp, border, clamp as in frame_warp.  `out` must not alias
+    `src` or `depth`."""
+    ps = _nchw(src, "src")
+    if interp not in L.WARP_INTERP or border not in L.WARP_BORDER:
+        raise ValueError(f"interp must be one of {sorted(L.WARP_INTERP)} and border one of {sorted(L.WARP_BORDER)}, got {interp!r} and {border!r}")
+    R, T = [float(v) for v in camera.R], [float(v) for v in camera.T]
+    if len(R) != 9 or len(T) != 3:
+        raise ValueError(f"camera: expected 9 entries of R and 3 of T, got {len(R)} and {len(T)}")
+    if isinstance(iters, bool) or int(iters) != iters:
+        raise ValueError(f"iters must be an integer, got {iters!r}")
+    B, Cn, H, W = src.shape
+    pd = None
+    if depth is not None:
+        pd = _nchw(depth, "depth")
+        if tuple(depth.shape[1:]) != (1, H, W) or depth.shape[0] not in (1, B):
+            raise ValueError(f"depth: expected (1 or {B}, 1, {H}, {W}), got {tuple(depth.shape)}")
+        if depth.device != src.device:
+            raise ValueError(f"depth is on {depth.device}, src on {src.device}")
+    if out is None:
+        out = th.empty_like(src)
+    po = _nchw(out, "out")
+    if tuple(out.shape) != tuple(src.shape):
+        raise ValueError(f"out: shape {tuple(out.shape)}, src has {tuple(src.shape)}")
+    cam = L.Camera((C.c_double * 9)(*R), (C.c_double * 3)(*T), float(camera.f), float(camera.cx), float(camera.cy), float(camera.z0),
+                   float(camera.near), int(iters), L.WARP_INTERP[interp], L.WARP_BORDER[border], int(bool(clamp)))
+    ctx.check(ctx.lib.cgd_frame_warp3d(ctx.h, ps, po, pd, 0 if depth is None else int(depth.shape[0]), B, Cn, H, W, C.byref(cam), _s()))
+    return out
+
+
 def channel_stats(ctx, x, out=None):
     """(B,C,2): mean and population standard deviation of every plane of x (B,C,H,W), sums in fp64 (cgd_channel_stats)."""
     px = _nchw(x, "x")

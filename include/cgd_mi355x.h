@@ -612,6 +612,34 @@ int cgd_channel_stats(cgd_ctx* ctx, const float* x, float* stats, int B, int C, 
 int cgd_color_match(cgd_ctx* ctx, float* x, const float* stats_x, const float* stats_ref, int ref_batch, float amount, int clamp, int B, int C,
                     int H, int W, void* stream);
 
+/* ---- 3D animation (Disco Diffusion's 3D mode, Deforum): frame k starts from frame k - 1 as a pinhole camera sees it after moving, with a
+ *      depth for every pixel (parallax).  One launch; NCHW fp32, any C.
+ *      Camera axes: x right, y down, z into the screen; pixel centres sit on integers; (cx, cy) is the principal point and f the focal
+ *      length in pixels.  A source position q of depth z > 0 is the point X = z ((qx - cx) / f, (qy - cy) / f, 1); the motion between two
+ *      frames is X' = R X + T (R row-major); X' is seen at (cx, cy) + f (X'x, X'y) / X'z.  cgd_frame_warp3d gathers: destination pixel p reads
+ *      the source at G(p, z), the exact inverse of that map for a source point of depth z,
+ *        r = ((px - cx) / f, (py - cy) / f, 1),  a = R^T r with a_z <- max(a_z, 1e-6),  b = R^T T,
+ *        lambda = max((z + b_z) / a_z, near),  Xs = lambda a - b,  G = (cx + f Xs_x / z, cy + f Xs_y / z)
+ *      all in fp64.  depth NULL: z = max(z0, near) everywhere (a homography).  depth (depth_batch, 1, H, W), depth_batch 1 or B, in the units
+ *      of z0: the depth belongs to the unknown source pixel and is resolved by `iters` fixed-point steps s_0 = p,
+ *      s_{k+1} = G(p, max(D(s_k), near)); D(s) is bilinear with a replicate border, taps and weights in fp64, exactly the stored value at an
+ *      integer position; a NaN depth reads as near.  The final position is clamped to +-2^30, then floored, split and sampled exactly as
+ *      cgd_frame_warp samples (interp, border, clamp as there, the same summation order).  A camera with R = I and T = 0 exactly copies
+ *      bits, with or without a depth map.  Gather form, no atomics, no scratch buffer: the same bits on every run.  Plane offsets are
+ *      64-bit.  Returns -2 (cgd_last_error), before any launch and before the context is looked at, for a null src, dst or cam, a dst that
+ *      overlaps src or depth, a pointer that is not 4-byte aligned, a non-positive size, H W >= 2^31, an unknown interp or border, iters
+ *      outside 1..4, a non-finite camera entry, f, z0 or near <= 0, max |R R^T - I| > 1e-9 or det R < 0, or a depth_batch other than 1 or
+ *      B when depth is given; an accepted call returns -3 with a NULL context. ---- */
+typedef struct cgd_camera {
+  double R[9], T[3], f, cx, cy, z0, near;
+  int iters;  /* fixed-point steps of the depth lookup, 1..4 (not used without a depth map) */
+  int interp; /* 0 bilinear, 1 bicubic */
+  int border; /* 0 wrap, 1 reflect, 2 replicate */
+  int clamp;  /* 1: clamp the result to [-1, 1] */
+} cgd_camera;
+int cgd_frame_warp3d(cgd_ctx* ctx, const float* src, float* dst, const float* depth, int depth_batch, int B, int C, int H, int W,
+                     const cgd_camera* cam, void* stream);
+
 /* ---- windowed sampling (MultiDiffusion, Bar-Tal et al., 2023): the frame is cut into overlapping S x S windows of the model's trained size, the
  *      model runs on all windows as one batch, and the window outputs are averaged into one prediction for the frame.  An adjoint pair, one
  *      launch each whatever B, C and the window count:

@@ -279,29 +279,48 @@ __global__ __launch_bounds__((BM / WM) * (BN / 32) * 64) void sconv_kernel(const
   }
 }
 
-template <int MODE, int DGRAD>
-int sconv_launch_mode(cgd_ctx* ctx, const float* A, const float* Bw, float* C, const float* bias, const float* R, SconvParams p, hipStream_t s) {
+// The tile and split-K choice of one launch: pure host logic, shared by the launcher below and by cgd_op_plan_conv_s2 (CPU tests).
+// M: rows (per parity class in the backward), N: output columns, Kc: channels per tap of the contraction.
+struct SconvPlan {
+  int bm, bn, ntm, ntn, splitk;
+  long grid;  // workgroups along gridDim.x
+};
+SconvPlan sconv_select(bool dgrad, int M, int N, int Kc, int num_cu, bool have_ws, size_t ws_bytes) {
+  SconvPlan pl;
   // 128 x 64 tiles (four wavefronts of 64 x 32) where they give every CU a workgroup; 64 x 32 (two wavefronts of 32 x 32) below that
-  const long big = (long)cdiv(p.M, 128) * cdiv(p.N, 64) * (DGRAD ? 4 : 1);
-  const bool small = big < ctx->num_cu;
-  const int bm = small ? 64 : 128, bn = small ? 32 : 64;
-  p.ntm = cdiv(p.M, bm);
-  p.ntn = cdiv(p.N, bn);
-  const long tiles = (long)p.ntm * p.ntn;
-  const long grid = DGRAD ? (long)cdiv(tiles, 8) * 32 : tiles;
-  if (grid > 0x7fffffffL) CGD_FAIL(ctx, "conv3x3_s2: too many tiles for one launch");
+  const long big = (long)cdiv(M, 128) * cdiv(N, 64) * (dgrad ? 4 : 1);
+  const bool small = big < num_cu;
+  pl.bm = small ? 64 : 128;
+  pl.bn = small ? 32 : 64;
+  pl.ntm = cdiv(M, pl.bm);
+  pl.ntn = cdiv(N, pl.bn);
+  const long tiles = (long)pl.ntm * pl.ntn;
+  pl.grid = dgrad ? (long)cdiv(tiles, 8) * 32 : tiles;
   // Split-K for the small maps (a 16 x 16 x 512 input is 16 tiles of 144 K tiles each): about two workgroups per CU, at least two K tiles per slice
   // of the shortest contraction (the backward's 1-tap class), at most 16 slices, through the context's workspace and its deferred-slice record
   // exactly as cgd_launch_gemm does it: the slices are summed, with bias and `add`, by the reduce launch of cgd_flush_pending
-  const long out_rows = DGRAD ? 4L * p.M : p.M;
-  const long work = tiles * (DGRAD ? 4 : 1);
-  const int short_nkt = (DGRAD ? 1 : 9) * (p.Kc / SBK);
-  p.splitk = 1;
-  if (work < ctx->num_cu && ctx->ws) {
-    long want = std::min<long>(std::min<long>(cdiv(2L * ctx->num_cu, work), short_nkt / 2), 16);
-    while (want > 1 && (size_t)want * out_rows * p.N * sizeof(float) > ctx->ws_bytes) --want;
-    if (want >= 2) p.splitk = (int)want;
+  const long out_rows = dgrad ? 4L * M : M;
+  const long work = tiles * (dgrad ? 4 : 1);
+  const int short_nkt = (dgrad ? 1 : 9) * (Kc / SBK);
+  pl.splitk = 1;
+  if (work < num_cu && have_ws) {
+    long want = std::min<long>(std::min<long>(cdiv(2L * num_cu, work), short_nkt / 2), 16);
+    while (want > 1 && (size_t)want * out_rows * N * sizeof(float) > ws_bytes) --want;
+    if (want >= 2) pl.splitk = (int)want;
   }
+  return pl;
+}
+
+template <int MODE, int DGRAD>
+int sconv_launch_mode(cgd_ctx* ctx, const float* A, const float* Bw, float* C, const float* bias, const float* R, SconvParams p, hipStream_t s) {
+  const SconvPlan pl = sconv_select(DGRAD, p.M, p.N, p.Kc, ctx->num_cu, ctx->ws != nullptr, ctx->ws_bytes);
+  const bool small = pl.bm == 64;
+  p.ntm = pl.ntm;
+  p.ntn = pl.ntn;
+  p.splitk = pl.splitk;
+  const long grid = pl.grid;
+  if (grid > 0x7fffffffL) CGD_FAIL(ctx, "conv3x3_s2: too many tiles for one launch");
+  const long out_rows = DGRAD ? 4L * p.M : p.M;
   p.ws_stride = out_rows * p.N;
   const dim3 g((unsigned)grid, (unsigned)p.splitk);
   ProfRec pr;  // with the MFMA GEMM kernels and their split-K reduce (kind 0)
@@ -389,4 +408,16 @@ int cgd_launch_sconv_dgrad(cgd_ctx* ctx, const float* dy, int lddy, const float*
   p.b_bytes = (unsigned)((long)Cin * 9 * Cout * 4);
   cgd_chanstats_invalidate(ctx, dx, (long)B * H * W, lddx, Cin);
   return sconv_launch<1>(ctx, dy, wd, dx, nullptr, add, p, s);
+}
+
+// Host-only view of sconv_select (no GPU, no context; the context's fixed 256 MiB workspace): out4 = {tile rows, tile columns, split-K slices,
+// workgroups of the main launch} of the forward (dgrad = 0) or the backward (dgrad = 1) of a dense (B, H, W, Cin) -> Cout problem; B, H, W: the
+// INPUT's.  -2 where cgd_op_conv3x3_s2_accepts refuses the problem.  Test support, as cgd_op_attn_plan.
+extern "C" int cgd_op_plan_conv_s2(int dgrad, int B, int H, int W, int Cin, int Cout, int num_cu, int* out4) {
+  if (!out4) return -3;
+  if (cgd_sconv_refusal(dgrad, dgrad ? Cout : Cin, dgrad ? Cin : Cout, 0, B, H, W, Cin, Cout)) return -2;
+  const int M = B * (H / 2) * (W / 2);
+  const SconvPlan pl = sconv_select(dgrad != 0, M, dgrad ? Cin : Cout, dgrad ? Cout : Cin, num_cu > 0 ? num_cu : cgd_ctx().num_cu, true, (size_t)256 << 20);
+  out4[0] = pl.bm; out4[1] = pl.bn; out4[2] = pl.splitk; out4[3] = (int)(pl.grid * pl.splitk);
+  return 0;
 }

@@ -248,6 +248,7 @@ _SIGS = {
     "cgd_op_conv3x3_s2": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_op_conv3x3_s2_dgrad": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_op_conv3x3_s2_accepts": (i32, [i32] * 9),
+    "cgd_op_plan_conv_s2": (i32, [i32] * 7 + [C.POINTER(i32)]),
     "cgd_op_conv3x3_s2_packed": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_op_conv3x3_s2_dgrad_packed": (i32, [vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "cgd_op_conv3x3": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),

@@ -785,6 +785,11 @@ int cgd_op_conv3x3_s2(cgd_ctx* ctx, const float* x_nhwc, int ldx, const float* w
 int cgd_op_conv3x3_s2_dgrad(cgd_ctx* ctx, const float* dy_nhwc, int lddy, const float* w_torch, float* dx_nhwc, int lddx, const float* add,
                             int ldadd, int B, int H, int W, int Cin, int Cout, void* stream);
 int cgd_op_conv3x3_s2_accepts(int dgrad, int ld_in, int ld_out, int ldadd, int B, int H, int W, int Cin, int Cout);
+/* host-only (no GPU, no context; test support, as cgd_op_attn_plan): the launcher's tile and split-K choice for the forward (dgrad = 0) or the backward
+ * (dgrad = 1) of a dense problem on a device of num_cu compute units with the context's fixed 256 MiB workspace; B, H, W: the INPUT's.
+ * out4 = {tile rows (128 | 64), tile columns (64 | 32), split-K slices, workgroups of the main launch (the backward's grid is rounded up to whole
+ * groups of 8 tiles x 4 parity classes; the surplus workgroups return at once)}.  -2 where cgd_op_conv3x3_s2_accepts refuses the problem. */
+int cgd_op_plan_conv_s2(int dgrad, int B, int H, int W, int Cin, int Cout, int num_cu, int* out4);
 /* The same two on weights the caller packed once (what the UNet's Downsample runs per step; benchmarks time these, so that no per-call weight
  * pack is inside the figure): w_fwd [Cout][9 Cin] with column (ky * 3 + kx) * Cin + ci, w_dgrad [Cin][9 Cout] with column
  * ((2 - ky) * 3 + (2 - kx)) * Cout + co = w[co][ci][ky][kx] (ops.pack_conv3x3 gives both). */

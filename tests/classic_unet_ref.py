@@ -139,3 +139,7 @@ FLAG_COMBOS = [(True, True), (True, False), (False, True), (False, False)]  # (r
 TINY = dict(image_size=32, model_channels=64, num_res_blocks=1, attention_resolutions="16", channel_mult=(1, 2), num_heads=1)
 # the comics-faces / pixel-art configuration (cgd.model_flags.COMMUNITY_LOOKUP)
 COMICS = dict(image_size=256, model_channels=128, num_res_blocks=2, attention_resolutions="16", num_heads=1)
+# the STRUCTURE of that configuration at a quarter of its width: six levels, five Downsamples and Upsamples, two ResBlocks per level, one-head
+# attention where the map is 1 / 16 of the frame (128 channels here, 512 in the checkpoints); frames must be multiples of 32
+NARROW = dict(COMICS, model_channels=32, channel_mult=(1, 1, 2, 2, 4, 4))
+CASES = {"tiny": TINY, "narrow": NARROW, "comics": COMICS}

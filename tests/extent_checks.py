@@ -409,6 +409,100 @@ def check_conv_far(precision=1):
 
 
 # ---------------------------------------------------------------------------------------------------------
+SCONV_REFUSE = "an operand of 2^31 bytes or more"
+
+
+def sconv_below_at(rows, width):
+    """(largest accepted, smallest refused) row stride of a stride-2 conv operand of `rows` rows of `width` floats: cgd_sconv_refusal counts
+    the operand's extent ((rows - 1) * ld + width) * 4 < 2^31 bytes, not rows * ld"""
+    b = ((P31 // 4 - 1 - width) // (rows - 1)) // 4 * 4
+    assert ((rows - 1) * b + width) * 4 < P31 <= ((rows - 1) * (b + 4) + width) * 4
+    return b, b + 4
+
+
+# (far operand, B, Cin, Cout): 8 x 8 input maps.  The forward splits K (4 slices at 32 channels per tap, 9 at 64: the reduce launch writes y), the
+# backward at 32 / 64 channels per tap does not (the kernel's own epilogue writes dx and reads add) and at 128 takes two slices (the reduce does)
+SCONV_FAR = (("x", 1, 32, 64), ("x", 2, 64, 32), ("y", 2, 32, 64), ("y", 1, 64, 32), ("dy", 2, 32, 32), ("dy", 1, 64, 64), ("dx", 1, 32, 64),
+             ("dx", 2, 64, 128), ("add", 2, 32, 64), ("add", 1, 64, 128))
+
+
+def sconv_far_shape(far, Bn, Ci, Co, H=8, W=8):
+    """(shape of the far operand, backward?)"""
+    return {"x": ((Bn, H, W, Ci), 0), "y": ((Bn, H // 2, W // 2, Co), 0), "dy": ((Bn, H // 2, W // 2, Co), 1), "dx": ((Bn, H, W, Ci), 1),
+            "add": ((Bn, H, W, Ci), 1)}[far]
+
+
+def _sconv_run(ctx, p, tag, far, Bn, Ci, Co, ld, col, refuse=None):
+    """cgd_op_conv3x3_s2 (far x / y) or cgd_op_conv3x3_s2_dgrad with add (far dy / dx / add) at Bn x 8 x 8"""
+    lib = ctx.lib
+    H = W = 8
+    shape, dgrad = sconv_far_shape(far, Bn, Ci, Co)
+    w = _r((Co, Ci, 3, 3), 6) / math.sqrt(9 * Ci)
+    wd = w.to(DEV)
+    name = f"conv3x3_s2[p{p}] far {far} {tag} B{Bn} {Ci}->{Co} ld{ld}+{col}"
+    big, small = (Bn, H, W, Ci), (Bn, H // 2, W // 2, Co)
+    if not dgrad:
+        x, b = _r(big, 5), _r((Co,), 7, 0.3)
+        bd = b.to(DEV)
+        X = _op(big, ld if far == "x" else Ci + 32, col if far == "x" else 32, far == "x")
+        Y = _op(small, ld if far == "y" else Co + 32, col if far == "y" else 16, far == "y")
+
+        def launch():
+            ctx.check(lib.cgd_op_conv3x3_s2(ctx.h, X.ptr, X.ld, wd.data_ptr(), bd.data_ptr(), Y.ptr, Y.ld, Bn, H, W, Ci, Co, _s()))
+
+        if refuse:
+            X.load(x, GAP[0])
+            return _refusal(ctx, name, [Y], launch, refuse)
+        ref = F.conv2d(x.double().permute(0, 3, 1, 2), w.double(), b.double(), stride=2, padding=1).permute(0, 2, 3, 1)
+        return _case(ctx, name, [(X, x)], [Y], [ref], launch, GEMM_ROUTE)
+    dy, add = _r(small, 8), _r(big, 9, 0.3)
+    xr = th.zeros(Bn, Ci, H, W, dtype=th.float64, requires_grad=True)
+    (gx,) = th.autograd.grad(F.conv2d(xr, w.double(), None, stride=2, padding=1), xr, dy.double().permute(0, 3, 1, 2))
+    sd = unit_seed(gx)
+    dy = dy * sd
+    ref = gx.permute(0, 2, 3, 1) * sd + add.double()
+    DY = _op(small, ld if far == "dy" else Co + 32, col if far == "dy" else 32, far == "dy")
+    DX = _op(big, ld if far == "dx" else Ci + 32, col if far == "dx" else 16, far == "dx")
+    AD = _op(big, ld if far == "add" else Ci + 48, col if far == "add" else 4, far == "add")
+
+    def launch():
+        ctx.check(lib.cgd_op_conv3x3_s2_dgrad(ctx.h, DY.ptr, DY.ld, wd.data_ptr(), DX.ptr, DX.ld, AD.ptr, AD.ld, Bn, H, W, Ci, Co, _s()))
+
+    if refuse:
+        DY.load(dy, GAP[0])
+        AD.load(add, GAP[0])
+        return _refusal(ctx, name, [DX], launch, refuse)
+    return _case(ctx, name, [(DY, dy), (AD, add)], [DX], [ref], launch, GEMM_ROUTE)
+
+
+def check_sconv_far(precision=1):
+    """cgd_op_conv3x3_s2 / _dgrad at B x 8 x 8 with ONE far operand (SCONV_FAR): x, y of the forward, dy, dx, add of the backward, each at the
+    last row stride cgd_sconv_refusal accepts (the operand ends within one stride step below 2^31 bytes; the columns once at the right edge of the
+    stride, once at 16) and at the next one up, which must be refused with nothing written.  Both the call and cgd_op_conv3x3_s2_accepts are
+    asked.  sconv_kernel forms 32-bit byte offsets for x / dy and the weights; y, dx and add are indexed with 64-bit rows."""
+    ctx = _ctx(precision)
+    lib, out = ctx.lib, []
+    try:
+        for far, Bn, Ci, Co in SCONV_FAR:
+            shape, dgrad = sconv_far_shape(far, Bn, Ci, Co)
+            lb, la = sconv_below_at(math.prod(shape[:-1]), shape[-1])
+            for side, ld, cols in (("below", lb, (lb - shape[-1], 16)), ("at", la, (la - shape[-1],))):
+                cin, cout = (Co, Ci) if dgrad else (Ci, Co)
+                lds = {"in": cin + 32, "out": cout + 32, "add": Ci + 48 if dgrad else 0}
+                lds[{"x": "in", "dy": "in", "y": "out", "dx": "out", "add": "add"}[far]] = ld
+                acc = int(lib.cgd_op_conv3x3_s2_accepts(dgrad, lds["in"], lds["out"], lds["add"], Bn, 8, 8, Ci, Co))
+                out.append(_flag(f"conv3x3_s2 far {far} {side} ld{ld}: cgd_op_conv3x3_s2_accepts says {acc}", acc == int(side == "below")))
+                if acc != int(side == "below"):
+                    continue  # (a stride the predicate would let through is not launched)
+                for col in cols:
+                    out += _sconv_run(ctx, precision, side, far, Bn, Ci, Co, ld, col, refuse=None if side == "below" else SCONV_REFUSE)
+        th.cuda.synchronize()
+    finally:
+        release()
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
 WINO_REFUSE = "Winograd conv kernel does not support this problem"
 
 

@@ -640,6 +640,71 @@ def check_precision_switch():
     return recs
 
 
+# ---- the classic architecture (conv resampling, additive embedding) through the same sequences ------------------------------------------------
+CLASSIC_CASE = "classic_narrow"
+CLASSIC_WALK = [(1, 64, 64), (2, 128, 128), (1, 64, 64), (2, 32, 64), (1, 128, 128), (2, 128, 128)]
+CLASSIC_WARM = [(1, 64, 64), (2, 32, 64), (2, 128, 128), (1, 128, 128)]
+
+
+def check_classic_walk():
+    """One handle of the narrow community structure through CLASSIC_WALK at precision 1: Downsample / Upsample own grow-only buffers (`out`, `dx`,
+    `d1`), views stashed into the concat buffers (`dst`) and the B, H, W the forward saved for the backward; the step to 128 x 128 grows them all,
+    the way back runs on buffers that are too large, 32 x 64 is non-square with a 1 x 2 bottom map.  Then CLASSIC_WARM, during which the context
+    must not allocate."""
+    ctx = _ctx(1)
+    seed = SEEDS["unet"][0]
+    dev = _handle(ctx, "unet", seed, CLASSIC_CASE)
+    recs = walk([], "classic walk", dev, unet_calls(CLASSIC_WALK, CLASSIC_CASE), seed)
+    a0 = allocs(ctx)
+    for k, (B, H, W) in enumerate(CLASSIC_WARM):
+        call = UNetCall(B, H, W, CLASSIC_WALK.index((B, H, W)), CLASSIC_CASE)
+        judge(recs, f"classic warm pass {k}", call, seed, run_pass(call, dev, seed))
+    recs.append(_flag(f"classic warm: no device allocation in {len(CLASSIC_WARM)} passes after the largest shape ({allocs(ctx) - a0} made)", allocs(ctx) == a0))
+    dev.close()
+    return recs
+
+
+def check_classic_order_reupload_and_precision():
+    """forward(A) forward(B) dgrad, three dgrads of one forward, a forward refused for its frame (48 x 48 is no multiple of 32) between a forward
+    and its dgrad; weights of seed 2 into the handle that ran seed 1 (the packed stride-2 conv weights are refilled); precision 1 -> 0 -> 1"""
+    recs = []
+    ctx = _ctx(1)
+    s1, s2 = SEEDS["unet"]
+    dev = _handle(ctx, "unet", s1, CLASSIC_CASE)
+    A, Bc = UNetCall(1, 64, 64, 0, CLASSIC_CASE), UNetCall(2, 32, 64, 3, CLASSIC_CASE)
+    bad, obuf = th.zeros(1, 3, 48, 48, device=DEV), _nan_like((1, 6, 48, 48))
+    _order(recs, "classic order:", dev, A, Bc, s1, lambda: dev.forward(bad, A.t.to(DEV), None, out=obuf), UNetCall(1, 64, 64, 2, CLASSIC_CASE))
+    recs.append(_flag("classic order: the refused forward wrote nothing", _untouched(obuf)))
+    _load(dev, "unet", s2, CLASSIC_CASE)
+    judge(recs, "classic re-upload: seed 2 into the handle that ran seed 1", A, s2, run_pass(A, dev, s2))
+    _load(dev, "unet", s1, CLASSIC_CASE)
+    for p in (1, 0, 1):
+        ctx.set_precision(p)
+        judge(recs, f"classic precision switch -> {p}", A, s1, run_pass(A, dev, s1), p)
+    dev.close()
+    return recs
+
+
+def check_classic_shared_context():
+    """a classic and a published-architecture handle interleaved in one context: forward(classic), forward(mini), dgrad(classic), dgrad(mini), twice
+    (the split-K workspace, `ctx->pending`, the GroupNorm record pool and the packed-weight scratch are the context's)"""
+    recs = []
+    ctx = _ctx(1)
+    seed = SEEDS["unet"][0]
+    classic, mini = _handle(ctx, "unet", seed, CLASSIC_CASE), _handle(ctx, "unet", seed, UNET_CASE)
+    for k, (cc, cm) in enumerate(((UNetCall(1, 64, 64, 0, CLASSIC_CASE), UNetCall(1, 64, 64, 0)), (UNetCall(2, 32, 64, 3, CLASSIC_CASE), UNetCall(2, 32, 64, 6)))):
+        fc = cc.forward(classic).clone()
+        fm = cm.forward(mini).clone()
+        gc = cc.dgrad(classic, oracle(cc, seed)["sd"]).clone()
+        gm = cm.dgrad(mini, oracle(cm, seed)["sd"]).clone()
+        th.cuda.synchronize()
+        judge(recs, f"classic + mini interleaved, round {k}", cc, seed, (fc.cpu(), gc.cpu()))
+        judge(recs, f"classic + mini interleaved, round {k}", cm, seed, (fm.cpu(), gm.cpu()))
+    classic.close()
+    mini.close()
+    return recs
+
+
 # ---- 9. two sampler runs on the same objects ----------------------------------------------------------------------------------------------
 def check_two_runs():
     """The `mini` scene of step_checks.py, two guided steps at 64 x 64, then another scene (64 x 96, other prompt weights, other cutn) on the same
@@ -690,6 +755,23 @@ def unet_buffer_counts(case, B, H, W):
     return out
 
 
+def classic_resample_counts(case, B, H, W):
+    """Host-only: element counts of the grow-only buffers of the classic architecture's resampling modules (unet.hip Downsample / Upsample), from the
+    configuration: the Downsample under level l reads B x h x w x ch (`dx`) and writes a quarter of it (`out`); the Upsample above level l + 1
+    reads B x (h / 2) x (w / 2) x ch' (`dx`) and writes four times that (`out`, and `d1`, the conv's gradient at the high resolution)"""
+    kw = pc.UNET_CASES[case]
+    mult, mc = kw["channel_mult"], kw["model_channels"]
+    out = {}
+    for lvl in range(len(mult) - 1):
+        h, w = H >> lvl, W >> lvl
+        ch, chu = int(mult[lvl] * mc), int(mult[lvl + 1] * mc)
+        out[f"Downsample {lvl} dx"] = B * h * w * ch
+        out[f"Downsample {lvl} out"] = B * (h // 2) * (w // 2) * ch
+        out[f"Upsample {lvl + 1} dx"] = B * (h // 2) * (w // 2) * chu
+        out[f"Upsample {lvl + 1} out"] = out[f"Upsample {lvl + 1} d1"] = B * h * w * chu
+    return out
+
+
 GROUPS = {
     "unet_walk": [lambda: check_unet_shape_walk(1), lambda: check_unet_shape_walk(0), check_unet_cfg64_walk],
     "order": [check_pass_order],
@@ -699,4 +781,5 @@ GROUPS = {
     "precision": [check_precision_switch],
     "towers": [check_tower_walks],
     "two_runs": [check_two_runs],
+    "classic": [check_classic_walk, check_classic_order_reupload_and_precision, check_classic_shared_context],
 }

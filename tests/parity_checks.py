@@ -788,8 +788,16 @@ UNET_CASES = {
 }
 
 
+# the structure of the community checkpoints of the classic architecture at a quarter of their width (tests/classic_unet_ref.NARROW): conv
+# resampling, additive embedding, six levels, one attention head
+UNET_CASES["classic_narrow"] = dict(image_size=256, model_channels=32, num_res_blocks=2, attention_resolutions="16", channel_mult=(1, 1, 2, 2, 4, 4),
+                                    num_heads=1, resblock_updown=False, use_scale_shift_norm=False)
+
+
 def oracle_unet(case, seed=1234, head_scale=1.0):
     from oracle.unet import UNetModel, synthetic_init_
+    if "resblock_updown" in UNET_CASES[case]:  # the classic architecture has its reference in the tests
+        from tests.classic_unet_ref import ClassicUNetModel as UNetModel  # noqa: F811
     ref = synthetic_init_(UNetModel(**UNET_CASES[case]), seed=seed).eval()
     if head_scale != 1.0:  # small eps-hat / variance head (tests/step_checks.py explains the tame scenario)
         with th.no_grad():

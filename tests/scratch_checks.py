@@ -251,6 +251,10 @@ def _attn_rows():
             add(2, 2, T, d, i & 1)  # the generic family: all five buffers
     for T in (33, 65):
         add(2, 3, T, 64, 0, causal=1)
+    for T in (255, 256, 257):  # one head of 512 channels (the classic architecture's community checkpoints at 256 x 256): generic, all five buffers
+        for nb in (1, 2):
+            for legacy in (0, 1):
+                add(nb, 1, T, 512, legacy)
     for T in (33, 64):  # the one-workgroup backward: statistics rows of Tq = 64
         add(2, 3, T, 64, 0, ctxs=("p1_flash3",))
     return rows

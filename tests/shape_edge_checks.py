@@ -80,6 +80,21 @@ CLAUSES = {
     "attn.block32": ("attn.hip", 769, "cdiv(T, 32)", "T a multiple of the 32-row block / one key or query either side"),
     "attn.generic": ("attn.hip", 687, "ATTN_GENERIC", "d = 64 on a fused family / any other head dim on batched GEMMs"),
     "attn.d80": ("attn.hip", 677, "sh.d != 80", "d = 80: T <= 32 on batched GEMMs / T > 32 on the flash kernels (bf16x3)"),
+    "sconv.tile": ("sconv.hip", 292, "big < num_cu", "fewer 128 x 64 tiles than CUs: the 64 x 32 tile / big >= num_cu (256 = num_cu exactly included): 128 x 64"),
+    "sconv.rows": ("sconv.hip", 295, "cdiv(M, pl.bm)", "M <= bm: one row tile / a second, ragged one (a_ok, sconv.hip:99)"),
+    "sconv.cols": ("sconv.hip", 296, "cdiv(N, pl.bn)", "N <= bn / N > bn (b_off, sconv.hip:110; the last column tile half filled where N % bn)"),
+    "sconv.grid8": ("sconv.hip", 298, "cdiv(tiles, 8) * 32", "backward: a tile count that is a multiple of 8 / surplus workgroups return (sconv.hip:82)"),
+    "sconv.work": ("sconv.hip", 306, "work < num_cu", "fewer workgroups than CUs: split-K is considered / work >= num_cu: one slice"),
+    "sconv.short": ("sconv.hip", 307, "short_nkt / 2", "the slice count comes from the work or the cap of 16 / from two K tiles per slice of the shortest class"),
+    "sconv.cap16": ("sconv.hip", 307, ", 16)", "fewer than 16 slices / the cap of 16"),
+    "sconv.want2": ("sconv.hip", 309, "want >= 2", "at least two slices: split / the shortest class has fewer than 4 K tiles: one slice"),
+    "sconv.empty_slice": ("sconv.hip", 221, "if (kt0 < kt1)", "every slice of every parity class has K tiles / a slice is empty and writes a zero slab"),
+    "sconv.size": ("sconv.hip", 364, "H < 2 || W < 2", "a map of at least 2 x 2 / refused"),
+    "sconv.even": ("sconv.hip", 365, "(H | W) & 1", "even H and W / refused"),
+    "sconv.c32": ("sconv.hip", 366, "(Cin & 31) || (Cout & 31)", "Cin and Cout multiples of 32 / refused"),
+    "sconv.ld": ("sconv.hip", 368, "ld_in < c_in || ld_out < c_out", "row strides of at least the channel count / refused"),
+    "sconv.ld4": ("sconv.hip", 369, "(ld_in | ld_out | ldadd) & 3", "row strides multiples of 4 / refused"),
+    "sconv.lim": ("sconv.hip", 372, ">= lim", "every operand below 2^31 bytes / refused (the far-extent tier sits on the line itself)"),
     "gn.small_hw": ("norm.hip", 1257, "HW <= GN_SMALL_HW", "HW <= 1024: single launch / the chunked kernels"),
     "gn.c32": ("norm.hip", 1213, "C % 32 || C > 4096", "C a multiple of 32 up to 4096 / C = 48, 4128 refused"),
     "gn.v4": ("norm.hip", 1120, "!(cpg & 3)", "4 | C / 32: float4 kernel / scalar kernel"),
@@ -105,6 +120,9 @@ REFUSED = {
     "kconv": "weight-streaming conv kernel does not support this problem", "wconv": "Winograd conv kernel does not support this problem",
     "gn": "C must be a multiple of 32 and <= 4096", "c4": "C and strides must be multiples of 4", "pool.size": "must be positive",
     "ups.even": "positive and even", "bil": "C and the row strides must be multiples of 4",
+    "sconv.size": "B, H and W must be positive", "sconv.even": "H and W must be even", "sconv.c32": "Cin and Cout must be positive multiples of 32",
+    "sconv.ld": "a row stride is smaller than its channel count", "sconv.ld4": "row strides must be multiples of 4",
+    "sconv.lim": "an operand of 2^31 bytes or more",
 }
 ROUTES = {
     "gemm": ("igemm/hgemm/kgemm/gemv (kind 0, no halo kernel)", lambda c: c[0] >= 1 and all(c[j] == 0 for j in HALO)),
@@ -344,6 +362,12 @@ def _attn_rows():
             add(2, 2, T, d, i & 1)
     for T in (1, 2, 31, 32, 33, 65):
         add(2, 3, T, 64, 0, causal=1)
+    # one head of 512 channels over a 16 x 16 map (the community checkpoints of the classic architecture at a 256 x 256 frame) and one
+    # position either side: batched GEMMs with K = 512 (QK^T) and K = T (PV), both head orders
+    for T in (255, 256, 257):
+        for nb in (1, 2):
+            for legacy in (0, 1):
+                add(nb, 1, T, 512, legacy)
     return rows
 
 
@@ -430,7 +454,102 @@ def _elem_rows():
     return rows
 
 
-TABLE = _gemm_rows() + _halo_rows() + _wino_rows() + _attn_rows() + _norm_rows() + _elem_rows()
+def sconv_plan(dgrad, B, H, W, Ci, Co, num_cu=NUM_CU):
+    """restatement of sconv.hip sconv_select for a dense problem: dict(M, N, Kc, bm, bn, ntm, ntn, tiles, work, short, want, sk, wg).  M: rows
+    (per parity class in the backward), want: the slice count before `want >= 2` (the 256 MiB workspace never binds: the host file enumerates)"""
+    M, N, Kc = B * (H // 2) * (W // 2), (Ci if dgrad else Co), (Co if dgrad else Ci)
+    cls = 4 if dgrad else 1
+    small = ceil_div(M, 128) * ceil_div(N, 64) * cls < num_cu
+    bm, bn = (64, 32) if small else (128, 64)
+    ntm, ntn = ceil_div(M, bm), ceil_div(N, bn)
+    tiles = ntm * ntn
+    work, short = tiles * cls, (1 if dgrad else 9) * (Kc // 32)
+    want = min(ceil_div(2 * num_cu, work), short // 2, 16) if work < num_cu else 1
+    sk = want if want >= 2 else 1
+    return dict(M=M, N=N, Kc=Kc, bm=bm, bn=bn, ntm=ntm, ntn=ntn, tiles=tiles, work=work, short=short, want=want, sk=sk,
+                wg=(ceil_div(tiles, 8) * 32 if dgrad else tiles) * sk)
+
+
+def sconv_empty(dgrad, Kc, sk):
+    """empty slices per parity class (taps 1, 2, 2, 4; the forward is one class of 9 taps)"""
+    return [empty_slices(t * (Kc // 32), sk) for t in ((1, 2, 2, 4) if dgrad else (9,))]
+
+
+def _sconv_rows():
+    rows = {}
+    ctx3 = ("p0", "p1", "p2")
+
+    def add(dgrad, B, H, W, Kc, N, verdict="run", text=None, marks=(), ctxs=ctx3, ld=(0, 0, 0), tag=""):
+        Ci, Co = (N, Kc) if dgrad else (Kc, N)
+        name = f"sconv{tag} {'bwd' if dgrad else 'fwd'} B{B} {H}x{W} {Ci}->{Co}"
+        m = list(marks)
+        if verdict == "run":
+            p = sconv_plan(dgrad, B, H, W, Ci, Co)
+            m += [("sconv.tile", _side(p["bm"] == 64)), ("sconv.rows", _side(p["M"] <= p["bm"])), ("sconv.cols", _side(N <= p["bn"])),
+                  ("sconv.work", _side(p["work"] < NUM_CU)), ("sconv.empty_slice", _side(not any(sconv_empty(dgrad, Kc, p["sk"])))),
+                  ("sconv.size", "lo"), ("sconv.even", "lo"), ("sconv.c32", "lo"), ("sconv.ld", "lo"), ("sconv.ld4", "lo"), ("sconv.lim", "lo")]
+            if dgrad:
+                m.append(("sconv.grid8", _side(p["tiles"] % 8 == 0)))
+            if p["work"] < NUM_CU:
+                m += [("sconv.want2", _side(p["want"] >= 2)), ("sconv.short", _side(p["want"] < p["short"] // 2)),
+                      ("sconv.cap16", _side(p["want"] < 16))]
+        if name in rows:
+            m = list(rows[name].marks) + m
+        rows[name] = Row("sconv", "sconv", name, ctxs, verdict, dict(dgrad=dgrad, B=B, H=H, W=W, Ci=Ci, Co=Co, ld=ld), "igemm", text, tuple(m))
+
+    # rows per parity class M = B (H / 2) (W / 2): 63 / 64 / 65 around the 64-row tile, 127 / 128 / 129 around two of them, from non-square maps and
+    # B = 3 so that a tile crosses a sample boundary (63 = 3 x (3 x 7), 129 = 3 x (1 x 43)) and a map-row boundary (65 = 5 x 13, 129 = 3 x 43);
+    # 127 = 1 x 127 is one output row of a map with H = 2
+    MS = ((3, 6, 14), (1, 8, 32), (1, 10, 26), (1, 2, 254), (1, 16, 32), (1, 6, 86), (3, 2, 86))
+    for dgrad in (0, 1):
+        for (B, H, W) in MS:
+            add(dgrad, B, H, W, 32, 96)  # (backward: 3 column tiles x 1 / 2 / 3 row tiles = 3 / 6 / 9 tiles of the 8-tile groups)
+        for N in (32, 64, 96, 160):
+            add(dgrad, 1, 10, 26, 64, N)
+        for Kc in (32, 64, 96, 128, 288):  # one tile: forward 4 / 9 / 13 / 16 / 16 slices; backward 1 / 1 / 1 / 2 / 4, the last with an empty one
+            add(dgrad, 3, 6, 14, Kc, 32)
+        add(dgrad, 1, 26, 2, 64, 64)  # one output column
+        add(dgrad, 1, 2, 2, 32, 32)  # one output pixel: five of the nine taps are padding
+        add(dgrad, 2, 4, 4, 1024, 32)  # backward: 32 K tiles in the one-tap class, the cap of 16 slices
+    add(1, 1, 32, 56, 32, 32)  # backward: 7 tiles
+    add(1, 1, 16, 32, 32, 128)  # backward: 8 tiles
+    # either side of `big < num_cu` at 256 CUs: the forward of 256 x 256 x 128 -> 128 is 128 x 2 = 256 tiles of 128 x 64, the backward of
+    # 128 x 128 x 128 <- 128 is 32 x 2 x 4; one row of tiles fewer takes the 64 x 32 tile.  The ragged 128-row tile: 16383 = 129 x 127 rows in the
+    # forward and 4095 = 63 x 65 per class in the backward hold 127 rows in their last tile (32 channels per tap keep the reference cheap)
+    add(0, 1, 256, 256, 128, 128)
+    add(0, 1, 254, 256, 128, 128)
+    add(0, 1, 258, 254, 32, 128)
+    add(1, 1, 128, 128, 128, 128)
+    add(1, 1, 124, 128, 128, 128)
+    add(1, 1, 126, 130, 32, 128)
+    # either side of `work < num_cu`: 64 x 4 = 256 tiles of 64 x 32 forward (63 x 4 = 252: 3 slices), 16 x 4 x 4 = 256 backward (15 x 4 x 4 = 240:
+    # two slices, two K tiles each in the one-tap class)
+    add(0, 1, 128, 128, 32, 128)
+    add(0, 1, 126, 128, 32, 128)
+    add(1, 1, 64, 64, 128, 128)
+    add(1, 1, 60, 64, 128, 128)
+    # every clause of cgd_sconv_refusal, forward and backward (ld: what is added to the row stride of the gathered / written / add operand)
+    for dgrad in (0, 1):
+        r = dict(verdict="refuse", ctxs=("p1",))
+        add(dgrad, 1, 0, 4, 32, 32, text=REFUSED["sconv.size"], marks=[("sconv.size", "hi")], **r)
+        add(dgrad, 1, 6, 5, 32, 32, text=REFUSED["sconv.even"], marks=[("sconv.even", "hi")], **r)
+        add(dgrad, 1, 3, 4, 32, 32, text=REFUSED["sconv.even"], marks=[("sconv.even", "hi")], **r)
+        add(dgrad, 1, 4, 4, 48, 32, text=REFUSED["sconv.c32"], marks=[("sconv.c32", "hi")], **r)
+        add(dgrad, 1, 4, 4, 32, 80, text=REFUSED["sconv.c32"], marks=[("sconv.c32", "hi")], **r)
+        add(dgrad, 1, 4, 4, 64, 32, text=REFUSED["sconv.ld"], marks=[("sconv.ld", "hi")], ld=(-12, 0, 0), tag=" ld_in = channels - 4", **r)
+        add(dgrad, 1, 4, 4, 32, 64, text=REFUSED["sconv.ld"], marks=[("sconv.ld", "hi")], ld=(0, -12, 0), tag=" ld_out = channels - 4", **r)
+        add(dgrad, 1, 4, 4, 32, 32, text=REFUSED["sconv.ld4"], marks=[("sconv.ld4", "hi")], ld=(2, 0, 0), tag=" ld_in+2", **r)
+        add(dgrad, 1, 4, 4, 32, 32, text=REFUSED["sconv.ld4"], marks=[("sconv.ld4", "hi")], ld=(0, 6, 0), tag=" ld_out+6", **r)
+        # 16 (4 in the half-size map) rows at a row stride of 2^28 floats more than the channels: the fourth row ends beyond 2^31 bytes.  Refused before anything is read
+        add(dgrad, 1, 4, 4, 32, 32, text=REFUSED["sconv.lim"], marks=[("sconv.lim", "hi")], ld=(2 ** 28, 0, 0), tag=" ld_in far", **r)
+        add(dgrad, 1, 4, 4, 32, 32, text=REFUSED["sconv.lim"], marks=[("sconv.lim", "hi")], ld=(0, 2 ** 28, 0), tag=" ld_out far", **r)
+    add(1, 1, 4, 4, 32, 64, text=REFUSED["sconv.ld"], marks=[("sconv.ld", "hi")], ld=(0, 0, -8), tag=" ldadd = channels - 4", verdict="refuse", ctxs=("p1",))
+    add(1, 1, 4, 4, 32, 32, text=REFUSED["sconv.ld4"], marks=[("sconv.ld4", "hi")], ld=(0, 0, 2), tag=" ldadd+2", verdict="refuse", ctxs=("p1",))
+    add(1, 1, 4, 4, 32, 32, text=REFUSED["sconv.lim"], marks=[("sconv.lim", "hi")], ld=(0, 0, 2 ** 28), tag=" ldadd far", verdict="refuse", ctxs=("p1",))
+    return list(rows.values())
+
+
+TABLE = _gemm_rows() + _halo_rows() + _wino_rows() + _attn_rows() + _norm_rows() + _elem_rows() + _sconv_rows()
 GROUPS = sorted({(r.fam, ck) for r in TABLE for ck in r.ctxs})
 
 
@@ -464,6 +583,24 @@ def conv_data(B, H, W, Ci, Co, ups, dgrad, gn=0):
     ab = th.stack([0.5 + th.rand(B, cin, generator=g(18)), 0.5 * th.randn(B, cin, generator=g(19))], dim=2).contiguous() if gn else None
     wref = w.flip(2, 3).transpose(0, 1) if dgrad else w
     return x, w, b, r, ab, _conv_ref(x, wref, b, ups, r, ab)
+
+
+@functools.lru_cache(maxsize=None)
+def sconv_data(dgrad, B, H, W, Ci, Co, dtype=th.float64):
+    """one stride-2 conv row, NHWC: forward (x, w, bias, y = conv2d(stride=2, padding=1)); backward (dy at unit-peak gradient, w, add, dx = the
+    autograd gradient of that conv2d + add)"""
+    nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous()  # noqa: E731
+    w = _r((Co, Ci, 3, 3), 52) / math.sqrt(9 * Ci)
+    x = _r((B, H, W, Ci), 51)
+    if not dgrad:
+        b = _r((Co,), 53, 0.3)
+        y = F.conv2d(x.to(dtype).permute(0, 3, 1, 2), w.to(dtype), b.to(dtype), stride=2, padding=1)
+        return x, w, b, nhwc(y)
+    dy, add = _r((B, H // 2, W // 2, Co), 54), _r((B, H, W, Ci), 55, 0.3)
+    xr = x.to(dtype).permute(0, 3, 1, 2).requires_grad_()
+    (gx,) = th.autograd.grad(F.conv2d(xr, w.to(dtype), None, stride=2, padding=1), xr, dy.to(dtype).permute(0, 3, 1, 2))
+    sd = unit_seed(gx)
+    return dy * sd, w, add, nhwc(gx) * sd + add.to(dtype)
 
 
 def attn_cols(heads, d, legacy):
@@ -581,6 +718,8 @@ def references(row, dtype=th.float64):
         return [("y", conv_data(s["B"], s["H"], s["W"], s["Ci"], s["Co"], s["ups"], s["dgrad"])[5])]
     if row.op == "wino":
         return [("y", conv_data(s["B"], s["H"], s["W"], s["Ci"], s["Co"], s["ups"], 0, s["gn"])[5])]
+    if row.op == "sconv":
+        return [("dx" if s["dgrad"] else "y", sconv_data(s["dgrad"], s["B"], s["H"], s["W"], s["Ci"], s["Co"], dtype)[3])]
     if row.op == "attn":
         _, _, out, dq = attn_data(s["nb"], s["heads"], s["T"], s["d"], s["legacy"], s["causal"], dtype)
         res = [("out", out)]
@@ -882,10 +1021,68 @@ def run_resample(ctx, row, ck, keep):
     return _case(ctx, row, [(X, x)], [Y], [ref], launch, "none", labels=["out"])[0]
 
 
-RUNNERS = {"gemm": run_gemm, "conv": run_conv, "wino": run_wino, "attn": run_attn, "gn": run_gn, "ln": run_ln, "act": run_act,
+def reduce_launches(lib):
+    """split-K reduce launches of the library since it was loaded (cgd_launch_counts)"""
+    o = (C.c_uint64 * 2)()
+    assert lib.cgd_launch_counts(o) == 0
+    return int(o[1])
+
+
+def run_sconv(ctx, row, ck, keep):
+    s = row.spec
+    dgrad, B, H, W, Ci, Co = s["dgrad"], s["B"], s["H"], s["W"], s["Ci"], s["Co"]
+    lib = ctx.lib
+    p1 = lambda v: max(v, 1)  # noqa: E731  (a refused row of zero height still needs an allocation to watch)
+    big, small = (B, p1(H), p1(W), Ci), (B, p1(H // 2), p1(W // 2), Co)
+    ishape, oshape = (small, big) if dgrad else (big, small)
+    # the allocations keep their own strides; a refused row passes the stride it names (nothing is read or written before the refusal)
+    a_in, a_out, a_add = ishape[-1] + 8, oshape[-1] + 8, Ci + 4
+    ld_in, ld_out, ldadd = (a + d for a, d in zip((a_in, a_out, a_add), s["ld"]))
+    X, Y = Guarded(ishape, a_in, 4), Guarded(oshape, a_out, 4)
+    AD = Guarded(big, a_add, 0) if dgrad else None
+    wshape = (Co, Ci, 3, 3)
+
+    def call(wptr, bptr):
+        if dgrad:
+            return lib.cgd_op_conv3x3_s2_dgrad(ctx.h, X.ptr, ld_in, wptr, Y.ptr, ld_out, AD.ptr, ldadd, B, H, W, Ci, Co, _s())
+        return lib.cgd_op_conv3x3_s2(ctx.h, X.ptr, ld_in, wptr, bptr, Y.ptr, ld_out, B, H, W, Ci, Co, _s())
+
+    if row.verdict == "refuse":
+        # the host predicate first: a row it accepts at these strides is not launched (its strides do not describe the allocations)
+        if lib.cgd_op_conv3x3_s2_accepts(dgrad, ld_in, ld_out, ldadd if dgrad else 0, B, H, W, Ci, Co) != 0:
+            return _tag([_flag(f"{row.name}: cgd_op_conv3x3_s2_accepts refuses the row", False)], row, "refused")
+        wd = th.zeros(wshape, device=DEV)
+        X.load(_r(ishape, 51), GAP[0])
+        return _refuse(ctx, row, [Y], lambda: ctx.check(call(wd.data_ptr(), None)))
+    xin, w, third, ref = sconv_data(dgrad, B, H, W, Ci, Co)
+    wd = w.to(DEV)
+    bd = None if dgrad else third.to(DEV)
+    plan = (C.c_int * 4)()
+    ncu = th.cuda.get_device_properties(0).multi_processor_count  # what cgd_ctx_create reads
+    assert lib.cgd_op_plan_conv_s2(dgrad, B, H, W, Ci, Co, ncu, plan) == 0, row.name
+    deltas = []
+
+    def launch():
+        before = reduce_launches(lib)
+        ctx.check(call(wd.data_ptr(), None if bd is None else bd.data_ptr()))
+        deltas.append(reduce_launches(lib) - before)
+
+    ins = [(X, xin)] + ([(AD, third)] if dgrad else [])
+    recs = _case(ctx, row, ins, [Y], [ref], launch, row.route, labels=["dx" if dgrad else "y"], sanity=CONTEXTS[ck][0] == 2)[0]
+    want = int(plan[2] > 1)
+    recs += _tag([_flag(f"{row.name}: plan {list(plan)} on {ncu} CUs, reduce launches per call {deltas} (one exactly when the plan splits)",
+                        len(deltas) == 2 and all(d == want for d in deltas))], row, "plan")
+    if dgrad:
+        recs += _tag([_flag(f"{row.name}: the add operand and its gaps are unchanged",
+                            th.equal(AD.view, third.to(DEV)) and bool((AD.buf[~AD.inside] == GAP[1]).all().item()))], row, "sentinel")
+    return recs
+
+
+RUNNERS = {"sconv": run_sconv, "gemm": run_gemm, "conv": run_conv, "wino": run_wino, "attn": run_attn, "gn": run_gn, "ln": run_ln, "act": run_act,
            "pool2x2": run_resample, "upsample2x": run_resample, "bilinear_up2x": run_resample}
 VERDICTS_RUN = {"parity", "sentinel", "rerun", "route"}
 VERDICTS_REFUSE = {"refused", "untouched"}
+VERDICTS_EXTRA = {"sconv": {"plan"}}  # the plan entry's slice count against the reduce counter
 
 
 def check_group(fam, ck, keep=None, ctx=None):
@@ -903,7 +1100,8 @@ def verdicts_complete(recs, fam, ck):
     have = {}
     for r in recs:
         have.setdefault(r["row"], set()).add(r["verdict"])
-    return [row.name for row in rows_of(fam, ck) if not have.get(row.name, set()) >= (VERDICTS_RUN if row.verdict == "run" else VERDICTS_REFUSE)]
+    need = lambda row: (VERDICTS_RUN | VERDICTS_EXTRA.get(row.fam, set())) if row.verdict == "run" else VERDICTS_REFUSE  # noqa: E731
+    return [row.name for row in rows_of(fam, ck) if not have.get(row.name, set()) >= need(row)]
 
 
 if __name__ == "__main__":  # one report: every record with its figures, the route table and the wall time per group, as JSON on stdout

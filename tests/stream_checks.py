@@ -349,6 +349,24 @@ case("conv3x3 hconv2 1x32x32 128->128 sk2")(_conv_case(1, 32, 32, 128, 128, 512,
 case("conv3x3 kconv 1x16x16 160->32")(_conv_case(1, 16, 16, 160, 32, 516, 1))
 
 
+def _sconv_case(Bn, H, W, Ci, Co):
+    """cgd_op_conv3x3_s2 and its dgrad with `add` (csrc/sconv.hip; the weight is packed per call into the context's scratch copy, on the stream)"""
+    def build():
+        from cgd_amd import ops
+        ctx = ctx_of(1)
+        x, w, b, _ = _conv_operands(Bn, H, W, Ci, Co)
+        dy = th.randn(Bn, H // 2, W // 2, Co, generator=g(8))
+        add = 0.3 * th.randn(Bn, H, W, Ci, generator=g(9))
+        return dict(fn=lambda x_, w_, b_, dy_, add_: (ops.conv3x3_s2(ctx, x_, w_, b_), ops.conv3x3_s2_dgrad(ctx, dy_, w_, add=add_)),
+                    inputs=_dev(x, w, b, dy, add))
+    return build
+
+
+# (the launcher's plan at 256 CUs, cgd_op_plan_conv_s2: 16 slices forward and 2 backward; one slice both ways)
+case("conv3x3_s2 + dgrad 2x8x8 128->128 split-K")(_sconv_case(2, 8, 8, 128, 128))
+case("conv3x3_s2 + dgrad 1x128x128 32->128 one slice")(_sconv_case(1, 128, 128, 32, 128))
+
+
 @case("conv3x3_wino 1x16x16 32->32 gn_ab")
 def _wconv():
     from cgd_amd import ops
@@ -1016,6 +1034,18 @@ def _unet_case(precision, slots=False):
 case("unet mini 1x64x64 forward + dgrad p1")(_unet_case(1))
 case("unet mini 1x64x64 forward + dgrad p0")(_unet_case(0))
 case("unet mini 1x64x64 embed + forward_slot + dgrad")(_unet_case(1, slots=True))
+
+
+@case("unet classic narrow 1x64x64 forward + dgrad p1")
+def _classic_unet_case():
+    """the narrow community structure (conv resampling, additive embedding): five Downsamples and Upsamples"""
+    seed = lc.SEEDS["unet"][0]
+    ctx = pc._ctx(1)
+    dev = lc._handle(ctx, "unet", seed, lc.CLASSIC_CASE)
+    call = lc.UNetCall(1, 64, 64, 0, lc.CLASSIC_CASE)
+    sd = lc.oracle(call, seed)["sd"]
+    return dict(fn=lambda x_, t_, go_: (dev.forward(x_, t_), dev.dgrad(go_)), inputs=_dev(call.x, call.t, call.gout * sd), grade=_grade(call, seed),
+                keep=(ctx, dev))
 
 
 def _tower_case(kind):

@@ -248,6 +248,101 @@ def test_flash_attention_row_loaders_at_every_tower_width_and_first_failure():
     assert (1 << 24) <= fb <= ec.far_ld(32) + 4, fb  # no guard: 32 rows * ld * 4 bytes reach 2^31 at ld = 2^24, the last row's start a row later
 
 
+# ---- the stride-2 conv (sconv.hip SC_GLOAD): off = ok ? ((a_pix + yy * Ws + xx) * lda + kin) * 4 : 0x80000000 with records a_bytes = the operand's
+# extent; weights b_off = n < N ? n * ldb * 4 : 0x80000000, off = b_off < 0 ? 0x80000000 : b_off + ((tap * Kc + kin) * 4), records b_bytes.  No soffset.
+def sconv_a(dgrad, B, H, W, lda, Kc):
+    """the gathered operand: x (forward: taps 2 r - 1 .. 2 r + 1) or dy (backward: taps r, r + 1 over the four parity classes), every row of the
+    64-row tiles (rows beyond M are masked by a_ok) x every tap x every 16-byte lane of a tap's Kc channels"""
+    Ho, Wo = H // 2, W // 2
+    Hs, Ws = (Ho, Wo) if dgrad else (H, W)
+    M = B * Ho * Wo
+    m = np.arange(-(-M // 64) * 64)[:, None, None, None]
+    b, rem = m // (Ho * Wo), m % (Ho * Wo)
+    r, c = rem // Wo, rem % Wo
+    d = (np.arange(2) if dgrad else np.arange(-1, 2))
+    yy = (r if dgrad else 2 * r) + d[None, :, None, None]
+    xx = (c if dgrad else 2 * c) + d[None, None, :, None]
+    kin = np.arange(0, Kc, 4)[None, None, None, :]
+    ok = (m < M) & (yy >= 0) & (yy < Hs) & (xx >= 0) & (xx < Ws) & (kin >= 0)
+    pix = b * Hs * Ws + yy * Ws + xx
+    voff = np.where(ok, i32(i32(i32(pix) * lda + kin) * 4), OOB)
+    ext = ((B * Hs * Ws - 1) * lda + Kc) * 4
+    return judge(voff, 0, ok, (pix * lda + kin) * 4, ext % P32, ext)
+
+
+def sconv_b(N, Kc, rows=None):
+    """the packed weights [N][9 Kc] (dense: ldb = 9 Kc), rows n of the 32-row tiles (all, or the given ones)"""
+    n = (np.arange(-(-N // 32) * 32) if rows is None else np.asarray(rows))[:, None, None]
+    tap, kin = np.arange(9)[None, :, None], np.arange(0, Kc, 4)[None, None, :]
+    b_off = np.where(n < N, i32(i32(n * (9 * Kc)) * 4), OOB)
+    wanted = (n < N) & (tap >= 0) & (kin >= 0)
+    voff = np.where(b_off < 0, OOB, i32(b_off + i32((tap * Kc + kin) * 4)))
+    ext = N * 9 * Kc * 4
+    return judge(voff, 0, wanted, (n * 9 * Kc + tap * Kc + kin) * 4, ext % P32, ext)
+
+
+@pytest.mark.parametrize("dgrad", [0, 1])
+@pytest.mark.parametrize("B,Kc", [(1, 32), (2, 64)])
+def test_sconv_gather_offsets_below_the_guard_and_first_failure(dgrad, B, Kc):
+    H = W = 8
+    rows = B * (H // 2) * (W // 2) if dgrad else B * H * W
+    below, at = ec.sconv_below_at(rows, Kc)
+    for lda in sorted({Kc, Kc + 4, 4096, 65536 + 4, below // 4 // 4 * 4, below // 2 // 4 * 4, below - 64, below - 4, below}):
+        assert sconv_a(dgrad, B, H, W, lda, Kc) == (0, 0), lda
+    # the guard counts the extent to the byte, so the model fails right at the guard's `at` stride or one step later (the last 16-byte lane of the
+    # last row ends at the extent): at <= first failure <= at + 4, well within one row below the stride that puts the last ROW's start at 2^31
+    fb = first_bad(lambda ld: sconv_a(dgrad, B, H, W, ld, Kc), below, ec.far_ld(rows) + 4)
+    assert at <= fb <= at + 4 <= ec.far_ld(rows) + 4, (at, fb)
+    assert sconv_a(dgrad, B, H, W, ec.far_ld(rows), Kc)[0] > 0
+
+
+def test_sconv_gather_offsets_at_the_real_levels_and_the_gpu_cases():
+    for (H, C_) in ((256, 128), (128, 128), (64, 256), (32, 256), (16, 512)):  # the five Downsamples of the community checkpoints at 256 x 256
+        for ld in (C_, 2 * C_):
+            assert sconv_a(0, 1, H, H, ld, C_) == (0, 0) and sconv_a(1, 1, H, H, ld, C_) == (0, 0)
+    for far, Bn, Ci, Co in ec.SCONV_FAR:
+        shape, dgrad = ec.sconv_far_shape(far, Bn, Ci, Co)
+        if far in ("x", "dy"):
+            rows = int(np.prod(shape[:-1]))
+            lb, la = ec.sconv_below_at(rows, shape[-1])
+            assert sconv_a(dgrad, Bn, 8, 8, lb, shape[-1]) == (0, 0)
+        assert sconv_b(Ci if dgrad else Co, Co if dgrad else Ci) == (0, 0)
+
+
+def test_sconv_weight_offsets_either_side_of_the_guard():
+    """Cin * Cout * 9 * 4 < 2^31: 7712 x 7712 channels is the last accepted square, 7744 the first refused"""
+    edge = lambda N: [0, 1, N // 2, N - 33, N - 2, N - 1] + list(range(N, -(-N // 32) * 32 + 32))  # noqa: E731
+    for N, Kc in ((32, 32), (96, 160), (512, 512), (1024, 1024)):
+        assert sconv_b(N, Kc) == (0, 0)
+    assert 7712 * 7712 * 36 < P31 <= 7744 * 7744 * 36
+    assert sconv_b(7712, 7712, edge(7712)) == (0, 0)
+    assert sconv_b(7744, 7744, edge(7744))[0] > 0
+    lib = handle_()
+    for dgrad in (0, 1):
+        assert lib.cgd_op_conv3x3_s2_accepts(dgrad, 7712, 7712, 0, 1, 2, 2, 7712, 7712) == 1
+        assert lib.cgd_op_conv3x3_s2_accepts(dgrad, 7744, 7744, 0, 1, 2, 2, 7744, 7744) == 0
+
+
+def test_sconv_predicate_either_side_of_every_operand_line():
+    lib = handle_()
+    for far, Bn, Ci, Co in ec.SCONV_FAR:
+        shape, dgrad = ec.sconv_far_shape(far, Bn, Ci, Co)
+        lb, la = ec.sconv_below_at(int(np.prod(shape[:-1])), shape[-1])
+        cin, cout = (Co, Ci) if dgrad else (Ci, Co)
+        for ld, want in ((lb, 1), (la, 0)):
+            lds = {"in": cin + 32, "out": cout + 32, "add": Ci + 48 if dgrad else 0}
+            lds[{"x": "in", "dy": "in", "y": "out", "dx": "out", "add": "add"}[far]] = ld
+            assert lib.cgd_op_conv3x3_s2_accepts(dgrad, lds["in"], lds["out"], lds["add"], Bn, 8, 8, Ci, Co) == want, (far, ld)
+            lay = ec.far_layout(shape, ld, ld - shape[-1])
+            assert lay["n"] * 4 < 4.5 * 2 ** 30
+
+
+def handle_():
+    import cgd_amd  # noqa: F401
+    from cgd_amd import lib as L
+    return L.load()
+
+
 def test_the_model_checker_notices_a_moved_guard():
     """the restated constants are what the tightness tests hang on: one stride step above each, a model that is asked to run anyway must not be
     reported clean for the WRONG reason - kgemm's `records` wraps right at the guard, the others hold for less than one more row"""

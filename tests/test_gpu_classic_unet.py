@@ -5,6 +5,7 @@ Net: image 32 x 32, model_channels 64, one res block, channel_mult (1, 2), atten
 seeded weights, all four combinations of the two switches at batch 1 and 2.  Bound: that of the existing whole-network tests
 (parity_checks.check_unet, test_gpu_superres.py, test_gpu_classifier.py): |a - b| <= 1e-4 + 1e-3 |ref| for every element of the output and of
 the input gradient, the gradient's seed scaled so that the reference gradient has unit peak."""
+import copy
 import ctypes as C
 import functools
 
@@ -185,3 +186,53 @@ def test_attention_at_head_dim_512(legacy):
     for r in (pc.rec(f"attention T16 d512 legacy{legacy} out", out, ref), pc.rec(f"attention T16 d512 legacy{legacy} dqkv", dq, dref)):
         print(f"{r['name']}: abs {r['err_abs']:.3e} peak {r['ref_max']:.3f}")
         assert r["ok"], r
+
+
+# ---- the community structure as a network: six levels, five Downsamples / Upsamples (classic_unet_ref.NARROW, .COMICS), against FLOAT64 ----------
+@functools.lru_cache(maxsize=None)
+def wide_reference(case, film):
+    ref = R.synthetic_init_(R.ClassicUNetModel(**R.CASES[case], resblock_updown=False, use_scale_shift_norm=film), seed=1234).eval()
+    for p in ref.parameters():
+        p.requires_grad_(False)
+    return ref
+
+
+@functools.lru_cache(maxsize=None)
+def wide_net(case, film, precision):
+    from cgd_amd import nets
+    dev = nets.UNet(context(precision), **R.CASES[case], resblock_updown=False, use_scale_shift_norm=film)
+    return dev.load_state_dict(pc.device_sd(wide_reference(case, film)))
+
+
+@functools.lru_cache(maxsize=None)
+def wide_scenario(case, film, B, H, W):
+    """the float64 copy of the fp32 weights the device holds: output and unit-peak input gradient, once per scenario"""
+    ref = copy.deepcopy(wide_reference(case, film)).double()
+    x = th.randn(B, 3, H, W, generator=pc.g(60))
+    t = th.tensor([417.0 + 100.0 * b for b in range(B)])
+    gout = th.randn(B, 6, H, W, generator=pc.g(62))
+    gout[:, 3:] = 0
+    xr = x.double().requires_grad_()
+    o = ref(xr, t.double())
+    (o * gout.double()).sum().backward()
+    sd = pc.unit_seed(xr.grad)
+    return dict(x=x, t=t, gout=gout * sd, out=o.detach(), grad=xr.grad * sd)
+
+
+# 32 x 32: the last Downsample makes a 1 x 1 map; 64 x 96: non-square, bottom map 2 x 3; 128 x 128: the Downsamples' forward runs 1 / 4 / 9 / 16 / 16
+# slices at this width
+NARROW_RUNS = [(False, 2, 32, 32, 1), (False, 2, 64, 96, 1), (False, 1, 128, 128, 1), (False, 2, 32, 32, 0), (False, 2, 64, 96, 0), (True, 2, 64, 96, 1)]
+
+
+@pytest.mark.parametrize("film,B,H,W,precision", NARROW_RUNS, ids=[f"{'film' if f else 'additive'}-B{b}-{h}x{w}-p{p}" for f, b, h, w, p in NARROW_RUNS])
+def test_community_structure_at_a_narrow_width_matches_float64(film, B, H, W, precision):
+    s = wide_scenario("narrow", film, B, H, W)
+    od, gx = run(wide_net("narrow", film, precision), s)
+    grade(f"classic unet[narrow community structure, film={film} p{precision} B{B} {H}x{W}]", od, gx, s)
+
+
+def test_community_flags_at_128x128_match_float64():
+    """model_channels 128 as the checkpoints have it: d = 512 attention at T = 64 and two of the five Downsamples on split-K"""
+    s = wide_scenario("comics", False, 1, 128, 128)
+    od, gx = run(wide_net("comics", False, 1), s)
+    grade("classic unet[community flags, p1 B1 128x128]", od, gx, s)

@@ -39,6 +39,11 @@ def test_conv3x3_winograd_groupnorm_records_of_a_far_output():
     _assert_all(ec.check_wino_records_far())
 
 
+@pytest.mark.parametrize("precision", [0, 1])
+def test_conv3x3_stride2_far_operands(precision):
+    _assert_all(ec.check_sconv_far(precision))
+
+
 def test_groupnorm_far_operands():
     _assert_all(ec.check_gn_far())
 

@@ -53,3 +53,15 @@ def test_tower_batch_walks_and_no_allocation_once_warm():
 
 def test_two_sampler_runs_on_the_same_objects():
     _assert_all(lc.check_two_runs())
+
+
+def test_classic_unet_shape_walk_and_no_allocation_once_warm():
+    _assert_all(lc.check_classic_walk())
+
+
+def test_classic_unet_pass_order_reupload_and_precision_switch():
+    _assert_all(lc.check_classic_order_reupload_and_precision())
+
+
+def test_classic_and_published_unet_interleaved_in_one_context():
+    _assert_all(lc.check_classic_shared_context())

@@ -146,3 +146,28 @@ def test_the_wrappers_pass_the_current_batch_and_shape_on_every_call():
     except AssertionError:
         raised = True
     assert raised and len(rec.calls) == n
+
+
+def test_classic_walk_grows_shrinks_and_repeats_every_resampling_buffer():
+    """CLASSIC_WALK B1 64^2 -> B2 128^2 -> B1 64^2 -> B2 32x64 -> B1 128^2 -> B2 128^2 over Downsample::out / dx and Upsample::out / d1 / dx: step 1
+    grows every buffer, steps 2 - 4 run on buffers that are too large, step 5 is exactly the largest shape seen; frames are multiples of 32 (five
+    Downsamples), 32 x 64 ends on a 1 x 2 map; the warm passes stay within the peak and end on it"""
+    assert lc.CLASSIC_WALK == [(1, 64, 64), (2, 128, 128), (1, 64, 64), (2, 32, 64), (1, 128, 128), (2, 128, 128)]
+    counts = [lc.classic_resample_counts(lc.CLASSIC_CASE, *s) for s in lc.CLASSIC_WALK]
+    assert len(counts[0]) == 25 and all(v > 0 for c in counts for v in c.values())
+    for k in range(1, len(counts)):
+        c = counts[k]
+        peak = {n: max(p[n] for p in counts[:k]) for n in c}
+        if k == 1:
+            assert all(c[n] > peak[n] for n in c)
+        elif k == 5:
+            assert c == peak
+        else:
+            assert all(c[n] < peak[n] for n in c)
+    assert all(H % 32 == 0 and W % 32 == 0 for _, H, W in lc.CLASSIC_WALK) and (32 >> 5, 64 >> 5) == (1, 2)
+    peak = {n: max(c[n] for c in counts) for n in counts[0]}
+    warm = [lc.classic_resample_counts(lc.CLASSIC_CASE, *s) for s in lc.CLASSIC_WARM]
+    assert all(s in lc.CLASSIC_WALK for s in lc.CLASSIC_WARM) and all(w[n] <= peak[n] for w in warm for n in w) and warm[2] == peak
+    kw = lc.pc.UNET_CASES[lc.CLASSIC_CASE]
+    from tests import classic_unet_ref as R
+    assert {k: kw[k] for k in R.NARROW} == R.NARROW and (kw["resblock_updown"], kw["use_scale_shift_norm"]) == (False, False)

@@ -171,6 +171,8 @@ def test_split_rows_name_their_empty_slices():
         marks = dict((c, side) for c, side in r.marks if c.endswith(".empty_slice"))
         if not marks:
             continue
+        if r.fam == "sconv":  # slices per parity class: test_sconv_rows_name_their_empty_slices_per_parity_class
+            continue
         (clause, side), = marks.items()
         units = {"igemm": -(-s.get("K", 0) // 32), "hgemm": s.get("K", 0) // 64}.get(clause.split(".")[0], s.get("Ci", 0) // 32)
         per = int(np.ceil(units / max(sk, 1)))
@@ -228,3 +230,139 @@ def test_fp32_references_of_the_non_mfma_rows_stay_within_a_quarter_of_the_bound
                 worst[r.fam] = (f, f"{r.name} {label}")
             assert f <= ADMISSIBLE_FRACTION, f"{r.name} {label}: fp32 PyTorch at {f:.3f} of the bound"
     print("worst fp32 fraction of the bound per family: " + ", ".join(f"{k} {v[0]:.3f} ({v[1]})" for k, v in sorted(worst.items())))
+
+
+# ---- the stride-2 conv (csrc/sconv.hip): the plan entry against the clauses restated in numpy ----------------------------------------------------
+SCONV = [r for r in se.TABLE if r.fam == "sconv"]
+WS_BYTES = 256 << 20
+
+
+def _sconv_plan_np(dgrad, B, H, W, Ci, Co, ncu):
+    """sconv.hip sconv_select in numpy integers, clause by clause (lines 291-310): (bm, bn, slices, workgroups of the main launch)"""
+    M = np.int64(B) * (H // 2) * (W // 2)
+    N, Kc = np.int64(Ci if dgrad else Co), np.int64(Co if dgrad else Ci)
+    cls = np.int64(4 if dgrad else 1)
+    cdiv = lambda a, b: -(-a // b)  # noqa: E731
+    big = cdiv(M, 128) * cdiv(N, 64) * cls
+    bm, bn = (64, 32) if big < ncu else (128, 64)
+    tiles = cdiv(M, bm) * cdiv(N, bn)
+    grid = cdiv(tiles, 8) * 32 if dgrad else tiles
+    out_rows, work, short = cls * M if dgrad else M, tiles * cls, (1 if dgrad else 9) * (Kc // 32)
+    sk = 1
+    if work < ncu:
+        want = min(cdiv(2 * ncu, work), short // 2, 16)
+        while want > 1 and want * out_rows * N * 4 > WS_BYTES:
+            want -= 1
+        if want >= 2:
+            sk = want
+    return int(bm), int(bn), int(sk), int(grid * sk)
+
+
+def _plan_s2(s, ncu):
+    o = (C.c_int * 4)()
+    rc = L.load().cgd_op_plan_conv_s2(s["dgrad"], s["B"], s["H"], s["W"], s["Ci"], s["Co"], ncu, o)
+    return rc, tuple(o)
+
+
+@pytest.mark.parametrize("ncu", [256, 304, 64])
+def test_sconv_rows_against_the_plan_entry(ncu):
+    """every row's plan {bm, bn, slices, workgroups} = the numpy restatement, at the table's 256 CUs = what the table claims (tile, slices, the
+    closed form of the grid), and refused where the table says so (dense strides: the stride rows are asked through _accepts)"""
+    h = L.load()
+    seen, bwd_tiles = Counter(), Counter()
+    for r in SCONV:
+        s = r.spec
+        dense = s["ld"] == (0, 0, 0)
+        rc, o = _plan_s2(s, ncu)
+        if r.verdict == "refuse":
+            cin, cout = (s["Co"], s["Ci"]) if s["dgrad"] else (s["Ci"], s["Co"])
+            ld = [c + 8 + d for c, d in zip((cin, cout), s["ld"][:2])] + [s["Ci"] + 4 + s["ld"][2] if s["dgrad"] else 0]
+            assert h.cgd_op_conv3x3_s2_accepts(s["dgrad"], ld[0], ld[1], ld[2], s["B"], s["H"], s["W"], s["Ci"], s["Co"]) == 0, r.name
+            assert rc == (-2 if dense else 0), (r.name, rc)  # (the plan entry asks for the dense problem)
+            continue
+        assert h.cgd_op_conv3x3_s2_accepts(s["dgrad"], (s["Co"] if s["dgrad"] else s["Ci"]) + 8, (s["Ci"] if s["dgrad"] else s["Co"]) + 8,
+                                           s["Ci"] + 4 if s["dgrad"] else 0, s["B"], s["H"], s["W"], s["Ci"], s["Co"]) == 1, r.name
+        assert rc == 0 and o == _sconv_plan_np(s["dgrad"], s["B"], s["H"], s["W"], s["Ci"], s["Co"], ncu), (r.name, o)
+        if ncu == se.NUM_CU:
+            p = se.sconv_plan(s["dgrad"], s["B"], s["H"], s["W"], s["Ci"], s["Co"])
+            assert o == (p["bm"], p["bn"], p["sk"], p["wg"]), (r.name, o, p)
+            tiles = se.ceil_div(p["M"], o[0]) * se.ceil_div(p["N"], o[1])
+            assert o[3] == (se.ceil_div(tiles, 8) * 32 if s["dgrad"] else tiles) * o[2]  # the closed form of the grid
+            seen[(s["dgrad"], o[0], o[2])] += 1
+            if s["dgrad"]:
+                bwd_tiles[tiles] += 1
+    if ncu == se.NUM_CU:
+        print("rows per (backward, tile rows, slices): " + ", ".join(f"{k} {v}" for k, v in sorted(seen.items(), key=str)))
+        for dgrad in (0, 1):
+            assert seen[(dgrad, 128, 1)] >= 2 and {sk for (d, bm, sk) in seen if d == dgrad and bm == 64} >= {1, 2 + (1 - dgrad), 4, 16}, seen
+        assert all(bwd_tiles[t] for t in (1, 7, 8, 9)), bwd_tiles
+        assert h.cgd_op_plan_conv_s2(0, 1, 4, 4, 32, 32, 256, None) == -3
+
+
+def test_sconv_boundary_shapes_sit_on_their_clauses():
+    """big = num_cu exactly takes the 128 x 64 tile (`<`, not `<=`), one row of tiles fewer the 64 x 32 one; work = num_cu exactly is unsplit"""
+    plan = lambda *a: _plan_s2(dict(zip(("dgrad", "B", "H", "W", "Ci", "Co"), a)), 256)[1]  # noqa: E731
+    assert plan(0, 1, 256, 256, 128, 128) == (128, 64, 1, 256) and plan(0, 1, 254, 256, 128, 128) == (64, 32, 1, 1016)
+    assert plan(1, 1, 128, 128, 128, 128) == (128, 64, 1, 256) and plan(1, 1, 124, 128, 128, 128) == (64, 32, 1, 992)
+    assert plan(0, 1, 128, 128, 32, 128) == (64, 32, 1, 256) and plan(0, 1, 126, 128, 32, 128) == (64, 32, 3, 756)
+    assert plan(1, 1, 64, 64, 128, 128) == (64, 32, 1, 256) and plan(1, 1, 60, 64, 128, 128) == (64, 32, 2, 512)
+    # the five Downsamples of the community checkpoints at a 256 x 256 frame, forward / backward
+    want = {(256, 128): ((128, 64, 1), (128, 64, 1)), (128, 128): ((64, 32, 1), (128, 64, 1)), (64, 256): ((64, 32, 4), (64, 32, 1)),
+            (32, 256): ((64, 32, 16), (64, 32, 4)), (16, 512): ((64, 32, 16), (64, 32, 8))}
+    for (hw, c), (f, b) in want.items():
+        assert plan(0, 1, hw, hw, c, c)[:3] == f and plan(1, 1, hw, hw, c, c)[:3] == b, (hw, c, plan(0, 1, hw, hw, c, c), plan(1, 1, hw, hw, c, c))
+
+
+def test_sconv_rows_name_their_empty_slices_per_parity_class():
+    seen = Counter()
+    for r in SCONV:
+        if r.verdict != "run":
+            continue
+        s = r.spec
+        p = se.sconv_plan(s["dgrad"], s["B"], s["H"], s["W"], s["Ci"], s["Co"])
+        empties = []
+        for taps in ((1, 2, 2, 4) if s["dgrad"] else (9,)):
+            nkt = taps * (p["Kc"] // 32)
+            per = int(np.ceil(nkt / p["sk"]))
+            lo = np.arange(p["sk"]) * per
+            empties.append(int((lo >= np.minimum(nkt, lo + per)).sum()))
+        assert empties == se.sconv_empty(s["dgrad"], p["Kc"], p["sk"]), r.name
+        assert (dict(r.marks)["sconv.empty_slice"] == "hi") == (sum(empties) > 0), (r.name, empties)
+        if sum(empties):
+            seen[(s["dgrad"], p["sk"], tuple(empties))] += 1
+    print("rows with empty slices (backward, slices, empty per class): " + ", ".join(f"{k} x{v}" for k, v in sorted(seen.items())))
+    assert seen[(1, 4, (1, 0, 0, 0))], seen  # Kc = 288 backward: 9 K tiles of the one-tap class in 4 slices of 3
+    assert any(k[0] == 0 for k in seen)
+
+
+def test_sconv_workspace_cap_is_unreachable():
+    """the `ws_bytes` clause of the want loop (sconv.hip:308): split-K is considered below num_cu workgroups only, so the slices hold at most
+    16 x (tiles x 64 x 32) floats; enumerated for every tile grid below 304 CUs"""
+    worst = 0
+    for ncu in (256, 304):
+        for dgrad in (0, 1):
+            cls = 4 if dgrad else 1
+            for ntm in range(1, ncu):
+                for ntn in range(1, ncu // ntm + 1):
+                    if ntm * ntn * cls < ncu:
+                        worst = max(worst, 16 * cls * (ntm * 64) * (ntn * 32) * 4)
+    print(f"largest split-K workspace the stride-2 conv can ask for: {worst} bytes of {WS_BYTES}: the cap is " + ("REACHABLE" if worst > WS_BYTES else "unreachable"))
+    assert worst <= WS_BYTES
+
+
+def test_sconv_references_are_admissible():
+    worst = (0.0, "")
+    for r in SCONV:
+        if r.verdict != "run":
+            continue
+        s = r.spec
+        (label, r64), = se.references(r)
+        (_, r32), = se.references(r, th.float32)
+        assert r64.abs().max().item() >= MIN_PEAK, r.name
+        if s["dgrad"]:
+            add = se.sconv_data(1, s["B"], s["H"], s["W"], s["Ci"], s["Co"])[2]
+            assert abs((r64 - add.double()).abs().max().item() - 1.0) < 1e-9, r.name
+        f = se.bound_fraction(r32, r64)
+        worst = max(worst, (f, f"{r.name} {label}"))
+        assert f <= ADMISSIBLE_FRACTION, f"{r.name} {label}: fp32 PyTorch at {f:.3f} of the bound"
+    print(f"worst fp32 fraction of the bound over the stride-2 conv rows: {worst[0]:.3f} ({worst[1]})")

@@ -41,6 +41,15 @@ def test_attention_cases_are_admissible(cls, regime):
         assert f32 <= vr.FP32_SHARE and (emu is None or emu <= vr.EMU_SHARE)
 
 
+@pytest.mark.parametrize("cls", ["f32", "x3"])
+def test_attention_gain_case_at_one_head_of_512_channels_is_admissible(cls):
+    for sh in vr.ATTN_GAIN_ONLY:
+        f32, emu = vr.attn_fractions(sh, "gain", vr.ATTN_GAIN[cls], False, emulate=cls == "x3")
+        _line(f"attention[{cls}]", sh, f"gain {vr.ATTN_GAIN[cls]} (gain case only)", f"fp32 {f32:.3f}", "" if emu is None else f"bf16x3 emulation {emu:.3f}")
+        assert f32 <= vr.FP32_SHARE and (emu is None or emu <= vr.EMU_SHARE)
+        assert vr.attn_class(1, {}, sh[3]) == "x3" and vr.attn_class(1, {"CGD_ATTN_X3": "0"}, sh[3]) == "x3" and vr.attn_class(0, {}, sh[3]) == "f32"
+
+
 def test_attention_cases_left_out_of_bf16x3_contexts_do_fail_the_emulation():
     for shape, regime, kind in vr.ATTN_X3_LEFT_OUT:
         c = vr.attn_case(shape, regime)

@@ -74,6 +74,8 @@ def env(**kv):
 ATTN_SHAPES = [(2, 2, 64, 64, 1), (1, 3, 50, 64, 0), (1, 2, 100, 64, 0), (1, 2, 197, 64, 0), (1, 2, 257, 64, 1), (1, 2, 1152, 64, 1),
                (1, 2, 64, 128, 1), (1, 2, 100, 128, 0)]
 ATTN_CAUSAL_SHAPES = [(1, 2, 77, 64, 0), (1, 2, 100, 64, 0), (1, 2, 50, 64, 0)]
+# one head of 512 channels over a 16 x 16 map (the classic architecture's community checkpoints at 256 x 256): the logit-gain case only
+ATTN_GAIN_ONLY = [(1, 1, 256, 512, 0)]
 ATTN_REGIMES = ("gain", "planted", "ascending", "descending", "offset", "identical")
 # peaked (half the rows one-hot to 0.9): "planted" in every context, "gain" at the gain exact-fp32 products admit; at the gain the bf16x3
 # emulation admits, "gain" is a logit-gain case only
@@ -279,11 +281,11 @@ def check_attn_regimes(name, precision, envd):
     with env(**envd):
         ctx = pc._ctx(precision)
     for causal in (False, True):
-        for shape in (ATTN_CAUSAL_SHAPES if causal else ATTN_SHAPES):
+        for shape in (ATTN_CAUSAL_SHAPES if causal else ATTN_SHAPES + ATTN_GAIN_ONLY):
             nb, heads, T, d, legacy = shape
             cls = attn_class(precision, envd, d)
             at = ops.Attention(ctx, nb, heads, T, d, legacy, DEV)
-            for regime in ATTN_REGIMES:
+            for regime in (("gain",) if shape in ATTN_GAIN_ONLY else ATTN_REGIMES):
                 gain = ATTN_GAIN[cls] if regime == "gain" else None
                 c = attn_case(shape, regime, gain, causal)
                 tag = f"attn[{name}] {'causal ' if causal else ''}nb{nb} h{heads} T{T} d{d} legacy{legacy} {regime}{'' if gain is None else gain}"

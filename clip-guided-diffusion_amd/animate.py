@@ -6,7 +6,8 @@ change at keyframes.
         --border wrap --interp bicubic --frames_skip 0.6 --frames_scale 1500 --color_match 1 [--fixed_seed] \\
         [--prompts_at "40=a city at night|a skyline:0.5"]... -- <cgd command-line flags>
     python -m cgd_amd.animate --frames 120 --mode 3d --translation_z "0:(4)" --rotation_3d_y "0:(0),60:(0.5)" --translation_x 2 --fov 40 \\
-        [--depth_fn MODULE:FUNCTION --depth_iters 2] ... -- <cgd command-line flags>
+        [--depth_model dpt_large-midas-2f21e586.pt[:size=384][:offset=50][:scale=19] | --depth_fn MODULE:FUNCTION] [--depth_iters 2] ... \\
+        -- <cgd command-line flags>
 
 or, from Python, `animate(frames, zoom=..., **clip_guided_diffusion_kwargs)`, a generator of `(frame_idx, batch_idx, png_path)`.
 
@@ -36,8 +37,8 @@ every pixel, so that near things move faster than far ones (cgd_frame_warp3d, cs
       flies forward (at flat depth z0 a magnification of z0 / (z0 - tz / 200)), rotation_3d_z > 0 turns the picture counter-clockwise like
       `angle`, rotation_3d_y > 0 turns the camera right (content moves left), rotation_3d_x > 0 tilts it up (content moves down).  These
       signs are this project's own; they have not been compared with Deforum's.
-Depth is flat (Deforum's use_depth_warping=False) or the caller's: a tensor, or a callable of the previous frame.  No depth network is
-included.
+Depth is flat (Deforum's use_depth_warping=False), the caller's (a tensor, or a callable of the previous frame), or DPT-Large's
+(`--depth_model FILE`, nets.DepthNet: the MiDaS network Disco Diffusion and Deforum use, run natively once per frame).
 """
 import argparse
 import collections
@@ -244,7 +245,54 @@ def _check(frames, border, interp, frames_skip, frames_scale, color_match, promp
     return frames, plan
 
 
-def _check_mode(mode, frames, zoom, angle, motion3d, fov, depth, depth_iters, near):
+def parse_depth_model(spec):
+    """'FILE[:size=N][:offset=A][:scale=B]' -> (FILE, {'size': int, 'offset': float, 'scale': float} of the options given); None -> None.
+    ValueError for an empty file name, an unknown or repeated option, or a value that is no number."""
+    if spec is None:
+        return None
+    file, *opts = str(spec).split(":")
+    if not file.strip():
+        raise ValueError(f"depth_model {spec!r}: expected 'FILE[:size=N][:offset=A][:scale=B]'")
+    out = {}
+    for opt in opts:
+        key, sep, val = opt.partition("=")
+        key = key.strip()
+        if not sep or key not in ("size", "offset", "scale") or key in out:
+            raise ValueError(f"depth_model {spec!r}: {opt!r} is not one of size=N, offset=A, scale=B (each at most once)")
+        try:
+            out[key] = int(val) if key == "size" else float(val)
+        except ValueError:
+            raise ValueError(f"depth_model {spec!r}: {val!r} is no number") from None
+        if not math.isfinite(out[key]) or (key == "size" and out[key] < 32) or (key == "scale" and out[key] == 0):
+            raise ValueError(f"depth_model {spec!r}: size must be at least 32, offset finite, scale finite and not 0")
+    return file.strip(), out
+
+
+def load_depth_model(ctx, spec):
+    """The DepthNet of a parsed `depth_model` on the run's context: the checkpoint FILE (a torch file holding the published state dict, or
+    {'state_dict': ...}); with CGD_SYNTHETIC_WEIGHTS=1 a known file name gets seeded random weights and FILE is not read."""
+    import os
+
+    import torch as th
+
+    from cgd import script_util
+    from cgd_amd import nets, synthetic
+    file, opts = spec
+    config = nets.DEPTH_CHECKPOINTS.get(os.path.basename(file), "dpt_large")
+    if script_util.synthetic_weights_enabled():
+        if os.path.basename(file) not in nets.DEPTH_CHECKPOINTS:
+            raise ValueError(f"depth_model {file!r}: with CGD_SYNTHETIC_WEIGHTS=1 the file is not read, so only {sorted(nets.DEPTH_CHECKPOINTS)} work")
+        sd = synthetic.depth_state_dict(config)
+    elif not os.path.isfile(file):
+        raise FileNotFoundError(f"{file} not found (set CGD_SYNTHETIC_WEIGHTS=1 for seeded random weights)")
+    else:
+        sd = th.load(file, map_location="cpu")
+        if isinstance(sd, dict) and isinstance(sd.get("state_dict"), dict):
+            sd = sd["state_dict"]
+    return nets.DepthNet(ctx, config, **opts).load_state_dict(sd)
+
+
+def _check_mode(mode, frames, zoom, angle, motion3d, fov, depth, depth_iters, near, depth_model=None):
     """The refusals of the mode arguments, before anything is loaded -> the five 3D tracks (translation_z, rotation_3d_x / y / z, fov)."""
     if mode not in MODES:
         raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
@@ -260,12 +308,14 @@ def _check_mode(mode, frames, zoom, angle, motion3d, fov, depth, depth_iters, ne
     if mode == "2d":
         given = [n for n, t in zip(names, tracks) if any(v != 0 for v in t)]
         given += ["fov"] * any(v != 40 for v in tracks[4]) + ["depth"] * (depth is not None) + ["depth_iters"] * (depth_iters != 1)
-        given += ["near"] * (near != 0.05)
+        given += ["near"] * (near != 0.05) + ["depth_model"] * (depth_model is not None)
         if given:
             raise ValueError(f"{', '.join(given)}: only with mode='3d'")
         return tracks
     if any(v != 1 for v in keyframes(zoom, frames)) or any(v != 0 for v in keyframes(angle, frames)):
         raise ValueError("mode='3d' takes no zoom or angle: fly with translation_z and turn with rotation_3d_z")
+    if depth is not None and depth_model is not None:
+        raise ValueError("depth_model and depth (--depth_fn) exclude each other: one source of depth")
     if depth is not None and not callable(depth):
         import torch as th
         if not isinstance(depth, th.Tensor) or depth.dim() not in (2, 4):
@@ -290,7 +340,7 @@ def _depth_map(depth, k, B, H, W, device=None):
 
 def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, border="wrap", interp="bicubic", frames_skip=0.6,
             frames_scale=1500, color_match=0.0, fixed_seed=False, prompts_at=None, mode="2d", translation_z=0.0, rotation_3d_x=0.0,
-            rotation_3d_y=0.0, rotation_3d_z=0.0, fov=40.0, depth=None, depth_iters=1, near=0.05, **cgd_kwargs):
+            rotation_3d_y=0.0, rotation_3d_z=0.0, fov=40.0, depth=None, depth_iters=1, near=0.05, depth_model=None, **cgd_kwargs):
     """Generator of `(frame_idx, batch_idx, png_path)`: `frames` frames, each the last image of one sampling run, written to
     prefix_path/<prompts>/<batch_idx:02>/<frame_idx:04>.png.
 
@@ -309,7 +359,9 @@ def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, b
     (H, W) used for every frame, or a callable that is called once per frame k > 0 with the previous frame's pred_xstart as (B, 3, H, W) in
     [0, 1] on the GPU and returns such a tensor; the units are those in which the flat depth is 1.0.  `depth_iters` in 1..4: fixed-point steps
     that look the depth up at the source pixel (1: the destination pixel's own depth).  A depth of the wrong shape, or one that is not finite
-    and positive everywhere, raises ValueError naming the frame.
+    and positive everywhere, raises ValueError naming the frame.  A nets.DepthNet is such a callable; `depth_model` =
+    'FILE[:size=N][:offset=A][:scale=B]' (parse_depth_model) builds one from a DPT-Large checkpoint, once, on the run's context, and excludes
+    `depth`.
 
     Refused before anything is loaded (ValueError): an unknown `mode`, `zoom` / `angle` in 3D mode, a 3D-only argument in 2D mode,
     `depth_iters` outside 1..4, a `fov` that leaves (0, 180), an init_image with '::MASK', 'invert=', 'upsample=' or 'ilvrN=', 'SOURCE=>TARGET'
@@ -325,7 +377,9 @@ def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, b
     tracks = [keyframes(spec, frames) for spec in (zoom, angle, translation_x, translation_y)]
     if any(not z > 0 for z in tracks[0]):
         raise ValueError("zoom must stay positive on every frame")
-    tracks3d = _check_mode(mode, frames, zoom, angle, (translation_z, rotation_3d_x, rotation_3d_y, rotation_3d_z), fov, depth, depth_iters, near)
+    depth_model = parse_depth_model(depth_model)
+    tracks3d = _check_mode(mode, frames, zoom, angle, (translation_z, rotation_3d_x, rotation_3d_y, rotation_3d_z), fov, depth, depth_iters, near,
+                           depth_model)
     seed = cgd_kwargs.get("seed", 0)
     run = entry.prepare_run(**cgd_kwargs, lpips_for_later=frames > 1 and frames_scale != 0)
     if run is None:
@@ -352,6 +406,8 @@ def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, b
         cond_fn.set_targets([th.cat(e + list(img)) for e, img in zip(embeds, run.image_embeds)], w / w.sum().abs())
 
     B = run.shape[0]
+    if depth_model is not None and frames > 1:
+        depth = load_depth_model(ctx, depth_model)
     if mode == "3d" and depth is not None and not callable(depth):
         depth = _depth_map(depth, 0, B, H, W)  # judged now that the frame size is known; it joins the state's device at its first use
     previous = previous_x0 = stats0 = None
@@ -406,6 +462,9 @@ def build_parser():
         p.add_argument(f"--{name}", default=default, help=f"{what}: a number or keyframes 'FRAME:(VALUE), ...'")
     p.add_argument("--depth_fn", default=None, help="3d: MODULE:FUNCTION, called with the previous frame (B,3,H,W) in [0,1], returns its depth "
                                                     "(1 or B,1,H,W), 1.0 = the flat default; without it the depth is flat")
+    p.add_argument("--depth_model", default=None, help="3d: FILE[:size=N][:offset=A][:scale=B], a DPT-Large (MiDaS v3) checkpoint such as "
+                                                       "dpt_large-midas-2f21e586.pt: the depth of the previous frame from the native depth network "
+                                                       "(net size N, depth = (A - inverse depth) / B); not together with --depth_fn")
     p.add_argument("--depth_iters", type=int, default=1, help="3d: fixed-point steps of the depth lookup, 1..4")
     p.add_argument("--near", type=float, default=0.05, help="3d: the near plane, in depth units")
     p.add_argument("--border", default="wrap", choices=BORDERS, help="what the warp reads outside the frame")
@@ -442,7 +501,7 @@ def main(argv=None):
                         interp=a.interp, frames_skip=a.frames_skip, frames_scale=a.frames_scale, color_match=a.color_match,
                         fixed_seed=a.fixed_seed, prompts_at=parse_prompts_at(a.prompts_at), mode=a.mode, translation_z=a.translation_z,
                         rotation_3d_x=a.rotation_3d_x, rotation_3d_y=a.rotation_3d_y, rotation_3d_z=a.rotation_3d_z, fov=a.fov,
-                        depth=load_depth_fn(a.depth_fn), depth_iters=a.depth_iters, near=a.near, **kwargs):
+                        depth=load_depth_fn(a.depth_fn), depth_iters=a.depth_iters, near=a.near, depth_model=a.depth_model, **kwargs):
         print("\t".join(str(v) for v in item))
 
 

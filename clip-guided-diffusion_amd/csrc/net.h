@@ -127,9 +127,13 @@ struct ClipBlock {
   std::string pre;  // parameter prefix, "transformer.resblocks.{l}"
   int W = 0, heads = 0;
   int act = 2;  // activation between c_fc and c_proj: 2 QuickGELU (OpenAI's towers), 3 exact GELU (open_clip's); cgd_vit_set_activation / cgd_text_set_activation
+  float eps = 1e-5f;  // of both LayerNorms (CLIP's; the depth net's timm blocks use 1e-6)
+  std::string names[12];  // the twelve parameters in the order of the pointers below (CLIP's names, or timm's for the depth net's backbone)
   float *ln1g = 0, *ln1b = 0, *inw = 0, *inb = 0, *ow = 0, *ob = 0;
   float *ln2g = 0, *ln2b = 0, *fcw = 0, *fcb = 0, *pjw = 0, *pjb = 0;
-  void add_params(NetBase& net, const std::string& prefix, int width, int nheads);  // build(): registers the twelve parameters
+  // build(): registers the twelve parameters; timm: under timm's VisionTransformer block names (norm1, attn.qkv, attn.proj, norm2, mlp.fc1, mlp.fc2:
+  // the same tensors in the same layouts)
+  void add_params(NetBase& net, const std::string& prefix, int width, int nheads, bool timm = false);
   void lookup(NetBase& net);                                                        // finalize(): their device pointers
 };
 // the forward activations of one block (the image tower keeps one set per layer for its backward pass, the text tower reuses one set)

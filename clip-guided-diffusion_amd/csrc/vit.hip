@@ -12,31 +12,26 @@
 #include "net.h"
 
 // ---- ClipBlock (net.h): also the text tower's block
-void ClipBlock::add_params(NetBase& net, const std::string& prefix, int width, int nheads) {
+void ClipBlock::add_params(NetBase& net, const std::string& prefix, int width, int nheads, bool timm) {
   pre = prefix;
   W = width;
   heads = nheads;
-  net.add_param(pre + ".ln_1.weight", W);
-  net.add_param(pre + ".ln_1.bias", W);
-  net.add_param(pre + ".attn.in_proj_weight", (int64_t)3 * W * W);
-  net.add_param(pre + ".attn.in_proj_bias", 3 * W);
-  net.add_param(pre + ".attn.out_proj.weight", (int64_t)W * W);
-  net.add_param(pre + ".attn.out_proj.bias", W);
-  net.add_param(pre + ".ln_2.weight", W);
-  net.add_param(pre + ".ln_2.bias", W);
-  net.add_param(pre + ".mlp.c_fc.weight", (int64_t)4 * W * W);
-  net.add_param(pre + ".mlp.c_fc.bias", 4 * W);
-  net.add_param(pre + ".mlp.c_proj.weight", (int64_t)4 * W * W);
-  net.add_param(pre + ".mlp.c_proj.bias", W);
+  static const char* const clip_names[12] = {".ln_1.weight", ".ln_1.bias", ".attn.in_proj_weight", ".attn.in_proj_bias", ".attn.out_proj.weight",
+                                             ".attn.out_proj.bias", ".ln_2.weight", ".ln_2.bias", ".mlp.c_fc.weight", ".mlp.c_fc.bias",
+                                             ".mlp.c_proj.weight", ".mlp.c_proj.bias"};
+  static const char* const timm_names[12] = {".norm1.weight", ".norm1.bias", ".attn.qkv.weight", ".attn.qkv.bias", ".attn.proj.weight", ".attn.proj.bias",
+                                             ".norm2.weight", ".norm2.bias", ".mlp.fc1.weight", ".mlp.fc1.bias", ".mlp.fc2.weight", ".mlp.fc2.bias"};
+  const int64_t w = W;
+  const int64_t numel[12] = {w, w, 3 * w * w, 3 * w, w * w, w, w, w, 4 * w * w, 4 * w, 4 * w * w, w};
+  for (int i = 0; i < 12; ++i) {
+    names[i] = pre + (timm ? timm_names : clip_names)[i];
+    net.add_param(names[i], numel[i]);
+  }
 }
 
 void ClipBlock::lookup(NetBase& net) {
-  ln1g = net.P(pre + ".ln_1.weight"); ln1b = net.P(pre + ".ln_1.bias");
-  inw = net.P(pre + ".attn.in_proj_weight"); inb = net.P(pre + ".attn.in_proj_bias");
-  ow = net.P(pre + ".attn.out_proj.weight"); ob = net.P(pre + ".attn.out_proj.bias");
-  ln2g = net.P(pre + ".ln_2.weight"); ln2b = net.P(pre + ".ln_2.bias");
-  fcw = net.P(pre + ".mlp.c_fc.weight"); fcb = net.P(pre + ".mlp.c_fc.bias");
-  pjw = net.P(pre + ".mlp.c_proj.weight"); pjb = net.P(pre + ".mlp.c_proj.bias");
+  float** const dst[12] = {&ln1g, &ln1b, &inw, &inb, &ow, &ob, &ln2g, &ln2b, &fcw, &fcb, &pjw, &pjb};
+  for (int i = 0; i < 12; ++i) *dst[i] = net.P(names[i]);
 }
 
 int clip_block_fwd(NetBase& net, const ClipBlock& b, ClipActs& t, const float* x, float* xo, int N, int T, bool causal, hipStream_t s) {
@@ -47,12 +42,12 @@ int clip_block_fwd(NetBase& net, const ClipBlock& b, ClipActs& t, const float* x
   CGD_TRY(net.ensure(t.y, rows * W)); CGD_TRY(net.ensure(t.qkv, rows * 3 * W)); CGD_TRY(net.ensure(t.a, rows * W));
   CGD_TRY(net.ensure(t.x1, rows * W)); CGD_TRY(net.ensure(t.y2, rows * W)); CGD_TRY(net.ensure(t.u, rows * 4 * W));
   CGD_TRY(net.ensure(t.ga, rows * 4 * W));
-  CGD_TRY(cgd_launch_ln_fwd(ctx, x, W, t.y.p, W, (int)rows, W, b.ln1g, b.ln1b, 1e-5f, t.st1.p, s));
+  CGD_TRY(cgd_launch_ln_fwd(ctx, x, W, t.y.p, W, (int)rows, W, b.ln1g, b.ln1b, b.eps, t.st1.p, s));
   CGD_TRY(cgd_launch_gemm(ctx, lin(t.y.p, W, b.inw, W, t.qkv.p, 3 * W, b.inb, nullptr, 0, rows, 3 * W), s));
   const AttnShape sh{N, b.heads, T, W / b.heads, W, 0, causal ? 1 : 0};
   CGD_TRY(net.attn_fwd(t.att, sh, t.qkv.p, 3 * W, t.a.p, W, s));
   CGD_TRY(cgd_launch_gemm(ctx, lin(t.a.p, W, b.ow, W, t.x1.p, W, b.ob, x, W, rows, W, 1), s));
-  CGD_TRY(cgd_launch_ln_fwd(ctx, t.x1.p, W, t.y2.p, W, (int)rows, W, b.ln2g, b.ln2b, 1e-5f, t.st2.p, s));
+  CGD_TRY(cgd_launch_ln_fwd(ctx, t.x1.p, W, t.y2.p, W, (int)rows, W, b.ln2g, b.ln2b, b.eps, t.st2.p, s));
   {
     // c_fc + QuickGELU / GELU (b.act): the activation runs in the GEMM's epilogue where hgemm2 takes the launch in one slice (u is kept
     // for the image tower's backward pass, ga feeds c_proj); otherwise the separate elementwise kernel

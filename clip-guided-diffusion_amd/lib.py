@@ -41,6 +41,12 @@ class ViTConfig(C.Structure):
     _fields_ = [("resolution", i32), ("patch", i32), ("width", i32), ("layers", i32), ("heads", i32), ("out_dim", i32)]
 
 
+class DepthConfig(C.Structure):
+    """cgd_depth_config"""
+    _fields_ = [("patch", i32), ("width", i32), ("layers", i32), ("heads", i32), ("hooks", i32 * 4), ("native_grid", i32), ("features", i32),
+                ("reassemble_channels", i32 * 4)]
+
+
 class TextConfig(C.Structure):
     _fields_ = [("context_length", i32), ("vocab_size", i32), ("width", i32), ("layers", i32), ("heads", i32), ("out_dim", i32)]
 
@@ -184,6 +190,23 @@ _SIGS = {
     "cgd_secondary_combine": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, f32, vp]),
     "cgd_op_secondary_pack": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, vp]),
     "cgd_op_bilinear_up2x": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "cgd_depth_manifest": (i32, [C.POINTER(DepthConfig), MANIFEST_CB, vp]),
+    "cgd_depth_create": (i32, [vp, C.POINTER(DepthConfig), C.POINTER(vp)]),
+    "cgd_depth_destroy": (None, [vp]),
+    "cgd_depth_num_params": (i32, [vp]),
+    "cgd_depth_param_info": (i32, [vp, i32, C.c_char_p, i32, C.POINTER(i64)]),
+    "cgd_depth_set_param": (i32, [vp, C.c_char_p, vp, i64]),
+    "cgd_depth_finalize": (i32, [vp]),
+    "cgd_depth_set_pos_embed": (i32, [vp, i32, i32, vp]),
+    "cgd_depth_forward": (i32, [vp, vp, i32, i32, i32, f32, f32, f32, vp, vp, vp]),
+    "cgd_depth_debug_map": (i32, [vp, i32, vp, C.POINTER(i32), vp]),
+    "cgd_depth_debug_stop": (i32, [vp, i32]),
+    "cgd_op_relu_rows": (i32, [vp, vp, i32, vp, i32, i64, i32, vp]),
+    "cgd_op_bilinear_up2x_ac": (i32, [vp, vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "cgd_op_conv_transpose": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "cgd_op_depth_readout": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
+    "cgd_op_depth_head_tail": (i32, [vp, vp, i32, vp, vp, vp, vp, i64, i32, f32, f32, f32, vp]),
+    "cgd_op_resize_cubic": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, f32, i32, vp]),
     "cgd_classifier_manifest": (i32, [C.POINTER(ClassifierConfig), MANIFEST_CB, vp]),
     "cgd_classifier_create": (i32, [vp, C.POINTER(ClassifierConfig), C.POINTER(vp)]),
     "cgd_classifier_destroy": (None, [vp]),

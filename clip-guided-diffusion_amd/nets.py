@@ -773,6 +773,171 @@ class NoisyClassifier(_Net):
         return g
 
 
+DEPTH_CONFIGS = {
+    # name: the fields of cgd_depth_config.  DPT-Large (MiDaS v3, dpt_large-midas-2f21e586.pt): timm's vit_large_patch16_384 with hooks behind
+    # blocks 5, 11, 17, 23, trained at a 24 x 24 token grid.  Written from memory of isl-org/DPT; loading a checkpoint cross-checks every shape.
+    "dpt_large": dict(patch=16, width=1024, layers=24, heads=16, hooks=(5, 11, 17, 23), native_grid=24, features=256,
+                      reassemble_channels=(256, 512, 1024, 1024)),
+}
+DEPTH_CHECKPOINTS = {"dpt_large-midas-2f21e586.pt": "dpt_large"}
+# groups of the published file that the forward does not use
+DEPTH_IGNORED_PREFIXES = ("pretrained.model.norm.", "pretrained.model.head.", "scratch.refinenet4.resConfUnit1.")
+
+
+def depth_config(config):
+    """A name of DEPTH_CONFIGS, or a dict of its fields -> (lib.DepthConfig, the dict)."""
+    if isinstance(config, str):
+        if config not in DEPTH_CONFIGS:
+            raise ValueError(f"depth config must be one of {sorted(DEPTH_CONFIGS)} or a dict of its fields, got {config!r}")
+        config = DEPTH_CONFIGS[config]
+    d = dict(config)
+    if len(d["hooks"]) != 4 or len(d["reassemble_channels"]) != 4:
+        raise ValueError("depth config: four hooks and four reassemble_channels")
+    cfg = L.DepthConfig()
+    cfg.patch, cfg.width, cfg.layers, cfg.heads = d["patch"], d["width"], d["layers"], d["heads"]
+    cfg.native_grid, cfg.features = d["native_grid"], d["features"]
+    for i in range(4):
+        cfg.hooks[i] = d["hooks"][i]
+        cfg.reassemble_channels[i] = d["reassemble_channels"][i]
+    return cfg, d
+
+
+def depth_param_shapes(config):
+    """{key: shape} of every tensor of the published DPT checkpoint layout that the forward uses, for a configuration (host only).  The key
+    table is written from memory of isl-org/DPT and timm: no checkpoint was available to check it against."""
+    _, d = depth_config(config)
+    W, P, F, ng = d["width"], d["patch"], d["features"], d["native_grid"]
+    m, out = "pretrained.model.", {}
+    out[m + "patch_embed.proj.weight"], out[m + "patch_embed.proj.bias"] = (W, 3, P, P), (W,)
+    out[m + "cls_token"], out[m + "pos_embed"] = (1, 1, W), (1, 1 + ng * ng, W)
+    for l in range(d["layers"]):
+        b = f"{m}blocks.{l}."
+        for name, shape in (("norm1", None), ("attn.qkv", (3 * W, W)), ("attn.proj", (W, W)), ("norm2", None), ("mlp.fc1", (4 * W, W)),
+                            ("mlp.fc2", (W, 4 * W))):
+            out[b + name + ".weight"] = shape or (W,)
+            out[b + name + ".bias"] = (shape[0],) if shape else (W,)
+    for k, c in enumerate(d["reassemble_channels"]):
+        a = f"pretrained.act_postprocess{k + 1}."
+        out[a + "0.project.0.weight"], out[a + "0.project.0.bias"] = (W, 2 * W), (W,)
+        out[a + "3.weight"], out[a + "3.bias"] = (c, W, 1, 1), (c,)
+        ks = {0: 4, 1: 2, 3: 3}.get(k)  # ConvTranspose2d k = s = 4 / 2, Identity, Conv2d 3x3 stride 2
+        if ks:
+            out[a + "4.weight"], out[a + "4.bias"] = (c, c, ks, ks), (c,)
+        out[f"scratch.layer{k + 1}_rn.weight"] = (F, c, 3, 3)
+    for k in range(4):
+        r = f"scratch.refinenet{k + 1}."
+        for unit in ((1, 2) if k < 3 else (2,)):
+            for conv in (1, 2):
+                out[f"{r}resConfUnit{unit}.conv{conv}.weight"], out[f"{r}resConfUnit{unit}.conv{conv}.bias"] = (F, F, 3, 3), (F,)
+        out[r + "out_conv.weight"], out[r + "out_conv.bias"] = (F, F, 1, 1), (F,)
+    out["scratch.output_conv.0.weight"], out["scratch.output_conv.0.bias"] = (F // 2, F, 3, 3), (F // 2,)
+    out["scratch.output_conv.2.weight"], out["scratch.output_conv.2.bias"] = (32, F // 2, 3, 3), (32,)
+    out["scratch.output_conv.4.weight"], out["scratch.output_conv.4.bias"] = (1, 32, 1, 1), (1,)
+    return out
+
+
+def depth_net_size(H, W, size=384):
+    """The size the depth net runs a (H, W) frame at: the short side goes to `size`, both sides to the nearest multiple of 32 (at least 32)."""
+    import math
+    s = size / min(H, W)
+    return tuple(max(32, 32 * int(math.floor(side * s / 32 + 0.5))) for side in (H, W))
+
+
+def depth_resize_pos_embed(pos, native_grid, gh, gw):
+    """pos_embed (1, 1 + n n, W) -> the rows (1 + gh gw, W) of a (gh, gw) token grid: the grid part resized bilinearly (align_corners=False),
+    the class row kept; the native grid comes back unchanged."""
+    pos = pos.reshape(1 + native_grid * native_grid, -1).float()
+    if (gh, gw) == (native_grid, native_grid):
+        return pos
+    grid = pos[1:].reshape(1, native_grid, native_grid, -1).permute(0, 3, 1, 2)
+    grid = th.nn.functional.interpolate(grid, size=(gh, gw), mode="bilinear", align_corners=False)
+    return th.cat([pos[:1], grid.permute(0, 2, 3, 1).reshape(gh * gw, -1)])
+
+
+class DepthNet(_Net):
+    """DPT-Large (MiDaS v3, Ranftl et al., "Vision Transformers for Dense Prediction"), forward only: the depth network of 3D animation.
+    `load_state_dict` takes the published dpt_large-midas-2f21e586.pt by its own keys (depth_param_shapes; every shape is cross-checked, a
+    missing key or a wrong shape is a ValueError naming it; `pretrained.model.norm.*`, `pretrained.model.head.*` and
+    `scratch.refinenet4.resConfUnit1.*` are ignored).  The key table is written from memory: no checkpoint was available to check it against.
+
+    The object is the callable `animate(depth=...)` takes: `net(frame)` with frame (B, 3, H, W) in [0, 1] on the GPU returns (B, 1, H, W)
+    fp32, finite and at least `floor`.  The frame goes to depth_net_size(H, W, size) through the antialiased cubic resize (edge-replicating),
+    normalised to [-1, 1] in the same launch; the net's inverse depth becomes depth = max((offset - inv_depth) / scale, floor) at net size
+    (50 and 19 are Deforum's constants as remembered: typical MiDaS output lands near the flat default 1.0), and the same resize takes it back
+    to (H, W), clamped at `floor` again because the cubic overshoots."""
+    _prefix = "depth"
+
+    def __init__(self, ctx, config="dpt_large", size=384, offset=50.0, scale=19.0, floor=0.05):
+        self.ctx = ctx
+        self.cfg, self.config = depth_config(config)
+        self.size, self.offset, self.scale, self.floor = int(size), float(offset), float(scale), float(floor)
+        if self.size < 32 or not self.scale != 0 or not self.floor > 0:
+            raise ValueError(f"DepthNet: size >= 32, scale != 0 and floor > 0 are required, got {size}, {scale}, {floor}")
+        h = C.c_void_p()
+        ctx.check(ctx.lib.cgd_depth_create(ctx.h, C.byref(self.cfg), C.byref(h)))
+        self._adopt(h)
+        self._pos, self._grids = None, set()
+
+    def load_state_dict(self, sd, prefix=""):
+        shapes = depth_param_shapes(self.config)
+        for key, shape in shapes.items():
+            if prefix + key not in sd:
+                raise ValueError(f"depth checkpoint: missing key {prefix + key}")
+            if tuple(sd[prefix + key].shape) != tuple(shape):
+                raise ValueError(f"depth checkpoint: {prefix + key} has shape {tuple(sd[prefix + key].shape)}, expected {tuple(shape)}")
+        self._pos = sd[prefix + "pretrained.model.pos_embed"].detach().float().cpu()
+        self._grids = set()
+        return super().load_state_dict(sd, prefix)
+
+    def _ensure_grid(self, gh, gw):
+        ng = self.config["native_grid"]
+        if (gh, gw) == (ng, ng) or (gh, gw) in self._grids:
+            return
+        if self._pos is None:
+            raise RuntimeError("DepthNet: load_state_dict first")
+        rows = depth_resize_pos_embed(self._pos, ng, gh, gw).contiguous()
+        th.cuda.current_stream(self.ctx.device).synchronize()  # (the upload is a blocking copy outside the stream's order)
+        self.ctx.check(self.ctx.lib.cgd_depth_set_pos_embed(self.h, gh, gw, rows.data_ptr()))
+        self._grids.add((gh, gw))
+
+    def forward(self, img, want="inv_depth"):
+        """img (B, 3, h, w) fp32 NCHW on the GPU, already normalised to [-1, 1], h and w multiples of 32 -> inv_depth (B, 1, h, w), or with
+        want="depth" the mapped depth, or with want="both" the pair."""
+        img = img.contiguous().float()
+        B, _, h, w = img.shape
+        if h % 32 or w % 32:
+            raise ValueError(f"DepthNet: the net runs at multiples of 32, got {h} x {w}")
+        p = self.config["patch"]
+        self._ensure_grid(h // p, w // p)
+        inv = th.empty((B, 1, h, w), device=img.device, dtype=th.float32) if want in ("inv_depth", "both") else None
+        dep = th.empty((B, 1, h, w), device=img.device, dtype=th.float32) if want in ("depth", "both") else None
+        self.ctx.check(self.ctx.lib.cgd_depth_forward(self.h, img.data_ptr(), B, h, w, self.offset, self.scale, self.floor,
+                                                      None if inv is None else inv.data_ptr(), None if dep is None else dep.data_ptr(),
+                                                      self.ctx.stream()))
+        self._keep = img  # inputs must outlive the enqueued work
+        return (inv, dep) if want == "both" else (inv if dep is None else dep)
+
+    def debug_map(self, k):
+        """Test support: the reassembled map of tap k = 0..3 of the last forward, (B, c_k, h_k, w_k)."""
+        out3 = (C.c_int * 3)()
+        self.ctx.check(self.ctx.lib.cgd_depth_debug_map(self.h, k, None, out3, self.ctx.stream()))
+        B = self._keep.shape[0]
+        t = th.empty((B, out3[0], out3[1], out3[2]), device=self._keep.device, dtype=th.float32)
+        self.ctx.check(self.ctx.lib.cgd_depth_debug_map(self.h, k, t.data_ptr(), out3, self.ctx.stream()))
+        return t.permute(0, 3, 1, 2)
+
+    def __call__(self, frame):
+        from . import ops
+        if frame.dim() != 4 or frame.shape[1] != 3:
+            raise ValueError(f"DepthNet: expected a (B, 3, H, W) frame, got {tuple(frame.shape)}")
+        frame = frame.contiguous().float()
+        B, _, H, W = frame.shape
+        h, w = depth_net_size(H, W, self.size)
+        img = ops.resize_cubic(self.ctx, frame, h, w, a=2.0, b=-1.0)  # (x - 0.5) / 0.5 in the resize's launch
+        dep = self.forward(img, want="depth")
+        return ops.resize_cubic(self.ctx, dep, H, W, lo=self.floor)
+
+
 def manifest(kind, cfg=None):
     """[(name, numel)] of a network configuration from the library's host-only manifest functions (no GPU, no context)."""
     out = []

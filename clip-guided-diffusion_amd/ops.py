@@ -380,6 +380,21 @@ def frame_warp3d(ctx, src, camera, depth=None, interp="bicubic", border="wrap", 
     return out
 
 
+def resize_cubic(ctx, x, Ho, Wo, a=1.0, b=0.0, lo=None, out=None):
+    """a * resize(x) + b of x (B,C,H,W) to (B,C,Ho,Wo) in one launch (cgd_op_resize_cubic): the antialiased cubic weights of the resized
+    cutouts, the taps outside the image read at the nearest edge pixel; `lo`: the result is clamped from below.  An identical size copies."""
+    px = _nchw(x, "x")
+    B, Cn, H, W = x.shape
+    if out is None:
+        out = th.empty((B, Cn, int(Ho), int(Wo)), device=x.device, dtype=th.float32)
+    po = _dense(out, "out")
+    if tuple(out.shape) != (B, Cn, int(Ho), int(Wo)):
+        raise ValueError(f"out: expected shape {(B, Cn, int(Ho), int(Wo))}, got {tuple(out.shape)}")
+    ctx.check(ctx.lib.cgd_op_resize_cubic(ctx.h, px, po, B * Cn, H, W, int(Ho), int(Wo), float(a), float(b), float(lo or 0.0), int(lo is not None),
+                                          _s()))
+    return out
+
+
 def channel_stats(ctx, x, out=None):
     """(B,C,2): mean and population standard deviation of every plane of x (B,C,H,W), sums in fp64 (cgd_channel_stats)."""
     px = _nchw(x, "x")

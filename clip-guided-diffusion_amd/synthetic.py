@@ -157,3 +157,37 @@ def aesthetic_head(dim, seed=1357, device="cpu"):
     per element, so that a . normalize(e) is of order 1 like the spread of a trained head's scores, and beta = 5, the middle of their 1-10 scale."""
     g = th.Generator().manual_seed(seed + int(dim))
     return {"head": th.cat([th.randn(int(dim), generator=g), th.tensor([5.0])]).to(device)}
+
+
+def depth_state_dict(config="dpt_large", seed=4321, device="cpu"):
+    """Seeded stand-in for a DPT checkpoint (`nets.DepthNet`) under the published file's key names and shapes (nets.depth_param_shapes): the ViT
+    as the CLIP towers are drawn (N(0, 1 / fan_in) matrices, width^-0.5 class token and position embedding, 1 + N(0, 0.02) norm gains),
+    He-scaled convolutions in the ReLU decoder so that the activations do not die out, N(0, 0.02) biases; the last conv is a tenth of that and its bias 0.5, so that
+    the inverse depth is O(1), positive on part of the image and zero (its ReLU) elsewhere."""
+    from . import nets
+    g = th.Generator().manual_seed(seed)
+    shapes = nets.depth_param_shapes(config)
+    width = shapes["pretrained.model.cls_token"][-1]
+    sd = {}
+    for name, shape in shapes.items():
+        leaf = name.rsplit(".", 1)[-1]
+        if ".norm1." in name or ".norm2." in name:
+            t = 0.02 * th.randn(shape, generator=g) + (1.0 if leaf == "weight" else 0.0)
+        elif name == "scratch.output_conv.4.bias":
+            t = th.full(shape, 0.5)
+        elif leaf == "bias":
+            t = 0.02 * th.randn(shape, generator=g)
+        elif leaf in ("cls_token", "pos_embed"):
+            t = width ** -0.5 * th.randn(shape, generator=g)
+        else:
+            fan_in = 1
+            for n in shape[1:]:
+                fan_in *= n
+            if ".4.weight" in name and len(shape) == 4 and shape[2] in (2, 4):  # ConvTranspose2d [Cin][Cout][k][k]: every output sees Cin inputs
+                fan_in = shape[0]
+            gain = 2.0 if name.startswith("scratch.") else 1.0
+            t = (gain / fan_in) ** 0.5 * th.randn(shape, generator=g)
+            if name == "scratch.output_conv.4.weight":
+                t = 0.1 * t
+        sd[name] = t.to(device)
+    return sd

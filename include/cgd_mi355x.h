@@ -259,6 +259,62 @@ int cgd_op_secondary_pack(cgd_ctx* ctx, const float* x, const float* t, const fl
 int cgd_op_bilinear_up2x(cgd_ctx* ctx, const float* in, int ldi, float* out, int ldo, int B, int Hi, int Wi, int C, int adjoint,
                          void* stream);
 
+/* ---- DPT-Large (MiDaS v3: dpt_large-midas-2f21e586.pt), the depth network of 3D animation; forward only (csrc/depth.hip).  Parameter names
+ *      are the checkpoint's own (pretrained.model.*, pretrained.act_postprocess{1..4}.*, scratch.*); the groups the forward does not use
+ *      (pretrained.model.norm / head, scratch.refinenet4.resConfUnit1) are not part of the manifest.  DPT-Large is
+ *      {16, 1024, 24, 16, {5, 11, 17, 23}, 24, 256, {256, 512, 1024, 1024}}.  create refuses (-2) what the kernels cannot run: channel counts
+ *      that are no multiples of 32, a head dim other than 64 or 80, hooks that are not increasing block indices.
+ *   set_pos_embed   the position embedding [(1 + gh gw)][width] (class row first; host or device memory) of a token grid other than the
+ *                   native one, resized by the caller (bilinear, align_corners = False, on the grid part); kept per grid.
+ *   forward         img (B,3,H,W) NCHW fp32, already normalised, H and W multiples of 32 -> inv_depth (B,1,H,W) and / or
+ *                   depth = max((offset - inv_depth) / scale, floor) (either may be NULL, not both).  Anything else fails (-2) before any
+ *                   launch, as does a grid without a position embedding.
+ *   debug_map       test support: the reassembled map of tap k = 0..3 of the last forward (in front of layer{k+1}_rn) as dense NHWC rows;
+ *                   out3 = {height, width, channels}; out == NULL only reports the shape. */
+typedef struct cgd_depth cgd_depth;
+typedef struct cgd_depth_config {
+  int patch, width, layers, heads, hooks[4], native_grid, features, reassemble_channels[4];
+} cgd_depth_config;
+int cgd_depth_manifest(const cgd_depth_config* cfg, cgd_manifest_cb cb, void* user);
+int cgd_depth_create(cgd_ctx* ctx, const cgd_depth_config* cfg, cgd_depth** out);
+void cgd_depth_destroy(cgd_depth* v);
+int cgd_depth_num_params(cgd_depth* v);
+int cgd_depth_param_info(cgd_depth* v, int index, char* name_buf, int buf_len, int64_t* numel);
+int cgd_depth_set_param(cgd_depth* v, const char* name, const float* data, int64_t numel);
+int cgd_depth_finalize(cgd_depth* v);
+int cgd_depth_set_pos_embed(cgd_depth* v, int gh, int gw, const float* data);
+int cgd_depth_forward(cgd_depth* v, const float* img, int B, int H, int W, float offset, float scale, float floor, float* inv_depth,
+                      float* depth, void* stream);
+int cgd_depth_debug_map(cgd_depth* v, int k, float* out, int* out3, void* stream);
+/* measurement support (benchmarks/depth_step.py): after_backbone != 0 makes every later forward return behind the last hooked block, writing
+ * no output; 0 restores the whole forward */
+int cgd_depth_debug_stop(cgd_depth* v, int after_backbone);
+/* single ops of the depth network, exported for parity tests.  All work on NHWC rows (C and the row strides multiples of 4, pointers 16-byte
+ * aligned) unless stated otherwise and fail (-2) before anything is launched when an argument breaks a rule.
+ *   relu_rows         out = relu(in) on [rows][C] views (out may be in)
+ *   bilinear_up2x_ac  align_corners = True: in [B][Hi][Wi] -> out [B][2Hi][2Wi] (+ add, of out's shape, or NULL); output o reads the source
+ *                     position o (n - 1) / (2n - 1); n = 1 is a copy
+ *   conv_transpose    ConvTranspose2d with kernel = stride = k in {2, 4}: w [Cin][Cout][k][k] as torch stores it, bias [Cout] or NULL, Cin and
+ *                     Cout multiples of 32; wpack (Cin Cout k k floats) and g (B H W Cout k k floats) are scratch
+ *   depth_readout     DPT's ProjectReadout: tok [B (L + 1)][W] (class token first), w [W][2W], bias [W] -> out [B L][W] =
+ *                     GELU(w [tok_i | cls] + bias); tmp (B (L + 1) W floats) and clsv (B W floats) are scratch; W a multiple of 32
+ *   depth_head_tail   x [rows][32] (stride ldx) -> inv_depth[r] = relu(bias[0] + sum_c w[c] act(x[r][c])), act = ReLU when relu_in;
+ *                     depth[r] = max((offset - inv_depth[r]) / scale, floor); either output may be NULL
+ *   resize_cubic      `planes` dense (Hi, Wi) planes -> (Ho, Wo): out = a * resize(in) + b (clamp_lo: max(., lo) of that) with the antialiased cubic weights of the resized
+ *                     cutouts, the taps outside the image read at the nearest edge pixel; one launch, gather form; an identical size copies
+ *                     (bit-identical for a = 1, b = 0); at most an 8-fold reduction per axis */
+int cgd_op_relu_rows(cgd_ctx* ctx, const float* in, int ldi, float* out, int ldo, int64_t rows, int C, void* stream);
+int cgd_op_bilinear_up2x_ac(cgd_ctx* ctx, const float* in, int ldi, float* out, int ldo, const float* add, int ldadd, int B, int Hi, int Wi,
+                            int C, void* stream);
+int cgd_op_conv_transpose(cgd_ctx* ctx, const float* x, int ldx, const float* w, const float* bias, float* out, int ldo, float* wpack,
+                          float* g, int B, int H, int W, int Cin, int Cout, int k, void* stream);
+int cgd_op_depth_readout(cgd_ctx* ctx, const float* tok, const float* w, const float* bias, float* out, float* tmp, float* clsv, int B,
+                         int L, int W, void* stream);
+int cgd_op_depth_head_tail(cgd_ctx* ctx, const float* x, int ldx, const float* w, const float* bias, float* inv_depth, float* depth,
+                           int64_t rows, int relu_in, float offset, float scale, float floor, void* stream);
+int cgd_op_resize_cubic(cgd_ctx* ctx, const float* in, float* out, int planes, int Hi, int Wi, int Ho, int Wo, float a, float b,
+                        float lo, int clamp_lo, void* stream);
+
 /* ---- Noisy ImageNet classifier of guided-diffusion (EncoderUNetModel with pool="attention": 64x64_classifier.pt ... 512x512_classifier.pt):
  *      the encoder half of the ADM UNet (time_embed, input_blocks, middle_block: same ResBlocks and legacy-order AttentionBlocks, no label_emb,
  *      no output blocks), then out.0 (GroupNorm32) -> SiLU -> out.2 (AttentionPool2d: positional_embedding (C, S*S+1), qkv_proj, c_proj; new

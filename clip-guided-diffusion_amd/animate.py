@@ -9,6 +9,9 @@ change at keyframes.
         [--depth_model dpt_large-midas-2f21e586.pt[:size=384][:offset=50][:scale=19] | --depth_fn MODULE:FUNCTION] [--depth_iters 2] ... \\
         -- <cgd command-line flags>
 
+    python -m cgd_amd.animate --frames 120 --mode video --video_frames DIR_OR_GLOB [--flow_blend 0.999] [--check_consistency] \\
+        [--flow_levels 4] [--flow_iters 4] [--flow_radius 4] ... -- <cgd command-line flags>
+
 or, from Python, `animate(frames, zoom=..., **clip_guided_diffusion_kwargs)`, a generator of `(frame_idx, batch_idx, png_path)`.
 
 Networks, cutout maker, tables and guidance are built once (cgd.cgd.prepare_run) and every frame runs the sampler loop on them.  Between two
@@ -39,9 +42,26 @@ every pixel, so that near things move faster than far ones (cgd_frame_warp3d, cs
       signs are this project's own; they have not been compared with Deforum's.
 Depth is flat (Deforum's use_depth_warping=False), the caller's (a tensor, or a callable of the previous frame), or DPT-Large's
 (`--depth_model FILE`, nets.DepthNet: the MiDaS network Disco Diffusion and Deforum use, run natively once per frame).
+
+Video mode (`--mode video`, Disco Diffusion's video input and Warp notebooks, Deforum's hybrid video): an existing clip is stylised.  The motion
+is not typed in but estimated from the clip, natively (csrc/flow.hip): dense pyramidal Lucas-Kanade optical flow, then a warp that follows it.
+  A flow is (B, 2, H, W) fp32, channel 0 the x displacement in pixels (positive: right), channel 1 the y displacement (positive: down), pixel
+      centres on integers; ops.flow_estimate(tmpl, img) returns F with img(p + F(p)) ~ tmpl(p).
+  Frame 0 starts from video frame 0 (the init image, skip_timesteps = round(frames_skip T), LPIPS weight frames_scale).  Frame k > 0 takes
+      F = flow_estimate(video_k, video_{k-1}), so that the previous stylised frame read at p + F(p) lies where the clip's frame k has it, and
+      starts from  w S(p + F(p)) + (1 - w) video_k(p),  w = flow_blend m(p): `flow_blend` is the share of the warped previous stylised frame
+      where the flow is trusted (m = 1); the rest, and everything where it is not (m = 0), is the clip's own frame k.  With
+      `check_consistency` the flow of the opposite direction is estimated too and m = 0 where the two disagree (occlusions) or where the
+      flow leaves the frame; without it m = 1 everywhere.
+  `border` and `interp` are the warp's, as in the other modes.  The driver's default border, wrap, suits a tiling 2D zoom and is a poor choice
+      for a clip: a flow that points out of the frame then reads the opposite edge.  Give `--border replicate` (or reflect), or
+      `--check_consistency`, which falls back to the clip's frame wherever the flow leaves the frame.
+  Only the clip's frames k - 1 and k are on the GPU at a time.  Image quality on trained weights and on real footage has not been judged here:
+      only seeded random weights and synthetic clips were available.
 """
 import argparse
 import collections
+import glob
 import importlib
 import math
 import re
@@ -49,7 +69,9 @@ import sys
 
 BORDERS = ("wrap", "reflect", "replicate")
 INTERPS = ("bilinear", "bicubic")
-MODES = ("2d", "3d")
+MODES = ("2d", "3d", "video")
+VIDEO_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".webp", ".tif", ".tiff")
+VIDEO_DEFAULTS = dict(video_frames=None, flow_blend=0.999, check_consistency=False, flow_levels=4, flow_iters=4, flow_radius=4)
 TRANSLATION_SCALE = 200.0
 
 Camera = collections.namedtuple("Camera", "R T f cx cy z0 near")
@@ -292,6 +314,71 @@ def load_depth_model(ctx, spec):
     return nets.DepthNet(ctx, config, **opts).load_state_dict(sd)
 
 
+def list_video_frames(spec):
+    """The clip of video mode: a tensor (N, 3, H, W) in [-1, 1] passes through; a directory gives its image files (VIDEO_EXTENSIONS) and a
+    glob pattern its matches, both in name order; a list or tuple of paths is taken as it stands.  ValueError for anything else."""
+    import os
+    if spec is None:
+        raise ValueError("mode='video' needs video_frames: a directory, a glob, a list of paths or a tensor (N, 3, H, W)")
+    if hasattr(spec, "dim"):
+        if spec.dim() != 4 or spec.shape[1] != 3:
+            raise ValueError(f"video_frames: a tensor must be (N, 3, H, W), got {tuple(spec.shape)}")
+        return spec
+    if isinstance(spec, (list, tuple)):
+        return [os.fspath(p) for p in spec]
+    spec = os.fspath(spec)
+    if os.path.isdir(spec):
+        return [os.path.join(spec, n) for n in sorted(os.listdir(spec)) if n.lower().endswith(VIDEO_EXTENSIONS)]
+    return sorted(glob.glob(spec))
+
+
+def _check_video(mode, frames, video, motion, motion3d, fov, depth, depth_iters, near, depth_model, kw):
+    """The refusals of video mode and of its arguments in the other modes, before anything is loaded -> the clip (list_video_frames) or
+    None.  `video`: the six video arguments by name; `motion`: zoom, angle, translation_x, translation_y."""
+    if mode != "video":
+        given = [n for n, v in video.items() if v is not VIDEO_DEFAULTS[n] and v != VIDEO_DEFAULTS[n]]
+        if given:
+            raise ValueError(f"{', '.join(given)}: only with mode='video'")
+        return None
+    names = ("zoom", "angle", "translation_x", "translation_y", "translation_z", "rotation_3d_x", "rotation_3d_y", "rotation_3d_z", "fov")
+    neutral = (1, 0, 0, 0, 0, 0, 0, 0, 40)
+    given = [n for n, spec, v0 in zip(names, tuple(motion) + tuple(motion3d) + (fov,), neutral) if any(v != v0 for v in keyframes(spec, frames))]
+    given += ["depth"] * (depth is not None) + ["depth_iters"] * (depth_iters != 1) + ["near"] * (near != 0.05)
+    given += ["depth_model"] * (depth_model is not None)
+    if given:
+        raise ValueError(f"{', '.join(given)}: not with mode='video', where the motion comes from the clip")
+    if kw.get("init_image"):
+        raise ValueError("mode='video' takes no init_image: frame 0 starts from the clip's first frame")
+    if not (0 <= video["flow_blend"] <= 1):
+        raise ValueError(f"flow_blend must lie in [0, 1], got {video['flow_blend']!r}")
+    for name, lo, hi in (("flow_levels", 1, 8), ("flow_iters", 1, 16), ("flow_radius", 1, 7)):
+        v = video[name]
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
+    clip = list_video_frames(video["video_frames"])
+    if len(clip) < 1:
+        raise ValueError(f"video_frames {video['video_frames']!r}: fewer than one frame")
+    if frames > len(clip):
+        raise ValueError(f"frames = {frames}, but the clip has {len(clip)} frames")
+    return clip
+
+
+def _video_frame(clip, k, B, H, W, device):
+    """Frame k of the clip as (B, 3, H, W) fp32 in [-1, 1] on `device`: a file is opened with PIL and resized to the run's frame as the
+    init image is; a tensor must have the run's frame size."""
+    import numpy as np
+    import torch as th
+    if hasattr(clip, "dim"):
+        if tuple(clip.shape[2:]) != (H, W):
+            raise ValueError(f"video_frames: the tensor's frames are {tuple(clip.shape[2:])}, the run's {(H, W)}")
+        frame = clip[k:k + 1].detach().to(device=device, dtype=th.float32)
+    else:
+        from PIL import Image
+        pil = Image.open(clip[k]).convert("RGB").resize((W, H))
+        frame = th.from_numpy(np.array(pil)).float().div(255).permute(2, 0, 1).to(device).unsqueeze(0).mul(2).sub(1)
+    return frame.expand(B, -1, -1, -1).contiguous()
+
+
 def _check_mode(mode, frames, zoom, angle, motion3d, fov, depth, depth_iters, near, depth_model=None):
     """The refusals of the mode arguments, before anything is loaded -> the five 3D tracks (translation_z, rotation_3d_x / y / z, fov)."""
     if mode not in MODES:
@@ -340,7 +427,8 @@ def _depth_map(depth, k, B, H, W, device=None):
 
 def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, border="wrap", interp="bicubic", frames_skip=0.6,
             frames_scale=1500, color_match=0.0, fixed_seed=False, prompts_at=None, mode="2d", translation_z=0.0, rotation_3d_x=0.0,
-            rotation_3d_y=0.0, rotation_3d_z=0.0, fov=40.0, depth=None, depth_iters=1, near=0.05, depth_model=None, **cgd_kwargs):
+            rotation_3d_y=0.0, rotation_3d_z=0.0, fov=40.0, depth=None, depth_iters=1, near=0.05, depth_model=None, video_frames=None, flow_blend=0.999,
+            check_consistency=False, flow_levels=4, flow_iters=4, flow_radius=4, **cgd_kwargs):
     """Generator of `(frame_idx, batch_idx, png_path)`: `frames` frames, each the last image of one sampling run, written to
     prefix_path/<prompts>/<batch_idx:02>/<frame_idx:04>.png.
 
@@ -363,6 +451,15 @@ def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, b
     'FILE[:size=N][:offset=A][:scale=B]' (parse_depth_model) builds one from a DPT-Large checkpoint, once, on the run's context, and excludes
     `depth`.
 
+    `mode="video"` stylises a clip (module docstring): `video_frames` is a directory or a glob of image files (taken in name order), a list of
+    paths, or a tensor (N, 3, H, W) in [-1, 1]; files are opened with PIL and resized to the run's frame as an init image is.  Frame 0 starts
+    from the clip's frame 0 (skip_timesteps = round(frames_skip * num_timesteps), LPIPS weight `frames_scale`); frame k > 0 from
+    ops.frame_warp_flow(previous, ops.flow_estimate(clip_k, clip_{k-1}, flow_levels, flow_iters, flow_radius), flow_back, fallback=clip_k,
+    blend=flow_blend, interp, border, clamp=True), with flow_back = ops.flow_estimate(clip_{k-1}, clip_k, ...) under `check_consistency` and
+    None otherwise; colour matching, seeds, `prompts_at` and the PNG paths are those of the other modes.  Video mode takes no `zoom`, `angle`,
+    `translation_*`, `rotation_3d_*`, `fov`, depth argument or `init_image`, the other modes take no video argument, and `frames` may not
+    exceed the clip's length.
+
     Refused before anything is loaded (ValueError): an unknown `mode`, `zoom` / `angle` in 3D mode, a 3D-only argument in 2D mode,
     `depth_iters` outside 1..4, a `fov` that leaves (0, 180), an init_image with '::MASK', 'invert=', 'upsample=' or 'ilvrN=', 'SOURCE=>TARGET'
     prompts, use_augs, a world size above 1, frames < 1, frames_skip outside [0, 1) or so high that no step is left, and prompts_at together
@@ -378,16 +475,21 @@ def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, b
     if any(not z > 0 for z in tracks[0]):
         raise ValueError("zoom must stay positive on every frame")
     depth_model = parse_depth_model(depth_model)
-    tracks3d = _check_mode(mode, frames, zoom, angle, (translation_z, rotation_3d_x, rotation_3d_y, rotation_3d_z), fov, depth, depth_iters, near,
-                           depth_model)
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+    motion3d = (translation_z, rotation_3d_x, rotation_3d_y, rotation_3d_z)
+    clip = _check_video(mode, frames, dict(video_frames=video_frames, flow_blend=flow_blend, check_consistency=check_consistency,
+                                           flow_levels=flow_levels, flow_iters=flow_iters, flow_radius=flow_radius),
+                        (zoom, angle, translation_x, translation_y), motion3d, fov, depth, depth_iters, near, depth_model, cgd_kwargs)
+    tracks3d = _check_mode("2d" if mode == "video" else mode, frames, zoom, angle, motion3d, fov, depth, depth_iters, near, depth_model)
     seed = cgd_kwargs.get("seed", 0)
-    run = entry.prepare_run(**cgd_kwargs, lpips_for_later=frames > 1 and frames_scale != 0)
+    run = entry.prepare_run(**cgd_kwargs, lpips_for_later=(frames > 1 or mode == "video") and frames_scale != 0)
     if run is None:
         return
     cond_fn, ctx = run.cond_fn, run.model.ctx
     _, _, H, W = run.shape
     skip = int(round(frames_skip * run.diffusion.num_timesteps))
-    if frames > 1 and skip >= run.diffusion.num_timesteps:
+    if (frames > 1 or mode == "video") and skip >= run.diffusion.num_timesteps:
         raise ValueError(f"frames_skip {frames_skip} leaves no step of the {run.diffusion.num_timesteps} for the frames after the first")
 
     def retarget(texts):
@@ -410,14 +512,25 @@ def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, b
         depth = load_depth_model(ctx, depth_model)
     if mode == "3d" and depth is not None and not callable(depth):
         depth = _depth_map(depth, 0, B, H, W)  # judged now that the frame size is known; it joins the state's device at its first use
-    previous = previous_x0 = stats0 = None
+    previous = previous_x0 = stats0 = video_now = video_before = None
+    flow_kw = dict(levels=flow_levels, iters=flow_iters, radius=flow_radius)
     for k in range(frames):
         if k in plan:
             retarget(plan[k])
         init = None
+        if mode == "video":  # only the clip's frames k - 1 and k are on the GPU
+            video_before, video_now = video_now, _video_frame(clip, k, B, H, W, run.device)
+            if k == 0:
+                init = video_now
+                cond_fn.set_init(init if frames_scale != 0 else None, frames_scale)
         if k > 0:
             th.manual_seed(seed if fixed_seed else seed + k)
-            if mode == "3d":
+            if mode == "video":
+                flow = ops.flow_estimate(ctx, video_now[:1], video_before[:1], **flow_kw)
+                back = ops.flow_estimate(ctx, video_before[:1], video_now[:1], **flow_kw) if check_consistency else None
+                init = ops.frame_warp_flow(ctx, previous, flow, flow_back=back, fallback=video_now, blend=flow_blend, interp=interp,
+                                           border=border, clamp=True)
+            elif mode == "3d":
                 cam = camera(tracks[2][k], tracks[3][k], *(t[k] for t in tracks3d), H, W, near=near)
                 if callable(depth):
                     dmap = _depth_map(depth((previous_x0.clamp(-1, 1) + 1) / 2), k, B, H, W, previous.device)
@@ -431,7 +544,7 @@ def animate(frames, zoom=1.0, angle=0.0, translation_x=0.0, translation_y=0.0, b
                 ops.color_match(ctx, init, stats0, amount=color_match, clamp=True)
             cond_fn.set_init(init if frames_scale != 0 else None, frames_scale)
         last = None
-        for last in (run.samples() if k == 0 else run.samples(init_image=init, skip_timesteps=skip)):
+        for last in (run.samples() if init is None else run.samples(init_image=init, skip_timesteps=skip)):
             cond_fn.current_timestep -= 1
         if last is None:
             raise RuntimeError(f"frame {k}: the sampler loop made no step")
@@ -453,7 +566,16 @@ def build_parser():
                                 ("translation_x", "0", "pixels per frame, positive moves the content right"),
                                 ("translation_y", "0", "pixels per frame, positive moves the content down")):
         p.add_argument(f"--{name}", default=default, help=f"{what}: a number or keyframes 'FRAME:(VALUE), ...'")
-    p.add_argument("--mode", default="2d", choices=MODES, help="2d: affine warp (zoom, angle, translation_x / y); 3d: a moving pinhole camera")
+    p.add_argument("--mode", default="2d", choices=MODES, help="2d: affine warp (zoom, angle, translation_x / y); 3d: a moving pinhole camera; "
+                                                               "video: the motion of a clip (--video_frames), estimated as optical flow")
+    p.add_argument("--video_frames", default=None, help="video: a directory or a glob of image files, taken in name order")
+    p.add_argument("--flow_blend", type=float, default=0.999, help="video: share of the warped previous frame where the flow is trusted, in [0, 1]; "
+                                                                   "the rest is the clip's own frame")
+    p.add_argument("--check_consistency", action="store_true", help="video: also estimate the opposite flow and fall back to the clip's frame "
+                                                                    "where the two disagree (occlusions)")
+    p.add_argument("--flow_levels", type=int, default=4, help="video: pyramid levels of the flow, 1..8")
+    p.add_argument("--flow_iters", type=int, default=4, help="video: iterations per level, 1..16")
+    p.add_argument("--flow_radius", type=int, default=4, help="video: window radius in pixels, 1..7")
     for name, default, what in (("translation_z", "0", "3d: 1 / 200 depth units per frame, positive flies forward"),
                                 ("rotation_3d_x", "0", "3d: degrees per frame, positive tilts the camera up (the content moves down)"),
                                 ("rotation_3d_y", "0", "3d: degrees per frame, positive turns the camera right (the content moves left)"),
@@ -467,7 +589,7 @@ def build_parser():
                                                        "(net size N, depth = (A - inverse depth) / B); not together with --depth_fn")
     p.add_argument("--depth_iters", type=int, default=1, help="3d: fixed-point steps of the depth lookup, 1..4")
     p.add_argument("--near", type=float, default=0.05, help="3d: the near plane, in depth units")
-    p.add_argument("--border", default="wrap", choices=BORDERS, help="what the warp reads outside the frame")
+    p.add_argument("--border", default="wrap", choices=BORDERS, help="what the warp reads outside the frame (video: prefer replicate; wrap reads the opposite edge)")
     p.add_argument("--interp", default="bicubic", choices=INTERPS, help="interpolation of the warp")
     p.add_argument("--frames_skip", type=float, default=0.6, help="fraction of the schedule the frames after the first skip")
     p.add_argument("--frames_scale", type=float, default=1500, help="LPIPS weight toward the warped previous frame (0: no LPIPS)")
@@ -501,7 +623,9 @@ def main(argv=None):
                         interp=a.interp, frames_skip=a.frames_skip, frames_scale=a.frames_scale, color_match=a.color_match,
                         fixed_seed=a.fixed_seed, prompts_at=parse_prompts_at(a.prompts_at), mode=a.mode, translation_z=a.translation_z,
                         rotation_3d_x=a.rotation_3d_x, rotation_3d_y=a.rotation_3d_y, rotation_3d_z=a.rotation_3d_z, fov=a.fov,
-                        depth=load_depth_fn(a.depth_fn), depth_iters=a.depth_iters, near=a.near, depth_model=a.depth_model, **kwargs):
+                        depth=load_depth_fn(a.depth_fn), depth_iters=a.depth_iters, near=a.near, depth_model=a.depth_model,
+                        video_frames=a.video_frames, flow_blend=a.flow_blend, check_consistency=a.check_consistency, flow_levels=a.flow_levels,
+                        flow_iters=a.flow_iters, flow_radius=a.flow_radius, **kwargs):
         print("\t".join(str(v) for v in item))
 
 

@@ -8,7 +8,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -Wno-unused-resul
 mkdir -p build
 objs=()
 pids=()
-for src in gemm hconv kconv wconv sconv hgemm conv_thin superres norm elem attn attn_flash guidance direction regions aesthetic plms dpm threshold mask ilvr warp warp3d window invert cutaug cutresize unet classifier vit text resnet gram lpips secondary depth capi; do
+for src in gemm hconv kconv wconv sconv hgemm conv_thin superres norm elem attn attn_flash guidance direction regions aesthetic plms dpm threshold mask ilvr warp warp3d flow window invert cutaug cutresize unet classifier vit text resnet gram lpips secondary depth capi; do
   obj=build/$src.o
   objs+=("$obj")
   if [[ ! -f $obj || $src.hip -nt $obj || common.h -nt $obj || mfma_stage.h -nt $obj || elem_pack.h -nt $obj || resize_rows.h -nt $obj || warp_sample.h -nt $obj || kernels.h -nt $obj || net.h -nt $obj || guidance.h -nt $obj || region_cov.h -nt $obj \

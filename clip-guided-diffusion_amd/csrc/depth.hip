@@ -608,6 +608,11 @@ hipStream_t SS(void* s) { return (hipStream_t)s; }
 
 }  // namespace
 
+int cgd_launch_resize_cubic(cgd_ctx* ctx, const float* in, float* out, int planes, int Hi, int Wi, int Ho, int Wo, float a, float b, float lo,
+                            int clamp_lo, hipStream_t s) {
+  return launch_resize(ctx, in, out, planes, Hi, Wi, Ho, Wo, a, b, lo, clamp_lo, s);
+}
+
 struct cgd_depth {
   Depth net;
 };

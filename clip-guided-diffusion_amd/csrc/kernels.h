@@ -174,6 +174,9 @@ int cgd_launch_color_match(cgd_ctx* ctx, float* x, const float* stats_x, const f
 struct cgd_camera;
 int cgd_launch_frame_warp3d(cgd_ctx* ctx, const float* src, float* dst, const float* depth, int depth_batch, int B, int C, int H, int W,
                             const cgd_camera* cam, hipStream_t s);
+// depth.hip: the launcher behind cgd_op_resize_cubic (include/cgd_mi355x.h), for flow.hip's pyramid; needs a context
+int cgd_launch_resize_cubic(cgd_ctx* ctx, const float* in, float* out, int planes, int Hi, int Wi, int Ho, int Wo, float a, float b, float lo,
+                            int clamp_lo, hipStream_t s);
 // window.hip: the adjoint pair of windowed sampling (include/cgd_mi355x.h: cgd_window_gather / cgd_window_merge); oy [ny], ox [nx]: host arrays of
 // window origins; ay [ny][S], ax [nx][S]: device weight tables, both or neither (null = ones)
 int cgd_launch_window_gather(cgd_ctx* ctx, const float* full, float* win, const int* oy, int ny, const int* ox, int nx, const float* ay,

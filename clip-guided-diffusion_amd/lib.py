@@ -99,6 +99,18 @@ class Camera(C.Structure):
                 ("near", C.c_double), ("iters", i32), ("interp", i32), ("border", i32), ("clamp", i32)]
 
 
+class FlowParams(C.Structure):
+    """cgd_flow_params: pyramid levels, iterations per level, window radius, the regulariser lambda and the longest step of one iteration
+    (pixels) of the Lucas-Kanade flow (cgd_flow_estimate)"""
+    _fields_ = [("levels", i32), ("iters", i32), ("radius", i32), ("lam", f32), ("max_step", f32)]
+
+
+class WarpFlow(C.Structure):
+    """cgd_warp_flow: the settings of cgd_frame_warp_flow: blend, the forward-backward check's alpha and beta, interp / border / clamp as in
+    cgd_warp"""
+    _fields_ = [("blend", f32), ("alpha", f32), ("beta", f32), ("interp", i32), ("border", i32), ("clamp", i32)]
+
+
 WARP_INTERP = {"bilinear": 0, "bicubic": 1}
 WARP_BORDER = {"wrap": 0, "reflect": 1, "replicate": 2}
 
@@ -254,6 +266,11 @@ _SIGS = {
     "cgd_ilvr_refine": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp]),
     "cgd_frame_warp": (i32, [vp, vp, vp, i32, i32, i32, i32, C.POINTER(Warp), vp]),
     "cgd_frame_warp3d": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(Camera), vp]),
+    "cgd_flow_levels": (i32, [i32, i32, i32, i32]),
+    "cgd_flow_scratch_floats": (C.c_long, [i32, i32, i32, i32, i32]),
+    "cgd_flow_estimate": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(FlowParams), vp]),
+    "cgd_op_flow_level": (i32, [vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, C.POINTER(FlowParams), vp]),
+    "cgd_frame_warp_flow": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(WarpFlow), vp]),
     "cgd_channel_stats": (i32, [vp, vp, vp, i32, i32, i32, i32, vp]),
     "cgd_color_match": (i32, [vp, vp, vp, vp, i32, f32, i32, i32, i32, i32, i32, vp]),
     "cgd_window_gather": (i32, [vp, vp, vp, C.POINTER(i32), i32, C.POINTER(i32), i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),

@@ -380,6 +380,99 @@ def frame_warp3d(ctx, src, camera, depth=None, interp="bicubic", border="wrap", 
     return out
 
 
+def _flow_params(levels, iters, radius, lam, max_step):
+    for name, v in (("levels", levels), ("iters", iters), ("radius", radius)):
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    return L.FlowParams(int(levels), int(iters), int(radius), float(lam), float(max_step))
+
+
+def flow_estimate(ctx, tmpl, img, levels=4, iters=4, radius=4, lam=1e-3, max_step=1.0, out=None):
+    """Dense pyramidal Lucas-Kanade flow F (B,2,H,W) with img(p + F(p)) ~ tmpl(p) (cgd_flow_estimate): channel 0 the x displacement in
+    pixels, channel 1 the y displacement; tmpl and img are (B,C,H,W) with C 3 (luminance) or 1.  `levels` pyramid levels at the most
+    (cgd_flow_levels), `iters` iterations per level, windows of (2 radius + 1)^2 pixels, regulariser `lam`, steps of at most `max_step`
+    pixels.  The scratch is the context's, one buffer per (device, size).  `out` must not alias an input."""
+    pt, pi = _nchw(tmpl, "tmpl"), _nchw(img, "img")
+    if tuple(img.shape) != tuple(tmpl.shape) or img.device != tmpl.device:
+        raise ValueError(f"img: shape {tuple(img.shape)} on {img.device}, tmpl has {tuple(tmpl.shape)} on {tmpl.device}")
+    B, Cn, H, W = tmpl.shape
+    p = _flow_params(levels, iters, radius, lam, max_step)
+    if out is None:
+        out = th.empty((B, 2, H, W), device=tmpl.device, dtype=th.float32)
+    po = _nchw(out, "out")
+    if tuple(out.shape) != (B, 2, H, W):
+        raise ValueError(f"out: expected shape {(B, 2, H, W)}, got {tuple(out.shape)}")
+    n = int(ctx.lib.cgd_flow_scratch_floats(B, H, W, p.levels, p.radius))
+    cache = ctx.__dict__.setdefault("_flow_scratch", {})
+    key = (tmpl.device, n)
+    if key not in cache:
+        cache[key] = th.empty(max(n, 1), device=tmpl.device, dtype=th.float32)
+    ctx.check(ctx.lib.cgd_flow_estimate(ctx.h, pt, pi, po, cache[key].data_ptr(), B, Cn, H, W, C.byref(p), _s()))
+    return out
+
+
+def flow_level(ctx, b, a, coarse=None, iters=4, radius=4, lam=1e-3, max_step=1.0, out=None):
+    """One pyramid level of flow_estimate on given planes (cgd_op_flow_level, test support): b, a (B,H,W) template and image level, `coarse`
+    None (start from zero) or the coarser level's flow (B,2,Hc,Wc); returns the level's flow (B,2,H,W)."""
+    pb, pa, pc = _dense(b, "b"), _dense(a, "a"), _dense(coarse, "coarse")
+    if b.dim() != 3 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"b and a: expected one shape (B, H, W), got {tuple(b.shape)} and {tuple(a.shape)}")
+    B, H, W = b.shape
+    Hc = Wc = 0
+    if coarse is not None:
+        if coarse.dim() != 4 or tuple(coarse.shape[:2]) != (B, 2):
+            raise ValueError(f"coarse: expected ({B}, 2, Hc, Wc), got {tuple(coarse.shape)}")
+        Hc, Wc = coarse.shape[2:]
+    p = _flow_params(1, iters, radius, lam, max_step)
+    if out is None:
+        out = th.empty((B, 2, H, W), device=b.device, dtype=th.float32)
+    po = _nchw(out, "out")
+    if tuple(out.shape) != (B, 2, H, W):
+        raise ValueError(f"out: expected shape {(B, 2, H, W)}, got {tuple(out.shape)}")
+    ctx.check(ctx.lib.cgd_op_flow_level(ctx.h, pb, pa, pc, Hc, Wc, po, B, H, W, C.byref(p), _s()))
+    return out
+
+
+def frame_warp_flow(ctx, src, flow, flow_back=None, fallback=None, blend=1.0, alpha=0.01, beta=0.5, interp="bicubic", border="replicate",
+                    clamp=False, out=None, mask_out=None):
+    """out(p) = w S(p + flow(p)) + (1 - w) fallback(p), w = blend m(p), in one launch (cgd_frame_warp_flow): S samples src (B,C,H,W) as
+    frame_warp does (interp, border, clamp); `flow` (1 or B, 2, H, W) in pixels, x first.  m = 1 without `flow_back`; with it (the flow of
+    the opposite direction, same shape) m = 0 where p + flow(p) leaves the frame or the forward-backward check
+    |F + Fb|^2 <= alpha (|F|^2 + |Fb|^2) + beta fails.  `fallback` (B,C,H,W) may be None only with blend == 1 and no flow_back.
+    `mask_out` (B,1,H,W) receives m.  `out` and `mask_out` must not alias an input."""
+    ps = _nchw(src, "src")
+    if interp not in L.WARP_INTERP or border not in L.WARP_BORDER:
+        raise ValueError(f"interp must be one of {sorted(L.WARP_INTERP)} and border one of {sorted(L.WARP_BORDER)}, got {interp!r} and {border!r}")
+    B, Cn, H, W = src.shape
+    pf = _nchw(flow, "flow")
+    if tuple(flow.shape[1:]) != (2, H, W) or flow.shape[0] not in (1, B):
+        raise ValueError(f"flow: expected (1 or {B}, 2, {H}, {W}), got {tuple(flow.shape)}")
+    pb = pfb = pm = None
+    if flow_back is not None:
+        pb = _nchw(flow_back, "flow_back")
+        if tuple(flow_back.shape) != tuple(flow.shape):
+            raise ValueError(f"flow_back: shape {tuple(flow_back.shape)}, flow has {tuple(flow.shape)}")
+    if fallback is not None:
+        pfb = _nchw(fallback, "fallback")
+        if tuple(fallback.shape) != tuple(src.shape):
+            raise ValueError(f"fallback: shape {tuple(fallback.shape)}, src has {tuple(src.shape)}")
+    if out is None:
+        out = th.empty_like(src)
+    po = _nchw(out, "out")
+    if tuple(out.shape) != tuple(src.shape):
+        raise ValueError(f"out: shape {tuple(out.shape)}, src has {tuple(src.shape)}")
+    if mask_out is not None:
+        pm = _nchw(mask_out, "mask_out")
+        if tuple(mask_out.shape) != (B, 1, H, W):
+            raise ValueError(f"mask_out: expected shape {(B, 1, H, W)}, got {tuple(mask_out.shape)}")
+    for name, t in (("flow", flow), ("flow_back", flow_back), ("fallback", fallback), ("out", out), ("mask_out", mask_out)):
+        if t is not None and t.device != src.device:
+            raise ValueError(f"{name} is on {t.device}, src on {src.device}")
+    w = L.WarpFlow(float(blend), float(alpha), float(beta), L.WARP_INTERP[interp], L.WARP_BORDER[border], int(bool(clamp)))
+    ctx.check(ctx.lib.cgd_frame_warp_flow(ctx.h, ps, pf, pb, pfb, po, pm, int(flow.shape[0]), B, Cn, H, W, C.byref(w), _s()))
+    return out
+
+
 def resize_cubic(ctx, x, Ho, Wo, a=1.0, b=0.0, lo=None, out=None):
     """a * resize(x) + b of x (B,C,H,W) to (B,C,Ho,Wo) in one launch (cgd_op_resize_cubic): the antialiased cubic weights of the resized
     cutouts, the taps outside the image read at the nearest edge pixel; `lo`: the result is clamped from below.  An identical size copies."""

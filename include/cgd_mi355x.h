@@ -696,6 +696,58 @@ typedef struct cgd_camera {
 int cgd_frame_warp3d(cgd_ctx* ctx, const float* src, float* dst, const float* depth, int depth_batch, int B, int C, int H, int W,
                      const cgd_camera* cam, void* stream);
 
+/* ---- video mode (Disco Diffusion's video input and Warp notebooks, Deforum's hybrid video): frame k starts from the stylised frame k - 1,
+ *      moved the way the clip moved.  Dense pyramidal Lucas-Kanade optical flow in the PATCH form (each pixel moves its whole window by its
+ *      own flow) and the warp that follows a flow (csrc/flow.hip).  NCHW fp32; pixel centres sit on integers.
+ *      A flow is (B, 2, H, W): channel 0 the x displacement in pixels, channel 1 the y displacement.  cgd_flow_estimate(tmpl, img) writes F
+ *      with img(p + F(p)) ~ tmpl(p); tmpl and img are (B, C, H, W), C 3 (luminance Y = (0.2989 R + 0.587 G) + 0.114 B in fp32) or 1.
+ *      Pyramid: level 0 is Y, level l + 1 the antialiased cubic resize (cgd_op_resize_cubic's launcher) of level l to
+ *      (ceil(H_l / 2), ceil(W_l / 2)), both frames and the whole batch as 2B planes in one launch.  cgd_flow_levels: the largest L <= levels
+ *      whose coarsest level has a shorter side of at least 2 radius + 1, at least 1 (0 for arguments that are refused).  The coarsest level
+ *      starts from zero; a finer level (Hf, Wf) reads the coarser flow (Hc, Wc) bilinearly at ((x + 0.5) Wc / Wf - 0.5,
+ *      (y + 0.5) Hc / Hf - 0.5), fp64 coordinates, taps and weights, replicate border, times Wf / Wc (x) or Hf / Hc (y), rounded to fp32.
+ *      One iteration at pixel p with flow u, over the window q = p + (dx, dy), |dx|, |dy| <= radius, q inside the frame, ascending dy then
+ *      ascending dx: b the template level, bx, by its central differences divided by 2 (replicate border); s = q + u in fp64 counts when
+ *      0 <= sx <= W - 1 and 0 <= sy <= H - 1 and contributes to nothing otherwise; a(s) bilinear, split in fp64 with fp32 weights as
+ *      cgd_frame_warp splits; e = b(q) - a(s); fp32 sums Gxx = lambda + sum bx^2, Gyy = lambda + sum by^2, Gxy = sum bx by,
+ *      rx = sum bx e, ry = sum by e; det = Gxx Gyy - Gxy^2, du = (Gyy rx - Gxy ry) / det, dv = (Gxx ry - Gxy rx) / det; a non-finite
+ *      step is zero, a step longer than max_step is scaled to that length; u += (du, dv).  All `iters` iterations of a level run in one
+ *      launch (a pixel reads only its own flow); an estimate is about 2 L launches.  Fixed summation order, no atomics: the same bits on
+ *      every run.  scratch: cgd_flow_scratch_floats(B, H, W, levels, radius) floats (0 for arguments that are refused).
+ *      cgd_op_flow_level (test support): one level on given planes b, a (B, H, W); coarse (B, 2, Hc, Wc) or NULL (start from zero); flow
+ *      (B, 2, H, W) is written only.
+ *      cgd_frame_warp_flow, one launch, gather form:  dst(p) = w S(p + F(p)) + (1 - w) fallback(p),  w = blend m(p).  S samples src
+ *      (B, C, H, W) exactly as cgd_frame_warp does (interp, border, clamp, summation order; position p + (double)F(p) clamped to +-2^30).
+ *      m = 1 without flow_back.  With flow_back (the flow of the opposite direction) Fb is read bilinearly at s = p + F(p) (fp64 taps,
+ *      replicate border) and m = 0 when s lies outside [0, W - 1] x [0, H - 1], when Fb(s) is not finite, or unless
+ *      |F + Fb|^2 <= alpha (|F|^2 + |Fb|^2) + beta, in fp64 (the forward-backward check of Sundaram et al., 2010; usual values
+ *      alpha 0.01, beta 0.5).  A non-finite F reads as zero flow with m = 0.  w == 1 stores the sample's bits (zero flow with blend 1
+ *      copies src), w == 0 the fallback's.  fallback (B, C, H, W) may be NULL only with blend == 1 and no flow_back; the sample is then
+ *      stored whatever m.  mask_out (B, 1, H, W), optional, receives m.  flow and flow_back are (flow_batch, 2, H, W), flow_batch 1 or B.
+ *      The arguments are judged before the context is looked at: a refused call returns -2 (cgd_last_error), an accepted one -3 with a
+ *      NULL context.  Refused: a null or not 4-byte-aligned pointer, a non-positive size, H W >= 2^31, C not 1 or 3 (estimate), radius
+ *      outside 1..7, iters outside 1..16, levels outside 1..8, a lambda or max_step that is not finite and positive, a flow that aliases
+ *      an input, more than 32767 samples, H W >= 2^30 when more than one pyramid level would run (the resize's limit); for the warp also an unknown interp or border, a flow_batch other than 1 or B, blend outside [0, 1], a negative or
+ *      non-finite alpha or beta, and a dst or mask_out that overlaps an input. ---- */
+typedef struct cgd_flow_params {
+  int levels, iters, radius; /* defaults 4, 4, 4 */
+  float lambda, max_step;    /* defaults 1e-3, 1 */
+} cgd_flow_params;
+typedef struct cgd_warp_flow {
+  float blend, alpha, beta; /* defaults 1, 0.01, 0.5 */
+  int interp;               /* 0 bilinear, 1 bicubic */
+  int border;               /* 0 wrap, 1 reflect, 2 replicate */
+  int clamp;                /* 1: clamp the sample to [-1, 1] */
+} cgd_warp_flow;
+int cgd_flow_levels(int H, int W, int levels, int radius);
+long cgd_flow_scratch_floats(int B, int H, int W, int levels, int radius);
+int cgd_flow_estimate(cgd_ctx* ctx, const float* tmpl, const float* img, float* flow, float* scratch, int B, int C, int H, int W,
+                      const cgd_flow_params* params, void* stream);
+int cgd_op_flow_level(cgd_ctx* ctx, const float* b, const float* a, const float* coarse, int Hc, int Wc, float* flow, int B, int H, int W,
+                      const cgd_flow_params* params, void* stream);
+int cgd_frame_warp_flow(cgd_ctx* ctx, const float* src, const float* flow, const float* flow_back, const float* fallback, float* dst,
+                        float* mask_out, int flow_batch, int B, int C, int H, int W, const cgd_warp_flow* settings, void* stream);
+
 /* ---- windowed sampling (MultiDiffusion, Bar-Tal et al., 2023): the frame is cut into overlapping S x S windows of the model's trained size, the
  *      model runs on all windows as one batch, and the window outputs are averaged into one prediction for the frame.  An adjoint pair, one
  *      launch each whatever B, C and the window count:
